@@ -21,9 +21,17 @@ same for every N, so scaling is "strong".
 torch is used for device memory and that bootstrap only; the numerics are libsgpr_hip.so
 (hand-written HIP) called through its C ABI.
 
-Reported besides `value` (device-resident pipeline, K steps enqueued back to back):
-`calculate_wall`: median wall time of one ActiveCalculator.calculate() on the same frame — numpy
-positions in, numpy results out, synchronised every call — SURVEY.md section 8(d)'s definition.
+A plain run sets up, warms up (resident-frame steps until the step time has settled, then the MD
+run's 200 equilibration and W warm-up steps), times exactly --steps steps of the headline (one batch
+between two fences: `value`, `ms_per_step`) and prints the line.  --dump-outputs DIR also writes
+what the last timed step computed to DIR/<name>.npy (float64; the inputs are seeded, the same in
+every run).
+
+--full adds everything else, measured as before: the batch repeated until MIN_TIMED_MS have been
+timed (`timed`), the resident-frames pipeline (`value_resident_frames`),
+per-kernel times and `roofline`, `md_loop` over --md-steps steps, `calculate_wall`: median wall time of
+one ActiveCalculator.calculate() on the same frame — numpy positions in, numpy results out,
+synchronised every call — SURVEY.md section 8(d)'s definition, its 16384-atom twin and `cpu_baseline`.
 """
 import argparse
 import ctypes as C
@@ -38,7 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-MIN_TIMED_MS = 50.0       # the --steps batch is repeated until this much has been timed; the median batch is reported
+MIN_TIMED_MS = 50.0       # --full: the --steps batch is repeated until this much has been timed; the median batch is reported
 FP64_MFMA_PEAK_TF = 78.6  # BASELINE.md §4 (MI355X FP64 matrix peak)
 
 
@@ -252,6 +260,11 @@ def main():
                          "MD loop runs sharded on it), else RCCL, else host staged; ipc / native (= RCCL all-reduce on the step's "
                          "stream) / torch (torch.distributed all_reduce of the packed buffer, host staged): only that one")
     ap.add_argument("--cpu-sample", type=int, default=0, help="atoms in the CPU-baseline sample (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated batches, resident frames, per-kernel times and roofline, md_loop, "
+                         "calculate() walls, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -409,6 +422,9 @@ def main():
                 stop = bool(t.item())
             if stop:
                 break
+        # ... and on to the start of the frame loop: the timed steps read the same frames in every run
+        while counter[0] % nframes:
+            step()
         _lib.check(lib.sgpr_sync_check(h, sp))
 
     def fence():
@@ -425,9 +441,10 @@ def main():
         return x
 
     def batches_of(first_dt):
-        """A batch = exactly --steps steps between two fences (the contract's timed region).  One batch of 20 steps is
-        under 2 ms: the batch is REPEATED until >= MIN_TIMED_MS of steps have been timed and the MEDIAN batch is reported
-        (min / max beside it).  The count follows from the first batch's max-over-ranks time: the same on every rank."""
+        """A batch = exactly --steps steps between two fences (the contract's timed region; the first batch is the
+        headline).  --full: the batch is REPEATED until >= MIN_TIMED_MS of steps have been timed and the MEDIAN batch is
+        reported beside it (min / max too).  The count follows from the first batch's max-over-ranks time: the same on
+        every rank."""
         return int(min(400, max(1, np.ceil(MIN_TIMED_MS * 1e-3 / max(first_dt, 1e-9)))))
 
     def resident_batch():
@@ -438,107 +455,121 @@ def main():
         fence()
         return max_over_ranks(time.perf_counter() - t0)
 
-    rb0 = C.c_int64(0)
-    _lib.check(lib.sgpr_get_list_rebuilds(h, C.addressof(rb0)))
-    with Watchdog("timed steps", seconds=max(600, int(0.05 * args.steps)), rank=rank):
-        res_dts = [resident_batch()]
-        for _ in range(batches_of(res_dts[0]) - 1):
-            res_dts.append(resident_batch())
-    rb1 = C.c_int64(0)
-    _lib.check(lib.sgpr_get_list_rebuilds(h, C.addressof(rb1)))
-    _lib.check(lib.sgpr_sync_check(h, sp))
-    dt = float(np.median(res_dts))
-    ms_per_step = dt / args.steps * 1e3
-    value = N * args.steps / dt
-    out_host = packed.cpu().numpy()  # the reduced result of the last timed step
+    def dump(arrays):
+        """--dump-outputs: the arrays a caller of the timed path receives after its last step, one float64 .npy each."""
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
 
-    # ---- per-kernel durations: HIP events on the launch stream, same steps run eagerly
-    mdl.profile(True)
-    acc = {}
-    nprof = max(min(args.steps, 50), 30)
-    for _ in range(nprof):
-        step()
-        torch.cuda.synchronize(dev)
-        for k, v in mdl.stage_times().items():
-            acc.setdefault(k, []).append(v)
-    mdl.profile(False)
-    # (medians: one stalled launch in fifty — a rebuild step, a clock change — would otherwise sit in the mean of its stage)
-    stage_ms = {k: float(np.median(v)) for k, v in acc.items() if len(v) >= nprof // 2}
-    # An event-to-event interval holds one launch's marker/dispatch overhead besides the kernel.
-    # Calibration: the same steps without the markers (and without the collective) take t_plain;
-    # the markers therefore cost (sum of intervals - t_plain) / n_stages per stage.
-    torch.cuda.synchronize(dev)
-    tp = time.perf_counter()
-    for _ in range(nprof):
-        step()
-    torch.cuda.synchronize(dev)
-    t_plain_ms = (time.perf_counter() - tp) / nprof * 1e3
-    overhead_ms = max((sum(stage_ms.values()) - t_plain_ms) / max(len(stage_ms), 1), 0.0)
-    stage_ms = {k: max(v - overhead_ms, 0.0) for k, v in stage_ms.items()}
-    dims = mdl.dims
-    # N > 1: every rank's own stage times (a curve can only be read if one sees whose share is the long one) and the
-    # collective alone: the packed buffer all-reduced back to back, hip events on the step's stream
-    per_rank, allreduce_us = None, None
-    if world > 1:
-        if native:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            scratch = packed.clone()
-            nar = 50
-            for _ in range(5):
-                _lib.check(lib.sgpr_comm_allreduce(h, scratch.data_ptr(), scratch.numel(), 0, sp))
-            e0.record(stream)
-            for _ in range(nar):
-                _lib.check(lib.sgpr_comm_allreduce(h, scratch.data_ptr(), scratch.numel(), 0, sp))
-            e1.record(stream)
+    # the headline is the device MD loop where it can run, else the resident-frames pipeline
+    md_headline = args.md_steps > 0 and (world == 1 or backend == "ipc")
+    res_dts, value, ms_per_step, out_host, list_rebuilds = None, None, None, None, None
+    if args.full or not md_headline:
+        rb0 = C.c_int64(0)
+        _lib.check(lib.sgpr_get_list_rebuilds(h, C.addressof(rb0)))
+        with Watchdog("timed steps", seconds=max(600, int(0.05 * args.steps)), rank=rank):
+            res_dts = [resident_batch()]
+            if not md_headline and args.dump_outputs and rank == 0:
+                o = packed.cpu().numpy()   # [F (3N) | covloss (N) | E | virial (9) | ...] of the last timed step
+                dump({"forces": o[:3 * N].reshape(N, 3), "covloss": o[3 * N:4 * N], "energy": o[4 * N:4 * N + 1],
+                      "virial": o[4 * N + 1:4 * N + 10]})
+            if args.full:
+                for _ in range(batches_of(res_dts[0]) - 1):
+                    res_dts.append(resident_batch())
+        rb1 = C.c_int64(0)
+        _lib.check(lib.sgpr_get_list_rebuilds(h, C.addressof(rb1)))
+        _lib.check(lib.sgpr_sync_check(h, sp))
+        list_rebuilds = int(rb1.value - rb0.value)
+        dt = float(np.median(res_dts))
+        ms_per_step = dt / args.steps * 1e3
+        value = N * args.steps / dt
+        out_host = packed.cpu().numpy()  # the reduced result of the last timed step
+
+    stage_ms, overhead_ms, nprof, per_rank, allreduce_us = {}, 0.0, 0, None, None
+    host_rate, calc_wall, calc_wall_big = None, None, None
+    if args.full:
+        # ---- per-kernel durations: HIP events on the launch stream, same steps run eagerly
+        mdl.profile(True)
+        acc = {}
+        nprof = max(min(args.steps, 50), 30)
+        for _ in range(nprof):
+            step()
             torch.cuda.synchronize(dev)
-            allreduce_us = e0.elapsed_time(e1) / nar * 1e3
-        mine = {"rank": rank, "local_atoms": (N - rank + world - 1) // world, "step_us": round(t_plain_ms * 1e3, 2),
-                "allreduce_us": None if allreduce_us is None else round(allreduce_us, 2),
-                **{k + "_us": round(v * 1e3, 2) for k, v in stage_ms.items()}}
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
-    # PCIe-inclusive rate of the host-array entry point (never `value`): numpy in, numpy out
-    host_rate = None
-    calc_wall = None
-    calc_wall_big = None
-    if world == 1:
-        mdl.predict(numbers, pos, cell, pbc, beta=True)
-        th = time.perf_counter()
-        nh = 20
-        for _ in range(nh):
+            for k, v in mdl.stage_times().items():
+                acc.setdefault(k, []).append(v)
+        mdl.profile(False)
+        # (medians: one stalled launch in fifty — a rebuild step, a clock change — would otherwise sit in the mean of its stage)
+        stage_ms = {k: float(np.median(v)) for k, v in acc.items() if len(v) >= nprof // 2}
+        # An event-to-event interval holds one launch's marker/dispatch overhead besides the kernel.
+        # Calibration: the same steps without the markers (and without the collective) take t_plain;
+        # the markers therefore cost (sum of intervals - t_plain) / n_stages per stage.
+        torch.cuda.synchronize(dev)
+        tp = time.perf_counter()
+        for _ in range(nprof):
+            step()
+        torch.cuda.synchronize(dev)
+        t_plain_ms = (time.perf_counter() - tp) / nprof * 1e3
+        overhead_ms = max((sum(stage_ms.values()) - t_plain_ms) / max(len(stage_ms), 1), 0.0)
+        stage_ms = {k: max(v - overhead_ms, 0.0) for k, v in stage_ms.items()}
+        # N > 1: every rank's own stage times (a curve can only be read if one sees whose share is the long one) and the
+        # collective alone: the packed buffer all-reduced back to back, hip events on the step's stream
+        if world > 1:
+            if native:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                scratch = packed.clone()
+                nar = 50
+                for _ in range(5):
+                    _lib.check(lib.sgpr_comm_allreduce(h, scratch.data_ptr(), scratch.numel(), 0, sp))
+                e0.record(stream)
+                for _ in range(nar):
+                    _lib.check(lib.sgpr_comm_allreduce(h, scratch.data_ptr(), scratch.numel(), 0, sp))
+                e1.record(stream)
+                torch.cuda.synchronize(dev)
+                allreduce_us = e0.elapsed_time(e1) / nar * 1e3
+            mine = {"rank": rank, "local_atoms": (N - rank + world - 1) // world, "step_us": round(t_plain_ms * 1e3, 2),
+                    "allreduce_us": None if allreduce_us is None else round(allreduce_us, 2),
+                    **{k + "_us": round(v * 1e3, 2) for k, v in stage_ms.items()}}
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+        # PCIe-inclusive rate of the host-array entry point (never `value`): numpy in, numpy out
+        if world == 1:
             mdl.predict(numbers, pos, cell, pbc, beta=True)
-        host_rate = N * nh / (time.perf_counter() - th)
-        # wall time of one calculate() (NL + descriptors + K_nm + E/F/stress + covloss) through
-        # the drop-in surface, median of >= 50 calls after 5 warm-ups; the atoms move every call by the same
-        # random-walk step as above, so nothing is served from ASE's result cache and the neighbour candidates
-        # are rebuilt at the MD rate
-        from autoforce_amd.ase_shim import Atoms
-        from autoforce_amd.calculator import ActiveCalculator
-        calc = ActiveCalculator(covariance=mdl, logfile=None)
-        atoms = Atoms(numbers, pos.copy(), cell, pbc)
-        atoms.calc = calc
-        rng = np.random.default_rng(5)
-        walls = []
-        for it in range(55):
-            atoms.positions = atoms.positions + (args.walk_sigma or 1e-3) * rng.normal(size=pos.shape)
-            tc = time.perf_counter()
-            atoms.get_forces()
-            walls.append(time.perf_counter() - tc)
-        w = float(np.median(walls[5:]))
-        calc_wall = {"median_ms": w * 1e3, "atom_steps_per_s": N / w, "calls": len(walls) - 5,
-                     "device_step_ms": t_plain_ms, "wall_over_device": w * 1e3 / t_plain_ms,
-                     "what": "ActiveCalculator.calculate() wall, numpy in / numpy out, one synchronised call per step"}
-        if not args.no_big_wall:
-            calc_wall_big = calculate_wall_big(local_rank, args.walk_sigma or 1e-3)
+            th = time.perf_counter()
+            nh = 20
+            for _ in range(nh):
+                mdl.predict(numbers, pos, cell, pbc, beta=True)
+            host_rate = N * nh / (time.perf_counter() - th)
+            # SURVEY 8(d): wall time of one calculate() (NL + descriptors + K_nm + E/F/stress + covloss) through
+            # the drop-in surface, median of >= 50 calls after 5 warm-ups; the atoms move every call by the same
+            # random-walk step as above, so nothing is served from ASE's result cache and the neighbour candidates
+            # are rebuilt at the MD rate
+            from autoforce_amd.ase_shim import Atoms
+            from autoforce_amd.calculator import ActiveCalculator
+            calc = ActiveCalculator(covariance=mdl, logfile=None)
+            atoms = Atoms(numbers, pos.copy(), cell, pbc)
+            atoms.calc = calc
+            rng = np.random.default_rng(5)
+            walls = []
+            for it in range(55):
+                atoms.positions = atoms.positions + (args.walk_sigma or 1e-3) * rng.normal(size=pos.shape)
+                tc = time.perf_counter()
+                atoms.get_forces()
+                walls.append(time.perf_counter() - tc)
+            w = float(np.median(walls[5:]))
+            calc_wall = {"median_ms": w * 1e3, "atom_steps_per_s": N / w, "calls": len(walls) - 5,
+                         "device_step_ms": t_plain_ms, "wall_over_device": w * 1e3 / t_plain_ms,
+                         "what": "ActiveCalculator.calculate() wall, numpy in / numpy out, one synchronised call per step"}
+            if not args.no_big_wall:
+                calc_wall_big = calculate_wall_big(local_rank, args.walk_sigma or 1e-3)
 
     # ---- an MD LOOP: step k + 1 starts from the forces of step k.  Langevin NVT (600 K, 1 fs, friction as cl/md.py:31)
     # with positions and velocities in device memory (sgpr_md_*): the wall time of K dependent steps, noise upload
     # included.  (The bench model's weights are random: scaled by 0.01 for this loop so that the forces are of the size a
     # fitted model gives — the work per step does not depend on their values.)
-    md_loop, md_head = None, None
+    md_loop, md_head, md_batches = None, None, None
     # (several ranks: the loop runs sharded over the library's own exchange — every rank integrates all atoms from the
     # summed forces —; with RCCL or the host-staged collective only the resident-frames figure exists)
-    if args.md_steps > 0 and (world == 1 or backend == "ipc"):
+    if md_headline:
         from autoforce_amd.ase_shim import kB
         from autoforce_amd.workloads import FS, MASS, fit_to_teacher
         snap = mdl.snapshot_weights()
@@ -568,123 +599,62 @@ def main():
                 resizes += code == 2   # a neighbour capacity outgrown on the way: the next call re-sizes and goes on
             return time.perf_counter() - tm, np.concatenate(rows), resizes
 
-        # THE HEADLINE: exactly --steps dependent MD steps between two fences, max over the ranks — one BATCH; batches are
-        # repeated (each continues the run where the one before stopped) until >= MIN_TIMED_MS have been timed, and the
-        # median batch is what `value` / `ms_per_step` quote
+        # one BATCH: exactly --steps dependent MD steps between two fences, max over the ranks (each batch continues the
+        # run where the one before stopped)
         def md_batch():
             fence()
             th = time.perf_counter()
             _, sc_b, rz_b = md_timed(None, args.steps)
             fence()
-            return max_over_ranks(time.perf_counter() - th), len(sc_b) == args.steps and rz_b == 0
+            return max_over_ranks(time.perf_counter() - th), sc_b, rz_b
 
-        md_dts = []
-        d0, ok0 = md_batch()
-        for _ in range(batches_of(d0) - 1 if ok0 else 0):
-            md_dts.append(md_batch())
-        md_dts = [d0] * bool(ok0) + [d for d, ok in md_dts if ok]   # (a batch that outgrew a capacity is not a sample)
-        if md_dts:
-            dt_md = float(np.median(md_dts))
-            md_head = {"ms_per_step": dt_md / args.steps * 1e3, "value": N * args.steps / dt_md, "batches": len(md_dts),
-                       "ms_per_step_min": min(md_dts) / args.steps * 1e3, "ms_per_step_max": max(md_dts) / args.steps * 1e3,
-                       "ms_per_step_first_batch": d0 / args.steps * 1e3}
-        rbm0 = mdl.list_rebuilds()
-        tmd, sc, resizes = md_timed(None)                       # deviates drawn on the device
-        rbm1 = mdl.list_rebuilds()
-        if world == 1:
-            t_rows, sc_rows, _ = md_timed(mrng.normal(size=(K, N, 3)))   # numpy's deviates, uploaded (the host loop's stream)
-        else:
-            t_rows, sc_rows = tmd, sc
-        T_md = sc[:, 12] / (3 * N * kB)
-        md_loop = {"steps": int(len(sc)), "capacity_resizes": int(resizes), "ms_per_step": tmd / max(len(sc), 1) * 1e3,
-                   "atom_steps_per_s": N * len(sc) / tmd, "list_rebuilds": int(rbm1 - rbm0),
-                   "ms_per_step_with_uploaded_deviates": t_rows / max(len(sc_rows), 1) * 1e3,
-                   "temperature_K_mean": float(T_md.mean()) if len(sc) else None,
-                   "energy_first_last": [float(sc[0, 0]), float(sc[-1, 0])] if len(sc) else None,
-                   "largest_covloss_first_last": [float(sc[0, 11]), float(sc[-1, 11])] if len(sc) else None,
-                   "what": "sgpr_md_run: BAOAB Langevin 600 K, 1 fs, friction 1e-3 (cl/md.py:31), state resident in HBM, "
-                           "integrator + binning of the next step inside the step's last kernel (5 launches per step), the "
-                           "Langevin deviates drawn on the device (counter-based); wall time of K dependent steps, the host reads "
-                           "16 scalars per step; weights fitted to workloads.PairTeacher on the start frame (a model whose "
-                           "forces hold the lattice together; the work per step does not depend on the weights)"}
+        # THE HEADLINE: the first batch — `value` / `ms_per_step`
+        d0, sc0, _ = md_batch()
+        if len(sc0) != args.steps:
+            raise SystemExit(f"the timed MD batch stopped after {len(sc0)} of {args.steps} steps (neighbour capacities)")
+        if args.dump_outputs and rank == 0:
+            st = mdl.md_state(which=-1, results=True)   # (which=0 is the next configuration, not evaluated yet)
+            dump({"positions": st["positions"], "velocities": st["velocities"], "forces": st["forces"],
+                  "covloss": st["beta"], "energy": [st["energy"]], "stress": st["stress"], "md_scalars": sc0[-1]})
+        md_head = {"ms_per_step": d0 / args.steps * 1e3, "value": N * args.steps / d0}
+        if args.full:
+            # the batch repeated until >= MIN_TIMED_MS have been timed: the spread of the headline
+            md_dts = [d0]
+            for _ in range(batches_of(d0) - 1):
+                d, sc_b, rz_b = md_batch()
+                if len(sc_b) == args.steps and rz_b == 0:   # (a batch that outgrew a capacity is not a sample)
+                    md_dts.append(d)
+            md_batches = {"batches": len(md_dts), "ms_per_step_median": float(np.median(md_dts)) / args.steps * 1e3,
+                          "ms_per_step_min": min(md_dts) / args.steps * 1e3, "ms_per_step_max": max(md_dts) / args.steps * 1e3,
+                          "ms_per_step_first_batch": d0 / args.steps * 1e3}
+            rbm0 = mdl.list_rebuilds()
+            tmd, sc, resizes = md_timed(None)                       # deviates drawn on the device
+            rbm1 = mdl.list_rebuilds()
+            if world == 1:
+                t_rows, sc_rows, _ = md_timed(mrng.normal(size=(K, N, 3)))   # numpy's deviates, uploaded (the host loop's stream)
+            else:
+                t_rows, sc_rows = tmd, sc
+            T_md = sc[:, 12] / (3 * N * kB)
+            md_loop = {"steps": int(len(sc)), "capacity_resizes": int(resizes), "ms_per_step": tmd / max(len(sc), 1) * 1e3,
+                       "atom_steps_per_s": N * len(sc) / tmd, "list_rebuilds": int(rbm1 - rbm0),
+                       "ms_per_step_with_uploaded_deviates": t_rows / max(len(sc_rows), 1) * 1e3,
+                       "temperature_K_mean": float(T_md.mean()) if len(sc) else None,
+                       "energy_first_last": [float(sc[0, 0]), float(sc[-1, 0])] if len(sc) else None,
+                       "largest_covloss_first_last": [float(sc[0, 11]), float(sc[-1, 11])] if len(sc) else None,
+                       "what": "sgpr_md_run: BAOAB Langevin 600 K, 1 fs, friction 1e-3 (cl/md.py:31), state resident in HBM, "
+                               "integrator + binning of the next step inside the step's last kernel (5 launches per step), the "
+                               "Langevin deviates drawn on the device (counter-based); wall time of K dependent steps, the host reads "
+                               "16 scalars per step; weights fitted to workloads.PairTeacher on the start frame (a model whose "
+                               "forces hold the lattice together; the work per step does not depend on the weights)"}
         mdl.set_weights(snap["mu"], choli=choli0, vscale=snap["vscale"] or None)
 
     result = None
     if rank == 0:
+        dims = mdl.dims
         cnt = (N - rank + world - 1) // world
         ptr, _, _ = mdl.neighbors(N)
         nn_mean = float(ptr[-1]) / max(cnt, 1)
         Dc = dims["Dc"]
-        # algorithmic bytes of THIS formulation: packed rows (Dc) and only this rank's atoms
-        cs = dims["S"] * 64
-        ab = algorithmic_bytes(cnt, nn_mean, Dc, m, cs)
-        rev_key = "descriptor_rev_covloss" if "descriptor_rev_covloss" in stage_ms else "descriptor_rev"
-        w_key = "gemm_w" if "gemm_w" in stage_ms else "gemm_w_covloss"
-        dom = max((k for k in stage_ms if k in ab), key=lambda k: stage_ms[k])
-        dom_s = stage_ms[dom] * 1e-3
-        # HBM traffic of the dominant kernel: PMC counters cannot be read inside this run (rocprofv3 --pmc
-        # is a separate pass); the committed summary of the builder's own pass over this command is quoted
-        # with its source, or null
-        traffic, traffic_source = None, None
-        sha = csrc_sha()
-        tpath = latest_profile(f"r*_pmc_traffic_lips{N}_m{m}.json")
-        pmc = None
-        if world == 1 and tpath:
-            tj = json.load(open(tpath))
-            if tj.get("csrc_sha") == sha:
-                pmc = tj
-                traffic = tj["kernels"].get(dom, {}).get("fetch_x2_plus_write")
-                traffic_source = f"profiles/{os.path.basename(tpath)} ({tj.get('source', 'builder run')}; same kernel sources: csrc sha {sha})"
-            else:
-                traffic_source = (f"null: profiles/{os.path.basename(tpath)} was collected on other kernel sources "
-                                  f"(csrc sha {tj.get('csrc_sha')} then, {sha} now)")
-        af = algorithmic_flops(numbers, [x.number for x in mdl.X], dims["Dpad"], world)
-        if dom in af:  # a GEMM leads: price it against the dense fp64 MFMA peak
-            Dd = dims["D"] * dims["S"] ** 2
-            dense = {"gemm_knm": 2.0 * cnt * m * Dd, "gemm_w": 2.0 * cnt * m * Dd, "gemm_w_covloss": 2.0 * cnt * m * Dd + float(m) * m * cnt}
-            head = {"bound": "mfma", "achieved": af[dom] / dom_s / 1e12, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": af[dom] / dom_s / 1e12 / FP64_MFMA_PEAK_TF, "algorithmic_flops": af[dom],
-                    "dense_equiv_flops": dense.get(dom),
-                    "flops_note": "algorithmic_flops counts what the block-diagonal formulation needs: K_nm, W and L^-1 are zero "
-                                  "outside a species block (atoms and inducing points are species-sorted) and rows are packed "
-                                  f"{Dd} -> {dims['Dpad']} doubles (p[u,v,l] is symmetric in u,v); dense_equiv_flops is SURVEY 8(d)'s "
-                                  "formula for the same product on dense unpacked operands (2NmD + m^2 N): pricing the launch with "
-                                  "it would exceed the fp64 MFMA peak, so frac uses the block count"}
-        else:
-            head = {"bound": "hbm", "achieved": ab[dom] / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ab[dom] / dom_s / 1e9 / HBM_PEAK_GBS}
-        roof = {
-            "kernel": dom,
-            **head,
-            "traffic": traffic,
-            "traffic_source": traffic_source,
-            "algorithmic_bytes": ab[dom],
-            "avg_launch_us": stage_ms[dom] * 1e3,
-            "timing": f"hip events on the launch stream, {nprof} eager steps after the timed region, minus the "
-                      f"per-stage marker overhead ({overhead_ms * 1e3:.2f} us = (sum of intervals - marker-free step time) / stages)",
-            # scalar keys (a parser that drops nested objects keeps these): per-kernel time, the descriptor kernels
-            # against the HBM roofline with their algorithmic bytes, the GEMMs against the fp64 MFMA peak
-            **{k + "_us": round(v * 1e3, 2) for k, v in stage_ms.items()},
-            "desc_fwd_GBs": round(ab["list_forward"] / (stage_ms["list_forward"] * 1e-3) / 1e9, 1) if stage_ms.get("list_forward") else None,
-            "desc_rev_GBs": round(ab[rev_key] / (stage_ms[rev_key] * 1e-3) / 1e9, 1) if stage_ms.get(rev_key) else None,
-            "desc_hbm_frac": round((ab["list_forward"] + ab[rev_key]) /
-                                   ((stage_ms.get("list_forward", 0) + stage_ms.get(rev_key, 0)) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-            if stage_ms.get("list_forward") and stage_ms.get(rev_key) else None,
-            "desc_valu_frac": (pmc or {}).get("desc_valu_frac"),
-            "desc_valu_note": (pmc or {}).get("desc_valu_note"),
-            "knm_TFs": round(af["gemm_knm"] / (stage_ms["gemm_knm"] * 1e-3) / 1e12, 2) if stage_ms.get("gemm_knm") else None,
-            "wcov_TFs": round(af[w_key] / (stage_ms[w_key] * 1e-3) / 1e12, 2) if stage_ms.get(w_key) else None,
-            "gemm_phase_us": round(sum(stage_ms.get(k, 0.0) for k in ("gemm_knm", "gemm_w", "gemm_w_covloss")) * 1e3, 2),
-            "knm_frac": round(af["gemm_knm"] / (stage_ms["gemm_knm"] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF, 4) if stage_ms.get("gemm_knm") else None,
-            "wcov_frac": round(af[w_key] / (stage_ms[w_key] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF, 4) if stage_ms.get(w_key) else None,
-            "stage_us": {k: round(v * 1e3, 2) for k, v in stage_ms.items()},
-            "gemm_TFLOPs": {k: round(af[k] / (stage_ms[k] * 1e-3) / 1e12, 2) for k in af if stage_ms.get(k)},
-            "hbm_GBs": {k: round(ab[k] / (stage_ms[k] * 1e-3) / 1e9, 1) for k in ab if stage_ms.get(k)},
-            "step_bytes_this_formulation": sum(v for k, v in ab.items() if k in stage_ms),
-            "step_bytes_survey_formula": survey_step_bytes(cnt, nn_mean, dims["D"] * dims["S"] ** 2, m),
-            "step_GBs_survey_formula": survey_step_bytes(cnt, nn_mean, dims["D"] * dims["S"] ** 2, m) / (ms_per_step * 1e-3) / 1e9,
-            "pass_GBs_packed": sum(v for k, v in ab.items() if k in stage_ms) / (sum(stage_ms[k] for k in ab if k in stage_ms) * 1e-3) / 1e9,
-        }
         result = {
             "metric": "MD-step atoms*steps/sec (SGPR predict: NL + descriptors + K_nm + E/F/stress + covloss); `value`: a Langevin "
                       "MD loop on the device, every step from the forces of the one before (sgpr_md_run; --steps dependent steps "
@@ -692,21 +662,17 @@ def main():
                       "back to back; `md_loop`: the same MD loop over --md-steps steps; `value_calculate_wall`: SURVEY 8(d)'s "
                       "t_step = wall of one synchronised ActiveCalculator.calculate()"
                       + ("" if md_head else "  [no device MD loop in this configuration: `value` is the resident-frames figure]"),
-            "value": md_head["value"] if md_head else value,
+            "value": md_head["value"] if md_head else N * args.steps / res_dts[0],
             "unit": "atom*steps/s",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": md_head["ms_per_step"] if md_head else ms_per_step,
+            "ms_per_step": md_head["ms_per_step"] if md_head else res_dts[0] / args.steps * 1e3,
             "value_is": "md_loop (dependent steps)" if md_head else "resident frames",
-            "timed": {"batch_steps": args.steps, "min_timed_ms": MIN_TIMED_MS,
-                      "what": "a batch = exactly --steps steps between two fences (barrier + synchronize), max over ranks; repeated "
-                              "until min_timed_ms have been timed; value / ms_per_step = the MEDIAN batch",
-                      "md_loop": md_head, "resident_frames": {"batches": len(res_dts), "ms_per_step_min": min(res_dts) / args.steps * 1e3,
-                                                              "ms_per_step_max": max(res_dts) / args.steps * 1e3,
-                                                              "ms_per_step_first_batch": res_dts[0] / args.steps * 1e3}},
-            "value_resident_frames": value,
-            "ms_per_step_resident_frames": ms_per_step,
+            "timed": {"batch_steps": args.steps,
+                      "what": "a batch = exactly --steps steps between two fences (barrier + synchronize), max over ranks; value / "
+                              "ms_per_step = the first batch" + ("; --full repeats it until min_timed_ms have been timed" if args.full
+                                                                 else "")},
             "collective": backend if world > 1 else None,
             "higher_is_better": True,
             "scaling": "strong",
@@ -716,44 +682,125 @@ def main():
             "config": {
                 "workload": f"LiPS {N} atoms (3 species), {m} inducing points, lmax=nmax=3, eta=4, rc=6.0",
                 "atoms": N, "inducing": m, "mean_neighbors": round(nn_mean, 2), "max_neighbors": dims["nn_max"],
-                "packed_row": Dc, "graph": bool(args.graph), "launches_per_step": (5 if args.fuse_next else 6) if world == 1 else len(stage_ms),
+                "packed_row": Dc, "graph": bool(args.graph),
+                "launches_per_step": (5 if args.fuse_next else 6) if world == 1 else (len(stage_ms) or None),
                 "input": (f"closed Gaussian random walk, sigma {args.walk_sigma} A per component per step, {nframes} frames "
                           f"resident in HBM" if nframes > 1 else "static frame"),
                 "neighbor_skin_A": args.skin,
                 "md_state": ("the timed MD steps continue a run of 200 equilibration steps (the start lattice relaxing under the "
                              "fitted model: part of building the state) + the W warm-up steps") if md_head else None,
-                "list_rebuilds_in_timed_steps": int(rb1.value - rb0.value),
+                "list_rebuilds_in_timed_steps": list_rebuilds,
                 "host_array_path_atom_steps_per_s": host_rate,
                 "parallelism": f"atoms sharded x{world}, " + (
                     "single rank: no collective" if world == 1 else
                     f"the library's own exchange per step: all-gather of {3 * N + 4 * ((N + world - 1) // world) + 11} words of partial sums into hipIpc-mapped "
                     "peer buffers + local sum in rank order" if backend == "ipc" else
-                    f"one RCCL all-reduce of {len(out_host)} doubles per step, issued by libsgpr_hip on the step stream"
-                    if backend == "rccl" else f"torch.distributed all-reduce of {len(out_host)} doubles, host staged"),
+                    f"one RCCL all-reduce of {packed.numel()} doubles per step, issued by libsgpr_hip on the step stream"
+                    if backend == "rccl" else f"torch.distributed all-reduce of {packed.numel()} doubles, host staged"),
             },
-            "roofline": roof,
-            "per_rank": per_rank,
-            "allreduce_us": allreduce_us,
-            "value_calculate_wall": None if calc_wall is None else calc_wall["atom_steps_per_s"],
-            "value_md_loop": None if md_loop is None else md_loop["atom_steps_per_s"],
-            "md_loop": md_loop,
-            "warmup_batches_ms": [round(1e3 * b, 4) for b in warm_batches],
-            "calculate_wall": calc_wall,
-            "calculate_wall_ms": None if calc_wall is None else calc_wall["median_ms"],
-            "roofline_16384": None if calc_wall_big is None else calc_wall_big.pop("roofline", None),
-            "calculate_wall_16384": calc_wall_big,
-            "energy": float(out_host[4 * N]),
-            "max_force": float(np.abs(out_host[:3 * N]).max()),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            sample = args.cpu_sample or N
-            v, cdt, reps, cores = cpu_baseline(numbers, pos, cell, pbc, mdl, mdl.mu, sample)
-            result["cpu_baseline"] = {
-                "value": v, "unit": "atom*steps/s", "cores": cores, "kind": "port",
-                "sample": f"{reps} passes over {sample} of {N} atoms of the same frame (linked-cell neighbour list + "
-                          f"descriptors + K_nm + reverse pass + covloss), {cdt:.1f} s, "
-                          f"oracle/sgpr_oracle.c with OpenMP on {cores} threads",
+        if args.full:
+            # algorithmic bytes of THIS formulation: packed rows (Dc) and only this rank's atoms
+            cs = dims["S"] * 64
+            ab = algorithmic_bytes(cnt, nn_mean, Dc, m, cs)
+            rev_key = "descriptor_rev_covloss" if "descriptor_rev_covloss" in stage_ms else "descriptor_rev"
+            w_key = "gemm_w" if "gemm_w" in stage_ms else "gemm_w_covloss"
+            dom = max((k for k in stage_ms if k in ab), key=lambda k: stage_ms[k])
+            dom_s = stage_ms[dom] * 1e-3
+            # HBM traffic of the dominant kernel: PMC counters cannot be read inside this run (rocprofv3 --pmc
+            # is a separate pass); the committed summary of the builder's own pass over this command is quoted
+            # with its source, or null
+            traffic, traffic_source = None, None
+            sha = csrc_sha()
+            tpath = latest_profile(f"r*_pmc_traffic_lips{N}_m{m}.json")
+            pmc = None
+            if world == 1 and tpath:
+                tj = json.load(open(tpath))
+                if tj.get("csrc_sha") == sha:
+                    pmc = tj
+                    traffic = tj["kernels"].get(dom, {}).get("fetch_x2_plus_write")
+                    traffic_source = f"profiles/{os.path.basename(tpath)} ({tj.get('source', 'builder run')}; same kernel sources: csrc sha {sha})"
+                else:
+                    traffic_source = (f"null: profiles/{os.path.basename(tpath)} was collected on other kernel sources "
+                                      f"(csrc sha {tj.get('csrc_sha')} then, {sha} now)")
+            af = algorithmic_flops(numbers, [x.number for x in mdl.X], dims["Dpad"], world)
+            if dom in af:  # a GEMM leads: price it against the dense fp64 MFMA peak
+                Dd = dims["D"] * dims["S"] ** 2
+                dense = {"gemm_knm": 2.0 * cnt * m * Dd, "gemm_w": 2.0 * cnt * m * Dd, "gemm_w_covloss": 2.0 * cnt * m * Dd + float(m) * m * cnt}
+                head = {"bound": "mfma", "achieved": af[dom] / dom_s / 1e12, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": af[dom] / dom_s / 1e12 / FP64_MFMA_PEAK_TF, "algorithmic_flops": af[dom],
+                        "dense_equiv_flops": dense.get(dom),
+                        "flops_note": "algorithmic_flops counts what the block-diagonal formulation needs: K_nm, W and L^-1 are zero "
+                                      "outside a species block (atoms and inducing points are species-sorted) and rows are packed "
+                                      f"{Dd} -> {dims['Dpad']} doubles (p[u,v,l] is symmetric in u,v); dense_equiv_flops is SURVEY 8(d)'s "
+                                      "formula for the same product on dense unpacked operands (2NmD + m^2 N): pricing the launch with "
+                                      "it would exceed the fp64 MFMA peak, so frac uses the block count"}
+            else:
+                head = {"bound": "hbm", "achieved": ab[dom] / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ab[dom] / dom_s / 1e9 / HBM_PEAK_GBS}
+            roof = {
+                "kernel": dom,
+                **head,
+                "traffic": traffic,
+                "traffic_source": traffic_source,
+                "algorithmic_bytes": ab[dom],
+                "avg_launch_us": stage_ms[dom] * 1e3,
+                "timing": f"hip events on the launch stream, {nprof} eager steps after the timed region, minus the "
+                          f"per-stage marker overhead ({overhead_ms * 1e3:.2f} us = (sum of intervals - marker-free step time) / stages)",
+                # scalar keys (a parser that drops nested objects keeps these): per-kernel time, the descriptor kernels
+                # against the HBM roofline with their algorithmic bytes, the GEMMs against the fp64 MFMA peak
+                **{k + "_us": round(v * 1e3, 2) for k, v in stage_ms.items()},
+                "desc_fwd_GBs": round(ab["list_forward"] / (stage_ms["list_forward"] * 1e-3) / 1e9, 1) if stage_ms.get("list_forward") else None,
+                "desc_rev_GBs": round(ab[rev_key] / (stage_ms[rev_key] * 1e-3) / 1e9, 1) if stage_ms.get(rev_key) else None,
+                "desc_hbm_frac": round((ab["list_forward"] + ab[rev_key]) /
+                                       ((stage_ms.get("list_forward", 0) + stage_ms.get(rev_key, 0)) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                if stage_ms.get("list_forward") and stage_ms.get(rev_key) else None,
+                "desc_valu_frac": (pmc or {}).get("desc_valu_frac"),
+                "desc_valu_note": (pmc or {}).get("desc_valu_note"),
+                "knm_TFs": round(af["gemm_knm"] / (stage_ms["gemm_knm"] * 1e-3) / 1e12, 2) if stage_ms.get("gemm_knm") else None,
+                "wcov_TFs": round(af[w_key] / (stage_ms[w_key] * 1e-3) / 1e12, 2) if stage_ms.get(w_key) else None,
+                "gemm_phase_us": round(sum(stage_ms.get(k, 0.0) for k in ("gemm_knm", "gemm_w", "gemm_w_covloss")) * 1e3, 2),
+                "knm_frac": round(af["gemm_knm"] / (stage_ms["gemm_knm"] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF, 4) if stage_ms.get("gemm_knm") else None,
+                "wcov_frac": round(af[w_key] / (stage_ms[w_key] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF, 4) if stage_ms.get(w_key) else None,
+                "stage_us": {k: round(v * 1e3, 2) for k, v in stage_ms.items()},
+                "gemm_TFLOPs": {k: round(af[k] / (stage_ms[k] * 1e-3) / 1e12, 2) for k in af if stage_ms.get(k)},
+                "hbm_GBs": {k: round(ab[k] / (stage_ms[k] * 1e-3) / 1e9, 1) for k in ab if stage_ms.get(k)},
+                "step_bytes_this_formulation": sum(v for k, v in ab.items() if k in stage_ms),
+                "step_bytes_survey_formula": survey_step_bytes(cnt, nn_mean, dims["D"] * dims["S"] ** 2, m),
+                "step_GBs_survey_formula": survey_step_bytes(cnt, nn_mean, dims["D"] * dims["S"] ** 2, m) / (ms_per_step * 1e-3) / 1e9,
+                "pass_GBs_packed": sum(v for k, v in ab.items() if k in stage_ms) / (sum(stage_ms[k] for k in ab if k in stage_ms) * 1e-3) / 1e9,
             }
+            result["timed"].update({
+                "min_timed_ms": MIN_TIMED_MS, "md_loop": md_batches,
+                "resident_frames": {"batches": len(res_dts), "ms_per_step_min": min(res_dts) / args.steps * 1e3,
+                                    "ms_per_step_max": max(res_dts) / args.steps * 1e3,
+                                    "ms_per_step_first_batch": res_dts[0] / args.steps * 1e3}})
+            result.update({
+                "value_resident_frames": value,
+                "ms_per_step_resident_frames": ms_per_step,
+                "roofline": roof,
+                "per_rank": per_rank,
+                "allreduce_us": allreduce_us,
+                "value_calculate_wall": None if calc_wall is None else calc_wall["atom_steps_per_s"],
+                "value_md_loop": None if md_loop is None else md_loop["atom_steps_per_s"],
+                "md_loop": md_loop,
+                "warmup_batches_ms": [round(1e3 * b, 4) for b in warm_batches],
+                "calculate_wall": calc_wall,
+                "calculate_wall_ms": None if calc_wall is None else calc_wall["median_ms"],
+                "roofline_16384": None if calc_wall_big is None else calc_wall_big.pop("roofline", None),
+                "calculate_wall_16384": calc_wall_big,
+                "energy": float(out_host[4 * N]),
+                "max_force": float(np.abs(out_host[:3 * N]).max()),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                sample = args.cpu_sample or N
+                v, cdt, reps, cores = cpu_baseline(numbers, pos, cell, pbc, mdl, mdl.mu, sample)
+                result["cpu_baseline"] = {
+                    "value": v, "unit": "atom*steps/s", "cores": cores, "kind": "port",
+                    "sample": f"{reps} passes over {sample} of {N} atoms of the same frame (linked-cell neighbour list + "
+                              f"descriptors + K_nm + reverse pass + covloss), {cdt:.1f} s, "
+                              f"oracle/sgpr_oracle.c with OpenMP on {cores} threads",
+                }
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

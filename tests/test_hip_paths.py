@@ -379,15 +379,15 @@ def test_fused_gemm_launch_equals_the_three_launches(side, m, monkeypatch):
 
 
 def test_bench_line_keeps_its_contract():
-    """`python bench.py` as the driver runs it (fewer steps, a small CPU sample): ONE JSON line on stdout with the metric
-    BASELINE.json names, the whole-job value, and the `roofline` / `cpu_baseline` objects with every field the contract
-    lists; `frac` = achieved / peak, the value consistent with ms_per_step."""
+    """`python bench.py --full` (fewer steps, a small CPU sample): ONE JSON line on stdout with the metric BASELINE.json
+    names, the whole-job value, and the `roofline` / `cpu_baseline` objects with every field the contract lists; `frac` =
+    achieved / peak, the value consistent with ms_per_step."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--md-steps", "60", "--no-big-wall", "--cpu-sample", "256"], capture_output=True, text=True,
+                          "--md-steps", "60", "--no-big-wall", "--cpu-sample", "256", "--full"], capture_output=True, text=True,
                          timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -417,7 +417,8 @@ def test_bench_line_keeps_its_contract():
     assert d["value_is"].startswith("md_loop") and d["value_resident_frames"] > 0 and d["ms_per_step_resident_frames"] > 0
     assert abs(d["value_resident_frames"] - atoms / (d["ms_per_step_resident_frames"] * 1e-3)) <= 1e-6 * d["value_resident_frames"]
     assert d["value"] <= 1.05 * d["value_resident_frames"]
-    # the timed region: --steps is the BATCH, repeated until >= 50 ms have been timed; the median batch is the headline
+    # the timed region: --steps is the BATCH and the first batch is the headline; --full repeats it until >= 50 ms have
+    # been timed
     t = d["timed"]
     assert t["batch_steps"] == 20 and t["min_timed_ms"] >= 50.0
     for leg, ms in ((t["md_loop"], d["ms_per_step"]), (t["resident_frames"], d["ms_per_step_resident_frames"])):
@@ -426,3 +427,37 @@ def test_bench_line_keeps_its_contract():
     # the flop count behind frac is the block-diagonal one; the dense formula of SURVEY 8(d) is quoted beside it
     if r["bound"] == "mfma":
         assert r["dense_equiv_flops"] > r["algorithmic_flops"] > 0
+
+
+def test_plain_bench_line_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py` without --full, as it is run for every change: ONE JSON line with the headline fields only (none of
+    what --full adds), exactly --steps timed steps behind `ms_per_step`, and with --dump-outputs the arrays of the last timed
+    MD step as float64 .npy files: two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in range(2):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "4",
+                              "--dump-outputs", str(tmp_path / str(run))], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["metric"].startswith("MD-step atoms*steps/sec") and d["unit"] == "atom*steps/s" and d["dtype"] == "f64"
+        assert d["steps"] == 30 and d["warmup"] == 4 and d["timed"]["batch_steps"] == 30 and d["value_is"].startswith("md_loop")
+        assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        for key in ("roofline", "cpu_baseline", "md_loop", "calculate_wall", "value_resident_frames"):
+            assert key not in d, key
+        arrays = {f[:-4]: np.load(tmp_path / str(run) / f) for f in sorted(os.listdir(tmp_path / str(run)))}
+        assert set(arrays) == {"positions", "velocities", "forces", "covloss", "energy", "stress", "md_scalars"}
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in arrays.values())
+        assert arrays["positions"].shape == arrays["forces"].shape == (4096, 3) and arrays["covloss"].shape == (4096,)
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert np.isclose(arrays["energy"][0], arrays["md_scalars"][0], rtol=1e-12, atol=0)   # (row 0 of the scalars: E)
+        got.append(arrays)
+    for k in got[0]:
+        np.testing.assert_array_equal(got[0][k], got[1][k], err_msg=k)

@@ -232,7 +232,7 @@ def test_bench_two_ranks_over_the_exchange_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SGPR_PEER_TIMEOUT_MS="20000")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10",
-                          "--warmup", "3", "--collective", "ipc", "--no-cpu-baseline", "--no-big-wall", "--md-steps", "40"],
+                          "--warmup", "3", "--collective", "ipc", "--no-cpu-baseline", "--no-big-wall", "--md-steps", "40", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

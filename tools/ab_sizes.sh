@@ -6,7 +6,7 @@ for envs in "$@"; do
   for cfg in $SIZES; do
     side=${cfg%,*}; m=${cfg#*,}
     echo -n "[$envs] side $side m $m: "
-    env $envs python3 bench.py --atoms-side $side --inducing $m --steps 50 --warmup 10 --md-steps 0 --no-cpu-baseline --no-big-wall 2>/dev/null | python3 -c "
+    env $envs python3 bench.py --full --atoms-side $side --inducing $m --steps 50 --warmup 10 --md-steps 0 --no-cpu-baseline --no-big-wall 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(round(d['ms_per_step_resident_frames']*1e3,1), 'knm', r['stage_us']['gemm_knm'], r['knm_frac'], 'wcov', r['stage_us'].get('gemm_w_covloss'), r['wcov_frac'])"
   done
