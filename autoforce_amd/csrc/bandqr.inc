@@ -329,6 +329,7 @@ static int launch_band_qr(int rows, int cols, double *At, int ldr, double *x, do
                           int extra, int batch, size_t bs_mat, size_t bs_work, double *keepVT = nullptr /*[panels][band_qr_keep_stride()]: V, T of every panel stay*/)
 {
     if (band <= 0) return -2;
+    if (cols > QR_MAX_COLS) return -1;   // the back substitution's right-hand side lives in LDS (backsolve_attr)
     for (int k0 = 0; k0 < cols; k0 += 32) {
         const int nb = std::min(32, cols - k0);
         const int row_end = std::min(rows, band * (k0 + nb) + band_off);
@@ -371,6 +372,7 @@ static int launch_band_qr(int rows, int cols, double *At, int ldr, double *x, do
         q.Vp = q.Vn; q.Tp = q.Tn;
         par ^= 1;
     }
+    if (x) backsolve_attr();
     if (x) hipLaunchKernelGGL(qr_backsolve_kernel, dim3(batch), dim3(1024), sizeof(double) * cols, st, cols, At, ldr, At + (size_t)cols * ldr, x, bs_mat);
     return 0;
 }
@@ -506,6 +508,7 @@ int launch_band2_keep(int rows, int cols, double *At, int ldr, double *x, double
 int launch_band2_append(int m_old, int nnew, double *W, int ldw, const double *keepVT, const double *At_kept, int ldr_kept, double *x,
                         double *tmp, hipStream_t st)
 {
+    if (m_old > QR_MAX_COLS) return -1;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void *)band_qr_append_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)band_qr_lds_bytes());
@@ -514,6 +517,7 @@ int launch_band2_append(int m_old, int nnew, double *W, int ldw, const double *k
     BandAppend q = {};
     q.W = W; q.ldw = ldw; q.m_old = m_old; q.nnew = nnew; q.VT = keepVT; q.stride = band_qr_keep_stride(); q.rhs = tmp; q.x = x;
     hipLaunchKernelGGL(band_qr_append_kernel, dim3(1), dim3(BQT), band_qr_lds_bytes(), st, q);
+    backsolve_attr();
     hipLaunchKernelGGL(qr_backsolve_kernel, dim3(1), dim3(1024), sizeof(double) * m_old, st, m_old, At_kept, ldr_kept, tmp, x);
     return 0;
 }

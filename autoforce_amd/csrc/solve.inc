@@ -332,7 +332,8 @@ static int solve_stage2(sgpr_model *h, double noise0, double *mu_out, double *ch
         if (d_W.alloc((size_t)2 * ldw + mo + 64)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (least squares, stage 2)");
         hipLaunchKernelGGL(stage2_cols_kernel, dim3((m + 255) / 256), dim3(256), 0, st, m, route == 2 ? m - 1 : -1, h->d_R1.p, m,
                            h->d_R1.p + (size_t)m * m, h->d_L.p, ld, sigma, d_so.p, d_W.p, ldw);
-        launch_band2_append(mo, route == 2 ? 1 : 0, d_W.p, ldw, k2.VT.p, d_A.p, rup(2 * mo, 64), d_x.p, d_W.p + (size_t)2 * ldw, st);
+        if (launch_band2_append(mo, route == 2 ? 1 : 0, d_W.p, ldw, k2.VT.p, d_A.p, rup(2 * mo, 64), d_x.p, d_W.p + (size_t)2 * ldw, st))
+            return fail(SGPR_E_UNSUPPORTED, "least squares: m=%d exceeds the QR kernel limit", m);
     } else {
         k2.valid = false;   // (the factored matrix of the kept one lives in d_A)
         if (d_A.alloc((size_t)cpad * ldr) || d_work.alloc(lstsq_qr_blocked_work_doubles(R, m), false))
