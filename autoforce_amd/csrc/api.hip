@@ -277,6 +277,8 @@ struct sgpr_model {
     int rows16_mb = 16384;                              // hand-over buffer of the sixteen-column form (SGPR_ROWS16_MB)
     int rows16_min = 1;                                 // fewest columns of a call that take it (SGPR_ROWS16_MIN; 1: a column has the same bits whatever call computed it)
     const char *info_rows = "none yet";                 // form of the last rows call (sgpr_solve_info)
+    int info_step_bm_k = 0, info_step_bm_w = 0, info_step_chain = 0;  // tile forms of the last step (sgpr_solve_info)
+    const char *info_step_cov = "none";
     std::vector<int> rows_cols;
     // resident training set (data.inc): the design matrix [K_e; K_f; K_v] of the stored frames, column-major in the
     // caller's column order, design[c * design_rcap + r]; rows in frame-major blocks (e, 3N f, nv v)
@@ -387,6 +389,7 @@ struct sgpr_model {
     DevBuf<long long> d_pstamps; // SGPR_STAMPS=1 + a -DSGPR_PHASE_STAMPS build: [2][N][8] phase stamps (forward | reverse)
     DevBuf<int4> t_knm, t_w, t_cov, t_kmm, t_wcov;  // working-tile tables of the GEMMs
     DevBuf<int4> t_covl;                            // covloss tiles alone, longest reductions first (ride in the reverse kernel)
+    int wcov_chained = 0;    // W + covloss tiles that run behind another one in the grouped launch (build_tiles)
     bool cov_in_rev = false; // option "cov_in_rev": covloss tiles in the reverse kernel's launch instead of grouped with W
                              // (measured at 4096 / 512: W alone 22.7 -> 18.5 us, reverse + covloss 17.0 -> 24.6: the reverse pass
                              // already fills every SIMD's four wave slots, the tiles only push a third of its workgroups
@@ -1715,6 +1718,8 @@ static int build_tiles(sgpr_model *h, int kind)
             }
         }
         h->wcov_grid = (int)both.size();
+        h->wcov_chained = 0;
+        for (auto &e : extra) h->wcov_chained += (int)e.size();
         {
             // the successors behind the dispatched part; links become table positions
             size_t base[8];
@@ -1988,9 +1993,17 @@ extern "C" int sgpr_set_weights(sgpr_model *h, const double *mu, const double *m
 {
     if (!h || !mu) return fail(SGPR_E_INVALID, "sgpr_set_weights: bad arguments");
     if (h->m <= 0) return fail(SGPR_E_NOMODEL, "sgpr_set_weights: no inducing set");
+    const int m = h->m;
+    // K_mm is block-diagonal by species, so L and L^-1 have no cross-species entries.  The covloss tile table skips every
+    // output column outside the row tile's species range: a cross-species entry would silently count as zero, so refuse it.
+    if (choli)
+        for (int a = 0; a < m; a++)
+            for (int b = 0; b < m; b++)
+                if (h->ind_slot[a] != h->ind_slot[b] && choli[(size_t)h->ind_perm[a] * m + h->ind_perm[b]] != 0.0)
+                    return fail(SGPR_E_INVALID, "sgpr_set_weights: choli[%d][%d] couples two species (must be zero)",
+                                h->ind_perm[a], h->ind_perm[b]);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int m = h->m;
     std::vector<double> mus(h->m_pad, 0.0);
     for (int k = 0; k < m; k++) mus[k] = mu[h->ind_perm[k]];
     HIPCHK(hipMemcpy(h->d_mu.p, mus.data(), sizeof(double) * h->m_pad, hipMemcpyHostToDevice));
@@ -2005,9 +2018,8 @@ extern "C" int sgpr_set_weights(sgpr_model *h, const double *mu, const double *m
         for (int a = 0; a < m; a++)
             for (int b = 0; b < m; b++)
                 c[(size_t)a * h->m_pad + b] = choli[(size_t)h->ind_perm[a] * m + h->ind_perm[b]];
-        // K_mm is block-diagonal by species, so L and L^-1 have no cross-species entries and the
-        // stable species sort keeps each block lower-triangular.  A caller may still hand over
-        // a general matrix: detect, and only then give up the triangular trimming.
+        // The stable species sort keeps each (checked above) species block lower-triangular.  A caller may still hand
+        // over general blocks: detect, and only then give up the triangular trimming.
         bool lower = true;
         for (int a = 0; a < m && lower; a++)
             for (int b = a + 1; b < m; b++)
@@ -2376,9 +2388,11 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     const bool beta = h->m > 0 && h->has_choli && cnt > 0 && !h->rows_mu;
     // one launch for the three products when their tile forms allow it: the K_nm tiles first, the W and covloss tiles of
     // a row panel start when that panel's K_nm tiles have signalled (gemm_tile.inc, EPI_FUSED)
+    // option "cov_in_rev": the covloss tiles ride in the reverse kernel's launch where its four-atom workgroups take them
+    // (descriptor.hip: run_bwd; at nine to sixteen species it runs one atom per workgroup and would drop them)
+    const bool cov_rev = h->cov_in_rev && h->gemm_bm_w == 32 && h->gemm_kd_w == 16 && h->t_covl.n > 0 && SGPR_REV_WPW(h->S) == 4;
     const bool fused3 = predict && beta && h->gemm_fused && h->t_fused.n > 0 && !h->use_graph &&
-                        !(h->use_fork && h->side && !h->profile) &&
-                        !(h->cov_in_rev && h->gemm_bm_w == 32 && h->gemm_kd_w == 16 && h->t_covl.n > 0);
+                        !(h->use_fork && h->side && !h->profile) && !cov_rev;
     if (h->m > 0 && cnt > 0 && !fused3) {
         gemm_kernel_pm(h, h->d_Pn.p, cnt, h->d_lslot.p, h->d_lnn.p, h->t_knm, h->d_K.p, h->d_Aw.p,
                        h->rows_mu ? h->rows_mu : (h->has_mu ? h->d_mu.p : nullptr), h->d_Epart.p, st);
@@ -2422,7 +2436,7 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
         (void)hipEventRecord(h->ev_join, h->side);
         launch_gemm_nt(gw, EPI_STORE, st);
         forked = true;
-    } else if (predict && beta && h->cov_in_rev && h->gemm_bm_w == 32 && h->gemm_kd_w == 16 && h->t_covl.n > 0) {
+    } else if (predict && beta && cov_rev) {
         // W alone; the covloss tiles ride in the reverse kernel's launch below
         launch_gemm_nt(gw, EPI_STORE, st);
         stamp(h, "gemm_w", st);
@@ -2436,6 +2450,13 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     } else if (beta) {
         launch_gemm_nt(gc, EPI_ROWSQ, st);
         stamp(h, "gemm_covloss", st);
+    }
+    if (h->m > 0 && cnt > 0) {
+        h->info_step_bm_k = h->gemm_bm_k;
+        h->info_step_bm_w = h->gemm_bm_w;
+        h->info_step_chain = 0;
+        h->info_step_cov = !beta ? "none" : fused3 ? "fused" : forked ? "forked" : cov_rides ? "rev" : predict ? "grouped" : "alone";
+        if (!strcmp(h->info_step_cov, "grouped")) h->info_step_chain = h->wcov_chained;
     }
     if (predict) {
         dp.xq = h->xcd_quads ? h->gemm_bm_w / 4 : 0;  // the reverse pass reads the rows of the W tiles

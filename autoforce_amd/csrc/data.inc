@@ -1223,7 +1223,9 @@ extern "C" int sgpr_data_factor(sgpr_model *h, const double *Y, int with_energie
 extern "C" int sgpr_solve_info(sgpr_model *h, char *buf, int cap)
 {
     if (!h || !buf || cap < 1) return fail(SGPR_E_INVALID, "sgpr_solve_info: bad arguments");
-    snprintf(buf, (size_t)cap, "stage1=%s; stage2=%s; kmm_blocks=%d/%d; rows=%s", h->info_stage1.c_str(), h->info_stage2, h->info_blocks_done,
-             h->info_blocks, h->info_rows);
+    // ("rows=" stays the last field: callers read everything behind it as the route)
+    snprintf(buf, (size_t)cap, "stage1=%s; stage2=%s; kmm_blocks=%d/%d; step=knm%d wcov%d chain%d cov=%s; rows=%s", h->info_stage1.c_str(),
+             h->info_stage2, h->info_blocks_done, h->info_blocks, h->info_step_bm_k, h->info_step_bm_w, h->info_step_chain,
+             h->info_step_cov, h->info_rows);
     return SGPR_OK;
 }

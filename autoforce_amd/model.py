@@ -93,9 +93,10 @@ class SGPRModel:
         return self._h
 
     def solve_info(self):
-        """Route of the last data_solve / data_factor (sgpr_solve_info): 'stage1=...; kmm_blocks=a/b'."""
-        buf = C.create_string_buffer(256)
-        check(_lib.load().sgpr_solve_info(self._h, buf, 256))
+        """Route of the last data_solve / data_factor and tile forms of the last step (sgpr_solve_info):
+        'stage1=...; kmm_blocks=a/b; step=...; rows=...'."""
+        buf = C.create_string_buffer(512)
+        check(_lib.load().sgpr_solve_info(self._h, buf, 512))
         return buf.value.decode()
 
     def list_rebuilds(self):

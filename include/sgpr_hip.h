@@ -94,7 +94,9 @@ int sgpr_get_kmm_rowsum(sgpr_model *h, double *sums);
  *   :219-227 AutoMean weights, :644-649 _vscale.
  * mu[m]; mean_w[S] per-species constant energy (may be NULL = 0); vscale[S] (may be NULL =
  * 1; use +inf for species with no inducing point, calculator/active.py:795-800);
- * choli[m][m] = L^-1 lower-triangular, caller order (may be NULL: beta is then not computed).
+ * choli[m][m] = L^-1 lower-triangular, caller order (may be NULL: beta is then not computed).  Entries inside a species
+ * block may take any value (upper ones give up the triangular trimming of the covloss product); an entry that couples two
+ * species must be zero, as in every L^-1 of the block-diagonal K_mm: otherwise SGPR_E_INVALID and nothing is changed.
  */
 int sgpr_set_weights(sgpr_model *h, const double *mu, const double *mean_w, const double *vscale,
                      const double *choli);
@@ -206,11 +208,15 @@ int sgpr_data_factor(sgpr_model *h, const double *Y, int with_energies);
 /* Diagnostics of the last sgpr_data_solve / sgpr_data_factor: which route the first stage took ("full factorisation",
  * "columns appended / popped through the kept reflectors", "kept", "rows of the new frame appended to the kept
  * factor", "found in the cache", "from scratch") and how many species blocks of K_mm were factored, as text
- * ("stage1=...; stage2=...; kmm_blocks=a/b; rows=...": stage2 = "factorisation" or, for the model a kept second stage was
+ * ("stage1=...; stage2=...; kmm_blocks=a/b; step=...; rows=...", rows= last: stage2 = "factorisation" or, for the model a kept second stage was
  * made for asked again / with one appended column, "kept reflectors, ...").  The reference always refits from scratch (gppotential.py:548-605); tests use
  * this to assert that an edit (append, pop, select / downsize) was followed incrementally.  "rows=" names the kernel
  * form of the last rows / columns call: "sixteen columns per workgroup pass" (lmax and nmax <= 3, <= 4 species, lists of
- * <= 64 neighbours) or "one column per wave". */
+ * <= 64 neighbours) or "one column per wave".  "step=knmA wcovB chainC cov=D" names the GEMM tile forms of the last
+ * step: A and B the row heights (16, 32 or 64) of the K_nm and the W + covloss tiles, C the number of W + covloss tiles
+ * chained behind another one in the grouped launch (0: none, or covloss not grouped), D where the covloss product ran:
+ * "grouped" (one launch with W), "alone" (no W: no weights), "rev" (in the reverse kernel's launch), "fused" (one launch
+ * with K_nm and W), "forked" (side stream) or "none". */
 int sgpr_solve_info(sgpr_model *h, char *buf, int cap);
 
 /*

@@ -71,6 +71,19 @@ def compare(mdl, lmax, nmax, eta, rc, numbers, pos, cell, pbc, nl, tol=1e-8, rad
     assert np.abs(out["forces"] - ref["forces"]).max() <= tol * np.abs(ref["forces"]).max()
     assert np.abs(out["stress"] - ref["stress"]).max() <= tol * max(np.abs(ref["stress"]).max(), 1e-12)
     np.testing.assert_allclose(out["beta"], ref["beta"], rtol=0, atol=3e-6)
+    # covloss c = |choli k|^2 at full precision (vscale = 1: c = 1 - beta^2), against the oracle's K rows and choli, within
+    # what the K tolerance above allows (plus the device's own rounding); beta at 3e-6 lets a lost k-slice through
+    LD = np.longdouble
+    Kr = np.asarray(ref["cov"], float)
+    y = Kr.astype(LD) @ choli.astype(LD).T
+    dK = (1e-9 + len(X) * np.finfo(float).eps) * np.abs(Kr) + 1e-12
+    dy = dK @ np.abs(choli).T
+    bound = ((2 * np.abs(y).astype(float) + dy) * dy).sum(axis=1) + 8 * np.finfo(float).eps
+    c_ref = (y * y).sum(axis=1)
+    c_dev = 1.0 - np.asarray(out["beta"], float) ** 2
+    ok = np.asarray(out["beta"]) > 0                      # (c >= 1: beta is clamped to 0 and carries no c)
+    err = np.abs(c_dev.astype(LD) - c_ref).astype(float)
+    assert np.all(err[ok] <= bound[ok]), (err[ok].max(), bound[ok][np.argmax(err[ok] - bound[ok])])
     return out
 
 
