@@ -547,13 +547,31 @@ __device__ __forceinline__ double fin_lane(double v, int l)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
-__device__ __forceinline__ double fin_wave_sum(double v)
+// sum over a 16-lane row (quads, half rows, rows): every lane of the row holds it
+__device__ __forceinline__ double fin_row_sum(double v)
 {
     v += fin_dpp<0xB1>(v);
     v += fin_dpp<0x4E>(v);
     v += fin_dpp<0x141>(v);
     v += fin_dpp<0x140>(v);
+    return v;
+}
+__device__ __forceinline__ double fin_wave_sum(double v)
+{
+    v = fin_row_sum(v);
     return (fin_lane(v, 0) + fin_lane(v, 16)) + (fin_lane(v, 32) + fin_lane(v, 48));
+}
+// fin_wave_sum of a value that a row holds in four parts, part j standing for lanes 16 j .. 16 j + 15 of a wave: the
+// same bits
+__device__ __forceinline__ double fin_row_sum4(const double (&v)[4])
+{
+    return (fin_row_sum(v[0]) + fin_row_sum(v[1])) + (fin_row_sum(v[2]) + fin_row_sum(v[3]));
+}
+// lane K of every quad (quad_perm [K,K,K,K]): lanes 0..3 of a row see lane K of that row
+template <int K>
+__device__ __forceinline__ double fin_quad_lane(double v)
+{
+    return fin_dpp<K * 0x55>(v);
 }
 
 // reducer workgroup q: E (0), the nine virial components (1..9), the largest neighbour count (10)
@@ -993,17 +1011,22 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
     }
 }
 
-// The same gather, and with it the first kernel of the NEXT step (FinNext): a wave takes an atom to its next position —
-// read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild decision.
-// Grid: ceil(N / 4) gather workgroups, 11 reducers of this step, 2 lagged reducers.
+// The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
+// position — read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild
+// decision.  Grid: ceil(N / 16) gather workgroups (four atoms per wave), 11 reducers of this step, 2 lagged reducers.
 //   What bounds this kernel is its chain of dependent memory round trips, each of them a cold miss (2 - 3 us per link at
 // 4096 atoms).  The gather alone is two links (row + counts -> sums -> stores), the binning kernel four (index -> position
 // -> returning atomic -> record).  Fused naively they add up (12.4 us against 7.1 + 4.4 as two launches, measured).  So:
-//   * MODE 1: the two jobs of a wave are INDEPENDENT — it sums the forces of sorted atom number w and bins CALLER atom
+//   * MODE 1: the two jobs of a row are INDEPENDENT — it sums the forces of sorted atom number w and bins CALLER atom
 //     number w (position and species slot by caller index: no indirection in front of the atomic); the atomic is issued
 //     before the sums, its record is stored after them;
 //   * MODE 2: the position depends on the force, but on nothing else behind an indirection (the noise is sorted on upload);
 //   * the halt word of an MD run is requested with everything else and looked at before the first store.
+//   A row, not a wave, per atom: most of an atom's work sits on one to three lanes (the integrator and its deviates, beta,
+// the bin atomic and its records), and at one wave per atom (four per SIMD at 4096 atoms) issuing instructions for the idle
+// lanes was most of the time.  Lane l of a row holds the pair slots l, l + 16, l + 32, l + 48 (slot s >= 64 adds into the
+// value of slot s mod 64, as before): the row sum of value j is the sum over row j of the wave-per-atom form, and the four
+// are combined as fin_wave_sum combines its rows — the same bits, beta's covloss partials alike.
 template <int MODE>
 __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
 {
@@ -1014,29 +1037,46 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         // a run that has halted (covloss gate / capacity overflow at an earlier step): nothing may be touched any more
         if (halt_w < x.step) return;
         if (b >= nA + 11) {
+            if (b == nA + 12 && tid == 0) {
+                // binning of step s + 1: its flag is flag[(s + 1) & 3] (cleared two binnings ago, read by nobody now); the
+                // flag of step s + 3 is cleared for the binning after the next (neighbor.hip does the same with its cycle).
+                // (Here, not in an atom's wave: the guard's eighteen values would be live beside everything a row holds.)
+                const int s1 = x.step + 1;
+                if (x.force) atomicMax(&x.flags[s1 & 3], 1);
+                x.flags[(s1 + 2) & 3] = 0;
+                fin_cell_guard(f, *f.flag, s1);
+            }
             if (MODE == 2 && x.packed_prev) finalize_reduce_prev(f, b - nA - 11);
         } else
             finalize_reduce(f, b - nA);
         return;
     }
     const int s1 = x.step + 1;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int i = b * 4 + wave;          // sorted atom whose forces this wave sums
+    const int lane = tid & 15;           // lane of the row
+    const int i = b * 16 + (tid >> 4);   // sorted atom whose forces this row sums
     const bool act = i < f.N;
     const int ia = act ? i : 0;
     // ---- requests: ONE round trip.  Every load below is unconditional (clamped indices, the value masked afterwards): a
     // load inside `if (lane < 3)` or behind `act` becomes a branch with an s_waitcnt vmcnt(0) at its join, and the five
     // such joins of the first version of this kernel were five cold misses one behind the other (ISA; 12.4 us)
-    const int l3 = lane < 3 ? lane : 2, lg = lane < f.maxnn ? lane : f.maxnn - 1, lc = lane < f.csq_slots ? lane : f.csq_slots - 1;
-    const int rebuilt = *f.flag;
-    const NlGrid g = *f.grid;
-    const double2 *grow = (const double2 *)(f.G + ((size_t)ia * f.maxnn + lg) * 4);
-    double2 g0 = grow[0], g1 = grow[1];
-    const int n_ld = f.nn[ia];
-    double fs = f.Fself[3 * (size_t)ia + l3];
+    const int l3 = lane < 3 ? lane : 2;
     const int c = f.perm[ia];
     const int slot_i = f.slot[ia];
-    // the atom this wave BINS: MODE 1: caller atom number i (sorted index ib = iperm[i]); MODE 2: sorted atom i itself
+    const int rebuilt = *f.flag;
+    const NlGrid g = *f.grid;
+    const int n_ld = f.nn[ia];
+    // pair slots lane + 16 j
+    double2 g0[4];
+    double g1[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int s = lane + 16 * j;
+        const double *p = f.G + ((size_t)ia * f.maxnn + (s < f.maxnn ? s : f.maxnn - 1)) * 4;
+        g0[j] = *(const double2 *)p;
+        g1[j] = p[2];
+    }
+    double fs = f.Fself[3 * (size_t)ia + l3];
+    // the atom this row BINS: MODE 1: caller atom number i (sorted index ib = iperm[i]); MODE 2: sorted atom i itself
     const int ib = MODE == 1 ? x.iperm[ia] : ia;
     const int slot_b = MODE == 1 ? x.cslot[ia] : slot_i;
     double xc = 0.0, p0 = 0.0, vc = 0.0, ms = 1.0, sg = 0.0, nz = 0.0, xn = 0.0;
@@ -1051,32 +1091,40 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     }
     double xpv = 0.0, zeta = 0.0;
     if (MODE == 2 && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (wave-uniform condition)
-    double csv = f.has_beta ? f.csq[(size_t)ia * f.csq_slots + lc] : 0.0;   // (wave-uniform condition)
-    if (lane >= f.csq_slots) csv = 0.0;
+    // covloss partials lane + 16 j (and + 64, ...); without beta, four loads of Fself[0] (a wave-uniform condition on the
+    // pointer, not a branch around four loads)
+    const double *cqp = f.has_beta ? f.csq + (size_t)ia * f.csq_slots : f.Fself;
+    double cq[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int s = lane + 16 * j;
+        cq[j] = cqp[f.has_beta && s < f.csq_slots ? s : (f.has_beta ? f.csq_slots - 1 : 0)];
+        if (!f.has_beta || s >= f.csq_slots) cq[j] = 0.0;
+    }
     if (f.has_beta)
-        for (int k = lane + 64; k < f.csq_slots; k += 64) csv += f.csq[(size_t)ia * f.csq_slots + k];  // (more than 64 slots: rare)
-    if (lane >= f.maxnn) { g0 = make_double2(0.0, 0.0); g1 = g0; }
-    if (lane >= 3) fs = 0.0;
-    const int n = act ? n_ld : 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            for (int k = lane + 16 * j + 64; k < f.csq_slots; k += 64) cq[j] += f.csq[(size_t)ia * f.csq_slots + k];  // (more than 64 slots: rare)
     // second link (beside the atomic below): what hangs on an index that was itself loaded
     const double vs = f.has_beta ? f.vs_sqrt[slot_i < x.S ? slot_i : 0] : 0.0;
     if (MODE == 1) {
         xc = x.pos[3 * (size_t)ib + l3];
         p0 = f.pos0[3 * (size_t)ib + l3];
     }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (lane + 16 * j >= f.maxnn) { g0[j] = make_double2(0.0, 0.0); g1[j] = 0.0; }
+    if (lane >= 3) fs = 0.0;
+    const int n = act ? n_ld : 0;
     if (halt_w < x.step) return;  // (before the first store)
-    for (int k = b * 256 + tid; k < f.nbins_clear; k += nA * 256) x.bc_cur[(size_t)k * SGPR_BIN_STRIDE] = 0;
-    if (b == 0 && tid == 0) {
-        // binning of step s + 1: its flag is flag[(s + 1) & 3] (cleared two binnings ago, read by nobody now); the flag of
-        // step s + 3 is cleared for the binning after the next (neighbor.hip does the same with its cycle)
-        if (x.force) atomicMax(&x.flags[s1 & 3], 1);
-        x.flags[(s1 + 2) & 3] = 0;
-        fin_cell_guard(f, rebuilt, s1);
-    }
-    if (!act) return;
+    // this step's bin counters are cleared last (as early, the loop's registers came on top of the requests in flight)
+    auto clear_bins = [&]() {
+        for (int k = b * 256 + tid; k < f.nbins_clear; k += nA * 256) x.bc_cur[(size_t)k * SGPR_BIN_STRIDE] = 0;
+    };
+    if (!act) { clear_bins(); return; }   // (a whole row: the row's DPP below reads no other row)
     if (f.has_beta)
-        for (int k = lane; k < f.csq_slots; k += 64) x.csq_rw[(size_t)i * f.csq_slots + k] = 0.0;  // (the binning kernel clears these)
-    // bin of a position (lane 0 of the wave), and the atomic that hands out its slot
+        for (int k = lane; k < f.csq_slots; k += 16) x.csq_rw[(size_t)i * f.csq_slots + k] = 0.0;  // (the binning kernel clears these)
+    // bin of a position (lane 0 of the row), and the atomic that hands out its slot
     int bin = 0, kb = -1, w0 = 0, w1 = 0, w2 = 0;
     auto place = [&](double X, double Y, double Z) {
         int bidx[3], w[3];
@@ -1099,25 +1147,39 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     };
     double X = 0.0, Y = 0.0, Z = 0.0;
     if (MODE == 1) {
-        X = fin_lane(xn, 0); Y = fin_lane(xn, 1); Z = fin_lane(xn, 2);
+        X = fin_quad_lane<0>(xn); Y = fin_quad_lane<1>(xn); Z = fin_quad_lane<2>(xn);
         if (lane == 0) place(X, Y, Z);   // (the atomic's round trip runs beside the second link's loads)
     }
     // ---- the forces of atom i
-    const double cs = f.has_beta ? fin_wave_sum(csv) : 1.0;
-    double fx = 0.0, fy = 0.0, fz = 0.0;
-    for (int t0 = 0; t0 < n; t0 += 64) {
-        const int t = t0 + lane;
-        if (t < n) {
-            double2 b0 = g0, b1 = g1;
-            if (t0 > 0) {
-                const double2 *row = (const double2 *)(f.G + ((size_t)i * f.maxnn + t) * 4);
-                b0 = row[0]; b1 = row[1];
+    double cs = 1.0;
+    if (f.has_beta) {
+        cs = fin_row_sum4(cq);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    double fx[4], fy[4], fz[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        fx[j] = 0.0; fy[j] = 0.0; fz[j] = 0.0;
+        if (lane + 16 * j < n) { fx[j] += g0[j].x; fy[j] += g0[j].y; fz[j] += g1[j]; }
+    }
+    for (int t0 = 64; t0 < n; t0 += 64) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int t = t0 + lane + 16 * j;
+            if (t < n) {
+                const double *row = f.G + ((size_t)i * f.maxnn + t) * 4;
+                const double2 b0 = *(const double2 *)row;
+                fx[j] += b0.x; fy[j] += b0.y; fz[j] += row[2];
             }
-            fx += b0.x; fy += b0.y; fz += b1.x;
         }
     }
-    fx = fin_wave_sum(fx); fy = fin_wave_sum(fy); fz = fin_wave_sum(fz);
-    const double Fv = fs - (lane == 0 ? fx : lane == 1 ? fy : fz);
+    // (one component at a time: twelve interleaved row sums held 24 more VGPRs than the kernel has)
+    const double Fx = fin_row_sum4(fx);
+    __builtin_amdgcn_sched_barrier(0);
+    const double Fy = fin_row_sum4(fy);
+    __builtin_amdgcn_sched_barrier(0);
+    const double Fz = fin_row_sum4(fz);
+    const double Fv = fs - (lane == 0 ? Fx : lane == 1 ? Fy : Fz);
     if (lane < 3) f.packed[3 * (size_t)c + lane] = Fv;
     if (lane == 3) {
         const double v = 1.0 - cs;
@@ -1151,10 +1213,10 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         x.v_next[3 * (size_t)i + lane] = v3;
     }
     if (MODE == 2) {
-        const double k3 = fin_lane(ke, 0) + fin_lane(ke, 1) + fin_lane(ke, 2);
-        const double p3 = fin_lane(kp, 0) + fin_lane(kp, 1) + fin_lane(kp, 2);
+        const double k3 = fin_quad_lane<0>(ke) + fin_quad_lane<1>(ke) + fin_quad_lane<2>(ke);
+        const double p3 = fin_quad_lane<0>(kp) + fin_quad_lane<1>(kp) + fin_quad_lane<2>(kp);
         if (lane == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);
-        X = fin_lane(xn, 0); Y = fin_lane(xn, 1); Z = fin_lane(xn, 2);
+        X = fin_quad_lane<0>(xn); Y = fin_quad_lane<1>(xn); Z = fin_quad_lane<2>(xn);
         if (lane == 0) place(X, Y, Z);
     }
     if (rebuilt) p0 = xc;  // this step rebuilt the candidates: built at this step's positions
@@ -1163,7 +1225,8 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         if (rebuilt) f.pos0[3 * (size_t)ib + lane] = xc;
     }
     const double dd = xn - p0;
-    const double d2 = fin_lane(dd, 0) * fin_lane(dd, 0) + fin_lane(dd, 1) * fin_lane(dd, 1) + fin_lane(dd, 2) * fin_lane(dd, 2);
+    const double dx = fin_quad_lane<0>(dd), dy = fin_quad_lane<1>(dd), dz = fin_quad_lane<2>(dd);
+    const double d2 = dx * dx + dy * dy + dz * dz;
     if (lane == 0) {
         if (!(d2 <= x.thr2)) atomicMax(&x.flags[s1 & 3], 1);
         x.bin_of[ib] = bin;
@@ -1182,6 +1245,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
                 atomicMax(&f.stat[1], kb + 1);
         }
     }
+    clear_bins();
 }
 
 // normal deviates of an MD run, caller order -> sorted order (so that the integrator reads them without an indirection)
@@ -2307,7 +2371,7 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
         x.bc_cur = h->d_bin_count.p + SGPR_BIN_INTS * (step & 1u); x.bc_next = h->d_bin_count.p + SGPR_BIN_INTS * ((step + 1) & 1u);
         x.bin_of = h->d_bin_of.p; x.kslot = h->d_kslot.p; x.b_rec = h->d_b_rec.p; x.b_aux = h->d_b_aux.p;
         x.csq_rw = h->d_csq.p;
-        const dim3 grid((std::max(N, 1) + 3) / 4 + 13);
+        const dim3 grid((std::max(N, 1) + 15) / 16 + 13);
         if (consume) {
             // the consumer of a sharded step's exchange (peer.inc): totals, the next positions, the next step's bins
             const dim3 gs((std::max(N, 1) + 63) / 64 + 3);
