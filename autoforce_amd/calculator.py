@@ -505,7 +505,7 @@ class ActiveCalculator(Calculator):
         return float(min(self._ediff_lb.values))
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -521,10 +521,29 @@ class ActiveCalculator(Calculator):
         and at the end.  Falls back to the host loop (workloads.langevin_nvt) where md_on_device_ok() says no.
         tdamp_fs: Nose-Hoover NVT with that damping time instead of Langevin — the reference's DEFAULT dynamics,
         md(dynamics="NPT", bulk_modulus=None) = ase.md.npt.NPT(pfactor=None, ttime=tdamp fs) (cl/md.py:17, :131-166); no
-        deviates, `friction` / `rng` / `seed` unused; host loop: workloads.nose_hoover_nvt."""
+        deviates, `friction` / `rng` / `seed` unused; host loop: workloads.nose_hoover_nvt.
+        pfactor (with tdamp_fs): ... and a barostat — ase.md.npt.NPT with that pfactor (ptime^2 x bulk modulus; eV, Angstrom, amu
+        units as npt.NPT), externalstress (a pressure or six Voigt components), mask, iso (set_fraction_traceless(0)): the
+        moving cell of cl/md.py:131-166 inside the device loop (SGPRModel.md_begin).  atoms.cell is set wherever
+        atoms.positions are — sync points, a halted configuration before its calculate(), the end —, to the cell of THAT
+        configuration.  The cell must be upper triangular (npt.make_cell_upper_triangular).  Host loop:
+        workloads.npt_moving_cell."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, langevin_nvt, nose_hoover_nvt
+        from .workloads import FS, MASS, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         nh = tdamp_fs is not None
+        npt = pfactor is not None
+        if npt and not nh:
+            raise ValueError("run_md: a barostat (pfactor) needs the Nose-Hoover thermostat (tdamp_fs)")
+        baro = dict(pfactor=pfactor, externalstress=externalstress, mask=mask, iso=iso) if npt else {}
+
+        def put(st, vkey):
+            if npt:
+                if hasattr(atoms.cell, "array"):
+                    atoms.set_cell(st["cell"])
+                else:
+                    atoms.cell = np.array(st["cell"], float)
+            atoms.positions = st["positions"]
+            atoms.set_velocities(st[vkey])
         if len(getattr(atoms, "constraints", None) or ()):
             # (neither integrator of this method knows ASE's constraints: an ASE dynamics object around calculate() does)
             raise NotImplementedError("run_md integrates unconstrained atoms; with atoms.constraints set, drive calculate() "
@@ -541,26 +560,32 @@ class ActiveCalculator(Calculator):
         vel = atoms.get_velocities()
         vel = np.zeros((N, 3)) if vel is None else np.asarray(vel, float)
         first_on_host = self._needs_seed() or not self.md_on_device_ok()
+        if npt:
+            # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
+            # logs — those velocities; md_begin and the host twin are handed the caller's and remove it themselves)
+            from .npt import zero_mean_momentum
+            atoms.set_velocities(zero_mean_momentum(vel, masses))
         if first_on_host:
             # (an empty model is seeded by its first calculate(); then the device loop can take over)
             atoms.calc = self
             atoms.get_forces()
             if not self.md_on_device_ok():
-                loop = (nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel) if nh else
+                loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro) if npt else
+                        nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel) if nh else
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng))
                 for st, E, T, _, p, v, *rest in loop:
-                    atoms.positions = p
-                    atoms.set_velocities(v)
+                    put(dict(positions=p, velocities=v, cell=rest[0] if npt else None), "velocities")
                     yield st, E, T, bool(self.updated), _
                 return
         eng = self.engine
         kT = kB * temperature_K
         self._peer_fit(eng, N)
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
-                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None)
+                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro)
         # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
+        ke_before = None   # (moving cell: sum m v^2 of the configuration before the row at hand — the velocities calculate() is handed)
         batch = min(8, chunk)   # evaluations per md_run call: grows while nothing halts the device, shrinks back after a halt
         while done <= steps:    # (every call uploads its rows of deviates; a halt throws the unused ones' upload away)
             n = 1 if skip_gate else min(batch, steps + 1 - done)
@@ -582,32 +607,30 @@ class ActiveCalculator(Calculator):
                 if skip_gate:      # (the configuration calculate() has just dealt with, evaluated again with the new model:
                     skip_gate, upd, wall = False, bool(self.updated), share + t_host   # its line is written, its step counted)
                 else:
-                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), float(r[13] / (3 * N * kB)), float(r[11]), "")))
+                    # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a
+                    # moving cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
+                    ke_line = r[13] if (not npt or ke_before is None) else ke_before
+                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), float(ke_line / (3 * N * kB)), float(r[11]), "")))
                     self.step += 1
+                ke_before = r[12]
                 out.append((done, float(r[0]), float(r[12] / (3 * N * kB)), upd, wall))
                 done += 1
             self._log_lines(lines)
             if sync_every and out and out[-1][0] % sync_every == 0 and code != 1:
                 # the configuration of the batch's last row: the device has moved on to the next one unless the run is over
-                st = eng.md_state(which=0 if final else -1)
-                atoms.positions = st["positions"]
-                atoms.set_velocities(st["velocities_pre"])
+                put(eng.md_state(which=0 if final else -1), "velocities_pre")
             yield from out
             rows = rows[accepted:]
             batch = min(8, chunk) if code else min(2 * batch, chunk)
             if code == 1:
                 t_host = time.time()
-                st = eng.md_state(results=True)
-                atoms.positions = st["positions"]
-                atoms.set_velocities(st["velocities_pre"])   # what the integrator holds when it asks for forces
+                put(eng.md_state(results=True), "velocities_pre")   # (what the integrator holds when it asks for forces)
                 atoms.calc = self
                 self.results = {}
                 self.calculate(atoms)        # update_results + update + the log line, as inside an ASE loop
                 skip_gate = True
                 t_host = time.time() - t_host
-        st = eng.md_state(results=True)
-        atoms.positions = st["positions"]
-        atoms.set_velocities(st["velocities"])
+        put(eng.md_state(results=True), "velocities")
 
     def _log_lines(self, lines):
         """A batch of per-step lines in one open (a device loop produces them by the hundred)."""

@@ -183,6 +183,17 @@ struct MdState {
     int *mark = nullptr, *mark_dev = nullptr;  // [rows] mapped host memory: evaluation j has passed its last kernel (look-ahead throttle)
     size_t scal_rows = 0;
     std::vector<double> mass_sorted;
+    // moving cell (sgpr_md_barostat): Nose-Hoover with the cell, the strain rate and scaled coordinates in rings of four
+    // (NptSlot, sgpr_internal.h, has the argument for four)
+    bool npt = false, npt_started = false;
+    NptParams np = {};
+    double npt_pfactor = 0.0;
+    DevBuf<char> npt_ring;         // [4] NptSlot by evaluation index & 3
+    DevBuf<double> Q;              // [4][N][3] scaled coordinates q = x h^-1 - 1/2, sorted order, beside X
+    DevBuf<double> cells_d;        // [rows][SGPR_MD_CELL] cell and strain rate per evaluation of a call (device memory)
+    std::vector<double> cells;     // ... of the last call, and the evaluation index of its first row
+    long long cells_first = 0;
+    NptSlot *slot(long long n) const { return (NptSlot *)npt_ring.p + (n & 3); }
 };
 
 struct sgpr_model {
@@ -254,6 +265,7 @@ struct sgpr_model {
     // the last kernel of a step as the first of the next (finalize_next_kernel): what it pre-binned
     bool pre_valid = false;
     const double *pre_pos = nullptr, *pre_cell = nullptr;
+    const NlGrid *step_grid = nullptr;  // moving-cell MD: the grid the previous evaluation's last kernel binned this step in (md_npt.inc)
     unsigned pre_step = 0;
     bool fuse_next = true;           // option "fuse_next" (SGPR_FUSE_NEXT=0 at creation): off = every step bins for itself
     bool bin_identity = false;       // the positions handed to the binning kernel are in sorted order already (MD state)
@@ -467,6 +479,7 @@ __global__ void transpose_kernel(int rows, int cols, const double *A, int lda, d
 // calculate() (calculator/active.py:492-499) therefore fires one launch late — step s + 1 has been computed
 // speculatively by then and is discarded; positions, velocities and results of the last three steps are kept in
 // rings, so the state handed back is exactly step s.  After a halt every later launch of the queue exits at once.
+#define SGPR_MD_CELL 18   // doubles per evaluation of a moving-cell run: the cell, the strain rate eta (sgpr_md_cells)
 #define SGPR_MD_SCAL 16   // doubles per step in the host-visible scalar ring: E, virial[9], overflow, max covloss, 2 x kinetic energy
 struct FinNext {
     int mode;                  // 0 none, 1 frames, 2 md, 3 md tail (only the lagged reductions of the last step)
@@ -504,6 +517,11 @@ struct FinNext {
                                    //   reached ediff, [1] the step that overflowed a capacity (INT_MAX: none)
     double *scal_cur, *scal_prev;  // rows of the scalar ring (device memory)
     int *mark_cur;                 // mapped host memory: set to 1 by this evaluation's last kernel (ONE posted write per step)
+    // moving cell (sgpr_md_barostat, md_npt.inc; finalize_next_kernel<3>): the ring slots of this evaluation and the next,
+    // scaled coordinates of this configuration, the one before it and (out) the next
+    const struct NptSlot *npt_cur, *npt_next;
+    const double *q_cur, *q_prev;
+    double *q_next;
 };
 
 struct FinArgs {
@@ -1011,6 +1029,8 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
     }
 }
 
+#include "md_npt.inc"
+
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
 // position — read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild
 // decision.  Grid: ceil(N / 16) gather workgroups (four atoms per wave), 11 reducers of this step, 2 lagged reducers.
@@ -1027,12 +1047,16 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 // lanes was most of the time.  Lane l of a row holds the pair slots l, l + 16, l + 32, l + 48 (slot s >= 64 adds into the
 // value of slot s mod 64, as before): the row sum of value j is the sum over row j of the wave-per-atom form, and the four
 // are combined as fin_wave_sum combines its rows — the same bits, beta's covloss partials alike.
+//   MODE 3 (the template parameter: FinNext::mode stays 2) is MODE 2 with a moving cell (md_npt.inc): the integrator works on scaled coordinates, with 3 x 3 matrices that
+// md_npt_kernel left behind the previous evaluation (wave-uniform addresses, a column per lane, requested with everything
+// else); the atom is binned in the grid of the NEXT cell and tested against the binning kernel's affine rebuild rule.  Its own
+// instantiation: MODE 2 sits at its register limit and stays as it is.
 template <int MODE>
 __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
 {
     const int tid = threadIdx.x, b = blockIdx.x, nA = gridDim.x - 13;
     const FinNext &x = f.nx;
-    const int halt_w = MODE == 2 ? *x.halt : 0x7fffffff;
+    const int halt_w = MODE >= 2 ? *x.halt : 0x7fffffff;
     if (b >= nA) {
         // a run that has halted (covloss gate / capacity overflow at an earlier step): nothing may be touched any more
         if (halt_w < x.step) return;
@@ -1044,9 +1068,9 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
                 const int s1 = x.step + 1;
                 if (x.force) atomicMax(&x.flags[s1 & 3], 1);
                 x.flags[(s1 + 2) & 3] = 0;
-                fin_cell_guard(f, *f.flag, s1);
+                if (MODE != 3) fin_cell_guard(f, *f.flag, s1);   // (MODE 3 applies the affine rule itself)
             }
-            if (MODE == 2 && x.packed_prev) finalize_reduce_prev(f, b - nA - 11);
+            if (MODE >= 2 && x.packed_prev) finalize_reduce_prev(f, b - nA - 11);
         } else
             finalize_reduce(f, b - nA);
         return;
@@ -1063,7 +1087,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     const int c = f.perm[ia];
     const int slot_i = f.slot[ia];
     const int rebuilt = *f.flag;
-    const NlGrid g = *f.grid;
+    const NlGrid g = MODE == 3 ? x.npt_next->grid : *f.grid;
     const int n_ld = f.nn[ia];
     // pair slots lane + 16 j
     double2 g0[4];
@@ -1091,6 +1115,24 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     }
     double xpv = 0.0, zeta = 0.0;
     if (MODE == 2 && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (wave-uniform condition)
+    // MODE 3: q_n, q_(n-1), and column l3 of the matrices: h_n^-1, B - 1, (B + 1)^-1, h_n, h_(n+1), the two affine maps
+    double qc = 0.0, qp = 0.0, c_hinv[3], c_bm1[3], c_bp1[3], c_h[3], c_hn[3], c_ak[3], c_ar[3], thr2_k = 0.0, thr2_r = 0.0;
+    if (MODE == 3) {
+        const NptSlot *nc = x.npt_cur, *nn = x.npt_next;
+        xc = x.x_cur[3 * (size_t)ia + l3];
+        p0 = f.pos0[3 * (size_t)ia + l3];
+        vc = x.v_cur[3 * (size_t)ia + l3];
+        ms = x.mass[ia];
+        qc = x.q_cur[3 * (size_t)ia + l3];
+        qp = x.q_prev[3 * (size_t)ia + l3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            c_hinv[j] = nc->hinv[3 * j + l3]; c_bm1[j] = nc->bm1[3 * j + l3]; c_bp1[j] = nc->bp1inv[3 * j + l3];
+            c_h[j] = nc->h[3 * j + l3]; c_hn[j] = nn->h[3 * j + l3];
+            c_ak[j] = nc->aff_keep[3 * j + l3]; c_ar[j] = nc->aff_reb[3 * j + l3];
+        }
+        thr2_k = nc->thr2_keep; thr2_r = nc->thr2_reb;
+    }
     // covloss partials lane + 16 j (and + 64, ...); without beta, four loads of Fself[0] (a wave-uniform condition on the
     // pointer, not a branch around four loads)
     const double *cqp = f.has_beta ? f.csq + (size_t)ia * f.csq_slots : f.Fself;
@@ -1187,7 +1229,29 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     }
     // ---- the next step
     double ke = 0.0, kp = 0.0;
-    if (MODE == 2 && x.nh) {
+    // row vector (lanes 0..2 of the row) times the matrix whose column `lane` is c: (v_0 c_0 + v_1 c_1) + v_2 c_2
+    auto row_mul = [&](double v, const double (&c)[3]) {
+#pragma clang fp contract(off)
+        return (fin_quad_lane<0>(v) * c[0] + fin_quad_lane<1>(v) * c[1]) + fin_quad_lane<2>(v) * c[2];
+    };
+    if (MODE == 3) {
+        // workloads.npt_moving_cell's operations in its order (md_npt.inc has the scheme): no contraction, true divisions
+#pragma clang fp contract(off)
+        const double dt = 2.0 * x.hdt;
+        const double a = __ddiv_rn((dt * dt) * Fv, ms);
+        const double num = ((2.0 * qc) + row_mul(qp, c_bm1)) + row_mul(a, c_hinv);
+        const double qn = row_mul(num, c_bp1);
+        const double vcen = __ddiv_rn(row_mul(qn - qp, c_h), 2.0 * dt);
+        const double vnow = x.nh_first ? vc : vcen;   // (the first time v_0 is the caller's own, as at constant cell)
+        xn = row_mul(qn + 0.5, c_hn);
+        if (lane < 3) {
+            ke = ms * (vnow * vnow);
+            kp = ke;
+            x.q_next[3 * (size_t)i + lane] = qn;
+            x.x_next[3 * (size_t)i + lane] = xn;
+            x.v_now[3 * (size_t)i + lane] = vnow;
+        }
+    } else if (MODE == 2 && x.nh) {
         if (lane < 3) {
             const double vnow = md_nh_advance(x, Fv, ms, xc, vc, xpv, zeta, xn);
             ke = ms * (vnow * vnow);
@@ -1212,7 +1276,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         x.x_next[3 * (size_t)i + lane] = xn;
         x.v_next[3 * (size_t)i + lane] = v3;
     }
-    if (MODE == 2) {
+    if (MODE >= 2) {
         const double k3 = fin_quad_lane<0>(ke) + fin_quad_lane<1>(ke) + fin_quad_lane<2>(ke);
         const double p3 = fin_quad_lane<0>(kp) + fin_quad_lane<1>(kp) + fin_quad_lane<2>(kp);
         if (lane == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);
@@ -1224,11 +1288,14 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         x.pos[3 * (size_t)ib + lane] = xn;
         if (rebuilt) f.pos0[3 * (size_t)ib + lane] = xc;
     }
-    const double dd = xn - p0;
+    // MODE 3: the build-time position mapped into the next cell (A = h0^-1 h, neighbor.hip), h0 = this step's cell if it rebuilt
+    if (MODE == 3 && rebuilt) { c_ak[0] = c_ar[0]; c_ak[1] = c_ar[1]; c_ak[2] = c_ar[2]; }
+    const double dd = MODE == 3 ? xn - row_mul(p0, c_ak) : xn - p0;
+    const double thr2 = MODE == 3 ? (rebuilt ? thr2_r : thr2_k) : x.thr2;
     const double dx = fin_quad_lane<0>(dd), dy = fin_quad_lane<1>(dd), dz = fin_quad_lane<2>(dd);
     const double d2 = dx * dx + dy * dy + dz * dz;
     if (lane == 0) {
-        if (!(d2 <= x.thr2)) atomicMax(&x.flags[s1 & 3], 1);
+        if (!(d2 <= thr2)) atomicMax(&x.flags[s1 & 3], 1);
         x.bin_of[ib] = bin;
         x.kslot[ib] = kb;
         if (slot_b < x.S) {
@@ -1494,6 +1561,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         for (auto b : mdb) b->release();
         m.halt.release();
         m.zeta.release();
+        m.npt_ring.release(); m.Q.release(); m.cells_d.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
         for (auto b : tb) b->release();
         h->d_panel_cnt.release();
@@ -2327,6 +2395,7 @@ struct FinBatch { int batch; double *G, *F, *virpart; size_t g_stride, f_stride,
 struct StepNext {
     int mode = 0;                      // 1: the next frame's positions are on the device, 2: integrate (sgpr_md_run)
     const double *pos_next = nullptr;  // mode 1: caller order
+    const double *cell_next = nullptr; // mode 2 with a moving cell: the cell of the next step (null: this step's)
     FinNext md;                        // mode 2: the integrator's fields (the binning fields are filled in launch_finalize)
 };
 
@@ -2347,7 +2416,7 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
     f.mean_energy = mean_energy; f.packed = packed_dev; f.stat = h->d_stat.p; f.bin_count = h->d_bin_count.p;
     f.flag = h->step_flag ? h->step_flag : h->d_flag.p; f.pos = h->d_pos.p; f.pos0 = h->d_pos0.p;
     f.rebuilds = h->d_flag.p + 4;
-    f.cell = h->last_cell; f.grid = (const NlGrid *)h->d_grid.p; f.cell0 = h->d_cell0.p;
+    f.cell = h->last_cell; f.grid = h->step_grid ? h->step_grid : (const NlGrid *)h->d_grid.p; f.cell0 = h->d_cell0.p;
     int batch = 1;
     if (fb) step = h->step_count - 1;  // (the step whose lists the batch re-uses)
     if (fb) {
@@ -2383,6 +2452,7 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
             x.csq_rw = h->d_csq.p;
             hipLaunchKernelGGL(finalize_scatter_next_kernel, dim3((std::max(N, 1) + 255) / 256 + 11), dim3(256), 0, st, f);
         } else if (nx->mode == 1) hipLaunchKernelGGL(finalize_next_kernel<1>, grid, dim3(256), 0, st, f);
+        else if (nx->md.npt_cur) hipLaunchKernelGGL(finalize_next_kernel<3>, grid, dim3(256), 0, st, f);
         else hipLaunchKernelGGL(finalize_next_kernel<2>, grid, dim3(256), 0, st, f);
         return;
     }
@@ -2431,6 +2501,9 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     const bool pre = h->pre_valid && h->pre_pos == pos_dev && h->pre_cell == cell_dev && h->pre_step == step && !sc.force;
     if (h->pre_valid && !pre) (void)hipMemsetAsync(sc.bin_count, 0, SGPR_BIN_INTS * sizeof(int), st);
     h->pre_valid = false;
+    // (a moving-cell MD step that was pre-binned: in the grid its cell has in the ring, which the binning kernel never made)
+    if (!(pre && nx && nx->mode == 2 && nx->md.npt_cur)) h->step_grid = nullptr;
+    if (h->step_grid) sc.grid = (NlGrid *)h->step_grid;
     if (!pre) {
         launch_neighbor_bin(np, h->bin_identity ? nullptr : h->d_perm.p, pos_dev, h->d_pos.p, cell_dev, h->rc + skin, sc, h->d_F.p, 3 * N,
                             h->d_csq.p, cnt * h->csq_slots, st);
@@ -2543,7 +2616,10 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     // takes the same consumer with its own partial sums as the one slice (frames the gather form cannot serve; the twin a
     // sharded run is compared with bit for bit).
     const bool px = peer_on(h) && h->world > 1;
-    const bool can_next = nx && nx->mode && h->fuse_next && predict && !forked && !h->use_graph && h->skin > 0.0;
+    // (a zero skin rebuilds every step through the binning kernel: the moving-cell loop runs that way too, as the reference
+    // of its rebuild rule; the other forms of the loop refuse it as before)
+    const bool can_next = nx && nx->mode && h->fuse_next && predict && !forked && !h->use_graph &&
+                          (h->skin > 0.0 || (nx->mode == 2 && nx->md.npt_cur));
     const bool shard_next = can_next && !gather && (px || (nx->mode == 2 && h->world == 1)) && !no_exchange;
     const bool fuse = can_next && !shard_next &&
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
@@ -2573,7 +2649,7 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
         h->reduce_done = true;
     }
     if (fuse || shard_next) {
-        h->pre_valid = true; h->pre_pos = nx->pos_next; h->pre_cell = cell_dev; h->pre_step = step + 1;
+        h->pre_valid = true; h->pre_pos = nx->pos_next; h->pre_cell = nx->cell_next ? nx->cell_next : cell_dev; h->pre_step = step + 1;
     }
     stamp(h, shard_next ? "sum_bin_next" : fuse ? "finalize_bin_next" : "finalize", st);
     return SGPR_OK;
@@ -3064,6 +3140,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.rank = tr; m.world = tw;
     m.N = N; m.t = 0; m.dt = dt; m.hdt = 0.5 * dt; m.c1 = exp(-friction * dt);
     m.ring = 3; m.nh = false; m.evaluated = false;
+    m.npt = false; m.npt_started = false; m.cells.clear();
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -3098,13 +3175,157 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
     if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
-    if (kind == 0) { m.nh = false; m.ring = 3; return SGPR_OK; }
+    if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
     const double tfact = 2.0 / ((double)(3 * m.N) * kT * ttime * ttime);
     m.nh = true; m.ring = 4;
     m.nh_c1 = m.dt * tfact; m.nh_c2 = 2.0 * m.dt * tfact; m.nh_K0 = 1.5 * (double)(m.N - 1) * kT;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
+    return SGPR_OK;
+}
+
+// A barostat for the Nose-Hoover run (sgpr_md_thermostat(kind = 1) first, before the first sgpr_md_run): ase.md.npt.NPT with
+// a pfactor, the moving cell of cl/md.py:131-166 — md_npt.inc has the scheme.  The cell of sgpr_md_begin must be upper
+// triangular (ASE's own condition) and periodic in all three directions.  pfactor = ptime^2 x bulk modulus and the external
+// stress (six Voigt components; a pressure P is (-P, -P, -P, 0, 0, 0)) in the units of the run; mask: nine zeros / ones (which
+// cell components may move); frac_traceless: 1 = all of the strain rate (with the mask), 0 = its trace only (`iso`).
+// Single rank only: the sharded last kernel (peer.inc) integrates at constant cell.
+extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *externalstress, const double *mask, double frac_traceless)
+{
+    if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.nh) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
+    if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
+    if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
+    if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
+    HIPCHK(hipSetDevice(h->device));
+    double c[9];
+    HIPCHK(hipMemcpy(c, m.cell.p, sizeof(c), hipMemcpyDeviceToHost));
+    if (!(c[3] == 0.0 && c[6] == 0.0 && c[7] == 0.0))
+        return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be upper triangular (h[1][0] = h[2][0] = h[2][1] = 0)");
+    const double det = (c[0] * c[4]) * c[8];
+    if (!(det > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell's diagonal must be positive");
+    if (m.npt_ring.alloc(4 * sizeof(NptSlot)) || m.Q.alloc((size_t)12 * m.N)) return fail(SGPR_E_NODEVICE, "sgpr_md_barostat: device allocation failed");
+    NptParams &p = m.np;
+    p = NptParams();
+    p.dt = m.dt; p.c1 = m.nh_c1; p.c2 = m.nh_c2; p.K0 = m.nh_K0;
+    p.pfact = 1.0 / (pfactor * det);
+    for (int k = 0; k < 6; k++) p.ext[k] = externalstress[k];
+    for (int k = 0; k < 9; k++) p.mask[k] = mask ? (mask[k] != 0.0 ? 1.0 : 0.0) : 1.0;
+    p.frac = frac_traceless;
+    for (int k = 0; k < 3; k++) p.pbc[k] = 1;
+    m.npt_pfactor = pfactor;
+    m.npt = true; m.npt_started = false;
+    return SGPR_OK;
+}
+
+// Fixed-order sum of md_npt_kernel / md_nh_kernel on the host: 256 strided partial sums, then a pairwise tree
+static double md_host_order_sum(const std::vector<double> &x)
+{
+    double p[256];
+    for (int t = 0; t < 256; t++) p[t] = 0.0;
+    for (size_t k = 0; k < x.size(); k++) p[k & 255] += x[k];
+    for (int w = 256; w > 1; w >>= 1)
+        for (int t = 0; t < w / 2; t++) p[t] = p[2 * t] + p[2 * t + 1];
+    return p[0];
+}
+
+// Start of a moving-cell trajectory (NPT.initialize(), autoforce_amd/npt.py): one synchronised evaluation of configuration 0,
+// then q_0 = x_0 h^-1 - 1/2 and q_(-1) by the backward step that is corrected twice (with ASE's test on the mean kinetic
+// energy per atom between the two corrections) on the host, in the operations of workloads.npt_moving_cell — once per
+// trajectory.  eta_0 = zeta_0 = 0 and therefore h_(-1) = h_1 = h_0; eta_(-1), zeta_(-1) are md_npt_kernel's (n = 0).
+static int md_npt_start(sgpr_model *h, hipStream_t st)
+{
+#pragma clang fp contract(off)
+    MdState &m = h->md;
+    const int N = m.N;
+    NptSlot s0 = {};
+    HIPCHK(hipMemcpy(s0.h, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
+    npt_matrices(m.np.dt, s0.h, s0.eta, 0.0, s0.hinv, s0.bm1, s0.bp1inv);
+    s0.thr2_keep = s0.thr2_reb = -1.0;
+    HIPCHK(hipMemset(m.npt_ring.p, 0, 4 * sizeof(NptSlot)));
+    HIPCHK(hipMemcpy(m.slot(0), &s0, sizeof(NptSlot), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.slot(1)->h, s0.h, 9 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
+    const int rc_ = run_checked(h, m.X.p, m.slot(0)->h, m.P.p, st);
+    if (rc_) return rc_;
+    h->warm = true;
+    std::vector<double> x((size_t)3 * N), v((size_t)3 * N), F((size_t)3 * N), q((size_t)3 * N), qp((size_t)3 * N), ke(N);
+    HIPCHK(hipMemcpy(x.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(F.data(), m.P.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));   // (packed forces: caller order)
+    const double dt = m.np.dt;
+    auto row_mul = [](const double *r, const double *mat, double *o) {
+#pragma clang fp contract(off)
+        for (int k = 0; k < 3; k++) o[k] = (r[0] * mat[k] + r[1] * mat[3 + k]) + r[2] * mat[6 + k];
+    };
+    for (int i = 0; i < N; i++) {
+        double t[3];
+        row_mul(&x[3 * (size_t)i], s0.hinv, t);
+        for (int k = 0; k < 3; k++) q[3 * (size_t)i + k] = t[k] - 0.5;
+    }
+    std::vector<double> vb = v;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int i = 0; i < N; i++) {
+            const int c = m.perm[i];
+            const double ms = m.mass_sorted[i];
+            const double *qi = &q[3 * (size_t)i];
+            double *qpi = &qp[3 * (size_t)i];
+            double t[3], a[3], al[3], num[3], qn[3], dq[3], vc[3];
+            row_mul(&vb[3 * (size_t)i], s0.hinv, t);
+            for (int k = 0; k < 3; k++) qpi[k] = qi[k] - dt * t[k];
+            for (int k = 0; k < 3; k++) a[k] = ((dt * dt) * F[3 * (size_t)c + k]) / ms;
+            row_mul(qpi, s0.bm1, t);
+            row_mul(a, s0.hinv, al);
+            for (int k = 0; k < 3; k++) num[k] = ((2.0 * qi[k]) + t[k]) + al[k];
+            row_mul(num, s0.bp1inv, qn);
+            for (int k = 0; k < 3; k++) dq[k] = qn[k] - qpi[k];
+            row_mul(dq, s0.h, t);
+            for (int k = 0; k < 3; k++) vc[k] = t[k] / (2.0 * dt);
+            ke[i] = (ms * (vc[0] * vc[0]) + ms * (vc[1] * vc[1])) + ms * (vc[2] * vc[2]);
+            for (int k = 0; k < 3; k++) vb[3 * (size_t)i + k] = (v[3 * (size_t)i + k] - vc[k]) + v[3 * (size_t)i + k];
+        }
+        if (0.5 * md_host_order_sum(ke) / N < 1e-5) break;
+    }
+    HIPCHK(hipMemcpy(m.Q.p, q.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.Q.p + (size_t)9 * N, qp.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    // the grids of h_0 and h_1 and the rebuild rule of evaluation 0 (which rebuilds: the first of its call)
+    hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p, (const double *)nullptr,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)h->d_cell0.p, -1,
+                       (const int *)m.halt.p, -1, (double *)nullptr, (double *)nullptr);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    m.npt_started = true;
+    return SGPR_OK;
+}
+
+// Cell and strain rate of a moving-cell run, SGPR_MD_CELL = 18 doubles (h[9], eta[9]) per configuration `first` ...
+// `first + count - 1` (indices of the trajectory: 0 = the configuration of sgpr_md_begin): those the last sgpr_md_run
+// evaluated, and the current one — the cell sgpr_md_state's positions belong to.
+extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out)
+{
+    if (!h || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_cells: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.npt) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const long long have = (long long)(m.cells.size() / SGPR_MD_CELL);
+    for (int r = 0; r < count; r++) {
+        const long long n = (long long)first + r;
+        double *o = out + (size_t)SGPR_MD_CELL * r;
+        if (n >= m.cells_first && n < m.cells_first + have)
+            memcpy(o, m.cells.data() + (size_t)SGPR_MD_CELL * (n - m.cells_first), sizeof(double) * SGPR_MD_CELL);
+        else if (n == m.t && m.npt_started) {
+            HIPCHK(hipMemcpy(o, m.slot(n)->h, 9 * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(o + 9, m.slot(n)->eta, 9 * sizeof(double), hipMemcpyDeviceToHost));
+        } else if (n == 0 && m.t == 0) {
+            HIPCHK(hipMemcpy(o, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
+            for (int k = 0; k < 9; k++) o[9 + k] = 0.0;
+        } else
+            return fail(SGPR_E_INVALID, "sgpr_md_cells: configuration %lld is neither the current one (%lld) nor one of the last run's", n, m.t);
+    }
     return SGPR_OK;
 }
 
@@ -3166,12 +3387,23 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host, 2 * sizeof(int), hipMemcpyHostToDevice, st));
     }
     h->bin_identity = true;
-    struct Restore { sgpr_model *h; ~Restore() { h->bin_identity = false; h->pre_valid = false; } } restore{h};
+    struct Restore { sgpr_model *h; ~Restore() { h->bin_identity = false; h->pre_valid = false; h->step_grid = nullptr; } } restore{h};
     // the first evaluation sizes the capacities for this configuration if nothing has yet (synchronised, results discarded)
     const int RG = m.ring;
     const int s0 = (int)(m.t % RG);
+    if (m.npt) { m.np.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.np.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
+    if (m.npt && !m.npt_started) {
+        const int rc_ = md_npt_start(h, st);
+        if (rc_) return rc_;
+    }
+    if (m.npt) {
+        if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
+    }
+    // (moving cell: the cell of configuration n is in the ring)
+    auto cell_of = [&](long long n) -> const double * { return m.npt ? m.slot(n)->h : m.cell.p; };
     if (!h->warm) {
-        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, m.cell.p, m.P.p + plen * s0, st);
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, cell_of(m.t), m.P.p + plen * s0, st);
         if (rc_) return rc_;
         h->warm = true;
     }
@@ -3184,7 +3416,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     m.chain_ok = false;
     if (chain) {
         h->lists_valid = true;
-        h->pre_valid = true; h->pre_pos = m.chain_pos; h->pre_cell = m.cell.p; h->pre_step = h->step_count;
+        h->pre_valid = true; h->pre_pos = m.chain_pos; h->pre_cell = cell_of(m.t); h->pre_step = h->step_count;
     } else {
         h->lists_valid = false;
         h->pre_valid = false;
@@ -3237,6 +3469,12 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
             if (m.t + j > 0) x.v_cur = m.V.p + (size_t)3 * N * sp;
             x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
         }
+        if (m.npt) {
+            x.npt_cur = m.slot(m.t + j); x.npt_next = m.slot(m.t + j + 1);
+            x.q_cur = m.Q.p + (size_t)3 * N * sl; x.q_prev = m.Q.p + (size_t)3 * N * sp; x.q_next = m.Q.p + (size_t)3 * N * sn;
+            nx.cell_next = x.npt_next->h;
+            h->step_grid = &x.npt_cur->grid;
+        }
         x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
         x.ke_cur = m.KE.p + (size_t)2 * N * sl; x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
         x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
@@ -3245,12 +3483,17 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         x.scal_cur = m.scal_d.p + (size_t)SGPR_MD_SCAL * j; x.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (j > 0 ? j - 1 : 0);
         x.mark_cur = m.mark_dev + j;
         (void)integrate;  // (the last evaluation of a `final` run integrates speculatively too: its outcome is not adopted below)
-        rc_ = enqueue_step(h, x.x_cur, m.cell.p, m.P.p + plen * sl, st, &nx);
+        rc_ = enqueue_step(h, x.x_cur, cell_of(m.t + j), m.P.p + plen * sl, st, &nx);
         if (rc_) break;
         h->lists_valid = true;  // (the first evaluation rebuilt the candidates; an overflow halts the run: FinNext)
         if (!h->pre_valid) { rc_ = fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the fused last kernel is not available for this model / frame (sharded "
                                         "without the library's own exchange, graph capture or a zero skin)"); break; }
-        if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
+        if (m.npt)  // zeta, eta and the matrices of the next configuration, the cell after it (md_npt.inc)
+            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p,
+                               (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + (size_t)3 * N * sl), (const double *)m.mass.p,
+                               (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.t + j) & 0x3fffffff), (const int *)m.halt.p,
+                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j);
+        else if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
             hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
                                m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
         enq = j + 1;
@@ -3271,6 +3514,11 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         HIPCHK(hipMemcpyAsync(m.scal_pin, m.scal_d.p, sizeof(double) * SGPR_MD_SCAL * (size_t)enq, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
+    if (m.npt) {
+        m.cells.assign((size_t)SGPR_MD_CELL * (size_t)enq, 0.0);
+        m.cells_first = m.t;
+        if (enq > 0) HIPCHK(hipMemcpy(m.cells.data(), m.cells_d.p, sizeof(double) * SGPR_MD_CELL * (size_t)enq, hipMemcpyDeviceToHost));
+    }
     if (const int pc = peer_check(h)) return pc;
     // (covloss halts and capacity overflows each leave the evaluation in their own mapped word; the earlier one halted the run)
     int hv[4] = {std::min(m.halt_host[0], m.halt_host[1]), 0, 0, 0};
@@ -3303,6 +3551,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         m.t += adv;
     }
     if (code == 2) done -= 1;  // (the overflowing evaluation's own results are void)
+    if (m.npt) m.cells.resize((size_t)SGPR_MD_CELL * (size_t)std::max(done, 0));
     if (keep_chain) {
         m.chain_ok = true; m.chain_step = h->step_count; m.chain_bind = h->bind_gen; m.chain_opt = h->opt_gen; m.chain_t = m.t;
         m.chain_pos = keep_pos;

@@ -60,6 +60,38 @@ struct NlGrid {
     double w[3];     // bin width along each cell vector's normal (perpendicular height / nb)
 };
 
+// Moving-cell MD (sgpr_md_barostat; md_npt.inc has the scheme): rings by evaluation index & 3.  Four slots, by the argument
+// that gives the Nose-Hoover rings four: a covloss halt at evaluation k is seen by launch k + 1, which has been computed
+// speculatively by then.  When the queue stops, md_npt_kernel has run behind evaluation k (the one behind k + 1 exits on the
+// halt word) and has written zeta, eta and the matrices of slot k + 1 and h and the grid of slot k + 2; the last kernel of
+// k + 1 has written Q and X of slot k + 2 and V of slot k + 1.  The restart at configuration k reads q_k, q_(k-1), x_k, h_k,
+// h_(k+1), eta_k and the matrices of slot k, and its md_npt_kernel reads eta_(k-1), zeta_(k-1) and the integral of slot k:
+// all of it in slots k - 1 and k, which nothing above has touched because k - 1, k, k + 1 and k + 2 are four different
+// slots.  With three, q_(k+2) would have landed on q_(k-1) and h_(k+2) on h_(k-1).
+struct NptSlot {
+    double h[9];          // cell of configuration n (rows = cell vectors, upper triangular)
+    double eta[9];        // strain rate eta_n
+    double hinv[9];       // h_n^-1
+    double bm1[9];        // B_n - 1
+    double bp1inv[9];     // (B_n + 1)^-1
+    double aff_keep[9];   // rebuild rule for the atoms moved into h_(n+1): h0^-1 h_(n+1) with h0 the cell the lists were built in ...
+    double aff_reb[9];    //   ... and with h0 = h_n, for an evaluation that has just rebuilt them
+    double thr2_keep, thr2_reb;   // its threshold squared (-1: rebuild)
+    double pad[15];
+    NlGrid grid;          // bin grid of h_n
+};
+static_assert(sizeof(NptSlot) % 16 == 0, "slots of the ring stay aligned");
+
+struct NptParams {
+    double dt, c1, c2, K0;        // time step, dt tfact, 2 dt tfact, desired kinetic energy
+    double pfact;                 // 1 / (pfactor det(h_0))
+    double ext[6];                // external stress (Voigt)
+    double mask[9];               // zeros and ones
+    double frac;                  // fraction of the traceless part kept (1: all, with the mask; else ASE applies no mask)
+    double rc_list, rc_phys;      // rc + skin, rc
+    int pbc[3];
+};
+
 // Bin populations sit SGPR_BIN_STRIDE ints apart: one counter per 128-byte line.  Packed, the ~350 counters of a 4096-atom
 // frame are eleven lines, and the returning atomics of the binning (one per atom, device scope: they execute at the
 // memory side, one after the other per line) were most of the binning kernel's 7 us.

@@ -578,13 +578,19 @@ class SGPRModel:
     # ------------------------------------------------------------------ device-resident molecular dynamics
     MD_SCALARS = 16  # per evaluation: E, virial[9], overflow word, largest covloss, sum m v^2, 3 spare
 
-    def md_begin(self, numbers, positions, cell, pbc, masses, velocities=None, dt=1.0, friction=0.0, kT=0.0, seed=0, ttime=None):
+    def md_begin(self, numbers, positions, cell, pbc, masses, velocities=None, dt=1.0, friction=0.0, kT=0.0, seed=0, ttime=None,
+                 pfactor=None, externalstress=0.0, mask=None, iso=False):
         """State of an MD run into device memory (cl/md.py:117-128 drives ase.md.langevin around calculate();
         here the integrator is part of the step's last kernel).  dt, friction and kT in the caller's units
         (workloads.FS / ase_shim.kB for fs / K)."""
         numbers = i32(numbers)
         N = len(numbers)
         self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=f64(masses), hdt=0.5 * dt)
+        if pfactor is not None:
+            if ttime is None:
+                raise ValueError("a barostat (pfactor) needs the Nose-Hoover thermostat (ttime)")
+            from .npt import zero_mean_momentum   # (NPT.__init__ removes the mean momentum: the host twin starts from the same bits)
+            velocities = zero_mean_momentum(np.zeros((N, 3)) if velocities is None else velocities, masses)
         v = None if velocities is None else f64(velocities).reshape(N, 3)
         self.generation += 1
         check(_lib.load().sgpr_md_begin(self._h, N, ptr(numbers), ptr(f64(positions).reshape(N, 3)), ptr(self._md["cell"]),
@@ -597,6 +603,16 @@ class SGPRModel:
         if ttime is not None:
             check(_lib.load().sgpr_md_thermostat(self._h, 1, float(ttime), float(kT)))
             self._md["nh"] = True
+        # pfactor: ... and a barostat — the moving cell of cl/md.py:131-166 (ase.md.npt.NPT with a pfactor; npt.py restates it,
+        # workloads.npt_moving_cell is the host twin).  externalstress: a pressure or six Voigt components; mask: 3 or 3 x 3;
+        # iso: the trace of the strain rate only (set_fraction_traceless(0)).  The cell must be upper triangular.
+        if pfactor is not None:
+            ext = np.asarray(externalstress, float)
+            ext = np.array([-float(ext)] * 3 + [0.0] * 3) if ext.ndim == 0 else f64(ext).reshape(6)
+            mk = np.not_equal(np.ones(3) if mask is None else np.asarray(mask), 0)
+            mk = f64((np.outer(mk, mk) if mk.shape == (3,) else mk.reshape(3, 3)).astype(float))
+            check(_lib.load().sgpr_md_barostat(self._h, float(pfactor), ptr(f64(ext)), ptr(mk), 0.0 if iso else 1.0))
+            self._md["npt"] = True
         self._md["t"] = 0
 
     def md_deviates(self, t_first, count):
@@ -618,7 +634,22 @@ class SGPRModel:
         self.generation += 1
         check(_lib.load().sgpr_md_run(self._h, int(nevals), ptr(noise), float(ediff), int(bool(final)), ptr(sc),
                                       C.addressof(done), C.addressof(code)))
+        if self._md.get("npt"):   # (where the state is now: sgpr_md_run's rules)
+            t0 = self._md["t"]
+            self._md["run"] = (t0, done.value)
+            self._md["t"] = t0 + (done.value - 1 if (code.value == 1 or (code.value == 0 and final)) else done.value)
         return sc[:done.value], code.value
+
+    def md_cells(self, first=None, count=None):
+        """Moving-cell runs: (cells [count, 3, 3], eta [count, 3, 3]) of the configurations first ... first + count - 1 of the
+        trajectory; default: those the last md_run evaluated.  The current configuration can always be asked for."""
+        if first is None:
+            first, count = self._md.get("run", (0, 0))
+        count = 1 if count is None else int(count)
+        out = np.zeros((count, 18))
+        if count:
+            check(_lib.load().sgpr_md_cells(self._h, int(first), count, ptr(out)))
+        return out[:, :9].reshape(count, 3, 3).copy(), out[:, 9:].reshape(count, 3, 3).copy()
 
     def md_state(self, which=0, results=False):
         """Positions, velocities of the current configuration (which = -1: the one before it); with results=True also
@@ -630,10 +661,15 @@ class SGPRModel:
         packed = np.empty(4 * N + 11) if results else None
         check(_lib.load().sgpr_md_state(self._h, ptr(x), ptr(v), C.addressof(pend), ptr(packed), int(which)))
         out = dict(positions=x, velocities_pre=v, pending=bool(pend.value))
+        cell = self._md["cell"]
+        if self._md.get("npt"):   # the cell these positions belong to, and its strain rate
+            c, e = self.md_cells(self._md["t"] + which, 1)
+            cell = out["cell"] = f64(c[0])
+            out["eta"] = e[0]
         if results:
             F = packed[:3 * N].reshape(N, 3).copy()
             stress = np.zeros(6)
-            check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress)))
+            check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[4 * N + 1:4 * N + 10])), ptr(cell), ptr(stress)))
             out.update(forces=F, beta=packed[3 * N:4 * N].copy(), energy=float(packed[4 * N]), stress=stress)
             if self._md.get("nh"):   # Nose-Hoover: the centred velocity of this configuration (v is the one before it)
                 vn = np.empty((N, 3))

@@ -54,6 +54,16 @@ def make_cell_upper_triangular(positions, cell):
     return np.asarray(positions, float) @ R.T, new_cell, R.T
 
 
+def zero_mean_momentum(velocities, masses):
+    """NPT.zero_center_of_mass_momentum as velocities: ASE subtracts the MEAN momentum per atom from every momentum.  One
+    function for everybody who starts this dynamics (NPT below takes momenta; workloads.npt_moving_cell and the device loop
+    take these velocities), so that they start from the same bits."""
+    m = np.asarray(masses, float)[:, None]
+    p = np.asarray(velocities, float) * m
+    p = p - p.sum(0) / len(m)
+    return p / m
+
+
 def _upper(six):
     return np.array(((six[0], six[5], six[4]), (0.0, six[1], six[3]), (0.0, 0.0, six[2])))
 

@@ -253,6 +253,171 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         xp, x = x, xn
 
 
+# ---- the moving-cell scheme of npt.py in the device's operations (npt_moving_cell, and what md_npt_kernel / the MODE 3 last
+# kernel of api.hip compute): 3 x 3 matrices as nested lists of floats, every product and sum spelled out in one fixed order
+def _m3_mul(a, b):
+    """a b, every entry (a_r0 b_0c + a_r1 b_1c) + a_r2 b_2c."""
+    return [[(a[r][0] * b[0][c] + a[r][1] * b[1][c]) + a[r][2] * b[2][c] for c in range(3)] for r in range(3)]
+
+
+def _m3_inv_upper(h):
+    """Inverse of an upper-triangular matrix in closed form (true divisions)."""
+    i00, i11, i22 = 1.0 / h[0][0], 1.0 / h[1][1], 1.0 / h[2][2]
+    i01 = -((h[0][1] * i00) * i11)
+    i12 = -((h[1][2] * i11) * i22)
+    i02 = ((h[0][1] * h[1][2] - h[0][2] * h[1][1]) * i00) * (i11 * i22)
+    return [[i00, i01, i02], [0.0, i11, i12], [0.0, 0.0, i22]]
+
+
+def _row_mul(q, m):
+    """Row vectors times a matrix: out[:, c] = (q[:, 0] m_0c + q[:, 1] m_1c) + q[:, 2] m_2c."""
+    return np.stack([(q[:, 0] * m[0][c] + q[:, 1] * m[1][c]) + q[:, 2] * m[2][c] for c in range(3)], axis=1)
+
+
+def _npt_deta(fdt, pfact, h, stress6, ext6, mask, frac):
+    """npt.NPT._deta: -fdt pfact det(h) (stress - external) as a strain-rate increment, with the mask or the trace /
+    traceless split applied.  det of an upper-triangular h: (h00 h11) h22."""
+    c = fdt * (pfact * ((h[0][0] * h[1][1]) * h[2][2]))
+    de = [-(c * (stress6[k] - ext6[k])) for k in range(6)]
+    u = [[de[0], de[5], de[4]], [0.0, de[1], de[3]], [0.0, 0.0, de[2]]]
+    if frac == 1.0:
+        return [[mask[r][c_] * u[r][c_] for c_ in range(3)] for r in range(3)]
+    tr = ((u[0][0] + u[1][1]) + u[2][2]) / 3.0
+    return [[(tr if r == c_ else 0.0) + frac * (u[r][c_] - (tr if r == c_ else 0.0)) for c_ in range(3)] for r in range(3)]
+
+
+def _npt_matrices(dt, h, eta, zeta):
+    """What the per-atom update of a configuration in the cell h needs: h^-1, B - 1 and (B + 1)^-1 with
+    B = dt h ((eta + zeta/2 1) h^-1) (npt.NPT._q_future)."""
+    hinv = _m3_inv_upper(h)
+    hz = 0.5 * zeta
+    g = [[eta[r][c] + (hz if r == c else 0.0) for c in range(3)] for r in range(3)]
+    gh = _m3_mul(h, _m3_mul(g, hinv))
+    b = [[dt * gh[r][c] for c in range(3)] for r in range(3)]
+    bm1 = [[b[r][c] - (1.0 if r == c else 0.0) for c in range(3)] for r in range(3)]
+    bp1 = [[b[r][c] + (1.0 if r == c else 0.0) for c in range(3)] for r in range(3)]
+    return hinv, bm1, _m3_inv_upper(bp1)
+
+
+def _npt_q_next(dt, F, mass, q, q_prev, hinv, bm1, bp1inv):
+    """npt.NPT._q_future: (2 q + q_prev (B - 1) + dt^2 (F / m) h^-1) (B + 1)^-1."""
+    a = ((dt * dt) * F) / mass
+    return _row_mul(((2.0 * q) + _row_mul(q_prev, bm1)) + _row_mul(a, hinv), bp1inv)
+
+
+def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, pfactor=None,
+                    externalstress=0.0, mask=None, iso=False, vel=None, species=None):
+    """Nose-Hoover / Parrinello-Rahman dynamics with a moving cell in numpy around any calculator with the ASE surface: npt.NPT
+    (ase.md.npt.NPT restated; what cl/md.py:131-166 runs when a bulk modulus is given) written by evaluation index, in the
+    operations and the order of the device loop (sgpr_md_barostat: md_npt_kernel and the moving-cell form of the step's last
+    kernel, api.hip) — its host twin, bit for bit.  No BLAS / LAPACK call (they fix no order of operations): the 3 x 3 algebra
+    is spelled out (_m3_mul, _m3_inv_upper — h, eta and B are upper triangular —, _row_mul), sums over the atoms go through
+    _device_order_sum in the library's species-sorted order (`species`: the model's table, default the sorted numbers).
+    pfactor and externalstress in eV, Angstrom, amu units (npt.GPA, FS); externalstress a scalar pressure or six Voigt
+    components; mask 3 or 3 x 3; iso: npt.NPT.set_fraction_traceless(0).  The cell must be upper triangular
+    (npt.make_cell_upper_triangular).  pfactor = None: no barostat, the recurrence of nose_hoover_nvt.
+      Blocks, by the lines of npt.py they restate:
+        * the mean momentum removed (NPT.__init__, :133-134): npt.zero_mean_momentum;
+        * constants tfact, pfact, desiredEkin (_constants, :174-178);
+        * the start (initialize, :230-252): h_(-1), eta_(-1), zeta_(-1) by half increments, q_(-1) by the backward step that
+          is corrected twice;
+        * per evaluation n: the ideal-gas part of the stress (_stress, :194-201), eta_(n+1), zeta_(n+1), h_(n+2) (step,
+          :259-261, with _deta, :212-221), q_(n+1) (_q_future, :223-228) and the centred velocity (:272), the positions of
+          configuration n + 1 in ITS cell (_set_box_and_positions, :203-209).
+    Yields (step, energy, temperature, wall seconds, positions, centred velocities, cell, eta, zeta, integral of zeta) per
+    evaluated configuration (the velocities of configuration 0 are the ones handed over)."""
+    import time
+    from .ase_shim import Atoms, kB
+    from .npt import zero_mean_momentum
+    N = len(numbers)
+    mass = np.array([MASS[int(z)] for z in numbers])[:, None]
+    kT = kB * temperature
+    if vel is None:
+        rng = np.random.default_rng(1)
+        vel = rng.normal(size=(N, 3)) * np.sqrt(kT / mass)
+        vel -= (mass * vel).sum(0) / mass.sum()
+    v0 = zero_mean_momentum(vel, mass[:, 0])
+    hdt = 0.5 * (dt_fs * FS)
+    dt = 2.0 * hdt
+    ttime = tdamp_fs * FS
+    tfact = 2.0 / (float(3 * N) * kT * ttime * ttime)
+    c1, c2, K0 = dt * tfact, 2.0 * dt * tfact, 1.5 * float(N - 1) * kT
+    h0 = [[float(v) for v in row] for row in np.asarray(cell, float).reshape(3, 3)]
+    if not (h0[1][0] == 0.0 and h0[2][0] == 0.0 and h0[2][1] == 0.0):
+        raise ValueError("the cell must be upper triangular (npt.make_cell_upper_triangular)")
+    baro = pfactor is not None
+    pfact = 1.0 / (float(pfactor) * ((h0[0][0] * h0[1][1]) * h0[2][2])) if baro else 0.0
+    ext = np.asarray(externalstress, float)
+    ext6 = [-float(ext)] * 3 + [0.0] * 3 if ext.ndim == 0 else [float(v) for v in ext.reshape(6)]
+    mk = np.ones(3) if mask is None else np.asarray(mask)
+    mk = np.not_equal(mk, 0)
+    mk = (np.outer(mk, mk) if mk.shape == (3,) else mk).astype(float).tolist()
+    frac = 0.0 if iso else 1.0
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+    zero3 = [[0.0] * 3 for _ in range(3)]
+
+    def evaluate(x, h, v):
+        at = Atoms(numbers, x, np.array(h), pbc, velocities=v, masses=mass[:, 0])
+        at.calc = calc
+        return np.asarray(at.get_forces(), float), float(at.get_potential_energy()), (np.asarray(at.get_stress(), float) if baro else np.zeros(6))
+
+    def sums(v):
+        ke3 = mass * (v * v)
+        KE = 0.5 * _device_order_sum(((ke3[:, 0] + ke3[:, 1]) + ke3[:, 2])[order])
+        S = [_device_order_sum((mass[:, 0] * (v[:, a] * v[:, b]))[order]) for a, b in VOIGT] if baro else [0.0] * 6
+        return KE, S
+
+    def sigma(stress6, S, h):
+        vol = abs((h[0][0] * h[1][1]) * h[2][2])
+        return [stress6[k] - S[k] / vol for k in range(6)]
+
+    h, eta, zeta, zint = {0: h0}, {0: zero3}, {0: 0.0}, {0: 0.0}
+    x = np.array(pos, float)
+    q, qp = None, None
+    for n in range(steps + 1):
+        t0 = time.time()
+        F, E, stress6 = evaluate(x, h[n], v0 if n == 0 else v)
+        if n == 0:
+            # ---- initialize(): eta_0 = 0, zeta_0 = 0
+            hinv, bm1, bp1inv = _npt_matrices(dt, h[0], eta[0], zeta[0])
+            q = _row_mul(x, hinv) - 0.5
+            he = _m3_mul(h[0], eta[0])
+            h[-1] = [[h[0][r][c] - dt * he[r][c] for c in range(3)] for r in range(3)]
+            KE, S = sums(v0)
+            d0 = _npt_deta(dt, pfact, h[0], sigma(stress6, S, h[0]), ext6, mk, frac) if baro else zero3
+            eta[-1] = [[eta[0][r][c] - d0[r][c] for c in range(3)] for r in range(3)]
+            zeta[-1] = zeta[0] - c1 * (KE - K0)
+            vb = v0
+            for _ in range(2):
+                qp = q - dt * _row_mul(vb, hinv)
+                qn = _npt_q_next(dt, F, mass, q, qp, hinv, bm1, bp1inv)
+                vc = _row_mul(qn - qp, h[0]) / (2.0 * dt)
+                if sums(vc)[0] / N < 1e-5:
+                    break
+                vb = (v0 - vc) + v0
+            he = _m3_mul(h[0], eta[0])
+            h[1] = [[h[-1][r][c] + (2.0 * dt) * he[r][c] for c in range(3)] for r in range(3)]
+            v = v0
+        else:
+            hinv, bm1, bp1inv = _npt_matrices(dt, h[n], eta[n], zeta[n])
+        qn = _npt_q_next(dt, F, mass, q, qp, hinv, bm1, bp1inv)
+        if n > 0:
+            v = _row_mul(qn - qp, h[n]) / (2.0 * dt)
+        # ---- what the one-workgroup launch behind evaluation n computes: zeta, eta of n + 1, the cell of n + 2
+        KE, S = sums(v)
+        d = _npt_deta(2.0 * dt, pfact, h[n], sigma(stress6, S, h[n]), ext6, mk, frac) if baro else zero3
+        eta[n + 1] = [[eta[n - 1][r][c] + d[r][c] for c in range(3)] for r in range(3)]
+        zeta[n + 1] = zeta[n - 1] + c2 * (KE - K0)
+        zint[n + 1] = zint[n] + dt * zeta[n + 1]
+        he = _m3_mul(h[n + 1], eta[n + 1])
+        h[n + 2] = [[h[n][r][c] + (2.0 * dt) * he[r][c] for c in range(3)] for r in range(3)]
+        yield n, E, float(2.0 * KE / (3 * N * kB)), time.time() - t0, x, v, np.array(h[n]), np.array(eta[n]), zeta[n], zint[n]
+        x = _row_mul(qn + 0.5, h[n + 1])
+        qp, q = q, qn
+
+
 def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None,
                         ediff=0.0, chunk=256, on_halt=None, device_rng=False):
     """langevin_nvt with the state in device memory (SGPRModel.md_begin / md_run): same scheme, same random stream

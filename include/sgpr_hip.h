@@ -372,6 +372,24 @@ int sgpr_md_seed(sgpr_model *h, uint64_t seed);
  * centred velocities (pending = 0). */
 int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double kT);
 int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, double *out);
+/* A barostat on top of the Nose-Hoover thermostat (between sgpr_md_thermostat(kind = 1) and the first sgpr_md_run): the
+ * combined Nose-Hoover / Parrinello-Rahman dynamics of ase.md.npt.NPT with a pfactor — the moving cell the reference's command
+ * line runs when a bulk modulus is given (cl/md.py:131-166) — inside the device loop: cell, strain rate eta and scaled
+ * coordinates live in rings on the device, one small launch behind each evaluation advances them, and the step's last kernel
+ * moves the atoms into the NEXT cell, bins them there and keeps the candidate lists while the strain since their build
+ * allows it.  pfactor = ptime^2 x bulk modulus; externalstress[6] (Voigt xx yy zz yz xz xy; a pressure P is -P, -P, -P, 0, 0, 0);
+ * mask[9] zeros and ones: the cell components that may move (NULL: all); frac_traceless: 1 = the whole strain rate (masked),
+ * 0 = its trace only (an isotropic cell; ASE applies no mask then).  Units as given to sgpr_md_begin.
+ * SGPR_E_INVALID: a cell that is not upper triangular (h[1][0] = h[2][0] = h[2][1] = 0 exactly), a direction that is not
+ * periodic, pfactor <= 0, no Nose-Hoover thermostat, a run that has started.  SGPR_E_UNSUPPORTED: a run begun on more than one
+ * rank (the sharded last kernel integrates at constant cell).  The handle goes on working after any of them.
+ * scalars of sgpr_md_run as for Nose-Hoover (14 / 15: zeta and its integral).  sgpr_md_state returns the positions of the
+ * current configuration in ITS cell:
+ * sgpr_md_cells   out[count][18] = cell h[9] (rows = cell vectors) and strain rate eta[9] of the configurations first ...
+ *                 first + count - 1 (index in the trajectory, 0 = the configuration of sgpr_md_begin): any evaluated by the
+ *                 last sgpr_md_run, and the current one. */
+int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *externalstress, const double *mask, double frac_traceless);
+int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
