@@ -40,6 +40,13 @@ class Atoms:
     def get_cell(self):
         return self.cell.copy()
 
+    def set_cell(self, cell, scale_atoms=False):
+        """ase.Atoms.set_cell: scale_atoms moves the atoms with the cell (the same fractional coordinates)."""
+        new = np.asarray(cell, dtype=float).reshape(3, 3).copy()
+        if scale_atoms:
+            self.positions = self.positions @ np.linalg.solve(self.cell, new)
+        self.cell = new
+
     def get_pbc(self):
         return self.pbc.copy()
 

@@ -632,6 +632,87 @@ class ActiveCalculator(Calculator):
                 t_host = time.time() - t_host
         put(eng.md_state(results=True), "velocities")
 
+    def run_relax(self, atoms, fmax=0.01, steps=100000, cell=False, mask=None, clear_hist=False, chunk=256, **fire):
+        """FIRE relaxation of atoms.positions — with cell=True also of atoms.cell, through the coordinates of
+        ase.constraints.UnitCellFilter(atoms, mask=mask) — as theforce/cl/relax.py minimises around this calculator, but with
+        the state in device memory between model updates: run_md's loop with the optimizer in the place of the integrator
+        (SGPRModel.relax_begin; md_relax.inc).  The host reads 16 scalars per evaluation and writes the log line calculate()
+        would (temperature 0); an evaluation whose largest covloss reaches the sampling threshold stops the device, is handed to
+        calculate() — which updates the model as inside an ASE loop —, the optimizer is re-initialised if clear_hist (and the
+        model was updated), and the run goes on with the new model.  At most `steps` moves.  atoms.positions and atoms.cell are
+        current after every update and at the end, where self.results are those of the final configuration.  fire: the keywords
+        of ase.optimize.FIRE.  Falls back to the host loop (cl/relax.py::FIRE and UnitCellFilter around calculate()) where
+        md_on_device_ok() says no or the run is sharded.  Returns dict(converged, steps, evaluations)."""
+        from .cl.relax import FIRE, UnitCellFilter, force_max
+        if len(getattr(atoms, "constraints", None) or ()):
+            raise NotImplementedError("run_relax moves unconstrained atoms; with atoms.constraints set, drive calculate() from an "
+                                      "ase.optimize optimizer as theforce/cl/relax.py does")
+
+        def put(st):
+            if cell:
+                if hasattr(atoms.cell, "array"):
+                    atoms.set_cell(st["cell"])
+                else:
+                    atoms.cell = np.array(st["cell"], float)
+            atoms.positions = st["positions"]
+
+        def device_ok():
+            return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "relax_begin")
+        first_on_host = self._needs_seed() or not device_ok()
+        if first_on_host:
+            atoms.calc = self
+            atoms.get_forces()
+            if not device_ok():
+                target = UnitCellFilter(atoms, mask=mask) if cell else atoms
+                opt = FIRE(target, **fire)
+                forces, n = target.get_forces(), 0
+                while force_max(forces) >= fmax and n < steps:
+                    opt.step(forces)
+                    n += 1
+                    forces = target.get_forces()
+                    if self.updated and clear_hist:
+                        opt.initialize()
+                return dict(converged=force_max(forces) < fmax, steps=n, evaluations=n + 1)
+        numbers, pos, cell0, pbc = self._system(atoms)
+        eng = self.engine
+        eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **fire)
+        done, skip_gate, converged = 0, first_on_host, False
+        batch = min(8, chunk)
+        while done <= steps and not converged:
+            n = 1 if skip_gate else min(batch, steps + 1 - done)
+            gate = 0.0 if skip_gate else self._md_gate(numbers)
+            sc, code = eng.md_run(n, None, ediff=gate, final=(done + n == steps + 1))
+            accepted = len(sc) - 1 if code == 1 else len(sc)
+            lines = []
+            for r in sc[:accepted]:
+                if skip_gate:      # (the configuration calculate() has just dealt with: its line is written, its step counted)
+                    skip_gate = False
+                else:
+                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), 0.0, float(r[11]), "")))
+                    self.step += 1
+                done += 1
+            self._log_lines(lines)
+            batch = min(8, chunk) if code else min(2 * batch, chunk)
+            if code == 1:
+                put(eng.md_state())
+                atoms.calc = self
+                self.results = {}
+                self.calculate(atoms)        # update_results + update + the log line, as inside an ASE loop
+                if clear_hist and self.updated:
+                    eng.relax_reset()
+                skip_gate = True
+            converged = code == 3
+        st = eng.md_state(results=True)
+        put(st)
+        # (the calculator answers for the final configuration from what the device has just computed)
+        atoms.calc = self
+        Calculator.calculate(self, atoms, ("energy",), all_changes)
+        self._beta = st["beta"]
+        self._cov, self._nl = None, None
+        self._set_results(st)
+        self.results["free_energy"] = self.results["energy"]
+        return dict(converged=converged, steps=max(done - 1, 0), evaluations=done)
+
     def _log_lines(self, lines):
         """A batch of per-step lines in one open (a device loop produces them by the hundred)."""
         if not lines:

@@ -8,8 +8,13 @@ active calculator — the model learns on the way, `calculate()` being what it i
 is updated and the relaxation continues from there.  With ASE installed this driver uses ASE's optimizers (and
 `UnitCellFilter` for `cell = True`) exactly as the reference does.  ASE is a dependency of the reference, not part of it,
 and is absent from the build image: without it two of its optimizers are restated here from their published algorithms
-(ase/optimize/bfgs.py, ase/optimize/fire.py, ASE 3.22) for positions only — `BFGS` (dense Hessian, H0 = 70 eV/A^2, the
-step taken through the eigen-decomposition with |omega|, the longest atomic step scaled down to 0.2 A) and `FIRE`.
+(ase/optimize/bfgs.py, ase/optimize/fire.py, ASE 3.22) — `BFGS` (dense Hessian, H0 = 70 eV/A^2, the step taken through the
+eigen-decomposition with |omega|, the longest atomic step scaled down to 0.2 A) and `FIRE` — and so is the cell filter of
+`cell = True` (ase/constraints.py::UnitCellFilter with a mask, ASE 3.22, LGPL: `UnitCellFilter` below) — through this driver
+with `algo = 'FIRE'`; `cell = True` with `'BFGS'` still asks for ASE.
+  Only `FIRE` runs on the device (ActiveCalculator.run_relax: the state stays in HBM between model updates): it is per-atom
+arithmetic and three global sums.  `BFGS`, the reference's default and therefore the default here, keeps a dense 3N x 3N
+Hessian and takes its eigen-decomposition every step — 12288^2 at 4096 atoms — and stays on the host, for small systems.
 Structures and the trajectory are extended XYZ."""
 import argparse
 
@@ -25,8 +30,64 @@ def force_max(forces):
     return float(np.sqrt((np.asarray(forces) ** 2).sum(axis=1).max())) if len(forces) else 0.0
 
 
+def voigt_mask(mask):
+    """Six Voigt flags xx yy zz yz xz xy (None: all ones) as the symmetric 3 x 3 matrix UnitCellFilter multiplies with."""
+    m = np.ones(6) if mask is None else np.asarray(mask, float)
+    if m.shape == (3, 3):
+        return m.copy()
+    if m.shape != (6,):
+        raise ValueError("mask: six Voigt flags (xx yy zz yz xz xy) or a 3 x 3 matrix")
+    return np.array([[m[0], m[5], m[4]], [m[5], m[1], m[3]], [m[4], m[3], m[2]]])
+
+
+class UnitCellFilter:
+    """ase.constraints.UnitCellFilter(atoms, mask=mask) restated (ASE 3.22, LGPL; the only form the reference uses,
+    cl/relax.py:45-48): positions and cell as ONE set of N + 3 generalised coordinates for an optimizer.  With h0 the cell at
+    construction (rows = vectors), D the deformation gradient (h = h0 D^T) and c = N (ASE's cell_factor):
+        get_positions:  [ x D^-T ; c D ]
+        get_forces:     [ F D ; (W D^-T o M) / c ],   W = -V stress (the full 3 x 3 matrix of the six components)
+        set_positions:  D = X[N:] / c,  h = h0 D^T,  x = X[:N] D^T
+    The other keywords of ASE's class are not restated."""
+
+    def __init__(self, atoms, mask=None, cell_factor=None, hydrostatic_strain=False, constant_volume=False, scalar_pressure=0.0):
+        if hydrostatic_strain or constant_volume or scalar_pressure:
+            raise NotImplementedError("UnitCellFilter: hydrostatic_strain, constant_volume and scalar_pressure are ASE's own: install ASE")
+        self.atoms = atoms
+        self.orig_cell = np.array(atoms.cell, float).reshape(3, 3)
+        self.mask = voigt_mask(mask)
+        self.cell_factor = float(len(atoms)) if cell_factor is None else float(cell_factor)
+
+    def __len__(self):
+        return len(self.atoms) + 3
+
+    def deform_grad(self):
+        return np.linalg.solve(self.orig_cell, np.asarray(self.atoms.cell, float)).T
+
+    def get_positions(self):
+        D = self.deform_grad()
+        return np.concatenate([np.linalg.solve(D, self.atoms.positions.T).T, self.cell_factor * D])
+
+    def set_positions(self, new):
+        n = len(self.atoms)
+        new = np.asarray(new, float)
+        D = new[n:] / self.cell_factor
+        self.atoms.set_cell(self.orig_cell @ D.T, scale_atoms=False)
+        self.atoms.set_positions(new[:n] @ D.T)
+
+    def get_forces(self):
+        a = self.atoms
+        F, s = np.asarray(a.get_forces(), float), np.asarray(a.get_stress(), float)
+        W = -a.get_volume() * np.array([[s[0], s[5], s[4]], [s[5], s[1], s[3]], [s[4], s[3], s[2]]])
+        D = self.deform_grad()
+        return np.concatenate([F @ D, np.linalg.solve(D, W.T).T * self.mask / self.cell_factor])
+
+    def get_potential_energy(self):
+        return self.atoms.get_potential_energy()
+
+
 class BFGS:
-    """ase/optimize/bfgs.py restated: quasi-Newton on the positions with a dense 3N x 3N Hessian."""
+    """ase/optimize/bfgs.py restated: quasi-Newton on the coordinates with a dense 3N x 3N Hessian (an eigen-decomposition
+    per step: for small systems)."""
 
     def __init__(self, atoms, maxstep=0.2, alpha=70.0):
         self.atoms, self.maxstep, self.alpha = atoms, maxstep, alpha
@@ -103,8 +164,10 @@ BUILT_IN = {"BFGS": BFGS, "FIRE": FIRE}
 class _Runner:
     """`dyn.irun(fmax)` / `dyn.run(fmax)` / `dyn.initialize()` of an ase.optimize optimizer around the built-in steppers."""
 
-    def __init__(self, atoms, algo, trajectory, master, max_steps=100000):
-        self.atoms, self.opt, self.master, self.max_steps = atoms, BUILT_IN[algo](atoms), master, max_steps
+    def __init__(self, atoms, algo, trajectory, master, max_steps=100000, target=None):
+        # (target: what the optimizer moves — the atoms, or a UnitCellFilter around them)
+        self.target = atoms if target is None else target
+        self.atoms, self.opt, self.master, self.max_steps = atoms, BUILT_IN[algo](self.target), master, max_steps
         self.out = open(trajectory, "w") if (trajectory and master) else None
         self.nsteps = 0
 
@@ -114,19 +177,19 @@ class _Runner:
     def _dump(self, forces):
         if self.out is not None:
             a = self.atoms
-            self.out.writelines(format_extxyz(Frame(a.numbers, a.positions, a.cell, a.pbc, a.calc.results.get("energy"), forces, None)))
+            self.out.writelines(format_extxyz(Frame(a.numbers, a.positions, a.cell, a.pbc, a.calc.results.get("energy"), forces[:len(a)], None)))
             self.out.flush()
         if self.master:
             print(f"{type(self.opt).__name__}: {self.nsteps:4d}  energy {self.atoms.calc.results.get('energy', float('nan')):.6f}  fmax {force_max(forces):.4f}")
 
     def irun(self, fmax):
-        forces = self.atoms.get_forces()
+        forces = self.target.get_forces()
         self._dump(forces)
         yield False
         while force_max(forces) >= fmax and self.nsteps < self.max_steps:
             self.opt.step(forces)
             self.nsteps += 1
-            forces = self.atoms.get_forces()
+            forces = self.target.get_forces()
             self._dump(forces)
             yield False
         yield True
@@ -134,28 +197,68 @@ class _Runner:
     def run(self, fmax):
         for _ in self.irun(fmax):
             pass
-        return force_max(self.atoms.get_forces()) < fmax
+        return force_max(self.target.get_forces()) < fmax
 
 
-def _optimizer(atoms, algo, cell, mask, trajectory, master):
+class _DeviceRunner:
+    """The same surface around ActiveCalculator.run_relax: FIRE with the state in device memory between model updates.  Every
+    run starts the optimizer afresh (relax_begin); clear_hist re-initialises it behind every model update inside a run."""
+
+    def __init__(self, atoms, calc, cell, mask, trajectory, master, clear_hist, max_steps=100000):
+        self.atoms, self.calc, self.cell, self.mask, self.master, self.clear_hist, self.max_steps = atoms, calc, cell, mask, master, clear_hist, max_steps
+        self.out = open(trajectory, "w") if (trajectory and master) else None
+        self.nsteps = 0
+
+    def initialize(self):
+        pass
+
+    def run(self, fmax):
+        res = self.calc.run_relax(self.atoms, fmax=fmax, steps=self.max_steps, cell=self.cell, mask=self.mask, clear_hist=self.clear_hist)
+        self.nsteps += res["steps"]
+        a, r = self.atoms, self.calc.results
+        if self.out is not None:
+            self.out.writelines(format_extxyz(Frame(a.numbers, a.positions, a.cell, a.pbc, float(r["energy"]), r["forces"], None)))
+            self.out.flush()
+        if self.master:
+            print(f"FIRE (device): {self.nsteps:4d}  energy {float(r['energy']):.6f}  fmax {force_max(r['forces']):.4f}")
+        return res["converged"]
+
+    def irun(self, fmax):
+        yield False
+        yield self.run(fmax)
+
+
+def _optimizer(atoms, algo, cell, mask, trajectory, master, clear_hist=False):
+    calc = atoms.calc
+    # FIRE is per-atom arithmetic and three global sums: it runs inside the device loop where the calculator can hand the loop
+    # over (BFGS, the default, needs a dense Hessian's eigen-decomposition per step and stays on the host)
+    if algo == "FIRE" and hasattr(calc, "run_relax") and hasattr(calc, "md_on_device_ok") and (calc.md_on_device_ok() or calc._needs_seed()) \
+            and not len(getattr(atoms, "constraints", None) or ()):
+        return _DeviceRunner(atoms, calc, cell, mask, trajectory, master, clear_hist)
     try:
         from ase import optimize
-        from ase.constraints import UnitCellFilter
+        from ase.constraints import UnitCellFilter as AseUnitCellFilter
     except ImportError:
-        if cell:
-            raise NotImplementedError("cell = True is ase.constraints.UnitCellFilter around an ase.optimize optimizer "
-                                      "(cl/relax.py:46-49): install ASE; without it positions only")
         if algo not in BUILT_IN:
             raise NotImplementedError(f"algo = '{algo}' is an ase.optimize class: install ASE; without it: {sorted(BUILT_IN)}")
-        return _Runner(atoms, algo, trajectory, master)
-    filtered = UnitCellFilter(atoms, mask=mask) if cell else atoms          # cl/relax.py:46-49
+        if cell and algo != "FIRE":
+            # (the driver relaxes a cell with FIRE only: the dense Hessian of BFGS over 3N + 9 coordinates that differ in scale
+            # by the cell factor is ASE's own business — the class itself accepts the filter, for whoever drives it by hand)
+            raise NotImplementedError("cell = True with algo = 'BFGS' is ase.constraints.UnitCellFilter around ase.optimize.BFGS "
+                                      "(cl/relax.py:46-49): install ASE; without it algo = 'FIRE' relaxes the cell")
+        return _Runner(atoms, algo, trajectory, master, target=UnitCellFilter(atoms, mask=mask) if cell else None)
+    filtered = AseUnitCellFilter(atoms, mask=mask) if cell else atoms          # cl/relax.py:46-49
     return getattr(optimize, algo)(filtered, trajectory=trajectory, master=master)
 
 
 def relax(atoms, fmax=0.01, cell=False, mask=None, algo="BFGS", trajectory="relax.xyz", rattle=0.02, clear_hist=False, confirm=True,
           calc=None, seed=None):
     """The keywords of theforce/cl/relax.py::relax (same names and defaults; the trajectory is extended XYZ unless ASE
-    writes it).  Returns the number of exact (teacher) calculations the run asked for."""
+    writes it).  Returns the number of exact (teacher) calculations the run asked for.
+      algo = "FIRE" with a calculator whose md_on_device_ok() holds: the minimisation and every re-run of the confirm loop go
+    through ActiveCalculator.run_relax — the state stays on the device between model updates, cell = True included.  The default
+    stays the reference's "BFGS", which does not scale (a dense 3N x 3N Hessian and its eigen-decomposition every step) and
+    runs on the host only."""
     rng = np.random.default_rng(seed)
     numbers = np.asarray(atoms.numbers)
     calc = gen_active_calc(species=sorted(set(int(z) for z in numbers))) if calc is None else calc
@@ -164,7 +267,7 @@ def relax(atoms, fmax=0.01, cell=False, mask=None, algo="BFGS", trajectory="rela
     if rattle:
         atoms.set_positions(atoms.get_positions() + rng.normal(scale=rattle, size=(len(numbers), 3)))   # atoms.rattle(rattle)
     atoms.calc = calc
-    dyn = _optimizer(atoms, algo, cell, mask, trajectory, master)
+    dyn = _optimizer(atoms, algo, cell, mask, trajectory, master, clear_hist)
     for _ in dyn.irun(fmax):
         if calc.updated and clear_hist:
             dyn.initialize()

@@ -194,6 +194,13 @@ struct MdState {
     std::vector<double> cells;     // ... of the last call, and the evaluation index of its first row
     long long cells_first = 0;
     NptSlot *slot(long long n) const { return (NptSlot *)npt_ring.p + (n & 3); }
+    // FIRE relaxation (sgpr_md_relax, md_relax.inc): the run is a minimisation, not dynamics — rings of RLX_RING slots
+    bool relax = false;
+    bool relax_started = false;
+    RelaxParams rp = {};
+    DevBuf<double> rx_state;       // [RLX_LEN] the optimizer's scalars, the cell rows of X and their velocity, the move's coefficients
+    DevBuf<double> rx_ref;         // [N][3] positions referred to the first cell (r = x D^-T), sorted order; their velocity is V's slot 0
+    DevBuf<double> rx_cells;       // [RLX_RING][RLX_CELL] cell and deformation gradient by evaluation index % RLX_RING
 };
 
 struct sgpr_model {
@@ -1030,6 +1037,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 }
 
 #include "md_npt.inc"
+#include "md_relax.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
 // position — read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild
@@ -3119,7 +3127,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
                              const int32_t *pbc, const double *masses, const double *velocities, double dt,
                              double friction, double kT)
 {
-    if (!h || N <= 0 || !numbers || !positions || !cell || !masses)
+    if (!h || N <= 0 || !numbers || !positions || !cell)   // (masses = NULL: ones — a relaxation, sgpr_md_relax, has no use for them)
         return fail(SGPR_E_INVALID, "sgpr_md_begin: bad arguments");
     if (!(dt > 0.0) || friction < 0.0 || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_begin: dt > 0, friction >= 0, kT >= 0");
     HIPCHK(hipSetDevice(h->device));
@@ -3141,6 +3149,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.N = N; m.t = 0; m.dt = dt; m.hdt = 0.5 * dt; m.c1 = exp(-friction * dt);
     m.ring = 3; m.nh = false; m.evaluated = false;
     m.npt = false; m.npt_started = false; m.cells.clear();
+    m.relax = false; m.relax_started = false;
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -3149,7 +3158,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
             xs[3 * (size_t)i + k] = positions[3 * (size_t)c + k];
             if (velocities) vs[3 * (size_t)i + k] = velocities[3 * (size_t)c + k];
         }
-        ms[i] = masses[c];
+        ms[i] = masses ? masses[c] : 1.0;
         if (!(ms[i] > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_begin: mass of atom %d is not positive", c);
         sg[i] = friction > 0.0 ? c2 * sqrt(kT / ms[i]) : 0.0;   // (as workloads.langevin_nvt: c2 * np.sqrt(kT / mass))
     }
@@ -3175,6 +3184,7 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
     if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
+    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
     if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
     const double tfact = 2.0 / ((double)(3 * m.N) * kT * ttime * ttime);
@@ -3195,7 +3205,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
 {
     if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.nh) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
+    if (!m.active || !m.nh || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
     if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
@@ -3308,10 +3318,23 @@ extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *ou
 {
     if (!h || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_cells: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.npt) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat first");
+    if (!m.active || !(m.npt || m.relax)) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat (or sgpr_md_relax) first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const long long have = (long long)(m.cells.size() / SGPR_MD_CELL);
+    if (m.relax) {   // a relaxation: the cell and, in the place of eta, the deformation gradient D
+        for (int r = 0; r < count; r++) {
+            const long long n = (long long)first + r;
+            double *o = out + (size_t)SGPR_MD_CELL * r;
+            if (n >= m.cells_first && n < m.cells_first + have)
+                memcpy(o, m.cells.data() + (size_t)SGPR_MD_CELL * (n - m.cells_first), sizeof(double) * SGPR_MD_CELL);
+            else if (n == m.t)
+                HIPCHK(hipMemcpy(o, m.rx_cells.p + (size_t)RLX_CELL * (n % RLX_RING), RLX_CELL * sizeof(double), hipMemcpyDeviceToHost));
+            else
+                return fail(SGPR_E_INVALID, "sgpr_md_cells: configuration %lld is neither the current one (%lld) nor one of the last run's", n, m.t);
+        }
+        return SGPR_OK;
+    }
     for (int r = 0; r < count; r++) {
         const long long n = (long long)first + r;
         double *o = out + (size_t)SGPR_MD_CELL * r;
@@ -3329,6 +3352,208 @@ extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *ou
     return SGPR_OK;
 }
 
+// FIRE relaxation for the run begun by sgpr_md_begin (whose masses, velocities, dt, friction and kT it ignores), before the
+// first sgpr_md_run: the optimizer of ase/optimize/fire.py on the positions and, with move_cell, on the cell through
+// ase.constraints.UnitCellFilter's coordinates — md_relax.inc has the scheme, workloads.fire_relax is the host twin.
+// fire: dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (NULL: ASE's defaults); mask6: which of the six Voigt components
+// xx yy zz yz xz xy of the cell may move (NULL: all).  sgpr_md_run then evaluates, moves, and stops with halt code 3 at the
+// first configuration whose largest generalised force is below fmax — the state IS that configuration, nothing moved.  Single
+// rank only.
+static const double RLX_ASE[8] = {0.1, 0.2, 1.0, 5.0, 1.1, 0.5, 0.1, 0.99};
+
+static int md_relax_init_state(sgpr_model *h)
+{
+    MdState &m = h->md;
+    double s[RLX_LEN] = {};
+    HIPCHK(hipMemcpy(s, m.rx_state.p, sizeof(s), hipMemcpyDeviceToHost));
+    s[RLX_DT] = m.rp.dt0; s[RLX_A] = m.rp.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
+    for (int k = 0; k < 9; k++) s[RLX_VC + k] = 0.0;
+    s[RLX_ALPHA] = s[RLX_BETA] = s[RLX_CD] = 0.0;
+    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.V.p, 0, sizeof(double) * 3 * (size_t)m.N));
+    return SGPR_OK;
+}
+
+extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_relax: call sgpr_md_begin first");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
+    if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
+    if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
+    if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
+    const double *fp = fire ? fire : RLX_ASE;
+    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
+        return fail(SGPR_E_INVALID, "sgpr_md_relax: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.N;
+    RelaxParams p = {};
+    HIPCHK(hipMemcpy(p.h0, m.cell.p, sizeof(p.h0), hipMemcpyDeviceToHost));
+    if (move_cell) {
+        if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_relax: a cell that moves must be periodic in all three directions");
+        if (!(fabs(rlx_det(p.h0)) > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: the cell is singular");
+    }
+    p.fmax2 = fmax * fmax;
+    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
+    double m6[6];
+    for (int k = 0; k < 6; k++) m6[k] = mask6 ? (mask6[k] != 0.0 ? 1.0 : 0.0) : 1.0;
+    const double M[9] = {m6[0], m6[5], m6[4], m6[5], m6[1], m6[3], m6[4], m6[3], m6[2]};
+    for (int k = 0; k < 9; k++) p.mask[k] = M[k];
+    p.cf = (double)N;
+    p.cell = move_cell ? 1 : 0;
+    // rings of RLX_RING slots, every slot a valid configuration from the start (what runs behind a halt evaluates stale slots)
+    std::vector<double> x0((size_t)3 * N);
+    HIPCHK(hipMemcpy(x0.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    if (m.X.alloc((size_t)3 * N * RLX_RING) || m.P.alloc((size_t)RLX_RING * (size_t)sgpr_packed_len(N)) || m.rx_state.alloc(RLX_LEN) ||
+        m.rx_ref.alloc((size_t)3 * N) || m.rx_cells.alloc((size_t)RLX_RING * RLX_CELL))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_relax: device allocation failed");
+    double slot[RLX_CELL] = {};
+    for (int k = 0; k < 9; k++) { slot[k] = p.h0[k]; slot[9 + k] = (k % 4 == 0) ? 1.0 : 0.0; }
+    for (int r = 0; r < RLX_RING; r++) {
+        HIPCHK(hipMemcpy(m.X.p + (size_t)3 * N * r, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.rx_cells.p + (size_t)RLX_CELL * r, slot, sizeof(slot), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(m.rx_ref.p, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    double s[RLX_LEN] = {};
+    for (int k = 0; k < 9; k++) s[RLX_XC + k] = (k % 4 == 0) ? p.cf : 0.0;
+    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    m.rp = p;
+    m.relax = true; m.relax_started = false; m.ring = RLX_RING;
+    m.cells.clear(); m.cells_first = 0;
+    return md_relax_init_state(h);
+}
+
+// optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (the reference's relax(clear_hist=True) behind a model update)
+extern "C" int sgpr_md_relax_reset(sgpr_model *h)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.relax) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: call sgpr_md_begin and sgpr_md_relax first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return md_relax_init_state(h);
+}
+
+// sgpr_md_run for a relaxation: every evaluation is the plain step (its own binning kernel, the plain last kernel) with
+// md_fire_kernel and md_fire_move_kernel behind it.  The halts — covloss gate (1), capacity overflow (2), convergence (3) — are
+// decided by md_fire_kernel on the evaluation itself, before anything moves: what the host has enqueued behind a halt (its
+// look-ahead) evaluates stale slots of the rings and changes nothing.  final_eval: the last evaluation moves nothing and leaves
+// the optimizer as it was.
+static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
+{
+    MdState &m = h->md;
+    HIPCHK(hipSetDevice(h->device));
+    {
+        bool same = h->N == m.N && h->rank == m.rank && h->world == m.world && (int)h->numbers.size() == m.N;
+        for (int i = 0; i < m.N && same; i++) same = h->numbers[i] == m.numbers[i];
+        for (int k = 0; k < 3 && same; k++) same = h->pbc[k] == (m.pbc[k] != 0);
+        if (!same) {
+            const int rb = sgpr_bind_system(h, m.N, m.numbers.data(), m.pbc, m.rank, m.world);
+            if (rb) return rb;
+        }
+    }
+    hipStream_t st = h->stream;
+    const int N = m.N, RG = RLX_RING;
+    const size_t plen = (size_t)sgpr_packed_len(N);
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    if (m.scal_rows < (size_t)nevals + 1) {
+        if (m.mark) (void)hipHostFree(m.mark);
+        if (m.scal_pin) (void)hipHostFree(m.scal_pin);
+        m.mark = nullptr; m.scal_pin = nullptr; m.scal_rows = 0;
+        if (m.scal_d.alloc((size_t)SGPR_MD_SCAL * ((size_t)nevals + 1), false) ||
+            hipHostMalloc((void **)&m.mark, sizeof(int) * ((size_t)nevals + 1), hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&m.mark_dev, m.mark, 0) != hipSuccess ||
+            hipHostMalloc((void **)&m.scal_pin, sizeof(double) * SGPR_MD_SCAL * ((size_t)nevals + 1), hipHostMallocDefault) != hipSuccess)
+            return fail(SGPR_E_NODEVICE, "sgpr_md_run: no memory for the scalar ring");
+        m.scal_rows = (size_t)nevals + 1;
+    }
+    HIPCHK(hipMemsetAsync(m.scal_d.p, 0, sizeof(double) * SGPR_MD_SCAL * ((size_t)nevals + 1), st));
+    memset(m.mark, 0, sizeof(int) * ((size_t)nevals + 1));
+    const int halt_none = 0x7fffffff;
+    m.halt_host[0] = halt_none; m.halt_host[1] = halt_none; m.halt_host[2] = halt_none;
+    HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    h->bin_identity = true;
+    struct Restore { sgpr_model *h; ~Restore() { h->bin_identity = false; h->pre_valid = false; h->step_grid = nullptr; } } restore{h};
+    if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
+    auto cell_of = [&](long long n) -> double * { return m.rx_cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
+    m.relax_started = true;
+    if (!h->warm) {
+        const int sw = (int)(m.t % RG);
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.t), m.P.p + plen * sw, st);
+        if (rc_) return rc_;
+        h->warm = true;
+    }
+    m.chain_ok = false;
+    h->lists_valid = false;
+    h->pre_valid = false;
+    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    const unsigned step0 = h->step_count;
+    const int LA = std::min(6, std::max(2, (int)lround(24576.0 / std::max(N, 1))));
+    const double gate = ediff > 0.0 ? ediff : 1e300;
+    int enq = 0, rc_ = SGPR_OK;
+    bool halted = false;
+    const volatile int *hh = m.halt_host;
+    for (int j = 0; j < nevals && !halted && !rc_; j++) {
+        if (j >= LA) {
+            const volatile int *mark = m.mark + (j - LA);
+            unsigned spins = 0;
+            while (*mark == 0 && hh[0] == halt_none && hh[1] == halt_none && hh[2] == halt_none) {
+                if ((++spins & 0x3fffu) == 0) {  // (a dead queue must not hang the host)
+                    const hipError_t q = hipStreamQuery(st);
+                    if (q == hipSuccess && *mark == 0) { rc_ = fail(SGPR_E_NODEVICE, "sgpr_md_run: the queue drained without evaluation %d reporting", j - LA); break; }
+                    if (q != hipSuccess && q != hipErrorNotReady) { rc_ = fail(SGPR_E_NODEVICE, "sgpr_md_run: %s", hipGetErrorString(q)); break; }
+                }
+            }
+            if (rc_) break;
+            if (hh[0] != halt_none || hh[1] != halt_none || hh[2] != halt_none) { halted = true; break; }
+        }
+        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG;
+        double *packed = m.P.p + plen * sl;
+        rc_ = enqueue_step(h, m.X.p + (size_t)3 * N * sl, cell_of(m.t + j), packed, st, nullptr);
+        if (rc_) break;
+        h->lists_valid = true;
+        const bool stay = final_eval && j == nevals - 1;
+        hipLaunchKernelGGL(md_fire_kernel, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p, (const double *)packed, (const int *)h->d_perm.p,
+                           (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host_dev,
+                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark_dev + j, stay ? 1 : 0);
+        if (!stay)
+            hipLaunchKernelGGL(md_fire_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell, (const double *)m.rx_state.p,
+                               (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.rx_ref.p, m.X.p + (size_t)3 * N * sn,
+                               (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j));
+        enq = j + 1;
+    }
+    if (rc_) { (void)hipStreamSynchronize(st); return rc_; }
+    if (scalars && enq > 0)
+        HIPCHK(hipMemcpyAsync(m.scal_pin, m.scal_d.p, sizeof(double) * SGPR_MD_SCAL * (size_t)enq, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    m.cells.assign((size_t)SGPR_MD_CELL * (size_t)enq, 0.0);
+    m.cells_first = m.t;
+    if (enq > 0) HIPCHK(hipMemcpy(m.cells.data(), m.cells_d.p, sizeof(double) * SGPR_MD_CELL * (size_t)enq, hipMemcpyDeviceToHost));
+    const int hv = std::min(std::min(m.halt_host[0], m.halt_host[1]), m.halt_host[2]);
+    int done = enq, code = 0;
+    if (hv != halt_none) {
+        const int k = hv - (int)step0;
+        if (k < 0 || k >= enq) return fail(SGPR_E_INVALID, "sgpr_md_run: inconsistent halt record (%d of %d)", k, enq);
+        code = m.halt_host[1] == hv ? 2 : (m.halt_host[0] == hv ? 1 : 3);
+        done = k + 1;
+        m.t += k;
+        if (code == 2) { h->warm = false; done -= 1; }
+    } else
+        m.t += final_eval ? enq - 1 : enq;
+    m.cells.resize((size_t)SGPR_MD_CELL * (size_t)std::max(done, 0));
+    if (scalars && done > 0) memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)done);
+    m.evaluated = code == 1 || code == 3 || (code == 0 && final_eval != 0);
+    *evals_done = done;
+    if (halt_code) *halt_code = code;
+    h->lists_valid = false;
+    return SGPR_OK;
+}
+
 // Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last
 // the integrator moves on with the next row of `noise` ([nevals][N][3] standard normal deviates, caller atom order; null:
 // velocity Verlet).  Stops at the first evaluation whose largest covloss reaches `ediff` (<= 0: never): *evals_done
@@ -3343,6 +3568,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_run: call sgpr_md_begin first");
     if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
+    if (m.relax) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
     HIPCHK(hipSetDevice(h->device));
     {   // whatever ran on the handle since sgpr_md_begin (a model update computes the training rows of stored frames and
         // trial models evaluate them: each rebinds the handle) — the run's own system is bound again before it goes on
@@ -3590,12 +3816,12 @@ extern "C" int sgpr_md_state(sgpr_model *h, double *positions, double *velocitie
         for (int i = 0; i < N; i++)
             for (int k = 0; k < 3; k++) positions[3 * (size_t)m.perm[i] + k] = buf[3 * (size_t)i + k];
     }
-    if (velocities_pre) {
-        HIPCHK(hipMemcpy(buf.data(), m.V.p + (size_t)3 * N * sl, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    if (velocities_pre) {   // (a relaxation: the optimizer's velocity of the atoms' coordinates, one slot)
+        HIPCHK(hipMemcpy(buf.data(), m.V.p + (size_t)3 * N * (m.relax ? 0 : sl), sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
         for (int i = 0; i < N; i++)
             for (int k = 0; k < 3; k++) velocities_pre[3 * (size_t)m.perm[i] + k] = buf[3 * (size_t)i + k];
     }
-    if (pending) *pending = (!m.nh && (m.t + which) > 0) ? 1 : 0;   // (every configuration but the start of the trajectory)
+    if (pending) *pending = (!m.nh && !m.relax && (m.t + which) > 0) ? 1 : 0;   // (every configuration but the start of the trajectory)
     if (m.nh && velocities_pre && (m.t + which) > 0) {
         // Nose-Hoover: what the integrator holds when it asks for the forces of configuration n is the centred velocity of
         // configuration n - 1 (ASE sets the momenta of a step after its force call); sgpr_md_velocities has v_n itself
@@ -3616,6 +3842,7 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     if (!h || !velocities) return fail(SGPR_E_INVALID, "sgpr_md_velocities: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_velocities: call sgpr_md_begin first");
+    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
     if (!m.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -92,6 +92,24 @@ struct NptParams {
     int pbc[3];
 };
 
+// FIRE relaxation on the device (sgpr_md_relax; md_relax.inc has the scheme)
+struct RelaxParams {
+    double fmax2;                                        // fmax^2
+    double dt0, maxstep, dtmax, finc, fdec, astart, fa;  // ase.optimize.FIRE's keywords
+    double nmin;
+    double mask[9];                                      // the six Voigt flags as a symmetric matrix of zeros and ones
+    double h0[9];                                        // the cell of sgpr_md_begin
+    double cf;                                           // ASE's cell_factor: N
+    int cell;                                            // 1: the cell moves
+};
+
+// the optimizer's state in device memory (doubles)
+enum { RLX_DT = 0, RLX_A = 1, RLX_NSTEPS = 2, RLX_FRESH = 3, RLX_XC = 4 /* [9] c D */, RLX_VC = 13 /* [9] its velocity */,
+       RLX_ALPHA = 22, RLX_BETA = 23, RLX_CD = 24, RLX_LEN = 32 };
+#define RLX_CELL 18   // doubles per slot of the ring of cells: h[9], D[9]
+#define RLX_RING 9    // slots of the rings of positions / results / cells: the host runs at most 6 evaluations ahead, and what is
+                      // enqueued behind a halt (it evaluates stale slots, moves nothing) must not land on configurations k, k - 1
+
 // Bin populations sit SGPR_BIN_STRIDE ints apart: one counter per 128-byte line.  Packed, the ~350 counters of a 4096-atom
 // frame are eleven lines, and the returning atomics of the binning (one per atom, device scope: they execute at the
 // memory side, one after the other per line) were most of the binning kernel's 7 us.

@@ -615,6 +615,34 @@ class SGPRModel:
             self._md["npt"] = True
         self._md["t"] = 0
 
+    def relax_begin(self, numbers, positions, cell, pbc, fmax, cell_relax=False, mask=None, **fire):
+        """State of a FIRE relaxation into device memory (sgpr_md_relax: ase/optimize/fire.py on the positions and, with
+        cell_relax, on the cell through ase.constraints.UnitCellFilter(atoms, mask=mask)'s coordinates; workloads.fire_relax is
+        the host twin).  fire: dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (ASE's defaults).  md_run / md_state / md_cells /
+        md_end then serve the relaxation as they serve an MD run: md_run's halt code 3 = converged at its last row, nothing
+        moved; its rows carry max |G_row|^2, G.v, dt and a in the columns 12..15; md_cells returns (cells, D)."""
+        from .workloads import FIRE_DEFAULTS
+        unknown = set(fire) - set(FIRE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"relax_begin: unknown FIRE keywords {sorted(unknown)}")
+        numbers = i32(numbers)
+        N = len(numbers)
+        self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=np.ones(N), hdt=0.0, relax=True, npt=True)
+        self.generation += 1
+        lib = _lib.load()
+        check(lib.sgpr_md_begin(self._h, N, ptr(numbers), ptr(f64(positions).reshape(N, 3)), ptr(self._md["cell"]),
+                                ptr(i32(np.asarray(pbc, bool).astype(np.int32))), None, None, 1.0, 0.0, 0.0))
+        par = dict(FIRE_DEFAULTS)
+        par.update(fire)
+        fp = f64([par[k] for k in ("dt", "maxstep", "dtmax", "nmin", "finc", "fdec", "astart", "fa")])
+        mk = None if mask is None else f64(np.asarray(mask, float).reshape(6))
+        check(lib.sgpr_md_relax(self._h, float(fmax), ptr(fp), int(bool(cell_relax)), ptr(mk)))
+        self._md["t"] = 0
+
+    def relax_reset(self):
+        """optimizer.initialize() of the relaxation on the device: v = 0; dt, a, nsteps back to their start."""
+        check(_lib.load().sgpr_md_relax_reset(self._h))
+
     def md_deviates(self, t_first, count):
         out = np.empty((int(count), self._md["N"], 3))
         check(_lib.load().sgpr_md_deviates(self._h, int(t_first), int(count), ptr(out)))
@@ -624,7 +652,8 @@ class SGPRModel:
         """Evaluate `nevals` configurations starting with the current one, integrating between them on the device
         (noise: [nevals, N, 3] standard normal deviates or None).  Returns (scalars [done, 16], halt code): code 1 =
         the last row's largest covloss reached ediff and the state is that configuration (calculator/active.py:492-499),
-        2 = a neighbour capacity overflowed at evaluation `done` (repeat the call)."""
+        2 = a neighbour capacity overflowed at evaluation `done` (repeat the call), 3 (a relaxation, relax_begin) = the last
+        row's configuration has converged and is the state."""
         N = self._md["N"]
         if noise is not None:
             noise = f64(noise).reshape(-1, N, 3)
@@ -637,7 +666,7 @@ class SGPRModel:
         if self._md.get("npt"):   # (where the state is now: sgpr_md_run's rules)
             t0 = self._md["t"]
             self._md["run"] = (t0, done.value)
-            self._md["t"] = t0 + (done.value - 1 if (code.value == 1 or (code.value == 0 and final)) else done.value)
+            self._md["t"] = t0 + (done.value - 1 if (code.value in (1, 3) or (code.value == 0 and final)) else done.value)
         return sc[:done.value], code.value
 
     def md_cells(self, first=None, count=None):
@@ -665,13 +694,15 @@ class SGPRModel:
         if self._md.get("npt"):   # the cell these positions belong to, and its strain rate
             c, e = self.md_cells(self._md["t"] + which, 1)
             cell = out["cell"] = f64(c[0])
-            out["eta"] = e[0]
+            out["D" if self._md.get("relax") else "eta"] = e[0]
         if results:
             F = packed[:3 * N].reshape(N, 3).copy()
             stress = np.zeros(6)
             check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[4 * N + 1:4 * N + 10])), ptr(cell), ptr(stress)))
             out.update(forces=F, beta=packed[3 * N:4 * N].copy(), energy=float(packed[4 * N]), stress=stress)
-            if self._md.get("nh"):   # Nose-Hoover: the centred velocity of this configuration (v is the one before it)
+            if self._md.get("relax"):
+                out["velocities"] = v.copy()
+            elif self._md.get("nh"):   # Nose-Hoover: the centred velocity of this configuration (v is the one before it)
                 vn = np.empty((N, 3))
                 check(_lib.load().sgpr_md_velocities(self._h, ptr(vn)))
                 out["velocities"] = vn

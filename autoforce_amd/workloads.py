@@ -418,6 +418,147 @@ def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         qp, q = q, qn
 
 
+# ---- FIRE relaxation of positions (and cell) in the device's operations (fire_relax; md_relax.inc: md_fire_kernel and
+# md_fire_move_kernel)
+FIRE_DEFAULTS = dict(dt=0.1, maxstep=0.2, dtmax=1.0, nmin=5, finc=1.1, fdec=0.5, astart=0.1, fa=0.99)   # ase/optimize/fire.py, ASE 3.22
+
+
+def _m3_inv(d):
+    """Inverse of a general 3 x 3 matrix in closed form: cofactors over the determinant (true divisions)."""
+    c00 = d[1][1] * d[2][2] - d[1][2] * d[2][1]
+    c01 = d[1][0] * d[2][2] - d[1][2] * d[2][0]
+    c02 = d[1][0] * d[2][1] - d[1][1] * d[2][0]
+    det = (d[0][0] * c00 - d[0][1] * c01) + d[0][2] * c02
+    return [[c00 / det, (d[0][2] * d[2][1] - d[0][1] * d[2][2]) / det, (d[0][1] * d[1][2] - d[0][2] * d[1][1]) / det],
+            [-c01 / det, (d[0][0] * d[2][2] - d[0][2] * d[2][0]) / det, (d[0][2] * d[1][0] - d[0][0] * d[1][2]) / det],
+            [c02 / det, (d[0][1] * d[2][0] - d[0][0] * d[2][1]) / det, (d[0][0] * d[1][1] - d[0][1] * d[1][0]) / det]]
+
+
+def _m3_mul_t(a, b):
+    """a b^T, every entry (a_r0 b_c0 + a_r1 b_c1) + a_r2 b_c2."""
+    return [[(a[r][0] * b[c][0] + a[r][1] * b[c][1]) + a[r][2] * b[c][2] for c in range(3)] for r in range(3)]
+
+
+def _cell_volume(c):
+    """|det| of a cell as sgpr_stress_from_virial takes it."""
+    return abs(c[0][0] * (c[1][1] * c[2][2] - c[1][2] * c[2][1]) - c[0][1] * (c[1][0] * c[2][2] - c[1][2] * c[2][0])
+               + c[0][2] * (c[1][0] * c[2][1] - c[1][1] * c[2][0]))
+
+
+def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mask=None, species=None, reset_at=(), **fire):
+    """FIRE (ase/optimize/fire.py, ASE 3.22, LGPL, as cl/relax.py::FIRE restates it) on the positions — and, with cell_relax,
+    on the cell through ase.constraints.UnitCellFilter(atoms, mask=mask) (cl/relax.py::UnitCellFilter) — in numpy around any
+    calculator with the ASE surface, written by evaluation index in the operations and the summation order of the device loop
+    (sgpr_md_relax: md_fire_kernel and md_fire_move_kernel, md_relax.inc): its host twin, bit for bit.  The state is the
+    generalised coordinate vector X = [r ; c D] (r: positions referred to the cell h0 of the start, D: the deformation gradient,
+    c = N) and its velocity.  Per evaluation n, with G = [F D ; (W D^-T o M) / c], W = -V stress:
+        max over rows |G_row|^2 < fmax^2:  converged, nothing moves
+        first evaluation (or the first after a reset):  alpha = 0,  beta = dt
+        P = G.v > 0:   alpha = 1 - a,  beta = a |v| / |G| + dt   (then, if nsteps > nmin: dt = min(dt finc, dtmax), a *= fa — ASE
+                       raises dt BEFORE the step that uses it; nsteps += 1)
+        else:          alpha = 0,  a = astart,  dt *= fdec,  nsteps = 0,  beta = dt
+        v = alpha v + beta G;  |v|^2 = alpha^2 v.v + 2 alpha beta G.v + beta^2 G.G  (closed form: no second reduction);
+        X += s dt v  with  s = maxstep / (dt |v|) when dt |v| > maxstep, else 1
+    — ASE's `(1 - a) v + a |v| / |G| G` followed by `v += dt G` with the two multiples of G added first: the order of rounding
+    only.  Dots run over all 3N (+ 9) components: the atoms' part through _device_order_sum in the library's species-sorted
+    order (`species`: the model's table), the three cell rows added behind it.  No BLAS call.  reset_at: evaluation indices in
+    front of which the optimizer is re-initialised (optimizer.initialize(): v = 0, dt, a, nsteps as at the start).
+      Yields a dict per evaluated configuration: n, energy, positions, cell, D, gmax2 (largest |G_row|^2), P (G.v; 0 for a
+    first evaluation), dt and a as used for the move out of this configuration (as they stand when it has converged), nsteps
+    behind that move, converged.  The generator ends behind a converged configuration."""
+    from .ase_shim import Atoms
+    p = dict(FIRE_DEFAULTS)
+    p.update(fire)
+    N = len(numbers)
+    cf = float(N)
+    h0 = [[float(v) for v in row] for row in np.asarray(cell, float).reshape(3, 3)]
+    if mask is None:
+        mask = [1.0] * 6
+    mk6 = [1.0 if float(v) != 0.0 else 0.0 for v in np.asarray(mask, float).reshape(6)]
+    M = [[mk6[0], mk6[5], mk6[4]], [mk6[5], mk6[1], mk6[3]], [mk6[4], mk6[3], mk6[2]]]
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    eye = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    r = np.array(pos, float)
+    x = r.copy()
+    Xc = [[cf * eye[a][b] for b in range(3)] for a in range(3)]     # the cell rows of X: c D
+    D, h = eye, h0
+    v, vc = np.zeros_like(r), [[0.0] * 3 for _ in range(3)]
+    dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
+    fmax2 = float(fmax) * float(fmax)
+
+    def dot(u, w, uc, wc):
+        t = u * w
+        s = _device_order_sum(((t[:, 0] + t[:, 1]) + t[:, 2])[order])
+        if cell_relax:
+            rows = [(uc[k][0] * wc[k][0] + uc[k][1] * wc[k][1]) + uc[k][2] * wc[k][2] for k in range(3)]
+            s = s + ((rows[0] + rows[1]) + rows[2])
+        return s
+
+    for n in range(steps + 1):
+        if n in reset_at:
+            v, vc = np.zeros_like(r), [[0.0] * 3 for _ in range(3)]
+            dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
+        at = Atoms(numbers, x, np.array(h), pbc)
+        at.calc = calc
+        F, E = np.asarray(at.get_forces(), float), float(at.get_potential_energy())
+        Gc = [[0.0] * 3 for _ in range(3)]
+        if cell_relax:
+            s6 = [float(t) for t in np.asarray(at.get_stress(), float)]
+            vol = _cell_volume(h)
+            w6 = [-(vol * t) for t in s6]
+            W = [[w6[0], w6[5], w6[4]], [w6[5], w6[1], w6[3]], [w6[4], w6[3], w6[2]]]
+            T = _m3_mul_t(W, _m3_inv(D))
+            Gc = [[(T[a_][b] * M[a_][b]) / cf for b in range(3)] for a_ in range(3)]
+            G = _row_mul(F, D)
+        else:
+            G = F
+        g2 = G * G
+        g2 = (g2[:, 0] + g2[:, 1]) + g2[:, 2]
+        gmax2 = float(g2.max()) if N else 0.0
+        if cell_relax:
+            gmax2 = max(gmax2, max((Gc[k][0] * Gc[k][0] + Gc[k][1] * Gc[k][1]) + Gc[k][2] * Gc[k][2] for k in range(3)))
+        P = 0.0 if fresh else dot(G, v, Gc, vc)
+        out = dict(n=n, energy=E, positions=x, cell=np.array(h), D=np.array(D), gmax2=gmax2, P=P)
+        if gmax2 < fmax2:
+            out.update(dt=dt, a=a, nsteps=nsteps, converged=True)
+            yield out
+            return
+        GG = dot(G, G, Gc, Gc)
+        vv = 0.0
+        if fresh:
+            alpha, beta = 0.0, dt
+            fresh = False
+        elif P > 0.0:
+            vv = dot(v, v, vc, vc)
+            alpha = 1.0 - a
+            gamma = (a * np.sqrt(vv)) / np.sqrt(GG)
+            if nsteps > p["nmin"]:
+                dt = min(dt * p["finc"], p["dtmax"])
+                a = a * p["fa"]
+            nsteps += 1
+            beta = gamma + dt
+        else:
+            alpha, a, nsteps = 0.0, float(p["astart"]), 0
+            dt = dt * p["fdec"]
+            beta = dt
+        nv2 = ((alpha * alpha) * vv + (2.0 * (alpha * beta)) * P) + (beta * beta) * GG
+        drn = dt * float(np.sqrt(nv2))
+        cd = dt * (p["maxstep"] / drn) if drn > p["maxstep"] else dt
+        out.update(dt=dt, a=a, nsteps=nsteps, converged=False)
+        yield out
+        v = alpha * v + beta * G
+        r = r + cd * v
+        if cell_relax:
+            vc = [[alpha * vc[a_][b] + beta * Gc[a_][b] for b in range(3)] for a_ in range(3)]
+            Xc = [[Xc[a_][b] + cd * vc[a_][b] for b in range(3)] for a_ in range(3)]
+            D = [[Xc[a_][b] / cf for b in range(3)] for a_ in range(3)]
+            h = _m3_mul_t(h0, D)
+            x = _row_mul(r, [[D[b][a_] for b in range(3)] for a_ in range(3)])
+        else:
+            x = r
+
+
 def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None,
                         ediff=0.0, chunk=256, on_halt=None, device_rng=False):
     """langevin_nvt with the state in device memory (SGPRModel.md_begin / md_run): same scheme, same random stream

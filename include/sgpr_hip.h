@@ -390,6 +390,28 @@ int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, double *out);
  *                 last sgpr_md_run, and the current one. */
 int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *externalstress, const double *mask, double frac_traceless);
 int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out);
+/* A relaxation instead of dynamics (between sgpr_md_begin and the first sgpr_md_run; no thermostat, no barostat): FIRE
+ * (ase/optimize/fire.py, ASE 3.22) on the positions and, with move_cell, on the cell through the generalised coordinates of
+ * ase.constraints.UnitCellFilter(atoms, mask) — what the reference's relax(cell=True) minimises (cl/relax.py:45-48) — with the
+ * state in device memory between model updates.  With h0 the cell of sgpr_md_begin, D the deformation gradient, c = N:
+ *     h = h0 D^T,  x = r D^T,  X = [ r ; c D ],  G = [ F D ; (W D^-T o M) / c ],  W = -V stress
+ * and FIRE acting on (X, G) over all 3N (+ 9) components.  sgpr_md_begin's masses (NULL is accepted), velocities, dt, friction
+ * and kT are ignored.  fire[8] = dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (NULL: ASE's 0.1, 0.2, 1.0, 5, 1.1, 0.5, 0.1,
+ * 0.99); mask6: zeros and ones for the Voigt components xx yy zz yz xz xy of the cell (NULL: all ones).
+ * sgpr_md_run (its noise is ignored) evaluates and moves; the covloss gate (halt code 1) and a capacity overflow (2) work as in
+ * an MD run, and convergence — max over the N (+ 3) rows of |G_row|^2 < fmax^2 — is halt code 3: *evals_done counts the
+ * converged evaluation as the last one and the state IS that configuration, nothing moved.  final_eval: the last evaluation
+ * of the call moves nothing and leaves the optimizer as it was.
+ * scalars[.][0..11] as in an MD run; [12] = max |G_row|^2, [13] = G.v (0 for the optimizer's first evaluation), [14] = dt and
+ * [15] = a as used for the move out of this evaluation (as they stand when nothing moves).
+ * sgpr_md_cells returns h[9] and, in the place of eta, D[9] per configuration; sgpr_md_state the positions in the
+ * configuration's own cell and, as velocities_pre, the optimizer's velocity of the atoms' coordinates (pending = 0).
+ * SGPR_E_INVALID: a thermostat or barostat set, a run that has started, fmax <= 0, a FIRE parameter out of range, move_cell
+ * with a direction that is not periodic or a singular cell.  SGPR_E_UNSUPPORTED: a run begun on more than one rank.  The handle
+ * goes on working after any of them.
+ * sgpr_md_relax_reset  optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (between two sgpr_md_run calls). */
+int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6);
+int sgpr_md_relax_reset(sgpr_model *h);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
