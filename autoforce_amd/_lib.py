@@ -79,6 +79,7 @@ SIGNATURES = {
     "sgpr_md_cells": (C.c_int, [_vp, _i64, C.c_int, _vp]),
     "sgpr_md_relax": (C.c_int, [_vp, _dbl, _vp, C.c_int, _vp]),
     "sgpr_md_relax_reset": (C.c_int, [_vp]),
+    "sgpr_md_fix": (C.c_int, [_vp, _vp]),
     "sgpr_sync_check": (C.c_int, [_vp, _vp]),
     "sgpr_comm_unique_id": (C.c_int, [_vp]),
     "sgpr_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

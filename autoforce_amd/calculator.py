@@ -504,6 +504,25 @@ class ActiveCalculator(Calculator):
             return EPS
         return float(min(self._ediff_lb.values))
 
+    @staticmethod
+    def constraint_mask(atoms):
+        """atoms.constraints as the held-component mask of the device loops ([N, 3] booleans, True = held; None without
+        constraints).  Derived from what the constraints DO — each one's adjust_forces on an array of ones, the zeros it leaves —,
+        not from their attributes (FixCartesian's stored mask changed its meaning between ASE versions).  Only
+        ase.constraints.FixAtoms and FixCartesian (by class name: ASE's, or ase_shim's) hold Cartesian components of single
+        atoms; any other kind couples atoms or directions and raises NotImplementedError."""
+        cons = list(getattr(atoms, "constraints", None) or ())
+        if not cons:
+            return None
+        ones = np.ones((len(atoms), 3))
+        for c in cons:
+            if type(c).__name__ not in ("FixAtoms", "FixCartesian"):
+                raise NotImplementedError(f"run_md / run_relax hold atoms and Cartesian components (FixAtoms, FixCartesian); with a "
+                                          f"{type(c).__name__} in atoms.constraints, drive calculate() from an ase.md / ase.optimize "
+                                          f"object as theforce/cl/md.py and cl/relax.py do")
+            c.adjust_forces(atoms, ones)
+        return ones == 0.0
+
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
                tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
@@ -527,7 +546,14 @@ class ActiveCalculator(Calculator):
         moving cell of cl/md.py:131-166 inside the device loop (SGPRModel.md_begin).  atoms.cell is set wherever
         atoms.positions are — sync points, a halted configuration before its calculate(), the end —, to the cell of THAT
         configuration.  The cell must be upper triangular (npt.make_cell_upper_triangular).  Host loop:
-        workloads.npt_moving_cell."""
+        workloads.npt_moving_cell.
+        atoms.constraints: FixAtoms and FixCartesian are honoured inside the loop (constraint_mask -> SGPRModel.md_begin(fixed=);
+        host loops: the twins' fixed=): the integrator sees F = 0 on a held component — self.results["forces"] stay the model's
+        own, zeroing them is atoms.get_forces()' business —, its velocity is exactly 0 (the caller's value is dropped, as
+        set_momenta does), it receives no noise and keeps its coordinate bit for bit.  Temperatures (the log line, the yield) are
+        over the g = 3N - n_fixed remaining degrees of freedom, as atoms.get_temperature(); Nose-Hoover uses
+        tfact = 2 / (g kT ttime^2) and K0 = g kT / 2, the project's own definition (ase.md.npt.NPT takes no constraints).  Not
+        with a barostat; any other constraint kind: NotImplementedError."""
         from .ase_shim import kB
         from .workloads import FS, MASS, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         nh = tdamp_fs is not None
@@ -544,12 +570,16 @@ class ActiveCalculator(Calculator):
                     atoms.cell = np.array(st["cell"], float)
             atoms.positions = st["positions"]
             atoms.set_velocities(st[vkey])
-        if len(getattr(atoms, "constraints", None) or ()):
-            # (neither integrator of this method knows ASE's constraints: an ASE dynamics object around calculate() does)
-            raise NotImplementedError("run_md integrates unconstrained atoms; with atoms.constraints set, drive calculate() "
-                                      "from an ase.md dynamics object as theforce/cl/md.py does")
+        fx = self.constraint_mask(atoms)
+        if fx is not None and not fx.any():
+            fx = None
+        if fx is not None and npt:
+            raise NotImplementedError("run_md: atoms.constraints with a barostat (pfactor): the moving-cell dynamics run "
+                                      "unconstrained; drive calculate() from an ASE dynamics object instead")
+        hold = {} if fx is None else dict(fixed=fx)
         numbers, pos, cell, pbc = self._system(atoms)
         N = len(numbers)
+        dof = 3 * N if fx is None else 3 * N - int(fx.sum())   # (temperatures: sum m v^2 / (dof kB))
         on_device_rng = rng is None and friction > 0.0 and not nh
         rng = np.random.default_rng(seed) if rng is None else rng
         if getattr(atoms, "_masses", "ase") is None:  # (the stand-in Atoms without masses; ase.Atoms knows its own)
@@ -559,6 +589,11 @@ class ActiveCalculator(Calculator):
             masses = np.asarray(atoms.get_masses(), float)
         vel = atoms.get_velocities()
         vel = np.zeros((N, 3)) if vel is None else np.asarray(vel, float)
+        if fx is not None:
+            # (a held component has velocity 0 from the start, the caller's value is dropped: a first calculate() on the host
+            # sees — and logs — the velocities the loops start from)
+            vel = np.where(fx, 0.0, vel)
+            atoms.set_velocities(vel)
         first_on_host = self._needs_seed() or not self.md_on_device_ok()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -571,8 +606,8 @@ class ActiveCalculator(Calculator):
             atoms.get_forces()
             if not self.md_on_device_ok():
                 loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro) if npt else
-                        nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel) if nh else
-                        langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng))
+                        nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold) if nh else
+                        langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold))
                 for st, E, T, _, p, v, *rest in loop:
                     put(dict(positions=p, velocities=v, cell=rest[0] if npt else None), "velocities")
                     yield st, E, T, bool(self.updated), _
@@ -581,7 +616,7 @@ class ActiveCalculator(Calculator):
         kT = kB * temperature_K
         self._peer_fit(eng, N)
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
-                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro)
+                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold)
         # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
@@ -610,10 +645,10 @@ class ActiveCalculator(Calculator):
                     # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a
                     # moving cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
                     ke_line = r[13] if (not npt or ke_before is None) else ke_before
-                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), float(ke_line / (3 * N * kB)), float(r[11]), "")))
+                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]), "")))
                     self.step += 1
                 ke_before = r[12]
-                out.append((done, float(r[0]), float(r[12] / (3 * N * kB)), upd, wall))
+                out.append((done, float(r[0]), float(r[12] / (dof * kB)), upd, wall))
                 done += 1
             self._log_lines(lines)
             if sync_every and out and out[-1][0] % sync_every == 0 and code != 1:
@@ -642,11 +677,17 @@ class ActiveCalculator(Calculator):
         model was updated), and the run goes on with the new model.  At most `steps` moves.  atoms.positions and atoms.cell are
         current after every update and at the end, where self.results are those of the final configuration.  fire: the keywords
         of ase.optimize.FIRE.  Falls back to the host loop (cl/relax.py::FIRE and UnitCellFilter around calculate()) where
-        md_on_device_ok() says no or the run is sharded.  Returns dict(converged, steps, evaluations)."""
+        md_on_device_ok() says no or the run is sharded.  Returns dict(converged, steps, evaluations).
+        atoms.constraints: FixAtoms and FixCartesian are honoured inside the loop (constraint_mask ->
+        SGPRModel.relax_begin(fixed=); the host loop through the atoms' own set_positions / get_forces): the optimizer sees F = 0
+        on a held component and convergence is judged on the free ones — self.results["forces"] stay the model's own —; a held
+        coordinate keeps its bits at constant cell, and with cell=True keeps its undeformed coordinate while x follows the cell,
+        as FixAtoms inside UnitCellFilter.  Any other constraint kind: NotImplementedError."""
         from .cl.relax import FIRE, UnitCellFilter, force_max
-        if len(getattr(atoms, "constraints", None) or ()):
-            raise NotImplementedError("run_relax moves unconstrained atoms; with atoms.constraints set, drive calculate() from an "
-                                      "ase.optimize optimizer as theforce/cl/relax.py does")
+        fx = self.constraint_mask(atoms)
+        if fx is not None and not fx.any():
+            fx = None
+        hold = {} if fx is None else dict(fixed=fx)
 
         def put(st):
             if cell:
@@ -675,7 +716,7 @@ class ActiveCalculator(Calculator):
                 return dict(converged=force_max(forces) < fmax, steps=n, evaluations=n + 1)
         numbers, pos, cell0, pbc = self._system(atoms)
         eng = self.engine
-        eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **fire)
+        eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **hold, **fire)
         done, skip_gate, converged = 0, first_on_host, False
         batch = min(8, chunk)
         while done <= steps and not converged:

@@ -71,7 +71,9 @@ class UnitCellFilter:
         n = len(self.atoms)
         new = np.asarray(new, float)
         D = new[n:] / self.cell_factor
-        self.atoms.set_cell(self.orig_cell @ D.T, scale_atoms=False)
+        # (scale_atoms, as ASE does: atoms held by a constraint follow the cell — their undeformed coordinate is what stays —;
+        # without constraints the positions are overwritten in full below and the scaling would be work for nothing)
+        self.atoms.set_cell(self.orig_cell @ D.T, scale_atoms=bool(len(getattr(self.atoms, "constraints", None) or ())))
         self.atoms.set_positions(new[:n] @ D.T)
 
     def get_forces(self):
@@ -232,8 +234,9 @@ def _optimizer(atoms, algo, cell, mask, trajectory, master, clear_hist=False):
     calc = atoms.calc
     # FIRE is per-atom arithmetic and three global sums: it runs inside the device loop where the calculator can hand the loop
     # over (BFGS, the default, needs a dense Hessian's eigen-decomposition per step and stays on the host)
+    # (atoms.constraints: FixAtoms and FixCartesian are held inside the device loop; any other kind stays with the host optimizer)
     if algo == "FIRE" and hasattr(calc, "run_relax") and hasattr(calc, "md_on_device_ok") and (calc.md_on_device_ok() or calc._needs_seed()) \
-            and not len(getattr(atoms, "constraints", None) or ()):
+            and all(type(c).__name__ in ("FixAtoms", "FixCartesian") for c in (getattr(atoms, "constraints", None) or ())):
         return _DeviceRunner(atoms, calc, cell, mask, trajectory, master, clear_hist)
     try:
         from ase import optimize

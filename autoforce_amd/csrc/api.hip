@@ -201,6 +201,13 @@ struct MdState {
     DevBuf<double> rx_state;       // [RLX_LEN] the optimizer's scalars, the cell rows of X and their velocity, the move's coefficients
     DevBuf<double> rx_ref;         // [N][3] positions referred to the first cell (r = x D^-T), sorted order; their velocity is V's slot 0
     DevBuf<double> rx_cells;       // [RLX_RING][RLX_CELL] cell and deformation gradient by evaluation index % RLX_RING
+    // held components (sgpr_md_fix): the mask in sorted atom order, on the device and here; n_fixed = 0: nothing is held and
+    // every launch is the one of a run without a mask
+    bool started = false;          // sgpr_md_run has been called since sgpr_md_begin
+    int n_fixed = 0;
+    DevBuf<unsigned char> fixed;   // [N][3]
+    std::vector<unsigned char> fixed_sorted;
+    const unsigned char *fix() const { return n_fixed ? fixed.p : nullptr; }
 };
 
 struct sgpr_model {
@@ -529,6 +536,9 @@ struct FinNext {
     const struct NptSlot *npt_cur, *npt_next;
     const double *q_cur, *q_prev;
     double *q_next;
+    // held components (sgpr_md_fix; finalize_next_kernel<4>, shard_next_kernel<4>): [N][3] sorted order, nonzero = the
+    // integrator sees F = 0 there, draws no noise, keeps v = 0 and hands the coordinate on as it is (null: nothing is held)
+    const unsigned char *fixed;
 };
 
 struct FinArgs {
@@ -1055,6 +1065,10 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 // lanes was most of the time.  Lane l of a row holds the pair slots l, l + 16, l + 32, l + 48 (slot s >= 64 adds into the
 // value of slot s mod 64, as before): the row sum of value j is the sum over row j of the wave-per-atom form, and the four
 // are combined as fin_wave_sum combines its rows — the same bits, beta's covloss partials alike.
+//   MODE 4 (the template parameter: FinNext::mode stays 2) is MODE 2 with held components (sgpr_md_fix: FinNext::fixed, a byte
+// per component requested with mass and sigma): the integrator of a held component sees F = 0 and no noise, its velocity is 0
+// and its next coordinate is the current one, selected explicitly — workloads.langevin_nvt / nose_hoover_nvt with fixed=.  The
+// forces written to `packed` stay the model's.  Its own instantiation: runs without a mask launch MODE 2 as it is.
 //   MODE 3 (the template parameter: FinNext::mode stays 2) is MODE 2 with a moving cell (md_npt.inc): the integrator works on scaled coordinates, with 3 x 3 matrices that
 // md_npt_kernel left behind the previous evaluation (wave-uniform addresses, a column per lane, requested with everything
 // else); the atom is binned in the grid of the NEXT cell and tested against the binning kernel's affine rebuild rule.  Its own
@@ -1063,6 +1077,7 @@ template <int MODE>
 __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
 {
     const int tid = threadIdx.x, b = blockIdx.x, nA = gridDim.x - 13;
+    constexpr bool MD = MODE == 2 || MODE == 4;   // the constant-cell integrator (4: with held components)
     const FinNext &x = f.nx;
     const int halt_w = MODE >= 2 ? *x.halt : 0x7fffffff;
     if (b >= nA) {
@@ -1110,10 +1125,11 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     double fs = f.Fself[3 * (size_t)ia + l3];
     // the atom this row BINS: MODE 1: caller atom number i (sorted index ib = iperm[i]); MODE 2: sorted atom i itself
     const int ib = MODE == 1 ? x.iperm[ia] : ia;
+    const bool held = MODE == 4 ? x.fixed[3 * (size_t)ia + l3] != 0 : false;   // (a byte in the same round trip as mass and sigma)
     const int slot_b = MODE == 1 ? x.cslot[ia] : slot_i;
     double xc = 0.0, p0 = 0.0, vc = 0.0, ms = 1.0, sg = 0.0, nz = 0.0, xn = 0.0;
     if (MODE == 1) xn = x.pos_in[3 * (size_t)ia + l3];
-    if (MODE == 2) {
+    if (MD) {
         xc = x.x_cur[3 * (size_t)ia + l3];
         p0 = f.pos0[3 * (size_t)ia + l3];
         vc = x.v_cur[3 * (size_t)ia + l3];
@@ -1122,7 +1138,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         nz = x.noise ? x.noise[3 * (size_t)ia + l3] : 0.0;   // (wave-uniform condition)
     }
     double xpv = 0.0, zeta = 0.0;
-    if (MODE == 2 && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (wave-uniform condition)
+    if (MD && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (wave-uniform condition)
     // MODE 3: q_n, q_(n-1), and column l3 of the matrices: h_n^-1, B - 1, (B + 1)^-1, h_n, h_(n+1), the two affine maps
     double qc = 0.0, qp = 0.0, c_hinv[3], c_bm1[3], c_bp1[3], c_h[3], c_hn[3], c_ak[3], c_ar[3], thr2_k = 0.0, thr2_r = 0.0;
     if (MODE == 3) {
@@ -1259,28 +1275,32 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_now[3 * (size_t)i + lane] = vnow;
         }
-    } else if (MODE == 2 && x.nh) {
+    } else if (MD && x.nh) {
         if (lane < 3) {
-            const double vnow = md_nh_advance(x, Fv, ms, xc, vc, xpv, zeta, xn);
+            // (a held component: F = 0 for the integrator, then the coordinate as it is and v = 0, selected — not computed)
+            double vnow = md_nh_advance(x, held ? 0.0 : Fv, ms, xc, vc, xpv, zeta, xn);
+            if (held) { xn = xc; vnow = 0.0; }
             ke = ms * (vnow * vnow);
             kp = ke;
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_now[3 * (size_t)i + lane] = vnow;
         }
-    } else if (MODE == 2 && lane < 3) {
+    } else if (MD && lane < 3) {
         // BAOAB, exactly the operations (and their order) of workloads.langevin_nvt: no contraction into fused
         // multiply-adds, a true division
 #pragma clang fp contract(off)
-        const double kick = __ddiv_rn(x.hdt * Fv, ms);
+        const double kick = __ddiv_rn(x.hdt * (held ? 0.0 : Fv), ms);
         double v = vc;
         if (x.pending) v = v + kick;       // closes step s: the velocity an observer sees at step s
         ke = ms * (v * v);
         kp = ms * (vc * vc);               // ... and the one the calculator is handed with the positions (its log line)
         const double v2 = v + kick;        // B
         const double x1 = xc + x.hdt * v2; // A
-        if (!x.noise && x.seed != 0ull && sg != 0.0) nz = md_deviate(x.seed, x.t_index, c, lane);
-        const double v3 = x.c1 * v2 + sg * nz;  // O
+        if (!x.noise && x.seed != 0ull && sg != 0.0 && !held) nz = md_deviate(x.seed, x.t_index, c, lane);
+        if (held) nz = 0.0;                // (no noise on a held component)
+        double v3 = x.c1 * v2 + sg * nz;   // O
         xn = x1 + x.hdt * v3;              // A
+        if (held) { xn = xc; v3 = 0.0; }   // (selected, not computed)
         x.x_next[3 * (size_t)i + lane] = xn;
         x.v_next[3 * (size_t)i + lane] = v3;
     }
@@ -1570,6 +1590,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.halt.release();
         m.zeta.release();
         m.npt_ring.release(); m.Q.release(); m.cells_d.release();
+        m.fixed.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
         for (auto b : tb) b->release();
         h->d_panel_cnt.release();
@@ -2453,6 +2474,7 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
             // the consumer of a sharded step's exchange (peer.inc): totals, the next positions, the next step's bins
             const dim3 gs((std::max(N, 1) + 63) / 64 + 3);
             if (nx->mode == 1) hipLaunchKernelGGL(shard_next_kernel<1>, gs, dim3(256), 0, st, f, *consume);
+            else if (nx->md.fixed) hipLaunchKernelGGL(shard_next_kernel<4>, gs, dim3(256), 0, st, f, *consume);
             else hipLaunchKernelGGL(shard_next_kernel<2>, gs, dim3(256), 0, st, f, *consume);
             return;
         }
@@ -2461,6 +2483,7 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
             hipLaunchKernelGGL(finalize_scatter_next_kernel, dim3((std::max(N, 1) + 255) / 256 + 11), dim3(256), 0, st, f);
         } else if (nx->mode == 1) hipLaunchKernelGGL(finalize_next_kernel<1>, grid, dim3(256), 0, st, f);
         else if (nx->md.npt_cur) hipLaunchKernelGGL(finalize_next_kernel<3>, grid, dim3(256), 0, st, f);
+        else if (nx->md.fixed) hipLaunchKernelGGL(finalize_next_kernel<4>, grid, dim3(256), 0, st, f);
         else hipLaunchKernelGGL(finalize_next_kernel<2>, grid, dim3(256), 0, st, f);
         return;
     }
@@ -3150,6 +3173,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.ring = 3; m.nh = false; m.evaluated = false;
     m.npt = false; m.npt_started = false; m.cells.clear();
     m.relax = false; m.relax_started = false;
+    m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -3173,6 +3197,47 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     return SGPR_OK;
 }
 
+// Held atoms and components for the run begun by sgpr_md_begin: fixed3N[N][3] in caller atom order, nonzero = that Cartesian
+// component of that atom is held (ase.constraints.FixAtoms: all three of an atom; FixCartesian: the chosen ones).  NULL or all
+// zeros: nothing is held, the run is the one without this call.  Inside the device loops (finalize_next_kernel<4>,
+// shard_next_kernel<4>, the FIX forms of md_relax.inc) a held component
+//   * is integrated / optimised with F = 0 — the forces REPORTED (packed, sgpr_md_state) stay the model's;
+//   * has velocity exactly 0 from here on (the value given to sgpr_md_begin is dropped), in sgpr_md_velocities too;
+//   * draws no Langevin noise (the free components draw what they draw without a mask: the deviates are counter-based);
+//   * keeps its coordinate, selected explicitly: at constant cell the bits uploaded; in a relaxation with a moving cell the
+//     undeformed coordinate r is what is held and x = r D^T follows the cell.
+// Degrees of freedom g = 3N - n_fixed: sgpr_md_thermostat then uses tfact = 2 / (g kT ttime^2) and K0 = g kT / 2.
+// After sgpr_md_begin; before sgpr_md_thermostat, sgpr_md_relax and the first sgpr_md_run (SGPR_E_INVALID otherwise, and
+// when every component is held).  sgpr_md_barostat behind a non-empty mask: SGPR_E_UNSUPPORTED.
+extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_fix: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
+    if (m.nh || m.npt || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
+    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
+    const int N = m.N;
+    std::vector<unsigned char> fs((size_t)3 * N, 0);
+    int n = 0;
+    if (fixed3N)
+        for (int i = 0; i < N; i++)
+            for (int k = 0; k < 3; k++)
+                if (fixed3N[3 * (size_t)m.perm[i] + k]) { fs[3 * (size_t)i + k] = 1; n++; }
+    if (n == 3 * N) return fail(SGPR_E_INVALID, "sgpr_md_fix: every component is held, nothing is left to move");
+    if (n == 0) { m.n_fixed = 0; m.fixed_sorted.clear(); return SGPR_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    if (m.fixed.alloc((size_t)3 * N)) return fail(SGPR_E_NODEVICE, "sgpr_md_fix: device allocation failed");
+    HIPCHK(hipMemcpy(m.fixed.p, fs.data(), (size_t)3 * N, hipMemcpyHostToDevice));
+    std::vector<double> v((size_t)3 * N);
+    HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < (size_t)3 * N; e++)
+        if (fs[e]) v[e] = 0.0;
+    HIPCHK(hipMemcpy(m.V.p, v.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    m.n_fixed = n;
+    m.fixed_sorted = fs;
+    return SGPR_OK;
+}
+
 // Nose-Hoover NVT for the run begun by sgpr_md_begin (kind = 1; 0 = back to the Langevin / velocity-Verlet step of
 // sgpr_md_begin's friction): what the reference's default md(dynamics="NPT", bulk_modulus=None) is — ase.md.npt.NPT with
 // pfactor = None and ttime = tdamp fs (cl/md.py:17, :131-166) — restated in md_nh_advance / md_nh_kernel.  kT as given to
@@ -3187,9 +3252,12 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
     if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
-    const double tfact = 2.0 / ((double)(3 * m.N) * kT * ttime * ttime);
+    // (held components, sgpr_md_fix: g = 3N - n_fixed degrees of freedom, none removed for the centre of mass — momentum is
+    // not conserved beside a held atom; the project's own definition, ASE's NPT takes no constraints)
+    const double g = (double)(3 * m.N - m.n_fixed);
+    const double tfact = 2.0 / (g * kT * ttime * ttime);
     m.nh = true; m.ring = 4;
-    m.nh_c1 = m.dt * tfact; m.nh_c2 = 2.0 * m.dt * tfact; m.nh_K0 = 1.5 * (double)(m.N - 1) * kT;
+    m.nh_c1 = m.dt * tfact; m.nh_c2 = 2.0 * m.dt * tfact; m.nh_K0 = m.n_fixed ? 0.5 * g * kT : 1.5 * (double)(m.N - 1) * kT;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
     return SGPR_OK;
@@ -3208,6 +3276,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (!m.active || !m.nh || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
     if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
+    if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.n_fixed);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -3480,7 +3549,7 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
     if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
     HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
     auto cell_of = [&](long long n) -> double * { return m.rx_cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
-    m.relax_started = true;
+    m.relax_started = true; m.started = true;
     if (!h->warm) {
         const int sw = (int)(m.t % RG);
         const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.t), m.P.p + plen * sw, st);
@@ -3517,13 +3586,18 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
         if (rc_) break;
         h->lists_valid = true;
         const bool stay = final_eval && j == nevals - 1;
-        hipLaunchKernelGGL(md_fire_kernel, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p, (const double *)packed, (const int *)h->d_perm.p,
+        // (held components, sgpr_md_fix: the FIX forms; without a mask the kernels of a run without one)
+        hipLaunchKernelGGL(m.n_fixed ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p,
+                           (const double *)packed, (const int *)h->d_perm.p,
                            (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host_dev,
-                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark_dev + j, stay ? 1 : 0);
+                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark_dev + j, stay ? 1 : 0,
+                           m.fix());
         if (!stay)
-            hipLaunchKernelGGL(md_fire_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell, (const double *)m.rx_state.p,
+            hipLaunchKernelGGL(m.n_fixed ? md_fire_move_kernel<true> : md_fire_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell,
+                               (const double *)m.rx_state.p,
                                (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.rx_ref.p, m.X.p + (size_t)3 * N * sn,
-                               (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j));
+                               (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j),
+                               m.fix());
         enq = j + 1;
     }
     if (rc_) { (void)hipStreamSynchronize(st); return rc_; }
@@ -3587,6 +3661,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     const size_t plen = (size_t)sgpr_packed_len(N);
     *evals_done = 0;
     if (halt_code) *halt_code = 0;
+    m.started = true;
     // scalar ring in mapped host memory
     if (m.scal_rows < (size_t)nevals + 1) {
         if (m.mark) (void)hipHostFree(m.mark);
@@ -3702,6 +3777,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
             h->step_grid = &x.npt_cur->grid;
         }
         x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
+        x.fixed = m.fix();
         x.ke_cur = m.KE.p + (size_t)2 * N * sl; x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
         x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
         x.ediff = ediff > 0.0 ? ediff : 1e300;
@@ -3857,7 +3933,8 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     for (int i = 0; i < N; i++) {
         const int c = m.perm[i];
         for (int k = 0; k < 3; k++)
-            velocities[3 * (size_t)c + k] = kick ? v[3 * (size_t)i + k] + m.hdt * F[3 * (size_t)c + k] / m.mass_sorted[i] : v[3 * (size_t)i + k];
+            velocities[3 * (size_t)c + k] = (m.n_fixed && m.fixed_sorted[3 * (size_t)i + k]) ? 0.0   // (a held component: F = 0, v = 0)
+                : kick ? v[3 * (size_t)i + k] + m.hdt * F[3 * (size_t)c + k] / m.mass_sorted[i] : v[3 * (size_t)i + k];
     }
     return SGPR_OK;
 }

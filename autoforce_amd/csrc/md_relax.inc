@@ -17,6 +17,11 @@
 //     no lag —, the cell rows of G from the packed virial, the FIRE scalars, the three coefficients of the move, the new D
 //     and the next cell h0 D^T (into the next slot of the ring of cells);
 //   * md_fire_move_kernel, a quad of lanes per atom: v, r, x = r D^T of the next configuration.
+// Held components (sgpr_md_fix; the FIX instantiations, `fixed` a byte per component in sorted order): the optimizer sees F = 0
+// there and the component of G = F D is zero in the three sums and in max |G_row|^2 — convergence is judged on the free
+// components, the cell rows are as they are —; its velocity is 0 and the coordinate r is handed on as it is, selected
+// explicitly: at constant cell x = r keeps its bits, under a moving cell r is what is held and x = r D^T follows the cell
+// (ase.constraints.FixAtoms inside UnitCellFilter).  The forces in `packed` stay the model's.
 // The next evaluation bins its atoms itself (the binning kernel: general cells, the affine rebuild rule under strain).
 //   Operations and their order are those of workloads.fire_relax (the host twin): no contraction, true divisions, the 3 x 3
 // algebra spelled out with a general closed-form inverse (a relaxed cell has all nine components).
@@ -61,9 +66,10 @@ __host__ __device__ inline double rlx_det(const double *c)
 // velocities of the atoms' coordinates (sorted order), cur / nxt: this configuration's and the next one's slot of the ring of
 // cells.  The sixteen scalars: 0..10 as the last kernel left them in `packed`, 11 the largest covloss, 12 the largest |G_row|^2,
 // 13 G.v, 14 dt and 15 a as used for the move out of this configuration (as they stand when nothing moves).
+template <bool FIX>
 __global__ __launch_bounds__(256) void md_fire_kernel(int N, RelaxParams p, double *state, const double *packed, const int *perm, const double *vel,
                                                       const double *cur, double *nxt, double ediff, int *halt, int *halt_host, int step,
-                                                      double *scal_row, double *cell_row, int *mark, int stay)
+                                                      double *scal_row, double *cell_row, int *mark, int stay, const unsigned char *fixed)
 {
 #pragma clang fp contract(off)
     if (*halt < step) return;
@@ -75,13 +81,25 @@ __global__ __launch_bounds__(256) void md_fire_kernel(int N, RelaxParams p, doub
     double s_gv = 0.0, s_gg = 0.0, s_vv = 0.0, gmx = 0.0, bmx = 0.0;
     for (int k = tid; k < N; k += 256) {
         const int c = perm[k];
-        const double f0 = packed[3 * (size_t)c], f1 = packed[3 * (size_t)c + 1], f2 = packed[3 * (size_t)c + 2];
+        double f0 = packed[3 * (size_t)c], f1 = packed[3 * (size_t)c + 1], f2 = packed[3 * (size_t)c + 2];
+        bool h0 = false, h1 = false, h2 = false;
+        if (FIX) {
+            h0 = fixed[3 * (size_t)k] != 0; h1 = fixed[3 * (size_t)k + 1] != 0; h2 = fixed[3 * (size_t)k + 2] != 0;
+            if (h0) f0 = 0.0;
+            if (h1) f1 = 0.0;
+            if (h2) f2 = 0.0;
+        }
         const double v0 = vel[3 * (size_t)k], v1 = vel[3 * (size_t)k + 1], v2 = vel[3 * (size_t)k + 2];
         double g0 = f0, g1 = f1, g2 = f2;
         if (p.cell) {
             g0 = (f0 * D[0] + f1 * D[3]) + f2 * D[6];
             g1 = (f0 * D[1] + f1 * D[4]) + f2 * D[7];
             g2 = (f0 * D[2] + f1 * D[5]) + f2 * D[8];
+            if (FIX) {
+                if (h0) g0 = 0.0;
+                if (h1) g1 = 0.0;
+                if (h2) g2 = 0.0;
+            }
         }
         const double gg = (g0 * g0 + g1 * g1) + g2 * g2;
         s_gv += (g0 * v0 + g1 * v1) + g2 * v2;
@@ -197,8 +215,10 @@ __global__ __launch_bounds__(256) void md_fire_kernel(int N, RelaxParams p, doub
 // The move out of an evaluation that md_fire_kernel has let pass: lanes 0..2 of a quad take the three components of sorted atom
 // i — G = F D, v = alpha v + beta G, r += cd v, x = r D'^T (D' the next configuration's) — in workloads.fire_relax's operations.
 // A halted run (at this evaluation or before it) moves nothing.
+template <bool FIX>
 __global__ __launch_bounds__(256) void md_fire_move_kernel(int N, int cell, const double *state, const int *perm, const double *packed, double *vel,
-                                                           double *ref, double *x_next, const double *cur, const double *nxt, const int *halt, int step)
+                                                           double *ref, double *x_next, const double *cur, const double *nxt, const int *halt, int step,
+                                                           const unsigned char *fixed)
 {
 #pragma clang fp contract(off)
     const int tid = threadIdx.x, lane = tid & 3, l3 = lane < 3 ? lane : 2;
@@ -215,12 +235,16 @@ __global__ __launch_bounds__(256) void md_fire_move_kernel(int N, int cell, cons
 #pragma unroll
         for (int j = 0; j < 3; j++) { dcol[j] = cur[9 + 3 * j + l3]; drow[j] = nxt[9 + 3 * l3 + j]; }
     }
-    const double F = packed[3 * (size_t)c + l3];
+    const bool held = FIX ? fixed[3 * (size_t)ia + l3] != 0 : false;   // (with the first round trip)
+    double F = packed[3 * (size_t)c + l3];
     if (halt_w <= step) return;
+    if (held) F = 0.0;
     double G = F;
     if (cell) G = (fin_quad_lane<0>(F) * dcol[0] + fin_quad_lane<1>(F) * dcol[1]) + fin_quad_lane<2>(F) * dcol[2];
-    const double vn = alpha * v + beta * G;
-    const double rn = r + cd * vn;
+    if (held) G = 0.0;
+    double vn = alpha * v + beta * G;
+    double rn = r + cd * vn;
+    if (held) { vn = 0.0; rn = r; }   // (selected, not computed)
     double xn = rn;
     if (cell) xn = (fin_quad_lane<0>(rn) * drow[0] + fin_quad_lane<1>(rn) * drow[1]) + fin_quad_lane<2>(rn) * drow[2];
     if (act && lane < 3) {

@@ -132,20 +132,22 @@ __global__ __launch_bounds__(256) void peer_sum_kernel(ShardSrc s, size_t len, i
 // to its next position — MODE 1: read from the next resident frame; MODE 2: integrated from the TOTAL force, every rank
 // integrating every atom: after the exchange every rank holds the same bits, the deviates are counter-based or uploaded
 // alike, so the ranks' states stay identical without ever being compared —, bins it, takes part in the rebuild decision
-// and clears the accumulators of the next step's reverse pass.  Grid: ceil(N / 64) + 2 lagged reducers (MODE 2) + 1
+// and clears the accumulators of the next step's reverse pass.  MODE 4: MODE 2 with held components (FinNext::fixed), the
+// rules of finalize_next_kernel<4>.  Grid: ceil(N / 64) + 2 lagged reducers (MODE 2) + 1
 // workgroup for the eleven scalars.
 template <int MODE>
 __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
 {
     const FinNext &x = f.nx;
+    constexpr bool MD = MODE >= 2;   // the integrator (MODE 4: with held components, as finalize_next_kernel<4>)
     const int tid = threadIdx.x, b = blockIdx.x, nA = gridDim.x - 3;
     const int N = f.N;
-    const int halt_w = MODE == 2 ? *x.halt : 0x7fffffff;
+    const int halt_w = MD ? *x.halt : 0x7fffffff;
     if (halt_w < x.step) return;
     if (b >= nA) {
         const int q = b - nA;
         if (q < 2) {
-            if (MODE == 2 && x.packed_prev) finalize_reduce_prev(f, q);
+            if (MD && x.packed_prev) finalize_reduce_prev(f, q);
             return;
         }
         if (tid < 11) {
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
             // overflow word: the MD loop halts on it, the host's sgpr_md_run / sgpr_compute report the time-out)
             if (tid == 10 && s.ctl && __hip_atomic_load(s.ctl + SGPR_PEER_CTL_DEAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) v = SGPR_PEER_POISON;
             f.packed[4 * (size_t)N + tid] = v;
-            if (MODE == 2) {
+            if (MD) {
                 x.scal_cur[tid] = tid == 10 ? (v != 0.0 ? 1.0 : 0.0) : v;
                 if (tid == 10) {
                     *x.mark_cur = 1;
@@ -183,7 +185,8 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
     const int slot_i = f.slot[ia];
     const double p0 = f.pos0[3 * (size_t)ia + kk];
     double xc = 0.0, vc = 0.0, ms = 1.0, sg = 0.0, nz = 0.0, xn = 0.0;
-    if (MODE == 2) {
+    const bool held = MODE == 4 ? x.fixed[3 * (size_t)ia + kk] != 0 : false;
+    if (MD) {
         xc = x.x_cur[3 * (size_t)ia + kk];
         vc = x.v_cur[3 * (size_t)ia + kk];
         ms = x.mass[ia];
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
         nz = x.noise ? x.noise[3 * (size_t)ia + kk] : 0.0;
     }
     double xpv = 0.0, zeta = 0.0;
-    if (MODE == 2 && x.nh) { xpv = x.x_prev[3 * (size_t)ia + kk]; zeta = *x.nh_zeta; }
+    if (MD && x.nh) { xpv = x.x_prev[3 * (size_t)ia + kk]; zeta = *x.nh_zeta; }
     if (MODE == 1) xn = x.pos_in[3 * (size_t)c + kk];
     // the totals: lanes 0..2 a force component (integer part summed over the ranks + the owner's own part), lane 3 the covloss
     // (the owner's): sorted atom i belongs to rank i % world, where it is atom i / world
@@ -214,30 +217,33 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
     }
     // ---- the next step
     double ke = 0.0, kp = 0.0, v3 = 0.0;
-    if (MODE == 2 && x.nh) {
+    if (MD && x.nh) {
         if (k < 3) {
-            const double vnow = md_nh_advance(x, tot, ms, xc, vc, xpv, zeta, xn);
+            double vnow = md_nh_advance(x, held ? 0.0 : tot, ms, xc, vc, xpv, zeta, xn);
+            if (held) { xn = xc; vnow = 0.0; }
             ke = ms * (vnow * vnow);
             kp = ke;
             x.v_now[3 * (size_t)i + k] = vnow;
         }
-    } else if (MODE == 2 && k < 3) {
+    } else if (MD && k < 3) {
         // BAOAB, the operations of finalize_next_kernel<2> (= workloads.langevin_nvt) in their order: no contraction
 #pragma clang fp contract(off)
-        const double kick = __ddiv_rn(x.hdt * tot, ms);
+        const double kick = __ddiv_rn(x.hdt * (held ? 0.0 : tot), ms);
         double v = vc;
         if (x.pending) v = v + kick;
         ke = ms * (v * v);
         kp = ms * (vc * vc);
         const double v2 = v + kick;
         const double x1 = xc + x.hdt * v2;
-        if (!x.noise && x.seed != 0ull && sg != 0.0) nz = md_deviate(x.seed, x.t_index, c, k);
+        if (!x.noise && x.seed != 0ull && sg != 0.0 && !held) nz = md_deviate(x.seed, x.t_index, c, k);
+        if (held) nz = 0.0;
         v3 = x.c1 * v2 + sg * nz;
         xn = x1 + x.hdt * v3;
+        if (held) { xn = xc; v3 = 0.0; }
     }
     // the quad's three components, in the order (0 + 1) + 2 of the single-rank kernel
     const double X = fin_dpp<0x00>(xn), Y = fin_dpp<0x55>(xn), Z = fin_dpp<0xAA>(xn);
-    if (MODE == 2) {
+    if (MD) {
         const double k3 = fin_dpp<0x00>(ke) + fin_dpp<0x55>(ke) + fin_dpp<0xAA>(ke);
         const double p3 = fin_dpp<0x00>(kp) + fin_dpp<0x55>(kp) + fin_dpp<0xAA>(kp);
         if (k == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);

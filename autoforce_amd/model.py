@@ -579,14 +579,25 @@ class SGPRModel:
     MD_SCALARS = 16  # per evaluation: E, virial[9], overflow word, largest covloss, sum m v^2, 3 spare
 
     def md_begin(self, numbers, positions, cell, pbc, masses, velocities=None, dt=1.0, friction=0.0, kT=0.0, seed=0, ttime=None,
-                 pfactor=None, externalstress=0.0, mask=None, iso=False):
+                 pfactor=None, externalstress=0.0, mask=None, iso=False, fixed=None):
         """State of an MD run into device memory (cl/md.py:117-128 drives ase.md.langevin around calculate();
         here the integrator is part of the step's last kernel).  dt, friction and kT in the caller's units
-        (workloads.FS / ase_shim.kB for fs / K)."""
+        (workloads.FS / ase_shim.kB for fs / K).
+          fixed: held atoms ([N] booleans: ase.constraints.FixAtoms) or Cartesian components ([N, 3]: FixCartesian), True =
+        held (sgpr_md_fix; None or nothing held: the run without a mask).  The integrator sees F = 0 on a held component — the
+        forces md_state reports stay the model's —, its velocity is exactly 0 from here on (the caller's value is dropped), it
+        draws no noise and keeps the coordinate it was uploaded with, bit for bit.  Nose-Hoover then works on the
+        g = 3N - n_fixed remaining degrees of freedom: tfact = 2 / (g kT ttime^2), K0 = g kT / 2 (the project's own definition:
+        ase.md.npt.NPT takes no constraints), and temperatures are sum m v^2 / (g kB) (md_dof()).  Not with a barostat."""
+        from .workloads import fixed_mask
         numbers = i32(numbers)
         N = len(numbers)
-        self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=f64(masses), hdt=0.5 * dt)
+        fx = fixed_mask(fixed, N)
+        self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=f64(masses), hdt=0.5 * dt, fixed=fx)
         if pfactor is not None:
+            if fx is not None:
+                raise NotImplementedError("md_begin: held components (fixed) with a barostat (pfactor): the moving-cell dynamics "
+                                          "run without a mask")
             if ttime is None:
                 raise ValueError("a barostat (pfactor) needs the Nose-Hoover thermostat (ttime)")
             from .npt import zero_mean_momentum   # (NPT.__init__ removes the mean momentum: the host twin starts from the same bits)
@@ -598,6 +609,7 @@ class SGPRModel:
                                         float(dt), float(friction), float(kT)))
         # seed != 0: md_run(noise=None) draws the Langevin deviates on the device (counter-based, md_deviates returns them)
         check(_lib.load().sgpr_md_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._md_fix(fx)
         # ttime: Nose-Hoover NVT with that time constant instead of the Langevin / velocity-Verlet step (the reference's
         # default dynamics, cl/md.py:131-166: ase.md.npt.NPT with pfactor = None)
         if ttime is not None:
@@ -615,19 +627,35 @@ class SGPRModel:
             self._md["npt"] = True
         self._md["t"] = 0
 
-    def relax_begin(self, numbers, positions, cell, pbc, fmax, cell_relax=False, mask=None, **fire):
+    def _md_fix(self, fx):
+        """The held components of the run just begun (sgpr_md_fix: before the thermostat / the relaxation is set)."""
+        if fx is not None:
+            check(_lib.load().sgpr_md_fix(self._h, ptr(np.ascontiguousarray(fx, dtype=np.uint8))))
+
+    def md_dof(self):
+        """Degrees of freedom of the run: 3N less the held components."""
+        fx = self._md.get("fixed")
+        return 3 * self._md["N"] - (0 if fx is None else int(fx.sum()))
+
+    def relax_begin(self, numbers, positions, cell, pbc, fmax, cell_relax=False, mask=None, fixed=None, **fire):
         """State of a FIRE relaxation into device memory (sgpr_md_relax: ase/optimize/fire.py on the positions and, with
         cell_relax, on the cell through ase.constraints.UnitCellFilter(atoms, mask=mask)'s coordinates; workloads.fire_relax is
         the host twin).  fire: dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (ASE's defaults).  md_run / md_state / md_cells /
         md_end then serve the relaxation as they serve an MD run: md_run's halt code 3 = converged at its last row, nothing
-        moved; its rows carry max |G_row|^2, G.v, dt and a in the columns 12..15; md_cells returns (cells, D)."""
-        from .workloads import FIRE_DEFAULTS
+        moved; its rows carry max |G_row|^2, G.v, dt and a in the columns 12..15; md_cells returns (cells, D).
+          fixed: held atoms ([N]) or components ([N, 3]), True = held (sgpr_md_fix): the optimizer sees F = 0 there, the entries
+        of G are zero in FIRE's sums and in max |G_row|^2 — convergence is judged on the free components, the forces reported
+        stay the model's —, and the coordinate stays: x itself at constant cell, bit for bit; with cell_relax the undeformed
+        r, x = r D^T following the cell (FixAtoms inside UnitCellFilter)."""
+        from .workloads import FIRE_DEFAULTS, fixed_mask
         unknown = set(fire) - set(FIRE_DEFAULTS)
         if unknown:
             raise TypeError(f"relax_begin: unknown FIRE keywords {sorted(unknown)}")
         numbers = i32(numbers)
         N = len(numbers)
-        self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=np.ones(N), hdt=0.0, relax=True, npt=True)
+        fx = fixed_mask(fixed, N)
+        self._md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=np.ones(N), hdt=0.0, relax=True, npt=True,
+                        fixed=fx)
         self.generation += 1
         lib = _lib.load()
         check(lib.sgpr_md_begin(self._h, N, ptr(numbers), ptr(f64(positions).reshape(N, 3)), ptr(self._md["cell"]),
@@ -636,6 +664,7 @@ class SGPRModel:
         par.update(fire)
         fp = f64([par[k] for k in ("dt", "maxstep", "dtmax", "nmin", "finc", "fdec", "astart", "fa")])
         mk = None if mask is None else f64(np.asarray(mask, float).reshape(6))
+        self._md_fix(fx)
         check(lib.sgpr_md_relax(self._h, float(fmax), ptr(fp), int(bool(cell_relax)), ptr(mk)))
         self._md["t"] = 0
 
@@ -708,6 +737,8 @@ class SGPRModel:
                 out["velocities"] = vn
             else:
                 out["velocities"] = v + self._md["hdt"] * F / self._md["masses"][:, None] if pend.value else v.copy()
+                if self._md.get("fixed") is not None:   # (a held component: the integrator's F = 0, v = 0)
+                    out["velocities"] = np.where(self._md["fixed"], 0.0, out["velocities"])
         return out
 
     def md_end(self):

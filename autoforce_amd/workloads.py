@@ -143,13 +143,33 @@ MASS = {1: 1.008, 3: 6.94, 8: 15.999, 9: 18.998, 11: 22.99, 12: 24.305, 14: 28.0
         40: 91.224, 57: 138.905}
 
 
-def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None, rng=None):
+def fixed_mask(fixed, N):
+    """A held-component mask as the device loops take it (sgpr_md_fix): None, or an [N] (whole atoms: ase.constraints.FixAtoms)
+    or [N, 3] (single Cartesian components: FixCartesian) array, True = held -> None when nothing is held, else bool [N, 3]."""
+    if fixed is None:
+        return None
+    m = np.asarray(fixed)
+    if m.shape == (N,):
+        m = np.repeat(m.reshape(N, 1), 3, axis=1)
+    if m.shape != (N, 3):
+        raise ValueError(f"fixed: an [N] or [N, 3] array for N = {N} atoms, not {m.shape}")
+    m = m != 0
+    return m if m.any() else None
+
+
+def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None, rng=None, fixed=None):
     """BAOAB Langevin dynamics in numpy around any calculator with the ASE surface; parameters as the reference's
     driver (cl/md.py:31,70-74: dt = 1 fs, friction 1e-3 per ASE time unit, T = 600 K; Maxwell-Boltzmann start as
     util/aseutil.py:11-20, or the velocities handed over).  Generator: yields (step, energy, temperature, wall seconds,
-    positions, velocities) after every step.  With ASE installed, ase.md.langevin.Langevin drives the same calculator."""
+    positions, velocities) after every step.  With ASE installed, ase.md.langevin.Langevin drives the same calculator.
+      fixed: held components (fixed_mask: [N] or [N, 3], True = held), the rules of the device loop (sgpr_md_fix): the integrator
+    sees F = 0 there (the calculator's results stay raw), the velocity is exactly 0 from the start (the caller's value is
+    dropped), the deviate of a held component is drawn — one rng.normal(size=(N, 3)) per step as ever, so the free components
+    consume what they consume without a mask — and not used, and the next coordinate is the current one, selected.  The
+    temperature is over the g = 3N - n_fixed remaining degrees of freedom (atoms.get_temperature() under constraints).  None
+    or nothing held: today's loop, bit for bit."""
     import time
-    from .ase_shim import Atoms, kB
+    from .ase_shim import Atoms, constraints_from_mask, kB
     rng = np.random.default_rng(seed) if rng is None else rng
     N = len(numbers)
     mass = np.array([MASS[int(z)] for z in numbers])[:, None]
@@ -158,28 +178,45 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
         vel = rng.normal(size=(N, 3)) * np.sqrt(kT / mass)
         vel -= (mass * vel).sum(0) / mass.sum()
     vel = np.array(vel, float)
+    fx = fixed_mask(fixed, N)
+    cons = constraints_from_mask(fx)
+    dof = 3 * N if fx is None else 3 * N - int(fx.sum())
+    if fx is not None:
+        vel[fx] = 0.0
     dt = dt_fs * FS
     c1 = np.exp(-friction * dt)
     c2 = np.sqrt(1 - c1 * c1)
     pos = np.array(pos, float)
 
     def forces(p, v):
-        at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0])
+        # (the atoms carry the constraints, as the Atoms of an ASE loop around the calculator do: a calculator that learns takes
+        # its copies — and its teacher's labels — from them; the forces taken here are the calculator's own)
+        at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0], constraint=cons)
         at.calc = calc
-        return at.get_forces(), at.get_potential_energy()
+        return at.get_forces(apply_constraint=False), at.get_potential_energy()
+
+    def seen(F):   # the forces the integrator sees
+        return F if fx is None else np.where(fx, 0.0, F)
 
     t0 = time.time()
     F, E = forces(pos, vel)
-    yield 0, E, float((mass * vel ** 2).sum() / (3 * N * kB)), time.time() - t0, pos, vel
+    yield 0, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel
     for step in range(1, steps + 1):
         t0 = time.time()
-        vel += 0.5 * dt * F / mass
+        held = pos
+        vel += 0.5 * dt * seen(F) / mass
         pos = pos + 0.5 * dt * vel
-        vel = c1 * vel + c2 * np.sqrt(kT / mass) * rng.normal(size=(N, 3))
+        xi = rng.normal(size=(N, 3))
+        if fx is not None:
+            xi = np.where(fx, 0.0, xi)
+        vel = c1 * vel + c2 * np.sqrt(kT / mass) * xi
         pos = pos + 0.5 * dt * vel
+        if fx is not None:   # (selected, not computed)
+            pos = np.where(fx, held, pos)
+            vel = np.where(fx, 0.0, vel)
         F, E = forces(pos, vel)
-        vel += 0.5 * dt * F / mass
-        yield step, E, float((mass * vel ** 2).sum() / (3 * N * kB)), time.time() - t0, pos, vel
+        vel += 0.5 * dt * seen(F) / mass
+        yield step, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel
 
 
 def _device_order_sum(x):
@@ -196,7 +233,8 @@ def _device_order_sum(x):
     return float(p[0])
 
 
-def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, vel=None, seed=1, species=None):
+def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, vel=None, seed=1, species=None,
+                    fixed=None):
     """Nose-Hoover NVT in numpy around any calculator with the ASE surface: the reference's DEFAULT dynamics —
     md(dynamics="NPT", bulk_modulus=None) = ase.md.npt.NPT(pfactor=None, ttime=tdamp fs), cl/md.py:17, :131-166 — restated
     from ASE's published algorithm (Melchionna, Ciccotti, Holian 1993; ASE is absent here):
@@ -205,9 +243,16 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     started with x_(-1) = x_0 - dt v_0 + dt^2 F_0 / 2m, zeta_0 = 0, zeta_(-1) = -dt tfact (KE_0 - ...).  The host twin of the
     device loop (sgpr_md_thermostat): same operations in the same order, bit for bit (the kinetic energy is summed over the
     atoms in the library's species-sorted order: `species` = the model's table, default the sorted atomic numbers).  Yields
-    (step, energy, temperature, wall seconds, positions, velocities, zeta, integral of zeta) per evaluated configuration."""
+    (step, energy, temperature, wall seconds, positions, velocities, zeta, integral of zeta) per evaluated configuration.
+      fixed: held components (fixed_mask), the rules of the device loop (sgpr_md_fix): F = 0 for the integrator, centred
+    velocity exactly 0, the next coordinate the current one — selected: x (1 + b) / (1 + b) is not x bit for bit.  With
+    g = 3N - n_fixed > 0 held components the thermostat works on the remaining degrees of freedom: tfact = 2 / (g kT ttime^2),
+    K0 = g kT / 2 (no centre-of-mass degree removed: momentum is not conserved beside a held atom), temperature
+    sum m v^2 / (g kB); conserved: E + KE + zeta^2 / tfact + 2 K0 int zeta dt, today's expression when nothing is held.  This
+    is the project's own definition — ase.md.npt.NPT takes no constraints at all.  None or nothing held: today's loop, bit for
+    bit."""
     import time
-    from .ase_shim import Atoms, kB
+    from .ase_shim import Atoms, constraints_from_mask, kB
     N = len(numbers)
     mass = np.array([MASS[int(z)] for z in numbers])[:, None]
     kT = kB * temperature
@@ -216,12 +261,17 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         vel = rng.normal(size=(N, 3)) * np.sqrt(kT / mass)
         vel -= (mass * vel).sum(0) / mass.sum()
     v0 = np.array(vel, float)
+    fx = fixed_mask(fixed, N)
+    cons = constraints_from_mask(fx)
+    if fx is not None:
+        v0[fx] = 0.0
+    dof = float(3 * N) if fx is None else float(3 * N - int(fx.sum()))
     dt = dt_fs * FS
     hdt = 0.5 * dt
     dt = 2.0 * hdt
     ttime = tdamp_fs * FS
-    tfact = 2.0 / (float(3 * N) * kT * ttime * ttime)
-    c1, c2, K0 = dt * tfact, 2.0 * dt * tfact, 1.5 * float(N - 1) * kT
+    tfact = 2.0 / (dof * kT * ttime * ttime)
+    c1, c2, K0 = dt * tfact, 2.0 * dt * tfact, (1.5 * float(N - 1) * kT if fx is None else 0.5 * dof * kT)
     x = np.array(pos, float)
     xp = None
     zeta, zint = {0: 0.0}, {0: 0.0}
@@ -229,19 +279,26 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
 
     def forces(p, v):
-        at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0])
+        # (the atoms carry the constraints, as the Atoms of an ASE loop around the calculator do: a calculator that learns takes
+        # its copies — and its teacher's labels — from them; the forces taken here are the calculator's own)
+        at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0], constraint=cons)
         at.calc = calc
-        return at.get_forces(), at.get_potential_energy()
+        return at.get_forces(apply_constraint=False), at.get_potential_energy()
 
     for n in range(steps + 1):
         t0 = time.time()
         F, E = forces(x, v0 if n == 0 else v)   # (the velocities the integrator holds when it asks for forces: v_(n-1))
+        if fx is not None:
+            F = np.where(fx, 0.0, F)
         a = ((dt * dt) * F) / mass
         if n == 0:
             xp = (x - dt * v0) + 0.5 * a
         b = hdt * zeta[n]
         xn = (((2.0 * x) - xp * (1.0 - b)) + a) / (1.0 + b)
         v = v0 if n == 0 else (xn - xp) / (2.0 * dt)
+        if fx is not None:   # (selected, not computed)
+            xn = np.where(fx, x, xn)
+            v = np.where(fx, 0.0, v)
         ke3 = mass * (v * v)
         ke_atom = (ke3[:, 0] + ke3[:, 1]) + ke3[:, 2]
         KE = 0.5 * _device_order_sum(ke_atom[order])
@@ -249,7 +306,7 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         zprev = -(c1 * d) if n == 0 else zeta[n - 1]
         zeta[n + 1] = zprev + c2 * d
         zint[n + 1] = zint[n] + dt * zeta[n + 1]
-        yield n, E, float(2.0 * KE / (3 * N * kB)), time.time() - t0, x, v, zeta[n], zint[n]
+        yield n, E, float(2.0 * KE / ((3 * N if fx is None else dof) * kB)), time.time() - t0, x, v, zeta[n], zint[n]
         xp, x = x, xn
 
 
@@ -445,7 +502,7 @@ def _cell_volume(c):
                + c[0][2] * (c[1][0] * c[2][1] - c[1][1] * c[2][0]))
 
 
-def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mask=None, species=None, reset_at=(), **fire):
+def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mask=None, species=None, reset_at=(), fixed=None, **fire):
     """FIRE (ase/optimize/fire.py, ASE 3.22, LGPL, as cl/relax.py::FIRE restates it) on the positions — and, with cell_relax,
     on the cell through ase.constraints.UnitCellFilter(atoms, mask=mask) (cl/relax.py::UnitCellFilter) — in numpy around any
     calculator with the ASE surface, written by evaluation index in the operations and the summation order of the device loop
@@ -463,10 +520,15 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
     only.  Dots run over all 3N (+ 9) components: the atoms' part through _device_order_sum in the library's species-sorted
     order (`species`: the model's table), the three cell rows added behind it.  No BLAS call.  reset_at: evaluation indices in
     front of which the optimizer is re-initialised (optimizer.initialize(): v = 0, dt, a, nsteps as at the start).
+      fixed: held components (fixed_mask), the rules of the device loop (sgpr_md_fix): the optimizer sees F = 0 there and the
+    component of G = F D is zero in all three sums and in max |G_row|^2 (convergence is judged on the free components; the cell
+    rows are unchanged), its velocity is 0 and its coordinate r is handed on as it is, selected: at constant cell x = r keeps its
+    bits, with cell_relax r is what is held and x = r D^T follows the cell — ase.constraints.FixAtoms inside UnitCellFilter.
+    None or nothing held: today's loop, bit for bit.
       Yields a dict per evaluated configuration: n, energy, positions, cell, D, gmax2 (largest |G_row|^2), P (G.v; 0 for a
     first evaluation), dt and a as used for the move out of this configuration (as they stand when it has converged), nsteps
     behind that move, converged.  The generator ends behind a converged configuration."""
-    from .ase_shim import Atoms
+    from .ase_shim import Atoms, constraints_from_mask
     p = dict(FIRE_DEFAULTS)
     p.update(fire)
     N = len(numbers)
@@ -486,6 +548,8 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
     v, vc = np.zeros_like(r), [[0.0] * 3 for _ in range(3)]
     dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
     fmax2 = float(fmax) * float(fmax)
+    fx = fixed_mask(fixed, N)
+    cons = constraints_from_mask(fx)   # (the atoms handed to the calculator carry them, as in an ASE loop)
 
     def dot(u, w, uc, wc):
         t = u * w
@@ -499,9 +563,11 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
         if n in reset_at:
             v, vc = np.zeros_like(r), [[0.0] * 3 for _ in range(3)]
             dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
-        at = Atoms(numbers, x, np.array(h), pbc)
+        at = Atoms(numbers, x, np.array(h), pbc, constraint=cons)
         at.calc = calc
-        F, E = np.asarray(at.get_forces(), float), float(at.get_potential_energy())
+        F, E = np.asarray(at.get_forces(apply_constraint=False), float), float(at.get_potential_energy())
+        if fx is not None:
+            F = np.where(fx, 0.0, F)
         Gc = [[0.0] * 3 for _ in range(3)]
         if cell_relax:
             s6 = [float(t) for t in np.asarray(at.get_stress(), float)]
@@ -511,6 +577,8 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
             T = _m3_mul_t(W, _m3_inv(D))
             Gc = [[(T[a_][b] * M[a_][b]) / cf for b in range(3)] for a_ in range(3)]
             G = _row_mul(F, D)
+            if fx is not None:
+                G = np.where(fx, 0.0, G)
         else:
             G = F
         g2 = G * G
@@ -548,7 +616,11 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
         out.update(dt=dt, a=a, nsteps=nsteps, converged=False)
         yield out
         v = alpha * v + beta * G
-        r = r + cd * v
+        if fx is None:
+            r = r + cd * v
+        else:   # (selected, not computed)
+            v = np.where(fx, 0.0, v)
+            r = np.where(fx, r, r + cd * v)
         if cell_relax:
             vc = [[alpha * vc[a_][b] + beta * Gc[a_][b] for b in range(3)] for a_ in range(3)]
             Xc = [[Xc[a_][b] + cd * vc[a_][b] for b in range(3)] for a_ in range(3)]
@@ -560,17 +632,20 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
 
 
 def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None,
-                        ediff=0.0, chunk=256, on_halt=None, device_rng=False):
+                        ediff=0.0, chunk=256, on_halt=None, device_rng=False, fixed=None):
     """langevin_nvt with the state in device memory (SGPRModel.md_begin / md_run): same scheme, same random stream
     (one rng.normal(size=(N, 3)) per step, drawn here and uploaded a chunk at a time), so positions and velocities equal
     the host loop's bit for bit.  Yields (step, energy, temperature, largest covloss) per evaluation.  With ediff > 0 an
     evaluation whose largest covloss reaches it stops the run ON THE DEVICE; on_halt(model, state) — the model update of
     calculator/active.py:477-484 — is called with that configuration and its results, and the evaluation is repeated
     with whatever model on_halt left behind (an on_halt that leaves the covloss above ediff must raise ediff itself:
-    it receives and may return the threshold)."""
+    it receives and may return the threshold).  fixed: held components (fixed_mask; SGPRModel.md_begin(fixed=)), the rules of
+    langevin_nvt(fixed=); the temperature is over the remaining degrees of freedom."""
     from .ase_shim import kB
     rng = np.random.default_rng(seed)
     N = len(numbers)
+    fx = fixed_mask(fixed, N)
+    dof = 3 * N if fx is None else 3 * N - int(fx.sum())
     mass = np.array([MASS[int(z)] for z in numbers])
     kT = kB * temperature
     if vel is None:
@@ -579,7 +654,7 @@ def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0
     # device_rng: the deviates are drawn on the device (counter-based on `seed`; SGPRModel.md_deviates returns them for a
     # host twin) instead of from numpy here: nothing is generated or uploaded on the step's path
     model.md_begin(numbers, pos, cell, pbc, mass, vel, dt=dt_fs * FS, friction=friction, kT=kT,
-                   seed=(int(seed) or 1) if device_rng else 0)
+                   seed=(int(seed) or 1) if device_rng else 0, **({} if fx is None else dict(fixed=fx)))
     done = 0                      # evaluations accepted so far (evaluation k = the configuration after k steps)
     rows = np.empty((0, N, 3))    # deviates drawn and not yet consumed: rows[0] moves the current configuration on
     skip_gate = False
@@ -595,7 +670,7 @@ def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0
         if accepted:
             skip_gate = False   # (code 2 with nothing accepted: a capacity was outgrown, the same call again re-sizes it)
         for r in sc[:accepted]:
-            yield done, float(r[0]), float(r[12] / (3 * N * kB)), float(r[11])
+            yield done, float(r[0]), float(r[12] / (dof * kB)), float(r[11])
             done += 1
         rows = rows[accepted:]
         if code == 1:

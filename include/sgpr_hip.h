@@ -412,6 +412,30 @@ int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out);
  * sgpr_md_relax_reset  optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (between two sgpr_md_run calls). */
 int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6);
 int sgpr_md_relax_reset(sgpr_model *h);
+/* Held atoms and components (after sgpr_md_begin; before sgpr_md_thermostat, sgpr_md_relax and the first sgpr_md_run):
+ * fixed3N[N][3] in caller atom order, nonzero = that Cartesian component of that atom is held — all three of an atom for
+ * ase.constraints.FixAtoms, the chosen ones for FixCartesian.  NULL or all zeros: nothing is held, and the run launches what a
+ * run without this call launches.  Honoured inside the device loops — BAOAB Langevin, velocity Verlet, Nose-Hoover NVT (sharded
+ * runs too), FIRE with and without a moving cell —, where a held component
+ *   - is moved with F = 0: the forces the library REPORTS (packed results, sgpr_md_state) stay the model's own, and energy,
+ *     virial and covloss are untouched;
+ *   - has velocity exactly 0 from this call on (the value given to sgpr_md_begin is dropped), in the closing half kick of
+ *     sgpr_md_velocities, in the Nose-Hoover centred velocity and in FIRE's velocity alike;
+ *   - receives no Langevin noise: the device's deviates are counter-based on (seed; configuration, atom, component), so the
+ *     free components draw exactly what they draw in a run without a mask; uploaded rows are read as before, held entries unused;
+ *   - keeps its coordinate by selection, not by arithmetic that should cancel: at constant cell the bits uploaded by
+ *     sgpr_md_begin for the whole run; in a relaxation with move_cell the undeformed coordinate r is what is held and
+ *     x = r D^T follows the cell (FixAtoms inside UnitCellFilter).  The entries of G = F D of held components are zero in FIRE's
+ *     three sums and in max |G_row|^2: convergence is judged on the free components; the cell rows are unchanged.
+ * Degrees of freedom g = 3N - (held components).  With a non-empty mask sgpr_md_thermostat uses tfact = 2 / (g kT ttime^2) and
+ * K0 = g kT / 2 — no centre-of-mass degree is removed, momentum is not conserved beside a held atom — and the conserved quantity
+ * is E + KE + zeta^2 / tfact + 2 K0 int zeta dt, which is the expression above when nothing is held.  (The project's own
+ * definition: ase.md.npt.NPT takes no constraints.)  scalars[.][12] / [13] are sums over all atoms as before: the temperature is
+ * sum m v^2 / (g kB).
+ * SGPR_E_INVALID: no run begun, a thermostat or a relaxation already set, a run that has started, every component held.
+ * SGPR_E_UNSUPPORTED: from sgpr_md_barostat behind a non-empty mask (the moving-cell dynamics run without one).  The handle
+ * goes on working after any of them. */
+int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
