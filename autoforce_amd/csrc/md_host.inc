@@ -1,0 +1,842 @@
+// md_host.inc — the host side of the device-resident loops (sgpr_md_*: MD, moving-cell NPT, FIRE relaxation), included by
+// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc and md_relax.inc.
+//
+// The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
+// from util/aseutil.py:11-20) and crosses into the calculator once per step.  Here the state (positions, velocities)
+// lives in HBM, the integrator is part of the step's last kernel (finalize_next_kernel<2>), and the host reads a few
+// scalars per step; the covloss gate of calculate() (calculator/active.py:492-499) halts the run ON THE DEVICE at the
+// step whose largest covloss reaches `ediff`, with that step's state and results intact for the model update.
+static int md_alloc(sgpr_model *h, int N)
+{
+    MdState &m = h->md;
+    bool bad = false;
+    bad |= m.X.alloc((size_t)12 * N); bad |= m.V.alloc((size_t)12 * N); bad |= m.P.alloc(4 * (size_t)sgpr_packed_len(N));
+    bad |= m.KE.alloc((size_t)8 * N); bad |= m.mass.alloc(N); bad |= m.sig.alloc(N); bad |= m.cell.alloc(9);
+    bad |= m.halt.alloc(4); bad |= m.zeta.alloc(8);
+    if (bad) return fail(SGPR_E_NODEVICE, "sgpr_md_begin: device allocation failed");
+    if (!m.halt_host) {
+        if (hipHostMalloc((void **)&m.halt_host, 64, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&m.halt_host_dev, m.halt_host, 0) != hipSuccess)
+            return fail(SGPR_E_NODEVICE, "sgpr_md_begin: no mapped host memory");
+    }
+    return SGPR_OK;
+}
+
+// Is the handle bound to this system (pbc = NULL: periodic in all three directions)?
+static bool md_same_system(const sgpr_model *h, int N, const int32_t *numbers, const int32_t *pbc, int rank, int world)
+{
+    bool same = (N == h->N && h->rank == rank && h->world == world && (int)h->numbers.size() == N);
+    for (int i = 0; i < N && same; i++) same = h->numbers[i] == numbers[i];
+    for (int k = 0; k < 3 && same; k++) same = h->pbc[k] == (pbc ? (pbc[k] != 0) : 1);
+    return same;
+}
+
+// Whatever ran on the handle since sgpr_md_begin (a model update computes the training rows of stored frames and trial models
+// evaluate them: each rebinds the handle) — the run's own system is bound again before it goes on (warm = false: the checked
+// pass of the run functions)
+static int md_rebind(sgpr_model *h)
+{
+    const MdState &m = h->md;
+    if (md_same_system(h, m.N, m.numbers.data(), m.pbc, m.rank, m.world)) return SGPR_OK;
+    return sgpr_bind_system(h, m.N, m.numbers.data(), m.pbc, m.rank, m.world);
+}
+
+extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const double *positions, const double *cell,
+                             const int32_t *pbc, const double *masses, const double *velocities, double dt,
+                             double friction, double kT)
+{
+    if (!h || N <= 0 || !numbers || !positions || !cell)   // (masses = NULL: ones — a relaxation, sgpr_md_relax, has no use for them)
+        return fail(SGPR_E_INVALID, "sgpr_md_begin: bad arguments");
+    if (!(dt > 0.0) || friction < 0.0 || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_begin: dt > 0, friction >= 0, kT >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    // with the library's own exchange attached the run is sharded over its ranks (every rank integrates all atoms from the
+    // summed forces: shard_next_kernel); otherwise a single process
+    const int tr = peer_on(h) ? h->peer.rank : 0, tw = peer_on(h) ? h->peer.world : 1;
+    int rc_ = md_same_system(h, N, numbers, pbc, tr, tw) ? SGPR_OK : sgpr_bind_system(h, N, numbers, pbc, tr, tw);
+    if (rc_) return rc_;
+    rc_ = md_alloc(h, N);
+    if (rc_) return rc_;
+    MdState &m = h->md;
+    m.numbers.assign(numbers, numbers + N);
+    m.perm = h->perm;
+    for (int k = 0; k < 3; k++) m.pbc[k] = pbc ? (pbc[k] != 0) : 1;
+    m.rank = tr; m.world = tw;
+    m.N = N; m.t = 0; m.dt = dt; m.hdt = 0.5 * dt; m.c1 = exp(-friction * dt);
+    m.ring = 3; m.nh = false; m.evaluated = false;
+    m.npt = false; m.npt_started = false; m.cells.clear();
+    m.relax = false; m.relax_started = false;
+    m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
+    const double c2 = sqrt(1.0 - m.c1 * m.c1);
+    std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
+    for (int i = 0; i < N; i++) {
+        const int c = h->perm[i];
+        for (int k = 0; k < 3; k++) {
+            xs[3 * (size_t)i + k] = positions[3 * (size_t)c + k];
+            if (velocities) vs[3 * (size_t)i + k] = velocities[3 * (size_t)c + k];
+        }
+        ms[i] = masses ? masses[c] : 1.0;
+        if (!(ms[i] > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_begin: mass of atom %d is not positive", c);
+        sg[i] = friction > 0.0 ? c2 * sqrt(kT / ms[i]) : 0.0;   // (as workloads.langevin_nvt: c2 * np.sqrt(kT / mass))
+    }
+    m.mass_sorted = ms;
+    HIPCHK(hipMemcpy(m.X.p, xs.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.V.p, vs.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.mass.p, ms.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.sig.p, sg.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.cell.p, cell, sizeof(double) * 9, hipMemcpyHostToDevice));
+    m.active = true;
+    h->pre_valid = false;
+    return SGPR_OK;
+}
+
+// Held atoms and components for the run begun by sgpr_md_begin: fixed3N[N][3] in caller atom order, nonzero = that Cartesian
+// component of that atom is held (ase.constraints.FixAtoms: all three of an atom; FixCartesian: the chosen ones).  NULL or all
+// zeros: nothing is held, the run is the one without this call.  Inside the device loops (finalize_next_kernel<4>,
+// shard_next_kernel<4>, the FIX forms of md_relax.inc) a held component
+//   * is integrated / optimised with F = 0 — the forces REPORTED (packed, sgpr_md_state) stay the model's;
+//   * has velocity exactly 0 from here on (the value given to sgpr_md_begin is dropped), in sgpr_md_velocities too;
+//   * draws no Langevin noise (the free components draw what they draw without a mask: the deviates are counter-based);
+//   * keeps its coordinate, selected explicitly: at constant cell the bits uploaded; in a relaxation with a moving cell the
+//     undeformed coordinate r is what is held and x = r D^T follows the cell.
+// Degrees of freedom g = 3N - n_fixed: sgpr_md_thermostat then uses tfact = 2 / (g kT ttime^2) and K0 = g kT / 2.
+// After sgpr_md_begin; before sgpr_md_thermostat, sgpr_md_relax and the first sgpr_md_run (SGPR_E_INVALID otherwise, and
+// when every component is held).  sgpr_md_barostat behind a non-empty mask: SGPR_E_UNSUPPORTED.
+extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_fix: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
+    if (m.nh || m.npt || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
+    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
+    const int N = m.N;
+    std::vector<unsigned char> fs((size_t)3 * N, 0);
+    int n = 0;
+    if (fixed3N)
+        for (int i = 0; i < N; i++)
+            for (int k = 0; k < 3; k++)
+                if (fixed3N[3 * (size_t)m.perm[i] + k]) { fs[3 * (size_t)i + k] = 1; n++; }
+    if (n == 3 * N) return fail(SGPR_E_INVALID, "sgpr_md_fix: every component is held, nothing is left to move");
+    if (n == 0) { m.n_fixed = 0; m.fixed_sorted.clear(); return SGPR_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    if (m.fixed.alloc((size_t)3 * N)) return fail(SGPR_E_NODEVICE, "sgpr_md_fix: device allocation failed");
+    HIPCHK(hipMemcpy(m.fixed.p, fs.data(), (size_t)3 * N, hipMemcpyHostToDevice));
+    std::vector<double> v((size_t)3 * N);
+    HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < (size_t)3 * N; e++)
+        if (fs[e]) v[e] = 0.0;
+    HIPCHK(hipMemcpy(m.V.p, v.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    m.n_fixed = n;
+    m.fixed_sorted = fs;
+    return SGPR_OK;
+}
+
+// Nose-Hoover NVT for the run begun by sgpr_md_begin (kind = 1; 0 = back to the Langevin / velocity-Verlet step of
+// sgpr_md_begin's friction): what the reference's default md(dynamics="NPT", bulk_modulus=None) is — ase.md.npt.NPT with
+// pfactor = None and ttime = tdamp fs (cl/md.py:17, :131-166) — restated in md_nh_advance / md_nh_kernel.  kT as given to
+// sgpr_md_begin; tfact = 2 / (3 N kT ttime^2), desired kinetic energy 1.5 (N - 1) kT (ASE's constants).  Before the first
+// sgpr_md_run of the run.
+extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double kT)
+{
+    if (!h || (kind != 0 && kind != 1)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: kind is 0 (Langevin / velocity Verlet) or 1 (Nose-Hoover)");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
+    if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
+    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
+    if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
+    if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
+    // (held components, sgpr_md_fix: g = 3N - n_fixed degrees of freedom, none removed for the centre of mass — momentum is
+    // not conserved beside a held atom; the project's own definition, ASE's NPT takes no constraints)
+    const double g = (double)(3 * m.N - m.n_fixed);
+    const double tfact = 2.0 / (g * kT * ttime * ttime);
+    m.nh = true; m.ring = 4;
+    m.nh_c1 = m.dt * tfact; m.nh_c2 = 2.0 * m.dt * tfact; m.nh_K0 = m.n_fixed ? 0.5 * g * kT : 1.5 * (double)(m.N - 1) * kT;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
+    return SGPR_OK;
+}
+
+// A barostat for the Nose-Hoover run (sgpr_md_thermostat(kind = 1) first, before the first sgpr_md_run): ase.md.npt.NPT with
+// a pfactor, the moving cell of cl/md.py:131-166 — md_npt.inc has the scheme.  The cell of sgpr_md_begin must be upper
+// triangular (ASE's own condition) and periodic in all three directions.  pfactor = ptime^2 x bulk modulus and the external
+// stress (six Voigt components; a pressure P is (-P, -P, -P, 0, 0, 0)) in the units of the run; mask: nine zeros / ones (which
+// cell components may move); frac_traceless: 1 = all of the strain rate (with the mask), 0 = its trace only (`iso`).
+// Single rank only: the sharded last kernel (peer.inc) integrates at constant cell.
+extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *externalstress, const double *mask, double frac_traceless)
+{
+    if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.nh || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
+    if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
+    if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.n_fixed);
+    if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
+    if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
+    HIPCHK(hipSetDevice(h->device));
+    double c[9];
+    HIPCHK(hipMemcpy(c, m.cell.p, sizeof(c), hipMemcpyDeviceToHost));
+    if (!(c[3] == 0.0 && c[6] == 0.0 && c[7] == 0.0))
+        return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be upper triangular (h[1][0] = h[2][0] = h[2][1] = 0)");
+    const double det = (c[0] * c[4]) * c[8];
+    if (!(det > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell's diagonal must be positive");
+    if (m.npt_ring.alloc(4 * sizeof(NptSlot)) || m.Q.alloc((size_t)12 * m.N)) return fail(SGPR_E_NODEVICE, "sgpr_md_barostat: device allocation failed");
+    NptParams &p = m.np;
+    p = NptParams();
+    p.dt = m.dt; p.c1 = m.nh_c1; p.c2 = m.nh_c2; p.K0 = m.nh_K0;
+    p.pfact = 1.0 / (pfactor * det);
+    for (int k = 0; k < 6; k++) p.ext[k] = externalstress[k];
+    for (int k = 0; k < 9; k++) p.mask[k] = mask ? (mask[k] != 0.0 ? 1.0 : 0.0) : 1.0;
+    p.frac = frac_traceless;
+    for (int k = 0; k < 3; k++) p.pbc[k] = 1;
+    m.npt_pfactor = pfactor;
+    m.npt = true; m.npt_started = false;
+    return SGPR_OK;
+}
+
+// Fixed-order sum of md_npt_kernel / md_nh_kernel on the host: 256 strided partial sums, then a pairwise tree
+static double md_host_order_sum(const std::vector<double> &x)
+{
+    double p[256];
+    for (int t = 0; t < 256; t++) p[t] = 0.0;
+    for (size_t k = 0; k < x.size(); k++) p[k & 255] += x[k];
+    for (int w = 256; w > 1; w >>= 1)
+        for (int t = 0; t < w / 2; t++) p[t] = p[2 * t] + p[2 * t + 1];
+    return p[0];
+}
+
+// Start of a moving-cell trajectory (NPT.initialize(), autoforce_amd/npt.py): one synchronised evaluation of configuration 0,
+// then q_0 = x_0 h^-1 - 1/2 and q_(-1) by the backward step that is corrected twice (with ASE's test on the mean kinetic
+// energy per atom between the two corrections) on the host, in the operations of workloads.npt_moving_cell — once per
+// trajectory.  eta_0 = zeta_0 = 0 and therefore h_(-1) = h_1 = h_0; eta_(-1), zeta_(-1) are md_npt_kernel's (n = 0).
+static int md_npt_start(sgpr_model *h, hipStream_t st)
+{
+#pragma clang fp contract(off)
+    MdState &m = h->md;
+    const int N = m.N;
+    NptSlot s0 = {};
+    HIPCHK(hipMemcpy(s0.h, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
+    npt_matrices(m.np.dt, s0.h, s0.eta, 0.0, s0.hinv, s0.bm1, s0.bp1inv);
+    s0.thr2_keep = s0.thr2_reb = -1.0;
+    HIPCHK(hipMemset(m.npt_ring.p, 0, 4 * sizeof(NptSlot)));
+    HIPCHK(hipMemcpy(m.slot(0), &s0, sizeof(NptSlot), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.slot(1)->h, s0.h, 9 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
+    const int rc_ = run_checked(h, m.X.p, m.slot(0)->h, m.P.p, st);
+    if (rc_) return rc_;
+    h->warm = true;
+    std::vector<double> x((size_t)3 * N), v((size_t)3 * N), F((size_t)3 * N), q((size_t)3 * N), qp((size_t)3 * N), ke(N);
+    HIPCHK(hipMemcpy(x.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(F.data(), m.P.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));   // (packed forces: caller order)
+    const double dt = m.np.dt;
+    auto row_mul = [](const double *r, const double *mat, double *o) {
+#pragma clang fp contract(off)
+        for (int k = 0; k < 3; k++) o[k] = (r[0] * mat[k] + r[1] * mat[3 + k]) + r[2] * mat[6 + k];
+    };
+    for (int i = 0; i < N; i++) {
+        double t[3];
+        row_mul(&x[3 * (size_t)i], s0.hinv, t);
+        for (int k = 0; k < 3; k++) q[3 * (size_t)i + k] = t[k] - 0.5;
+    }
+    std::vector<double> vb = v;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int i = 0; i < N; i++) {
+            const int c = m.perm[i];
+            const double ms = m.mass_sorted[i];
+            const double *qi = &q[3 * (size_t)i];
+            double *qpi = &qp[3 * (size_t)i];
+            double t[3], a[3], al[3], num[3], qn[3], dq[3], vc[3];
+            row_mul(&vb[3 * (size_t)i], s0.hinv, t);
+            for (int k = 0; k < 3; k++) qpi[k] = qi[k] - dt * t[k];
+            for (int k = 0; k < 3; k++) a[k] = ((dt * dt) * F[3 * (size_t)c + k]) / ms;
+            row_mul(qpi, s0.bm1, t);
+            row_mul(a, s0.hinv, al);
+            for (int k = 0; k < 3; k++) num[k] = ((2.0 * qi[k]) + t[k]) + al[k];
+            row_mul(num, s0.bp1inv, qn);
+            for (int k = 0; k < 3; k++) dq[k] = qn[k] - qpi[k];
+            row_mul(dq, s0.h, t);
+            for (int k = 0; k < 3; k++) vc[k] = t[k] / (2.0 * dt);
+            ke[i] = (ms * (vc[0] * vc[0]) + ms * (vc[1] * vc[1])) + ms * (vc[2] * vc[2]);
+            for (int k = 0; k < 3; k++) vb[3 * (size_t)i + k] = (v[3 * (size_t)i + k] - vc[k]) + v[3 * (size_t)i + k];
+        }
+        if (0.5 * md_host_order_sum(ke) / N < 1e-5) break;
+    }
+    HIPCHK(hipMemcpy(m.Q.p, q.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.Q.p + (size_t)9 * N, qp.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    // the grids of h_0 and h_1 and the rebuild rule of evaluation 0 (which rebuilds: the first of its call)
+    hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p, (const double *)nullptr,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)h->d_cell0.p, -1,
+                       (const int *)m.halt.p, -1, (double *)nullptr, (double *)nullptr);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    m.npt_started = true;
+    return SGPR_OK;
+}
+
+// Cell and strain rate of a moving-cell run, SGPR_MD_CELL = 18 doubles (h[9], eta[9]) per configuration `first` ...
+// `first + count - 1` (indices of the trajectory: 0 = the configuration of sgpr_md_begin): those the last sgpr_md_run
+// evaluated, and the current one — the cell sgpr_md_state's positions belong to.
+extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out)
+{
+    if (!h || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_cells: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !(m.npt || m.relax)) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat (or sgpr_md_relax) first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const long long have = (long long)(m.cells.size() / SGPR_MD_CELL);
+    for (int r = 0; r < count; r++) {
+        const long long n = (long long)first + r;
+        double *o = out + (size_t)SGPR_MD_CELL * r;
+        if (n >= m.cells_first && n < m.cells_first + have)
+            memcpy(o, m.cells.data() + (size_t)SGPR_MD_CELL * (n - m.cells_first), sizeof(double) * SGPR_MD_CELL);
+        else if (m.relax && n == m.t)   // a relaxation: the cell and, in the place of eta, the deformation gradient D
+            HIPCHK(hipMemcpy(o, m.rx_cells.p + (size_t)RLX_CELL * (n % RLX_RING), RLX_CELL * sizeof(double), hipMemcpyDeviceToHost));
+        else if (!m.relax && n == m.t && m.npt_started) {
+            HIPCHK(hipMemcpy(o, m.slot(n)->h, 9 * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(o + 9, m.slot(n)->eta, 9 * sizeof(double), hipMemcpyDeviceToHost));
+        } else if (!m.relax && n == 0 && m.t == 0) {
+            HIPCHK(hipMemcpy(o, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
+            for (int k = 0; k < 9; k++) o[9 + k] = 0.0;
+        } else
+            return fail(SGPR_E_INVALID, "sgpr_md_cells: configuration %lld is neither the current one (%lld) nor one of the last run's", n, m.t);
+    }
+    return SGPR_OK;
+}
+
+// FIRE relaxation for the run begun by sgpr_md_begin (whose masses, velocities, dt, friction and kT it ignores), before the
+// first sgpr_md_run: the optimizer of ase/optimize/fire.py on the positions and, with move_cell, on the cell through
+// ase.constraints.UnitCellFilter's coordinates — md_relax.inc has the scheme, workloads.fire_relax is the host twin.
+// fire: dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (NULL: ASE's defaults); mask6: which of the six Voigt components
+// xx yy zz yz xz xy of the cell may move (NULL: all).  sgpr_md_run then evaluates, moves, and stops with halt code 3 at the
+// first configuration whose largest generalised force is below fmax — the state IS that configuration, nothing moved.  Single
+// rank only.
+static const double RLX_ASE[8] = {0.1, 0.2, 1.0, 5.0, 1.1, 0.5, 0.1, 0.99};
+
+static int md_relax_init_state(sgpr_model *h)
+{
+    MdState &m = h->md;
+    double s[RLX_LEN] = {};
+    HIPCHK(hipMemcpy(s, m.rx_state.p, sizeof(s), hipMemcpyDeviceToHost));
+    s[RLX_DT] = m.rp.dt0; s[RLX_A] = m.rp.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
+    for (int k = 0; k < 9; k++) s[RLX_VC + k] = 0.0;
+    s[RLX_ALPHA] = s[RLX_BETA] = s[RLX_CD] = 0.0;
+    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.V.p, 0, sizeof(double) * 3 * (size_t)m.N));
+    return SGPR_OK;
+}
+
+extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_relax: call sgpr_md_begin first");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
+    if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
+    if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
+    if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
+    const double *fp = fire ? fire : RLX_ASE;
+    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
+        return fail(SGPR_E_INVALID, "sgpr_md_relax: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.N;
+    RelaxParams p = {};
+    HIPCHK(hipMemcpy(p.h0, m.cell.p, sizeof(p.h0), hipMemcpyDeviceToHost));
+    if (move_cell) {
+        if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_relax: a cell that moves must be periodic in all three directions");
+        if (!(fabs(rlx_det(p.h0)) > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: the cell is singular");
+    }
+    p.fmax2 = fmax * fmax;
+    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
+    double m6[6];
+    for (int k = 0; k < 6; k++) m6[k] = mask6 ? (mask6[k] != 0.0 ? 1.0 : 0.0) : 1.0;
+    const double M[9] = {m6[0], m6[5], m6[4], m6[5], m6[1], m6[3], m6[4], m6[3], m6[2]};
+    for (int k = 0; k < 9; k++) p.mask[k] = M[k];
+    p.cf = (double)N;
+    p.cell = move_cell ? 1 : 0;
+    // rings of RLX_RING slots, every slot a valid configuration from the start (what runs behind a halt evaluates stale slots)
+    std::vector<double> x0((size_t)3 * N);
+    HIPCHK(hipMemcpy(x0.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    if (m.X.alloc((size_t)3 * N * RLX_RING) || m.P.alloc((size_t)RLX_RING * (size_t)sgpr_packed_len(N)) || m.rx_state.alloc(RLX_LEN) ||
+        m.rx_ref.alloc((size_t)3 * N) || m.rx_cells.alloc((size_t)RLX_RING * RLX_CELL))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_relax: device allocation failed");
+    double slot[RLX_CELL] = {};
+    for (int k = 0; k < 9; k++) { slot[k] = p.h0[k]; slot[9 + k] = (k % 4 == 0) ? 1.0 : 0.0; }
+    for (int r = 0; r < RLX_RING; r++) {
+        HIPCHK(hipMemcpy(m.X.p + (size_t)3 * N * r, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.rx_cells.p + (size_t)RLX_CELL * r, slot, sizeof(slot), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(m.rx_ref.p, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    double s[RLX_LEN] = {};
+    for (int k = 0; k < 9; k++) s[RLX_XC + k] = (k % 4 == 0) ? p.cf : 0.0;
+    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    m.rp = p;
+    m.relax = true; m.relax_started = false; m.ring = RLX_RING;
+    m.cells.clear(); m.cells_first = 0;
+    return md_relax_init_state(h);
+}
+
+// optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (the reference's relax(clear_hist=True) behind a model update)
+extern "C" int sgpr_md_relax_reset(sgpr_model *h)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.relax) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: call sgpr_md_begin and sgpr_md_relax first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return md_relax_init_state(h);
+}
+
+// ---- the look-ahead driver of the run functions (sgpr_md_run and md_relax_run, its form for a relaxation) ----
+// The halt words are three ints in mapped host memory, each the step (h->step_count) of the evaluation that halted the run or
+// MD_HALT_NONE: [0] the covloss gate, [1] a capacity overflow, [2] a relaxation's convergence (no MD kernel writes it); the
+// device has its own copy of the first two (m.halt).  The earliest one halted the run.
+static const int MD_HALT_NONE = 0x7fffffff;
+static int md_halt_step(const MdState &m) { return std::min(std::min(m.halt_host[0], m.halt_host[1]), m.halt_host[2]); }
+
+// For the length of a call the positions handed to the binning kernel are in sorted order already (the rings); on every way
+// out the handle is an ordinary one again: no pre-binned configuration, no grid of a moving cell.
+struct MdBinIdentity {
+    sgpr_model *h;
+    explicit MdBinIdentity(sgpr_model *h_) : h(h_) { h->bin_identity = true; }
+    ~MdBinIdentity() { h->bin_identity = false; h->pre_valid = false; h->step_grid = nullptr; }
+};
+
+// Sets a call up: the scalar ring (device rows, a mapped mark word per evaluation, the page-locked buffer the rows are copied
+// out to) grown to the call and zeroed, the per-evaluation cell record where the run has one (NPT, relaxation), the halts armed.
+static int md_prepare_call(sgpr_model *h, int nevals, hipStream_t st, bool want_cells)
+{
+    MdState &m = h->md;
+    const size_t rows = (size_t)nevals + 1;
+    if (m.scal_rows < rows) {
+        if (m.mark) (void)hipHostFree(m.mark);
+        if (m.scal_pin) (void)hipHostFree(m.scal_pin);
+        m.mark = nullptr; m.scal_pin = nullptr; m.scal_rows = 0;
+        if (m.scal_d.alloc((size_t)SGPR_MD_SCAL * rows, false) ||
+            hipHostMalloc((void **)&m.mark, sizeof(int) * rows, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&m.mark_dev, m.mark, 0) != hipSuccess ||
+            hipHostMalloc((void **)&m.scal_pin, sizeof(double) * SGPR_MD_SCAL * rows, hipHostMallocDefault) != hipSuccess)
+            return fail(SGPR_E_NODEVICE, "sgpr_md_run: no memory for the scalar ring");
+        m.scal_rows = rows;
+    }
+    HIPCHK(hipMemsetAsync(m.scal_d.p, 0, sizeof(double) * SGPR_MD_SCAL * rows, st));
+    memset(m.mark, 0, sizeof(int) * rows);
+    if (want_cells) {
+        if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
+    }
+    m.halt_host[0] = m.halt_host[1] = m.halt_host[2] = MD_HALT_NONE;   // (page-locked: the source of the copy outlives the call)
+    HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    return SGPR_OK;
+}
+
+// The host runs AHEAD of the device by at most this many evaluations: before evaluation j is enqueued, evaluation j - LA must
+// have set its mark (one int per evaluation in mapped host memory, written by the reducer of the overflow word: the ONLY
+// posted write of a step — the sixteen scalars stay in device memory and are copied out once per call), or the run must
+// have halted.  A halt therefore leaves at most LA + 1 evaluations in the queue (they exit at once or
+// recompute a discarded step), where a fixed chunk of 16 left up to 32 (14 ms per halt at 16384 atoms).  LA = 6 at 4096
+// atoms (the host needs ~25 us to enqueue a step of ~80 us), 2 at 16384 (~0.5 ms per step).
+static int md_look_ahead(int N) { return std::min(6, std::max(2, (int)lround(24576.0 / std::max(N, 1)))); }   // (fewer for large frames: their steps are long)
+
+// The throttle: spins until evaluation `e` of the call has set its mark or a halt word is set (*halted).  Both are posted
+// writes of the device into mapped host memory: the wait costs no call into the runtime — but a dead queue writes neither, so
+// every 16384 spins the stream is asked: one that is empty with the mark still unset, or in error, ends the wait with an error.
+static int md_wait_for(const MdState &m, hipStream_t st, int e, bool *halted)
+{
+    const volatile int *mark = m.mark + e, *hh = m.halt_host;
+    auto running = [hh] { return hh[0] == MD_HALT_NONE && hh[1] == MD_HALT_NONE && hh[2] == MD_HALT_NONE; };
+    unsigned spins = 0;
+    while (*mark == 0 && running()) {
+        if ((++spins & 0x3fffu) == 0) {  // (a dead queue must not hang the host)
+            const hipError_t q = hipStreamQuery(st);
+            if (q == hipSuccess && *mark == 0) return fail(SGPR_E_NODEVICE, "sgpr_md_run: the queue drained without evaluation %d reporting", e);
+            if (q != hipSuccess && q != hipErrorNotReady) return fail(SGPR_E_NODEVICE, "sgpr_md_run: %s", hipGetErrorString(q));
+        }
+    }
+    *halted = !running();
+    return SGPR_OK;
+}
+
+// Enqueues evaluations 0 ... nevals - 1 of a call behind the throttle, until the run halts; *enq: how many.  one(j) enqueues
+// evaluation j and returns an error code (a callable inlined here: nothing is allocated or called indirectly per evaluation).
+template <typename One>
+static int md_enqueue_ahead(sgpr_model *h, int nevals, hipStream_t st, int *enq, One one)
+{
+    const MdState &m = h->md;
+    const int LA = md_look_ahead(m.N);
+    *enq = 0;
+    int rc_ = SGPR_OK;
+    bool halted = false;
+    for (int j = 0; j < nevals; j++) {
+        if (j >= LA) rc_ = md_wait_for(m, st, j - LA, &halted);
+        if (rc_ || halted) break;
+        rc_ = one(j);
+        if (rc_) break;
+        *enq = j + 1;
+    }
+    if (rc_) (void)hipStreamSynchronize(st);   // (the queue is drained before the error is reported)
+    return rc_;
+}
+
+// The scalars travel behind the last kernel: ONE wait for the whole call (the halt words are in mapped host memory); then the
+// cell record of the evaluations enqueued, where the run has one.
+static int md_collect(sgpr_model *h, int enq, hipStream_t st, const double *scalars, bool want_cells)
+{
+    MdState &m = h->md;
+    if (scalars && enq > 0)
+        HIPCHK(hipMemcpyAsync(m.scal_pin, m.scal_d.p, sizeof(double) * SGPR_MD_SCAL * (size_t)enq, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (want_cells) {
+        m.cells.assign((size_t)SGPR_MD_CELL * (size_t)enq, 0.0);
+        m.cells_first = m.t;
+        if (enq > 0) HIPCHK(hipMemcpy(m.cells.data(), m.cells_d.p, sizeof(double) * SGPR_MD_CELL * (size_t)enq, hipMemcpyDeviceToHost));
+    }
+    return SGPR_OK;
+}
+
+// What a call leaves behind its wait.  k: the evaluation, relative to this call, that halted the run (-1: none); code: 0 none,
+// 1 covloss gate, 2 overflow, 3 converged; done: the evaluations whose results stand, the halting one included unless it
+// overflowed.  m.t moves on: after a halt the state is configuration k, not evaluated as far as the NEXT call goes; otherwise
+// every evaluation stands and the state is the next configuration — with final_eval the last one evaluated.
+struct MdHalt { int k = -1, code = 0, done = 0; };
+static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval, bool want_cells, MdHalt *out)
+{
+    MdState &m = h->md;
+    const int hv = md_halt_step(m);
+    MdHalt &r = *out;
+    r.done = enq;
+    if (hv != MD_HALT_NONE) {
+        r.k = hv - (int)step0;
+        if (r.k < 0 || r.k >= enq) return fail(SGPR_E_INVALID, "sgpr_md_run: inconsistent halt record (%d of %d)", r.k, enq);
+        r.code = m.halt_host[1] == hv ? 2 : (m.halt_host[0] == hv ? 1 : 3);
+        r.done = r.k + 1;
+        m.t += r.k;
+        // a capacity overflowed: the next call's checked pass grows it, and the overflowing evaluation's own results are void
+        if (r.code == 2) { h->warm = false; r.done -= 1; }
+    } else
+        m.t += final_eval ? enq - 1 : enq;
+    if (want_cells) m.cells.resize((size_t)SGPR_MD_CELL * (size_t)std::max(r.done, 0));
+    return SGPR_OK;
+}
+
+// sgpr_md_run for a relaxation: every evaluation is the plain step (its own binning kernel, the plain last kernel) with
+// md_fire_kernel and md_fire_move_kernel behind it.  The halts — covloss gate (1), capacity overflow (2), convergence (3) — are
+// decided by md_fire_kernel on the evaluation itself, before anything moves: what the host has enqueued behind a halt (its
+// look-ahead) evaluates stale slots of the rings and changes nothing.  final_eval: the last evaluation moves nothing and leaves
+// the optimizer as it was.
+static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
+{
+    MdState &m = h->md;
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rb = md_rebind(h)) return rb;
+    hipStream_t st = h->stream;
+    const int N = m.N, RG = RLX_RING;
+    const size_t plen = (size_t)sgpr_packed_len(N);
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    MdBinIdentity guard(h);
+    if (const int rp = md_prepare_call(h, nevals, st, true)) return rp;
+    auto cell_of = [&](long long n) -> double * { return m.rx_cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
+    m.relax_started = true; m.started = true;
+    if (!h->warm) {
+        const int sw = (int)(m.t % RG);
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.t), m.P.p + plen * sw, st);
+        if (rc_) return rc_;
+        h->warm = true;
+    }
+    m.chain_ok = false;
+    h->lists_valid = false;
+    h->pre_valid = false;
+    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    const unsigned step0 = h->step_count;
+    const double gate = ediff > 0.0 ? ediff : 1e300;
+    int enq = 0;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
+        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG;
+        double *packed = m.P.p + plen * sl;
+        const int re = enqueue_step(h, m.X.p + (size_t)3 * N * sl, cell_of(m.t + j), packed, st, nullptr);
+        if (re) return re;
+        h->lists_valid = true;
+        const bool stay = final_eval && j == nevals - 1;
+        // (held components, sgpr_md_fix: the FIX forms; without a mask the kernels of a run without one)
+        hipLaunchKernelGGL(m.n_fixed ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p,
+                           (const double *)packed, (const int *)h->d_perm.p,
+                           (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host_dev,
+                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark_dev + j, stay ? 1 : 0,
+                           m.fix());
+        if (!stay)
+            hipLaunchKernelGGL(m.n_fixed ? md_fire_move_kernel<true> : md_fire_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell,
+                               (const double *)m.rx_state.p,
+                               (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.rx_ref.p, m.X.p + (size_t)3 * N * sn,
+                               (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j),
+                               m.fix());
+        return SGPR_OK;
+    });
+    if (rc_) return rc_;
+    if (const int rc = md_collect(h, enq, st, scalars, true)) return rc;
+    MdHalt r;
+    if (const int rd = md_decode_halt(h, step0, enq, final_eval, true, &r)) return rd;
+    if (scalars && r.done > 0) memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
+    m.evaluated = r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0);
+    *evals_done = r.done;
+    if (halt_code) *halt_code = r.code;
+    h->lists_valid = false;
+    return SGPR_OK;
+}
+
+// Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last
+// the integrator moves on with the next row of `noise` ([nevals][N][3] standard normal deviates, caller atom order; null:
+// velocity Verlet).  Stops at the first evaluation whose largest covloss reaches `ediff` (<= 0: never): *evals_done
+// counts the evaluations whose results stand, the halting one included; the state then IS that configuration (its
+// forces are evaluated again by the next call — after the caller has updated the model).
+// scalars: [nevals][SGPR_MD_SCAL] = E, virial(9), overflow, largest covloss, sum m v^2 (closed | before the closing half
+// kick), 0, 0 per evaluation.
+extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars,
+                           int *evals_done, int *halt_code)
+{
+    if (!h || nevals <= 0 || !evals_done) return fail(SGPR_E_INVALID, "sgpr_md_run: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_run: call sgpr_md_begin first");
+    if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
+    if (m.relax) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rb = md_rebind(h)) return rb;
+    if (m.world > 1 && !(peer_on(h) && h->peer.world == m.world && h->peer.rank == m.rank))
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the run was begun on %d ranks, the exchange between them is gone", m.world);
+    hipStream_t st = h->stream;
+    const int N = m.N;
+    const size_t plen = (size_t)sgpr_packed_len(N);
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    m.started = true;
+    MdBinIdentity guard(h);
+    if (const int rp = md_prepare_call(h, nevals, st, m.npt)) return rp;   // (the cell record: a moving cell only)
+    if (noise) {
+        if (m.noise.alloc((size_t)nevals * 3 * N) || m.noise_raw.alloc((size_t)nevals * 3 * N))
+            return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * (size_t)nevals * 3 * N, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
+    }
+    // the first evaluation sizes the capacities for this configuration if nothing has yet (synchronised, results discarded)
+    const int RG = m.ring, s0 = (int)(m.t % RG);
+    if (m.npt) { m.np.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.np.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
+    if (m.npt && !m.npt_started)
+        if (const int rs = md_npt_start(h, st)) return rs;
+    // (moving cell: the cell of configuration n is in the ring)
+    auto cell_of = [&](long long n) -> const double * { return m.npt ? m.slot(n)->h : m.cell.p; };
+    if (!h->warm) {
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, cell_of(m.t), m.P.p + plen * s0, st);
+        if (rc_) return rc_;
+        h->warm = true;
+    }
+    // the continuation of the last call (nothing else ran on the handle since, no re-binding, no option touched): its candidate
+    // lists stand and its last kernel has binned this call's first configuration.  Otherwise: whatever ran in between — a model
+    // update evaluates other frames — may have left other lists and bin populations (a run that halted: those of a step that
+    // never ran)
+    const bool chain = m.chain_ok && h->warm && h->step_count == m.chain_step && h->bind_gen == m.chain_bind && h->opt_gen == m.chain_opt &&
+                       m.t == m.chain_t && m.chain_pos == m.X.p + (size_t)3 * N * s0;
+    m.chain_ok = false;
+    if (chain) {
+        h->lists_valid = true;
+        h->pre_valid = true; h->pre_pos = m.chain_pos; h->pre_cell = cell_of(m.t); h->pre_step = h->step_count;
+    } else {
+        h->lists_valid = false;
+        h->pre_valid = false;
+        HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    }
+    const unsigned step0 = h->step_count;
+    const unsigned epoch0 = h->peer.epoch;
+    const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
+    int enq = 0;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
+        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+        StepNext nx;
+        nx.mode = 2;
+        nx.pos_next = m.X.p + (size_t)3 * N * sn;
+        FinNext &x = nx.md;
+        memset(&x, 0, sizeof(x));
+        x.x_cur = m.X.p + (size_t)3 * N * sl; x.v_cur = m.V.p + (size_t)3 * N * sl;
+        x.x_next = m.X.p + (size_t)3 * N * sn; x.v_next = m.V.p + (size_t)3 * N * sn;
+        x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise ? m.noise.p + (size_t)j * 3 * N : nullptr;
+        x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
+        if (m.nh) {
+            x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
+            x.x_prev = m.X.p + (size_t)3 * N * sp; x.v_now = m.V.p + (size_t)3 * N * sl;
+            // (v_cur: what the integrator holds when it asks for the forces — ASE sets the momenta of step n after its force
+            // call: v_(n-1), the caller's v_0 the first time; its kinetic energy is scalars[13], the calculator's log line)
+            if (m.t + j > 0) x.v_cur = m.V.p + (size_t)3 * N * sp;
+            x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
+        }
+        if (m.npt) {
+            x.npt_cur = m.slot(m.t + j); x.npt_next = m.slot(m.t + j + 1);
+            x.q_cur = m.Q.p + (size_t)3 * N * sl; x.q_prev = m.Q.p + (size_t)3 * N * sp; x.q_next = m.Q.p + (size_t)3 * N * sn;
+            nx.cell_next = x.npt_next->h;
+            h->step_grid = &x.npt_cur->grid;
+        }
+        x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
+        x.fixed = m.fix();
+        x.ke_cur = m.KE.p + (size_t)2 * N * sl; x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
+        x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
+        x.ediff = ediff > 0.0 ? ediff : 1e300;
+        x.halt = m.halt.p; x.halt_host = m.halt_host_dev;
+        x.scal_cur = m.scal_d.p + (size_t)SGPR_MD_SCAL * j; x.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (j > 0 ? j - 1 : 0);
+        x.mark_cur = m.mark_dev + j;
+        // (the last evaluation of a `final` run integrates speculatively too: its outcome is not adopted below)
+        const int re = enqueue_step(h, x.x_cur, cell_of(m.t + j), m.P.p + plen * sl, st, &nx);
+        if (re) return re;
+        h->lists_valid = true;  // (the first evaluation rebuilt the candidates; an overflow halts the run: FinNext)
+        if (!h->pre_valid) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the fused last kernel is not available for this model / frame (sharded "
+                                        "without the library's own exchange, graph capture or a zero skin)");
+        if (m.npt)  // zeta, eta and the matrices of the next configuration, the cell after it (md_npt.inc)
+            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p,
+                               (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + (size_t)3 * N * sl), (const double *)m.mass.p,
+                               (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.t + j) & 0x3fffffff), (const int *)m.halt.p,
+                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j);
+        else if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
+            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
+                               m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
+        return SGPR_OK;
+    });
+    if (rc_) return rc_;
+    if (enq > 0) {  // the lagged reductions of the last evaluation enqueued
+        FinArgs f = {};
+        f.N = N;
+        const int sl = (int)((m.t + enq - 1) % RG);
+        f.nx.mode = 3; f.nx.step = (int)(step0 + enq);
+        f.nx.ke_prev = m.KE.p + (size_t)2 * N * sl; f.nx.packed_prev = m.P.p + plen * sl;
+        f.nx.ediff = ediff > 0.0 ? ediff : 1e300; f.nx.halt = m.halt.p; f.nx.halt_host = m.halt_host_dev;
+        f.nx.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (enq - 1);
+        hipLaunchKernelGGL(finalize_tail_kernel, dim3(2), dim3(256), 0, st, f);
+    }
+    if (const int rc = md_collect(h, enq, st, scalars, m.npt)) return rc;
+    if (const int pc = peer_check(h)) return pc;
+    // Where the run goes on: when every evaluation stands and the last one was integrated, the handle is left as the last kernel
+    // left it — the next sgpr_md_run continues from there (chain, above).  Otherwise the last kernel enqueued has binned a step
+    // that will not run — or, after a halt, the bins are those of a discarded speculative step: whoever uses the handle next
+    // starts from clean bin populations.
+    const bool keep_chain = md_halt_step(m) == MD_HALT_NONE && !final_eval && enq == nevals && h->pre_valid;
+    const double *keep_pos = h->pre_pos;
+    if (!keep_chain) HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    MdHalt r;
+    if (const int rd = md_decode_halt(h, step0, enq, final_eval, m.npt, &r)) return rd;
+    // exchanges that took place: the ranks have enqueued different numbers of evaluations behind the halt, all of them
+    // skipped on the device (peer_push_kernel): a covloss halt at evaluation k is seen by evaluation k + 1 (or by the
+    // tail kernel when k is the last), an overflow by evaluation k itself — the same count on every rank
+    if (r.code && peer_on(h)) {
+        h->peer.epoch = epoch0 + (unsigned)(r.code == 2 ? r.k + 1 : std::min(nevals, r.k + 2));
+        if (getenv("SGPR_PEER_TRACE"))
+            fprintf(stderr, "[sgpr peer] rank %d md_run halt: code %d k %d enq %d nevals %d -> epoch %u\n", h->peer.rank, r.code, r.k, enq, nevals, h->peer.epoch);
+    }
+    if (keep_chain) {
+        m.chain_ok = true; m.chain_step = h->step_count; m.chain_bind = h->bind_gen; m.chain_opt = h->opt_gen; m.chain_t = m.t;
+        m.chain_pos = keep_pos;
+    }
+    if (scalars && r.done > 0) {
+        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
+        if (!m.nh)   // (Nose-Hoover: zeta and its time integral of the evaluation's configuration; else spare)
+            for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
+    }
+    m.evaluated = r.code == 1 || (r.code == 0 && final_eval != 0);
+    *evals_done = r.done;
+    if (halt_code) *halt_code = r.code;
+    h->lists_valid = false;
+    return SGPR_OK;
+}
+
+// One slot of a device ring (N rows of three, sorted order) in caller atom order — through the run's OWN permutation: the
+// handle may be bound to another frame by now
+static int md_fetch_rows(const MdState &m, const double *slot_dev, double *out)
+{
+    std::vector<double> buf((size_t)3 * m.N);
+    HIPCHK(hipMemcpy(buf.data(), slot_dev, sizeof(double) * 3 * m.N, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m.N; i++)
+        for (int k = 0; k < 3; k++) out[3 * (size_t)m.perm[i] + k] = buf[3 * (size_t)i + k];
+    return SGPR_OK;
+}
+
+// State of the run in caller atom order: positions of the current configuration, its velocities BEFORE the closing half
+// kick (`pending` says whether one is due: v = v_pre + (dt/2) F / m once F is known), and — when the configuration has
+// been evaluated by the last sgpr_md_run (a halted or `final` run) — its packed results [F | beta | E | virial | overflow].
+extern "C" int sgpr_md_state(sgpr_model *h, double *positions, double *velocities_pre, int *pending, double *packed,
+                             int which /*0: the current configuration; -1: the one evaluated before it*/)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_state: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_state: call sgpr_md_begin first");
+    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_state: which = 0 or -1");
+    if (which == -1 && m.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_state: no earlier configuration");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.N;
+    const int sl = (int)((m.t + which + m.ring) % m.ring);
+    int rc_ = positions ? md_fetch_rows(m, m.X.p + (size_t)3 * N * sl, positions) : SGPR_OK;
+    // (a relaxation: the optimizer's velocity of the atoms' coordinates, one slot)
+    if (!rc_ && velocities_pre) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * (m.relax ? 0 : sl), velocities_pre);
+    // Nose-Hoover: what the integrator holds when it asks for the forces of configuration n is the centred velocity of
+    // configuration n - 1 (ASE sets the momenta of a step after its force call); sgpr_md_velocities has v_n itself
+    if (!rc_ && m.nh && velocities_pre && (m.t + which) > 0) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * ((sl + m.ring - 1) % m.ring), velocities_pre);
+    if (rc_) return rc_;
+    if (pending) *pending = (!m.nh && !m.relax && (m.t + which) > 0) ? 1 : 0;   // (every configuration but the start of the trajectory)
+    if (packed) HIPCHK(hipMemcpy(packed, m.P.p + (size_t)sgpr_packed_len(N) * sl, sizeof(double) * sgpr_packed_len(N), hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// The velocities an observer of the trajectory sees at the current configuration, which the last sgpr_md_run must have
+// evaluated (it halted there, or ran with final_eval): Langevin / velocity Verlet: the closing half kick applied; Nose-Hoover:
+// the centred velocity (x_(n+1) - x_(n-1)) / 2 dt.  Caller atom order.
+extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
+{
+    if (!h || !velocities) return fail(SGPR_E_INVALID, "sgpr_md_velocities: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_velocities: call sgpr_md_begin first");
+    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
+    if (!m.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.N, sl = (int)(m.t % m.ring);
+    if (const int rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * sl, velocities)) return rc_;
+    std::vector<double> F;
+    const bool kick = !m.nh && m.t > 0;
+    if (kick) {
+        F.resize((size_t)3 * N);   // (packed forces are in caller order)
+        HIPCHK(hipMemcpy(F.data(), m.P.p + (size_t)sgpr_packed_len(N) * sl, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < N; i++) {
+        const size_t c = m.perm[i];
+        for (int k = 0; k < 3; k++)
+            if (m.n_fixed && m.fixed_sorted[3 * (size_t)i + k]) velocities[3 * c + k] = 0.0;   // (a held component: F = 0, v = 0)
+            else if (kick) velocities[3 * c + k] = velocities[3 * c + k] + m.hdt * F[3 * c + k] / m.mass_sorted[i];
+    }
+    return SGPR_OK;
+}
+
+// Deviates of the integrator on the device: seed != 0 makes sgpr_md_run (called with noise = NULL) draw the standard
+// normal deviate of (configuration index, atom, component) from a counter-based generator; 0 switches that off.
+extern "C" int sgpr_md_seed(sgpr_model *h, uint64_t seed)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_seed: bad arguments");
+    h->md.seed = seed;
+    return SGPR_OK;
+}
+
+// The deviates sgpr_md_run uses to move configurations [t_first, t_first + count) on, out[count][N][3] in caller atom
+// order (for a host-side twin of a seeded run).
+extern "C" int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, double *out)
+{
+    if (!h || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_deviates: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || m.seed == 0) return fail(SGPR_E_INVALID, "sgpr_md_deviates: call sgpr_md_begin and sgpr_md_seed first");
+    HIPCHK(hipSetDevice(h->device));
+    ScopedBuf<double> d;
+    if (d.alloc((size_t)count * 3 * m.N, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_deviates: device allocation failed");
+    hipLaunchKernelGGL(md_deviates_kernel, dim3(1024), dim3(256), 0, h->stream, m.N, count, m.seed, (long long)t_first, d.p);
+    HIPCHK(hipMemcpy(out, d.p, sizeof(double) * (size_t)count * 3 * m.N, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+extern "C" int sgpr_md_end(sgpr_model *h)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_end: bad arguments");
+    h->md.active = false;
+    return SGPR_OK;
+}
