@@ -33,7 +33,7 @@ except ImportError:
     GPa = 1.0 / 160.21766208
     HAVE_ASE = False
 
-from .model import Local, SGPRModel
+from .model import Local, SGPRModel, recorded_indices
 from .posterior import EPS, Frame, PosteriorPotential
 from .sgprio import SgprIO
 from .sharding import pack_partial, rank_of_atoms, unpack_total
@@ -523,8 +523,10 @@ class ActiveCalculator(Calculator):
             c.adjust_forces(atoms, ones)
         return ones == 0.0
 
+    RECORD_BYTES = 256 << 20   # the frame record of one md_run call (run_md, run_relax) stays within this much device memory
+
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -538,6 +540,13 @@ class ActiveCalculator(Calculator):
         k = 0 mod sync_every end a batch and atoms.positions / velocities are theirs when they are yielded (a trajectory
         writer's loginterval, cl/md.py:24); atoms.positions / velocities are current at every yield that follows an update
         and at the end.  Falls back to the host loop (workloads.langevin_nvt) where md_on_device_ok() says no.
+        record (with sync_every, the device loop on one rank): the device copies the configuration of every step
+        k = 0 mod sync_every into a frame record behind its evaluation (SGPRModel.md_record) and batches are NOT cut at those
+        steps: the frames of a batch are fetched behind its single wait, and atoms.positions / velocities (the cell under NPT)
+        are set from step k's frame before step k is yielded — what a caller observes at those yields, after updates and at
+        the end is what the cutting path shows, but the loop keeps its look-ahead, its chained calls and its growing batch
+        (with the reference's default loginterval = 1 the cutting path is one md_run call per step).  A batch's record stays
+        within RECORD_BYTES.  record=False, and sharded runs by themselves: batches end at every multiple of sync_every.
         tdamp_fs: Nose-Hoover NVT with that damping time instead of Langevin — the reference's DEFAULT dynamics,
         md(dynamics="NPT", bulk_modulus=None) = ase.md.npt.NPT(pfactor=None, ttime=tdamp fs) (cl/md.py:17, :131-166); no
         deviates, `friction` / `rng` / `seed` unused; host loop: workloads.nose_hoover_nvt.
@@ -620,11 +629,17 @@ class ActiveCalculator(Calculator):
         # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
+        rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1)
+        if rec:   # (positions and the velocities the integrator holds; a batch of at most rec_max frames)
+            eng.md_record(sync_every, velocities=True, results=False)
+            rec_max = max(1, self.RECORD_BYTES // (48 * N))
         ke_before = None   # (moving cell: sum m v^2 of the configuration before the row at hand — the velocities calculate() is handed)
         batch = min(8, chunk)   # evaluations per md_run call: grows while nothing halts the device, shrinks back after a halt
         while done <= steps:    # (every call uploads its rows of deviates; a halt throws the unused ones' upload away)
             n = 1 if skip_gate else min(batch, steps + 1 - done)
-            if sync_every and not skip_gate:
+            if rec:
+                n = max(1, min(n, rec_max * sync_every - done % sync_every))
+            elif sync_every and not skip_gate:
                 n = min(n, sync_every - done % sync_every if done % sync_every else 1)   # (… a batch ends on a multiple)
             final = done + n == steps + 1
             need = 0 if (on_device_rng or nh) else (n - 1 if final else n)
@@ -636,7 +651,7 @@ class ActiveCalculator(Calculator):
             sc, code = eng.md_run(n, noise, ediff=gate, final=final)
             accepted = len(sc) - 1 if code == 1 else len(sc)
             share = (time.time() - t_run) / max(accepted, 1)
-            lines, out = [], []
+            lines, out, counts, step_now = [], [], [], self.step
             for r in sc[:accepted]:
                 upd, wall = False, share
                 if skip_gate:      # (the configuration calculate() has just dealt with, evaluated again with the new model:
@@ -645,16 +660,32 @@ class ActiveCalculator(Calculator):
                     # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a
                     # moving cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
                     ke_line = r[13] if (not npt or ke_before is None) else ke_before
-                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]), "")))
-                    self.step += 1
+                    lines.append((step_now, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]), "")))
+                    step_now += 1
                 ke_before = r[12]
                 out.append((done, float(r[0]), float(r[12] / (dof * kB)), upd, wall))
+                counts.append(step_now)
                 done += 1
             self._log_lines(lines)
-            if sync_every and out and out[-1][0] % sync_every == 0 and code != 1:
-                # the configuration of the batch's last row: the device has moved on to the next one unless the run is over
-                put(eng.md_state(which=0 if final else -1), "velocities_pre")
-            yield from out
+            if rec:
+                # the frames of the accepted rows at multiples of sync_every, each put before its row is yielded; self.step is
+                # what it is behind that row (on the cutting path a batch ends there)
+                fr = eng.md_frames(reuse=True) if recorded_indices(done - accepted, len(sc), code, sync_every) else dict(index=())
+                at = {int(i): k for k, i in enumerate(fr["index"])}
+                for o, cnt in zip(out, counts):
+                    self.step = cnt
+                    if o[0] % sync_every == 0:
+                        k = at[o[0]]
+                        put(dict(positions=fr["positions"][k].copy(), velocities_pre=fr["velocities_pre"][k].copy(), cell=fr["cell"][k] if npt else None),
+                            "velocities_pre")
+                    yield o
+            else:
+                self.step = step_now
+                if sync_every and out and out[-1][0] % sync_every == 0 and code != 1:
+                    # the configuration of the batch's last row: the device has moved on to the next one unless the run is over
+                    put(eng.md_state(which=0 if final else -1), "velocities_pre")
+                yield from out
+            self.step = step_now
             rows = rows[accepted:]
             batch = min(8, chunk) if code else min(2 * batch, chunk)
             if code == 1:
@@ -667,7 +698,8 @@ class ActiveCalculator(Calculator):
                 t_host = time.time() - t_host
         put(eng.md_state(results=True), "velocities")
 
-    def run_relax(self, atoms, fmax=0.01, steps=100000, cell=False, mask=None, clear_hist=False, chunk=256, **fire):
+    def run_relax(self, atoms, fmax=0.01, steps=100000, cell=False, mask=None, clear_hist=False, chunk=256, on_frame=None, interval=1,
+                  **fire):
         """FIRE relaxation of atoms.positions — with cell=True also of atoms.cell, through the coordinates of
         ase.constraints.UnitCellFilter(atoms, mask=mask) — as theforce/cl/relax.py minimises around this calculator, but with
         the state in device memory between model updates: run_md's loop with the optimizer in the place of the integrator
@@ -678,6 +710,12 @@ class ActiveCalculator(Calculator):
         current after every update and at the end, where self.results are those of the final configuration.  fire: the keywords
         of ase.optimize.FIRE.  Falls back to the host loop (cl/relax.py::FIRE and UnitCellFilter around calculate()) where
         md_on_device_ok() says no or the run is sharded.  Returns dict(converged, steps, evaluations).
+        on_frame (a trajectory writer; the optimizers' trajectory= of cl/relax.py): called as on_frame(n, dict(positions, cell,
+        energy, forces)) for every accepted evaluation n that is a multiple of `interval`, and for the final structure whatever
+        its index — from the frame record of the device loop (SGPRModel.md_record: the run is not cut for it; a batch's record
+        stays within RECORD_BYTES), in order, behind the batch that evaluated them.  An evaluation that was handed to
+        calculate() is reported once, with the results of its re-evaluation by the updated model.  The host loop calls it from
+        its own steps.  Without on_frame nothing is recorded.
         atoms.constraints: FixAtoms and FixCartesian are honoured inside the loop (constraint_mask ->
         SGPRModel.relax_begin(fixed=); the host loop through the atoms' own set_positions / get_forces): the optimizer sees F = 0
         on a held component and convergence is judged on the free ones — self.results["forces"] stay the model's own —; a held
@@ -706,21 +744,35 @@ class ActiveCalculator(Calculator):
             if not device_ok():
                 target = UnitCellFilter(atoms, mask=mask) if cell else atoms
                 opt = FIRE(target, **fire)
+
+                def report(n, last=False):
+                    if on_frame is not None and (n % interval == 0 or last):
+                        on_frame(n, dict(positions=np.array(atoms.positions), cell=np.array(getattr(atoms.cell, "array", atoms.cell), float),
+                                         energy=float(self.results["energy"]), forces=np.array(self.results["forces"])))
                 forces, n = target.get_forces(), 0
                 while force_max(forces) >= fmax and n < steps:
+                    report(n)
                     opt.step(forces)
                     n += 1
                     forces = target.get_forces()
                     if self.updated and clear_hist:
                         opt.initialize()
+                report(n, last=True)
                 return dict(converged=force_max(forces) < fmax, steps=n, evaluations=n + 1)
         numbers, pos, cell0, pbc = self._system(atoms)
         eng = self.engine
         eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **hold, **fire)
         done, skip_gate, converged = 0, first_on_host, False
         batch = min(8, chunk)
+        rec, reported = on_frame is not None, -1
+        if rec:   # (positions and the packed results; a batch of at most rec_max frames)
+            interval = max(1, int(interval))
+            eng.md_record(interval, velocities=False, results=True)
+            rec_max = max(1, self.RECORD_BYTES // (8 * (7 * len(numbers) + 11)))
         while done <= steps and not converged:
             n = 1 if skip_gate else min(batch, steps + 1 - done)
+            if rec:
+                n = max(1, min(n, rec_max * interval - done % interval))
             gate = 0.0 if skip_gate else self._md_gate(numbers)
             sc, code = eng.md_run(n, None, ediff=gate, final=(done + n == steps + 1))
             accepted = len(sc) - 1 if code == 1 else len(sc)
@@ -733,6 +785,11 @@ class ActiveCalculator(Calculator):
                     self.step += 1
                 done += 1
             self._log_lines(lines)
+            if rec and recorded_indices(done - accepted, len(sc), code, interval):   # (the accepted evaluations' frames: a halted one is recorded by its re-evaluation)
+                fr = eng.md_frames(reuse=True)
+                for k, i in enumerate(fr["index"]):
+                    on_frame(int(i), dict(positions=fr["positions"][k].copy(), cell=fr["cell"][k], energy=float(fr["energy"][k]), forces=fr["forces"][k].copy()))
+                    reported = int(i)
             batch = min(8, chunk) if code else min(2 * batch, chunk)
             if code == 1:
                 put(eng.md_state())
@@ -745,6 +802,8 @@ class ActiveCalculator(Calculator):
             converged = code == 3
         st = eng.md_state(results=True)
         put(st)
+        if rec and reported != done - 1:   # (the final structure, where its index is no multiple of the interval)
+            on_frame(done - 1, dict(positions=st["positions"], cell=np.array(st["cell"], float), energy=float(st["energy"]), forces=st["forces"]))
         # (the calculator answers for the final configuration from what the device has just computed)
         atoms.calc = self
         Calculator.calculate(self, atoms, ("energy",), all_changes)

@@ -214,12 +214,18 @@ class _DeviceRunner:
     def initialize(self):
         pass
 
+    def _write(self, n, fr):
+        a = self.atoms
+        self.out.writelines(format_extxyz(Frame(a.numbers, fr["positions"], fr["cell"], a.pbc, float(fr["energy"]), fr["forces"], None)))
+
     def run(self, fmax):
-        res = self.calc.run_relax(self.atoms, fmax=fmax, steps=self.max_steps, cell=self.cell, mask=self.mask, clear_hist=self.clear_hist)
+        # (a frame per evaluation, as _Runner writes them: from the device loop's frame record, the run is not cut for it; the last
+        # one is the final structure with the results the calculator then answers with)
+        res = self.calc.run_relax(self.atoms, fmax=fmax, steps=self.max_steps, cell=self.cell, mask=self.mask, clear_hist=self.clear_hist,
+                                  on_frame=self._write if self.out is not None else None)
         self.nsteps += res["steps"]
         a, r = self.atoms, self.calc.results
         if self.out is not None:
-            self.out.writelines(format_extxyz(Frame(a.numbers, a.positions, a.cell, a.pbc, float(r["energy"]), r["forces"], None)))
             self.out.flush()
         if self.master:
             print(f"FIRE (device): {self.nsteps:4d}  energy {float(r['energy']):.6f}  fmax {force_max(r['forces']):.4f}")

@@ -208,6 +208,15 @@ struct MdState {
     DevBuf<unsigned char> fixed;   // [N][3]
     std::vector<unsigned char> fixed_sorted;
     const unsigned char *fix() const { return n_fixed ? fixed.p : nullptr; }
+    // the frame record (sgpr_md_record, md_record.inc): every rec_every-th configuration of a call, copied out behind its
+    // evaluation in caller atom order — rec_x always, rec_v / rec_p by the bits of rec_what.  rec_call_*: what the LAST
+    // sgpr_md_run recorded (sgpr_md_frames serves that call: its first trajectory index, its settings, the frames that stand)
+    int rec_every = 0, rec_what = 0;
+    DevBuf<double> rec_x, rec_v, rec_p;   // [frames][N][3] x 2, [frames][4N + 11]: one copy per array fetches a call
+    long long rec_call_t0 = 0;
+    int rec_call_every = 0, rec_call_what = 0, rec_call_count = 0;
+    // multiples of rec_every in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
+    static long long rec_between(long long a, long long b, int every) { return (b + every - 1) / every - (a + every - 1) / every; }
 };
 
 struct sgpr_model {
@@ -1048,6 +1057,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 
 #include "md_npt.inc"
 #include "md_relax.inc"
+#include "md_record.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
 // position — read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild
@@ -1591,6 +1601,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.zeta.release();
         m.npt_ring.release(); m.Q.release(); m.cells_d.release();
         m.fixed.release();
+        m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
         for (auto b : tb) b->release();
         h->d_panel_cnt.release();

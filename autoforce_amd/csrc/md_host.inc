@@ -1,5 +1,5 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*: MD, moving-cell NPT, FIRE relaxation), included by
-// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc and md_relax.inc.
+// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc, md_relax.inc and md_record.inc.
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
 // from util/aseutil.py:11-20) and crosses into the calculator once per step.  Here the state (positions, velocities)
@@ -66,6 +66,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.npt = false; m.npt_started = false; m.cells.clear();
     m.relax = false; m.relax_started = false;
     m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
+    m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -406,6 +407,15 @@ struct MdBinIdentity {
 static int md_prepare_call(sgpr_model *h, int nevals, hipStream_t st, bool want_cells)
 {
     MdState &m = h->md;
+    // the frame record of this call (sgpr_md_record): room for the frames it can record, grown like the scalar ring and not
+    // zeroed — before anything is enqueued
+    m.rec_call_t0 = m.t; m.rec_call_every = m.rec_every; m.rec_call_what = m.rec_what; m.rec_call_count = 0;
+    if (m.rec_every) {
+        const size_t fr = (size_t)MdState::rec_between(m.t, m.t + nevals, m.rec_every), N3 = (size_t)3 * m.N;
+        if (m.rec_x.alloc(fr * N3, false) || ((m.rec_what & 1) && m.rec_v.alloc(fr * N3, false)) ||
+            ((m.rec_what & 2) && m.rec_p.alloc(fr * (size_t)sgpr_packed_len(m.N), false)))
+            return fail(SGPR_E_NODEVICE, "sgpr_md_run: no device memory for the record of %zu frames", fr);
+    }
     const size_t rows = (size_t)nevals + 1;
     if (m.scal_rows < rows) {
         if (m.mark) (void)hipHostFree(m.mark);
@@ -519,6 +529,37 @@ static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval
     return SGPR_OK;
 }
 
+// The frame of evaluation j of a call (configuration n = m.t + j, n % rec_every == 0), behind the evaluation's last launch: the
+// ring slots sgpr_md_state(which = -1) would read had the call ended with this evaluation — X and P: n % ring; V: that slot
+// (Langevin, velocity Verlet), the slot before it (Nose-Hoover and NPT, n > 0: what the integrator holds when it asks for F_n),
+// slot 0 (a relaxation).  Its place in the record: its ordinal among the call's recorded evaluations.
+static void md_record_frame(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const long long n = m.t + j;
+    const int N = m.N, RG = m.ring, sl = (int)(n % RG), plen = (int)sgpr_packed_len(N);
+    const size_t f = (size_t)MdState::rec_between(m.t, n, m.rec_every), N3 = (size_t)3 * N;
+    const int sv = m.relax ? 0 : ((m.nh && n > 0) ? (sl + RG - 1) % RG : sl);
+    const bool wv = (m.rec_what & 1) != 0, wp = (m.rec_what & 2) != 0;
+    const int elems = wp ? std::max(3 * N, plen) : 3 * N;
+    hipLaunchKernelGGL(md_record_kernel, dim3((elems + 255) / 256), dim3(256), 0, st, N, plen, (const int *)h->d_perm.p,
+                       (const double *)(m.X.p + N3 * sl), wv ? (const double *)(m.V.p + N3 * sv) : (const double *)nullptr,
+                       wp ? (const double *)(m.P.p + (size_t)plen * sl) : (const double *)nullptr, m.rec_x.p + N3 * f,
+                       wv ? m.rec_v.p + N3 * f : (double *)nullptr, wp ? m.rec_p.p + (size_t)plen * f : (double *)nullptr,
+                       (const int *)m.halt.p, step);
+}
+
+// Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
+// one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
+// again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
+// keeps its frame: the final structure.  Frames that look-ahead evaluations wrote beyond that count are overwritten later.
+static void md_record_close(MdState &m, const MdHalt &r)
+{
+    if (!m.rec_call_every) return;
+    const int lim = std::max(r.code == 1 ? r.done - 1 : r.done, 0);
+    m.rec_call_count = (int)MdState::rec_between(m.rec_call_t0, m.rec_call_t0 + lim, m.rec_call_every);
+}
+
 // sgpr_md_run for a relaxation: every evaluation is the plain step (its own binning kernel, the plain last kernel) with
 // md_fire_kernel and md_fire_move_kernel behind it.  The halts — covloss gate (1), capacity overflow (2), convergence (3) — are
 // decided by md_fire_kernel on the evaluation itself, before anything moves: what the host has enqueued behind a halt (its
@@ -570,12 +611,18 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
                                (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.rx_ref.p, m.X.p + (size_t)3 * N * sn,
                                (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j),
                                m.fix());
+        // (the frame BEHIND the move: sgpr_md_state reads a relaxation's velocity from slot 0, which the move kernel updates in
+        // place — after a cut call that moved out of n it returns the moved velocity with the positions of n; where nothing
+        // moves — a halt at n, the last evaluation of a `final` call — it returns the one before the move, and so does this.
+        // Positions and results of n are in slots the move does not write.)
+        if (m.rec_every && (m.t + j) % m.rec_every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
     if (const int rc = md_collect(h, enq, st, scalars, true)) return rc;
     MdHalt r;
     if (const int rd = md_decode_halt(h, step0, enq, final_eval, true, &r)) return rd;
+    md_record_close(m, r);
     if (scalars && r.done > 0) memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
     m.evaluated = r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0);
     *evals_done = r.done;
@@ -695,6 +742,9 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         else if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
             hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
                                m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
+        // (the frame: the last kernel has written this evaluation's results and, Nose-Hoover, its centred velocity; the slots
+        // read here are written again only when the rings come round)
+        if (m.rec_every && (m.t + j) % m.rec_every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -719,6 +769,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (!keep_chain) HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
     MdHalt r;
     if (const int rd = md_decode_halt(h, step0, enq, final_eval, m.npt, &r)) return rd;
+    md_record_close(m, r);
     // exchanges that took place: the ranks have enqueued different numbers of evaluations behind the halt, all of them
     // skipped on the device (peer_push_kernel): a covloss halt at evaluation k is seen by evaluation k + 1 (or by the
     // tail kernel when k is the last), an overflow by evaluation k itself — the same count on every rank
@@ -807,6 +858,59 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
             if (m.n_fixed && m.fixed_sorted[3 * (size_t)i + k]) velocities[3 * c + k] = 0.0;   // (a held component: F = 0, v = 0)
             else if (kick) velocities[3 * c + k] = velocities[3 * c + k] + m.hdt * F[3 * c + k] / m.mass_sorted[i];
     }
+    return SGPR_OK;
+}
+
+// The frame record (md_record.inc): what a trajectory writer needs of a run that is not cut for it — the reference's writers
+// are attached to the host loop with `loginterval` (cl/md.py:24-26, :117-128, :155-166) and its optimizers take trajectory=
+// (cl/relax.py).  every >= 1: from the next sgpr_md_run on, the evaluation of every configuration n with n % every == 0 is
+// followed by one launch that copies the configuration out, in caller atom order; 0: off.  what: bit 0 the velocities the
+// integrator holds (sgpr_md_state's velocities_pre), bit 1 the packed results; positions always.  Between any two calls of a
+// run (the interval belongs to the writer, not to the integrator); sgpr_md_begin switches it off.
+extern "C" int sgpr_md_record(sgpr_model *h, int every, int what)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_record: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_record: call sgpr_md_begin first");
+    if (every < 0 || (what & ~3)) return fail(SGPR_E_INVALID, "sgpr_md_record: every >= 0, what = bit 0 (velocities) | bit 1 (results)");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.world);
+    m.rec_every = every;
+    m.rec_what = every ? what : 0;
+    return SGPR_OK;
+}
+
+// How many frames of the last sgpr_md_run stand (0: it recorded nothing).
+extern "C" int sgpr_md_frame_count(sgpr_model *h, int *count)
+{
+    if (!h || !count) return fail(SGPR_E_INVALID, "sgpr_md_frame_count: bad arguments");
+    if (!h->md.active) return fail(SGPR_E_INVALID, "sgpr_md_frame_count: call sgpr_md_begin first");
+    *count = h->md.rec_call_every ? h->md.rec_call_count : 0;
+    return SGPR_OK;
+}
+
+// Frames first ... first + count - 1 of the last call's record (valid until the next sgpr_md_run, like sgpr_md_cells): index[r]
+// the trajectory index, positions[count][N][3], velocities_pre[count][N][3], packed[count][4N + 11]; any of them NULL.  One
+// device-to-host copy per array: nothing is un-permuted on the host.
+extern "C" int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *positions, double *velocities_pre, double *packed)
+{
+    if (!h || first < 0 || count <= 0) return fail(SGPR_E_INVALID, "sgpr_md_frames: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_frames: call sgpr_md_begin first");
+    const int have = m.rec_call_every ? m.rec_call_count : 0;
+    if ((long long)first + count > have)
+        return fail(SGPR_E_INVALID, "sgpr_md_frames: frames %d ... %lld asked for, the last sgpr_md_run recorded %d", first, (long long)first + count - 1, have);
+    if ((velocities_pre && !(m.rec_call_what & 1)) || (packed && !(m.rec_call_what & 2)))
+        return fail(SGPR_E_INVALID, "sgpr_md_frames: %s not recorded (sgpr_md_record's `what`)", velocities_pre && !(m.rec_call_what & 1) ? "velocities were" : "results were");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N3 = (size_t)3 * m.N, plen = (size_t)sgpr_packed_len(m.N);
+    if (index) {
+        const long long ev = m.rec_call_every, n0 = (m.rec_call_t0 + ev - 1) / ev * ev;
+        for (int r = 0; r < count; r++) index[r] = n0 + ((long long)first + r) * ev;
+    }
+    if (positions) HIPCHK(hipMemcpy(positions, m.rec_x.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
+    if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.rec_v.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.rec_p.p + plen * first, sizeof(double) * plen * count, hipMemcpyDeviceToHost));
     return SGPR_OK;
 }
 

@@ -35,6 +35,18 @@ def default_radii(species):
     return np.array([0.5 if int(z) == 1 else 1.0 for z in species])
 
 
+def recorded_indices(t0, done, code, every):
+    """The trajectory indices of the frames that stand behind an md_run call (sgpr_md_frame_count's rule, for a caller's own
+    bookkeeping): the call began at configuration t0, `done` rows came back with halt code `code`, every `every`-th
+    configuration was recorded.  The rows' evaluations t0 ... t0 + done - 1 stand — an overflow (2) has left the halting one out
+    of `done` already, a converged relaxation (3) keeps its last — less the last one when the covloss gate fired (1): the next
+    call evaluates and records that configuration again."""
+    if not every:
+        return []
+    last = t0 + done - (1 if code == 1 else 0)
+    return [n for n in range(-(-t0 // every) * every, last, every)]
+
+
 class SGPRModel:
     def __init__(self, lmax=3, nmax=3, exponent=4, cutoff=6.0, species=None, radii=None, device=0,
                  unknown_species="error", lone_weight=1):
@@ -692,6 +704,7 @@ class SGPRModel:
         self.generation += 1
         check(_lib.load().sgpr_md_run(self._h, int(nevals), ptr(noise), float(ediff), int(bool(final)), ptr(sc),
                                       C.addressof(done), C.addressof(code)))
+        self._md["record_call"] = self._md.get("record")   # (what this call recorded: md_frames)
         if self._md.get("npt"):   # (where the state is now: sgpr_md_run's rules)
             t0 = self._md["t"]
             self._md["run"] = (t0, done.value)
@@ -739,6 +752,79 @@ class SGPRModel:
                 out["velocities"] = v + self._md["hdt"] * F / self._md["masses"][:, None] if pend.value else v.copy()
                 if self._md.get("fixed") is not None:   # (a held component: the integrator's F = 0, v = 0)
                     out["velocities"] = np.where(self._md["fixed"], 0.0, out["velocities"])
+        return out
+
+    def md_record(self, every, velocities=True, results=True):
+        """Record every `every`-th configuration of the run (trajectory index n with n % every == 0) from the next md_run on,
+        without cutting the run: behind the evaluation of such a configuration one extra launch copies it into a record in
+        device memory, in caller atom order (sgpr_md_record; a trajectory writer's loginterval, cl/md.py:24-26).  Positions
+        always; velocities: what the integrator holds (md_state's velocities_pre); results: forces, covloss, energy, virial.
+        every = 0: off.  After md_begin / relax_begin, between any two md_run calls; md_frames() fetches a call's frames."""
+        check(_lib.load().sgpr_md_record(self._h, int(every), (1 if velocities else 0) | (2 if results else 0)))
+        self._md["record"] = (int(every), bool(velocities), bool(results)) if every else None
+
+    def md_frame_count(self):
+        """Frames of the last md_run that stand (sgpr_md_frame_count)."""
+        k = C.c_int(0)
+        check(_lib.load().sgpr_md_frame_count(self._h, C.addressof(k)))
+        return k.value
+
+    def md_frames(self, closed=True, reuse=False):
+        """The frames the last md_run recorded, as md_state would have returned them had the run been cut behind each (the
+        same bits): dict(index [k], positions [k, N, 3]); velocities_pre [k, N, 3] where velocities were recorded; where
+        results were: forces, beta, energy (views of the one packed array fetched), stress (of the frame's own cell) and, for
+        Langevin / velocity Verlet with closed=True, velocities — the closing half kick applied, md_state(results=True)'s
+        expression, held components zero (three passes over [k, N, 3] on the host: closed=False leaves it out).  Moving-cell
+        runs and relaxations: cell, and eta or D, from md_cells' rows of the same evaluations.  The frame of an evaluation the
+        covloss gate halted is not among them: the next call records that configuration again.  One device-to-host copy per
+        array, nothing is un-permuted on the host.  reuse=True: the arrays are views of buffers the model keeps and fills again
+        at the next md_frames(reuse=True) — a caller that is done with a call's frames before it fetches the next call's
+        (a 256-frame call of 4096 atoms is 84 MB: fresh pages every call cost as much as the copy)."""
+        N, k = self._md["N"], self.md_frame_count()
+        if k == 0:
+            check(_lib.load().sgpr_md_frames(self._h, 0, 1, None, None, None, None))   # (SGPR_E_INVALID: the call recorded nothing)
+        _, want_v, want_r = self._md["record_call"]
+
+        def room(key, shape):
+            if not reuse:
+                return np.empty((k,) + shape)
+            buf = self._md.setdefault("frame_bufs", {})
+            if key not in buf or len(buf[key]) < k or buf[key].shape[1:] != shape:
+                buf[key] = np.empty((k,) + shape)
+            return buf[key][:k]
+        idx = np.zeros(k, dtype=np.int64)
+        x = room("x", (N, 3))
+        v = room("v", (N, 3)) if want_v else None
+        packed = room("p", (4 * N + 11,)) if want_r else None
+        check(_lib.load().sgpr_md_frames(self._h, 0, k, ptr(idx), ptr(x), ptr(v), ptr(packed)))
+        out = dict(index=idx, positions=x)
+        if want_v:
+            out["velocities_pre"] = v
+        cells = None
+        if self._md.get("npt"):
+            t0, done = self._md["run"]
+            c, e = self.md_cells(t0, done)
+            cells = out["cell"] = c[idx - t0]
+            out["D" if self._md.get("relax") else "eta"] = e[idx - t0]
+        if want_r:
+            out["forces"] = packed[:, :3 * N].reshape(k, N, 3)
+            out["beta"] = packed[:, 3 * N:4 * N]
+            out["energy"] = packed[:, 4 * N]
+            stress, vir = np.zeros((k, 6)), f64(packed[:, 4 * N + 1:4 * N + 10])
+            for r in range(k):
+                cell = self._md["cell"] if cells is None else f64(cells[r])
+                check(_lib.load().sgpr_stress_from_virial(ptr(vir[r]), ptr(cell), ptr(stress[r])))
+            out["stress"] = stress
+            if closed and want_v and not self._md.get("relax") and not self._md.get("nh"):
+                # v + hdt * F / m, operation by operation as md_state spells it (every configuration but the start of the
+                # trajectory has a half kick pending), in one array
+                vel = np.multiply(self._md["hdt"], out["forces"])
+                np.divide(vel, self._md["masses"][:, None], out=vel)
+                np.add(v, vel, out=vel)
+                vel[idx == 0] = v[idx == 0]
+                if self._md.get("fixed") is not None:   # (a held component: the integrator's F = 0, v = 0)
+                    vel[:, self._md["fixed"]] = 0.0
+                out["velocities"] = vel
         return out
 
     def md_end(self):

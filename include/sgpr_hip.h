@@ -436,6 +436,34 @@ int sgpr_md_relax_reset(sgpr_model *h);
  * SGPR_E_UNSUPPORTED: from sgpr_md_barostat behind a non-empty mask (the moving-cell dynamics run without one).  The handle
  * goes on working after any of them. */
 int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N);
+/* The frame record: a trajectory out of a run that is NOT cut for it.  The reference attaches its writers to the host loop
+ * (theforce/cl/md.py:24-26: `loginterval`, default 1; :117-128 and :155-166: dyn.attach(traj.write, interval=loginterval)) and
+ * its optimizers take trajectory= (theforce/cl/relax.py); each step there crosses into the calculator anyway.  Here a call of
+ * sgpr_md_run stays on the device for all its evaluations, and sgpr_md_state shows only where it ended.
+ *
+ * sgpr_md_record       every >= 1: from the next sgpr_md_run on, the evaluation of every configuration n (index in the
+ *                      trajectory) with n % every == 0 is followed by ONE extra launch that copies that configuration into a
+ *                      record in device memory, in caller atom order; every = 0 switches recording off.  what: bit 0 the
+ *                      velocities the integrator holds, bit 1 the packed results [F | beta | E | virial | overflow];
+ *                      positions are always recorded.  A frame holds exactly what sgpr_md_state(which = -1) would return for
+ *                      configuration n had the call ended with that evaluation — the same bits (Nose-Hoover / NPT:
+ *                      velocities_pre of frame n is the centred v_(n-1); a relaxation: FIRE's velocity as it stands behind
+ *                      the move out of n).  After sgpr_md_begin (which switches it off), between any two sgpr_md_run calls.
+ *                      SGPR_E_INVALID: before sgpr_md_begin, every < 0, unknown bits.  SGPR_E_UNSUPPORTED: the run was begun
+ *                      on more than one rank.  A run that records nothing launches exactly what it launched before.
+ * sgpr_md_frame_count  frames of the LAST sgpr_md_run that stand: those of the evaluations whose results stand (*evals_done),
+ *                      less the halting one when the covloss gate fired (halt code 1: the next call evaluates and records
+ *                      that configuration again, with the model the caller has installed by then); a converged relaxation
+ *                      (code 3) keeps the frame of its last evaluation.
+ * sgpr_md_frames       frames first ... first + count - 1 of that record (valid until the next sgpr_md_run): index[count] the
+ *                      trajectory indices, positions[count][N][3], velocities_pre[count][N][3], packed[count][4N + 11].  Any
+ *                      pointer may be NULL; a non-NULL pointer for an array that was not recorded, or frames beyond
+ *                      sgpr_md_frame_count: SGPR_E_INVALID.  One device-to-host copy per array.  Cell and strain rate (or D)
+ *                      of the same evaluations: sgpr_md_cells.
+ * The handle stays usable after every error above. */
+int sgpr_md_record(sgpr_model *h, int every, int what);
+int sgpr_md_frame_count(sgpr_model *h, int *count);
+int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *positions, double *velocities_pre, double *packed);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
