@@ -495,6 +495,15 @@ class ActiveCalculator(Calculator):
         return (hasattr(eng, "md_run") and (world == 1 or getattr(eng, "peer_world", 1) == world) and not self.test
                 and self.meta is None and "forces" not in self._veto and self.nbeads == 1 and eng.m > 0 and eng.mu is not None)
 
+    def _md_attach(self, eng):
+        """Hook of run_md, called right after eng.md_begin(...): whatever else the device loop must evaluate beside the live
+        model is attached to the run here, and the keys of what was attached are returned.  Nothing for a single model;
+        BCMActiveCalculator attaches the engines of its ready members (SGPRModel.md_committee)."""
+        return ()
+
+    def _md_attached_done(self, eng, keys):
+        """... and what the calculator keeps of such a run when it is over (BCMActiveCalculator: bcm_weights)."""
+
     def _md_gate(self, numbers):
         """The smallest covloss at which calculate() would do more than log (update_lce, active.py:806-839): below
         ediff_lb nothing happens unless a species of the frame has fewer than two inducing LCEs."""
@@ -603,7 +612,13 @@ class ActiveCalculator(Calculator):
             # sees — and logs — the velocities the loops start from)
             vel = np.where(fx, 0.0, vel)
             atoms.set_velocities(vel)
-        first_on_host = self._needs_seed() or not self.md_on_device_ok()
+        # (a committee with members — BCMActiveCalculator — runs on the device at constant cell and without a mask; under a
+        # barostat or constraints the host loops around calculate(), which answers with the committee, take it)
+        committee = bool(getattr(self, "model_dict", None))
+
+        def on_device():
+            return self.md_on_device_ok() and not (committee and (npt or fx is not None))
+        first_on_host = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
             # logs — those velocities; md_begin and the host twin are handed the caller's and remove it themselves)
@@ -613,7 +628,7 @@ class ActiveCalculator(Calculator):
             # (an empty model is seeded by its first calculate(); then the device loop can take over)
             atoms.calc = self
             atoms.get_forces()
-            if not self.md_on_device_ok():
+            if not on_device():
                 loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro) if npt else
                         nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold) if nh else
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold))
@@ -629,7 +644,9 @@ class ActiveCalculator(Calculator):
         # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
-        rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1)
+        attached = self._md_attach(eng)
+        # (a run with members attached records no frames: batches end at the multiples of sync_every)
+        rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1 and not attached)
         if rec:   # (positions and the velocities the integrator holds; a batch of at most rec_max frames)
             eng.md_record(sync_every, velocities=True, results=False)
             rec_max = max(1, self.RECORD_BYTES // (48 * N))
@@ -697,6 +714,8 @@ class ActiveCalculator(Calculator):
                 skip_gate = True
                 t_host = time.time() - t_host
         put(eng.md_state(results=True), "velocities")
+        if attached:
+            self._md_attached_done(eng, attached)
 
     def run_relax(self, atoms, fmax=0.01, steps=100000, cell=False, mask=None, clear_hist=False, chunk=256, on_frame=None, interval=1,
                   **fire):
@@ -709,7 +728,8 @@ class ActiveCalculator(Calculator):
         model was updated), and the run goes on with the new model.  At most `steps` moves.  atoms.positions and atoms.cell are
         current after every update and at the end, where self.results are those of the final configuration.  fire: the keywords
         of ase.optimize.FIRE.  Falls back to the host loop (cl/relax.py::FIRE and UnitCellFilter around calculate()) where
-        md_on_device_ok() says no or the run is sharded.  Returns dict(converged, steps, evaluations).
+        md_on_device_ok() says no, the run is sharded, or the calculator is a committee with members (the device relaxation
+        evaluates one model; calculate() answers with the committee).  Returns dict(converged, steps, evaluations).
         on_frame (a trajectory writer; the optimizers' trajectory= of cl/relax.py): called as on_frame(n, dict(positions, cell,
         energy, forces)) for every accepted evaluation n that is a multiple of `interval`, and for the final structure whatever
         its index — from the frame record of the device loop (SGPRModel.md_record: the run is not cut for it; a batch's record
@@ -736,7 +756,10 @@ class ActiveCalculator(Calculator):
             atoms.positions = st["positions"]
 
         def device_ok():
-            return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "relax_begin")
+            # (a committee with members — BCMActiveCalculator — relaxes through the host loop around calculate(): the device
+            # relaxation evaluates one model)
+            return (self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "relax_begin")
+                    and not getattr(self, "model_dict", None))
         first_on_host = self._needs_seed() or not device_ok()
         if first_on_host:
             atoms.calc = self

@@ -185,6 +185,36 @@ class BCMActiveCalculator(ActiveCalculator):
                                forces=sum(a * o["forces"] for a, o in zip(w, members)),
                                stress=sum(a * o["stress"] for a, o in zip(w, members))))
 
+    # ------------------------------------------------------------------ MD with the state in device memory
+    def _ready_members(self):
+        """Keys of the members with a model (the rule of _evaluate_engine), in model_dict order."""
+        return [k for k, post in self.model_dict.items() if post.engine.m > 0 and post.engine.mu is not None]
+
+    def md_on_device_ok(self):
+        """With frozen members the device loop must evaluate them too (SGPRModel.md_committee: one process, at most 15 ready
+        members, each with its choli and on the live model's device); anything else goes to the host loops around
+        calculate().  Without members everything is as for a single model."""
+        if not self.model_dict:
+            return super().md_on_device_ok()
+        if not (super().md_on_device_ok() and hasattr(self.engine, "md_committee") and self._dist()[1] == 1
+                and not self.members_over_ranks):
+            return False
+        ready = [self.model_dict[k].engine for k in self._ready_members()]
+        dev = getattr(self.engine, "device", 0)
+        return len(ready) <= 15 and all(e.choli is not None and getattr(e, "device", 0) == dev for e in ready)
+
+    def _md_attach(self, eng):
+        """The engines of the READY members (a member without a model has weight 0 and an infinite covloss — it changes
+        neither the combination nor the member-wise minimum), in model_dict order."""
+        keys = self._ready_members()
+        if keys:
+            eng.md_committee([self.model_dict[k].engine for k in keys])
+        return tuple(keys)
+
+    def _md_attached_done(self, eng, keys):
+        w = dict(zip(list(keys) + ["live"], eng.md_committee_info()[0].tolist()))
+        self.bcm_weights = {k: w.get(k, 0.0) for k in list(self.model_dict.keys()) + ["live"]}
+
     def get_covloss_total(self):
         """active_bcm.py:885-894."""
         b = self._beta

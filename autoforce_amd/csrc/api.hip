@@ -215,6 +215,13 @@ struct MdState {
     DevBuf<double> rec_x, rec_v, rec_p;   // [frames][N][3] x 2, [frames][4N + 11]: one copy per array fetches a call
     long long rec_call_t0 = 0;
     int rec_call_every = 0, rec_call_what = 0, rec_call_count = 0;
+    // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
+    // at every configuration (empty: the run is the one without a committee and launches what it launched before)
+    std::vector<struct sgpr_model *> bcm;
+    DevBuf<double> bcm_P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
+    DevBuf<double> bcm_x;          // [N][3] the current positions in caller atom order: what the members bin
+    DevBuf<double> bcm_info_d;     // [rows][32] weights | largest covlosses per evaluation of a call
+    std::vector<double> bcm_info;  // ... of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
     // multiples of rec_every in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
     static long long rec_between(long long a, long long b, int every) { return (b + every - 1) / every - (a + every - 1) / every; }
 };
@@ -1057,6 +1064,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 
 #include "md_npt.inc"
 #include "md_relax.inc"
+#include "md_bcm.inc"
 #include "md_record.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
@@ -1602,6 +1610,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.npt_ring.release(); m.Q.release(); m.cells_d.release();
         m.fixed.release();
         m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
+        m.bcm_P.release(); m.bcm_x.release(); m.bcm_info_d.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
         for (auto b : tb) b->release();
         h->d_panel_cnt.release();

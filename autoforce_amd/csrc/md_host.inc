@@ -67,6 +67,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.relax = false; m.relax_started = false;
     m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
     m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
+    m.bcm.clear(); m.bcm_info.clear();
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -109,6 +110,7 @@ extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
     if (m.nh || m.npt || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run has a committee (sgpr_md_committee), which runs without a mask");
     const int N = m.N;
     std::vector<unsigned char> fs((size_t)3 * N, 0);
     int n = 0;
@@ -143,6 +145,7 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
     if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
     if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
+    if (!m.bcm.empty()) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call it before sgpr_md_committee");
     if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
     // (held components, sgpr_md_fix: g = 3N - n_fixed degrees of freedom, none removed for the centre of mass — momentum is
@@ -169,6 +172,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (!m.active || !m.nh || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
     if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell");
     if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.n_fixed);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
@@ -332,6 +336,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_relax: call sgpr_md_begin first");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
     if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
     if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     const double *fp = fire ? fire : RLX_ASE;
@@ -631,6 +636,197 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
     return SGPR_OK;
 }
 
+// The Bayesian committee of the run begun by sgpr_md_begin (md_bcm.inc has the rule): members[K], frozen models evaluated
+// beside the live handle h at every configuration, in this order with h last; the run integrates the weighted forces, gates
+// on the largest member-wise minimum covloss and reports the weighted energy and virial.  After sgpr_md_begin and, if used,
+// sgpr_md_thermostat; before the first sgpr_md_run — a detach (K = 0 or members = NULL: the run is the one without this call)
+// too: a run that has started keeps what it has.
+// The members are BORROWED: the caller keeps them alive until sgpr_md_end or a detach, and may use them between two
+// sgpr_md_run calls (every call binds them to the run's system again).  Constant cell, one rank, no mask, no frame record.
+extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *members)
+{
+    if (!h || K < 0) return fail(SGPR_E_INVALID, "sgpr_md_committee: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_committee: call sgpr_md_begin first");
+    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
+    if (K == 0 || !members) { m.bcm.clear(); m.bcm_info.clear(); return SGPR_OK; }
+    if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
+    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
+    if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.n_fixed);
+    if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.world);
+    if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
+    for (int k = 0; k < K; k++) {
+        const sgpr_model *mk = members[k];
+        if (!mk) return fail(SGPR_E_INVALID, "sgpr_md_committee: member %d is null", k);
+        if (mk == h) return fail(SGPR_E_INVALID, "sgpr_md_committee: member %d is the live handle itself", k);
+        for (int q = 0; q < k; q++)
+            if (members[q] == mk) return fail(SGPR_E_INVALID, "sgpr_md_committee: member %d is member %d again", k, q);
+        if (!(mk->m > 0 && mk->has_mu)) return fail(SGPR_E_INVALID, "sgpr_md_committee: member %d has no weights", k);
+        if (!mk->has_choli) return fail(SGPR_E_INVALID, "sgpr_md_committee: member %d has no choli (its covloss is part of the rule)", k);
+        if (mk->device != h->device)
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: member %d lives on device %d, the run on device %d", k, mk->device, h->device);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N3 = (size_t)3 * m.N;
+    if (m.bcm_P.alloc((size_t)(K + 1) * (size_t)sgpr_packed_len(m.N)) || m.bcm_x.alloc(N3))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_committee: device allocation failed");
+    // every slot of the ring of positions a valid configuration from the start: what the host has enqueued behind a halt
+    // evaluates stale slots (and changes nothing) — zeros there would overflow the live model's lists
+    for (int r = 1; r < 4; r++) HIPCHK(hipMemcpy(m.X.p + N3 * r, m.X.p, sizeof(double) * N3, hipMemcpyDeviceToDevice));
+    m.bcm.assign(members, members + K);
+    m.bcm_info.clear();
+    return SGPR_OK;
+}
+
+// Weights and largest covlosses of the committee, K + 1 doubles each (the members in their order, the live model last), of the
+// last evaluation whose results stand: the numbers behind the packed results sgpr_md_state returns after a halted or `final` call.
+extern "C" int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || m.bcm.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: call sgpr_md_begin and sgpr_md_committee first");
+    if (m.bcm_info.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: no evaluation of the run stands yet");
+    const size_t K1 = m.bcm.size() + 1;
+    if (w) memcpy(w, m.bcm_info.data(), sizeof(double) * K1);
+    if (covmax) memcpy(covmax, m.bcm_info.data() + BCM_MAX, sizeof(double) * K1);
+    return SGPR_OK;
+}
+
+// sgpr_md_run for a run with a committee, in the shape of md_relax_run: every evaluation is K + 1 plain steps on the live
+// handle's stream — each member on the caller-order copy of the positions through its own binning kernel and permutation, the
+// live handle on its sorted ring slot — with md_bcm_kernel, md_bcm_move_kernel and md_bcm_ke_kernel behind them (Nose-Hoover:
+// md_nh_kernel too).  The halts — covloss gate (1), capacity overflow of any member (2) — are decided by md_bcm_kernel on the
+// evaluation itself, before anything moves: what the host has enqueued behind a halt evaluates stale slots and changes nothing.
+static int md_committee_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars, int *evals_done,
+                            int *halt_code)
+{
+    MdState &m = h->md;
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rb = md_rebind(h)) return rb;
+    hipStream_t st = h->stream;
+    const int N = m.N, RG = m.ring, K = (int)m.bcm.size(), K1 = K + 1;
+    const size_t plen = (size_t)sgpr_packed_len(N), N3 = (size_t)3 * N;
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    for (int k = 0; k < K; k++) {
+        const sgpr_model *mk = m.bcm[k];
+        if (!(mk->m > 0 && mk->has_mu && mk->has_choli)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: member %d of the committee has lost its weights", k);
+        HIPCHK(hipStreamSynchronize(mk->stream));   // (whatever the caller ran on the member between two calls is behind us)
+    }
+    m.started = true;
+    MdBinIdentity guard(h);
+    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
+    if (m.bcm_info_d.alloc((size_t)BCM_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    if (noise) {
+        if (m.noise.alloc((size_t)nevals * 3 * N) || m.noise_raw.alloc((size_t)nevals * 3 * N))
+            return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * (size_t)nevals * 3 * N, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
+    }
+    const int s0 = (int)(m.t % RG);
+    const unsigned step_a = h->step_count;
+    // the current configuration in caller order, for the members (the halt words are armed: nothing has halted this call)
+    hipLaunchKernelGGL(md_record_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, st, N, 0, (const int *)h->d_perm.p,
+                       (const double *)(m.X.p + N3 * s0), (const double *)nullptr, (const double *)nullptr, m.bcm_x.p, (double *)nullptr,
+                       (double *)nullptr, (const int *)m.halt.p, (int)step_a);
+    // Whatever ran on a handle since the last call — calculate() on a halt evaluates the same members, a model update binds the
+    // live one to stored frames — nothing is assumed about bound frame, lists or bin populations: bound again, a checked pass
+    // where the capacities are not sized for this system, lists rebuilt by the first evaluation, bin populations cleared
+    if (!h->warm) {
+        const int rc_ = run_checked(h, m.X.p + N3 * s0, m.cell.p, m.bcm_P.p + plen * K, st);
+        if (rc_) return rc_;
+        h->warm = true;
+    }
+    for (int k = 0; k < K; k++) {
+        sgpr_model *mk = m.bcm[k];
+        if (!md_same_system(mk, N, m.numbers.data(), m.pbc, 0, 1))
+            if (const int rb = sgpr_bind_system(mk, N, m.numbers.data(), m.pbc, 0, 1)) return rb;
+        if (!mk->warm) {
+            const int rc_ = run_checked(mk, m.bcm_x.p, m.cell.p, m.bcm_P.p + plen * k, st);
+            if (rc_) return rc_;
+            mk->warm = true;
+        }
+        mk->lists_valid = false;
+        mk->pre_valid = false;
+        HIPCHK(hipMemsetAsync(mk->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    }
+    m.chain_ok = false;
+    h->lists_valid = false;
+    h->pre_valid = false;
+    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    const unsigned step0 = h->step_count;
+    const double gate = ediff > 0.0 ? ediff : 1e300;
+    const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
+    int enq = 0;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
+        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+        for (int k = 0; k < K; k++) {
+            sgpr_model *mk = m.bcm[k];
+            const int re = enqueue_step(mk, m.bcm_x.p, m.cell.p, m.bcm_P.p + plen * k, st, nullptr);
+            if (re) return re;
+            mk->lists_valid = true;
+        }
+        const int re = enqueue_step(h, m.X.p + N3 * sl, m.cell.p, m.bcm_P.p + plen * K, st, nullptr);
+        if (re) return re;
+        h->lists_valid = true;
+        const int step = (int)(step0 + j);
+        double *packed = m.P.p + plen * sl, *info = m.bcm_info_d.p + (size_t)BCM_INFO * j, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
+        hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, packed, info, gate, m.halt.p,
+                           m.halt_host_dev, step, row, m.mark_dev + j);
+        // the integrator's record, field by field as sgpr_md_run fills it for the fused loop
+        FinNext x;
+        memset(&x, 0, sizeof(x));
+        x.step = step;
+        x.x_cur = m.X.p + N3 * sl; x.v_cur = m.V.p + N3 * sl;
+        x.x_next = m.X.p + N3 * sn; x.v_next = m.V.p + N3 * sn;
+        x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise ? m.noise.p + (size_t)j * 3 * N : nullptr;
+        x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
+        if (m.nh) {
+            x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
+            x.x_prev = m.X.p + N3 * sp; x.v_now = m.V.p + N3 * sl;
+            if (m.t + j > 0) x.v_cur = m.V.p + N3 * sp;   // (v_(n-1): what the integrator holds when it asks for the forces)
+            x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
+        }
+        x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
+        x.ke_cur = m.KE.p + (size_t)2 * N * sl;
+        x.halt = m.halt.p;
+        const bool stay = final_eval && j == nevals - 1;
+        hipLaunchKernelGGL(md_bcm_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, (const double *)info,
+                           packed, m.bcm_x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
+        hipLaunchKernelGGL(md_bcm_ke_kernel, dim3(1), dim3(256), 0, st, N, (const double *)(m.KE.p + (size_t)2 * N * sl), (const int *)m.halt.p,
+                           step, row);
+        if (m.nh)   // zeta of the next configuration from this one's kinetic energy
+            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
+                               m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, step, row);
+        return SGPR_OK;
+    });
+    for (int k = 0; k < K; k++) m.bcm[k]->lists_valid = false;
+    h->lists_valid = false;
+    if (rc_) return rc_;
+    if (const int rc = md_collect(h, enq, st, scalars, false)) return rc;
+    MdHalt r;
+    if (const int rd = md_decode_halt(h, step0, enq, final_eval, false, &r)) return rd;
+    // a capacity overflowed (md_decode_halt has cleared the live handle's `warm`): the next call's checked pass grows whatever it
+    // was, on whichever member
+    if (r.code == 2)
+        for (int k = 0; k < K; k++) m.bcm[k]->warm = false;
+    if (r.done > 0) {
+        m.bcm_info.assign(BCM_INFO, 0.0);
+        HIPCHK(hipMemcpy(m.bcm_info.data(), m.bcm_info_d.p + (size_t)BCM_INFO * (r.done - 1), sizeof(double) * BCM_INFO, hipMemcpyDeviceToHost));
+    }
+    if (scalars && r.done > 0) {
+        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
+        if (!m.nh)
+            for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
+    }
+    m.evaluated = r.code == 1 || (r.code == 0 && final_eval != 0);
+    *evals_done = r.done;
+    if (halt_code) *halt_code = r.code;
+    return SGPR_OK;
+}
+
 // Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last
 // the integrator moves on with the next row of `noise` ([nevals][N][3] standard normal deviates, caller atom order; null:
 // velocity Verlet).  Stops at the first evaluation whose largest covloss reaches `ediff` (<= 0: never): *evals_done
@@ -646,6 +842,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_run: call sgpr_md_begin first");
     if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
     if (m.relax) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    if (!m.bcm.empty()) return md_committee_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
     HIPCHK(hipSetDevice(h->device));
     if (const int rb = md_rebind(h)) return rb;
     if (m.world > 1 && !(peer_on(h) && h->peer.world == m.world && h->peer.rank == m.rank))
@@ -874,6 +1071,7 @@ extern "C" int sgpr_md_record(sgpr_model *h, int every, int what)
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_record: call sgpr_md_begin first");
     if (every < 0 || (what & ~3)) return fail(SGPR_E_INVALID, "sgpr_md_record: every >= 0, what = bit 0 (velocities) | bit 1 (results)");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.world);
+    if (every && !m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run has a committee (sgpr_md_committee), which records no frames");
     m.rec_every = every;
     m.rec_what = every ? what : 0;
     return SGPR_OK;
@@ -942,5 +1140,6 @@ extern "C" int sgpr_md_end(sgpr_model *h)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_end: bad arguments");
     h->md.active = false;
+    h->md.bcm.clear(); h->md.bcm_info.clear();   // (the borrowed members are let go)
     return SGPR_OK;
 }

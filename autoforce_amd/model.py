@@ -827,8 +827,31 @@ class SGPRModel:
                 out["velocities"] = vel
         return out
 
+    def md_committee(self, members):
+        """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
+        SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every
+        configuration of md_run, in the order given with this model last — the run integrates the weighted forces, gates on
+        the largest member-wise minimum covloss, and its rows and md_state(results=True) carry the committee's energy,
+        forces, stress and covloss.  After md_begin (and its thermostat), before the first md_run; an empty list detaches.
+        Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, no mask, no frame record.  The model keeps
+        references to the members until md_end, the next md_begin or a detach."""
+        members = list(members or ())
+        arr = (C.c_void_p * max(len(members), 1))(*[None if mm is None else mm._h.value for mm in members])
+        check(_lib.load().sgpr_md_committee(self._h, len(members), arr if members else None))
+        self._md["members"] = members
+
+    def md_committee_info(self):
+        """(w [K + 1], covmax [K + 1]) — the weights and the largest covlosses of the members in their order, this model last —
+        of the last evaluation whose results stand (sgpr_md_committee_info)."""
+        K1 = len(self._md.get("members") or ()) + 1
+        w, cm = np.zeros(K1), np.zeros(K1)
+        check(_lib.load().sgpr_md_committee_info(self._h, ptr(w), ptr(cm)))
+        return w, cm
+
     def md_end(self):
         check(_lib.load().sgpr_md_end(self._h))
+        if getattr(self, "_md", None):
+            self._md.pop("members", None)
 
     def descriptors(self, N):
         S, D = len(self.species), (self.nmax + 1) ** 2 * (self.lmax + 1)

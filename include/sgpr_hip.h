@@ -464,6 +464,34 @@ int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N);
 int sgpr_md_record(sgpr_model *h, int every, int what);
 int sgpr_md_frame_count(sgpr_model *h, int *count);
 int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *positions, double *velocities_pre, double *packed);
+/* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
+ * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
+ * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
+ * order given, h last (k = K):
+ *     covmax_k = max_i beta_k(i),  b_k = -ln(covmax_k) if covmax_k < 1 else 0,  s_k = b_k / covmax_k  (covmax_k = 0: +inf)
+ *     any s_k infinite: w_k = 1 where it is, 0 elsewhere;   sum_k s_k <= 0: w = e_K;   then w <- w / sum_k w_k
+ *     E, every force component and the nine virial entries: sum_k w_k (.)_k in member order, without contraction
+ *     beta_tot(i) = min_k beta_k(i): the covloss sgpr_md_state reports; max_i beta_tot(i) is what `ediff` gates (scalar 11)
+ * Fixed summation order, no float atomics: two runs give the same bits.  The covloss gate and a capacity overflow of ANY member
+ * halt the run at the evaluation itself, before anything moves.  The rows of scalars keep their layout.
+ *
+ * sgpr_md_committee       after sgpr_md_begin and, if used, sgpr_md_thermostat, before the first sgpr_md_run.  K = 0 or
+ *                         members = NULL detaches: the run is the one without this call and launches what it launched before.
+ *                         The members are BORROWED: the caller keeps them alive until sgpr_md_end, the next sgpr_md_begin or a
+ *                         detach (each lets them go), and may use them between two sgpr_md_run calls (every call binds them to the run's system
+ *                         again and repeats the capacity-checked pass where needed).  Langevin with uploaded or counter-based
+ *                         deviates, velocity Verlet, Nose-Hoover NVT.  SGPR_E_UNSUPPORTED: a run with a barostat, a relaxation,
+ *                         held components, an armed frame record (and sgpr_md_record, sgpr_md_fix, sgpr_md_barostat,
+ *                         sgpr_md_relax behind an attached committee), a run begun on more than one rank, a member on another
+ *                         device, K > 15.  SGPR_E_INVALID: a member that is h itself, a null or duplicate member, a member
+ *                         without weights or without choli, a run that has started (a detach too: a started run keeps
+ *                         what it has), and sgpr_md_thermostat behind an attached committee.
+ * sgpr_md_committee_info  w[K + 1] and covmax[K + 1] (either may be NULL) of the last evaluation whose results stand — after a
+ *                         halted or `final` call the numbers behind the packed results sgpr_md_state returns.  SGPR_E_INVALID
+ *                         without a committee or before an evaluation stands.
+ * The handle stays usable after every error above. */
+int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *members);
+int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
