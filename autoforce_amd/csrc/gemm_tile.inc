@@ -473,7 +473,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
                     const int row = row0 + wr * 16 * TM + tm * 16 + (lane >> 4) + 4 * r;
                     const double v = acc[tm][tn][r];
                     if (do_store) {
-                        if (row < p.M && col < p.N) p.C[(size_t)row * p.ldc + col] = v;
+                        if (row < p.M && col < p.N) {
+                            // (W of the grouped launch is read by the reverse kernel only: write-through, sgpr_internal.h)
+                            if constexpr (EPI == EPI_WCOV) st_wt(&p.C[(size_t)row * p.ldc + col], v);
+                            else p.C[(size_t)row * p.ldc + col] = v;
+                        }
                     } else if (EPI == EPI_SUBLOWER) {
                         if (row < p.M && col < p.N) p.C[(size_t)row * p.ldc + col] -= v;
                     } else if (do_kern) {
@@ -518,7 +522,10 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
                     s += row_dpp<0x141>(s);
                     s += row_dpp<0x140>(s);
                     const int row = row0 + wr * 16 * TM + tm * 16 + (lane >> 4) + 4 * r;
-                    if ((lane & 15) == 0 && row < p.M && s != 0.0) p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + wc] = s;
+                    if ((lane & 15) == 0 && row < p.M && s != 0.0) {
+                        if constexpr (EPI == EPI_WCOV) st_wt(&p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + wc], s);
+                        else p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + wc] = s;
+                    }
                 }
             }
         }
@@ -721,8 +728,9 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
                 const double k = (!rl && !cl) ? pm1 * v : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
                 const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
                 if (same && row < p.M && col < p.N) {
-                    p.C[(size_t)row * p.ldc + col] = k;
-                    if (p.Aw) p.Aw[(size_t)row * p.ldc + col] = e_mu * kp;
+                    // (K and Aw are read by the next launch only: write-through, sgpr_internal.h)
+                    st_wt(&p.C[(size_t)row * p.ldc + col], k);
+                    if (p.Aw) st_wt(&p.Aw[(size_t)row * p.ldc + col], e_mu * kp);
                     esum += k * e_mu;
                 }
             } else {  // row squares (covloss): the value itself; squared below
@@ -773,8 +781,8 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
         }
         if (lane == 0) {
             double *ep = g.Epart + (size_t)(g.p.tiles ? bid : rt * g.col_tiles + ct) * 8;
-            ep[wave] = esum;
-            if constexpr (HALF) ep[wave + 4] = 0.0;   // (the reducer sums eight partials per tile)
+            st_wt(&ep[wave], esum);
+            if constexpr (HALF) st_wt(&ep[wave + 4], 0.0);   // (the reducer sums eight partials per tile)
         }
     }
     if (g.stamps && threadIdx.x == 0) {

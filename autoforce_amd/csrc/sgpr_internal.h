@@ -41,6 +41,22 @@ struct PackEntry {
     double coef;    // nnl[n_u][n_v][l] * (u==v ? 1 : sqrt(2))
 };
 
+// ---- write-through stores of the step's hand-over arrays ----------------------------------
+// An array that a kernel of the step writes once and only a LATER kernel reads is stored device-scope write-through
+// (`sc1`): the bytes leave the XCD's L2 while the kernel still runs, instead of waiting dirty for the write-back at the
+// kernel's end, which the next kernel of the stream then stands behind.  The values are the plain stores' values.  A
+// relaxed device-scope atomic store: a form the compiler schedules and counts (global_store_dword / dwordx2 ... sc1),
+// for 4- and 8-byte values (int, double, 64-bit words) — the epilogues that use it store 8 bytes per lane as it is.
+// Used where the trace showed it to pay: K, Aw and the energy partials of the K_nm epilogue, W and
+// the covloss row sums of the grouped launch.  The descriptor kernels keep plain stores (DESIGN_HISTORY.md).
+template <typename T> struct WtValue { typedef T type; };   // (the pointer alone names the type)
+template <typename T>
+__device__ __forceinline__ void st_wt(T *p, typename WtValue<T>::type v)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "4- and 8-byte values");
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 struct DevModel;  // defined in api.hip
 
 // ---- launchers (each enqueues on `st`, never synchronises) -------------------------------
