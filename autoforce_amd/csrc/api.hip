@@ -19,6 +19,7 @@
 
 #include "../../include/sgpr_hip.h"
 #include "sgpr_internal.h"
+#include "nl_grid.inc"
 #include <cmath>
 #include <limits>
 
@@ -624,6 +625,14 @@ __device__ __forceinline__ double fin_quad_lane(double v)
 {
     return fin_dpp<K * 0x55>(v);
 }
+// the two kinetic terms of an atom, a component on each of lanes 0..2 of its quad, summed (0 + 1) + 2 into ke_cur[i]: m v^2
+// after the closing half kick | before it; `first`: the quad's lane 0 (of an atom that exists), which stores
+__device__ __forceinline__ void fin_store_ke(double ke, double kp, bool first, double *ke_cur, size_t i)
+{
+    const double k3 = fin_quad_lane<0>(ke) + fin_quad_lane<1>(ke) + fin_quad_lane<2>(ke);
+    const double p3 = fin_quad_lane<0>(kp) + fin_quad_lane<1>(kp) + fin_quad_lane<2>(kp);
+    if (first) *(double2 *)(ke_cur + 2 * i) = make_double2(k3, p3);
+}
 
 // reducer workgroup q: E (0), the nine virial components (1..9), the largest neighbour count (10)
 __device__ __forceinline__ void finalize_reduce(const FinArgs &f, int q)
@@ -878,19 +887,8 @@ __global__ __launch_bounds__(256) void finalize_scatter_next_kernel(FinArgs f)
     // ---- the next frame's atom w
     int bidx[3], w[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        double fr = xn[0] * g.inv[k] + xn[1] * g.inv[3 + k] + xn[2] * g.inv[6 + k];
-        w[k] = 0;
-        bidx[k] = 0;
-        if (x.pbc[k] && (g.inv[k] != 0.0 || g.inv[3 + k] != 0.0 || g.inv[6 + k] != 0.0)) {
-            const double fl = floor(fr);
-            w[k] = (int)fl;
-            fr -= fl;
-            const int bb = (int)(fr * g.nb[k]);
-            bidx[k] = bb >= g.nb[k] ? g.nb[k] - 1 : (bb < 0 ? 0 : bb);
-        }
-    }
-    const int bin = (bidx[0] * g.nb[1] + bidx[1]) * g.nb[2] + bidx[2];
+    for (int k = 0; k < 3; k++) bidx[k] = nl_place_axis(g, k, x.pbc[k], xn[0], xn[1], xn[2], w[k]);
+    const int bin = nl_bin_index(g, bidx);
     int kb = -1;
     if (slot_b < x.S) kb = atomicAdd(&x.bc_next[(size_t)bin * SGPR_BIN_STRIDE], 1);
     double d2 = 0.0;
@@ -904,19 +902,7 @@ __global__ __launch_bounds__(256) void finalize_scatter_next_kernel(FinArgs f)
     if (!(d2 <= x.thr2)) atomicMax(&x.flags[s1 & 3], 1);
     x.bin_of[ib] = bin;
     x.kslot[ib] = kb;
-    if (slot_b < x.S) {
-        if (max(max(abs(w[0]), abs(w[1])), abs(w[2])) > 32767) atomicMax(&f.stat[3], 1);
-        if (kb < x.cap) {
-            const size_t e = (size_t)bin * x.cap + kb;
-            BinRec r;
-            r.x = xn[0]; r.y = xn[1]; r.z = xn[2]; r.idx = ib; r.pad = 0;
-            x.b_rec[e] = r;
-            BinAux ax;
-            ax.w0 = (short)w[0]; ax.w1 = (short)w[1]; ax.w2 = (short)w[2]; ax.slot = (short)slot_b;
-            x.b_aux[e] = ax;
-        } else
-            atomicMax(&f.stat[1], kb + 1);
-    }
+    if (slot_b < x.S) nl_store_rec(x.b_rec, x.b_aux, x.cap, f.stat, bin, kb, xn[0], xn[1], xn[2], ib, w, slot_b);
 }
 
 // gather form: one wave per atom i,  F_i = (sum_t g_it, kept by the reverse kernel) - sum_t' G[i][t']
@@ -1018,18 +1004,46 @@ __global__ void md_deviates_kernel(int N, int rows, unsigned long long seed, lon
 //     v_n = (x_(n+1) - x_(n-1)) / (2 dt)          (the momenta ASE sets at the end of its step: the kinetic energy of the log line)
 // and, the first time, x_(-1) = x_0 - dt v_0 + dt^2 F_0 / (2 m) (its _calculate_q_past_and_future with zeta = 0).
 // Operations and their order are those of workloads.nose_hoover_nvt: no contraction, true divisions.  Returns v_n.
-__device__ __forceinline__ double md_nh_advance(const FinNext &x, double F, double ms, double xc, double v0, double xprev, double zeta, double &xn)
+// A held component (sgpr_md_fix): F = 0 for the integrator, then the coordinate as it is and v = 0, selected — not computed.
+__device__ __forceinline__ double md_nh_advance(const FinNext &x, bool held, double F, double ms, double xc, double v0, double xprev, double zeta,
+                                                double &xn)
 {
 #pragma clang fp contract(off)
     const double dt = 2.0 * x.hdt;
-    const double a = __ddiv_rn((dt * dt) * F, ms);
+    const double a = __ddiv_rn((dt * dt) * (held ? 0.0 : F), ms);
     double xp = xprev;
     if (x.nh_first) xp = (xc - dt * v0) + 0.5 * a;
     const double b = x.hdt * zeta;
     const double num = ((2.0 * xc) - xp * (1.0 - b)) + a;
     xn = __ddiv_rn(num, 1.0 + b);
     // (the first time v_0 is the caller's own: ASE's first thermostat step takes the kinetic energy of the initial momenta)
-    return x.nh_first ? v0 : __ddiv_rn(xn - xp, 2.0 * dt);
+    const double vnow = x.nh_first ? v0 : __ddiv_rn(xn - xp, 2.0 * dt);
+    if (held) xn = xc;
+    return held ? 0.0 : vnow;
+}
+
+// One BAOAB step of a coordinate (Langevin; without friction and deviates: velocity Verlet), exactly the operations (and their
+// order) of workloads.langevin_nvt: no contraction into fused multiply-adds, a true division.  F: the force of this step, vc:
+// the velocity BEFORE this step's closing half kick, nz: the uploaded deviate (drawn here for (caller atom c, component comp)
+// where the run has a seed instead).  Returns x_(n+1); v3: the velocity that goes with it, ke | kp: m v^2 of this step after
+// the closing half kick | before it.  A held component: as in md_nh_advance, and no noise.
+__device__ __forceinline__ double md_baoab_advance(const FinNext &x, bool held, double F, double ms, double sg, double nz, double xc, double vc, int c,
+                                                   int comp, double &v3, double &ke, double &kp)
+{
+#pragma clang fp contract(off)
+    const double kick = __ddiv_rn(x.hdt * (held ? 0.0 : F), ms);
+    double v = vc;
+    if (x.pending) v = v + kick;       // closes step s: the velocity an observer sees at step s
+    ke = ms * (v * v);
+    kp = ms * (vc * vc);               // ... and the one the calculator is handed with the positions (its log line)
+    const double v2 = v + kick;        // B
+    const double x1 = xc + x.hdt * v2; // A
+    if (!x.noise && x.seed != 0ull && sg != 0.0 && !held) nz = md_deviate(x.seed, x.t_index, c, comp);
+    if (held) nz = 0.0;                // (no noise on a held component)
+    v3 = x.c1 * v2 + sg * nz;          // O
+    double xn = x1 + x.hdt * v3;       // A
+    if (held) { xn = xc; v3 = 0.0; }   // (selected, not computed)
+    return xn;
 }
 
 // zeta_(n+1) = zeta_(n-1) + 2 dt tfact (KE_n - K0) behind evaluation n (ONE workgroup; its own launch: the integrating waves of
@@ -1209,24 +1223,12 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     if (f.has_beta)
         for (int k = lane; k < f.csq_slots; k += 16) x.csq_rw[(size_t)i * f.csq_slots + k] = 0.0;  // (the binning kernel clears these)
     // bin of a position (lane 0 of the row), and the atomic that hands out its slot
-    int bin = 0, kb = -1, w0 = 0, w1 = 0, w2 = 0;
+    int bin = 0, kb = -1, w[3] = {0, 0, 0};
     auto place = [&](double X, double Y, double Z) {
-        int bidx[3], w[3];
+        int bidx[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            double fr = X * g.inv[k] + Y * g.inv[3 + k] + Z * g.inv[6 + k];
-            w[k] = 0;
-            bidx[k] = 0;
-            if (x.pbc[k] && (g.inv[k] != 0.0 || g.inv[3 + k] != 0.0 || g.inv[6 + k] != 0.0)) {
-                const double fl = floor(fr);
-                w[k] = (int)fl;
-                fr -= fl;
-                const int bb = (int)(fr * g.nb[k]);
-                bidx[k] = bb >= g.nb[k] ? g.nb[k] - 1 : (bb < 0 ? 0 : bb);
-            }
-        }
-        bin = (bidx[0] * g.nb[1] + bidx[1]) * g.nb[2] + bidx[2];
-        w0 = w[0]; w1 = w[1]; w2 = w[2];
+        for (int k = 0; k < 3; k++) bidx[k] = nl_place_axis(g, k, x.pbc[k], X, Y, Z, w[k]);
+        bin = nl_bin_index(g, bidx);
         if (slot_b < x.S) kb = atomicAdd(&x.bc_next[(size_t)bin * SGPR_BIN_STRIDE], 1);
     };
     double X = 0.0, Y = 0.0, Z = 0.0;
@@ -1295,37 +1297,20 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         }
     } else if (MD && x.nh) {
         if (lane < 3) {
-            // (a held component: F = 0 for the integrator, then the coordinate as it is and v = 0, selected — not computed)
-            double vnow = md_nh_advance(x, held ? 0.0 : Fv, ms, xc, vc, xpv, zeta, xn);
-            if (held) { xn = xc; vnow = 0.0; }
+            const double vnow = md_nh_advance(x, held, Fv, ms, xc, vc, xpv, zeta, xn);
             ke = ms * (vnow * vnow);
             kp = ke;
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_now[3 * (size_t)i + lane] = vnow;
         }
     } else if (MD && lane < 3) {
-        // BAOAB, exactly the operations (and their order) of workloads.langevin_nvt: no contraction into fused
-        // multiply-adds, a true division
-#pragma clang fp contract(off)
-        const double kick = __ddiv_rn(x.hdt * (held ? 0.0 : Fv), ms);
-        double v = vc;
-        if (x.pending) v = v + kick;       // closes step s: the velocity an observer sees at step s
-        ke = ms * (v * v);
-        kp = ms * (vc * vc);               // ... and the one the calculator is handed with the positions (its log line)
-        const double v2 = v + kick;        // B
-        const double x1 = xc + x.hdt * v2; // A
-        if (!x.noise && x.seed != 0ull && sg != 0.0 && !held) nz = md_deviate(x.seed, x.t_index, c, lane);
-        if (held) nz = 0.0;                // (no noise on a held component)
-        double v3 = x.c1 * v2 + sg * nz;   // O
-        xn = x1 + x.hdt * v3;              // A
-        if (held) { xn = xc; v3 = 0.0; }   // (selected, not computed)
+        double v3;
+        xn = md_baoab_advance(x, held, Fv, ms, sg, nz, xc, vc, c, lane, v3, ke, kp);
         x.x_next[3 * (size_t)i + lane] = xn;
         x.v_next[3 * (size_t)i + lane] = v3;
     }
     if (MODE >= 2) {
-        const double k3 = fin_quad_lane<0>(ke) + fin_quad_lane<1>(ke) + fin_quad_lane<2>(ke);
-        const double p3 = fin_quad_lane<0>(kp) + fin_quad_lane<1>(kp) + fin_quad_lane<2>(kp);
-        if (lane == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);
+        fin_store_ke(ke, kp, lane == 0, x.ke_cur, i);
         X = fin_quad_lane<0>(xn); Y = fin_quad_lane<1>(xn); Z = fin_quad_lane<2>(xn);
         if (lane == 0) place(X, Y, Z);
     }
@@ -1344,19 +1329,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         if (!(d2 <= thr2)) atomicMax(&x.flags[s1 & 3], 1);
         x.bin_of[ib] = bin;
         x.kslot[ib] = kb;
-        if (slot_b < x.S) {
-            if (max(max(abs(w0), abs(w1)), abs(w2)) > 32767) atomicMax(&f.stat[3], 1);
-            if (kb < x.cap) {
-                const size_t e = (size_t)bin * x.cap + kb;
-                BinRec r;
-                r.x = X; r.y = Y; r.z = Z; r.idx = ib; r.pad = 0;
-                x.b_rec[e] = r;
-                BinAux ax;
-                ax.w0 = (short)w0; ax.w1 = (short)w1; ax.w2 = (short)w2; ax.slot = (short)slot_b;
-                x.b_aux[e] = ax;
-            } else
-                atomicMax(&f.stat[1], kb + 1);
-        }
+        if (slot_b < x.S) nl_store_rec(x.b_rec, x.b_aux, x.cap, f.stat, bin, kb, X, Y, Z, ib, w, slot_b);
     }
     clear_bins();
 }

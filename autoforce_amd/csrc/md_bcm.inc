@@ -14,9 +14,10 @@
 //     evaluation itself with nothing moved yet: no speculative evaluation, no lag —, the combined E and virial, the
 //     evaluation's row of scalars and its mark;
 //   * md_bcm_move_kernel, a quad of lanes per atom: the combined force and beta_tot into the run's packed ring slot (caller
-//     order: what sgpr_md_state returns), then the integrator with the combined force — the expressions of
-//     finalize_next_kernel<2> in their order: BAOAB Langevin with uploaded or counter-based deviates, velocity Verlet,
-//     Nose-Hoover through md_nh_advance — writing the next ring slot (sorted order) and the caller-order copy the members read;
+//     order: what sgpr_md_state returns), then the integrator with the combined force — the functions
+//     finalize_next_kernel<2> calls: md_baoab_advance (BAOAB Langevin with uploaded or counter-based deviates, velocity
+//     Verlet) or md_nh_advance (Nose-Hoover), the kinetic terms through fin_store_ke — writing the next ring slot (sorted
+//     order) and the caller-order copy the members read;
 //   * md_bcm_ke_kernel, ONE workgroup: the two kinetic sums of the evaluation in md_nh_kernel's fixed order (no lag: the row
 //     of an evaluation is complete behind its own launches); under Nose-Hoover md_nh_kernel follows as in the fused loop.
 // No float atomics, no contraction in the combination: two runs give the same bits.
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t 
     const int c = perm[ia];
     const double xc = x.x_cur[3 * (size_t)ia + l3], vc = x.v_cur[3 * (size_t)ia + l3];
     const double ms = x.mass[ia], sg = x.sig[ia];
-    double nz = x.noise ? x.noise[3 * (size_t)ia + l3] : 0.0;   // (uniform condition)
+    const double nz = x.noise ? x.noise[3 * (size_t)ia + l3] : 0.0;   // (uniform condition)
     double xpv = 0.0, zeta = 0.0;
     if (x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (uniform condition)
     double F = 0.0, bmin = 1e300;
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t 
     if (act && lane == 3) packed[3 * (size_t)N + c] = bmin;
     double ke, kp, xn;
     if (x.nh) {
-        const double vnow = md_nh_advance(x, F, ms, xc, vc, xpv, zeta, xn);
+        const double vnow = md_nh_advance(x, false, F, ms, xc, vc, xpv, zeta, xn);
         ke = ms * (vnow * vnow);
         kp = ke;
         if (act && lane < 3) {
@@ -152,25 +153,14 @@ __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t 
             if (move) x.x_next[3 * (size_t)i + lane] = xn;
         }
     } else {
-        // BAOAB, the operations of finalize_next_kernel<2> (= workloads.langevin_nvt) in their order: a true division
-        const double kick = __ddiv_rn(x.hdt * F, ms);
-        double v = vc;
-        if (x.pending) v = v + kick;       // closes this evaluation: the velocity an observer sees
-        ke = ms * (v * v);
-        kp = ms * (vc * vc);               // ... and the one the calculator is handed with the positions
-        const double v2 = v + kick;        // B
-        const double x1 = xc + x.hdt * v2; // A
-        if (!x.noise && x.seed != 0ull && sg != 0.0) nz = md_deviate(x.seed, x.t_index, c, l3);
-        const double v3 = x.c1 * v2 + sg * nz;   // O
-        xn = x1 + x.hdt * v3;              // A
+        double v3;
+        xn = md_baoab_advance(x, false, F, ms, sg, nz, xc, vc, c, l3, v3, ke, kp);
         if (act && lane < 3 && move) {
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_next[3 * (size_t)i + lane] = v3;
         }
     }
-    const double k3 = fin_quad_lane<0>(ke) + fin_quad_lane<1>(ke) + fin_quad_lane<2>(ke);
-    const double p3 = fin_quad_lane<0>(kp) + fin_quad_lane<1>(kp) + fin_quad_lane<2>(kp);
-    if (act && lane == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);
+    fin_store_ke(ke, kp, act && lane == 0, x.ke_cur, i);
     if (act && lane < 3 && move) x_caller[3 * (size_t)c + lane] = xn;
 }
 

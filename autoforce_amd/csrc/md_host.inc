@@ -534,6 +534,68 @@ static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval
     return SGPR_OK;
 }
 
+// The deviates of a call ([nevals][N][3], caller atom order; null: none) on the device, sorted on upload: m.noise.
+static int md_upload_noise(sgpr_model *h, int nevals, const double *noise, hipStream_t st)
+{
+    MdState &m = h->md;
+    if (!noise) return SGPR_OK;
+    const size_t len = (size_t)nevals * 3 * m.N;
+    if (m.noise.alloc(len) || m.noise_raw.alloc(len)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * len, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, m.N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
+    return SGPR_OK;
+}
+
+// Nothing is assumed about a handle's candidate lists, pre-binned configuration or bin populations: the next step on it rebuilds
+// the lists and bins into cleared counters.
+static int md_reset_lists(sgpr_model *h, hipStream_t st)
+{
+    h->lists_valid = false;
+    h->pre_valid = false;
+    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    return SGPR_OK;
+}
+
+// The integrator's part of the FinNext record of evaluation j of a call (configuration m.t + j), what the fused loop's last
+// kernel and md_bcm_move_kernel both read: ring slots, deviates (noise_dev: the call's sorted upload, null: none — then the
+// run's seed, if it has one), the Nose-Hoover block, the kinetic terms' slot, the halt word.  pend0: the closing half kick of
+// the call's first configuration is due.  Everything else in x is zero.
+static void md_fill_integrator(const MdState &m, int j, const double *noise_dev, bool pend0, FinNext &x)
+{
+    const int RG = m.ring, sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+    const size_t N3 = (size_t)3 * m.N;
+    memset(&x, 0, sizeof(x));
+    x.x_cur = m.X.p + N3 * sl; x.v_cur = m.V.p + N3 * sl;
+    x.x_next = m.X.p + N3 * sn; x.v_next = m.V.p + N3 * sn;
+    x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise_dev ? noise_dev + N3 * (size_t)j : nullptr;
+    x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
+    if (m.nh) {
+        x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
+        x.x_prev = m.X.p + N3 * sp; x.v_now = m.V.p + N3 * sl;
+        // (v_cur: what the integrator holds when it asks for the forces — ASE sets the momenta of step n after its force
+        // call: v_(n-1), the caller's v_0 the first time; its kinetic energy is scalars[13], the calculator's log line)
+        if (m.t + j > 0) x.v_cur = m.V.p + N3 * sp;
+        x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
+    }
+    x.seed = noise_dev ? 0ull : m.seed; x.t_index = m.t + j;
+    x.ke_cur = m.KE.p + (size_t)2 * m.N * sl;
+    x.halt = m.halt.p;
+}
+
+// The close of a call: the scalar rows of the evaluations that stand to the caller — columns 14 and 15 are zeta and its time
+// integral under Nose-Hoover, a relaxation's own (keep_14_15), else spare: zeroed — and what the call reports.
+static void md_finish_call(MdState &m, const MdHalt &r, double *scalars, bool keep_14_15, bool evaluated, int *evals_done, int *halt_code)
+{
+    if (scalars && r.done > 0) {
+        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
+        if (!keep_14_15)
+            for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
+    }
+    m.evaluated = evaluated;
+    *evals_done = r.done;
+    if (halt_code) *halt_code = r.code;
+}
+
 // The frame of evaluation j of a call (configuration n = m.t + j, n % rec_every == 0), behind the evaluation's last launch: the
 // ring slots sgpr_md_state(which = -1) would read had the call ended with this evaluation — X and P: n % ring; V: that slot
 // (Langevin, velocity Verlet), the slot before it (Nose-Hoover and NPT, n > 0: what the integrator holds when it asks for F_n),
@@ -591,9 +653,7 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
         h->warm = true;
     }
     m.chain_ok = false;
-    h->lists_valid = false;
-    h->pre_valid = false;
-    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    if (const int rl = md_reset_lists(h, st)) return rl;
     const unsigned step0 = h->step_count;
     const double gate = ediff > 0.0 ? ediff : 1e300;
     int enq = 0;
@@ -628,10 +688,7 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
     MdHalt r;
     if (const int rd = md_decode_halt(h, step0, enq, final_eval, true, &r)) return rd;
     md_record_close(m, r);
-    if (scalars && r.done > 0) memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
-    m.evaluated = r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0);
-    *evals_done = r.done;
-    if (halt_code) *halt_code = r.code;
+    md_finish_call(m, r, scalars, true, r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
     h->lists_valid = false;
     return SGPR_OK;
 }
@@ -719,12 +776,7 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
     if (m.bcm_info_d.alloc((size_t)BCM_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-    if (noise) {
-        if (m.noise.alloc((size_t)nevals * 3 * N) || m.noise_raw.alloc((size_t)nevals * 3 * N))
-            return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * (size_t)nevals * 3 * N, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
-    }
+    if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
     const int s0 = (int)(m.t % RG);
     const unsigned step_a = h->step_count;
     // the current configuration in caller order, for the members (the halt words are armed: nothing has halted this call)
@@ -748,14 +800,10 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
             if (rc_) return rc_;
             mk->warm = true;
         }
-        mk->lists_valid = false;
-        mk->pre_valid = false;
-        HIPCHK(hipMemsetAsync(mk->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+        if (const int rl = md_reset_lists(mk, st)) return rl;
     }
     m.chain_ok = false;
-    h->lists_valid = false;
-    h->pre_valid = false;
-    HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    if (const int rl = md_reset_lists(h, st)) return rl;
     const unsigned step0 = h->step_count;
     const double gate = ediff > 0.0 ? ediff : 1e300;
     const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
@@ -775,23 +823,9 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         double *packed = m.P.p + plen * sl, *info = m.bcm_info_d.p + (size_t)BCM_INFO * j, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
         hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, packed, info, gate, m.halt.p,
                            m.halt_host_dev, step, row, m.mark_dev + j);
-        // the integrator's record, field by field as sgpr_md_run fills it for the fused loop
         FinNext x;
-        memset(&x, 0, sizeof(x));
-        x.step = step;
-        x.x_cur = m.X.p + N3 * sl; x.v_cur = m.V.p + N3 * sl;
-        x.x_next = m.X.p + N3 * sn; x.v_next = m.V.p + N3 * sn;
-        x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise ? m.noise.p + (size_t)j * 3 * N : nullptr;
-        x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
-        if (m.nh) {
-            x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
-            x.x_prev = m.X.p + N3 * sp; x.v_now = m.V.p + N3 * sl;
-            if (m.t + j > 0) x.v_cur = m.V.p + N3 * sp;   // (v_(n-1): what the integrator holds when it asks for the forces)
-            x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
-        }
-        x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
-        x.ke_cur = m.KE.p + (size_t)2 * N * sl;
-        x.halt = m.halt.p;
+        md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
+        x.step = step;   // (the fused loop: enqueue_step sets it)
         const bool stay = final_eval && j == nevals - 1;
         hipLaunchKernelGGL(md_bcm_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, (const double *)info,
                            packed, m.bcm_x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
@@ -816,14 +850,7 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         m.bcm_info.assign(BCM_INFO, 0.0);
         HIPCHK(hipMemcpy(m.bcm_info.data(), m.bcm_info_d.p + (size_t)BCM_INFO * (r.done - 1), sizeof(double) * BCM_INFO, hipMemcpyDeviceToHost));
     }
-    if (scalars && r.done > 0) {
-        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
-        if (!m.nh)
-            for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
-    }
-    m.evaluated = r.code == 1 || (r.code == 0 && final_eval != 0);
-    *evals_done = r.done;
-    if (halt_code) *halt_code = r.code;
+    md_finish_call(m, r, scalars, m.nh, r.code == 1 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
     return SGPR_OK;
 }
 
@@ -855,12 +882,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     m.started = true;
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, m.npt)) return rp;   // (the cell record: a moving cell only)
-    if (noise) {
-        if (m.noise.alloc((size_t)nevals * 3 * N) || m.noise_raw.alloc((size_t)nevals * 3 * N))
-            return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * (size_t)nevals * 3 * N, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
-    }
+    if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
     // the first evaluation sizes the capacities for this configuration if nothing has yet (synchronised, results discarded)
     const int RG = m.ring, s0 = (int)(m.t % RG);
     if (m.npt) { m.np.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.np.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
@@ -883,11 +905,8 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (chain) {
         h->lists_valid = true;
         h->pre_valid = true; h->pre_pos = m.chain_pos; h->pre_cell = cell_of(m.t); h->pre_step = h->step_count;
-    } else {
-        h->lists_valid = false;
-        h->pre_valid = false;
-        HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
-    }
+    } else if (const int rl = md_reset_lists(h, st))
+        return rl;
     const unsigned step0 = h->step_count;
     const unsigned epoch0 = h->peer.epoch;
     const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
@@ -898,31 +917,18 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         nx.mode = 2;
         nx.pos_next = m.X.p + (size_t)3 * N * sn;
         FinNext &x = nx.md;
-        memset(&x, 0, sizeof(x));
-        x.x_cur = m.X.p + (size_t)3 * N * sl; x.v_cur = m.V.p + (size_t)3 * N * sl;
-        x.x_next = m.X.p + (size_t)3 * N * sn; x.v_next = m.V.p + (size_t)3 * N * sn;
-        x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise ? m.noise.p + (size_t)j * 3 * N : nullptr;
-        x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
-        if (m.nh) {
-            x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
-            x.x_prev = m.X.p + (size_t)3 * N * sp; x.v_now = m.V.p + (size_t)3 * N * sl;
-            // (v_cur: what the integrator holds when it asks for the forces — ASE sets the momenta of step n after its force
-            // call: v_(n-1), the caller's v_0 the first time; its kinetic energy is scalars[13], the calculator's log line)
-            if (m.t + j > 0) x.v_cur = m.V.p + (size_t)3 * N * sp;
-            x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
-        }
+        md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         if (m.npt) {
             x.npt_cur = m.slot(m.t + j); x.npt_next = m.slot(m.t + j + 1);
             x.q_cur = m.Q.p + (size_t)3 * N * sl; x.q_prev = m.Q.p + (size_t)3 * N * sp; x.q_next = m.Q.p + (size_t)3 * N * sn;
             nx.cell_next = x.npt_next->h;
             h->step_grid = &x.npt_cur->grid;
         }
-        x.seed = noise ? 0ull : m.seed; x.t_index = m.t + j;
         x.fixed = m.fix();
-        x.ke_cur = m.KE.p + (size_t)2 * N * sl; x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
+        x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
         x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
         x.ediff = ediff > 0.0 ? ediff : 1e300;
-        x.halt = m.halt.p; x.halt_host = m.halt_host_dev;
+        x.halt_host = m.halt_host_dev;
         x.scal_cur = m.scal_d.p + (size_t)SGPR_MD_SCAL * j; x.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (j > 0 ? j - 1 : 0);
         x.mark_cur = m.mark_dev + j;
         // (the last evaluation of a `final` run integrates speculatively too: its outcome is not adopted below)
@@ -963,7 +969,10 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     // starts from clean bin populations.
     const bool keep_chain = md_halt_step(m) == MD_HALT_NONE && !final_eval && enq == nevals && h->pre_valid;
     const double *keep_pos = h->pre_pos;
-    if (!keep_chain) HIPCHK(hipMemsetAsync(h->d_bin_count.p, 0, 2 * SGPR_BIN_INTS * sizeof(int), st));
+    // (the flags md_reset_lists clears with the populations are read by nobody before this function clears them itself on its
+    // way out: lists_valid below, pre_valid when `guard` goes; keep_chain and keep_pos were taken above)
+    if (!keep_chain)
+        if (const int rl = md_reset_lists(h, st)) return rl;
     MdHalt r;
     if (const int rd = md_decode_halt(h, step0, enq, final_eval, m.npt, &r)) return rd;
     md_record_close(m, r);
@@ -979,14 +988,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         m.chain_ok = true; m.chain_step = h->step_count; m.chain_bind = h->bind_gen; m.chain_opt = h->opt_gen; m.chain_t = m.t;
         m.chain_pos = keep_pos;
     }
-    if (scalars && r.done > 0) {
-        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
-        if (!m.nh)   // (Nose-Hoover: zeta and its time integral of the evaluation's configuration; else spare)
-            for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
-    }
-    m.evaluated = r.code == 1 || (r.code == 0 && final_eval != 0);
-    *evals_done = r.done;
-    if (halt_code) *halt_code = r.code;
+    md_finish_call(m, r, scalars, m.nh, r.code == 1 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
     h->lists_valid = false;
     return SGPR_OK;
 }

@@ -139,19 +139,8 @@ __global__ __launch_bounds__(256) void nl_bin_kernel(BinArgs a)
     }
     int bidx[3], w[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        double f = x * g.inv[k] + y * g.inv[3 + k] + z * g.inv[6 + k];
-        w[k] = 0;
-        bidx[k] = 0;
-        if (a.pbc[k] && (g.inv[k] != 0.0 || g.inv[3 + k] != 0.0 || g.inv[6 + k] != 0.0)) {
-            const double fl = floor(f);
-            w[k] = (int)fl;
-            f -= fl;
-            const int b = (int)(f * g.nb[k]);
-            bidx[k] = b >= g.nb[k] ? g.nb[k] - 1 : (b < 0 ? 0 : b);
-        }
-    }
-    const int bin = (bidx[0] * g.nb[1] + bidx[1]) * g.nb[2] + bidx[2];
+    for (int k = 0; k < 3; k++) bidx[k] = nl_place_axis(g, k, a.pbc[k], x, y, z, w[k]);
+    const int bin = nl_bin_index(g, bidx);
     a.bin_of[i] = bin;
     if (slot_i >= a.S) {  // a ghost (species outside the model's table, option "ignore_unknown_species"): nobody's neighbour
         a.kslot[i] = -1;
@@ -159,17 +148,7 @@ __global__ __launch_bounds__(256) void nl_bin_kernel(BinArgs a)
     }
     const int k = atomicAdd(&a.bin_count[(size_t)bin * SGPR_BIN_STRIDE], 1);
     a.kslot[i] = k;
-    if (max(max(abs(w[0]), abs(w[1])), abs(w[2])) > 32767) atomicMax(&a.stat[3], 1);  // atoms > 32767 cells away
-    if (k < a.cap) {
-        const size_t e = (size_t)bin * a.cap + k;
-        BinRec r;
-        r.x = x; r.y = y; r.z = z; r.idx = i; r.pad = 0;
-        a.b_rec[e] = r;
-        BinAux ax;
-        ax.w0 = (short)w[0]; ax.w1 = (short)w[1]; ax.w2 = (short)w[2]; ax.slot = (short)slot_i;
-        a.b_aux[e] = ax;
-    } else
-        atomicMax(&a.stat[1], k + 1);  // rare: capacity exceeded, the host grows it and reruns
+    nl_store_rec(a.b_rec, a.b_aux, a.cap, a.stat, bin, k, x, y, z, i, w, slot_i);
 }
 
 void launch_neighbor_bin(const NlParams &p, const int *perm, const double *pos_in, double *pos, const double *cell,

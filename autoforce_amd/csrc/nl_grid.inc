@@ -1,6 +1,9 @@
 // The bin grid of a cell (NlGrid, sgpr_internal.h), made on the device: by the binning kernel (neighbor.hip) for the cell
 // of its step, and by md_npt_kernel (md_npt.inc) for the cell a moving-cell MD step will bin its atoms in — one
-// definition, so that both make the same grid of the same cell.
+// definition, so that both make the same grid of the same cell.  And the rule that places an atom in that grid
+// (nl_place_axis, nl_bin_index) with the record a bin keeps of it (nl_store_rec): one definition for the binning kernel and
+// for every last kernel that bins the next step's atoms itself (finalize_next_kernel, finalize_scatter_next_kernel,
+// shard_next_kernel).
 #pragma once
 
 __device__ __forceinline__ double det3d(const double *h)
@@ -87,4 +90,47 @@ __device__ inline void nl_make_grid(const double *cell, const int *pbc, double r
         g.ortho = 0;
     }
     g.nbins = g.nb[0] * g.nb[1] * g.nb[2];
+}
+
+// Direction k of the rule that places position (X, Y, Z) in grid g: the index of its bin along k, and w: how many cells it
+// was wrapped by (the floor of the fractional coordinate; 0 along an open direction or without a cell).
+__device__ __forceinline__ int nl_place_axis(const NlGrid &g, int k, int periodic, double X, double Y, double Z, int &w)
+{
+    double fr = X * g.inv[k] + Y * g.inv[3 + k] + Z * g.inv[6 + k];
+    w = 0;
+    if (!(periodic && (g.inv[k] != 0.0 || g.inv[3 + k] != 0.0 || g.inv[6 + k] != 0.0))) return 0;
+    const double fl = floor(fr);
+    w = (int)fl;
+    fr -= fl;
+    const int b = (int)(fr * g.nb[k]);
+    return b >= g.nb[k] ? g.nb[k] - 1 : (b < 0 ? 0 : b);
+}
+
+// The bin of the three indices.  A caller places an atom with
+//     for (k = 0 .. 2) bidx[k] = nl_place_axis(g, k, pbc[k], X, Y, Z, w[k]);   bin = nl_bin_index(g, bidx);
+// The loop over the directions stays in the kernel on purpose: `pbc` lives in the kernel's argument record, and indexing that
+// record by the loop counter is what keeps the compiler from reading the whole record ahead of the kernel's first instruction
+// (with the loop inside a function here: 16 to 50 more SGPRs in three of the four kernels, one to four more VGPRs in two).
+__device__ __forceinline__ int nl_bin_index(const NlGrid &g, const int (&bidx)[3])
+{
+    return (bidx[0] * g.nb[1] + bidx[1]) * g.nb[2] + bidx[2];
+}
+
+// What bin `bin` keeps of the atom (sorted index idx, species slot `slot`) that nl_place_axis / nl_bin_index put there and whose returning atomic
+// on the bin's population handed out slot k — the atomic itself stays with the caller, who knows where its round trip hides.
+// stat[3]: a wrap beyond int16; stat[1]: the population of a bin beyond its capacity (rare: the host grows it and reruns).
+__device__ __forceinline__ void nl_store_rec(BinRec *b_rec, BinAux *b_aux, int cap, int *stat, int bin, int k, double X, double Y, double Z,
+                                             int idx, const int (&w)[3], int slot)
+{
+    if (max(max(abs(w[0]), abs(w[1])), abs(w[2])) > 32767) atomicMax(&stat[3], 1);  // atoms > 32767 cells away
+    if (k < cap) {
+        const size_t e = (size_t)bin * cap + k;
+        BinRec r;
+        r.x = X; r.y = Y; r.z = Z; r.idx = idx; r.pad = 0;
+        b_rec[e] = r;
+        BinAux ax;
+        ax.w0 = (short)w[0]; ax.w1 = (short)w[1]; ax.w2 = (short)w[2]; ax.slot = (short)slot;
+        b_aux[e] = ax;
+    } else
+        atomicMax(&stat[1], k + 1);
 }

@@ -219,34 +219,17 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
     double ke = 0.0, kp = 0.0, v3 = 0.0;
     if (MD && x.nh) {
         if (k < 3) {
-            double vnow = md_nh_advance(x, held ? 0.0 : tot, ms, xc, vc, xpv, zeta, xn);
-            if (held) { xn = xc; vnow = 0.0; }
+            const double vnow = md_nh_advance(x, held, tot, ms, xc, vc, xpv, zeta, xn);
             ke = ms * (vnow * vnow);
             kp = ke;
             x.v_now[3 * (size_t)i + k] = vnow;
         }
-    } else if (MD && k < 3) {
-        // BAOAB, the operations of finalize_next_kernel<2> (= workloads.langevin_nvt) in their order: no contraction
-#pragma clang fp contract(off)
-        const double kick = __ddiv_rn(x.hdt * (held ? 0.0 : tot), ms);
-        double v = vc;
-        if (x.pending) v = v + kick;
-        ke = ms * (v * v);
-        kp = ms * (vc * vc);
-        const double v2 = v + kick;
-        const double x1 = xc + x.hdt * v2;
-        if (!x.noise && x.seed != 0ull && sg != 0.0 && !held) nz = md_deviate(x.seed, x.t_index, c, k);
-        if (held) nz = 0.0;
-        v3 = x.c1 * v2 + sg * nz;
-        xn = x1 + x.hdt * v3;
-        if (held) { xn = xc; v3 = 0.0; }
-    }
-    // the quad's three components, in the order (0 + 1) + 2 of the single-rank kernel
-    const double X = fin_dpp<0x00>(xn), Y = fin_dpp<0x55>(xn), Z = fin_dpp<0xAA>(xn);
+    } else if (MD && k < 3)
+        xn = md_baoab_advance(x, held, tot, ms, sg, nz, xc, vc, c, k, v3, ke, kp);
+    // the quad's three components
+    const double X = fin_quad_lane<0>(xn), Y = fin_quad_lane<1>(xn), Z = fin_quad_lane<2>(xn);
     if (MD) {
-        const double k3 = fin_dpp<0x00>(ke) + fin_dpp<0x55>(ke) + fin_dpp<0xAA>(ke);
-        const double p3 = fin_dpp<0x00>(kp) + fin_dpp<0x55>(kp) + fin_dpp<0xAA>(kp);
-        if (k == 0) *(double2 *)(x.ke_cur + 2 * (size_t)i) = make_double2(k3, p3);
+        fin_store_ke(ke, kp, k == 0, x.ke_cur, i);
         if (k < 3) {
             x.x_next[3 * (size_t)i + k] = xn;
             if (!x.nh) x.v_next[3 * (size_t)i + k] = v3;
@@ -254,43 +237,19 @@ __global__ __launch_bounds__(256) void shard_next_kernel(FinArgs f, ShardSrc s)
     }
     if (k < 3) x.pos[3 * (size_t)i + k] = xn;
     const double dd = k < 3 ? xn - p0 : 0.0;
-    const double d0 = fin_dpp<0x00>(dd), d1 = fin_dpp<0x55>(dd), d2v = fin_dpp<0xAA>(dd);
+    const double d0 = fin_quad_lane<0>(dd), d1 = fin_quad_lane<1>(dd), d2v = fin_quad_lane<2>(dd);
     if (k != 0) return;
     const double d2 = d0 * d0 + d1 * d1 + d2v * d2v;
     int bidx[3], w[3];
-    const double P3[3] = {X, Y, Z};
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        double fr = P3[0] * g.inv[a] + P3[1] * g.inv[3 + a] + P3[2] * g.inv[6 + a];
-        w[a] = 0;
-        bidx[a] = 0;
-        if (x.pbc[a] && (g.inv[a] != 0.0 || g.inv[3 + a] != 0.0 || g.inv[6 + a] != 0.0)) {
-            const double fl = floor(fr);
-            w[a] = (int)fl;
-            fr -= fl;
-            const int bb = (int)(fr * g.nb[a]);
-            bidx[a] = bb >= g.nb[a] ? g.nb[a] - 1 : (bb < 0 ? 0 : bb);
-        }
-    }
-    const int bin = (bidx[0] * g.nb[1] + bidx[1]) * g.nb[2] + bidx[2];
+    for (int a = 0; a < 3; a++) bidx[a] = nl_place_axis(g, a, x.pbc[a], X, Y, Z, w[a]);
+    const int bin = nl_bin_index(g, bidx);
     int kb = -1;
     if (slot_i < x.S) kb = atomicAdd(&x.bc_next[(size_t)bin * SGPR_BIN_STRIDE], 1);
     if (!(d2 <= x.thr2)) atomicMax(&x.flags[s1 & 3], 1);
     x.bin_of[i] = bin;
     x.kslot[i] = kb;
-    if (slot_i < x.S) {
-        if (max(max(abs(w[0]), abs(w[1])), abs(w[2])) > 32767) atomicMax(&f.stat[3], 1);
-        if (kb < x.cap) {
-            const size_t e = (size_t)bin * x.cap + kb;
-            BinRec r;
-            r.x = X; r.y = Y; r.z = Z; r.idx = i; r.pad = 0;
-            x.b_rec[e] = r;
-            BinAux ax;
-            ax.w0 = (short)w[0]; ax.w1 = (short)w[1]; ax.w2 = (short)w[2]; ax.slot = (short)slot_i;
-            x.b_aux[e] = ax;
-        } else
-            atomicMax(&f.stat[1], kb + 1);
-    }
+    if (slot_i < x.S) nl_store_rec(x.b_rec, x.b_aux, x.cap, f.stat, bin, kb, X, Y, Z, i, w, slot_i);
 }
 
 // ---------------------------------------------------------------------------- host side
