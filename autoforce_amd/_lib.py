@@ -85,6 +85,9 @@ SIGNATURES = {
     "sgpr_md_frames": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sgpr_md_committee": (C.c_int, [_vp, C.c_int, _vp]),
     "sgpr_md_committee_info": (C.c_int, [_vp, _vp, _vp]),
+    "sgpr_md_filter": (C.c_int, [_vp, _dbl, _vp, _vp]),
+    "sgpr_md_filter_push": (C.c_int, [_vp, _vp, _vp]),
+    "sgpr_md_filter_state": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_sync_check": (C.c_int, [_vp, _vp]),
     "sgpr_comm_unique_id": (C.c_int, [_vp]),
     "sgpr_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

@@ -535,7 +535,7 @@ class ActiveCalculator(Calculator):
     RECORD_BYTES = 256 << 20   # the frame record of one md_run call (run_md, run_relax) stays within this much device memory
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -571,9 +571,18 @@ class ActiveCalculator(Calculator):
         set_momenta does), it receives no noise and keeps its coordinate bit for bit.  Temperatures (the log line, the yield) are
         over the g = 3N - n_fixed remaining degrees of freedom, as atoms.get_temperature(); Nose-Hoover uses
         tfact = 2 / (g kT ttime^2) and K0 = g kT / 2, the project's own definition (ase.md.npt.NPT takes no constraints).  Not
-        with a barostat; any other constraint kind: NotImplementedError."""
+        with a barostat; any other constraint kind: NotImplementedError.
+        ml_filter: the reference's FilterDeltas around the atoms (cl/md.py:76-79, calculator/active.py:47-76) inside the loop: a
+        shrink factor (0 < s < 1), or a workloads.FilterState (shrink, f, s) whose accumulators are read at the start and
+        filled at the end — one holder carries them through several run_md calls, as the reference's one wrapper does.  The
+        jump self.deltas that an update's calculate() publishes is pushed into the device's accumulators (SGPRModel.
+        md_filter_push) before the halted configuration is evaluated again; the integrator sees the filtered forces (and, with a
+        barostat, stress), self.results and the log stay the model's.  Host loops: the twins' ml_filter=.  With a filter the
+        device loop runs on one rank and without a committee.  None: no filter, today's run."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
+        filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
         npt = pfactor is not None
         if npt and not nh:
@@ -617,7 +626,8 @@ class ActiveCalculator(Calculator):
         committee = bool(getattr(self, "model_dict", None))
 
         def on_device():
-            return self.md_on_device_ok() and not (committee and (npt or fx is not None))
+            return (self.md_on_device_ok() and not (committee and (npt or fx is not None))
+                    and not (flt is not None and (committee or self._dist()[1] > 1)))
         first_on_host = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -629,18 +639,20 @@ class ActiveCalculator(Calculator):
             atoms.calc = self
             atoms.get_forces()
             if not on_device():
-                loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro) if npt else
-                        nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold) if nh else
-                        langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold))
+                loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro, **filt) if npt else
+                        nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold, **filt) if nh else
+                        langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold, **filt))
                 for st, E, T, _, p, v, *rest in loop:
                     put(dict(positions=p, velocities=v, cell=rest[0] if npt else None), "velocities")
+                    if flt is not None:   # (the accumulators as this configuration found them: what a run that goes on from it takes)
+                        flt.f, flt.s = rest[-1]
                     yield st, E, T, bool(self.updated), _
                 return
         eng = self.engine
         kT = kB * temperature_K
         self._peer_fit(eng, N)
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
-                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold)
+                     seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold, **filt)
         # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
@@ -711,9 +723,14 @@ class ActiveCalculator(Calculator):
                 atoms.calc = self
                 self.results = {}
                 self.calculate(atoms)        # update_results + update + the log line, as inside an ASE loop
+                if flt is not None and self.deltas:   # (the jump of this update: FilterDeltas reads it at its next call)
+                    eng.md_filter_push(self.deltas["forces"], self.deltas["stress"])
+                    flt.pushes += 1
                 skip_gate = True
                 t_host = time.time() - t_host
         put(eng.md_state(results=True), "velocities")
+        if flt is not None:
+            flt.f, flt.s = eng.md_filter_state()
         if attached:
             self._md_attached_done(eng, attached)
 

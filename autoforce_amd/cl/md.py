@@ -149,6 +149,11 @@ def md(atoms, calc=None, dynamics="NPT", dt=None, tem=300.0, picos=100, trajecto
     moving_cell = dynamics.upper() == "NPT" and bool(bulk_modulus)
     tdamp_fs = float(tdamp) if dynamics.upper() == "NPT" else None
     out = open(trajectory, "a" if append else "w") if (trajectory and calc.rank == 0) else None
+    # ONE filter of model-update jumps for all temperatures, as the reference wraps its atoms in one FilterDeltas before the
+    # loop (cl/md.py:76-79): run_md reads the holder's accumulators at its start and fills them at its end (the moving-cell
+    # branch below still wraps the atoms itself, per temperature)
+    from ..workloads import FilterState
+    filt = FilterState(ml_filter) if ml_filter else None
     for T in temperatures:
         steps = int(picos * 1000 / dt) if picos > 0 else int(-picos)
         if moving_cell:
@@ -161,7 +166,7 @@ def md(atoms, calc=None, dynamics="NPT", dt=None, tem=300.0, picos=100, trajecto
             continue
         for step, energy, temperature, updated, wall in calc.run_md(atoms, steps, T, dt_fs=dt, friction=friction, rng=None,
                                                                     seed=int(rng.integers(1, 2 ** 62)), sync_every=loginterval or None,
-                                                                    tdamp_fs=tdamp_fs):
+                                                                    tdamp_fs=tdamp_fs, ml_filter=filt):
             if out is not None and loginterval and step % loginterval == 0:
                 # (the state lives on the device: run_md brings the positions back at the steps a trajectory wants them)
                 out.writelines(format_extxyz(Frame(numbers, atoms.positions, atoms.cell, atoms.pbc, energy, None, None)))

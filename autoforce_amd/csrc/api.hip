@@ -209,6 +209,14 @@ struct MdState {
     DevBuf<unsigned char> fixed;   // [N][3]
     std::vector<unsigned char> fixed_sorted;
     const unsigned char *fix() const { return n_fixed ? fixed.p : nullptr; }
+    // the filter of model-update jumps (sgpr_md_filter): accumulated force jumps in a ring beside X (sorted order, slot = evaluation
+    // index % ring), accumulated stress jumps of a moving-cell run in a ring of four (evaluation index & 3) — at constant cell
+    // nobody asks for a stress and filt_s_host is handed back as it came; the run's own permutation on the device for the pushes
+    bool filter = false;
+    double shrink = 0.0;
+    DevBuf<double> filt_f, filt_s, filt_in;   // [4][N][3], [4][6], [N][3] a push's caller-order upload
+    DevBuf<int> filt_perm;                    // [N] sorted -> caller
+    double filt_s_host[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // the frame record (sgpr_md_record, md_record.inc): every rec_every-th configuration of a call, copied out behind its
     // evaluation in caller atom order — rec_x always, rec_v / rec_p by the bits of rec_what.  rec_call_*: what the LAST
     // sgpr_md_run recorded (sgpr_md_frames serves that call: its first trajectory index, its settings, the frames that stand)
@@ -556,6 +564,12 @@ struct FinNext {
     // held components (sgpr_md_fix; finalize_next_kernel<4>, shard_next_kernel<4>): [N][3] sorted order, nonzero = the
     // integrator sees F = 0 there, draws no noise, keeps v = 0 and hands the coordinate on as it is (null: nothing is held)
     const unsigned char *fixed;
+    // the filter of model-update jumps (sgpr_md_filter; finalize_next_kernel<5>, <6>, <7>): [N][3] sorted order, the accumulated
+    // jumps of this configuration (read) and of the next (written: this one's times `shrink`); the integrator sees the force
+    // minus that product clamped to +-1 eV/A (null: no filter)
+    const double *filt_cur;
+    double *filt_next;
+    double shrink;
 };
 
 struct FinArgs {
@@ -1105,11 +1119,18 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 // md_npt_kernel left behind the previous evaluation (wave-uniform addresses, a column per lane, requested with everything
 // else); the atom is binned in the grid of the NEXT cell and tested against the binning kernel's affine rebuild rule.  Its own
 // instantiation: MODE 2 sits at its register limit and stays as it is.
+//   MODES 5, 6, 7 (FinNext::mode stays 2) are MODES 2, 4, 3 with the filter of model-update jumps (sgpr_md_filter: FinNext::filt_cur,
+// the accumulated jump of the component, requested with mass and sigma): a = filt_cur * shrink is stored to filt_next beside
+// x_next and the integrator sees F - min(max(a, -1), 1) — workloads.*(ml_filter=), the reference's FilterDeltas by evaluation
+// index.  The forces written to `packed` stay the model's.  Their own instantiations: runs without a filter launch what they did.
 template <int MODE>
 __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
 {
     const int tid = threadIdx.x, b = blockIdx.x, nA = gridDim.x - 13;
-    constexpr bool MD = MODE == 2 || MODE == 4;   // the constant-cell integrator (4: with held components)
+    constexpr bool MD = MODE == 2 || MODE == 4 || MODE == 5 || MODE == 6;   // the constant-cell integrator (4, 6: with held components)
+    constexpr bool CELL = MODE == 3 || MODE == 7;                           // the moving-cell integrator
+    constexpr bool HELD = MODE == 4 || MODE == 6;
+    constexpr bool FILT = MODE >= 5;                                        // 5, 6, 7: 2, 4, 3 with the filter
     const FinNext &x = f.nx;
     const int halt_w = MODE >= 2 ? *x.halt : 0x7fffffff;
     if (b >= nA) {
@@ -1123,7 +1144,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
                 const int s1 = x.step + 1;
                 if (x.force) atomicMax(&x.flags[s1 & 3], 1);
                 x.flags[(s1 + 2) & 3] = 0;
-                if (MODE != 3) fin_cell_guard(f, *f.flag, s1);   // (MODE 3 applies the affine rule itself)
+                if (!CELL) fin_cell_guard(f, *f.flag, s1);   // (the moving cell applies the affine rule itself)
             }
             if (MODE >= 2 && x.packed_prev) finalize_reduce_prev(f, b - nA - 11);
         } else
@@ -1142,7 +1163,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     const int c = f.perm[ia];
     const int slot_i = f.slot[ia];
     const int rebuilt = *f.flag;
-    const NlGrid g = MODE == 3 ? x.npt_next->grid : *f.grid;
+    const NlGrid g = CELL ? x.npt_next->grid : *f.grid;
     const int n_ld = f.nn[ia];
     // pair slots lane + 16 j
     double2 g0[4];
@@ -1157,7 +1178,7 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
     double fs = f.Fself[3 * (size_t)ia + l3];
     // the atom this row BINS: MODE 1: caller atom number i (sorted index ib = iperm[i]); MODE 2: sorted atom i itself
     const int ib = MODE == 1 ? x.iperm[ia] : ia;
-    const bool held = MODE == 4 ? x.fixed[3 * (size_t)ia + l3] != 0 : false;   // (a byte in the same round trip as mass and sigma)
+    const bool held = HELD ? x.fixed[3 * (size_t)ia + l3] != 0 : false;   // (a byte in the same round trip as mass and sigma)
     const int slot_b = MODE == 1 ? x.cslot[ia] : slot_i;
     double xc = 0.0, p0 = 0.0, vc = 0.0, ms = 1.0, sg = 0.0, nz = 0.0, xn = 0.0;
     if (MODE == 1) xn = x.pos_in[3 * (size_t)ia + l3];
@@ -1169,11 +1190,12 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         sg = x.sig[ia];
         nz = x.noise ? x.noise[3 * (size_t)ia + l3] : 0.0;   // (wave-uniform condition)
     }
+    const double af = FILT ? x.filt_cur[3 * (size_t)ia + l3] : 0.0;   // (the same round trip)
     double xpv = 0.0, zeta = 0.0;
     if (MD && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (wave-uniform condition)
     // MODE 3: q_n, q_(n-1), and column l3 of the matrices: h_n^-1, B - 1, (B + 1)^-1, h_n, h_(n+1), the two affine maps
     double qc = 0.0, qp = 0.0, c_hinv[3], c_bm1[3], c_bp1[3], c_h[3], c_hn[3], c_ak[3], c_ar[3], thr2_k = 0.0, thr2_r = 0.0;
-    if (MODE == 3) {
+    if (CELL) {
         const NptSlot *nc = x.npt_cur, *nn = x.npt_next;
         xc = x.x_cur[3 * (size_t)ia + l3];
         p0 = f.pos0[3 * (size_t)ia + l3];
@@ -1278,11 +1300,19 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
 #pragma clang fp contract(off)
         return (fin_quad_lane<0>(v) * c[0] + fin_quad_lane<1>(v) * c[1]) + fin_quad_lane<2>(v) * c[2];
     };
-    if (MODE == 3) {
+    // the force the integrator sees: less the accumulated jumps of this configuration, shrunk once and clamped (in this order,
+    // no contraction: FilterDeltas.get_forces); the successor of the accumulator goes out with x_next
+    double Fi = Fv, an = 0.0;
+    if (FILT) {
+#pragma clang fp contract(off)
+        an = af * x.shrink;
+        Fi = Fv - fmin(fmax(an, -1.0), 1.0);
+    }
+    if (CELL) {
         // workloads.npt_moving_cell's operations in its order (md_npt.inc has the scheme): no contraction, true divisions
 #pragma clang fp contract(off)
         const double dt = 2.0 * x.hdt;
-        const double a = __ddiv_rn((dt * dt) * Fv, ms);
+        const double a = __ddiv_rn((dt * dt) * Fi, ms);
         const double num = ((2.0 * qc) + row_mul(qp, c_bm1)) + row_mul(a, c_hinv);
         const double qn = row_mul(num, c_bp1);
         const double vcen = __ddiv_rn(row_mul(qn - qp, c_h), 2.0 * dt);
@@ -1294,20 +1324,23 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
             x.q_next[3 * (size_t)i + lane] = qn;
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_now[3 * (size_t)i + lane] = vnow;
+            if (FILT) x.filt_next[3 * (size_t)i + lane] = an;
         }
     } else if (MD && x.nh) {
         if (lane < 3) {
-            const double vnow = md_nh_advance(x, held, Fv, ms, xc, vc, xpv, zeta, xn);
+            const double vnow = md_nh_advance(x, held, Fi, ms, xc, vc, xpv, zeta, xn);
             ke = ms * (vnow * vnow);
             kp = ke;
             x.x_next[3 * (size_t)i + lane] = xn;
             x.v_now[3 * (size_t)i + lane] = vnow;
+            if (FILT) x.filt_next[3 * (size_t)i + lane] = an;
         }
     } else if (MD && lane < 3) {
         double v3;
-        xn = md_baoab_advance(x, held, Fv, ms, sg, nz, xc, vc, c, lane, v3, ke, kp);
+        xn = md_baoab_advance(x, held, Fi, ms, sg, nz, xc, vc, c, lane, v3, ke, kp);
         x.x_next[3 * (size_t)i + lane] = xn;
         x.v_next[3 * (size_t)i + lane] = v3;
+        if (FILT) x.filt_next[3 * (size_t)i + lane] = an;
     }
     if (MODE >= 2) {
         fin_store_ke(ke, kp, lane == 0, x.ke_cur, i);
@@ -1319,10 +1352,10 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         x.pos[3 * (size_t)ib + lane] = xn;
         if (rebuilt) f.pos0[3 * (size_t)ib + lane] = xc;
     }
-    // MODE 3: the build-time position mapped into the next cell (A = h0^-1 h, neighbor.hip), h0 = this step's cell if it rebuilt
-    if (MODE == 3 && rebuilt) { c_ak[0] = c_ar[0]; c_ak[1] = c_ar[1]; c_ak[2] = c_ar[2]; }
-    const double dd = MODE == 3 ? xn - row_mul(p0, c_ak) : xn - p0;
-    const double thr2 = MODE == 3 ? (rebuilt ? thr2_r : thr2_k) : x.thr2;
+    // moving cell: the build-time position mapped into the next cell (A = h0^-1 h, neighbor.hip), h0 = this step's cell if it rebuilt
+    if (CELL && rebuilt) { c_ak[0] = c_ar[0]; c_ak[1] = c_ar[1]; c_ak[2] = c_ar[2]; }
+    const double dd = CELL ? xn - row_mul(p0, c_ak) : xn - p0;
+    const double thr2 = CELL ? (rebuilt ? thr2_r : thr2_k) : x.thr2;
     const double dx = fin_quad_lane<0>(dd), dy = fin_quad_lane<1>(dd), dz = fin_quad_lane<2>(dd);
     const double d2 = dx * dx + dy * dy + dz * dz;
     if (lane == 0) {
@@ -2475,7 +2508,11 @@ static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool bet
             x.csq_rw = h->d_csq.p;
             hipLaunchKernelGGL(finalize_scatter_next_kernel, dim3((std::max(N, 1) + 255) / 256 + 11), dim3(256), 0, st, f);
         } else if (nx->mode == 1) hipLaunchKernelGGL(finalize_next_kernel<1>, grid, dim3(256), 0, st, f);
-        else if (nx->md.npt_cur) hipLaunchKernelGGL(finalize_next_kernel<3>, grid, dim3(256), 0, st, f);
+        else if (nx->md.filt_cur) {   // (sgpr_md_filter: the filtered forms; a run without a filter launches what it launched before)
+            if (nx->md.npt_cur) hipLaunchKernelGGL(finalize_next_kernel<7>, grid, dim3(256), 0, st, f);
+            else if (nx->md.fixed) hipLaunchKernelGGL(finalize_next_kernel<6>, grid, dim3(256), 0, st, f);
+            else hipLaunchKernelGGL(finalize_next_kernel<5>, grid, dim3(256), 0, st, f);
+        } else if (nx->md.npt_cur) hipLaunchKernelGGL(finalize_next_kernel<3>, grid, dim3(256), 0, st, f);
         else if (nx->md.fixed) hipLaunchKernelGGL(finalize_next_kernel<4>, grid, dim3(256), 0, st, f);
         else hipLaunchKernelGGL(finalize_next_kernel<2>, grid, dim3(256), 0, st, f);
         return;
@@ -2647,6 +2684,8 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     const bool shard_next = can_next && !gather && (px || (nx->mode == 2 && h->world == 1)) && !no_exchange;
     const bool fuse = can_next && !shard_next &&
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
+    if (nx && nx->mode == 2 && nx->md.filt_cur && !(fuse && gather))
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
     const bool xp = !gather && (px || shard_next);
     const size_t xlen = peer_xlen(N, h->world);
     if (xp && h->d_xpacked.n < xlen + 1 && h->d_xpacked.alloc(xlen + 1)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (exchange buffer)");

@@ -1,5 +1,6 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*: MD, moving-cell NPT, FIRE relaxation), included by
-// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc, md_relax.inc and md_record.inc.
+// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc, md_relax.inc and md_record.inc (the one
+// small kernel of sgpr_md_filter_push stands beside it, at the end).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
 // from util/aseutil.py:11-20) and crosses into the calculator once per step.  Here the state (positions, velocities)
@@ -68,6 +69,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
     m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
     m.bcm.clear(); m.bcm_info.clear();
+    m.filter = false; m.shrink = 0.0;
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -232,6 +234,15 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
     HIPCHK(hipMemcpy(x.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(F.data(), m.P.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));   // (packed forces: caller order)
+    if (m.filter) {   // the forces the integrator sees at configuration 0 (finalize_next_kernel<7>'s operations; slot 0 stays as it is)
+        std::vector<double> a0((size_t)3 * N);
+        HIPCHK(hipMemcpy(a0.data(), m.filt_f.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+        for (int i = 0; i < N; i++)
+            for (int k = 0; k < 3; k++) {
+                const double an = a0[3 * (size_t)i + k] * m.shrink;
+                F[3 * (size_t)m.perm[i] + k] = F[3 * (size_t)m.perm[i] + k] - std::min(std::max(an, -1.0), 1.0);
+            }
+    }
     const double dt = m.np.dt;
     auto row_mul = [](const double *r, const double *mat, double *o) {
 #pragma clang fp contract(off)
@@ -270,7 +281,7 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
     // the grids of h_0 and h_1 and the rebuild rule of evaluation 0 (which rebuilds: the first of its call)
     hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p, (const double *)nullptr,
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)h->d_cell0.p, -1,
-                       (const int *)m.halt.p, -1, (double *)nullptr, (double *)nullptr);
+                       (const int *)m.halt.p, -1, (double *)nullptr, (double *)nullptr, (const double *)nullptr, (double *)nullptr, 0.0);
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     m.npt_started = true;
@@ -337,6 +348,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
     if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     const double *fp = fire ? fire : RLX_ASE;
@@ -580,6 +592,7 @@ static void md_fill_integrator(const MdState &m, int j, const double *noise_dev,
     x.seed = noise_dev ? 0ull : m.seed; x.t_index = m.t + j;
     x.ke_cur = m.KE.p + (size_t)2 * m.N * sl;
     x.halt = m.halt.p;
+    if (m.filter) { x.filt_cur = m.filt_f.p + N3 * sl; x.filt_next = m.filt_f.p + N3 * sn; x.shrink = m.shrink; }
 }
 
 // The close of a call: the scalar rows of the evaluations that stand to the caller — columns 14 and 15 are zeta and its time
@@ -707,6 +720,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_committee: call sgpr_md_begin first");
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
     if (K == 0 || !members) { m.bcm.clear(); m.bcm_info.clear(); return SGPR_OK; }
+    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
     if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
     if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
     if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.n_fixed);
@@ -941,7 +955,9 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
             hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p,
                                (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + (size_t)3 * N * sl), (const double *)m.mass.p,
                                (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.t + j) & 0x3fffffff), (const int *)m.halt.p,
-                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j);
+                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j,
+                               m.filter ? (const double *)(m.filt_s.p + 6 * ((m.t + j) & 3)) : (const double *)nullptr,
+                               m.filter ? m.filt_s.p + 6 * ((m.t + j + 1) & 3) : (double *)nullptr, m.shrink);
         else if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
             hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
                                m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
@@ -1050,6 +1066,12 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     if (kick) {
         F.resize((size_t)3 * N);   // (packed forces are in caller order)
         HIPCHK(hipMemcpy(F.data(), m.P.p + (size_t)sgpr_packed_len(N) * sl, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+        if (m.filter) {   // (the kick the filtered integrator gives: finalize_next_kernel<5>'s operations)
+#pragma clang fp contract(off)
+            std::vector<double> a((size_t)3 * N);
+            if (const int rc_ = md_fetch_rows(m, m.filt_f.p + (size_t)3 * N * sl, a.data())) return rc_;
+            for (size_t e = 0; e < (size_t)3 * N; e++) F[e] = F[e] - std::min(std::max(a[e] * m.shrink, -1.0), 1.0);
+        }
     }
     for (int i = 0; i < N; i++) {
         const size_t c = m.perm[i];
@@ -1135,6 +1157,106 @@ extern "C" int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, doubl
     if (d.alloc((size_t)count * 3 * m.N, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_deviates: device allocation failed");
     hipLaunchKernelGGL(md_deviates_kernel, dim3(1024), dim3(256), 0, h->stream, m.N, count, m.seed, (long long)t_first, d.p);
     HIPCHK(hipMemcpy(out, d.p, sizeof(double) * (size_t)count * 3 * m.N, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// The filter of model-update jumps for the run begun by sgpr_md_begin: the reference's default MD wraps its atoms in FilterDeltas
+// (cl/md.py:76-79, ml_filter = 0.8; calculator/active.py:47-76), which keeps a running sum of the jumps `deltas` an on-the-fly
+// update puts into forces and stress, shrinks it at every call and subtracts it (forces: clamped to 1 eV/A) from what the
+// integrator sees.  Here, by evaluation index, once per configuration n:
+//     A_f <- (A_f + dF_n) shrink,   F_seen = F_model - min(max(A_f, -1), 1)      (then a held component sees 0 as before)
+//     A_s <- (A_s + dS_n) shrink,   stress_seen = stress_model - A_s              (moving cell only: nobody else asks for a stress)
+// inside the step's last kernel (finalize_next_kernel<5>, <6>, <7>) and md_npt_kernel; dF_n, dS_n: what sgpr_md_filter_push added
+// to the accumulators of configuration n before its evaluation.  The accumulators live in rings indexed like X and V (slot n is
+// read, slot n + 1 written): the evaluation a halt discards leaves those of its configuration as they were.  What the run
+// REPORTS (packed, sgpr_md_state, the frame record, the scalar rows) stays the model's own.
+// After sgpr_md_begin (and sgpr_md_fix / _thermostat / _barostat), before the first sgpr_md_run.  0 < shrink < 1; f0[3N] caller
+// atom order and s0[6] Voigt: the accumulators of configuration 0 (NULL: zeros).  A relaxation, a committee, several ranks:
+// SGPR_E_UNSUPPORTED; sgpr_md_relax and sgpr_md_committee refuse a run that has a filter.
+extern "C" int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, const double *s0)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_filter: call sgpr_md_begin first");
+    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_filter: the run has started");
+    if (!(shrink > 0.0 && shrink < 1.0)) return fail(SGPR_E_INVALID, "sgpr_md_filter: 0 < shrink < 1");
+    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a relaxation (sgpr_md_relax), which applies no filter");
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.world);
+    HIPCHK(hipSetDevice(h->device));
+    const int N = m.N;
+    const size_t N3 = (size_t)3 * N;
+    if (m.filt_f.alloc(4 * N3) || m.filt_s.alloc(32) || m.filt_in.alloc(N3) || m.filt_perm.alloc(N))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_filter: device allocation failed");
+    HIPCHK(hipMemset(m.filt_f.p, 0, sizeof(double) * 4 * N3));
+    HIPCHK(hipMemset(m.filt_s.p, 0, sizeof(double) * 32));
+    HIPCHK(hipMemcpy(m.filt_perm.p, m.perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    if (f0) {
+        std::vector<double> fs(N3);
+        for (int i = 0; i < N; i++)
+            for (int k = 0; k < 3; k++) fs[3 * (size_t)i + k] = f0[3 * (size_t)m.perm[i] + k];
+        HIPCHK(hipMemcpy(m.filt_f.p, fs.data(), sizeof(double) * N3, hipMemcpyHostToDevice));
+    }
+    for (int k = 0; k < 6; k++) m.filt_s_host[k] = s0 ? s0[k] : 0.0;
+    HIPCHK(hipMemcpy(m.filt_s.p, m.filt_s_host, sizeof(double) * 6, hipMemcpyHostToDevice));
+    m.filter = true; m.shrink = shrink;
+    return SGPR_OK;
+}
+
+// caller order -> the run's sorted order, added into the accumulators of the current configuration (one thread per component;
+// the six stress jumps by thread 0)
+struct MdSix { double v[6]; };
+__global__ void md_filter_push_kernel(int N, const int *perm, const double *dF, double *acc, MdSix dS, double *acc_s)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < (size_t)3 * N) {
+        const size_t i = e / 3, k = e - 3 * i;
+        acc[e] = acc[e] + dF[3 * (size_t)perm[i] + k];
+    }
+    if (e == 0 && acc_s)
+        for (int q = 0; q < 6; q++) acc_s[q] = acc_s[q] + dS.v[q];
+}
+
+// The jump of a model update, between two sgpr_md_run calls (after the halt's calculate(), whose `deltas` these are): dF[N][3]
+// caller atom order (NULL: none), dS[6] Voigt (NULL: none; ignored at constant cell), added into the accumulators of the current
+// configuration — the next evaluation shrinks the sum and applies it.
+extern "C" int sgpr_md_filter_push(sgpr_model *h, const double *dF, const double *dS)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter_push: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.filter) return fail(SGPR_E_INVALID, "sgpr_md_filter_push: call sgpr_md_begin and sgpr_md_filter first");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    HIPCHK(hipStreamSynchronize(st));
+    const int N = m.N;
+    const size_t N3 = (size_t)3 * N;
+    MdSix six = {};
+    const bool ws = m.npt && dS;
+    if (ws) for (int k = 0; k < 6; k++) six.v[k] = dS[k];
+    if (!dF && !ws) return SGPR_OK;
+    if (dF) HIPCHK(hipMemcpy(m.filt_in.p, dF, sizeof(double) * N3, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(md_filter_push_kernel, dim3(dF ? (unsigned)((N3 + 255) / 256) : 1u), dim3(256), 0, st, dF ? N : 0, (const int *)m.filt_perm.p,
+                       (const double *)m.filt_in.p, m.filt_f.p + N3 * (size_t)(m.t % m.ring), six, ws ? m.filt_s.p + 6 * (m.t & 3) : (double *)nullptr);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return SGPR_OK;
+}
+
+// The accumulators of the current configuration — what its evaluation will shrink and apply; what sgpr_md_filter takes to go on
+// from here in another run: f[N][3] caller atom order, s[6] (either NULL: not wanted).
+extern "C" int sgpr_md_filter_state(sgpr_model *h, double *f, double *s)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter_state: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.filter) return fail(SGPR_E_INVALID, "sgpr_md_filter_state: call sgpr_md_begin and sgpr_md_filter first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (f)
+        if (const int rc_ = md_fetch_rows(m, m.filt_f.p + (size_t)3 * m.N * (size_t)(m.t % m.ring), f)) return rc_;
+    if (s) {
+        if (m.npt) HIPCHK(hipMemcpy(s, m.filt_s.p + 6 * (m.t & 3), sizeof(double) * 6, hipMemcpyDeviceToHost));
+        else memcpy(s, m.filt_s_host, sizeof(double) * 6);
+    }
     return SGPR_OK;
 }
 

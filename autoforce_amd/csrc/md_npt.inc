@@ -44,15 +44,20 @@ __host__ __device__ inline void npt_inv_upper(const double *h, double *o)
     o[3] = 0.0; o[6] = 0.0; o[7] = 0.0;
 }
 
-// sigma = the stress of the packed virial in the cell h (sgpr_stress_from_virial's operations) minus the ideal-gas part S / V
-__host__ __device__ inline void npt_sigma(const double *vir, const double *c, const double *S, double *sig)
+// sigma = the stress of the packed virial in the cell h (sgpr_stress_from_virial's operations) minus the ideal-gas part S / V;
+// acc (sgpr_md_filter; null: none): the accumulated stress jumps, subtracted from the model's stress first (FilterDeltas.get_stress)
+__host__ __device__ inline void npt_sigma(const double *vir, const double *c, const double *S, double *sig, const double *acc = nullptr)
 {
 #pragma clang fp contract(off)
     double vol = fabs(c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]));
     if (!(vol > 0.0)) vol = -2.0;
     const int voigt[6] = {0, 4, 8, 5, 2, 1};
     const double vh = fabs((c[0] * c[4]) * c[8]);
-    for (int k = 0; k < 6; k++) sig[k] = NPT_DIV(vir[voigt[k]], vol) - NPT_DIV(S[k], vh);
+    if (!acc) {
+        for (int k = 0; k < 6; k++) sig[k] = NPT_DIV(vir[voigt[k]], vol) - NPT_DIV(S[k], vh);
+        return;
+    }
+    for (int k = 0; k < 6; k++) sig[k] = (NPT_DIV(vir[voigt[k]], vol) - acc[k]) - NPT_DIV(S[k], vh);
 }
 
 // npt.NPT._deta: -fdt pfact det(h) (sigma - external) as a strain-rate increment
@@ -114,9 +119,12 @@ __device__ inline void npt_affine_rule(const double *h0inv, const double *h, con
 // workloads._device_order_sum) — m v_a v_b for the six Voigt components of the ideal-gas stress and the kinetic energy's
 // m v^2 as the last kernel left it per atom —, then on one lane the recurrences above and what the last kernel of evaluation
 // n + 1 needs.  Exits on the halt word like md_nh_kernel.
+//   fs_cur / fs_next (sgpr_md_filter; null: no filter, today's arithmetic): the six accumulated stress jumps of configuration n
+// and, out, of n + 1 — this one's times `shrink`, which is also what the stress of configuration n is reduced by.
 __global__ __launch_bounds__(256) void md_npt_kernel(int N, NptParams p, NptSlot *ring, double *zeta, const double *ke, const double *vel,
                                                      const double *mass, const double *packed, const double *cell0, int n,
-                                                     const int *halt, int step, double *scal_row, double *cell_row)
+                                                     const int *halt, int step, double *scal_row, double *cell_row,
+                                                     const double *fs_cur, double *fs_next, double shrink)
 {
     if (*halt < step) return;
     __shared__ double wsum[7][4];
@@ -146,7 +154,12 @@ __global__ __launch_bounds__(256) void md_npt_kernel(int N, NptParams p, NptSlot
         for (int q = 0; q < 6; q++) S[q] = (wsum[q][0] + wsum[q][1]) + (wsum[q][2] + wsum[q][3]);
         const double KE = 0.5 * ((wsum[6][0] + wsum[6][1]) + (wsum[6][2] + wsum[6][3]));
         for (int k = 0; k < 9; k++) { hc[k] = cur.h[k]; h1[k] = nxt.h[k]; }
-        npt_sigma(packed + 4 * (size_t)N + 1, hc, S, sig);
+        if (fs_cur) {
+            double acc[6];
+            for (int q = 0; q < 6; q++) { acc[q] = fs_cur[q] * shrink; fs_next[q] = acc[q]; }
+            npt_sigma(packed + 4 * (size_t)N + 1, hc, S, sig, acc);
+        } else
+            npt_sigma(packed + 4 * (size_t)N + 1, hc, S, sig);
         if (n == 0) {   // NPT.initialize(): eta_(-1) = eta_0 - half the increment, zeta_(-1) likewise
             npt_deta(p.dt, p, hc, sig, d);
             for (int k = 0; k < 9; k++) eprev[k] = cur.eta[k] - d[k];

@@ -591,7 +591,7 @@ class SGPRModel:
     MD_SCALARS = 16  # per evaluation: E, virial[9], overflow word, largest covloss, sum m v^2, 3 spare
 
     def md_begin(self, numbers, positions, cell, pbc, masses, velocities=None, dt=1.0, friction=0.0, kT=0.0, seed=0, ttime=None,
-                 pfactor=None, externalstress=0.0, mask=None, iso=False, fixed=None):
+                 pfactor=None, externalstress=0.0, mask=None, iso=False, fixed=None, ml_filter=None, filter_init=None):
         """State of an MD run into device memory (cl/md.py:117-128 drives ase.md.langevin around calculate();
         here the integrator is part of the step's last kernel).  dt, friction and kT in the caller's units
         (workloads.FS / ase_shim.kB for fs / K).
@@ -600,7 +600,12 @@ class SGPRModel:
         forces md_state reports stay the model's —, its velocity is exactly 0 from here on (the caller's value is dropped), it
         draws no noise and keeps the coordinate it was uploaded with, bit for bit.  Nose-Hoover then works on the
         g = 3N - n_fixed remaining degrees of freedom: tfact = 2 / (g kT ttime^2), K0 = g kT / 2 (the project's own definition:
-        ase.md.npt.NPT takes no constraints), and temperatures are sum m v^2 / (g kB) (md_dof()).  Not with a barostat."""
+        ase.md.npt.NPT takes no constraints), and temperatures are sum m v^2 / (g kB) (md_dof()).  Not with a barostat.
+          ml_filter: the shrink factor (0 < s < 1) of the filter of model-update jumps (sgpr_md_filter; the reference's
+        FilterDeltas, cl/md.py:76-79): per configuration A <- (A + pushed jumps) s, and the integrator sees
+        F - clip(A_f, -1, 1) and, with a barostat, stress - A_s; what md_state and the rows report stays the model's.
+        filter_init: (f [N, 3], s [6]) the accumulators of configuration 0 (either None: zeros).  md_filter_push adds the jumps
+        of an update between two md_run calls, md_filter_state returns the accumulators.  None: the run without a filter."""
         from .workloads import fixed_mask
         numbers = i32(numbers)
         N = len(numbers)
@@ -637,7 +642,29 @@ class SGPRModel:
             mk = f64((np.outer(mk, mk) if mk.shape == (3,) else mk.reshape(3, 3)).astype(float))
             check(_lib.load().sgpr_md_barostat(self._h, float(pfactor), ptr(f64(ext)), ptr(mk), 0.0 if iso else 1.0))
             self._md["npt"] = True
+        if ml_filter is not None:
+            f0, s0 = (None, None) if filter_init is None else filter_init
+            f0 = None if f0 is None else f64(np.asarray(f0, float)).reshape(N, 3)
+            s0 = None if s0 is None else f64(np.asarray(s0, float)).reshape(6)
+            check(_lib.load().sgpr_md_filter(self._h, float(ml_filter), ptr(f0), ptr(s0)))
+            self._md["shrink"] = float(ml_filter)
         self._md["t"] = 0
+
+    def md_filter_push(self, dforces, dstress=None):
+        """The jump of a model update — calculate()'s `deltas` after a halt — into the filter's accumulators of the current
+        configuration (sgpr_md_filter_push), between two md_run calls: dforces [N, 3] (or None), dstress [6] (or None; ignored at
+        constant cell).  The repeated evaluation shrinks the sum and applies it."""
+        N = self._md["N"]
+        dF = None if dforces is None else f64(np.asarray(dforces, float)).reshape(N, 3)
+        dS = None if dstress is None else f64(np.asarray(dstress, float)).reshape(6)
+        check(_lib.load().sgpr_md_filter_push(self._h, ptr(dF), ptr(dS)))
+
+    def md_filter_state(self):
+        """(f [N, 3], s [6]): the filter's accumulators of the current configuration — what its evaluation will shrink and
+        apply, and what md_begin(filter_init=) takes to go on from here (sgpr_md_filter_state)."""
+        f, s_ = np.empty((self._md["N"], 3)), np.empty(6)
+        check(_lib.load().sgpr_md_filter_state(self._h, ptr(f), ptr(s_)))
+        return f, s_
 
     def _md_fix(self, fx):
         """The held components of the run just begun (sgpr_md_fix: before the thermostat / the relaxation is set)."""
@@ -749,7 +776,10 @@ class SGPRModel:
                 check(_lib.load().sgpr_md_velocities(self._h, ptr(vn)))
                 out["velocities"] = vn
             else:
-                out["velocities"] = v + self._md["hdt"] * F / self._md["masses"][:, None] if pend.value else v.copy()
+                Fk = F
+                if pend.value and self._md.get("shrink") is not None and which == 0:   # (the kick the filtered integrator gives)
+                    Fk = F - np.clip(self.md_filter_state()[0] * self._md["shrink"], -1.0, 1.0)
+                out["velocities"] = v + self._md["hdt"] * Fk / self._md["masses"][:, None] if pend.value else v.copy()
                 if self._md.get("fixed") is not None:   # (a held component: the integrator's F = 0, v = 0)
                     out["velocities"] = np.where(self._md["fixed"], 0.0, out["velocities"])
         return out
@@ -815,7 +845,8 @@ class SGPRModel:
                 cell = self._md["cell"] if cells is None else f64(cells[r])
                 check(_lib.load().sgpr_stress_from_virial(ptr(vir[r]), ptr(cell), ptr(stress[r])))
             out["stress"] = stress
-            if closed and want_v and not self._md.get("relax") and not self._md.get("nh"):
+            # (a filtered run, md_begin(ml_filter=): the kick is the filtered force's and the record holds no accumulators — left out)
+            if closed and want_v and not self._md.get("relax") and not self._md.get("nh") and self._md.get("shrink") is None:
                 # v + hdt * F / m, operation by operation as md_state spells it (every configuration but the start of the
                 # trajectory has a half kick pending), in one array
                 vel = np.multiply(self._md["hdt"], out["forces"])

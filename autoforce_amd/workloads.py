@@ -157,7 +157,46 @@ def fixed_mask(fixed, N):
     return m if m.any() else None
 
 
-def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None, rng=None, fixed=None):
+class FilterState:
+    """What ActiveCalculator.run_md(ml_filter=) reads at its start and fills at its end: the shrink factor and the accumulators
+    (None: zeros) as the run's last configuration found them — the next run_md handed the same holder evaluates that
+    configuration again and goes on.  pushes: how many update jumps the device loops were handed."""
+
+    def __init__(self, shrink, f=None, s=None):
+        self.shrink, self.f, self.s, self.pushes = float(shrink), f, s, 0
+
+
+class DeltaFilter:
+    """The reference's FilterDeltas (calculator/active.py:47-76; `ml_filter` of cl/md.py:76-79) written by evaluation index, as
+    the device loop applies it (sgpr_md_filter) — once per configuration n, with `deltas` what the calculator published there:
+        A_f <- (A_f + deltas["forces"]) shrink,  F_seen = F - clip(A_f, -1, 1);   A_s <- (A_s + deltas["stress"]) shrink,  stress - A_s
+    f, s: the accumulators; `before`: (f, s) as the configuration evaluated last found them — what filter_init= takes to
+    evaluate that configuration again (SGPRModel.md_filter_state returns the same), so that a run cut there goes on bit for bit."""
+
+    def __init__(self, shrink, init=None, N=None):
+        if not 0.0 < float(shrink) < 1.0:
+            raise ValueError("ml_filter: a shrink factor with 0 < shrink < 1")
+        f0, s0 = (None, None) if init is None else init
+        self.shrink = float(shrink)
+        self.f = np.zeros((N, 3)) if f0 is None else np.array(f0, float)
+        self.s = np.zeros(6) if s0 is None else np.array(s0, float)
+        self.before = (self.f, self.s)
+
+    def forces(self, F, deltas):
+        self.before = (self.f, self.before[1])
+        f = self.f + deltas["forces"] if deltas else self.f
+        self.f = f * self.shrink
+        return F - np.clip(self.f, -1.0, 1.0)
+
+    def stress(self, S, deltas):
+        self.before = (self.before[0], self.s)
+        a = self.s + deltas["stress"] if deltas else self.s
+        self.s = a * self.shrink
+        return S - self.s
+
+
+def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None, rng=None, fixed=None,
+                 ml_filter=None, filter_init=None):
     """BAOAB Langevin dynamics in numpy around any calculator with the ASE surface; parameters as the reference's
     driver (cl/md.py:31,70-74: dt = 1 fs, friction 1e-3 per ASE time unit, T = 600 K; Maxwell-Boltzmann start as
     util/aseutil.py:11-20, or the velocities handed over).  Generator: yields (step, energy, temperature, wall seconds,
@@ -167,7 +206,11 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
     dropped), the deviate of a held component is drawn — one rng.normal(size=(N, 3)) per step as ever, so the free components
     consume what they consume without a mask — and not used, and the next coordinate is the current one, selected.  The
     temperature is over the g = 3N - n_fixed remaining degrees of freedom (atoms.get_temperature() under constraints).  None
-    or nothing held: today's loop, bit for bit."""
+    or nothing held: today's loop, bit for bit.
+      ml_filter: the shrink factor of the filter of model-update jumps (DeltaFilter: calc.deltas is read after every evaluation;
+    the device loop's sgpr_md_filter), filter_init: (f, s) its accumulators at the first configuration.  The integrator then
+    sees F - clip(A_f, -1, 1) (a held component 0 as before); energies and the calculator's results stay raw.  Every yield
+    gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit."""
     import time
     from .ase_shim import Atoms, constraints_from_mask, kB
     rng = np.random.default_rng(seed) if rng is None else rng
@@ -187,20 +230,25 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
     c1 = np.exp(-friction * dt)
     c2 = np.sqrt(1 - c1 * c1)
     pos = np.array(pos, float)
+    flt = None if ml_filter is None else DeltaFilter(ml_filter, filter_init, N)
+    tail = (lambda: ()) if flt is None else (lambda: (flt.before,))
 
     def forces(p, v):
         # (the atoms carry the constraints, as the Atoms of an ASE loop around the calculator do: a calculator that learns takes
         # its copies — and its teacher's labels — from them; the forces taken here are the calculator's own)
         at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0], constraint=cons)
         at.calc = calc
-        return at.get_forces(apply_constraint=False), at.get_potential_energy()
+        F = at.get_forces(apply_constraint=False)
+        if flt is not None:   # (once per configuration)
+            F = flt.forces(F, getattr(calc, "deltas", None))
+        return F, at.get_potential_energy()
 
     def seen(F):   # the forces the integrator sees
         return F if fx is None else np.where(fx, 0.0, F)
 
     t0 = time.time()
     F, E = forces(pos, vel)
-    yield 0, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel
+    yield (0, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel) + tail()
     for step in range(1, steps + 1):
         t0 = time.time()
         held = pos
@@ -216,7 +264,7 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
             vel = np.where(fx, 0.0, vel)
         F, E = forces(pos, vel)
         vel += 0.5 * dt * seen(F) / mass
-        yield step, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel
+        yield (step, E, float((mass * vel ** 2).sum() / (dof * kB)), time.time() - t0, pos, vel) + tail()
 
 
 def _device_order_sum(x):
@@ -234,7 +282,7 @@ def _device_order_sum(x):
 
 
 def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, vel=None, seed=1, species=None,
-                    fixed=None):
+                    fixed=None, ml_filter=None, filter_init=None):
     """Nose-Hoover NVT in numpy around any calculator with the ASE surface: the reference's DEFAULT dynamics —
     md(dynamics="NPT", bulk_modulus=None) = ase.md.npt.NPT(pfactor=None, ttime=tdamp fs), cl/md.py:17, :131-166 — restated
     from ASE's published algorithm (Melchionna, Ciccotti, Holian 1993; ASE is absent here):
@@ -250,7 +298,9 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     K0 = g kT / 2 (no centre-of-mass degree removed: momentum is not conserved beside a held atom), temperature
     sum m v^2 / (g kB); conserved: E + KE + zeta^2 / tfact + 2 K0 int zeta dt, today's expression when nothing is held.  This
     is the project's own definition — ase.md.npt.NPT takes no constraints at all.  None or nothing held: today's loop, bit for
-    bit."""
+    bit.
+      ml_filter, filter_init: the filter of model-update jumps, as in langevin_nvt (the filtered force, then the mask); every
+    yield gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit."""
     import time
     from .ase_shim import Atoms, constraints_from_mask, kB
     N = len(numbers)
@@ -277,6 +327,7 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     zeta, zint = {0: 0.0}, {0: 0.0}
     table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
     order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    flt = None if ml_filter is None else DeltaFilter(ml_filter, filter_init, N)
 
     def forces(p, v):
         # (the atoms carry the constraints, as the Atoms of an ASE loop around the calculator do: a calculator that learns takes
@@ -288,6 +339,8 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     for n in range(steps + 1):
         t0 = time.time()
         F, E = forces(x, v0 if n == 0 else v)   # (the velocities the integrator holds when it asks for forces: v_(n-1))
+        if flt is not None:   # (once per configuration)
+            F = flt.forces(F, getattr(calc, "deltas", None))
         if fx is not None:
             F = np.where(fx, 0.0, F)
         a = ((dt * dt) * F) / mass
@@ -306,7 +359,8 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         zprev = -(c1 * d) if n == 0 else zeta[n - 1]
         zeta[n + 1] = zprev + c2 * d
         zint[n + 1] = zint[n] + dt * zeta[n + 1]
-        yield n, E, float(2.0 * KE / ((3 * N if fx is None else dof) * kB)), time.time() - t0, x, v, zeta[n], zint[n]
+        yield (n, E, float(2.0 * KE / ((3 * N if fx is None else dof) * kB)), time.time() - t0, x, v, zeta[n], zint[n]) + (
+            () if flt is None else (flt.before,))
         xp, x = x, xn
 
 
@@ -363,7 +417,7 @@ def _npt_q_next(dt, F, mass, q, q_prev, hinv, bm1, bp1inv):
 
 
 def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, pfactor=None,
-                    externalstress=0.0, mask=None, iso=False, vel=None, species=None):
+                    externalstress=0.0, mask=None, iso=False, vel=None, species=None, ml_filter=None, filter_init=None):
     """Nose-Hoover / Parrinello-Rahman dynamics with a moving cell in numpy around any calculator with the ASE surface: npt.NPT
     (ase.md.npt.NPT restated; what cl/md.py:131-166 runs when a bulk modulus is given) written by evaluation index, in the
     operations and the order of the device loop (sgpr_md_barostat: md_npt_kernel and the moving-cell form of the step's last
@@ -382,7 +436,12 @@ def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
           :259-261, with _deta, :212-221), q_(n+1) (_q_future, :223-228) and the centred velocity (:272), the positions of
           configuration n + 1 in ITS cell (_set_box_and_positions, :203-209).
     Yields (step, energy, temperature, wall seconds, positions, centred velocities, cell, eta, zeta, integral of zeta) per
-    evaluated configuration (the velocities of configuration 0 are the ones handed over)."""
+    evaluated configuration (the velocities of configuration 0 are the ones handed over).
+      ml_filter, filter_init: the filter of model-update jumps (DeltaFilter; sgpr_md_filter on the device): once per configuration
+    the forces are reduced by the clamped force accumulator and, with a barostat, the stress by the stress accumulator — what
+    npt.NPT(npt.FilterDeltas(atoms, shrink)) does, which calls the getters more than once at configuration 0 only (the same
+    whenever the accumulators are zero there).  Every yield gains a last entry, (f, s) as this configuration found the
+    accumulators.  None: today's loop, bit for bit."""
     import time
     from .ase_shim import Atoms, kB
     from .npt import zero_mean_momentum
@@ -415,10 +474,18 @@ def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
     zero3 = [[0.0] * 3 for _ in range(3)]
 
+    flt = None if ml_filter is None else DeltaFilter(ml_filter, filter_init, N)
+
     def evaluate(x, h, v):
         at = Atoms(numbers, x, np.array(h), pbc, velocities=v, masses=mass[:, 0])
         at.calc = calc
-        return np.asarray(at.get_forces(), float), float(at.get_potential_energy()), (np.asarray(at.get_stress(), float) if baro else np.zeros(6))
+        F, E, S6 = np.asarray(at.get_forces(), float), float(at.get_potential_energy()), (np.asarray(at.get_stress(), float) if baro else np.zeros(6))
+        if flt is not None:   # (once per configuration)
+            d = getattr(calc, "deltas", None)
+            F = flt.forces(F, d)
+            if baro:
+                S6 = flt.stress(S6, d)
+        return F, E, S6
 
     def sums(v):
         ke3 = mass * (v * v)
@@ -470,7 +537,8 @@ def npt_moving_cell(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         zint[n + 1] = zint[n] + dt * zeta[n + 1]
         he = _m3_mul(h[n + 1], eta[n + 1])
         h[n + 2] = [[h[n][r][c] + (2.0 * dt) * he[r][c] for c in range(3)] for r in range(3)]
-        yield n, E, float(2.0 * KE / (3 * N * kB)), time.time() - t0, x, v, np.array(h[n]), np.array(eta[n]), zeta[n], zint[n]
+        yield (n, E, float(2.0 * KE / (3 * N * kB)), time.time() - t0, x, v, np.array(h[n]), np.array(eta[n]), zeta[n], zint[n]) + (
+            () if flt is None else (flt.before,))
         x = _row_mul(qn + 0.5, h[n + 1])
         qp, q = q, qn
 

@@ -492,6 +492,31 @@ int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *
  * The handle stays usable after every error above. */
 int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *members);
 int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax);
+/* The filter of model-update jumps inside the device MD loop: the reference's MD driver wraps the atoms in FilterDeltas by
+ * default (theforce/cl/md.py:76-79, ml_filter = 0.8; theforce/calculator/active.py:47-76): the jumps `deltas` = results after -
+ * results before that an on-the-fly update puts into forces and stress are summed, the sum is shrunk at every force or stress
+ * call and subtracted — the force part clamped to +-1 eV/A — from what the integrator sees.  Here, by evaluation index, once per
+ * configuration n, inside the step's last kernel and (stress, moving cell only) the barostat's launch:
+ *     A_f <- (A_f + dF_n) shrink,   F_seen = F_model - min(max(A_f, -1), 1)     (a held component, sgpr_md_fix, then sees 0)
+ *     A_s <- (A_s + dS_n) shrink,   stress_seen = stress_model - A_s
+ * in this order, without contraction.  Everything the run REPORTS (packed results, sgpr_md_state, the frame record, the rows of
+ * scalars) stays the model's own.  The accumulators live in rings indexed like the positions: an evaluation that a halt discards
+ * leaves those of its configuration as they were.  A filtered run launches as many kernels as the run without a filter.
+ *
+ * sgpr_md_filter        after sgpr_md_begin (and sgpr_md_fix, sgpr_md_thermostat, sgpr_md_barostat), before the first
+ *                       sgpr_md_run.  0 < shrink < 1.  f0[3N] (caller atom order) and s0[6] (Voigt): the accumulators of
+ *                       configuration 0, NULL: zeros.  SGPR_E_UNSUPPORTED: a relaxation, a run with a committee, a run begun on
+ *                       more than one rank (and sgpr_md_relax, sgpr_md_committee behind a filter; sgpr_md_run where the step
+ *                       is not the single-rank gather form).  SGPR_E_INVALID: shrink outside (0, 1), a run that has started.
+ *                       sgpr_md_begin switches the filter off.
+ * sgpr_md_filter_push   between two sgpr_md_run calls: dF[3N] (caller atom order; NULL: none) and dS[6] (NULL: none; ignored at
+ *                       constant cell, where nobody asks for a stress) are added into the accumulators of the current
+ *                       configuration — the `deltas` of the calculate() a halt led to, before the evaluation is repeated.
+ * sgpr_md_filter_state  f[3N], s[6] (either may be NULL): the accumulators of the current configuration, what its evaluation
+ *                       will shrink and apply — and what sgpr_md_filter takes to continue in another run. */
+int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, const double *s0);
+int sgpr_md_filter_push(sgpr_model *h, const double *dF, const double *dS);
+int sgpr_md_filter_state(sgpr_model *h, double *f, double *s);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
