@@ -1559,6 +1559,21 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         const int N = h->N;
         std::vector<long long> st((size_t)16 * N);
         (void)hipMemcpy(st.data(), h->d_pstamps.p, sizeof(long long) * st.size(), hipMemcpyDeviceToHost);
+        // every wave with its list length, for tools/stamps_tiles.py.  Diagnostic only: d_pstamps exists solely under
+        // SGPR_STAMPS=1 and holds stamps solely in a -DSGPR_PHASE_STAMPS build; a product build never gets here
+        if (const char *path = getenv("SGPR_PSTAMPS_FILE")) {
+            std::vector<int> nnh(h->d_nn.n, 0);
+            if (!nnh.empty()) (void)hipMemcpy(nnh.data(), h->d_nn.p, sizeof(int) * nnh.size(), hipMemcpyDeviceToHost);
+            if (FILE *f = fopen(path, "w")) {
+                for (int i = 0; i < h->cnt; i++) {
+                    const size_t gi = (size_t)h->rank + (size_t)i * h->world;
+                    const long long *fw = st.data() + (size_t)i * 8, *rv = st.data() + ((size_t)N + i) * 8;
+                    fprintf(f, "%d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", i, gi < nnh.size() ? nnh[gi] : -1, fw[0], fw[1], fw[2],
+                            fw[3], fw[4], fw[5], rv[0], rv[1], rv[2]);
+                }
+                fclose(f);
+            }
+        }
         for (int pass = 0; pass < 2; pass++) {
             double d[7] = {0, 0, 0, 0, 0, 0, 0};
             long long t0 = 1LL << 62, t1 = 0;

@@ -48,6 +48,16 @@ __device__ __forceinline__ const T *launder(const T *p)
     return p;
 }
 
+// opaque copy of a lane-dependent index: what is computed from it is computed HERE, not hoisted out of the enclosing
+// loop and kept in a register across it (the reverse kernel's tile loop has none to spare).  This steers one compiler's
+// register allocator: when a new toolchain stops honouring it, tests/test_kernel_resources_cpu.py fails on the scratch
+// bytes of desc_rev_kernel<3,3,1..4,true,false,false> — re-tune there first.
+__device__ __forceinline__ int opaque(int v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
@@ -351,11 +361,28 @@ template <int LMAX, int NMAX>
 struct WaveLds {
     static constexpr int L1 = LMAX + 1, N1 = NMAX + 1, LL = L1 * L1, LLP = LL + 1, NSLOT = N1 * LL;
     // doubles per wave for the neighbour tile
-    // neighbours per tile of the forward kernel: 48, not 64 — a 64-neighbour tile costs 50 KB of LDS per
-    // workgroup (3 workgroups per CU, so 1024 workgroups run as 1.33 rounds); 48 fits four per CU and
-    // the whole grid is resident at once.  Lists longer than 48 take another tile.
+    // neighbours per tile of desc_fwd_kernel (inducing environments): 48, rows padded to LLP — a padded 64-neighbour tile
+    // costs 50 KB of LDS per workgroup (3 workgroups per CU, so 1024 workgroups run as 1.33 rounds); 48 fits four per CU
+    // and the whole grid is resident at once.  Lists longer than 48 take another tile.
     static constexpr int CH = 48;
     static constexpr int TILE_D = CH * N1 + CH * LLP;
+    // neighbours per tile of the STEP kernels (nl_fwd_kernel, desc_rev_kernel): 64, one per lane.  A relaxed dense frame
+    // has lists of 49 - 64 in a third of its four-atom workgroups, and a second tile repeats the whole per-tile chain
+    // for a handful of rows while the launch lasts as long as its slowest waves.  64 rows fit the four-per-CU budget
+    // (1280 doubles per wave) without the padding column.  Forward kernel, LL = 16: the staged harmonic row is 16 doubles
+    // wide and element k of row r sits at column k ^ rot(r), rot(r) = (r ^ (r >> 4)) & 15 — a row's 16 columns (the MFMA
+    // operand reads: lanes = the columns of two rows) stay a permutation of one bank row, and for a fixed k the 16
+    // consecutive rows of a store's lane group (lane = row) hit 16 different banks.  Other LL keep the odd padded stride.
+    // (The reverse kernel reads its staged rows with lane = row and immediate offsets: RevDims::at.)
+    // The width is 64 for EVERY (lmax, nmax), fitting or not — the trade for the shapes that are not the reference's
+    // default: nl_fwd's region is 64 (N1 + RS) doubles per wave, so (3, 4) goes from 40 704 to 43 008 B per workgroup and
+    // from four to three workgroups per CU (the 1.33 rounds above), lmax = 4 from 51.5 - 54.5 KB to 57.3 - 61.4 KB and from
+    // three to two per CU; lmax = 2 and (3, 2) stay at four per CU.  None of these shapes has been timed with either width.
+    static constexpr int CHS = 64;
+    static constexpr bool SWZ = LL == 16;
+    static constexpr int RS = SWZ ? LL : (LL | 1);
+    static __device__ __forceinline__ int rot(int row) { return (row ^ (row >> 4)) & 15; }
+    static __device__ __forceinline__ int at(int row, int k) { return SWZ ? row * RS + (k ^ rot(row)) : row * RS + k; }
 };
 
 // =========================================================================== forward
@@ -568,7 +595,7 @@ __global__ __launch_bounds__(256) void desc_fwd_kernel(DescArgs a)
 //          positions, |r| < rc, ballot compaction — a subsequence of a sorted sequence, so the list has
 //          exactly the pairs AND the order of a from-scratch build.  The hit mask hm[i] lets the reverse
 //          pass turn a candidate position into a list position by a popcount.
-//  forward lane = neighbour (tiles of 48): radial weights, solid harmonics, staged in LDS;
+//  forward lane = neighbour (tiles of 64, WaveLds::CHS): radial weights, solid harmonics, staged in LDS;
 //          c[lm][(s,n)] += sum_t Y[t][lm] f[t][n] [s_t = s] on v_mfma_f64_16x16x4 (K = four neighbours);
 //          power spectrum with one lane per (u,v) pair; norm in-wave.  The displacement and exp(-d^2/2)
 //          of every pair are left in `prec` for the reverse pass.
@@ -604,14 +631,16 @@ struct NlArgs {
 template <int LMAX, int NMAX, int ST>
 struct FwdLds {
     using WL = WaveLds<LMAX, NMAX>;
-    static constexpr int CH = WL::CH;
+    static constexpr int CH = WL::CHS;
     // list-build view of the shared region: keys | candidate ids | bins worth visiting | hits of the first tile
     static constexpr int BINL = NL_SORT_MAX + NL_SORT_MAX / 2, HIT0 = BINL + 2 * 64;
     static constexpr int NLV = HIT0 + 4 * CH;
-    static constexpr int FWV = CH * WL::N1 + CH * WL::LLP + CH / 2;              // radial rows | harmonic rows | species
-    static constexpr int P4V = ST * WL::NSLOT;                                   // c for the power spectrum
+    static constexpr int FWV = CH * WL::N1 + CH * WL::RS;                        // radial rows | harmonic rows (the species stay in registers)
+    // c for the power spectrum: with <= 16 channels its rows are padded by one (stride LL + 1), up to 16 doubles more than
+    // ST * NSLOT — the padding used to be left out of this count, harmlessly: RA has always been set by FWV or NLV
+    static constexpr int P4V = ST * WL::NSLOT + 16;
     static constexpr int RA = (NLV > FWV ? (NLV > P4V ? NLV : P4V) : (FWV > P4V ? FWV : P4V));
-    static constexpr int PW = 4 * CH + RA;  // + the hits of the second tile
+    static constexpr int PW = RA;  // lmax = nmax = 3: 1280 doubles, 40 960 B per four-wave workgroup, four workgroups per CU
 };
 
 template <int LMAX, int NMAX, int ST>
@@ -619,7 +648,7 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
 {
     using WL = WaveLds<LMAX, NMAX>;
     using FL = FwdLds<LMAX, NMAX, ST>;
-    constexpr int N1 = WL::N1, LL = WL::LL, LLP = WL::LLP, NSLOT = WL::NSLOT, CH = WL::CH;
+    constexpr int N1 = WL::N1, LL = WL::LL, NSLOT = WL::NSLOT, CH = WL::CHS;
     constexpr int UC = ST * N1, CBS = (UC + 15) / 16, RBL = (LL + 15) / 16;
     extern __shared__ double smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -627,15 +656,13 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
     if (ia >= a.N) return;  // (no workgroup barrier in this kernel)
     const int i = a.first + ia * a.stride;
     double *wbase = smem + (size_t)wave * FL::PW;
-    double *hit1 = wbase;                                          // [CH][4] hits of the second tile (r, species)
-    double *RA = wbase + 4 * CH;
+    double *RA = wbase;
     unsigned long long *keys = (unsigned long long *)RA;           // [NL_SORT_MAX]   } list build view
     int *hq = (int *)(RA + NL_SORT_MAX);                           // [NL_SORT_MAX]   }
     int4 *binl = (int4 *)(RA + FL::BINL);                          // [64]            }
     double *hit0 = RA + FL::HIT0;                                  // [CH][4]         }
     double *fl = RA;                                               // [CH][N1]        } forward view
-    double *Yl = fl + CH * N1;                                     // [CH][LLP]       }
-    int *sl = (int *)(Yl + CH * LLP);                              // [CH]            }
+    double *Yl = fl + CH * N1;                                     // [CH][RS]        } (WaveLds::at)
     double *cl = RA;                                               // [ST][NSLOT]       power-spectrum view
 
     PHASE_STAMP(0);
@@ -904,7 +931,7 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
             n.nbr_j[e] = j;
             n.nbr_shift[e] = cd;
             n.cidx[e] = c;
-            double *dst = t < CH ? hit0 + 4 * t : (t < 2 * CH ? hit1 + 4 * (t - CH) : nullptr);
+            double *dst = t < CH ? hit0 + 4 * t : nullptr;
             if (dst) { dst[0] = r0; dst[1] = r1; dst[2] = r2; dst[3] = __hiloint2double(0, sj); }
             // does the neighbour sit inside the z cone? (ylm.py:10-23: then the whole environment shears;
             // the length unit scales all three components alike)
@@ -920,15 +947,15 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
         n.nn_local[ia] = nn;
     }
     wave_sync();
-    // tile 0 keeps its hits in registers (the region is about to be reused); tile 1 reads hit1; further tiles
-    // (> 96 neighbours) read the list back from memory
+    // tile 0 keeps its hits in registers (the region is about to be reused); further tiles (> 64 neighbours) read
+    // the list back from memory
     double h0r[3] = {1.0, 0.0, 0.0};
     int h0s = 0;
     if (lane < min(nn, CH)) {
         h0r[0] = hit0[4 * lane]; h0r[1] = hit0[4 * lane + 1]; h0r[2] = hit0[4 * lane + 2];
         h0s = __double2loint(hit0[4 * lane + 3]);
     }
-    if (nn > 2 * CH) __threadfence();  // rare: the list entries written above are read back below
+    if (nn > CH) __threadfence();  // rare: the list entries written above are read back below
     PHASE_STAMP(3);
     // ------------------------------------------------------------------ forward
     v4d D[RBL][CBS];
@@ -945,10 +972,7 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
         int s = 0;
         if (on) {
             if (t0 == 0) { r[0] = h0r[0]; r[1] = h0r[1]; r[2] = h0r[2]; s = h0s; }
-            else if (t0 == CH) {
-                r[0] = hit1[4 * lane]; r[1] = hit1[4 * lane + 1]; r[2] = hit1[4 * lane + 2];
-                s = __double2loint(hit1[4 * lane + 3]);
-            } else {
+            else {
                 const size_t e = (size_t)i * maxnn + t;
                 const int j = n.nbr_j[e];
                 const int cd = n.nbr_shift[e];
@@ -976,27 +1000,26 @@ __global__ __launch_bounds__(256, 4) void nl_fwd_kernel(DescArgs a, NlArgs n)
             dst[1] = make_double2(r[2], ex);
         }
         wave_sync();  // the region's previous user (list build / previous tile) is done
-        if (lane < CH) {
 #pragma unroll
-            for (int q = 0; q < N1; q++) fl[lane * N1 + q] = on ? f[q] : 0.0;
+        for (int q = 0; q < N1; q++) fl[lane * N1 + q] = on ? f[q] : 0.0;
 #pragma unroll
-            for (int k = 0; k < LL; k++) Yl[lane * LLP + k] = on ? Y[k] : 0.0;
-            sl[lane] = on ? s : -1;
-        }
+        for (int k = 0; k < LL; k++) Yl[WL::at(lane, k)] = on ? Y[k] : 0.0;
+        const int sv = on ? s : -1;  // species of the tile's rows: read across lanes below, no LDS copy
         wave_sync();
         // c[lm][(s,n)] += sum over the tile's neighbours, four per MFMA: A = Y[t][lm], B = f[t][n] [s_t = s]
         // (four k-steps per trip, their operands requested together: the rows beyond the count hold zeros, CH is a
-        // multiple of 16; one k-step per trip was a chain of LDS round trips, one per MFMA)
+        // multiple of 16; one k-step per trip was a chain of LDS round trips, one per MFMA).  Groups of 16 rows in
+        // ascending order whatever the tile width: c has the bits it had with tiles of 48.
         for (int g16 = 0; g16 < cnt; g16 += 16) {
             double av[4][RBL], bv[4][CBS];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int tr = g16 + 4 * q + (lane >> 4);
-                const int st = sl[tr];
+                const int st = __shfl(sv, tr, 64);
 #pragma unroll
                 for (int rb = 0; rb < RBL; rb++) {
                     const int lm = 16 * rb + (lane & 15);
-                    av[q][rb] = (RBL * 16 == LL || lm < LL) ? Yl[tr * LLP + (lm < LL ? lm : 0)] : 0.0;
+                    av[q][rb] = (RBL * 16 == LL || lm < LL) ? Yl[WL::at(tr, lm < LL ? lm : 0)] : 0.0;
                 }
 #pragma unroll
                 for (int cb = 0; cb < CBS; cb++) {
@@ -1162,8 +1185,16 @@ struct RevDims {
     static constexpr int N1 = NMAX + 1, L1 = LMAX + 1, LL = L1 * L1, NSLOT = N1 * LL;
     static constexpr int KS = (N1 + 3) / 4;      // MFMA K-steps over the radial channels
     static constexpr int CB = (LL + 15) / 16;    // MFMA column blocks over lm
-    static constexpr int CH = 48, RB = CH / 16;  // neighbours per tile, MFMA row blocks
-    static constexpr int SP = LL | 1;            // staged row stride (odd: conflict-free ds_read_b64 by row)
+    static constexpr int CH = WaveLds<LMAX, NMAX>::CHS, RB = CH / 16;  // neighbours per tile (64: one per lane), MFMA row blocks
+    // staged rows (hY, then gY) [CH][LL]: read back with lane = row through immediate offsets (Harm::dot / backward take
+    // a pointer), so the start of a row may be skewed but not its inside.  An odd stride (LL | 1) is conflict-free; for
+    // LL = 16 the padded [64][17] does not fit four workgroups per CU, and row r starts at 16 r + (r >> 1) — half a
+    // double of padding per row: a fixed column of 32 consecutive rows still covers the 32 double-wide banks once
+    // (bank = 16 (r & 1) + (r >> 1) + k mod 32), and a row's 16 columns are contiguous for the accumulator stores.
+    static constexpr bool SKEW = LL == 16;
+    static constexpr int SP = LL | 1;
+    static constexpr int STAGE = SKEW ? CH * LL + CH / 2 : CH * SP;
+    static __device__ __forceinline__ int at(int row) { return SKEW ? row * LL + (row >> 1) : row * SP; }
     static constexpr int FS = 8 * KS + 1;        // radial staging row [f | f'] (odd stride)
 };
 
@@ -1174,7 +1205,7 @@ static int rev_region_doubles(int Dpad)
     using RD = RevDims<LMAX, NMAX>;
     const int UT = ST * RD::N1;
     const int dc = ST * RD::NSLOT + (ST <= 4 ? UT * UT * RD::L1 : Dpad);
-    int r = RD::CH * RD::SP;
+    int r = RD::STAGE;
     if (RD::CH * RD::FS > r) r = RD::CH * RD::FS;
     if (12 * RD::CH > r) r = 12 * RD::CH;
     if (dc > r) r = dc;
@@ -1217,10 +1248,10 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
     const int qd = xcd_quad(bx, nbx, a.xq);  // (the virial partial below stays at the quad's index: same sums as ever)
     const int ia = qd * WPW + wave;
     const bool active = ia < a.N;
-    const int perwave = ST * NSLOT + a.rsz + CH / 2;
+    const int perwave = ST * NSLOT + a.rsz + CH / 8;
     double *dcl = smem + (size_t)wave * perwave;  // [ST][NSLOT] dE/dc of this atom
     double *R = dcl + ST * NSLOT;                 // shared scratch region (a.rsz doubles)
-    int *sl = (int *)(R + a.rsz);                 // [CH] species slot per tile row
+    unsigned char *sl = (unsigned char *)(R + a.rsz);  // [16][RB] species slot per tile row: row r at [r & 15][r >> 4]
     const int gi = a.first + (active ? ia : 0) * a.stride;
     // batch entry (training rows): column, seed scale and output bases
     const int bq = ROWS ? a.rows_cols[blockIdx.y] : 0;
@@ -1393,7 +1424,7 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
         PHASE_STAMP(1);
         // ---------------------------------------------------------------- phase B: pair terms
         const double ang = a.shear[ia] ? SGPR_TINY_ANGLE : 0.0;
-        double *stage = R;  // [CH][SP] one staged row set (hY, then gY); earlier in a tile: [CH][FS] radial rows
+        double *stage = R;  // [CH] rows at RD::at: one staged row set (hY, then gY); earlier in a tile: [CH][FS] radial rows
         // training rows: an atom of another species than the column's has k(i,q) = 0 identically: no pair terms, and
         // nothing to hand over — the finalize of a rows batch only adds the hand-overs of neighbours of the column's
         // species (their species is in the list's code word), so the slots this atom would have cleared are never read
@@ -1447,37 +1478,42 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
             double f[N1], g, dg;
             radial_ex<NMAX>(d, u, a.rc, a.irc, ex, f, g, dg);
             wave_sync();  // the previous user of the region (phase A / the previous tile) is done
+            // (LDS addresses that are used in one stage of a tile are formed from an opaque copy of the lane index, here
+            // and below: hoisted out of the tile loop each of them held a register across the two passes)
+            const int ln = opaque(lane);
             if (on) {
                 // f_n = g d^(2n);  f_n' = dg d^(2n) + 2n g d^(2n-1)
                 double rpow = 1.0;
                 const double rho = d * d;
 #pragma unroll
                 for (int n = 0; n < 4 * KS; n++) {
-                    stage[lane * FS + n] = n < N1 ? f[n < N1 ? n : 0] : 0.0;
-                    stage[lane * FS + 4 * KS + n] = n < N1 ? dg * rpow + (n ? g * 2.0 * n * rpow * id : 0.0) : 0.0;
+                    stage[ln * FS + n] = n < N1 ? f[n < N1 ? n : 0] : 0.0;
+                    stage[ln * FS + 4 * KS + n] = n < N1 ? dg * rpow + (n ? g * 2.0 * n * rpow * id : 0.0) : 0.0;
                     rpow *= rho;
                 }
             }
-            if (lane < CH) sl[lane] = on ? s : -1;
+            sl[(ln & 15) * RB + (ln >> 4)] = (unsigned char)(on ? s : 0xff);
             wave_sync();
-            // MFMA A operands: lane = (row i = lane & 15, k = lane >> 4) of each row block
+            // MFMA A operands: lane = (row i = lane & 15, k = lane >> 4) of each row block; the species of the lane's
+            // four rows in one word (a byte each: 0xff = no row)
             double af[RB][KS], ah[RB][KS];
-            int sr[RB];
+            static_assert(RB == 4, "species bytes of a lane's rows fill one word");
+            const int la = opaque(lane);
+            const unsigned srp = ((const unsigned *)sl)[la & 15];
 #pragma unroll
             for (int rb = 0; rb < RB; rb++) {
-                const int row = 16 * rb + (lane & 15);
-                sr[rb] = sl[row];
+                const int row = 16 * rb + (la & 15);
 #pragma unroll
                 for (int ks = 0; ks < KS; ks++) {
-                    af[rb][ks] = stage[row * FS + 4 * ks + (lane >> 4)];
-                    ah[rb][ks] = stage[row * FS + 4 * KS + 4 * ks + (lane >> 4)];
+                    af[rb][ks] = stage[row * FS + 4 * ks + (la >> 4)];
+                    ah[rb][ks] = stage[row * FS + 4 * KS + 4 * ks + (la >> 4)];
                 }
             }
             wave_sync();  // radial rows are in registers: the region is free for the staged outputs
             Harm<LMAX> h;
             h.hc = launder(&c_hc);
             h.prepare(x, y - ang * z, ang * y + z);
-            double dEdd = 0.0, gxs = 0.0, gys = 0.0, gzs = 0.0;
+            double rad = 0.0, gxs = 0.0, gys = 0.0, gzs = 0.0;  // rad = dE/dd / d
 #pragma unroll
             for (int pass = 0; pass < 2; pass++) {
                 // pass 0: hY = f'.dC (radial derivative part), pass 1: gY = f.dC (angular part)
@@ -1485,44 +1521,51 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
                 for (int cb = 0; cb < CB; cb++) {
                     // row block outermost: one accumulator tile (4 doubles) live at a time; the B
                     // fragment is re-read from LDS for every row block (one ds_read_b64)
-                    const int n_b = lane >> 4, lm = 16 * cb + (lane & 15);
+                    const int lp = opaque(lane);
+                    const int n_b = lp >> 4, lm = 16 * cb + (lp & 15);
 #pragma unroll
                     for (int rb = 0; rb < RB; rb++) {
                         v4d D = (v4d){0.0, 0.0, 0.0, 0.0};
+                        const int sr_rb = (int)((srp >> (8 * rb)) & 0xffu);
                         for (int sp = 0; sp < S_use; sp++) {
-                            if (__ballot(sr[rb] == sp) == 0ull) continue;
+                            if (__ballot(sr_rb == sp) == 0ull) continue;
 #pragma unroll
                             for (int ks = 0; ks < KS; ks++) {
                                 const int n = 4 * ks + n_b;
                                 const bool ok = n < N1 && lm < LL;
                                 const double bv = dcl[sp * NSLOT + (ok ? n * LL + lm : 0)];
                                 const double av = pass == 0 ? ah[rb][ks] : af[rb][ks];
-                                D = __builtin_amdgcn_mfma_f64_16x16x4f64(sr[rb] == sp ? av : 0.0, ok ? bv : 0.0, D, 0, 0, 0);
+                                D = __builtin_amdgcn_mfma_f64_16x16x4f64(sr_rb == sp ? av : 0.0, ok ? bv : 0.0, D, 0, 0, 0);
                             }
                         }
                         // C/D map of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
                         if (CB * 16 == LL || lm < LL) {
 #pragma unroll
-                            for (int q = 0; q < 4; q++) stage[(16 * rb + (lane >> 4) + 4 * q) * SP + lm] = D[q];
+                            for (int q = 0; q < 4; q++) stage[RD::at(lp >> 4) + lm + RD::at(16 * rb + 4 * q)] = D[q];  // (at() is additive over an even row offset: one address register, sixteen immediate offsets)
                         }
                     }
                 }
                 wave_sync();
                 if (on) {
-                    if (pass == 0) dEdd = h.dot(stage + lane * SP);
+                    const double *row = stage + RD::at(opaque(lane));
+                    if (pass == 0) rad = h.dot(row) * id;
                     else {
                         h.hc = launder(h.hc);
-                        h.backward(stage + lane * SP, gxs, gys, gzs);
+                        h.backward(row, gxs, gys, gzs);
                     }
                 }
                 wave_sync();
             }
-            // inverse shear (ylm.py:203-213) + radial part, then 1/u
-            const double rad = dEdd * id;
+            // inverse shear (ylm.py:203-213) + radial part, then 1/u.  (The unit is looked up a second time, behind an
+            // opaque copy of the species: u and 1/u do not stay live across the two passes — with 64 rows per tile the
+            // kernel has no registers to spare, tests/test_kernel_resources_cpu.py.)
+            int s_again = s;
+            asm volatile("" : "+v"(s_again));
+            const double u_e = unit_of<ST>(a, s_again), iu_e = inv_unit_of<ST>(a, s_again);
             double gr[3];
-            gr[0] = (gxs + rad * x) * iu;
-            gr[1] = (gys + ang * gzs + rad * y) * iu;
-            gr[2] = (-ang * gys + gzs + rad * z) * iu;
+            gr[0] = (gxs + rad * x) * iu_e;
+            gr[1] = (gys + ang * gzs + rad * y) * iu_e;
+            gr[2] = (-ang * gys + gzs + rad * z) * iu_e;
             if (on) {
                 if constexpr (GATHER) {
                     // handed to atom j at ITS list position: the last kernel reads whole rows, coalesced
@@ -1539,23 +1582,34 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
                 }
             }
             // 9 virial sums (+ 3 force sums in the sharded form) through the region: [12][CH], then 48
-            // lanes each add a quarter of a row and two shuffles finish it
-            if (lane < CH) {
-                const double rv[3] = {x * u, y * u, z * u};  // = r to rounding (r itself is not kept live)
+            // lanes each add a quarter of a row and two shuffles finish it.  The order of the sums is that of tiles of
+            // 48 (lists up to 64 give the bits they gave then): rows 0 - 47 in quarters of twelve; then, only when
+            // the tile has more rows, what a second tile's quarters were — rows 48 - 59, 60 - 63, nothing, nothing —
+            // as an addition of its own.
+            const int lv = opaque(lane);
+            {
+                const double rv[3] = {x * u_e, y * u_e, z * u_e};  // = r to rounding (r itself is not kept live)
 #pragma unroll
                 for (int p = 0; p < 3; p++)
 #pragma unroll
-                    for (int q = 0; q < 3; q++) stage[(3 * p + q) * CH + lane] = on ? rv[p] * gr[q] : 0.0;
+                    for (int q = 0; q < 3; q++) stage[(3 * p + q) * CH + lv] = on ? rv[p] * gr[q] : 0.0;
 #pragma unroll
-                for (int k = 0; k < 3; k++) stage[(9 + k) * CH + lane] = on ? gr[k] : 0.0;
+                for (int k = 0; k < 3; k++) stage[(9 + k) * CH + lv] = on ? gr[k] : 0.0;
             }
             wave_sync();
             if (lane < 48) {
-                const double *src = stage + (lane >> 2) * CH + (lane & 3) * (CH / 4);
+                const double *src = stage + (lv >> 2) * CH + (lv & 3) * 12;
                 double sacc = 0.0;
 #pragma unroll
-                for (int i = 0; i < CH / 4; i++) sacc += src[i];
+                for (int i = 0; i < 12; i++) sacc += src[i];
                 tot += sacc;
+                if (cnt > 48) {  // wave-uniform
+                    const int r0 = 48 + (lv & 3) * 12;
+                    double sacc2 = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 12; i++) sacc2 += r0 + i < CH ? src[48 + i] : 0.0;
+                    tot += sacc2;
+                }
             }
         }
     }
@@ -1627,7 +1681,7 @@ static int run_bwd(DescArgs a, hipStream_t st, const GemmParams *cov = nullptr)
     a.rsz = rev_region_doubles<LMAX, NMAX, ST>(a.Dpad);
     constexpr int WPW = SGPR_REV_WPW(ST);
     if (WPW == 1) a.xq = 0;
-    size_t lds = sizeof(double) * WPW * (size_t)(ST * RD::NSLOT + a.rsz + RD::CH / 2);
+    size_t lds = sizeof(double) * WPW * (size_t)(ST * RD::NSLOT + a.rsz + RD::CH / 8);
     static size_t attr_set[6] = {0, 0, 0, 0, 0, 0};
     const bool gather = a.G != nullptr, rows = a.rows_aw != nullptr;
     const bool with_cov = WPW == 4 && cov && !rows && cov->tiles && cov->ntiles > 0 && cov->bm == 32 && cov->kd == 16;
