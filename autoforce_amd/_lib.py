@@ -79,6 +79,10 @@ SIGNATURES = {
     "sgpr_md_cells": (C.c_int, [_vp, _i64, C.c_int, _vp]),
     "sgpr_md_relax": (C.c_int, [_vp, _dbl, _vp, C.c_int, _vp]),
     "sgpr_md_relax_reset": (C.c_int, [_vp]),
+    "sgpr_md_neb": (C.c_int, [_vp, C.c_int, _vp, _dbl, _dbl, C.c_int, _vp]),
+    "sgpr_md_neb_reset": (C.c_int, [_vp]),
+    "sgpr_md_neb_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "sgpr_md_neb_info": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sgpr_md_fix": (C.c_int, [_vp, _vp]),
     "sgpr_md_record": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sgpr_md_frame_count": (C.c_int, [_vp, _vp]),

@@ -853,6 +853,108 @@ class ActiveCalculator(Calculator):
         self.results["free_energy"] = self.results["energy"]
         return dict(converged=converged, steps=max(done - 1, 0), evaluations=done)
 
+    def run_neb(self, images, fmax=0.01, climb=False, k=0.1, steps=100000, chunk=256, on_band=None, **fire):
+        """Nudged elastic band over `images` (a list of K + 2 atoms objects that share numbers, cell and pbc; the first and
+        the last are the fixed ends) as theforce/cl/neb.py converges one around this calculator —
+        ase.neb.NEB(images, climb=climb, allow_shared_calculator=True) under an optimizer, one calculate() per image per step —
+        but with FIRE on all interior images at once and the band in device memory between model updates
+        (SGPRModel.neb_begin; md_neb.inc; workloads.neb_fire is the host twin and the definition: ASE's default `aseneb`
+        method, one spring constant k).  Every evaluation of the band is K plain steps of the live model; the host reads 16
+        scalars per evaluation and writes one log line for it (energy of the highest image, temperature 0, largest covloss).
+        An evaluation whose largest covloss over all images reaches the sampling threshold stops the device with nothing
+        moved: the image that carried it gets its positions and is handed to calculate() — the on-the-fly update —; if the
+        model grew, the optimizer is re-initialised (the reference's "model updated -> restart!"), and the run goes on with the
+        band evaluated again by the new model.  At most `steps` moves.  Returns dict(converged, steps, evaluations, energies
+        [K], forces [K, N, 3] of the interior images at the end) with the images' positions written back.
+        on_band(n, state): called behind every batch with the index of its last accepted evaluation and
+        SGPRModel.neb_state(results=True) of that band (positions, energy, forces [K, ...]) — a path writer.
+        atoms.constraints of image 1 (FixAtoms, FixCartesian) hold the same components in every image; images whose
+        constraints differ are refused.  The displacement of an atom between neighbouring images must stay well inside half a
+        cell (workloads.neb_check_band).  A committee calculator is refused: the device band evaluates one model.  Where
+        md_on_device_ok() says no or the run is sharded, the same loop runs on the host (neb_fire around calculate())."""
+        from .workloads import neb_fire
+        if hasattr(self, "model_dict"):
+            raise NotImplementedError("run_neb: the band is evaluated by one model; a committee calculator (BCMActiveCalculator) "
+                                      "answers with its members: drive calculate() from ase.neb.NEB as theforce/cl/neb.py does")
+        images = list(images)
+        K = len(images) - 2
+        if K < 1:
+            raise ValueError("run_neb: a band has at least one interior image between its two ends")
+        masks = [self.constraint_mask(im) for im in images[1:-1]]
+        fx = masks[0]
+        for mk in masks[1:]:
+            if (mk is None) != (fx is None) or (fx is not None and not np.array_equal(mk, fx)):
+                raise NotImplementedError("run_neb: the interior images hold different components (atoms.constraints); one mask serves every image")
+        if fx is not None and not fx.any():
+            fx = None
+        hold = {} if fx is None else dict(fixed=fx)
+        numbers, _, cell0, pbc = self._system(images[1])
+        for im in images:
+            n_, _, c_, p_ = self._system(im)
+            if not (np.array_equal(n_, numbers) and np.array_equal(c_, cell0) and np.array_equal(p_, pbc)):
+                raise ValueError("run_neb: the images of a band share numbers, cell and pbc")
+        R = np.array([np.asarray(im.positions, float) for im in images])
+
+        def device_ok():
+            return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "neb_begin")
+        if self._needs_seed() or not device_ok():
+            images[1].calc = self
+            images[1].get_forces()
+        if not device_ok():   # the host loop: calculate() per image, a restart of the optimizer whenever the model grew
+            size = [self.size]
+
+            def grew(o):
+                if self.size != size[0]:
+                    size[0] = self.size
+                    return "reset"
+            last = None
+            for last in neb_fire(self, numbers, R, cell0, pbc, steps, fmax, k=k, climb=climb, species=self.engine.species, update=grew, **hold, **fire):
+                if on_band is not None:
+                    on_band(last["n"], dict(positions=last["band"], energy=last["energies"], forces=last["forces"]))
+            for im, x in zip(images[1:-1], last["band"]):
+                im.positions = x
+            return dict(converged=last["converged"], steps=last["n"], evaluations=last["n"] + 1, energies=last["energies"], forces=last["forces"])
+        eng = self.engine
+        eng.neb_begin(numbers, R, cell0, pbc, fmax, k=k, climb=climb, **hold, **fire)
+        done, skip_gate, converged = 0, False, False
+        batch = min(8, chunk)
+        while done <= steps and not converged:
+            n = 1 if skip_gate else min(batch, steps + 1 - done)
+            gate = 0.0 if skip_gate else self._md_gate(numbers)
+            final = done + n == steps + 1
+            sc, code = eng.md_run(n, None, ediff=gate, final=final)
+            accepted = len(sc) - 1 if code == 1 else len(sc)
+            lines = []
+            for r in sc[:accepted]:
+                if skip_gate:      # (the band calculate() has just dealt with: its line is written, its step counted — as run_relax)
+                    skip_gate = False
+                else:
+                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), 0.0, float(r[11]), f"neb: highest image {int(r[1])}")))
+                    self.step += 1
+                done += 1
+            self._log_lines(lines)
+            batch = min(8, chunk) if code else min(2 * batch, chunk)
+            if on_band is not None and accepted:   # (the last accepted band: the current one where nothing moved behind it)
+                on_band(done - 1, eng.neb_state(which=0 if (code == 3 or (code == 0 and final)) else -1, results=True))
+            if code == 1:   # the image that carried the largest covloss goes to calculate(), as inside an ASE loop
+                i = int(sc[-1, 2])
+                img = images[i]
+                img.positions = eng.neb_state()["positions"][i - 1]
+                size = self.size
+                img.calc = self
+                self.results = {}
+                self.calculate(img)
+                if self.size != size:
+                    self.log("model updated -> restart!")
+                    eng.neb_reset()
+                skip_gate = True
+            converged = code == 3
+        st = eng.neb_state(results=True)
+        for im, x in zip(images[1:-1], st["positions"]):
+            im.positions = x
+        self.results = {}
+        return dict(converged=converged, steps=max(done - 1, 0), evaluations=done, energies=st["energy"], forces=st["forces"])
+
     def _log_lines(self, lines):
         """A batch of per-step lines in one open (a device loop produces them by the hundred)."""
         if not lines:

@@ -231,6 +231,20 @@ struct MdState {
     DevBuf<double> bcm_x;          // [N][3] the current positions in caller atom order: what the members bin
     DevBuf<double> bcm_info_d;     // [rows][32] weights | largest covlosses per evaluation of a call
     std::vector<double> bcm_info;  // ... of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
+    // the nudged elastic band (sgpr_md_neb, md_neb.inc): K interior images evaluated by this one handle per evaluation of the band;
+    // band, velocity and results in caller atom order, the optimizer's scalars in rx_state and rp (a relaxation's, cell = 0)
+    bool neb = false;
+    int nb_K = 0;
+    NebCell nb_cell = {};
+    DevBuf<double> nb_X;           // [RLX_RING][K][N][3] the band by evaluation index % RLX_RING
+    DevBuf<double> nb_V;           // [K][N][3] FIRE's velocity
+    DevBuf<double> nb_P;           // [RLX_RING][K][4N + 11] packed results of the images' plain steps
+    DevBuf<double> nb_ends;        // [2][N][3] images 0 and K + 1
+    DevBuf<double> nb_sums;        // [K][NEB_SUMS] md_neb_sums_kernel's output
+    DevBuf<double> nb_coef;        // [K][2] the projection's coefficients
+    DevBuf<char> nb_par;           // one NebFirePar: cell, FIRE's keywords, spring constant, climb — md_neb_fire_kernel's constants
+    DevBuf<double> nb_info_d;      // [rows][NEB_INFO] E | covmax per evaluation of a call
+    std::vector<double> nb_info;   // ... of the last call's evaluations that stand (sgpr_md_neb_info)
     // multiples of rec_every in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
     static long long rec_between(long long a, long long b, int every) { return (b + every - 1) / every - (a + every - 1) / every; }
 };
@@ -1093,6 +1107,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_npt.inc"
 #include "md_relax.inc"
 #include "md_bcm.inc"
+#include "md_neb.inc"
 #include "md_record.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
@@ -1632,6 +1647,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.fixed.release();
         m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
         m.bcm_P.release(); m.bcm_x.release(); m.bcm_info_d.release();
+        m.nb_X.release(); m.nb_V.release(); m.nb_P.release(); m.nb_ends.release(); m.nb_sums.release(); m.nb_coef.release(); m.nb_info_d.release(); m.nb_par.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
         for (auto b : tb) b->release();
         h->d_panel_cnt.release();

@@ -66,6 +66,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.ring = 3; m.nh = false; m.evaluated = false;
     m.npt = false; m.npt_started = false; m.cells.clear();
     m.relax = false; m.relax_started = false;
+    m.neb = false; m.nb_info.clear();
     m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
     m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
     m.bcm.clear(); m.bcm_info.clear();
@@ -111,6 +112,7 @@ extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
     if (m.nh || m.npt || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
+    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_neb");
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run has a committee (sgpr_md_committee), which runs without a mask");
     const int N = m.N;
@@ -147,6 +149,7 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
     if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
     if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
+    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a nudged elastic band (sgpr_md_neb)");
     if (!m.bcm.empty()) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call it before sgpr_md_committee");
     if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
@@ -350,6 +353,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
     if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
+    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     const double *fp = fire ? fire : RLX_ASE;
     if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
@@ -723,6 +727,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
     if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
     if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
+    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a nudged elastic band; a committee serves dynamics only");
     if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.n_fixed);
     if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.world);
@@ -868,6 +873,213 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     return SGPR_OK;
 }
 
+// ---- the nudged elastic band (sgpr_md_neb; md_neb.inc has the scheme, workloads.neb_fire is the host twin) ----
+// For the run begun by sgpr_md_begin (any interior image as its positions: they bind the system; masses, velocities, dt,
+// friction and kT are ignored) and, if used, sgpr_md_fix — one mask for every image —, before the first sgpr_md_run.
+// positions[K + 2][N][3]: the band in caller atom order, images 0 and K + 1 the fixed ends; fire as in sgpr_md_relax.
+// sgpr_md_run then evaluates the K interior images with this one handle, moves them with FIRE, and stops with halt code 3 at
+// the first band whose largest |G_row|^2 over all K N rows is below fmax^2.  Constant cell, one rank.
+static int md_neb_init_state(sgpr_model *h)
+{
+    MdState &m = h->md;
+    double s[RLX_LEN] = {};
+    s[RLX_DT] = m.rp.dt0; s[RLX_A] = m.rp.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
+    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.nb_V.p, 0, sizeof(double) * 3 * (size_t)m.N * (size_t)m.nb_K));
+    return SGPR_OK;
+}
+
+extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double fmax, double k_spring, int climb, const double *fire)
+{
+#pragma clang fp contract(off)
+    if (!h || !positions) return fail(SGPR_E_INVALID, "sgpr_md_neb: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_neb: call sgpr_md_begin first");
+    if (K < 1 || K > NEB_MAX) return fail(SGPR_E_INVALID, "sgpr_md_neb: %d interior images; a band has 1 to %d", K, NEB_MAX);
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run was begun on %d ranks; a band runs on one", m.world);
+    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has started");
+    if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has a thermostat or a barostat");
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a filter (sgpr_md_filter), which serves dynamics only");
+    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
+    if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
+    if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
+    const double *fp = fire ? fire : RLX_ASE;
+    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
+        return fail(SGPR_E_INVALID, "sgpr_md_neb: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.N;
+    const size_t N3 = (size_t)3 * N, plen = (size_t)sgpr_packed_len(N);
+    NebCell cl = {};
+    HIPCHK(hipMemcpy(cl.h, m.cell.p, sizeof(cl.h), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) cl.pbc[k] = m.pbc[k] ? 1 : 0;
+    const bool any_pbc = cl.pbc[0] || cl.pbc[1] || cl.pbc[2];
+    if (any_pbc) {
+        if (!(fabs(rlx_det(cl.h)) > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: the cell is singular");
+        rlx_m3_inv(cl.h, cl.hi);
+    }
+    // The rounding recovers a displacement only when it is well inside half a cell: no fractional component of a displacement
+    // after rounding at +-1/2 (where rint may go either way from one evaluation to the next), and the displacement after
+    // rounding no longer than half the smallest perpendicular width of the periodic directions (beyond it another image of
+    // the atom may be the nearer one).  The initial band only: the user keeps the images closer than that.
+    double wmin = 1e300;
+    for (int k = 0; k < 3; k++)
+        if (cl.pbc[k]) wmin = std::min(wmin, 1.0 / sqrt((cl.hi[k] * cl.hi[k] + cl.hi[3 + k] * cl.hi[3 + k]) + cl.hi[6 + k] * cl.hi[6 + k]));
+    for (int i = 1; i <= K + 1; i++)
+        for (int c = 0; c < N; c++) {
+            const double *a = positions + N3 * (size_t)(i - 1) + 3 * (size_t)c, *b = positions + N3 * (size_t)i + 3 * (size_t)c;
+            const double d[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+            double o[3];
+            neb_mic(cl, d[0], d[1], d[2], o[0], o[1], o[2]);
+            for (int k = 0; k < 3 && any_pbc; k++) {
+                const double sfr = (o[0] * cl.hi[k] + o[1] * cl.hi[3 + k]) + o[2] * cl.hi[6 + k];
+                if (cl.pbc[k] && fabs(sfr) >= 0.5 - 1e-9)
+                    return fail(SGPR_E_INVALID, "sgpr_md_neb: atom %d moves half a cell (fractional %.6f along vector %d) between images %d and %d: "
+                                "the minimum-image rounding cannot recover it; add images", c, sfr, k, i - 1, i);
+            }
+            const double len = sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]);
+            if (any_pbc && len > 0.5 * wmin)
+                return fail(SGPR_E_INVALID, "sgpr_md_neb: atom %d moves %.4f between images %d and %d, more than half the smallest perpendicular "
+                            "width of the cell (%.4f): the minimum-image rounding cannot recover it; add images", c, len, i - 1, i, wmin);
+        }
+    RelaxParams p = {};
+    for (int k = 0; k < 9; k++) p.h0[k] = cl.h[k];
+    p.fmax2 = fmax * fmax;
+    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
+    p.cf = (double)N; p.cell = 0;
+    // rings of RLX_RING slots, every slot the initial band (what runs behind a halt evaluates stale slots)
+    if (m.nb_X.alloc(N3 * (size_t)K * RLX_RING) || m.nb_V.alloc(N3 * (size_t)K) || m.nb_P.alloc(plen * (size_t)K * RLX_RING) || m.nb_ends.alloc(2 * N3) ||
+        m.nb_sums.alloc((size_t)NEB_SUMS * K) || m.nb_coef.alloc((size_t)2 * K) || m.rx_state.alloc(RLX_LEN) || m.nb_par.alloc(sizeof(NebFirePar)))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_neb: device allocation failed");
+    for (int r = 0; r < RLX_RING; r++)
+        HIPCHK(hipMemcpy(m.nb_X.p + N3 * (size_t)K * r, positions + N3, sizeof(double) * N3 * K, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.nb_ends.p, positions, sizeof(double) * N3, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.nb_ends.p + N3, positions + N3 * (size_t)(K + 1), sizeof(double) * N3, hipMemcpyHostToDevice));
+    NebFirePar par = {};
+    par.cell = cl; par.p = p; par.kspr = k_spring; par.climb = climb ? 1 : 0;
+    HIPCHK(hipMemcpy(m.nb_par.p, &par, sizeof(par), hipMemcpyHostToDevice));
+    m.rp = p;
+    m.nb_cell = cl; m.nb_K = K;
+    m.neb = true; m.ring = RLX_RING;
+    m.nb_info.clear();
+    return md_neb_init_state(h);
+}
+
+// optimizer.initialize() for the band: v = 0 and dt, a, nsteps back to their start (the reference's "model updated -> restart!")
+extern "C" int sgpr_md_neb_reset(sgpr_model *h)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_neb_reset: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_reset: call sgpr_md_begin and sgpr_md_neb first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return md_neb_init_state(h);
+}
+
+// The K interior images in caller atom order: positions[K][N][3] of the current band (which = 0) or the one evaluated before it
+// (-1), velocities[K][N][3] FIRE's, packed[K][4N + 11] the images' results where the last sgpr_md_run evaluated that band
+// (a halted or `final` call: which = 0; a call that ran through: which = -1).  Any of them NULL.
+extern "C" int sgpr_md_neb_state(sgpr_model *h, double *positions, double *velocities, double *packed, int which)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: call sgpr_md_begin and sgpr_md_neb first");
+    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: which = 0 or -1");
+    if (which == -1 && m.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: no earlier band");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N3 = (size_t)3 * m.N, plen = (size_t)sgpr_packed_len(m.N), K = (size_t)m.nb_K;
+    const size_t sl = (size_t)((m.t + which + RLX_RING) % RLX_RING);
+    if (positions) HIPCHK(hipMemcpy(positions, m.nb_X.p + N3 * K * sl, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
+    if (velocities) HIPCHK(hipMemcpy(velocities, m.nb_V.p, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.nb_P.p + plen * K * sl, sizeof(double) * plen * K, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// The band record of the last sgpr_md_run: out[count][32] = E[16] | covmax[16] (image i at entry i - 1, the rest zero) of its
+// evaluations first ... first + count - 1 (0 = the call's first) among those that stand.
+extern "C" int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out)
+{
+    if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: call sgpr_md_begin and sgpr_md_neb first");
+    const long long have = (long long)(m.nb_info.size() / NEB_INFO);
+    if ((long long)first + count > have)
+        return fail(SGPR_E_INVALID, "sgpr_md_neb_info: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", first, (long long)first + count - 1, have);
+    memcpy(out, m.nb_info.data() + (size_t)NEB_INFO * first, sizeof(double) * NEB_INFO * (size_t)count);
+    return SGPR_OK;
+}
+
+// sgpr_md_run for a band, in the shape of md_relax_run and md_committee_run: every evaluation is K plain steps of the live
+// handle — image i's caller-order positions in the band ring through the handle's own binning kernel, into its own packed
+// buffer; before each the handle is as md_reset_lists leaves it: every image rebuilds its candidate lists (one list set per
+// image would save that: not done) — with md_neb_sums_kernel, md_neb_fire_kernel and md_neb_move_kernel behind them.  The
+// halts — covloss gate (1), capacity overflow at any image (2), convergence (3) — are decided by md_neb_fire_kernel on the
+// evaluation itself, before anything moves: what the host has enqueued behind a halt evaluates stale slots and changes nothing.
+// The halt words count evaluations of the band from the handle's step counter at the call's start (the handle's own counter
+// advances K per evaluation; no plain step reads the words).
+static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
+{
+    MdState &m = h->md;
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rb = md_rebind(h)) return rb;
+    hipStream_t st = h->stream;
+    const int N = m.N, RG = RLX_RING, K = m.nb_K;
+    const size_t plen = (size_t)sgpr_packed_len(N), N3 = (size_t)3 * N;
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
+    if (m.nb_info_d.alloc((size_t)NEB_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemsetAsync(m.nb_info_d.p, 0, sizeof(double) * NEB_INFO * ((size_t)nevals + 1), st));
+    m.started = true;
+    m.nb_info.clear();
+    if (!h->warm) {   // the checked pass grows capacities: over every interior image
+        const size_t sw = (size_t)(m.t % RG);
+        for (int i = 0; i < K; i++) {
+            const int rc_ = run_checked(h, m.nb_X.p + N3 * (K * sw + i), m.cell.p, m.nb_P.p + plen * (K * sw + i), st);
+            if (rc_) return rc_;
+        }
+        h->warm = true;
+    }
+    m.chain_ok = false;
+    const unsigned step0 = h->step_count;
+    const double gate = ediff > 0.0 ? ediff : 1e300;
+    int enq = 0;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
+        const size_t sl = (size_t)((m.t + j) % RG), sn = (sl + 1) % RG;
+        const double *band = m.nb_X.p + N3 * K * sl;
+        double *Pk = m.nb_P.p + plen * K * sl;
+        for (int i = 0; i < K; i++) {
+            if (const int rl = md_reset_lists(h, st)) return rl;
+            const int re = enqueue_step(h, band + N3 * i, m.cell.p, Pk + plen * i, st, nullptr);
+            if (re) return re;
+        }
+        const int step = (int)(step0 + j);
+        const bool stay = final_eval && j == nevals - 1;
+        const NebBand b = {N, K, plen, band, m.nb_ends.p, Pk, h->d_perm.p, m.fix()};
+        hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, st, b, m.nb_cell, m.nb_sums.p, (const int *)m.halt.p, step);
+        hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, st, b, (const NebFirePar *)m.nb_par.p, m.rx_state.p, (const double *)m.nb_V.p,
+                           (const double *)m.nb_sums.p, m.nb_coef.p, m.nb_info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host_dev, step,
+                           m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.mark_dev + j, stay ? 1 : 0);
+        if (!stay)
+            hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, st, b, m.nb_cell, (const double *)m.rx_state.p,
+                               (const double *)m.nb_coef.p, m.nb_V.p, m.nb_X.p + N3 * K * sn, (const int *)m.halt.p, step);
+        return SGPR_OK;
+    });
+    h->lists_valid = false;
+    if (rc_) return rc_;
+    if (const int rc = md_collect(h, enq, st, scalars, false)) return rc;
+    MdHalt r;
+    if (const int rd = md_decode_halt(h, step0, enq, final_eval, false, &r)) return rd;
+    if (r.done > 0) {
+        m.nb_info.assign((size_t)NEB_INFO * r.done, 0.0);
+        HIPCHK(hipMemcpy(m.nb_info.data(), m.nb_info_d.p, sizeof(double) * NEB_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
+    }
+    md_finish_call(m, r, scalars, true, r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
+    return SGPR_OK;
+}
+
 // Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last
 // the integrator moves on with the next row of `noise` ([nevals][N][3] standard normal deviates, caller atom order; null:
 // velocity Verlet).  Stops at the first evaluation whose largest covloss reaches `ediff` (<= 0: never): *evals_done
@@ -883,6 +1095,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_run: call sgpr_md_begin first");
     if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
     if (m.relax) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    if (m.neb) return md_neb_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
     if (!m.bcm.empty()) return md_committee_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
     HIPCHK(hipSetDevice(h->device));
     if (const int rb = md_rebind(h)) return rb;
@@ -1029,6 +1242,7 @@ extern "C" int sgpr_md_state(sgpr_model *h, double *positions, double *velocitie
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_state: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_state: call sgpr_md_begin first");
+    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_state: the run is a nudged elastic band; sgpr_md_neb_state returns its images");
     if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_state: which = 0 or -1");
     if (which == -1 && m.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_state: no earlier configuration");
     HIPCHK(hipSetDevice(h->device));
@@ -1056,6 +1270,7 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_velocities: call sgpr_md_begin first");
     if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
+    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a nudged elastic band; sgpr_md_neb_state returns its images and FIRE's velocity");
     if (!m.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1096,6 +1311,7 @@ extern "C" int sgpr_md_record(sgpr_model *h, int every, int what)
     if (every < 0 || (what & ~3)) return fail(SGPR_E_INVALID, "sgpr_md_record: every >= 0, what = bit 0 (velocities) | bit 1 (results)");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.world);
     if (every && !m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run has a committee (sgpr_md_committee), which records no frames");
+    if (every && m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run is a nudged elastic band (sgpr_md_neb), which records no frames; sgpr_md_neb_state behind a cut call serves trajectories");
     m.rec_every = every;
     m.rec_what = every ? what : 0;
     return SGPR_OK;
@@ -1181,6 +1397,7 @@ extern "C" int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, co
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_filter: the run has started");
     if (!(shrink > 0.0 && shrink < 1.0)) return fail(SGPR_E_INVALID, "sgpr_md_filter: 0 < shrink < 1");
     if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a relaxation (sgpr_md_relax), which applies no filter");
+    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a nudged elastic band (sgpr_md_neb), which applies no filter");
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.world);
     HIPCHK(hipSetDevice(h->device));

@@ -126,6 +126,10 @@ enum { RLX_DT = 0, RLX_A = 1, RLX_NSTEPS = 2, RLX_FRESH = 3, RLX_XC = 4 /* [9] c
 #define RLX_RING 9    // slots of the rings of positions / results / cells: the host runs at most 6 evaluations ahead, and what is
                       // enqueued behind a halt (it evaluates stale slots, moves nothing) must not land on configurations k, k - 1
 
+// the constant cell of a nudged elastic band (sgpr_md_neb; md_neb.inc): h (rows = vectors), its closed-form inverse (rlx_m3_inv,
+// computed once on the host), pbc
+struct NebCell { double h[9], hi[9]; int pbc[3]; };
+
 // Bin populations sit SGPR_BIN_STRIDE ints apart: one counter per 128-byte line.  Packed, the ~350 counters of a 4096-atom
 // frame are eleven lines, and the returning atomics of the binning (one per atom, device scope: they execute at the
 // memory side, one after the other per line) were most of the binning kernel's 7 us.

@@ -711,6 +711,82 @@ class SGPRModel:
         """optimizer.initialize() of the relaxation on the device: v = 0; dt, a, nsteps back to their start."""
         check(_lib.load().sgpr_md_relax_reset(self._h))
 
+    def neb_begin(self, numbers, images, cell, pbc, fmax, k=0.1, climb=False, fixed=None, **fire):
+        """A nudged elastic band under FIRE into device memory (sgpr_md_neb: ASE's default `aseneb` method, md_neb.inc;
+        workloads.neb_fire is the host twin and the definition).  images [K + 2, N, 3]: images 0 and K + 1 are the ends, never
+        evaluated or moved; the K <= 16 interior ones share numbers, cell (constant) and pbc and are evaluated by this one
+        model, one plain step each per evaluation of the band.  k: the spring constant; climb: the image of highest energy
+        climbs; fixed: held atoms ([N]) or components ([N, 3]) of every image; fire: FIRE's keywords (ASE's defaults).
+        md_run then serves the band — (scalars, halt code): rows carry E of the highest image, its index and the index of the
+        image with the largest covloss (1 ... K) in columns 0..2, overflow, largest covloss, max |G_row|^2, G.v, dt and a in
+        10..15; code 1 = the covloss gate (nothing moved), 3 = converged —; neb_state returns the images, neb_info the
+        energies and largest covlosses per image of the last call's evaluations, neb_reset re-initialises the optimizer.
+          The displacement of an atom between neighbouring images must stay well inside half a cell (workloads.neb_check_band:
+        refused at the start, the caller's to keep for the rest of the run).  One rank; no thermostat, committee, filter or
+        frame record."""
+        from .workloads import FIRE_DEFAULTS, fixed_mask
+        unknown = set(fire) - set(FIRE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"neb_begin: unknown FIRE keywords {sorted(unknown)}")
+        numbers = i32(numbers)
+        N = len(numbers)
+        R = f64(np.asarray(images, float))
+        if R.ndim != 3 or R.shape[1:] != (N, 3) or len(R) < 2:
+            raise ValueError(f"neb_begin: images is [K + 2, N, 3] for N = {N} atoms, not {R.shape}")
+        K = len(R) - 2
+        fx = fixed_mask(fixed, N)
+        md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=np.ones(N), hdt=0.0, neb=K, fixed=fx)
+        self._md = None   # (no run until sgpr_md_neb has accepted the band)
+        self.generation += 1
+        lib = _lib.load()
+        check(lib.sgpr_md_begin(self._h, N, ptr(numbers), ptr(f64(R[min(1, len(R) - 1)])), ptr(md["cell"]),
+                                ptr(i32(np.asarray(pbc, bool).astype(np.int32))), None, None, 1.0, 0.0, 0.0))
+        par = dict(FIRE_DEFAULTS)
+        par.update(fire)
+        fp = f64([par[q] for q in ("dt", "maxstep", "dtmax", "nmin", "finc", "fdec", "astart", "fa")])
+        try:
+            self._md_fix(fx)
+            check(lib.sgpr_md_neb(self._h, K, ptr(R), float(fmax), float(k), int(bool(climb)), ptr(fp)))
+        except Exception:
+            lib.sgpr_md_end(self._h)   # (a refused band leaves no half-begun run behind: _md stays None and md_run says so)
+            raise
+        md["t"] = 0
+        self._md = md
+
+    def neb_reset(self):
+        """optimizer.initialize() of the band on the device: v = 0; dt, a, nsteps back to their start."""
+        check(_lib.load().sgpr_md_neb_reset(self._h))
+
+    def neb_state(self, which=0, results=False):
+        """The K interior images of the current band (which = -1: the one evaluated before it): dict(positions [K, N, 3],
+        velocities [K, N, 3] FIRE's); with results=True — where the last md_run evaluated that band: which = 0 after a halted or
+        `final` call, -1 after one that ran through — also forces [K, N, 3], beta [K, N], energy [K], stress [K, 6]."""
+        if not (getattr(self, "_md", None) and self._md.get("neb")):
+            raise RuntimeError("neb_state: no band on this model: neb_begin first (a refused neb_begin leaves none)")
+        N, K = self._md["N"], self._md["neb"]
+        x, v = np.empty((K, N, 3)), np.empty((K, N, 3))
+        packed = np.empty((K, 4 * N + 11)) if results else None
+        check(_lib.load().sgpr_md_neb_state(self._h, ptr(x), ptr(v), ptr(packed), int(which)))
+        out = dict(positions=x, velocities=v)
+        if results:
+            stress = np.zeros((K, 6))
+            for i in range(K):
+                check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[i, 4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress[i])))
+            out.update(forces=packed[:, :3 * N].reshape(K, N, 3).copy(), beta=packed[:, 3 * N:4 * N].copy(), energy=packed[:, 4 * N].copy(),
+                       stress=stress)
+        return out
+
+    def neb_info(self):
+        """(E [done, K], covmax [done, K]): energy and largest covloss of every interior image at the evaluations of the last
+        md_run that stand (sgpr_md_neb_info)."""
+        if not (getattr(self, "_md", None) and self._md.get("neb")):
+            raise RuntimeError("neb_info: no band on this model: neb_begin first (a refused neb_begin leaves none)")
+        K, done = self._md["neb"], self._md.get("neb_done", 0)
+        out = np.zeros((done, 32))
+        if done:
+            check(_lib.load().sgpr_md_neb_info(self._h, 0, done, ptr(out)))
+        return out[:, :K].copy(), out[:, 16:16 + K].copy()
+
     def md_deviates(self, t_first, count):
         out = np.empty((int(count), self._md["N"], 3))
         check(_lib.load().sgpr_md_deviates(self._h, int(t_first), int(count), ptr(out)))
@@ -722,6 +798,8 @@ class SGPRModel:
         the last row's largest covloss reached ediff and the state is that configuration (calculator/active.py:492-499),
         2 = a neighbour capacity overflowed at evaluation `done` (repeat the call), 3 (a relaxation, relax_begin) = the last
         row's configuration has converged and is the state."""
+        if not getattr(self, "_md", None):
+            raise RuntimeError("md_run: no run on this model: md_begin, relax_begin or neb_begin first (a refused begin leaves none)")
         N = self._md["N"]
         if noise is not None:
             noise = f64(noise).reshape(-1, N, 3)
@@ -732,6 +810,8 @@ class SGPRModel:
         check(_lib.load().sgpr_md_run(self._h, int(nevals), ptr(noise), float(ediff), int(bool(final)), ptr(sc),
                                       C.addressof(done), C.addressof(code)))
         self._md["record_call"] = self._md.get("record")   # (what this call recorded: md_frames)
+        if self._md.get("neb"):   # (the rows of the band record that stand: neb_info)
+            self._md["neb_done"] = done.value
         if self._md.get("npt"):   # (where the state is now: sgpr_md_run's rules)
             t0 = self._md["t"]
             self._md["run"] = (t0, done.value)

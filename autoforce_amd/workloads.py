@@ -699,6 +699,195 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
             x = r
 
 
+# ---- the nudged elastic band under FIRE in the device's operations (neb_fire; md_neb.inc: md_neb_sums_kernel, md_neb_fire_kernel
+# and md_neb_move_kernel)
+NEB_MAX = 16   # interior images of a band (md_neb.inc)
+
+
+def _neb_mic(d, h, hi, pbc):
+    """Minimum-image form of displacements d [N, 3]: d - rint(d h^-1) h in the periodic directions (neb_mic, md_neb.inc)."""
+    n = [np.rint((d[:, 0] * hi[0][k] + d[:, 1] * hi[1][k]) + d[:, 2] * hi[2][k]) if pbc[k] else np.zeros(len(d)) for k in range(3)]
+    return np.stack([d[:, c] - ((n[0] * h[0][c] + n[1] * h[1][c]) + n[2] * h[2][c]) for c in range(3)], axis=1)
+
+
+def _neb_cell(cell, pbc):
+    h = [[float(v) for v in row] for row in np.asarray(cell, float).reshape(3, 3)]
+    pbc = [bool(b) for b in np.broadcast_to(np.asarray(pbc, bool), (3,))]
+    hi = [[0.0] * 3 for _ in range(3)]
+    if any(pbc):
+        if not _cell_volume(h) > 0.0:
+            raise ValueError("neb: the cell is singular")
+        hi = _m3_inv(h)
+    return h, hi, pbc
+
+
+def neb_check_band(images, cell, pbc):
+    """The test sgpr_md_neb applies to the initial band: the rounding of _neb_mic recovers a displacement between neighbouring
+    images only when it is well inside half a cell.  ValueError when a fractional component of a displacement, after rounding,
+    is within 1e-9 of +-1/2 (rint may go either way from one evaluation to the next), or when the displacement after rounding
+    is longer than half the smallest perpendicular width of the periodic directions (another image of the atom may be the
+    nearer one).  The user keeps neighbouring images closer than that for the whole run: only the initial band is checked."""
+    h, hi, pbc = _neb_cell(cell, pbc)
+    if not any(pbc):
+        return
+    R = np.asarray(images, float)
+    wmin = min(1.0 / np.sqrt((hi[0][k] * hi[0][k] + hi[1][k] * hi[1][k]) + hi[2][k] * hi[2][k]) for k in range(3) if pbc[k])
+    for i in range(1, len(R)):
+        o = _neb_mic(R[i] - R[i - 1], h, hi, pbc)
+        for k in range(3):
+            if pbc[k]:
+                sfr = (o[:, 0] * hi[0][k] + o[:, 1] * hi[1][k]) + o[:, 2] * hi[2][k]
+                if (np.abs(sfr) >= 0.5 - 1e-9).any():
+                    c = int(np.argmax(np.abs(sfr)))
+                    raise ValueError(f"neb: atom {c} moves half a cell (fractional {sfr[c]:.6f} along vector {k}) between images {i - 1} and {i}: "
+                                     "the minimum-image rounding cannot recover it; add images")
+        ln = np.sqrt((o[:, 0] * o[:, 0] + o[:, 1] * o[:, 1]) + o[:, 2] * o[:, 2])
+        if (ln > 0.5 * wmin).any():
+            c = int(np.argmax(ln))
+            raise ValueError(f"neb: atom {c} moves {ln[c]:.4f} between images {i - 1} and {i}, more than half the smallest perpendicular "
+                             f"width of the cell ({wmin:.4f}): the minimum-image rounding cannot recover it; add images")
+
+
+def neb_fire(calc, numbers, images, cell, pbc, evals, fmax, k=0.1, climb=False, fixed=None, species=None, reset_at=(), update=None, **fire):
+    """The nudged elastic band — ASE's default `aseneb` method (ase/neb.py, ASE 3.22, LGPL) — under FIRE (fire_relax's recurrence
+    at constant cell) in numpy around any calculator with the three getters (forces and energy through the atoms,
+    calc.get_covloss()), one call per interior image per evaluation: the host twin of the device loop (sgpr_md_neb:
+    md_neb_sums_kernel, md_neb_fire_kernel, md_neb_move_kernel; md_neb.inc) in its operations and summation order, bit for bit —
+    and, ASE not being a dependency, the definition.  images [K + 2, N, 3]: images 0 and K + 1 are the ends, never evaluated or
+    moved; all share numbers, cell (constant) and pbc.  Per evaluation n, with F_i (zero on held components) and E_i of the
+    interior images i = 1 ... K:
+        t_i = mic(R_i - R_(i-1)), i = 1 ... K + 1          per atom d - rint(d h^-1) h in the periodic directions
+        imax = the interior image of highest energy, the later one on a tie
+        tau_i = t_(i+1) (i < imax),  t_i (i > imax),  t_i + t_(i+1) (i = imax)
+        G_i = F_i - (F_i.tau_i / tau_i^2) tau_i - (((k t_i - k t_(i+1)).tau_i) / tau_i^2) tau_i
+        climb, i = imax:  G_i = F_i - 2 (F_i.tau_i / tau_i^2) tau_i
+    every dot a combination of the five sums F.t_i, F.t_(i+1), t_i.t_i, t_(i+1).t_(i+1), t_i.t_(i+1) of the image (each through
+    _device_order_sum in the library's species-sorted order; `species`: the model's table), G_i = (F_i - ca_i t_i) - cb_i t_(i+1)
+    with c = ft / tt + spr / tt (climbing: 2 ft / tt); held components of G are zero, their velocity is 0 and their coordinate
+    keeps its bits.  FIRE runs over the concatenated K N rows: G.v, G.G, v.v per image in that order, the images added in the
+    order 1 ... K; one dt, a, nsteps and maxstep scale; converged when max |G_row|^2 over all rows < fmax^2.
+      reset_at: evaluation indices in front of which the optimizer is re-initialised.  update(out): called with every
+    evaluation's dict before anything moves; a true return means the model behind `calc` has been dealt with (the covloss gate
+    of the device loop and calculate() behind it): the same band is evaluated again — the repeat is not offered to update — behind
+    optimizer.initialize() when the return is the string "reset".
+      Yields a dict per evaluation: n, energies [K], covmax [K], imax and cimg (1 ... K: highest energy, largest covloss — the
+    earlier image on a tie), gmax2, P (0 for a first evaluation), dt and a as used for the move out of this band (as they stand
+    when it has converged), converged, band [K, N, 3] (a copy), forces [K, N, 3] (the model's), G [K, N, 3], velocities [K, N, 3] (FIRE's, in front of the move)."""
+    from .ase_shim import Atoms, constraints_from_mask
+    p = dict(FIRE_DEFAULTS)
+    p.update(fire)
+    R = np.array(images, float)
+    K, N = len(R) - 2, len(numbers)
+    if K < 1 or K > NEB_MAX:
+        raise ValueError(f"neb: {K} interior images; a band has 1 to {NEB_MAX}")
+    neb_check_band(R, cell, pbc)
+    h, hi, pb = _neb_cell(cell, pbc)
+    k = float(k)
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    fx = fixed_mask(fixed, N)
+    cons = constraints_from_mask(fx)
+    v = np.zeros((K, N, 3))
+    dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
+    fmax2 = float(fmax) * float(fmax)
+
+    def dot(u, w):
+        t = u * w
+        return _device_order_sum(((t[:, 0] + t[:, 1]) + t[:, 2])[order])
+
+    n, repeat = 0, False
+    while n <= evals:
+        if n in reset_at and not repeat:
+            v = np.zeros((K, N, 3))
+            dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
+        F, E, cov = np.zeros((K, N, 3)), [0.0] * K, [0.0] * K
+        for i in range(K):
+            at = Atoms(numbers, R[i + 1].copy(), np.array(h), pbc, constraint=cons)
+            at.calc = calc
+            F[i] = np.asarray(at.get_forces(apply_constraint=False), float)
+            E[i] = float(at.get_potential_energy())
+            c = np.asarray(calc.get_covloss(), float)
+            cov[i] = float(c.max()) if c.size else 0.0
+        Fm = F if fx is None else np.where(fx[None], 0.0, F)
+        t = [_neb_mic(R[i] - R[i - 1], h, hi, pb) for i in range(1, K + 2)]       # t[i - 1] = t_i
+        imax = 0
+        for i in range(1, K):
+            if E[i] >= E[imax]:
+                imax = i
+        cimg = 0
+        for i in range(1, K):
+            if cov[i] > cov[cimg]:
+                cimg = i
+        G = np.zeros((K, N, 3))
+        for i in range(K):
+            ti, tn = t[i], t[i + 1]
+            s = [dot(Fm[i], ti), dot(Fm[i], tn), dot(ti, ti), dot(tn, tn), dot(ti, tn)]
+            if i < imax:
+                ft, tt, spr = s[1], s[3], k * s[4] - k * s[3]
+            elif i > imax:
+                ft, tt, spr = s[0], s[2], k * s[2] - k * s[4]
+            else:
+                ft, tt, spr = s[0] + s[1], (s[2] + 2.0 * s[4]) + s[3], k * (s[2] + s[4]) - k * (s[4] + s[3])
+            c = (2.0 * ft) / tt if (climb and i == imax) else ft / tt + spr / tt
+            ca, cb = (0.0 if i < imax else c), (0.0 if i > imax else c)
+            G[i] = (Fm[i] - ca * ti) - cb * tn
+        if fx is not None:
+            G = np.where(fx[None], 0.0, G)
+        g2 = G * G
+        g2 = (g2[..., 0] + g2[..., 1]) + g2[..., 2]
+        gmax2 = max(0.0, float(g2.max()))
+        Gv = GG = vv = 0.0
+        for i in range(K):
+            Gv = Gv + dot(G[i], v[i])
+            GG = GG + dot(G[i], G[i])
+            vv = vv + dot(v[i], v[i])
+        P = 0.0 if fresh else Gv
+        out = dict(n=n, energies=np.array(E), covmax=np.array(cov), imax=imax + 1, cimg=cimg + 1, gmax2=gmax2, P=P, band=R[1:-1].copy(),
+                   forces=F, G=G, velocities=v.copy(), dt=dt, a=a, converged=False)
+        if update is not None and not repeat:
+            what = update(out)
+            if what:
+                if what == "reset":
+                    v = np.zeros((K, N, 3))
+                    dt, a, nsteps, fresh = float(p["dt"]), float(p["astart"]), 0, True
+                repeat = True
+                continue
+        repeat = False
+        if gmax2 < fmax2:
+            out.update(converged=True)
+            yield out
+            return
+        if fresh:
+            alpha, beta = 0.0, dt
+            fresh = False
+            vv = 0.0
+        elif P > 0.0:
+            alpha = 1.0 - a
+            gamma = (a * np.sqrt(vv)) / np.sqrt(GG)
+            if nsteps > p["nmin"]:
+                dt = min(dt * p["finc"], p["dtmax"])
+                a = a * p["fa"]
+            nsteps += 1
+            beta = gamma + dt
+        else:
+            alpha, a, nsteps = 0.0, float(p["astart"]), 0
+            dt = dt * p["fdec"]
+            beta = dt
+            vv = 0.0
+        nv2 = ((alpha * alpha) * vv + (2.0 * (alpha * beta)) * P) + (beta * beta) * GG
+        drn = dt * float(np.sqrt(nv2))
+        cd = dt * (p["maxstep"] / drn) if drn > p["maxstep"] else dt
+        out.update(dt=dt, a=a)
+        yield out
+        v = alpha * v + beta * G
+        if fx is None:
+            R[1:-1] = R[1:-1] + cd * v
+        else:   # (selected, not computed)
+            v = np.where(fx[None], 0.0, v)
+            R[1:-1] = np.where(fx[None], R[1:-1], R[1:-1] + cd * v)
+        n += 1
+
+
 def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None,
                         ediff=0.0, chunk=256, on_halt=None, device_rng=False, fixed=None):
     """langevin_nvt with the state in device memory (SGPRModel.md_begin / md_run): same scheme, same random stream

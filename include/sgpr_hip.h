@@ -412,6 +412,44 @@ int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out);
  * sgpr_md_relax_reset  optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (between two sgpr_md_run calls). */
 int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6);
 int sgpr_md_relax_reset(sgpr_model *h);
+/* Nudged elastic band with FIRE inside the device loop (md_neb.inc; the reference's cl/neb.py drives ase.neb.NEB under an
+ * ase.optimize optimizer and crosses into the calculator once per image per step).  ASE's default `aseneb` method, restated:
+ * images 0 ... K + 1 share numbers, cell (constant) and pbc; the ends never move and are never evaluated; with the model's
+ * forces F_i (zero on held components) and energies E_i of the interior images i = 1 ... K and one spring constant k
+ *     t_i = mic(R_i - R_(i-1)),  i = 1 ... K + 1      per atom d - rint(d h^-1) h in the periodic directions
+ *     imax = the interior image of highest energy (the later one on a tie)
+ *     tau_i = t_(i+1) for i < imax,  t_i for i > imax,  t_i + t_(i+1) for i = imax
+ *     G_i = F_i - (F_i.tau_i / tau_i^2) tau_i - (((k t_i - k t_(i+1)).tau_i) / tau_i^2) tau_i
+ *     climb, i = imax:  G_i = F_i - 2 (F_i.tau_i / tau_i^2) tau_i
+ * and FIRE (sgpr_md_relax's recurrence at constant cell) on the concatenated K N rows: ONE dt, a, nsteps and step limit for the
+ * band, G.v, G.G, v.v summed over all interior images, converged when max over all K N rows of |G_row|^2 < fmax^2.
+ * sgpr_md_neb        after sgpr_md_begin (positions: any interior image — they bind the system; masses, velocities, dt, friction
+ *                    and kT are ignored) and, if used, sgpr_md_fix (one mask for every image; a held component's velocity is 0
+ *                    and its coordinate keeps its bits), before the first sgpr_md_run.  positions[K + 2][N][3] caller atom order;
+ *                    fire[8] as in sgpr_md_relax (NULL: ASE's defaults).  SGPR_E_INVALID: K < 1 or K > 16, a thermostat or
+ *                    barostat, a run that has started, fmax <= 0, k_spring <= 0, a singular cell with a periodic direction, and an
+ *                    initial band the rounding cannot recover: a fractional component of a displacement between neighbouring
+ *                    images, after rounding, within 1e-9 of +-1/2, or such a displacement longer than half the smallest
+ *                    perpendicular width of the cell — the caller keeps neighbouring images closer than that for the whole run
+ *                    (only the initial band is checked).  SGPR_E_UNSUPPORTED: more than one rank, a committee, a filter, a
+ *                    relaxation (sgpr_md_relax), an armed frame record.
+ * sgpr_md_run        evaluates the band (K plain steps of this handle, each rebuilding its candidate lists) and moves it;
+ *                    halt code 1: the largest covloss over all images reached ediff (nothing moved), 2: a capacity overflowed at
+ *                    some image, 3: converged.  scalars[.][0] = E of imax, [1] = imax, [2] = the image that carried the largest
+ *                    covloss (both 1 ... K), [10] overflow, [11] largest covloss, [12] max |G_row|^2, [13] G.v, [14] dt, [15] a
+ *                    as used for the move out of the evaluation; the others zero.
+ * sgpr_md_neb_reset  optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (between two sgpr_md_run calls).
+ * sgpr_md_neb_state  the K interior images, caller atom order: positions[K][N][3] of the current band (which = 0) or the one
+ *                    before it (-1), velocities[K][N][3] (FIRE's), packed[K][4N + 11] the images' results where the last
+ *                    sgpr_md_run evaluated that band; any of them NULL.  sgpr_md_state refuses a band.
+ * sgpr_md_neb_info   out[count][32] = E[16] | covmax[16] per evaluation first ... first + count - 1 of the last sgpr_md_run
+ *                    (0 = its first) among those that stand; kept on the device during the call, fetched behind its one wait.
+ * sgpr_md_record, sgpr_md_committee, sgpr_md_filter, sgpr_md_thermostat, sgpr_md_relax and sgpr_md_fix behind sgpr_md_neb are
+ * refused. */
+int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double fmax, double k_spring, int climb, const double *fire);
+int sgpr_md_neb_reset(sgpr_model *h);
+int sgpr_md_neb_state(sgpr_model *h, double *positions, double *velocities, double *packed, int which);
+int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out);
 /* Held atoms and components (after sgpr_md_begin; before sgpr_md_thermostat, sgpr_md_relax and the first sgpr_md_run):
  * fixed3N[N][3] in caller atom order, nonzero = that Cartesian component of that atom is held — all three of an atom for
  * ase.constraints.FixAtoms, the chosen ones for FixCartesian.  NULL or all zeros: nothing is held, and the run launches what a
