@@ -92,6 +92,9 @@ SIGNATURES = {
     "sgpr_md_filter": (C.c_int, [_vp, _dbl, _vp, _vp]),
     "sgpr_md_filter_push": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_md_filter_state": (C.c_int, [_vp, _vp, _vp]),
+    "sgpr_md_meta": (C.c_int, [_vp, C.c_int, _vp, _vp, _dbl, _dbl, C.c_int, _i64, _i64, _vp, _vp]),
+    "sgpr_md_meta_info": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "sgpr_md_meta_hills": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "sgpr_sync_check": (C.c_int, [_vp, _vp]),
     "sgpr_comm_unique_id": (C.c_int, [_vp]),
     "sgpr_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

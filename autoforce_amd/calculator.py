@@ -471,6 +471,15 @@ class ActiveCalculator(Calculator):
             energies, kwargs = self.meta(self)
             if energies is not None:
                 meta = f"meta: {float(np.sum(energies))}"
+                if hasattr(self.meta, "bias"):
+                    # a meta.Meta: the bias acts — energy, forces and stress are added to the results as the reference's
+                    # reduce(op="+=") does (active.py:510-516, :557-580); any other callable is logged only, as before
+                    V, Fb, Sb = self.meta._last
+                    self.results["energy"] = np.asarray(self.results["energy"] + V)
+                    self.results["forces"] = self.results["forces"] + Fb
+                    self.results["stress"] = self.results["stress"] + Sb
+                    self._maxf = None
+                    energy = self.results["energy"]
         if (self.logfile or self.stdout) and self.rank == 0:  # (nobody reads the line otherwise: skip the kinetic energy)
             try:
                 temperature = self.atoms.get_temperature()
@@ -487,13 +496,20 @@ class ActiveCalculator(Calculator):
     # ------------------------------------------------------------------ MD with the state in device memory
     def md_on_device_ok(self):
         """The device loop replaces calculate() only where calculate() does nothing the device cannot see: a
-        single process, no periodic test, no meta-dynamics hook, no force veto, one bead."""
+        single process, no periodic test, no force veto, one bead, and no meta-dynamics hook other than a meta.Meta over the
+        built-in collective variables (device_spec(): run_md attaches it to the loop, SGPRModel.md_meta)."""
         eng = self.engine
         world = self._dist()[1]
         # (several ranks: only over the library's own exchange — every rank then integrates all atoms from the summed
         # forces and halts at the same step, sgpr_md_run)
         return (hasattr(eng, "md_run") and (world == 1 or getattr(eng, "peer_world", 1) == world) and not self.test
-                and self.meta is None and "forces" not in self._veto and self.nbeads == 1 and eng.m > 0 and eng.mu is not None)
+                and (self.meta is None or self._meta_spec() is not None) and "forces" not in self._veto and self.nbeads == 1 and eng.m > 0 and eng.mu is not None)
+
+    def _meta_spec(self):
+        """The components of self.meta as the device loop takes them, or None (no meta, a plain callable, a colvar that is not
+        built in)."""
+        spec = getattr(self.meta, "device_spec", None)
+        return spec() if spec is not None and hasattr(self.engine, "md_meta") else None
 
     def _md_attach(self, eng):
         """Hook of run_md, called right after eng.md_begin(...): whatever else the device loop must evaluate beside the live
@@ -578,7 +594,13 @@ class ActiveCalculator(Calculator):
         jump self.deltas that an update's calculate() publishes is pushed into the device's accumulators (SGPRModel.
         md_filter_push) before the halted configuration is evaluated again; the integrator sees the filtered forces (and, with a
         barostat, stress), self.results and the log stay the model's.  Host loops: the twins' ml_filter=.  With a filter the
-        device loop runs on one rank and without a committee.  None: no filter, today's run."""
+        device loop runs on one rank and without a committee.  None: no filter, today's run.
+        self.meta: a meta.Meta over the built-in collective variables (device_spec()) is attached to the loop behind md_begin
+        (SGPRModel.md_meta: the hills it holds stand from the start, room for every deposit of the run); after every batch the
+        new hill rows are appended to meta.hist and mirrored into the Meta — calculate() at a halt adds the same bias — and
+        `meta: V` goes on the log lines — with pace > 1 on the lines of the depositing configurations only: the device keeps V
+        per hill row, and a run goes on from a Meta only at a multiple of its pace (ValueError otherwise).  With a barostat, a committee or several ranks, and for any other meta, the host loops
+        around calculate(), which adds a Meta's bias itself; there meta.update() runs once per configuration."""
         from .ase_shim import kB
         from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
@@ -627,7 +649,8 @@ class ActiveCalculator(Calculator):
 
         def on_device():
             return (self.md_on_device_ok() and not (committee and (npt or fx is not None))
-                    and not (flt is not None and (committee or self._dist()[1] > 1)))
+                    and not (flt is not None and (committee or self._dist()[1] > 1))
+                    and not (self.meta is not None and (npt or committee or self._dist()[1] > 1)))
         first_on_host = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -643,6 +666,8 @@ class ActiveCalculator(Calculator):
                         nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold, **filt) if nh else
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold, **filt))
                 for st, E, T, _, p, v, *rest in loop:
+                    if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
+                        self.meta.update()
                     put(dict(positions=p, velocities=v, cell=rest[0] if npt else None), "velocities")
                     if flt is not None:   # (the accumulators as this configuration found them: what a run that goes on from it takes)
                         flt.f, flt.s = rest[-1]
@@ -657,6 +682,20 @@ class ActiveCalculator(Calculator):
         # and is evaluated once more on the device, whatever its covloss, to move on from it)
         done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
         attached = self._md_attach(eng)
+        meta = self.meta
+        if meta is not None:
+            # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
+            # every batch the new rows are mirrored into the Meta (meta.hist, and calculate() at a halt sees the same bias)
+            meta.species = list(eng.species)   # (the twin's mean of a posvar in the device's order)
+            if meta.pace > 1 and meta.n % meta.pace:
+                # (the device counts configurations from 0 in every run: a run that goes on from a Meta in the middle of its pace
+                # would deposit on another cadence than the Meta's own update())
+                raise ValueError(f"run_md: the Meta has seen {meta.n} configurations, no multiple of its pace {meta.pace}: the device loop "
+                                 "deposits configuration n of the run when n % pace == 0")
+            hills0 = meta.hills_array()
+            eng.md_meta(self._meta_spec(), meta.sigma, meta.w, tem=meta.tem, pace=meta.pace, hills=hills0 if len(hills0) else None,
+                        capacity=len(hills0) + (steps + 1) // meta.pace + 2)
+            meta_seen, meta_n0 = len(hills0), meta.n
         # (a run with members attached records no frames: batches end at the multiples of sync_every)
         rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1 and not attached)
         if rec:   # (positions and the velocities the integrator holds; a batch of at most rec_max frames)
@@ -681,6 +720,15 @@ class ActiveCalculator(Calculator):
             accepted = len(sc) - 1 if code == 1 else len(sc)
             share = (time.time() - t_run) / max(accepted, 1)
             lines, out, counts, step_now = [], [], [], self.step
+            meta_V = {}
+            if meta is not None:   # the rows of the configurations below the current one (a halted one deposits when it is repeated)
+                info = eng.md_meta_info()   # (the run's last configuration stands evaluated: its own row too)
+                below = info["held"] if (final and code == 0) else info["below"]
+                cvn, Vn = eng.md_meta_hills(meta_seen, below - meta_seen)
+                first_dep = -(-done // meta.pace) * meta.pace
+                meta_V = {first_dep + k * meta.pace: float(v) for k, v in enumerate(Vn)}
+                meta.absorb(cvn, meta_n0 + done + accepted)
+                meta_seen = below
             for r in sc[:accepted]:
                 upd, wall = False, share
                 if skip_gate:      # (the configuration calculate() has just dealt with, evaluated again with the new model:
@@ -689,7 +737,8 @@ class ActiveCalculator(Calculator):
                     # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a
                     # moving cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
                     ke_line = r[13] if (not npt or ke_before is None) else ke_before
-                    lines.append((step_now, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]), "")))
+                    lines.append((step_now, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]),
+                                                                 f"meta: {meta_V[done]}" if done in meta_V else "")))
                     step_now += 1
                 ke_before = r[12]
                 out.append((done, float(r[0]), float(r[12] / (dof * kB)), upd, wall))
@@ -776,7 +825,7 @@ class ActiveCalculator(Calculator):
             # (a committee with members — BCMActiveCalculator — relaxes through the host loop around calculate(): the device
             # relaxation evaluates one model)
             return (self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "relax_begin")
-                    and not getattr(self, "model_dict", None))
+                    and not getattr(self, "model_dict", None) and self.meta is None)   # (a bias: the host loop around calculate())
         first_on_host = self._needs_seed() or not device_ok()
         if first_on_host:
             atoms.calc = self
@@ -896,7 +945,7 @@ class ActiveCalculator(Calculator):
         R = np.array([np.asarray(im.positions, float) for im in images])
 
         def device_ok():
-            return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "neb_begin")
+            return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "neb_begin") and self.meta is None
         if self._needs_seed() or not device_ok():
             images[1].calc = self
             images[1].get_forces()

@@ -217,6 +217,17 @@ struct MdState {
     DevBuf<double> filt_f, filt_s, filt_in;   // [4][N][3], [4][6], [N][3] a push's caller-order upload
     DevBuf<int> filt_perm;                    // [N] sorted -> caller
     double filt_s_host[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // metadynamics (sgpr_md_meta, md_meta.inc): the hills in rows indexed by configuration — meta_pre rows uploaded at the attach,
+    // which took place at configuration meta_base; then one per configuration n with n % meta_pace == 0
+    bool meta = false, meta_fresh = false;   // (fresh: attached, no sgpr_md_run since)
+    MetaPar mp = {};
+    int meta_pace = 1;
+    long long meta_base = 0, meta_pre = 0, meta_cap = 0;
+    DevBuf<double> meta_centre, meta_rows;   // [cap][D] centres (room for 6), [cap][7] CV | V
+    DevBuf<int> meta_key;                    // [cap][D] super-block keys (room for 6)
+    DevBuf<unsigned char> meta_sel;          // [ncomp][N] posvar: the atoms of the mean, sorted order
+    static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
+    long long meta_slot(long long n) const { return meta_pre + meta_dep(n, meta_pace) - meta_dep(meta_base, meta_pace); }
     // the frame record (sgpr_md_record, md_record.inc): every rec_every-th configuration of a call, copied out behind its
     // evaluation in caller atom order — rec_x always, rec_v / rec_p by the bits of rec_what.  rec_call_*: what the LAST
     // sgpr_md_run recorded (sgpr_md_frames serves that call: its first trajectory index, its settings, the frames that stand)
@@ -1109,6 +1120,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_bcm.inc"
 #include "md_neb.inc"
 #include "md_record.inc"
+#include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
 // position — read from the next frame (MODE 1) or integrated (MODE 2) —, bins it there and takes part in the rebuild
@@ -1646,6 +1658,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.npt_ring.release(); m.Q.release(); m.cells_d.release();
         m.fixed.release();
         m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
+        m.meta_centre.release(); m.meta_rows.release(); m.meta_key.release(); m.meta_sel.release();
         m.bcm_P.release(); m.bcm_x.release(); m.bcm_info_d.release();
         m.nb_X.release(); m.nb_V.release(); m.nb_P.release(); m.nb_ends.release(); m.nb_sums.release(); m.nb_coef.release(); m.nb_info_d.release(); m.nb_par.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
@@ -2717,6 +2730,18 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
     if (nx && nx->mode == 2 && nx->md.filt_cur && !(fuse && gather))
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
+    if (nx && nx->mode == 2 && h->md.meta) {
+        // the bias of this configuration (sgpr_md_meta), behind the reverse pass's own sums and in front of the kernel that reads them
+        const MdState &m = h->md;
+        if (!(fuse && gather))
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
+                                            "and sharded frames take the host loop around calculate()");
+        const long long n = nx->md.t_index;
+        hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
+                           m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
+                           h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
+        stamp(h, "md_meta", st);
+    }
     const bool xp = !gather && (px || shard_next);
     const size_t xlen = peer_xlen(N, h->world);
     if (xp && h->d_xpacked.n < xlen + 1 && h->d_xpacked.alloc(xlen + 1)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (exchange buffer)");

@@ -71,6 +71,7 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
     m.bcm.clear(); m.bcm_info.clear();
     m.filter = false; m.shrink = 0.0;
+    m.meta = false;
     const double c2 = sqrt(1.0 - m.c1 * m.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
@@ -178,6 +179,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell");
+    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
     if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.n_fixed);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
@@ -351,6 +353,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
     if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased relaxation");
     if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
@@ -724,6 +727,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_committee: call sgpr_md_begin first");
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
     if (K == 0 || !members) { m.bcm.clear(); m.bcm_info.clear(); return SGPR_OK; }
+    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a bias (sgpr_md_meta), which the committee's loop does not apply; the host loop around calculate() serves it");
     if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
     if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
     if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
@@ -900,6 +904,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has started");
     if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has a thermostat or a barostat");
     if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased band");
     if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
     if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
@@ -1106,6 +1111,19 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     const size_t plen = (size_t)sgpr_packed_len(N);
     *evals_done = 0;
     if (halt_code) *halt_code = 0;
+    if (m.meta) {
+        // the bias rides in the single-rank gather form of the fused last kernel: what cannot take that form is refused here, before
+        // anything is enqueued (enqueue_step keeps its own check for what only a checked pass finds out: lists beyond the gather form)
+        if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only (one rank, no graph "
+                        "replay, no side-stream fork, a skin > 0): the host loop around calculate() serves this run");
+        // the last configuration of the call that deposits a hill must find its row
+        const long long nd = (m.t + nevals - 1) / m.meta_pace * m.meta_pace;
+        if (nd >= m.t && m.meta_slot(nd) >= m.meta_cap)
+            return fail(SGPR_E_INVALID, "sgpr_md_run: %d evaluations from configuration %lld deposit hills up to row %lld; the bias holds %lld "
+                        "(sgpr_md_meta again, with a larger capacity and the hills of sgpr_md_meta_hills)", nevals, m.t, m.meta_slot(nd), m.meta_cap);
+        m.meta_fresh = false;
+    }
     m.started = true;
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, m.npt)) return rp;   // (the cell record: a moving cell only)
@@ -1477,10 +1495,148 @@ extern "C" int sgpr_md_filter_state(sgpr_model *h, double *f, double *s)
     return SGPR_OK;
 }
 
+// ---- metadynamics (sgpr_md_meta; md_meta.inc has the scheme, workloads.meta_bias is the host twin) ----
+// The bias of the reference's calculator/meta.py for the run begun by sgpr_md_begin, attached between any two sgpr_md_run calls
+// (the first included).  cvs[ncomp][3]: the components of the collective variable in the order they are concatenated — kind 0:
+// distance(i = cvs[1], j = cvs[2]); kind 1: posvar(index = cvs[1], select = cvs[2]: an atomic number, or -1 for all atoms) —
+// atoms in caller order; D = sum of their dimensions (1 | 3) <= 6.  sigma[D]; w; kT > 0: well-tempered with gamma = 1 / kT, 0:
+// plain; pace >= 1: configuration n deposits when n % pace == 0; capacity: rows of hills; nhills rows hills_cv[nhills][D] (and
+// hills_V[nhills] or NULL: zeros) are there from the start — a restart, or the hills of sgpr_md_meta_hills when a run needs a
+// larger capacity: they stand for the deposits of the configurations below the current one.  ncomp = 0 detaches.
+extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const double *sigma, double w, double kT, int pace, int64_t capacity,
+                            int64_t nhills, const double *hills_cv, const double *hills_V)
+{
+#pragma clang fp contract(off)
+    if (!h || ncomp < 0) return fail(SGPR_E_INVALID, "sgpr_md_meta: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_meta: call sgpr_md_begin first");
+    if (ncomp == 0) { m.meta = false; return SGPR_OK; }
+    if (!cvs || !sigma || ncomp > META_MAXC) return fail(SGPR_E_INVALID, "sgpr_md_meta: 1 to %d components, their list and sigma", META_MAXC);
+    if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a barostat (sgpr_md_barostat); the bias runs at constant cell, the host loop around calculate() serves a biased NPT run");
+    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a relaxation (sgpr_md_relax); the bias serves dynamics only, the host loop around calculate() serves a biased relaxation");
+    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a nudged elastic band (sgpr_md_neb); the bias serves dynamics only, the host loop around calculate() serves a biased band");
+    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a committee (sgpr_md_committee), whose loop does not apply a bias; the host loop around calculate() serves it");
+    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run was begun on %d ranks; the bias runs on one, the host loop around calculate() serves sharded runs", m.world);
+    if (pace < 1 || capacity < 1 || capacity > (1 << 28) || nhills < 0 || nhills > capacity || (nhills > 0 && !hills_cv))
+        return fail(SGPR_E_INVALID, "sgpr_md_meta: pace >= 1, 1 <= capacity <= 2^28, 0 <= nhills <= capacity");
+    if (!(w == w) || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_meta: w a number, kT >= 0");
+    const int N = m.N;
+    MetaPar p = {};
+    std::vector<int> inv(N);
+    for (int i = 0; i < N; i++) inv[m.perm[i]] = i;
+    std::vector<unsigned char> sel((size_t)ncomp * N, 0);
+    int D = 0;
+    for (int q = 0; q < ncomp; q++) {
+        const int kind = cvs[3 * q], a = cvs[3 * q + 1], b = cvs[3 * q + 2];
+        if (kind != 0 && kind != 1) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: kind 0 (distance) or 1 (posvar)", q);
+        if (a < 0 || a >= N) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: atom %d of %d", q, a, N);
+        p.kind[q] = kind; p.ia[q] = inv[a]; p.nsel[q] = 1.0;
+        if (kind == 0) {
+            if (b < 0 || b >= N || b == a) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: distance between atoms %d and %d of %d", q, a, b, N);
+            p.ib[q] = inv[b];
+            D += 1;
+        } else {
+            int n = 0;
+            for (int i = 0; i < N; i++) {
+                const int cidx = m.perm[i];
+                if (b >= 0 && m.numbers[cidx] != b) continue;
+                n++;
+                if (cidx != a) sel[(size_t)q * N + i] = 1;
+            }
+            if (n == 0) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: no atom of species %d (the mean of nothing)", q, b);
+            p.nsel[q] = (double)n;
+            D += 3;
+        }
+    }
+    if (D > META_MAXD) return fail(SGPR_E_INVALID, "sgpr_md_meta: %d dimensions; at most %d", D, META_MAXD);
+    p.D = D; p.ncomp = ncomp; p.wt = kT > 0.0 ? 1 : 0;
+    p.w = w; p.gamma = kT > 0.0 ? 1.0 / kT : 0.0;
+    p.norm = 1.0;
+    const double sq2pi = sqrt(2.0 * M_PI);
+    for (int d = 0; d < META_MAXD; d++) {
+        p.sigma[d] = d < D ? sigma[d] : 1.0;
+        if (!(p.sigma[d] > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_meta: sigma[%d] > 0", d);
+        p.sigma5[d] = 5.0 * p.sigma[d];
+        if (d < D) p.norm = p.norm * sq2pi;
+    }
+    std::vector<double> ce((size_t)D * nhills, 0.0), rows((size_t)(META_MAXD + 1) * nhills, 0.0);
+    std::vector<int> ke((size_t)D * nhills, 0);   // (centres and keys in rows of D)
+    for (int64_t r = 0; r < nhills; r++)
+        for (int d = 0; d < D; d++) {
+            const double c = hills_cv[(size_t)D * r + d];
+            if (!(c == c)) return fail(SGPR_E_INVALID, "sgpr_md_meta: hill %lld, dimension %d is not a number", (long long)r, d);
+            const double kb = std::min(std::max(floor(c / p.sigma5[d]), -1e9), 1e9);   // (clamped as md_meta_kernel clamps the live key)
+            ce[(size_t)D * r + d] = (floor(c / p.sigma[d]) + 0.5) * p.sigma[d];
+            ke[(size_t)D * r + d] = (int)kb;
+            rows[(size_t)(META_MAXD + 1) * r + d] = c;
+            rows[(size_t)(META_MAXD + 1) * r + META_MAXD] = hills_V ? hills_V[r] : 0.0;
+        }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t cap = (size_t)capacity;
+    if (m.meta_centre.alloc(cap * META_MAXD) || m.meta_rows.alloc(cap * (META_MAXD + 1)) || m.meta_key.alloc(cap * META_MAXD) ||
+        m.meta_sel.alloc((size_t)ncomp * N))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_meta: device allocation failed");
+    if (nhills) {
+        HIPCHK(hipMemcpy(m.meta_centre.p, ce.data(), sizeof(double) * ce.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.meta_rows.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.meta_key.p, ke.data(), sizeof(int) * ke.size(), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(m.meta_sel.p, sel.data(), sel.size(), hipMemcpyHostToDevice));
+    m.mp = p; m.meta_pace = pace; m.meta_base = m.t; m.meta_pre = nhills; m.meta_cap = capacity;
+    m.meta = true; m.meta_fresh = true;
+    return SGPR_OK;
+}
+
+// D; `below`: the hills below the current configuration — the rows uploaded at the attach and the deposits of the configurations
+// before it: what sgpr_md_meta takes to go on from here —; `held`: those and the current configuration's own row where the last
+// sgpr_md_run evaluated it (a halted or `final` call): what sgpr_md_meta_hills serves; the capacity.  Any of them NULL.
+// (meta_fresh: no sgpr_md_run since the attach — the current configuration's own row is not in these buffers, whatever an earlier
+// call evaluated)
+static long long md_meta_held(const MdState &m) { return m.meta_slot(m.t) + ((m.evaluated && !m.meta_fresh && m.t % m.meta_pace == 0) ? 1 : 0); }
+extern "C" int sgpr_md_meta_info(sgpr_model *h, int *D, int64_t *below, int64_t *held, int64_t *capacity)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_meta_info: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || !m.meta) return fail(SGPR_E_INVALID, "sgpr_md_meta_info: call sgpr_md_begin and sgpr_md_meta first");
+    if (D) *D = m.mp.D;
+    if (below) *below = m.meta_slot(m.t);
+    if (held) *held = md_meta_held(m);
+    if (capacity) *capacity = m.meta_cap;
+    return SGPR_OK;
+}
+
+// Rows first ... first + count - 1 of the hills that stand: cv[count][D] where each was deposited and V[count], the bias its
+// configuration saw (either NULL: not wanted).
+extern "C" int sgpr_md_meta_hills(sgpr_model *h, int64_t first, int64_t count, double *cv, double *V)
+{
+    if (!h || first < 0 || count <= 0) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || !m.meta) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: call sgpr_md_begin and sgpr_md_meta first");
+    const long long held = md_meta_held(m);
+    if (first + count > held) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: rows %lld ... %lld asked for, %lld stand", (long long)first, (long long)(first + count - 1), held);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int D = m.mp.D;
+    std::vector<double> rows((size_t)(META_MAXD + 1) * count);
+    HIPCHK(hipMemcpy(rows.data(), m.meta_rows.p + (size_t)(META_MAXD + 1) * first, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < count; r++) {
+        if (cv) for (int d = 0; d < D; d++) cv[(size_t)D * r + d] = rows[(size_t)(META_MAXD + 1) * r + d];
+        if (V) V[r] = rows[(size_t)(META_MAXD + 1) * r + META_MAXD];
+    }
+    return SGPR_OK;
+}
+
 extern "C" int sgpr_md_end(sgpr_model *h)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_end: bad arguments");
     h->md.active = false;
+    if (h->md.meta || h->md.meta_rows.p) {   // (the hills of a bias are the run's: given back with it)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        h->md.meta = false;
+        h->md.meta_centre.release(); h->md.meta_rows.release(); h->md.meta_key.release(); h->md.meta_sel.release();
+    }
     h->md.bcm.clear(); h->md.bcm_info.clear();   // (the borrowed members are let go)
     return SGPR_OK;
 }

@@ -108,6 +108,22 @@ struct NptParams {
     int pbc[3];
 };
 
+// metadynamics inside the device MD loop (sgpr_md_meta; md_meta.inc has the scheme)
+#define META_MAXD 6
+#define META_MAXC 4
+#define META_TRIP 1024   // hills per trip of the strided sum: four partial sums per thread
+
+struct MetaPar {
+    int D, ncomp, wt, pad_;
+    int kind[META_MAXC];            // 0: distance, 1: posvar
+    int ia[META_MAXC];              // sorted index of atom i (distance) / of the index atom (posvar)
+    int ib[META_MAXC];              // sorted index of atom j (distance)
+    double nsel[META_MAXC];         // posvar: n = |sel|
+    double sigma[META_MAXD];
+    double sigma5[META_MAXD];       // 5 sigma, a product
+    double w, gamma, norm;          // height, 1 / kT (well-tempered), sqrt(2 pi)^D as a product of D factors
+};
+
 // FIRE relaxation on the device (sgpr_md_relax; md_relax.inc has the scheme)
 struct RelaxParams {
     double fmax2;                                        // fmax^2

@@ -666,6 +666,72 @@ class SGPRModel:
         check(_lib.load().sgpr_md_filter_state(self._h, ptr(f), ptr(s_)))
         return f, s_
 
+    META_KINDS = {"distance": 0, "posvar": 1}
+
+    def md_meta(self, cvs, sigma, w, tem=None, pace=1, hills=None, capacity=None):
+        """Metadynamics for the run begun by md_begin (sgpr_md_meta; md_meta.inc has the scheme, workloads.meta_bias is the host
+        twin and the definition; the reference's calculator/meta.py): from the next md_run on every configuration is evaluated
+        with the bias V = w kde(cv) — tem (K): the well-tempered log(1 + w kde gamma) / gamma, gamma = 1 / (kB tem) — of the
+        hills deposited by the configurations before it, and configuration n deposits its own when n % pace == 0.  Energy,
+        forces and stress of the rows, md_state and the frame record include the bias; the covloss gate does not see it.
+          cvs: the components of the collective variable in the order they are concatenated, ("distance", i, j) = |x_j - x_i|
+        and ("posvar", index, select) = x_index - (1/n) sum of the other atoms of species `select` (None: all atoms; n counts
+        the index atom where it is among them) — at most 4 components and 6 dimensions, raw coordinates, no minimum image.
+        sigma: a scalar or [D].  hills: [H, D] CV values (or (cv [H, D], V [H])) that stand from the start — a restart, or
+        md_meta_hills() of this run when it needs more room; capacity: rows of hills (default: those given + 4096) — md_run
+        refuses a call that would pass it before it enqueues anything, md_meta again with the rows of md_meta_hills(count=
+        md_meta_info()["below"]) and a larger capacity lets the run go on with the same bits.  cvs = None or (): no bias.
+        Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter= and
+        md_record; a barostat, a relaxation, a band, a committee and several ranks: NotImplementedError (the host loop
+        around calculate() serves them)."""
+        lib = _lib.load()
+        if not cvs:
+            check(lib.sgpr_md_meta(self._h, 0, None, None, 0.0, 0.0, 1, 1, 0, None, None))
+            self._md.pop("meta_D", None)
+            return
+        from .ase_shim import kB
+        spec, D = [], 0
+        for c in cvs:
+            kind = self.META_KINDS[c[0]]
+            spec.append((kind, int(c[1]), int(c[2]) if kind == 0 else (-1 if c[2] is None else int(c[2]))))
+            D += 1 if kind == 0 else 3
+        sg = f64(np.broadcast_to(np.asarray(sigma, float).reshape(-1), (D,)) if np.size(sigma) == 1 else np.asarray(sigma, float).reshape(-1))
+        if len(sg) != D:
+            raise ValueError(f"md_meta: sigma is a scalar or one value per dimension ({D}), not {len(sg)}")
+        hv = None
+        if isinstance(hills, tuple):
+            hills, hv = hills
+        hc = np.zeros((0, D)) if hills is None else f64(np.asarray(hills, float)).reshape(-1, D)
+        hv = None if hv is None else f64(np.asarray(hv, float)).reshape(len(hc))
+        cap = len(hc) + 4096 if capacity is None else int(capacity)
+        try:
+            check(lib.sgpr_md_meta(self._h, len(spec), ptr(i32(np.asarray(spec, np.int32).reshape(-1))), ptr(sg), float(w),
+                                   0.0 if tem is None else float(kB * tem), int(pace), cap, len(hc), ptr(hc) if len(hc) else None, ptr(hv)))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        self._md["meta_D"] = D
+
+    def md_meta_info(self):
+        """dict(D, below, held, capacity) of the run's bias (sgpr_md_meta_info): below = the hills below the current
+        configuration (what md_meta(hills=) takes to go on from here), held = those and the current configuration's own row
+        after a halted or `final` md_run (what md_meta_hills serves)."""
+        D = C.c_int(0)
+        below, held, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(_lib.load().sgpr_md_meta_info(self._h, C.addressof(D), C.addressof(below), C.addressof(held), C.addressof(cap)))
+        return dict(D=D.value, below=below.value, held=held.value, capacity=cap.value)
+
+    def md_meta_hills(self, first=0, count=None):
+        """(cv [count, D], V [count]): rows first ... first + count - 1 of the hills that stand (default: all from `first`) — where
+        each was deposited and the bias its configuration saw (sgpr_md_meta_hills)."""
+        info = self.md_meta_info()
+        count = info["held"] - int(first) if count is None else int(count)
+        cv, V = np.zeros((max(count, 0), info["D"])), np.zeros(max(count, 0))
+        if count > 0:
+            check(_lib.load().sgpr_md_meta_hills(self._h, int(first), count, ptr(cv), ptr(V)))
+        return cv, V
+
     def _md_fix(self, fx):
         """The held components of the run just begun (sgpr_md_fix: before the thermostat / the relaxation is set)."""
         if fx is not None:

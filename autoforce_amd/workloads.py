@@ -195,8 +195,159 @@ class DeltaFilter:
         return S - self.s
 
 
+def _wave_order_sum(v):
+    """fin_wave_sum (api.hip) of 64 values: the DPP network's order — lanes ^ 1, lanes ^ 2, the half row mirrored, the row
+    mirrored — and the four rows as a pairwise tree."""
+    v = np.asarray(v, float).reshape(64)
+    i = np.arange(64)
+    v = v + v[i ^ 1]
+    v = v + v[i ^ 2]
+    v = v + v[(i & ~7) | (7 - (i & 7))]
+    v = v + v[(i & ~15) | (15 - (i & 15))]
+    return float((v[0] + v[16]) + (v[32] + v[48]))
+
+
+def _block_order_sum(p256):
+    """The sum of a workgroup's 256 per-thread values as md_meta_kernel forms it: fin_wave_sum per wave, the waves pairwise."""
+    w = [_wave_order_sum(p256[64 * k:64 * (k + 1)]) for k in range(4)]
+    return (w[0] + w[1]) + (w[2] + w[3])
+
+
+META_TRIP = 1024   # hills per trip of md_meta_kernel's strided sum (four partial sums per thread)
+
+
+def meta_cv_dim(cvs):
+    return sum(1 if c[0] == "distance" else 3 for c in cvs)
+
+
+def meta_density(c, sigma, w, hills, tem=None):
+    """The bias on a given CV value c [D] — the one host statement of the hill rule, in md_meta_kernel's operations and order
+    (meta_bias has the scheme): returns (V, dV/dc [D], kde).  sigma [D]; hills [H, D] CV values as deposited (None: none)."""
+    from .ase_shim import kB
+    c = np.asarray(c, float).reshape(-1)
+    D = len(c)
+    sg = np.broadcast_to(np.asarray(sigma, float).reshape(-1), (D,)).astype(float)
+    sg5 = 5.0 * sg
+    kx = np.clip(np.floor(c / sg5), -1e9, 1e9)   # (the kernel's keys are ints, clamped there)
+    H = np.zeros((0, D)) if (hills is None or np.size(hills) == 0) else np.asarray(hills, float).reshape(-1, D)
+    S = np.zeros(1 + D)
+    if len(H):
+        centre = (np.floor(H / sg) + 0.5) * sg
+        key = np.clip(np.floor(H / sg5), -1e9, 1e9)
+        near = (np.abs(key - kx) <= 1).all(axis=1)
+        t = (c - centre) / sg
+        d2 = np.zeros(len(H))
+        for d in range(D):
+            d2 = d2 + t[:, d] * t[:, d]
+        e = np.where(near, np.exp(-0.5 * d2), 0.0)
+        terms = np.concatenate([e[:, None], e[:, None] * t], axis=1)   # [H, 1 + D]
+        terms[~near] = 0.0
+        pad = (-len(H)) % META_TRIP
+        trips = np.concatenate([terms, np.zeros((pad, 1 + D))]).reshape(-1, 4, 256, 1 + D)
+        acc = np.zeros((4, 256, 1 + D))
+        for tr in trips:
+            acc = acc + tr
+        per = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        S = np.array([_block_order_sum(per[:, d]) for d in range(1 + D)])
+    norm = 1.0
+    for d in range(D):
+        norm = norm * float(np.sqrt(2.0 * np.pi))
+    kde = S[0] / norm
+    V, fac = w * kde, w
+    if tem is not None:
+        gamma = 1.0 / (kB * tem)
+        a_ = 1.0 + V * gamma
+        V = float(np.log(a_)) / gamma
+        fac = w / a_
+    g = -(fac * ((S[1:] / sg) / norm))
+    return float(V), g, float(kde)
+
+
+def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=None):
+    """The bias potential of metadynamics at one configuration, in the operations of the device loop's md_meta_kernel
+    (md_meta.inc; SGPRModel.md_meta) — the reference's calculator/meta.py (Meta.energy over analysis/kde.py's Gaussian_kde)
+    restated for the built-in collective variables.  This function is the definition:
+      cvs: components concatenated like the reference's Catvar, ("distance", i, j) = |x_j - x_i| and ("posvar", index, select)
+    = x_index - (1/n) sum_{k in sel, k != index} x_k with sel all atoms (select None) or the atoms of species `select`, n = |sel|
+    (the index atom counts in n where it is in sel: the reference's Posvar) — raw coordinates, no minimum image;
+      a hill deposited at c (a row of `hills` [H, D]) is centred at (floor(c / sigma) + 0.5) sigma and carries the key
+    floor(c / (5 sigma)) — 5 sigma a product, the divisions IEEE —; kde(x) = sum exp(-|(x - centre) / sigma|^2 / 2) / sqrt(2 pi)^D
+    over the hills whose key differs from floor(x / (5 sigma)) by at most 1 in every dimension; sigma a scalar or [D];
+      V = w kde, or with tem (K) log(1 + w kde gamma) / gamma, gamma = 1 / (kB tem).
+    The sums run in the kernel's order (hill h in the partial sum (h % 256, (h // 256) % 4); the mean of a posvar over the
+    atoms in the library's species-sorted order, `species` = the model's table, 256 strided partial sums; fin_wave_sum's
+    tree); exp and log are this host's, so the device agrees to rounding, not bit for bit.
+    Returns dict(cv [D], energy, forces [N, 3] = -dV/dx, stress [6] = Voigt of -(1/V_cell) sum_i x_i (x) F_i — formed as the
+    kernel forms it: d (x) F_i for a distance, cv (x) dV/dcv for a posvar —, virial [9], dcv [D] = dV/dcv, kde, and margin:
+    the smallest distance, in units of sigma, of a CV component from a bin edge k sigma or a block edge k 5 sigma — a
+    comparison between two implementations means something only where a last-bit difference cannot move a hill by a bin)."""
+    from .ase_shim import kB
+    numbers = np.asarray(numbers)
+    x = np.asarray(positions, float)
+    N = len(numbers)
+    D = meta_cv_dim(cvs)
+    sg = np.broadcast_to(np.asarray(sigma, float).reshape(-1), (D,)).astype(float) if np.size(sigma) == 1 else np.asarray(sigma, float).reshape(D)
+    sg5 = 5.0 * sg
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    c = np.zeros(D)
+    parts = []   # per component: (kind, d0, ...) what the forces need
+    d0 = 0
+    for comp in cvs:
+        if comp[0] == "distance":
+            i, j = int(comp[1]), int(comp[2])
+            d = x[j] - x[i]
+            r = float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+            c[d0] = r
+            parts.append(("distance", d0, i, j, d, r))
+            d0 += 1
+        elif comp[0] == "posvar":
+            idx, select = int(comp[1]), comp[2]
+            insel = np.ones(N, bool) if select is None else (numbers == int(select))
+            n = float(insel.sum())
+            if n == 0:
+                raise ValueError(f"meta_bias: no atom of species {select} (the mean of nothing)")
+            a = insel.copy()
+            a[idx] = False
+            xs = np.where(a[order][:, None], x[order], 0.0)   # (an atom outside the mean adds nothing: the kernel skips it)
+            pad = (-N) % 256
+            rows = np.concatenate([xs, np.zeros((pad, 3))]).reshape(-1, 256, 3)
+            p = np.zeros((256, 3))
+            for r_ in rows:
+                p = p + r_
+            mean_sum = np.array([_block_order_sum(p[:, k]) for k in range(3)])
+            c[d0:d0 + 3] = x[idx] - mean_sum / n
+            parts.append(("posvar", d0, idx, a, n))
+            d0 += 3
+        else:
+            raise ValueError(f"meta_bias: a component is ('distance', i, j) or ('posvar', index, select), not {comp!r}")
+    V, g, kde = meta_density(c, sg, w, hills, tem=tem)
+    F = np.zeros((N, 3))
+    vir = np.zeros(9)
+    for part in parts:
+        if part[0] == "distance":
+            _, q, i, j, d, r = part
+            fi = (g[q] * d) / r
+            F[i] = F[i] + fi
+            F[j] = F[j] - fi
+            vir = vir + np.outer(d, fi).reshape(9)
+        else:
+            _, q, idx, a, n = part
+            F[idx] = F[idx] - g[q:q + 3]
+            F[a] = F[a] + g[q:q + 3] / n
+            vir = vir + np.outer(c[q:q + 3], g[q:q + 3]).reshape(9)
+    cl = np.asarray(cell, float).reshape(3, 3)
+    vol = abs(float(np.linalg.det(cl)))
+    if not vol > 0.0:
+        vol = -2.0   # (calculator/active.py:606-609)
+    u = c / sg
+    u5 = c / sg5
+    margin = float(min(np.min(np.minimum(u - np.floor(u), np.ceil(u) - u)), 5.0 * np.min(np.minimum(u5 - np.floor(u5), np.ceil(u5) - u5)))) if D else np.inf
+    return dict(cv=c, energy=float(V), forces=F, stress=vir[[0, 4, 8, 5, 2, 1]] / vol, virial=vir, dcv=g, kde=float(kde), margin=margin)
+
+
 def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None, rng=None, fixed=None,
-                 ml_filter=None, filter_init=None):
+                 ml_filter=None, filter_init=None, meta=None):
     """BAOAB Langevin dynamics in numpy around any calculator with the ASE surface; parameters as the reference's
     driver (cl/md.py:31,70-74: dt = 1 fs, friction 1e-3 per ASE time unit, T = 600 K; Maxwell-Boltzmann start as
     util/aseutil.py:11-20, or the velocities handed over).  Generator: yields (step, energy, temperature, wall seconds,
@@ -210,7 +361,12 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
       ml_filter: the shrink factor of the filter of model-update jumps (DeltaFilter: calc.deltas is read after every evaluation;
     the device loop's sgpr_md_filter), filter_init: (f, s) its accumulators at the first configuration.  The integrator then
     sees F - clip(A_f, -1, 1) (a held component 0 as before); energies and the calculator's results stay raw.  Every yield
-    gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit."""
+    gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit.
+      meta: an autoforce_amd.meta.Meta — metadynamics by evaluation index, the device loop's sgpr_md_meta: configuration n is
+    evaluated with the bias of the hills deposited by the configurations before it (energy + V, forces - dV/dx, added before
+    the filter and the mask see them), then deposits its own when n % meta.pace == 0 (the reference's dyn.attach(meta.update)).
+    For a calculator that does not add the bias itself (an ActiveCalculator(meta=) does: hand this loop meta=None then and
+    call meta.update() per step).  None: today's loop, bit for bit."""
     import time
     from .ase_shim import Atoms, constraints_from_mask, kB
     rng = np.random.default_rng(seed) if rng is None else rng
@@ -239,9 +395,14 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
         at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0], constraint=cons)
         at.calc = calc
         F = at.get_forces(apply_constraint=False)
+        E = at.get_potential_energy()
+        if meta is not None:   # (the bias of this configuration, then its own hill)
+            V, Fb, _ = meta.bias(p, cell, numbers)
+            F, E = F + Fb, E + V
+            meta.update()
         if flt is not None:   # (once per configuration)
             F = flt.forces(F, getattr(calc, "deltas", None))
-        return F, at.get_potential_energy()
+        return F, E
 
     def seen(F):   # the forces the integrator sees
         return F if fx is None else np.where(fx, 0.0, F)
@@ -282,7 +443,7 @@ def _device_order_sum(x):
 
 
 def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, tdamp_fs=25.0, vel=None, seed=1, species=None,
-                    fixed=None, ml_filter=None, filter_init=None):
+                    fixed=None, ml_filter=None, filter_init=None, meta=None):
     """Nose-Hoover NVT in numpy around any calculator with the ASE surface: the reference's DEFAULT dynamics —
     md(dynamics="NPT", bulk_modulus=None) = ase.md.npt.NPT(pfactor=None, ttime=tdamp fs), cl/md.py:17, :131-166 — restated
     from ASE's published algorithm (Melchionna, Ciccotti, Holian 1993; ASE is absent here):
@@ -300,7 +461,8 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
     is the project's own definition — ase.md.npt.NPT takes no constraints at all.  None or nothing held: today's loop, bit for
     bit.
       ml_filter, filter_init: the filter of model-update jumps, as in langevin_nvt (the filtered force, then the mask); every
-    yield gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit."""
+    yield gains a last entry, (f, s) as this configuration found the accumulators.  None: today's loop, bit for bit.
+      meta: metadynamics by evaluation index, as in langevin_nvt (the bias, then the filter, then the mask).  None: today's loop."""
     import time
     from .ase_shim import Atoms, constraints_from_mask, kB
     N = len(numbers)
@@ -334,7 +496,12 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         # its copies — and its teacher's labels — from them; the forces taken here are the calculator's own)
         at = Atoms(numbers, p, cell, pbc, velocities=v, masses=mass[:, 0], constraint=cons)
         at.calc = calc
-        return at.get_forces(apply_constraint=False), at.get_potential_energy()
+        F, E = at.get_forces(apply_constraint=False), at.get_potential_energy()
+        if meta is not None:   # (the bias of this configuration, then its own hill)
+            V, Fb, _ = meta.bias(p, cell, numbers)
+            F, E = F + Fb, E + V
+            meta.update()
+        return F, E
 
     for n in range(steps + 1):
         t0 = time.time()

@@ -555,6 +555,41 @@ int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax);
 int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, const double *s0);
 int sgpr_md_filter_push(sgpr_model *h, const double *dF, const double *dS);
 int sgpr_md_filter_state(sgpr_model *h, double *f, double *s);
+/* Metadynamics inside the device MD loop: the bias potential of the reference's theforce/calculator/meta.py (Meta over
+ * theforce/analysis/kde.py's Gaussian_kde; examples/meta-dyn/md.py), one small launch per configuration between the reverse
+ * descriptor pass and the step's last kernel.  Collective variables from the raw coordinates the integrator holds (no minimum
+ * image), concatenated, D <= 6 dimensions over at most 4 components: distance(i, j) = |x_j - x_i|; posvar(index, select) =
+ * x_index - (1/n) sum over the atoms k != index of `select` (all atoms, or one species) of x_k, with n counting the index atom
+ * where it is of that species (the reference's Posvar).  A hill deposited at c is centred at (floor(c / sigma) + 0.5) sigma
+ * and is summed at x when floor(c / (5 sigma)) and floor(x / (5 sigma)) differ by at most one in every dimension;
+ * kde = sum exp(-|(x - centre) / sigma|^2 / 2) / (2 pi)^(D/2); V = w kde, or log(1 + w kde / kT) kT (well-tempered).  The bias of
+ * configuration n sums the hills of the configurations below n; configuration n deposits when n % pace == 0.  Energy, forces
+ * and virial of everything the run reports and integrates include the bias; the covloss gate does not see it.  Hills are rows
+ * indexed by configuration: what a halt discards or a cut repeats overwrites its own row.
+ *
+ * sgpr_md_meta        after sgpr_md_begin, between any two sgpr_md_run calls.  cvs[ncomp][3] = kind (0 distance, 1 posvar), atom
+ *                     (i | index), second (j | select: an atomic number, -1: all atoms), caller atom order; sigma[D]; w; kT > 0:
+ *                     well-tempered, 0: plain; pace >= 1; capacity: rows of hills; nhills rows hills_cv[nhills][D] and
+ *                     hills_V[nhills] (NULL: zeros) stand from the start, for the deposits of the configurations below the
+ *                     current one (a restart; the rows of sgpr_md_meta_hills when a run needs more room).  ncomp = 0 detaches.
+ *                     SGPR_E_UNSUPPORTED, each naming the host loop around calculate(): a barostat, a relaxation, a nudged
+ *                     elastic band, a committee, a run begun on several ranks (and those calls behind a bias; sgpr_md_run
+ *                     where the step cannot take the single-rank gather form of the fused last kernel — graph replay, the
+ *                     side-stream fork, a zero skin, the scatter form: refused before anything is enqueued; lists that outgrow the
+ *                     gather form inside a call: at that evaluation).  sgpr_md_run refuses with SGPR_E_INVALID, before it
+ *                     enqueues anything, a call whose deposits would pass the capacity.  A CV further than 1e9 blocks of 5 sigma
+ *                     from the origin is beyond the scheme (keys are clamped there).  sgpr_md_begin detaches.
+ * sgpr_md_meta_info   D; below: the hills below the current configuration (those given and the deposits of the configurations
+ *                     before it: what sgpr_md_meta takes to go on from here); held: those and the current configuration's own
+ *                     row after a halted or `final` call (not behind a fresh sgpr_md_meta: the row is written when the run goes
+ *                     on); the capacity.  Any of them NULL.
+ * sgpr_md_meta_hills  rows first ... first + count - 1 of the hills that stand: cv[count][D], V[count] (the bias the depositing
+ *                     configuration saw); either NULL.
+ * sgpr_md_end releases the hills. */
+int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const double *sigma, double w, double kT, int pace, int64_t capacity,
+                 int64_t nhills, const double *hills_cv, const double *hills_V);
+int sgpr_md_meta_info(sgpr_model *h, int *D, int64_t *below, int64_t *held, int64_t *capacity);
+int sgpr_md_meta_hills(sgpr_model *h, int64_t first, int64_t count, double *cv, double *V);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
