@@ -95,6 +95,8 @@ SIGNATURES = {
     "sgpr_md_meta": (C.c_int, [_vp, C.c_int, _vp, _vp, _dbl, _dbl, C.c_int, _i64, _i64, _vp, _vp]),
     "sgpr_md_meta_info": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sgpr_md_meta_hills": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "sgpr_md_meta_merge": (C.c_int, [_vp, _i64]),
+    "sgpr_md_meta_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sgpr_sync_check": (C.c_int, [_vp, _vp]),
     "sgpr_comm_unique_id": (C.c_int, [_vp]),
     "sgpr_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),

@@ -694,7 +694,7 @@ class ActiveCalculator(Calculator):
                                  "deposits configuration n of the run when n % pace == 0")
             hills0 = meta.hills_array()
             eng.md_meta(self._meta_spec(), meta.sigma, meta.w, tem=meta.tem, pace=meta.pace, hills=hills0 if len(hills0) else None,
-                        capacity=len(hills0) + (steps + 1) // meta.pace + 2)
+                        capacity=len(hills0) + (steps + 1) // meta.pace + 2, **({"merge": meta.merge} if getattr(meta, "merge", None) else {}))
             meta_seen, meta_n0 = len(hills0), meta.n
         # (a run with members attached records no frames: batches end at the multiples of sync_every)
         rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1 and not attached)

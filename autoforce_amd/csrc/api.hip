@@ -226,6 +226,19 @@ struct MdState {
     DevBuf<double> meta_centre, meta_rows;   // [cap][D] centres (room for 6), [cap][7] CV | V
     DevBuf<int> meta_key;                    // [cap][D] super-block keys (room for 6)
     DevBuf<unsigned char> meta_sel;          // [ncomp][N] posvar: the atoms of the mean, sorted order
+    // the merged form (sgpr_md_meta_merge): the table of md_meta.inc, one entry per occupied bin, room for every row in a bin of its own
+    int meta_merge = 0;                      // the chunk length (0: every hill on its own)
+    long long meta_enq = 0;                  // chunks whose merge this call has enqueued or found done (the device word decides)
+    DevBuf<double> meta_tcentre, meta_tcnt, meta_tlast;
+    DevBuf<int> meta_tkey, meta_tstamp, meta_ctl;
+    MetaTab meta_tab(long long want) const
+    {
+        MetaTab tb;
+        tb.centre = meta_tcentre.p; tb.key = meta_tkey.p; tb.cnt = meta_tcnt.p; tb.last = meta_tlast.p; tb.stamp = meta_tstamp.p;
+        tb.ctl = meta_ctl.p; tb.ch = meta_merge; tb.want = (int)want;
+        return tb;
+    }
+    void meta_tab_release() { meta_tcentre.release(); meta_tcnt.release(); meta_tlast.release(); meta_tkey.release(); meta_tstamp.release(); meta_ctl.release(); }
     static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
     long long meta_slot(long long n) const { return meta_pre + meta_dep(n, meta_pace) - meta_dep(meta_base, meta_pace); }
     // the frame record (sgpr_md_record, md_record.inc): every rec_every-th configuration of a call, copied out behind its
@@ -1659,6 +1672,7 @@ extern "C" void sgpr_destroy(sgpr_model *h)
         m.fixed.release();
         m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
         m.meta_centre.release(); m.meta_rows.release(); m.meta_key.release(); m.meta_sel.release();
+        m.meta_tab_release();
         m.bcm_P.release(); m.bcm_x.release(); m.bcm_info_d.release();
         m.nb_X.release(); m.nb_V.release(); m.nb_P.release(); m.nb_ends.release(); m.nb_sums.release(); m.nb_coef.release(); m.nb_info_d.release(); m.nb_par.release();
         DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
@@ -2737,9 +2751,22 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
                                             "and sharded frames take the host loop around calculate()");
         const long long n = nx->md.t_index;
-        hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
-                           m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
-                           h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
+        if (m.meta_merge) {
+            // the chunks that lie below this configuration and are not merged yet: at a crossing, or at the first configuration
+            // of a call that is behind
+            const long long want = m.meta_slot(n) / m.meta_merge;
+            for (long long &j = h->md.meta_enq; j < want; j++) {
+                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.mp.D, m.meta_merge, (int)j, (const double *)m.meta_centre.p,
+                                   (const int *)m.meta_key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
+                stamp(h, "md_meta_merge", st);
+            }
+            hipLaunchKernelGGL(md_meta_merged_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
+                               m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
+                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
+        } else
+            hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
+                               m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
+                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
         stamp(h, "md_meta", st);
     }
     const bool xp = !gather && (px || shard_next);

@@ -1122,6 +1122,13 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         if (nd >= m.t && m.meta_slot(nd) >= m.meta_cap)
             return fail(SGPR_E_INVALID, "sgpr_md_run: %d evaluations from configuration %lld deposit hills up to row %lld; the bias holds %lld "
                         "(sgpr_md_meta again, with a larger capacity and the hills of sgpr_md_meta_hills)", nevals, m.t, m.meta_slot(nd), m.meta_cap);
+        if (m.meta_merge) {
+            // where the table stands: merges enqueued behind a halt were discarded, the one of the speculative step in front of it was not
+            int ctl[META_CTL_LEN];
+            HIPCHK(hipMemcpyAsync(ctl, m.meta_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            m.meta_enq = ctl[META_CTL_DONE];
+        }
         m.meta_fresh = false;
     }
     m.started = true;
@@ -1585,6 +1592,72 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     HIPCHK(hipMemcpy(m.meta_sel.p, sel.data(), sel.size(), hipMemcpyHostToDevice));
     m.mp = p; m.meta_pace = pace; m.meta_base = m.t; m.meta_pre = nhills; m.meta_cap = capacity;
     m.meta = true; m.meta_fresh = true;
+    m.meta_merge = 0; m.meta_enq = 0;   // (every hill on its own until sgpr_md_meta_merge says otherwise)
+    return SGPR_OK;
+}
+
+// The merged form of the bias (md_meta.inc; workloads.meta_density(merge=) is the definition): from the next sgpr_md_run on the
+// hills are merged by bin, chunk after chunk of `chunk` rows, and an evaluation sums one entry per occupied bin and the rows
+// behind the last whole chunk.  Valid after sgpr_md_meta and before the next sgpr_md_run; chunk = 0 switches merging off again.
+// The chunks of the uploaded hills are merged here, synchronously, through the kernel the loop enqueues: a run that goes on
+// from the rows of sgpr_md_meta_hills with the same chunk has the bits of the run that was never interrupted.
+extern "C" int sgpr_md_meta_merge(sgpr_model *h, int64_t chunk)
+{
+    if (!h || chunk < 0 || chunk > (1 << 28)) return fail(SGPR_E_INVALID, "sgpr_md_meta_merge: 0 <= chunk <= 2^28");
+    MdState &m = h->md;
+    if (!m.active || !m.meta || !m.meta_fresh)
+        return fail(SGPR_E_INVALID, "sgpr_md_meta_merge: call sgpr_md_meta first, and this before the next sgpr_md_run");
+    m.meta_merge = 0; m.meta_enq = 0;
+    if (chunk == 0) return SGPR_OK;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t cap = (size_t)m.meta_cap, D = (size_t)m.mp.D;
+    if (m.meta_tcentre.alloc(cap * D) || m.meta_tkey.alloc(cap * D) || m.meta_tcnt.alloc(cap) || m.meta_tlast.alloc(cap) || m.meta_tstamp.alloc(cap) ||
+        m.meta_ctl.alloc(META_CTL_LEN))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_meta_merge: device allocation failed");
+    const int ctl[META_CTL_LEN] = {0, 0, 0, INT_MAX};
+    HIPCHK(hipMemcpy(m.meta_ctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+    m.meta_merge = (int)chunk;
+    const long long pre = m.meta_pre / chunk;
+    for (long long j = 0; j < pre; j++)
+        hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, h->stream, m.mp.D, m.meta_merge, (int)j, (const double *)m.meta_centre.p,
+                           (const int *)m.meta_key.p, m.meta_tab(pre), (const int *)(m.meta_ctl.p + META_CTL_RUN), 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    m.meta_enq = pre;
+    return SGPR_OK;
+}
+
+// The table of the merged form as the current configuration sees it (the reference's Gaussian_kde.histogram()): *n_entries
+// entries in the order of the first row that occupied each, centres[*n_entries][D] and counts[*n_entries], merged from the
+// first *rows_merged rows.  Any of them NULL (call once for *n_entries, then with room).
+extern "C" int sgpr_md_meta_table(sgpr_model *h, double *centres, double *counts, int64_t *n_entries, int64_t *rows_merged)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_meta_table: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || !m.meta || !m.meta_merge) return fail(SGPR_E_INVALID, "sgpr_md_meta_table: call sgpr_md_begin, sgpr_md_meta and sgpr_md_meta_merge first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int ctl[META_CTL_LEN];
+    HIPCHK(hipMemcpy(ctl, m.meta_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+    // (behind a halt the table may be one chunk ahead of the current configuration: that chunk is taken off, as its evaluation does)
+    const long long want = std::min<long long>(m.meta_slot(m.t) / m.meta_merge, ctl[META_CTL_DONE]);
+    const bool ahead = ctl[META_CTL_DONE] != want;
+    const size_t T = (size_t)(ahead ? ctl[META_CTL_TPREV] : ctl[META_CTL_T]), D = (size_t)m.mp.D;
+    if (n_entries) *n_entries = (int64_t)T;
+    if (rows_merged) *rows_merged = (int64_t)(want * m.meta_merge);
+    if (centres && T) HIPCHK(hipMemcpy(centres, m.meta_tcentre.p, sizeof(double) * T * D, hipMemcpyDeviceToHost));
+    if (counts && T) {
+        HIPCHK(hipMemcpy(counts, m.meta_tcnt.p, sizeof(double) * T, hipMemcpyDeviceToHost));
+        if (ahead) {
+            std::vector<double> last(T);
+            std::vector<int> stamp(T);
+            HIPCHK(hipMemcpy(last.data(), m.meta_tlast.p, sizeof(double) * T, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(stamp.data(), m.meta_tstamp.p, sizeof(int) * T, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < T; k++)
+                if (stamp[k] == ctl[META_CTL_DONE] - 1) counts[k] -= last[k];
+        }
+    }
     return SGPR_OK;
 }
 
@@ -1636,6 +1709,7 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipStreamSynchronize(h->stream);
         h->md.meta = false;
         h->md.meta_centre.release(); h->md.meta_rows.release(); h->md.meta_key.release(); h->md.meta_sel.release();
+        h->md.meta_merge = 0; h->md.meta_tab_release();
     }
     h->md.bcm.clear(); h->md.bcm_info.clear();   // (the borrowed members are let go)
     return SGPR_OK;

@@ -20,6 +20,18 @@
 // alone adds V into slot 0 of the energy partials and x (x) F into slot 0 of the nine virial partials (both stored by the
 // step's earlier kernels, read by the last kernel's reducers) and stores the hill row.  No atomics, nothing depends on the
 // order the workgroups run in.
+//
+// The merged form (sgpr_md_meta_merge(chunk = CH); workloads.meta_density(merge=) is the definition): the rows are still kept,
+// and chunk j — the rows [j CH, (j + 1) CH) — is merged into a table of one entry per occupied bin (centre, the block key of the
+// first row, the number of rows as a double) by md_meta_merge_kernel, enqueued in front of the bias of the first configuration n
+// with slot(n) / CH > j.  Those rows are final there: a kernel of step n that runs un-halted has the positions of every
+// configuration below n behind it.  The bias of configuration n sums the entries of the chunks below slot(n) — entry k in thread
+// k % 256, partial sum (k / 256) % 4 — and then the rows [(slot(n) / CH) CH, slot(n)) — row B + r in thread r % 256, partial sum
+// (r / 256) % 4 of the same accumulators —, so it is a function of n and the rows below it alone.  The covloss gate halts
+// configuration k from the last kernel of step k + 1, whose merge, when k + 1 crosses a chunk, has run by then: the table is then
+// one chunk ahead of the halted configuration, which is evaluated again.  Each entry therefore keeps what the last chunk added to
+// it (last, stamp) and the table the entry count before that chunk: an evaluation that finds the table one chunk ahead takes
+// the last chunk off again — integers in doubles, the same bits as a table that never held it.
 // sums of three values over the workgroup in a fixed order: fin_wave_sum per wave, the four waves as a pairwise tree
 __device__ __forceinline__ void meta_block_sum3(double (&s)[3], double (*red)[4])
 {
@@ -38,12 +50,12 @@ __device__ __forceinline__ void meta_block_sum3(double (&s)[3], double (*red)[4]
 // x: [N][3] positions of this configuration, sorted order; sel: [ncomp][N] bytes, sorted order (posvar: 1 = in sel and not the
 // index atom); centre [cap][D], key [cap][D], rows [cap][7] = cv[6] | V; nh hills stand below this configuration; own: the row
 // this configuration deposits (-1: none: n % pace != 0)
-__global__ __launch_bounds__(256) void md_meta_kernel(int N, MetaPar p, const double *x, const unsigned char *sel, double *centre, int *key,
-                                                      double *rows, int nh, int own, double *Fself, double *Epart, double *virpart, int nV,
-                                                      const int *halt, int step)
+// (the body of both forms of the bias: MERGED sums the table tb and then the rows behind its chunks, otherwise every row)
+template <bool MERGED>
+__device__ __forceinline__ void meta_eval(int N, const MetaPar &p, const double *x, const unsigned char *sel, double *centre, int *key,
+                                          double *rows, int nh, int own, double *Fself, double *Epart, double *virpart, int nV, const MetaTab &tb)
 {
 #pragma clang fp contract(off)
-    if (*halt < step) return;
     __shared__ double red[1 + META_MAXD][4];
     __shared__ double csh[META_MAXD], gsh[META_MAXD];   // (indexed by a running dimension: not registers)
     const int tid = threadIdx.x;
@@ -91,7 +103,43 @@ __global__ __launch_bounds__(256) void md_meta_kernel(int N, MetaPar p, const do
     for (int u = 0; u < 4; u++)
 #pragma unroll
         for (int d = 0; d <= META_MAXD; d++) acc[u][d] = 0.0;
-    for (int h0 = tid; h0 < nh; h0 += META_TRIP) {
+    int hb = 0;   // the first row summed on its own
+    if constexpr (MERGED) {
+        // the entries of the chunks below this configuration: entry k adds cnt e and (cnt e) t_d
+        int T = tb.ctl[META_CTL_T];
+        const int done = tb.ctl[META_CTL_DONE];
+        const bool ahead = done != tb.want;   // (the table holds one chunk more: the speculative step behind a halted configuration merged it)
+        if (ahead) T = tb.ctl[META_CTL_TPREV];
+        for (int k0 = tid; k0 < T; k0 += META_TRIP) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int k = k0 + 256 * u;
+                if (k >= T) continue;
+                const int *kh = tb.key + (size_t)D * k;
+                bool near = true;
+#pragma unroll
+                for (int d = 0; d < META_MAXD; d++)
+                    if (d < D) near = near && abs(kh[d] - kx[d]) <= 1;
+                if (!near) continue;
+                const double *ch = tb.centre + (size_t)D * k;
+                double t[META_MAXD], d2 = 0.0;
+#pragma unroll
+                for (int d = 0; d < META_MAXD; d++) {
+                    t[d] = 0.0;
+                    if (d < D) t[d] = (c[d] - ch[d]) / p.sigma[d];
+                    d2 = d2 + t[d] * t[d];
+                }
+                double n = tb.cnt[k];
+                if (ahead && tb.stamp[k] == done - 1) n = n - tb.last[k];
+                const double e = n * exp(-0.5 * d2);
+                acc[u][0] += e;
+#pragma unroll
+                for (int d = 0; d < META_MAXD; d++) acc[u][1 + d] += e * t[d];
+            }
+        }
+        hb = tb.want * tb.ch;
+    }
+    for (int h0 = hb + tid; h0 < nh; h0 += META_TRIP) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int h = h0 + 256 * u;
@@ -202,5 +250,109 @@ __global__ __launch_bounds__(256) void md_meta_kernel(int N, MetaPar p, const do
             row[d] = c[d];
         }
         row[META_MAXD] = V;
+    }
+}
+
+// x: [N][3] positions of this configuration, sorted order; sel: [ncomp][N] bytes, sorted order (posvar: 1 = in sel and not the
+// index atom); centre [cap][D], key [cap][D], rows [cap][7] = cv[6] | V; nh hills stand below this configuration; own: the row
+// this configuration deposits (-1: none: n % pace != 0)
+__global__ __launch_bounds__(256) void md_meta_kernel(int N, MetaPar p, const double *x, const unsigned char *sel, double *centre, int *key,
+                                                      double *rows, int nh, int own, double *Fself, double *Epart, double *virpart, int nV,
+                                                      const int *halt, int step)
+{
+    if (*halt < step) return;
+    meta_eval<false>(N, p, x, sel, centre, key, rows, nh, own, Fself, Epart, virpart, nV, MetaTab());
+}
+
+// the merged form: the same launch in the same place of the step
+__global__ __launch_bounds__(256) void md_meta_merged_kernel(int N, MetaPar p, const double *x, const unsigned char *sel, double *centre, int *key,
+                                                             double *rows, int nh, int own, double *Fself, double *Epart, double *virpart, int nV,
+                                                             MetaTab tb, const int *halt, int step)
+{
+    if (*halt < step) return;
+    meta_eval<true>(N, p, x, sel, centre, key, rows, nh, own, Fself, Epart, virpart, nV, tb);
+}
+
+// Merges chunk j — the rows [j ch, (j + 1) ch) of centre / key — into the table: ONE workgroup.  Acts only when the table holds
+// exactly the chunks below j, so that an enqueue that is repeated, or one behind a discarded one, changes nothing.  256 rows at
+// a time, in row order: every row looks for its centre (by bits) among the entries that stand; the first row of each centre
+// among the 256 is its leader and counts the rows equal to it; the leaders whose centre is new take the positions T + rank, the
+// rank counted over the rows in row order — the order of first occurrence whatever the scheduling —; each leader is the one
+// writer of its entry (no atomics; the counts are integers in doubles, exact in any order).
+__global__ __launch_bounds__(256) void md_meta_merge_kernel(int D, int ch, int j, const double *centre, const int *key, MetaTab tb,
+                                                            const int *halt, int step)
+{
+    if (*halt < step) return;
+    __shared__ long long csh[256][META_MAXD];
+    __shared__ int wnew[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int done = tb.ctl[META_CTL_DONE];
+    int T = tb.ctl[META_CTL_T];
+    __syncthreads();   // (every thread has read the words thread 0 writes on its way out)
+    if (done != j) return;
+    const int T0 = T;
+    for (int r0 = 0; r0 < ch; r0 += 256) {
+        const int nr = ch - r0 < 256 ? ch - r0 : 256;
+        const bool live = tid < nr;
+        const size_t h = (size_t)j * ch + r0 + (live ? tid : 0);
+        long long cb[META_MAXD];
+#pragma unroll
+        for (int d = 0; d < META_MAXD; d++) {
+            cb[d] = d < D ? __double_as_longlong(centre[(size_t)D * h + d]) : 0;
+            csh[tid][d] = cb[d];
+        }
+        int m = -1;   // the entry that holds this row's centre
+        if (live)
+            for (int k = 0; k < T && m < 0; k++) {
+                bool eq = true;
+#pragma unroll
+                for (int d = 0; d < META_MAXD; d++)
+                    if (d < D) eq = eq && __double_as_longlong(tb.centre[(size_t)D * k + d]) == cb[d];
+                if (eq) m = k;
+            }
+        __syncthreads();
+        int first = -1;
+        double n = 0.0;
+        if (live)
+            for (int r = 0; r < nr; r++) {
+                bool eq = true;
+#pragma unroll
+                for (int d = 0; d < META_MAXD; d++) eq = eq && csh[r][d] == cb[d];
+                if (eq) {
+                    if (first < 0) first = r;
+                    n += 1.0;
+                }
+            }
+        const bool leader = live && first == tid, fresh = leader && m < 0;
+        const unsigned long long b = __ballot(fresh);
+        if (lane == 0) wnew[wave] = __popcll(b);
+        __syncthreads();
+        int pos = m;
+        if (fresh) {
+            pos = T + __popcll(b & ((1ull << lane) - 1ull));
+            for (int q = 0; q < wave; q++) pos += wnew[q];
+        }
+        if (leader) {
+            double old = 0.0, add = n;
+            if (fresh) {
+                for (int d = 0; d < D; d++) {
+                    tb.centre[(size_t)D * pos + d] = __longlong_as_double(cb[d]);
+                    tb.key[(size_t)D * pos + d] = key[(size_t)D * h + d];
+                }
+            } else {
+                old = tb.cnt[pos];
+                if (tb.stamp[pos] == j) add = tb.last[pos] + n;   // (an earlier 256 of this chunk)
+            }
+            tb.cnt[pos] = old + n;
+            tb.last[pos] = add;
+            tb.stamp[pos] = j;
+        }
+        T += (wnew[0] + wnew[1]) + (wnew[2] + wnew[3]);
+        __syncthreads();   // (the new entries stand for the next 256 rows; csh and wnew are free)
+    }
+    if (tid == 0) {
+        tb.ctl[META_CTL_TPREV] = T0;
+        tb.ctl[META_CTL_T] = T;
+        tb.ctl[META_CTL_DONE] = j + 1;
     }
 }

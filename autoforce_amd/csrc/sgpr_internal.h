@@ -124,6 +124,19 @@ struct MetaPar {
     double w, gamma, norm;          // height, 1 / kT (well-tempered), sqrt(2 pi)^D as a product of D factors
 };
 
+// the hills merged by bin (sgpr_md_meta_merge): one entry per occupied bin, in the order of the first row that occupied it
+enum { META_CTL_T = 0 /* entries */, META_CTL_DONE = 1 /* chunks merged */, META_CTL_TPREV = 2 /* entries before the last chunk */,
+       META_CTL_RUN = 3 /* INT_MAX: the halt word of a merge outside a run */, META_CTL_LEN = 4 };
+struct MetaTab {
+    double *centre;   // [cap][D]
+    int *key;         // [cap][D] the block key of the first row
+    double *cnt;      // [cap] rows in the bin, an exact integer
+    double *last;     // [cap] what chunk stamp[k] added to cnt[k]: an evaluation one chunk behind the table takes it off again
+    int *stamp;       // [cap] the last chunk that added to the entry
+    int *ctl;         // [META_CTL_LEN]
+    int ch, want;     // the chunk length; the chunks below the configuration evaluated: slot(n) / ch
+};
+
 // FIRE relaxation on the device (sgpr_md_relax; md_relax.inc has the scheme)
 struct RelaxParams {
     double fmax2;                                        // fmax^2

@@ -72,10 +72,16 @@ class Catvar:
 
 class Meta:
     """Meta(colvar, sigma=0.1, w=0.01, tem=None): the reference's constructor — it opens meta.hist with the header line
-    `# sigma` — plus pace (configuration n deposits when n % pace == 0; the reference: 1) and hist (the file; None: none)."""
+    `# sigma` — plus pace (configuration n deposits when n % pace == 0; the reference: 1), hist (the file; None: none) and
+    merge (a chunk length: the hills are merged by bin, chunk after chunk, workloads.meta_density(merge=) — the cost of the bias
+    then grows with the bins visited, not with time; the device loop takes it as SGPRModel.md_meta(merge=); None: every hill on
+    its own)."""
 
-    def __init__(self, colvar, sigma=0.1, w=0.01, tem=None, pace=1, hist="meta.hist"):
+    def __init__(self, colvar, sigma=0.1, w=0.01, tem=None, pace=1, hist="meta.hist", merge=None):
         self.colvar, self.sigma, self.w, self.tem, self.pace, self.hist = colvar, sigma, float(w), tem, int(pace), hist
+        self.merge = None if merge is None else int(merge)
+        if self.merge is not None and self.merge < 1:
+            raise ValueError(f"Meta: merge is a chunk length >= 1 or None, not {merge}")
         self.species = None   # the model's species table: the order in which a posvar's mean is summed (None: sorted numbers)
         self.hills = []     # CV values of the deposits, in order
         self.n = 0          # configurations update() has seen
@@ -96,6 +102,18 @@ class Meta:
     def hills_array(self, D=None):
         return np.asarray(self.hills, float).reshape(len(self.hills), -1) if self.hills else np.zeros((0, D or 0))
 
+    def histogram(self):
+        """(centres [T, D], counts [T]) of the hills held, merged by bin — the reference's Gaussian_kde.histogram() — by the rule
+        of workloads.meta_table: with merge, the rows below the last whole chunk (what the merged bias sums as entries, and what
+        SGPRModel.md_meta_table() returns); without, all of them."""
+        from .workloads import meta_table
+        H = self.hills_array()
+        if not len(H):
+            return np.zeros((0, H.shape[1])), np.zeros(0)
+        sg = np.asarray(self.sigma, float).reshape(-1)
+        centres, _, counts, _ = meta_table(H, sg if len(sg) > 1 else sg[0], self.merge or 1)
+        return centres, counts
+
     def bias(self, positions, cell, numbers=None):
         """(V, forces [N, 3], stress [6]) of the bias at this configuration with the hills deposited so far; the CV is kept
         for update()."""
@@ -104,7 +122,7 @@ class Meta:
         numbers = np.zeros(len(x), int) if numbers is None else np.asarray(numbers)
         spec = self.device_spec()
         if spec is not None:
-            out = meta_bias(spec, self.sigma, self.w, numbers, x, cell, self.hills_array(), tem=self.tem, species=self.species)
+            out = meta_bias(spec, self.sigma, self.w, numbers, x, cell, self.hills_array(), tem=self.tem, species=self.species, merge=self.merge)
             self._cv, self.energy, self.margin = out["cv"], out["energy"], out["margin"]
             return out["energy"], out["forces"], out["stress"]
         return self._bias_autograd(numbers, x, cell)
@@ -117,7 +135,7 @@ class Meta:
         xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
         cv = self.colvar(torch.as_tensor(np.asarray(numbers)), xt, torch.tensor(np.asarray(cell, float).reshape(3, 3)), None, None).reshape(-1)
         c = cv.detach().numpy()
-        V, g, _ = meta_density(c, self.sigma, self.w, self.hills_array(len(c)), tem=self.tem)
+        V, g, _ = meta_density(c, self.sigma, self.w, self.hills_array(len(c)), tem=self.tem, merge=self.merge)
         (gx,) = torch.autograd.grad(cv, xt, torch.tensor(g), allow_unused=True)
         F = np.zeros_like(x) if gx is None else -np.nan_to_num(gx.numpy())
         vol = abs(float(np.linalg.det(np.asarray(cell, float).reshape(3, 3))))

@@ -668,7 +668,7 @@ class SGPRModel:
 
     META_KINDS = {"distance": 0, "posvar": 1}
 
-    def md_meta(self, cvs, sigma, w, tem=None, pace=1, hills=None, capacity=None):
+    def md_meta(self, cvs, sigma, w, tem=None, pace=1, hills=None, capacity=None, merge=None):
         """Metadynamics for the run begun by md_begin (sgpr_md_meta; md_meta.inc has the scheme, workloads.meta_bias is the host
         twin and the definition; the reference's calculator/meta.py): from the next md_run on every configuration is evaluated
         with the bias V = w kde(cv) — tem (K): the well-tempered log(1 + w kde gamma) / gamma, gamma = 1 / (kB tem) — of the
@@ -683,12 +683,17 @@ class SGPRModel:
         md_meta_info()["below"]) and a larger capacity lets the run go on with the same bits.  cvs = None or (): no bias.
         Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter= and
         md_record; a barostat, a relaxation, a band, a committee and several ranks: NotImplementedError (the host loop
-        around calculate() serves them)."""
+        around calculate() serves them).
+          merge = CH: the merged form (sgpr_md_meta_merge; workloads.meta_density(merge=) is the definition) — the hills are
+        merged by bin, chunk after chunk of CH rows, inside the loop, and the cost of the bias grows with the bins visited, not
+        with time; md_meta_table() fetches the table.  None: every hill on its own, today's launches and bits."""
         lib = _lib.load()
         if not cvs:
             check(lib.sgpr_md_meta(self._h, 0, None, None, 0.0, 0.0, 1, 1, 0, None, None))
             self._md.pop("meta_D", None)
             return
+        if merge is not None and int(merge) < 1:
+            raise ValueError(f"md_meta: merge is a chunk length >= 1 or None, not {merge}")
         from .ase_shim import kB
         spec, D = [], 0
         for c in cvs:
@@ -712,6 +717,20 @@ class SGPRModel:
                 raise NotImplementedError(str(e)) from None
             raise
         self._md["meta_D"] = D
+        if merge is not None:
+            check(lib.sgpr_md_meta_merge(self._h, int(merge)))
+
+    def md_meta_table(self):
+        """(centres [T, D], counts [T], rows_merged) of the merged bias (sgpr_md_meta_table; md_meta(merge=)): one entry per
+        occupied bin in the order of the first hill that fell into it, as the current configuration sees it — the reference's
+        Gaussian_kde.histogram() — and the number of hill rows it was merged from."""
+        lib = _lib.load()
+        n, rows = C.c_int64(0), C.c_int64(0)
+        check(lib.sgpr_md_meta_table(self._h, None, None, C.addressof(n), C.addressof(rows)))
+        centres, counts = np.zeros((n.value, self._md["meta_D"])), np.zeros(n.value)
+        if n.value:
+            check(lib.sgpr_md_meta_table(self._h, ptr(centres), ptr(counts), C.addressof(n), C.addressof(rows)))
+        return centres, counts, rows.value
 
     def md_meta_info(self):
         """dict(D, below, held, capacity) of the run's bias (sgpr_md_meta_info): below = the hills below the current

@@ -220,9 +220,47 @@ def meta_cv_dim(cvs):
     return sum(1 if c[0] == "distance" else 3 for c in cvs)
 
 
-def meta_density(c, sigma, w, hills, tem=None):
+def meta_table(hills, sigma, merge):
+    """The hills merged by bin, as the merged form of the bias holds them (md_meta_merge_kernel; the reference's Gaussian_kde keeps
+    a counter per occupied bin): with B = (H // merge) * merge, the rows [0, B) of `hills` [H, D] become one entry per distinct
+    centre (floor(c / sigma) + 0.5) sigma — compared by bits, which is one distinct bin floor(c / sigma) per dimension — that
+    carries the block key floor(c / (5 sigma)) of the FIRST row that occupied it and the number of its rows as a double (an exact
+    integer: no order of counting changes its bits).  Entries stand in the order of the first row that occupied them.
+    Returns (centres [T, D], keys [T, D], counts [T], B)."""
+    H = np.zeros((0, np.size(sigma))) if (hills is None or np.size(hills) == 0) else np.asarray(hills, float)
+    H = H.reshape(len(H), -1) if H.ndim != 2 else H
+    D = H.shape[1]
+    merge = int(merge)
+    if merge < 1:
+        raise ValueError(f"meta_table: merge is a chunk length >= 1, not {merge}")
+    B = (len(H) // merge) * merge
+    sg = np.broadcast_to(np.asarray(sigma, float).reshape(-1), (D,)).astype(float)
+    centre = np.ascontiguousarray((np.floor(H[:B] / sg) + 0.5) * sg)
+    key = np.clip(np.floor(H[:B] / (5.0 * sg)), -1e9, 1e9)
+    where, first, counts = {}, [], []
+    for r in range(B):
+        k = centre[r].tobytes()
+        q = where.get(k)
+        if q is None:
+            where[k] = len(first)
+            first.append(r)
+            counts.append(1.0)
+        else:
+            counts[q] += 1.0
+    first = np.asarray(first, int)
+    return centre[first].reshape(-1, D), key[first].reshape(-1, D), np.asarray(counts, float), B
+
+
+def meta_density(c, sigma, w, hills, tem=None, merge=None):
     """The bias on a given CV value c [D] — the one host statement of the hill rule, in md_meta_kernel's operations and order
-    (meta_bias has the scheme): returns (V, dV/dc [D], kde).  sigma [D]; hills [H, D] CV values as deposited (None: none)."""
+    (meta_bias has the scheme): returns (V, dV/dc [D], kde).  sigma [D]; hills [H, D] CV values as deposited (None: none).
+      merge = CH (a chunk length >= 1; None: every hill on its own, today's bits): the merged form of the device bias
+    (sgpr_md_meta_merge).  The rows [0, B), B = (H // CH) * CH, are summed as the entries of meta_table — entry k adds cnt e to S
+    and (cnt e) t_d to A_d, with near, t and e as for a hill, from the entry's centre and key — and the rows [B, H) one by one as
+    before.  The order is a function of (rows, CH) alone: the entries first, entry k in the partial sum (k % 256, (k // 256) % 4),
+    trip after trip of 1024; then the tail rows, row B + r into the partial sum (r % 256, (r // 256) % 4) of the SAME
+    accumulators, trip after trip; then the four partial sums of a thread as (0 + 1) + (2 + 3) and fin_wave_sum's tree over
+    the workgroup.  No product is contracted with a sum."""
     from .ase_shim import kB
     c = np.asarray(c, float).reshape(-1)
     D = len(c)
@@ -231,7 +269,28 @@ def meta_density(c, sigma, w, hills, tem=None):
     kx = np.clip(np.floor(c / sg5), -1e9, 1e9)   # (the kernel's keys are ints, clamped there)
     H = np.zeros((0, D)) if (hills is None or np.size(hills) == 0) else np.asarray(hills, float).reshape(-1, D)
     S = np.zeros(1 + D)
-    if len(H):
+    if len(H) and merge is not None:
+        tc, tk, cnt, B = meta_table(H, sg, merge)
+        groups = []
+        for centre, key, n in ((tc, tk, cnt), ((np.floor(H[B:] / sg) + 0.5) * sg, np.clip(np.floor(H[B:] / sg5), -1e9, 1e9), None)):
+            near = (np.abs(key - kx) <= 1).all(axis=1)
+            t = (c - centre) / sg
+            d2 = np.zeros(len(centre))
+            for d in range(D):
+                d2 = d2 + t[:, d] * t[:, d]
+            e = np.where(near, np.exp(-0.5 * d2), 0.0)
+            if n is not None:
+                e = n * e
+            terms = np.concatenate([e[:, None], e[:, None] * t], axis=1)
+            terms[~near] = 0.0
+            groups += [terms, np.zeros(((-len(terms)) % META_TRIP, 1 + D))]   # (each of the two starts its own trips)
+        trips = np.concatenate(groups).reshape(-1, 4, 256, 1 + D)
+        acc = np.zeros((4, 256, 1 + D))
+        for tr in trips:
+            acc = acc + tr
+        per = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        S = np.array([_block_order_sum(per[:, d]) for d in range(1 + D)])
+    elif len(H):
         centre = (np.floor(H / sg) + 0.5) * sg
         key = np.clip(np.floor(H / sg5), -1e9, 1e9)
         near = (np.abs(key - kx) <= 1).all(axis=1)
@@ -263,7 +322,7 @@ def meta_density(c, sigma, w, hills, tem=None):
     return float(V), g, float(kde)
 
 
-def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=None):
+def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=None, merge=None):
     """The bias potential of metadynamics at one configuration, in the operations of the device loop's md_meta_kernel
     (md_meta.inc; SGPRModel.md_meta) — the reference's calculator/meta.py (Meta.energy over analysis/kde.py's Gaussian_kde)
     restated for the built-in collective variables.  This function is the definition:
@@ -277,6 +336,7 @@ def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=
     The sums run in the kernel's order (hill h in the partial sum (h % 256, (h // 256) % 4); the mean of a posvar over the
     atoms in the library's species-sorted order, `species` = the model's table, 256 strided partial sums; fin_wave_sum's
     tree); exp and log are this host's, so the device agrees to rounding, not bit for bit.
+      merge = CH: the merged form (meta_density has the rule and the order; meta_table the entries); None: today's bits.
     Returns dict(cv [D], energy, forces [N, 3] = -dV/dx, stress [6] = Voigt of -(1/V_cell) sum_i x_i (x) F_i — formed as the
     kernel forms it: d (x) F_i for a distance, cv (x) dV/dcv for a posvar —, virial [9], dcv [D] = dV/dcv, kde, and margin:
     the smallest distance, in units of sigma, of a CV component from a bin edge k sigma or a block edge k 5 sigma — a
@@ -321,7 +381,7 @@ def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=
             d0 += 3
         else:
             raise ValueError(f"meta_bias: a component is ('distance', i, j) or ('posvar', index, select), not {comp!r}")
-    V, g, kde = meta_density(c, sg, w, hills, tem=tem)
+    V, g, kde = meta_density(c, sg, w, hills, tem=tem, merge=merge)
     F = np.zeros((N, 3))
     vir = np.zeros(9)
     for part in parts:

@@ -11,6 +11,8 @@ is handed to ActiveCalculator(meta=...) and a hill is deposited per configuratio
   calculate(), where the bias is added to energy, forces and stress;
 * the reference attaches meta.update to its ASE dynamics; here run_md deposits per configuration on either path and writes
   meta.hist in the reference's format (a header `# sigma`, one line of CV values per deposit);
+* merge=1024: the hills are merged by bin, 1024 at a time, as the reference's Gaussian_kde counts them — the cost of the bias
+  grows with the bins the walk has visited, not with the length of the run (meta.histogram() returns the bins and their counts);
 * teacher, system and integrator: those of examples/md_nvt_otf.py.
 """
 import argparse
@@ -46,7 +48,7 @@ def main():
     numbers, pos, cell, pbc = rocksalt(args.side, species=species)
     N = len(numbers)
     meta = Meta(Catvar(Posvar(0, select=int(numbers[0])), Distance(0, 1)), sigma=args.sigma, w=args.w, tem=args.tem,
-                hist=f"{args.out}/meta.hist")
+                hist=f"{args.out}/meta.hist", merge=1024)
     teacher = PairTeacher(species)
     calc = ActiveCalculator(calculator=teacher, kernel_kw=dict(species=species), meta=meta, logfile=f"{args.out}/active.log",   # <- meta
                             tape=None, pckl=None, ediff=0.086, fdiff=0.129)

@@ -585,11 +585,26 @@ int sgpr_md_filter_state(sgpr_model *h, double *f, double *s);
  *                     on); the capacity.  Any of them NULL.
  * sgpr_md_meta_hills  rows first ... first + count - 1 of the hills that stand: cv[count][D], V[count] (the bias the depositing
  *                     configuration saw); either NULL.
+ * sgpr_md_meta_merge  the merged form: after sgpr_md_meta and before the next sgpr_md_run (otherwise SGPR_E_INVALID; so is a
+ *                     negative chunk).  The rows are kept as before, and chunk j — the rows [j chunk, (j + 1) chunk) — is merged
+ *                     into a table of one entry per occupied bin (the reference's Gaussian_kde keeps a counter per bin) in front
+ *                     of the bias of the first configuration with (hills below it) / chunk > j; a configuration with nh hills
+ *                     below it sums the entries of the rows [0, (nh / chunk) chunk) — count times the hill of the entry's centre —
+ *                     and then the rows behind them one by one: a function of the configuration and the rows below it, whatever
+ *                     the cuts and halts.  The cost of the bias then grows with the bins visited, not with time.  The chunks of
+ *                     the uploaded hills are merged in this call: a run that goes on from sgpr_md_meta_hills with the same chunk
+ *                     has the bits of the uninterrupted one.  chunk = 0: every hill on its own again.  sgpr_md_meta switches
+ *                     merging off.  Not bit-compatible with the unmerged sum (the same terms in another order).
+ * sgpr_md_meta_table  the table as the current configuration sees it (Gaussian_kde.histogram()): *n_entries entries in the order
+ *                     of the first row that occupied each, centres[*n_entries][D], counts[*n_entries], from the first
+ *                     *rows_merged rows.  Any of them NULL: ask for *n_entries first (at most the capacity).
  * sgpr_md_end releases the hills. */
 int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const double *sigma, double w, double kT, int pace, int64_t capacity,
                  int64_t nhills, const double *hills_cv, const double *hills_V);
 int sgpr_md_meta_info(sgpr_model *h, int *D, int64_t *below, int64_t *held, int64_t *capacity);
 int sgpr_md_meta_hills(sgpr_model *h, int64_t first, int64_t count, double *cv, double *V);
+int sgpr_md_meta_merge(sgpr_model *h, int64_t chunk);
+int sgpr_md_meta_table(sgpr_model *h, double *centres, double *counts, int64_t *n_entries, int64_t *rows_merged);
 /*
  * Multi-GPU (one process per GPU, atoms sharded as in sgpr_bind_system): the reference combines the
  * ranks' partial sums with four MPI all-reduces per step (calculator/active.py:562,601,602,777,
