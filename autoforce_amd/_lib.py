@@ -29,6 +29,7 @@ SIGNATURES = {
     "sgpr_last_error": (C.c_char_p, []),
     "sgpr_version": (C.c_int, []),
     "sgpr_device_count": (C.c_int, []),
+    "sgpr_live_device_memory": (None, [C.POINTER(_i64), C.POINTER(_i64)]),
     "sgpr_create": (C.c_int, [C.c_int, C.c_int, _dbl, _dbl, C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "sgpr_destroy": (None, [_vp]),
     "sgpr_set_inducing": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
@@ -181,7 +182,8 @@ class _Traced:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name in ("sgpr_last_error", "sgpr_version", "sgpr_device_count", "sgpr_packed_len", "sgpr_destroy"):
+        if name in ("sgpr_last_error", "sgpr_version", "sgpr_device_count", "sgpr_packed_len", "sgpr_destroy",
+                    "sgpr_live_device_memory"):
             return fn
 
         def call(*a):
@@ -227,3 +229,11 @@ def i64(a):
 
 def device_count():
     return load().sgpr_device_count()
+
+
+def live_device_memory():
+    """(bytes, buffers) of device memory the library's buffers hold in this process, over all handles; both return to
+    what they were once every handle created since has been closed."""
+    nbytes, nbufs = _i64(0), _i64(0)
+    load().sgpr_live_device_memory(C.byref(nbytes), C.byref(nbufs))
+    return nbytes.value, nbufs.value

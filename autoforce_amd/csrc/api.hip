@@ -11,7 +11,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <numeric>
+#include <type_traits>
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -91,38 +93,97 @@ static int rccl_load()
     return SGPR_OK;
 }
 
+// live device memory held by DevBufs, process-wide (sgpr_live_device_memory): touched only where a DevBuf really calls hipMalloc / hipFree
+static std::atomic<int64_t> g_live_bytes{0}, g_live_bufs{0};
 
+// Every device allocation of the library: owns its memory (move-only, freed by the destructor).  None has static duration: a
+// destructor must not run after the HIP runtime has shut down.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n;
+            o.p = nullptr; o.n = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int alloc(size_t count, bool zero = true)
     {
         if (count > n || !p) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-            n = 0;
+            release();
             if (hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return -1;
             n = count;
+            g_live_bytes.fetch_add((int64_t)(std::max<size_t>(n, 1) * sizeof(T)), std::memory_order_relaxed);
+            g_live_bufs.fetch_add(1, std::memory_order_relaxed);
         }
         if (zero && count) (void)hipMemset(p, 0, count * sizeof(T));
         return 0;
     }
     void release()
     {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            g_live_bytes.fetch_sub((int64_t)(std::max<size_t>(n, 1) * sizeof(T)), std::memory_order_relaxed);
+            g_live_bufs.fetch_sub(1, std::memory_order_relaxed);
+        }
         p = nullptr;
         n = 0;
     }
 };
-// a DevBuf that is a LOCAL of one entry point: given back on every way out of the scope (the members of the handle have
-// no destructor on purpose: sgpr_destroy releases them in its own order)
+static_assert(!std::is_copy_constructible<DevBuf<double>>::value && std::is_nothrow_move_constructible<DevBuf<double>>::value,
+              "a DevBuf is an owner: moved, never copied");
+
+// Page-locked host memory, optionally mapped into the device's address space (`dev`: the same bytes as a kernel addresses
+// them).  Move-only like DevBuf; alloc() always replaces what is held (-1 with `p` kept: the memory is there, its device alias is not).
 template <typename T>
-struct ScopedBuf : DevBuf<T> {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf &) = delete;
-    ScopedBuf &operator=(const ScopedBuf &) = delete;
-    ~ScopedBuf() { this->release(); }
+struct HostBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    HostBuf(HostBuf &&o) noexcept : p(o.p), dev(o.dev), n(o.n) { o.p = o.dev = nullptr; o.n = 0; }
+    HostBuf &operator=(HostBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p; dev = o.dev; n = o.n;
+            o.p = o.dev = nullptr; o.n = 0;
+        }
+        return *this;
+    }
+    ~HostBuf() { release(); }
+    int alloc_pinned(size_t count) { return alloc(count, false); }
+    int alloc_mapped(size_t count) { return alloc(count, true); }
+    int alloc(size_t count, bool mapped)
+    {
+        release();
+        if (hipHostMalloc((void **)&p, count * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault) != hipSuccess) {
+            p = nullptr;
+            return -1;
+        }
+        n = count;
+        if (mapped && hipHostGetDevicePointer((void **)&dev, p, 0) != hipSuccess) {
+            dev = nullptr;
+            return -1;
+        }
+        return 0;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+        n = 0;
+    }
 };
 
 // The library's own exchange between the ranks of ONE node (peer.inc): every rank owns a receive buffer
@@ -175,13 +236,13 @@ struct MdState {
     unsigned chain_step = 0, chain_bind = 0, chain_opt = 0;
     long long chain_t = 0;
     const double *chain_pos = nullptr;
-    double *scal_pin = nullptr;    // [rows][SGPR_MD_SCAL] page-locked: the scalars of a call travel behind its last kernel, one wait
+    HostBuf<double> scal_pin;      // [rows][SGPR_MD_SCAL] page-locked: the scalars of a call travel behind its last kernel, one wait
     unsigned long long seed = 0;   // != 0: the integrator draws its own deviates (sgpr_md_seed)
     DevBuf<double> X, V, P, KE, mass, sig, noise, noise_raw, cell;
     DevBuf<int> halt;
-    int *halt_host = nullptr, *halt_host_dev = nullptr;
+    HostBuf<int> halt_host;                   // the halt word as the host reads it (mapped)
     DevBuf<double> scal_d;                    // [rows][SGPR_MD_SCAL] per-evaluation scalars, device memory (copied out once per run)
-    int *mark = nullptr, *mark_dev = nullptr;  // [rows] mapped host memory: evaluation j has passed its last kernel (look-ahead throttle)
+    HostBuf<int> mark;                        // [rows] mapped host memory: evaluation j has passed its last kernel (look-ahead throttle)
     size_t scal_rows = 0;
     std::vector<double> mass_sorted;
     // moving cell (sgpr_md_barostat): Nose-Hoover with the cell, the strain rate and scaled coordinates in rings of four
@@ -432,7 +493,7 @@ struct sgpr_model {
         std::vector<Op> ops;
         bool selected = false;             // a selection since the last refit (diagnostics)
         int nflat = 0;                     // flats among the ops (slots of `store` / `ysnap` in use: a stack)
-        void clear_ops() { for (auto &o : ops) o.pstore.release(); ops.clear(); nflat = 0; }
+        void clear_ops() { ops.clear(); nflat = 0; }
         uint64_t age = 0;
     };
     QrKeep qr_keep[4];
@@ -466,11 +527,9 @@ struct sgpr_model {
     // per-step work arrays (local rows)
     DevBuf<double> d_Pn, d_norm, d_C, d_K, d_Aw, d_W, d_F, d_virpart, d_Epart, d_csq, d_packed;
     int csq_slots = 1;
-    double *pin_dev = nullptr; // the same buffer as the device addresses it (zero-copy results)
-    double *pin = nullptr;     // page-locked staging of sgpr_compute: [3N + 9] in | [4N + 11] out
-    size_t pin_doubles = 0;
+    HostBuf<double> pin;       // page-locked staging of sgpr_compute: [3N + 9] in | [4N + 11] out; mapped (zero-copy results)
     int pin_flip = 0;          // which of the two output halves of `pin` the last sgpr_compute wrote
-    double *pin_old = nullptr; // the buffer `pin` replaced when a larger frame came: views of the call before stay readable until the next growth
+    HostBuf<double> pin_old;   // the buffer `pin` replaced when a larger frame came: views of the call before stay readable until the next growth
     DevBuf<int> d_shear;
     int epart_len = 0, virpart_len = 0;
     DevBuf<long long> d_stamps;  // SGPR_STAMPS=1 diagnostic
@@ -522,6 +581,8 @@ struct sgpr_model {
     std::vector<std::string> stage_names;
     std::vector<double> stage_ms;
 };
+static_assert(!std::is_copy_constructible<sgpr_model>::value && !std::is_copy_constructible<MdState>::value &&
+              !std::is_copy_constructible<PeerXchg>::value, "a handle and its parts own device memory: never copied");
 
 // ---------------------------------------------------------------------------- small kernels
 __global__ void transpose_kernel(int rows, int cols, const double *A, int lda, double *B, int ldb)
@@ -1486,6 +1547,12 @@ extern "C" int sgpr_device_count(void)
     return n;
 }
 
+extern "C" void sgpr_live_device_memory(int64_t *bytes, int64_t *buffers)
+{
+    if (bytes) *bytes = g_live_bytes.load(std::memory_order_relaxed);
+    if (buffers) *buffers = g_live_bufs.load(std::memory_order_relaxed);
+}
+
 extern "C" int sgpr_create(int lmax, int nmax, double eta, double rc, int S, const int32_t *species_z,
                            const double *radii, int device, sgpr_model **out)
 {
@@ -1641,79 +1708,16 @@ extern "C" void sgpr_destroy(sgpr_model *h)
             }
         }
     }
-    h->d_pstamps.release();
     drop_graph(h);
     for (auto e : h->ev) (void)hipEventDestroy(e);
-    DevBuf<int> *ib[] = {&h->d_ind_slot, &h->d_ind_nn, &h->d_qoff, &h->d_perm, &h->d_slot, &h->d_aoff, &h->d_lslot,
-                         &h->d_lnn, &h->d_bin_of, &h->d_bin_count, &h->d_nn_raw, &h->d_nn,
-                         &h->d_nbr_j, &h->d_nbr_shift, &h->d_stat, &h->d_shear, &h->d_kslot, &h->d_aux,
-                         &h->d_flag, &h->d_ncand, &h->d_cand_j, &h->d_cand_code, &h->d_cidx};
-    for (auto b : ib) b->release();
-    DevBuf<double> *db[] = {&h->d_radii, &h->d_Pm, &h->d_PmT, &h->d_pm_norm, &h->d_M, &h->d_mu, &h->d_choli,
-                            &h->d_vs_sqrt, &h->d_gpart, &h->d_pos_in, &h->d_cell_in, &h->d_pos, &h->d_Pn, &h->d_norm, &h->d_C, &h->d_prec, &h->d_G,
-                            &h->d_K, &h->d_Aw, &h->d_W, &h->d_F, &h->d_virpart, &h->d_Epart, &h->d_csq, &h->d_packed,
-                            &h->d_rows_ones, &h->d_rows_out, &h->d_rows_ke, &h->d_L, &h->d_R1, &h->d_edit_tmp,
-                            &h->d_rows_bG, &h->d_rows_bF, &h->d_rows_bV, &h->d_rows_kepart, &h->d_design, &h->d_qr_A, &h->d_qr_work};
-    for (auto b : db) b->release();
-    h->d_rows_cols.release();
-    h->d_rows_rowof.release(); h->d_rows_qoff.release(); h->d_rows_vpart.release();
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->pin_old) (void)hipHostFree(h->pin_old);
-    if (h->md.halt_host) (void)hipHostFree(h->md.halt_host);
-    if (h->md.mark) (void)hipHostFree(h->md.mark);
-    if (h->md.scal_pin) (void)hipHostFree(h->md.scal_pin);
-    {   // (a DevBuf has no destructor — handles are copied around as plain structs —: every buffer is released by name)
-        MdState &m = h->md;
-        DevBuf<double> *mdb[] = {&m.X, &m.V, &m.P, &m.KE, &m.mass, &m.sig, &m.noise, &m.noise_raw, &m.cell, &m.scal_d};
-        for (auto b : mdb) b->release();
-        m.halt.release();
-        m.zeta.release();
-        m.npt_ring.release(); m.Q.release(); m.cells_d.release();
-        m.fixed.release();
-        m.rec_x.release(); m.rec_v.release(); m.rec_p.release();
-        m.meta_centre.release(); m.meta_rows.release(); m.meta_key.release(); m.meta_sel.release();
-        m.meta_tab_release();
-        m.bcm_P.release(); m.bcm_x.release(); m.bcm_info_d.release();
-        m.nb_X.release(); m.nb_V.release(); m.nb_P.release(); m.nb_ends.release(); m.nb_sums.release(); m.nb_coef.release(); m.nb_info_d.release(); m.nb_par.release();
-        DevBuf<int4> *tb[] = {&h->t_knm, &h->t_w, &h->t_cov, &h->t_kmm, &h->t_wcov, &h->t_fused};
-        for (auto b : tb) b->release();
-        h->d_panel_cnt.release();
-        h->d_stamps.release(); h->d_stamps2.release();
-    }
-    {
-        DevBuf<double> *sd[] = {&h->sc_s2A, &h->sc_s2x, &h->sc_s2work, &h->sc_mv_v, &h->sc_mv_o, &h->sc_ra_y, &h->sc_ra_t, &h->sc_vs_t,
-                                &h->sc_ai_er, &h->sc_ai_p, &h->sc_ai_norm, &h->sc_ai_krow, &h->sc_ai_kself, &h->sc_y, &h->sc_bA, &h->sc_bx,
-                                &h->sc_bwork};
-        for (auto b : sd) b->release();
-        DevBuf<int> *si[] = {&h->sc_s2so, &h->sc_ai_eslot, &h->sc_ai_oslot, &h->sc_ai_onn, &h->sc_ai_info, &h->sc_sel_idx,
-                             &h->sc_sel_map, &h->sc_chol_info};
-        h->sc_sel_A.release(); h->sc_sel_work.release(); h->d_design_alt.release();
-        h->sc_dense_part.release(); h->sc_ea_y.release(); h->sc_ea_rows.release();
-        h->sc_mae_v.release(); h->sc_mae_rows.release();
-        for (auto b : si) b->release();
-        h->sc_ai_ptr.release();
-        h->sc_erow.release();
-        h->sc_ise.release();
-    }
-    for (auto &e : h->r1_cache) e.r1.release();
-    h->s2k.VT.release(); h->s2k.R1.release(); h->sc_s2W.release(); h->sc_s2flag.release(); h->sc_potrf.release();
-    for (auto &k : h->qr_keep) { k.clear_ops(); k.erows.release(); k.store.release(); k.Rc.release(); k.yt.release(); k.yraw.release(); k.ysnap.release(); k.vec.release(); }
-    h->d_pack.release();
-    h->t_covl.release();
-    h->d_T.release();
-    h->d_hm.release();
-    h->d_pos0.release();
-    h->d_cell0.release();
-    h->d_b_rec.release();
-    h->d_b_aux.release();
-    h->d_grid.release();
     if (h->comm) (void)g_rccl.CommDestroy(h->comm);
     (void)sgpr_peer_destroy(h);
-    h->d_xpacked.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    // every buffer of the handle frees itself inside `delete h`: after the synchronisation above, with the handle's device
+    // current and the streams gone (hipFree and hipHostFree need no stream)
     delete h;
 }
 
@@ -2074,11 +2078,8 @@ extern "C" int sgpr_set_inducing(sgpr_model *h, int m, const int32_t *zc, const 
     if (n_ind_slot.alloc(m_rows_n) || n_ind_nn.alloc(m_rows_n) || n_qoff.alloc(h->S + 1) ||
         n_Pm.alloc((size_t)m_rows_n * h->Dpad) || n_PmT.alloc((size_t)rup(h->Dpad, 64) * m_pad_n) ||
         n_pm_norm.alloc(m_rows_n) || n_M.alloc((size_t)m_rows_n * m_pad_n) || n_mu.alloc(std::max(m_pad_n, m_rows_n)) ||
-        n_choli.alloc((size_t)m_rows_n * m_pad_n)) {
-        n_ind_slot.release(); n_ind_nn.release(); n_qoff.release(); n_Pm.release(); n_PmT.release(); n_pm_norm.release();
-        n_M.release(); n_mu.release(); n_choli.release();
+        n_choli.alloc((size_t)m_rows_n * m_pad_n))
         return fail(SGPR_E_NODEVICE, "hipMalloc failed (inducing set): the previous set is untouched");
-    }
     // ---- commit
     drop_graph(h);
     h->has_mu = h->has_choli = false;
@@ -2086,9 +2087,9 @@ extern "C" int sgpr_set_inducing(sgpr_model *h, int m, const int32_t *zc, const 
     h->chol_shape = false;
     h->m = m; h->m_pad = m_pad_n; h->m_rows = m_rows_n;
     h->ind_perm.swap(ind_perm_n); h->ind_slot.swap(ind_slot_n); h->qoff.swap(qoff_n);
-    auto take = [](auto &dst, auto &src) { dst.release(); dst = src; src.p = nullptr; src.n = 0; };
-    take(h->d_ind_slot, n_ind_slot); take(h->d_ind_nn, n_ind_nn); take(h->d_qoff, n_qoff); take(h->d_Pm, n_Pm);
-    take(h->d_PmT, n_PmT); take(h->d_pm_norm, n_pm_norm); take(h->d_M, n_M); take(h->d_mu, n_mu); take(h->d_choli, n_choli);
+    h->d_ind_slot = std::move(n_ind_slot); h->d_ind_nn = std::move(n_ind_nn); h->d_qoff = std::move(n_qoff);
+    h->d_Pm = std::move(n_Pm); h->d_PmT = std::move(n_PmT); h->d_pm_norm = std::move(n_pm_norm);
+    h->d_M = std::move(n_M); h->d_mu = std::move(n_mu); h->d_choli = std::move(n_choli);
     {   // keep the caller's list for the edit entry points (copy first: the inputs may alias h->env_*)
         const int64_t lo = m > 0 ? nbr_ptr[0] : 0, hi = m > 0 ? nbr_ptr[m] : 0;
         std::vector<int32_t> ezc(zc, zc + m), ez(nbr_z + lo, nbr_z + hi);
@@ -2200,8 +2201,8 @@ extern "C" int sgpr_get_kmm_rowsum(sgpr_model *h, double *sums)
     if (m <= 0) return SGPR_OK;
     std::vector<int> inv(m);
     for (int a = 0; a < m; a++) inv[h->ind_perm[a]] = a;
-    ScopedBuf<int> d_inv;
-    ScopedBuf<double> d_out;
+    DevBuf<int> d_inv;
+    DevBuf<double> d_out;
     if (d_inv.alloc(m) || d_out.alloc(m)) return fail(SGPR_E_NODEVICE, "hipMalloc failed");
     HIPCHK(hipMemcpyAsync(d_inv.p, inv.data(), sizeof(int) * m, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(kmm_rowsum_kernel, dim3((m + 63) / 64), dim3(64), 0, h->stream, m, h->d_M.p, h->m_pad, d_inv.p, d_out.p);
@@ -2222,7 +2223,6 @@ extern "C" int sgpr_get_inducing_descriptors(sgpr_model *h, double *P)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(buf.data(), d.p, sizeof(double) * buf.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < h->m; k++) memcpy(P + row * h->ind_perm[k], buf.data() + row * k, sizeof(double) * row);
-    d.release();
     return SGPR_OK;
 }
 
@@ -3025,22 +3025,16 @@ static int compute_core(sgpr_model *h, int N, const int32_t *numbers, const doub
     // way, ONE synchronisation; the step's own overflow word (packed[4N+10], finalize) says whether the capacities
     // held — if not, or on the first call, the checked path below re-sizes and repeats
     const size_t n_in = (size_t)3 * N + 9, n_out = (size_t)4 * N + 11 + 6;
-    if (h->pin_doubles < n_in + 2 * n_out) {
+    if (h->pin.n < n_in + 2 * n_out) {
         // (the stream is idle here: every call ends synchronised.  The outgoing buffer is kept for one more generation: a view
         // handed out by the previous call stays valid "until the call after next" also across a growth)
-        if (h->pin_old) (void)hipHostFree(h->pin_old);
-        h->pin_old = h->pin;
-        h->pin = nullptr; h->pin_doubles = 0;
-        if (hipHostMalloc((void **)&h->pin, sizeof(double) * (n_in + 2 * n_out + 64), hipHostMallocMapped) == hipSuccess) {
-            h->pin_doubles = n_in + 2 * n_out + 64;
-            h->pin_dev = nullptr;
-            if (hipHostGetDevicePointer((void **)&h->pin_dev, h->pin, 0) != hipSuccess) h->pin_dev = nullptr;
-        }
+        h->pin_old = std::move(h->pin);
+        (void)h->pin.alloc_mapped(n_in + 2 * n_out + 64);   // (without the device's alias the copies below take over)
     }
-    if (!h->pin) return fail(SGPR_E_NODEVICE, "sgpr_compute: no page-locked host memory");
+    if (!h->pin.p) return fail(SGPR_E_NODEVICE, "sgpr_compute: no page-locked host memory");
     h->pin_flip ^= 1;
     const size_t off_out = n_in + (size_t)h->pin_flip * n_out;
-    double *pi = h->pin, *po = h->pin + off_out;
+    double *pi = h->pin.p, *po = h->pin.p + off_out;
     *po_out = po;
     auto finish = [&]() {   // stress behind the packed results (calculator/active.py:604-610)
         sgpr_stress_from_virial(po + 4 * (size_t)N + 1, cell, po + 4 * (size_t)N + 11);
@@ -3057,15 +3051,15 @@ static int compute_core(sgpr_model *h, int N, const int32_t *numbers, const doub
         // SGPR_ZERO_COPY_IN=0: the copy command), which takes a DMA command and its enqueue out of every call
         if (tl) tls[1] = nowus();
         static const bool zin = !(getenv("SGPR_ZERO_COPY_IN") && atoi(getenv("SGPR_ZERO_COPY_IN")) == 0);
-        const bool in_direct = zin && h->pin_dev;
+        const bool in_direct = zin && h->pin.dev;
         if (!in_direct) HIPCHK(hipMemcpyAsync(h->d_pos_in.p, pi, sizeof(double) * n_in, hipMemcpyHostToDevice, h->stream));
         if (tl) tls[2] = nowus();
         // single rank: the last kernel writes the packed results straight into the page-locked buffer (host memory
         // mapped into the device's address space: posted PCIe writes inside the kernel) — no device-to-host copy
         // command behind the step, one synchronisation point less on the way out (option "zero_copy_out")
-        const bool direct = h->zero_copy_out && !h->comm && !peer_on(h) && h->world == 1 && h->pin_dev;
-        const double *pos_src = in_direct ? h->pin_dev : h->d_pos_in.p;
-        int rf = enqueue_step(h, pos_src, pos_src + 3 * (size_t)N, direct ? h->pin_dev + off_out : h->d_packed.p, h->stream);
+        const bool direct = h->zero_copy_out && !h->comm && !peer_on(h) && h->world == 1 && h->pin.dev;
+        const double *pos_src = in_direct ? h->pin.dev : h->d_pos_in.p;
+        int rf = enqueue_step(h, pos_src, pos_src + 3 * (size_t)N, direct ? h->pin.dev + off_out : h->d_packed.p, h->stream);
         if (rf) { poison_peers(h, N); return rf; }   // (a local enqueue failure: the peers are about to enter the all-reduce)
         rf = reduce_packed(h, h->d_packed.p, h->stream);
         if (rf) { h->warm = false; h->lists_valid = false; return rf; }
@@ -3383,7 +3377,6 @@ extern "C" int sgpr_get_descriptors(sgpr_model *h, double *P)
     memset(P, 0, sizeof(double) * row * h->N);
     for (int il = 0; il < h->cnt; il++)
         memcpy(P + row * h->perm[h->rank + il * h->world], buf.data() + row * il, sizeof(double) * row);
-    d.release();
     return SGPR_OK;
 }
 

@@ -81,7 +81,7 @@ static int design_reserve(sgpr_model *h, int64_t rows, int64_t cols, int64_t kee
     if (rows <= h->design_rcap && cols <= h->design_ccap && h->d_design.p) return SGPR_OK;
     const int64_t rcap = rows > h->design_rcap ? ((rows + rows / 2 + 63) / 64 * 64) : h->design_rcap;
     const int64_t ccap = cols > h->design_ccap ? ((cols + cols / 2 + 32 + 31) / 32 * 32) : h->design_ccap;
-    ScopedBuf<double> nb;
+    DevBuf<double> nb;
     // (the second buffer of the selection pair has the OLD capacity: useless after this growth, and the first thing to give
     // back when memory is short — it is allocated again by the next selection)
     h->d_design_alt.release();
@@ -94,9 +94,7 @@ static int design_reserve(sgpr_model *h, int64_t rows, int64_t cols, int64_t kee
     if (h->d_design.p && h->design_rows > 0 && keep_cols > 0)
         HIPCHK(hipMemcpy2D(nb.p, sizeof(double) * rcap, h->d_design.p, sizeof(double) * h->design_rcap,
                            sizeof(double) * h->design_rows, keep_cols, hipMemcpyDeviceToDevice));
-    h->d_design.release();
-    h->d_design = nb;
-    nb.p = nullptr;
+    h->d_design = std::move(nb);
     h->design_rcap = rcap;
     h->design_ccap = ccap;
     return SGPR_OK;
@@ -232,16 +230,14 @@ extern "C" int sgpr_data_pop(sgpr_model *h, int index)
     const int64_t r0 = h->frames[index].row0, nr = h->frames[index].rows, tail = h->design_rows - (r0 + nr);
     if (tail > 0 && h->m > 0 && h->d_design.p) {
         // the rows behind the frame move up: through a new buffer (the ranges overlap), rare (popfirst_1data)
-        ScopedBuf<double> nb;
+        DevBuf<double> nb;
         if (nb.alloc((size_t)h->design_rcap * h->design_ccap, false)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (resident design matrix)");
         if (r0 > 0)
             HIPCHK(hipMemcpy2D(nb.p, sizeof(double) * h->design_rcap, h->d_design.p, sizeof(double) * h->design_rcap,
                                sizeof(double) * r0, h->m, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy2D(nb.p + r0, sizeof(double) * h->design_rcap, h->d_design.p + r0 + nr, sizeof(double) * h->design_rcap,
                            sizeof(double) * tail, h->m, hipMemcpyDeviceToDevice));
-        h->d_design.release();
-        h->d_design = nb;
-        nb.p = nullptr;
+        h->d_design = std::move(nb);
     }
     h->frames.erase(h->frames.begin() + index);
     h->frame_ids.erase(h->frame_ids.begin() + index);
@@ -504,7 +500,7 @@ extern "C" int sgpr_data_get(sgpr_model *h, double *K)
     const int m = h->m;
     if (rows == 0 || m <= 0) return SGPR_OK;
     HIPCHK(hipSetDevice(h->device));
-    ScopedBuf<double> d_t;
+    DevBuf<double> d_t;
     if (d_t.alloc((size_t)rows * m, false)) return fail(SGPR_E_NODEVICE, "hipMalloc failed");
     // [m][rcap] -> [rows][m]
     hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((rows + 31) / 32), (m + 31) / 32), dim3(32, 8), 0, h->stream, m, (int)rows,
@@ -512,7 +508,6 @@ extern "C" int sgpr_data_get(sgpr_model *h, double *K)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(K, d_t.p, sizeof(double) * (size_t)rows * m, hipMemcpyDeviceToHost));
-    d_t.release();
     return SGPR_OK;
 }
 
@@ -686,7 +681,7 @@ static int qr_keep_append(sgpr_model *h, sgpr_model::QrKeep *k, int c, int64_t i
     HIPCHK(hipGetLastError());
     sgpr_model::QrKeep::Op op;
     op.kind = 0; op.k0 = k0; op.flat_ix = na; op.snap = 1;
-    k->ops.push_back(op);
+    k->ops.push_back(std::move(op));
     k->nflat++;
     k->store_used += (size_t)(k->ldr + 8);
     k->ncols++;
@@ -752,7 +747,6 @@ static int qr_keep_select(sgpr_model *h, sgpr_model::QrKeep *k, int count, const
     if (d_idx.alloc(count, false) || d_A.alloc((size_t)cpad * ldr2, false) ||
         d_work.alloc(lstsq_qr_blocked_work_doubles(R2, count), false) || op.pstore.alloc((size_t)R2 * ldr2, false) ||
         h->sc_dense_part.alloc((size_t)DENSE_QT_CHUNKS * 2176, false)) {
-        op.pstore.release();
         k->valid = false;  // no room: the next refit factors from scratch
         return SGPR_OK;
     }
@@ -764,7 +758,6 @@ static int qr_keep_select(sgpr_model *h, sgpr_model::QrKeep *k, int count, const
     double *E = d_A.p + (size_t)(count + 1) * ldr2;
     hipLaunchKernelGGL(identity_cols_kernel, dim3((R2 + 255) / 256), dim3(256), 0, st, R2, E, ldr2);
     if (launch_lstsq_qr_blocked(R2, count, d_A.p, ldr2, nullptr, d_work.p, st, 0, nullptr, nullptr, R2)) {
-        op.pstore.release();
         k->valid = false;
         return SGPR_OK;
     }
@@ -780,7 +773,7 @@ static int qr_keep_select(sgpr_model *h, sgpr_model::QrKeep *k, int count, const
         nan_check("selected yt", k->yt.p, (size_t)k->ldr);
     }
     for (auto &o : k->ops) o.snap = 0;  // the snapshots are in the basis from before the selection
-    k->ops.push_back(op);
+    k->ops.push_back(std::move(op));
     k->selected = true;
     k->ncols = count;
     k->col_ids = new_ids;

@@ -15,11 +15,7 @@ static int md_alloc(sgpr_model *h, int N)
     bad |= m.KE.alloc((size_t)8 * N); bad |= m.mass.alloc(N); bad |= m.sig.alloc(N); bad |= m.cell.alloc(9);
     bad |= m.halt.alloc(4); bad |= m.zeta.alloc(8);
     if (bad) return fail(SGPR_E_NODEVICE, "sgpr_md_begin: device allocation failed");
-    if (!m.halt_host) {
-        if (hipHostMalloc((void **)&m.halt_host, 64, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&m.halt_host_dev, m.halt_host, 0) != hipSuccess)
-            return fail(SGPR_E_NODEVICE, "sgpr_md_begin: no mapped host memory");
-    }
+    if (!m.halt_host.p && m.halt_host.alloc_mapped(16)) return fail(SGPR_E_NODEVICE, "sgpr_md_begin: no mapped host memory");
     return SGPR_OK;
 }
 
@@ -416,7 +412,7 @@ extern "C" int sgpr_md_relax_reset(sgpr_model *h)
 // MD_HALT_NONE: [0] the covloss gate, [1] a capacity overflow, [2] a relaxation's convergence (no MD kernel writes it); the
 // device has its own copy of the first two (m.halt).  The earliest one halted the run.
 static const int MD_HALT_NONE = 0x7fffffff;
-static int md_halt_step(const MdState &m) { return std::min(std::min(m.halt_host[0], m.halt_host[1]), m.halt_host[2]); }
+static int md_halt_step(const MdState &m) { return std::min(std::min(m.halt_host.p[0], m.halt_host.p[1]), m.halt_host.p[2]); }
 
 // For the length of a call the positions handed to the binning kernel are in sorted order already (the rings); on every way
 // out the handle is an ordinary one again: no pre-binned configuration, no grid of a moving cell.
@@ -442,24 +438,22 @@ static int md_prepare_call(sgpr_model *h, int nevals, hipStream_t st, bool want_
     }
     const size_t rows = (size_t)nevals + 1;
     if (m.scal_rows < rows) {
-        if (m.mark) (void)hipHostFree(m.mark);
-        if (m.scal_pin) (void)hipHostFree(m.scal_pin);
-        m.mark = nullptr; m.scal_pin = nullptr; m.scal_rows = 0;
-        if (m.scal_d.alloc((size_t)SGPR_MD_SCAL * rows, false) ||
-            hipHostMalloc((void **)&m.mark, sizeof(int) * rows, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&m.mark_dev, m.mark, 0) != hipSuccess ||
-            hipHostMalloc((void **)&m.scal_pin, sizeof(double) * SGPR_MD_SCAL * rows, hipHostMallocDefault) != hipSuccess)
+        m.mark.release();
+        m.scal_pin.release();
+        m.scal_rows = 0;
+        if (m.scal_d.alloc((size_t)SGPR_MD_SCAL * rows, false) || m.mark.alloc_mapped(rows) ||
+            m.scal_pin.alloc_pinned((size_t)SGPR_MD_SCAL * rows))
             return fail(SGPR_E_NODEVICE, "sgpr_md_run: no memory for the scalar ring");
         m.scal_rows = rows;
     }
     HIPCHK(hipMemsetAsync(m.scal_d.p, 0, sizeof(double) * SGPR_MD_SCAL * rows, st));
-    memset(m.mark, 0, sizeof(int) * rows);
+    memset(m.mark.p, 0, sizeof(int) * rows);
     if (want_cells) {
         if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
         HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
     }
-    m.halt_host[0] = m.halt_host[1] = m.halt_host[2] = MD_HALT_NONE;   // (page-locked: the source of the copy outlives the call)
-    HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    m.halt_host.p[0] = m.halt_host.p[1] = m.halt_host.p[2] = MD_HALT_NONE;   // (page-locked: the source of the copy outlives the call)
+    HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host.p, 2 * sizeof(int), hipMemcpyHostToDevice, st));
     return SGPR_OK;
 }
 
@@ -476,7 +470,7 @@ static int md_look_ahead(int N) { return std::min(6, std::max(2, (int)lround(245
 // every 16384 spins the stream is asked: one that is empty with the mark still unset, or in error, ends the wait with an error.
 static int md_wait_for(const MdState &m, hipStream_t st, int e, bool *halted)
 {
-    const volatile int *mark = m.mark + e, *hh = m.halt_host;
+    const volatile int *mark = m.mark.p + e, *hh = m.halt_host.p;
     auto running = [hh] { return hh[0] == MD_HALT_NONE && hh[1] == MD_HALT_NONE && hh[2] == MD_HALT_NONE; };
     unsigned spins = 0;
     while (*mark == 0 && running()) {
@@ -517,7 +511,7 @@ static int md_collect(sgpr_model *h, int enq, hipStream_t st, const double *scal
 {
     MdState &m = h->md;
     if (scalars && enq > 0)
-        HIPCHK(hipMemcpyAsync(m.scal_pin, m.scal_d.p, sizeof(double) * SGPR_MD_SCAL * (size_t)enq, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(m.scal_pin.p, m.scal_d.p, sizeof(double) * SGPR_MD_SCAL * (size_t)enq, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     if (want_cells) {
@@ -542,7 +536,7 @@ static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval
     if (hv != MD_HALT_NONE) {
         r.k = hv - (int)step0;
         if (r.k < 0 || r.k >= enq) return fail(SGPR_E_INVALID, "sgpr_md_run: inconsistent halt record (%d of %d)", r.k, enq);
-        r.code = m.halt_host[1] == hv ? 2 : (m.halt_host[0] == hv ? 1 : 3);
+        r.code = m.halt_host.p[1] == hv ? 2 : (m.halt_host.p[0] == hv ? 1 : 3);
         r.done = r.k + 1;
         m.t += r.k;
         // a capacity overflowed: the next call's checked pass grows it, and the overflowing evaluation's own results are void
@@ -607,7 +601,7 @@ static void md_fill_integrator(const MdState &m, int j, const double *noise_dev,
 static void md_finish_call(MdState &m, const MdHalt &r, double *scalars, bool keep_14_15, bool evaluated, int *evals_done, int *halt_code)
 {
     if (scalars && r.done > 0) {
-        memcpy(scalars, m.scal_pin, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
+        memcpy(scalars, m.scal_pin.p, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
         if (!keep_14_15)
             for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
     }
@@ -687,8 +681,8 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
         // (held components, sgpr_md_fix: the FIX forms; without a mask the kernels of a run without one)
         hipLaunchKernelGGL(m.n_fixed ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p,
                            (const double *)packed, (const int *)h->d_perm.p,
-                           (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host_dev,
-                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark_dev + j, stay ? 1 : 0,
+                           (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host.dev,
+                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark.dev + j, stay ? 1 : 0,
                            m.fix());
         if (!stay)
             hipLaunchKernelGGL(m.n_fixed ? md_fire_move_kernel<true> : md_fire_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell,
@@ -845,7 +839,7 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         const int step = (int)(step0 + j);
         double *packed = m.P.p + plen * sl, *info = m.bcm_info_d.p + (size_t)BCM_INFO * j, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
         hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, packed, info, gate, m.halt.p,
-                           m.halt_host_dev, step, row, m.mark_dev + j);
+                           m.halt_host.dev, step, row, m.mark.dev + j);
         FinNext x;
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         x.step = step;   // (the fused loop: enqueue_step sets it)
@@ -1065,8 +1059,8 @@ static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, d
         const NebBand b = {N, K, plen, band, m.nb_ends.p, Pk, h->d_perm.p, m.fix()};
         hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, st, b, m.nb_cell, m.nb_sums.p, (const int *)m.halt.p, step);
         hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, st, b, (const NebFirePar *)m.nb_par.p, m.rx_state.p, (const double *)m.nb_V.p,
-                           (const double *)m.nb_sums.p, m.nb_coef.p, m.nb_info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host_dev, step,
-                           m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.mark_dev + j, stay ? 1 : 0);
+                           (const double *)m.nb_sums.p, m.nb_coef.p, m.nb_info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host.dev, step,
+                           m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.mark.dev + j, stay ? 1 : 0);
         if (!stay)
             hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, st, b, m.nb_cell, (const double *)m.rx_state.p,
                                (const double *)m.nb_coef.p, m.nb_V.p, m.nb_X.p + N3 * K * sn, (const int *)m.halt.p, step);
@@ -1180,9 +1174,9 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
         x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
         x.ediff = ediff > 0.0 ? ediff : 1e300;
-        x.halt_host = m.halt_host_dev;
+        x.halt_host = m.halt_host.dev;
         x.scal_cur = m.scal_d.p + (size_t)SGPR_MD_SCAL * j; x.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (j > 0 ? j - 1 : 0);
-        x.mark_cur = m.mark_dev + j;
+        x.mark_cur = m.mark.dev + j;
         // (the last evaluation of a `final` run integrates speculatively too: its outcome is not adopted below)
         const int re = enqueue_step(h, x.x_cur, cell_of(m.t + j), m.P.p + plen * sl, st, &nx);
         if (re) return re;
@@ -1211,7 +1205,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         const int sl = (int)((m.t + enq - 1) % RG);
         f.nx.mode = 3; f.nx.step = (int)(step0 + enq);
         f.nx.ke_prev = m.KE.p + (size_t)2 * N * sl; f.nx.packed_prev = m.P.p + plen * sl;
-        f.nx.ediff = ediff > 0.0 ? ediff : 1e300; f.nx.halt = m.halt.p; f.nx.halt_host = m.halt_host_dev;
+        f.nx.ediff = ediff > 0.0 ? ediff : 1e300; f.nx.halt = m.halt.p; f.nx.halt_host = m.halt_host.dev;
         f.nx.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (enq - 1);
         hipLaunchKernelGGL(finalize_tail_kernel, dim3(2), dim3(256), 0, st, f);
     }
@@ -1394,7 +1388,7 @@ extern "C" int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, doubl
     MdState &m = h->md;
     if (!m.active || m.seed == 0) return fail(SGPR_E_INVALID, "sgpr_md_deviates: call sgpr_md_begin and sgpr_md_seed first");
     HIPCHK(hipSetDevice(h->device));
-    ScopedBuf<double> d;
+    DevBuf<double> d;
     if (d.alloc((size_t)count * 3 * m.N, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_deviates: device allocation failed");
     hipLaunchKernelGGL(md_deviates_kernel, dim3(1024), dim3(256), 0, h->stream, m.N, count, m.seed, (long long)t_first, d.p);
     HIPCHK(hipMemcpy(out, d.p, sizeof(double) * (size_t)count * 3 * m.N, hipMemcpyDeviceToHost));

@@ -219,7 +219,7 @@ static int solve_stage1(sgpr_model *h, int rows, Fill fill)
 static int solve_stage1_host(sgpr_model *h, int rows, const double *K, const double *Y)
 {
     const int m = h->m;
-    ScopedBuf<double> d_y, d_Kh;
+    DevBuf<double> d_y, d_Kh;
     if (d_y.alloc(std::max(rows, 1), false) || d_Kh.alloc(std::max((size_t)rows * m, (size_t)1), false))
         return fail(SGPR_E_NODEVICE, "hipMalloc failed (least squares, %d x %d)", rows, m);
     const int rc_ = solve_stage1(h, rows, [&](double *At, int ldr, hipStream_t st) -> int {
@@ -229,7 +229,7 @@ static int solve_stage1_host(sgpr_model *h, int rows, const double *K, const dou
                            d_Kh.p, d_y.p, At, ldr);
         return 0;
     });
-    d_y.release(); d_Kh.release();
+    d_y.release(); d_Kh.release();   // (in this order, as ever: the addresses later allocations get depend on it)
     return rc_;
 }
 
@@ -243,8 +243,8 @@ extern "C" int sgpr_jitcholesky(sgpr_model *h, int n, const double *A, double *L
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const int ld = rup(n, 64);
-    ScopedBuf<double> dA, dL, dsave;
-    ScopedBuf<int> dinfo;
+    DevBuf<double> dA, dL, dsave;
+    DevBuf<int> dinfo;
     if (dA.alloc((size_t)(ld + 64) * ld) || dL.alloc((size_t)(ld + 64) * ld) || dinfo.alloc(1) || dsave.alloc(2 * 64 * 64))
         return fail(SGPR_E_NODEVICE, "hipMalloc failed (jitcholesky)");
     HIPCHK(hipMemcpy2D(dA.p, sizeof(double) * ld, A, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
@@ -799,7 +799,7 @@ static int kernel_rows_range(sgpr_model *h, int N, const int32_t *numbers, const
     const size_t rowlen = (size_t)4 * N + 11;
     DevBuf<double> &d_rows = h->d_rows_out, &d_ke = h->d_rows_ke;
     // forces of all columns, transposed on the device into the caller's [3N][q_count] layout: one copy, no host loop
-    ScopedBuf<double> d_kft;
+    DevBuf<double> d_kft;
     if (Kf && q_count > 0) {
         if (d_kft.alloc((size_t)3 * N * q_count, false)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (training rows)");
         hipLaunchKernelGGL(transpose_kernel, dim3((3 * N + 31) / 32, (q_count + 31) / 32), dim3(32, 8), 0, st, q_count, 3 * N,
@@ -1354,9 +1354,9 @@ extern "C" int sgpr_kernel_local(sgpr_model *h, int32_t zc, int nn, const int32_
     }
     const int m = h->m;
     const int64_t ptr[2] = {0, nn};
-    ScopedBuf<int64_t> d_ptr;
-    ScopedBuf<int> d_eslot;
-    ScopedBuf<double> d_er, d_p, d_norm, d_out;
+    DevBuf<int64_t> d_ptr;
+    DevBuf<int> d_eslot;
+    DevBuf<double> d_er, d_p, d_norm, d_out;
     if (d_ptr.alloc(2, false) || d_eslot.alloc(std::max(nn, 1), false) || d_er.alloc(3 * (size_t)std::max(nn, 1), false) ||
         d_p.alloc(64 * (size_t)h->Dpad) || d_norm.alloc(64) || d_out.alloc(m + 1))
         return fail(SGPR_E_NODEVICE, "hipMalloc failed (local kernel)");

@@ -47,6 +47,11 @@ int sgpr_version(void);
 /* Number of usable gfx950 devices (0 if none; never initialises a context). */
 int sgpr_device_count(void);
 
+/* Device memory this process holds through the library's buffers, over all handles: bytes as allocated and the number of
+ * allocations (either pointer may be NULL).  Page-locked host memory and the exchange buffer of sgpr_peer_export are not
+ * counted.  After sgpr_destroy of every handle both are zero: a test of "nothing leaks" is a difference of two calls. */
+void sgpr_live_device_memory(int64_t *bytes, int64_t *buffers);
+
 /*
  * Create a model = kernel hyper-parameters + species table.
  * Replaces: calculator/active.py:28-38 default_kernel(lmax,nmax,exponent,cutoff) ->

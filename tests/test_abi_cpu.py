@@ -33,6 +33,23 @@ def test_version_and_packed_len():
     assert lib.sgpr_packed_len(4096) == 4 * 4096 + 11
 
 
+def test_live_device_memory_is_bound():
+    """sgpr_live_device_memory needs no GPU: either pointer may be NULL, and the package's wrapper returns (bytes, buffers)."""
+    import ctypes as C
+    import autoforce_amd
+    from autoforce_amd import _lib
+    lib = _lib.load()
+    assert _lib.SIGNATURES["sgpr_live_device_memory"] == (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
+    nbytes, nbufs = autoforce_amd.live_device_memory()
+    assert isinstance(nbytes, int) and isinstance(nbufs, int) and nbytes >= 0 and nbufs >= 0 and (nbytes == 0) == (nbufs == 0)
+    one = C.c_int64(-1)
+    lib.sgpr_live_device_memory(None, None)
+    lib.sgpr_live_device_memory(C.byref(one), None)
+    assert one.value >= 0
+    lib.sgpr_live_device_memory(None, C.byref(one))
+    assert one.value >= 0
+
+
 def test_stress_from_virial_host_helper():
     """calculator/active.py:574,604-610: Voigt picks [0,4,8,5,2,1] of virial/volume; volume -2
     for a rank-deficient cell."""
