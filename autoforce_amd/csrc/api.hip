@@ -210,10 +210,11 @@ struct PeerXchg {
     const double *slice(int parity, int r) const { return (const double *)base + ((size_t)parity * world + r) * cap; }
 };
 
-// device-resident molecular dynamics (sgpr_md_*): positions / velocities / results of the last three evaluations in
-// rings (sorted atom order), see FinNext
-struct MdState {
-    bool active = false;
+// device-resident molecular dynamics (sgpr_md_*), in two parts.  MdRun: what ONE run is — its system, its clock, and per mode
+// (named as its attach function) the flag and the settings of that mode; plain values, so that sgpr_md_begin starts a run by
+// assigning a fresh one and a new mode adds a struct here and nothing there.  MdState: what the HANDLE keeps from run to run —
+// the device and pinned buffers, grouped under the same mode names, whose capacity the next run reuses — and the run itself.
+struct MdRun {
     int N = 0;
     // the system the run was begun on: another evaluation on the handle in between (a model update computes training rows
     // of stored frames, trial models rebind) leaves the handle bound to something else — sgpr_md_run binds it back
@@ -225,113 +226,139 @@ struct MdState {
     double hdt = 0.0, c1 = 1.0, dt = 0.0;
     int ring = 3;                  // slots of the X / V / P / KE rings in use: 3 (Langevin / velocity Verlet), 4 (Nose-Hoover: the
                                    //   speculative step behind a halt must not overwrite x_(k-1), which the restart needs)
-    // Nose-Hoover NVT (sgpr_md_thermostat): zeta_(n+1) = zeta_(n-1) + 2 dt tfact (KE_n - K0), rings of four in `zeta`
-    bool nh = false;
-    double nh_c1 = 0.0, nh_c2 = 0.0, nh_K0 = 0.0;   // dt tfact, 2 dt tfact, desired kinetic energy
-    DevBuf<double> zeta;           // [4] zeta by evaluation index & 3 | [4] its time integral
     bool evaluated = false;        // the current configuration has been evaluated by the last sgpr_md_run (halted / final)
+    bool started = false;          // sgpr_md_run has been called since sgpr_md_begin
+    std::vector<double> mass_sorted;
     // a run that is cut into several sgpr_md_run calls goes on where the last call stopped — candidate lists, the bins its last
     // kernel filled for the next configuration — when nothing else has touched the handle in between
-    bool chain_ok = false;
-    unsigned chain_step = 0, chain_bind = 0, chain_opt = 0;
-    long long chain_t = 0;
-    const double *chain_pos = nullptr;
-    HostBuf<double> scal_pin;      // [rows][SGPR_MD_SCAL] page-locked: the scalars of a call travel behind its last kernel, one wait
-    unsigned long long seed = 0;   // != 0: the integrator draws its own deviates (sgpr_md_seed)
-    DevBuf<double> X, V, P, KE, mass, sig, noise, noise_raw, cell;
-    DevBuf<int> halt;
-    HostBuf<int> halt_host;                   // the halt word as the host reads it (mapped)
-    DevBuf<double> scal_d;                    // [rows][SGPR_MD_SCAL] per-evaluation scalars, device memory (copied out once per run)
-    HostBuf<int> mark;                        // [rows] mapped host memory: evaluation j has passed its last kernel (look-ahead throttle)
-    size_t scal_rows = 0;
-    std::vector<double> mass_sorted;
+    struct Chain { bool ok = false; unsigned step = 0, bind = 0, opt = 0; long long t = 0; const double *pos = nullptr; } chain;
+    // Nose-Hoover NVT (sgpr_md_thermostat): zeta_(n+1) = zeta_(n-1) + 2 dt tfact (KE_n - K0), rings of four in MdState::zeta
+    struct Nh { bool on = false; double c1 = 0.0, c2 = 0.0, K0 = 0.0; } nh;   // dt tfact, 2 dt tfact, desired kinetic energy
     // moving cell (sgpr_md_barostat): Nose-Hoover with the cell, the strain rate and scaled coordinates in rings of four
     // (NptSlot, sgpr_internal.h, has the argument for four)
-    bool npt = false, npt_started = false;
-    NptParams np = {};
-    double npt_pfactor = 0.0;
-    DevBuf<char> npt_ring;         // [4] NptSlot by evaluation index & 3
-    DevBuf<double> Q;              // [4][N][3] scaled coordinates q = x h^-1 - 1/2, sorted order, beside X
-    DevBuf<double> cells_d;        // [rows][SGPR_MD_CELL] cell and strain rate per evaluation of a call (device memory)
-    std::vector<double> cells;     // ... of the last call, and the evaluation index of its first row
-    long long cells_first = 0;
-    NptSlot *slot(long long n) const { return (NptSlot *)npt_ring.p + (n & 3); }
+    struct Npt {
+        bool on = false, started = false;
+        NptParams par = {};
+        double pfactor = 0.0;
+        std::vector<double> cells;     // cell and strain rate per evaluation of the last call (a relaxation's too), and the
+        long long cells_first = 0;     // evaluation index of its first row
+    } npt;
     // FIRE relaxation (sgpr_md_relax, md_relax.inc): the run is a minimisation, not dynamics — rings of RLX_RING slots
-    bool relax = false;
-    bool relax_started = false;
-    RelaxParams rp = {};
-    DevBuf<double> rx_state;       // [RLX_LEN] the optimizer's scalars, the cell rows of X and their velocity, the move's coefficients
-    DevBuf<double> rx_ref;         // [N][3] positions referred to the first cell (r = x D^-T), sorted order; their velocity is V's slot 0
-    DevBuf<double> rx_cells;       // [RLX_RING][RLX_CELL] cell and deformation gradient by evaluation index % RLX_RING
-    // held components (sgpr_md_fix): the mask in sorted atom order, on the device and here; n_fixed = 0: nothing is held and
-    // every launch is the one of a run without a mask
-    bool started = false;          // sgpr_md_run has been called since sgpr_md_begin
-    int n_fixed = 0;
-    DevBuf<unsigned char> fixed;   // [N][3]
-    std::vector<unsigned char> fixed_sorted;
-    const unsigned char *fix() const { return n_fixed ? fixed.p : nullptr; }
-    // the filter of model-update jumps (sgpr_md_filter): accumulated force jumps in a ring beside X (sorted order, slot = evaluation
-    // index % ring), accumulated stress jumps of a moving-cell run in a ring of four (evaluation index & 3) — at constant cell
-    // nobody asks for a stress and filt_s_host is handed back as it came; the run's own permutation on the device for the pushes
-    bool filter = false;
-    double shrink = 0.0;
-    DevBuf<double> filt_f, filt_s, filt_in;   // [4][N][3], [4][6], [N][3] a push's caller-order upload
-    DevBuf<int> filt_perm;                    // [N] sorted -> caller
-    double filt_s_host[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    // metadynamics (sgpr_md_meta, md_meta.inc): the hills in rows indexed by configuration — meta_pre rows uploaded at the attach,
-    // which took place at configuration meta_base; then one per configuration n with n % meta_pace == 0
-    bool meta = false, meta_fresh = false;   // (fresh: attached, no sgpr_md_run since)
-    MetaPar mp = {};
-    int meta_pace = 1;
-    long long meta_base = 0, meta_pre = 0, meta_cap = 0;
-    DevBuf<double> meta_centre, meta_rows;   // [cap][D] centres (room for 6), [cap][7] CV | V
-    DevBuf<int> meta_key;                    // [cap][D] super-block keys (room for 6)
-    DevBuf<unsigned char> meta_sel;          // [ncomp][N] posvar: the atoms of the mean, sorted order
-    // the merged form (sgpr_md_meta_merge): the table of md_meta.inc, one entry per occupied bin, room for every row in a bin of its own
-    int meta_merge = 0;                      // the chunk length (0: every hill on its own)
-    long long meta_enq = 0;                  // chunks whose merge this call has enqueued or found done (the device word decides)
-    DevBuf<double> meta_tcentre, meta_tcnt, meta_tlast;
-    DevBuf<int> meta_tkey, meta_tstamp, meta_ctl;
+    struct Relax { bool on = false, started = false; RelaxParams par = {}; } relax;   // (par: a band's FIRE too, cell = 0)
+    // held components (sgpr_md_fix): the mask in sorted atom order, here and in MdState::fixed; n = 0: nothing is held and every
+    // launch is the one of a run without a mask
+    struct Fix { int n = 0; std::vector<unsigned char> sorted; } fix;
+    // the filter of model-update jumps (sgpr_md_filter); at constant cell nobody asks for a stress and s_host is handed back as it came
+    struct Filter {
+        bool on = false;
+        double shrink = 0.0;
+        double s_host[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    } filter;
+    // metadynamics (sgpr_md_meta, md_meta.inc): the hills in rows indexed by configuration — `pre` rows uploaded at the attach,
+    // which took place at configuration `base`; then one per configuration n with n % pace == 0
+    struct Meta {
+        bool on = false, fresh = false;   // (fresh: attached, no sgpr_md_run since)
+        MetaPar par = {};
+        int pace = 1;
+        long long base = 0, pre = 0, cap = 0;
+        int merge = 0;                    // the merged form (sgpr_md_meta_merge): the chunk length (0: every hill on its own)
+        long long enq = 0;                // chunks whose merge this call has enqueued or found done (the device word decides)
+    } meta;
+    // the frame record (sgpr_md_record, md_record.inc): every `every`-th configuration of a call, copied out behind its evaluation
+    // in caller atom order — positions always, velocities / results by the bits of `what`.  call_*: what the LAST sgpr_md_run
+    // recorded (sgpr_md_frames serves that call: its first trajectory index, its settings, the frames that stand)
+    struct Rec {
+        int every = 0, what = 0;
+        long long call_t0 = 0;
+        int call_every = 0, call_what = 0, call_count = 0;
+    } rec;
+    // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
+    // at every configuration (empty: the run is the one without a committee and launches what it launched before)
+    struct Bcm {
+        std::vector<struct sgpr_model *> members;
+        std::vector<double> info;  // weights | largest covlosses of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
+    } bcm;
+    // the nudged elastic band (sgpr_md_neb, md_neb.inc): K interior images evaluated by this one handle per evaluation of the band
+    struct Neb {
+        bool on = false;
+        int K = 0;
+        NebCell cell = {};
+        std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_neb_info)
+    } neb;
+    static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
+    long long meta_slot(long long n) const { return meta.pre + meta_dep(n, meta.pace) - meta_dep(meta.base, meta.pace); }
+    // multiples of `every` in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
+    static long long rec_between(long long a, long long b, int every) { return (b + every - 1) / every - (a + every - 1) / every; }
+};
+static_assert(std::is_default_constructible<MdRun>::value && std::is_nothrow_move_assignable<MdRun>::value,
+              "a run is plain values, replaced by assignment: no DevBuf or HostBuf in it (they live in MdState)");
+
+struct MdState {
+    bool active = false;           // `run` is a run begun by sgpr_md_begin and not ended
+    // != 0: the integrator draws its own deviates (sgpr_md_seed).  NOT part of the run: sgpr_md_seed needs no active run, and a
+    // seed set before sgpr_md_begin holds for the run begun after it
+    unsigned long long seed = 0;
+    MdRun run;
+    // positions / velocities / results of the last three (four) evaluations in rings (sorted atom order), see FinNext
+    DevBuf<double> X, V, P, KE, mass, sig, noise, noise_raw, cell;
+    DevBuf<double> zeta;           // [4] Nose-Hoover's zeta by evaluation index & 3 | [4] its time integral
+    DevBuf<int> halt;
+    HostBuf<int> halt_host;        // the halt word as the host reads it (mapped)
+    DevBuf<double> scal_d;         // [rows][SGPR_MD_SCAL] per-evaluation scalars, device memory (copied out once per run)
+    HostBuf<double> scal_pin;      // [rows][SGPR_MD_SCAL] page-locked: the scalars of a call travel behind its last kernel, one wait
+    HostBuf<int> mark;             // [rows] mapped host memory: evaluation j has passed its last kernel (look-ahead throttle)
+    size_t scal_rows = 0;
+    struct {
+        DevBuf<char> ring;         // [4] NptSlot by evaluation index & 3
+        DevBuf<double> Q;          // [4][N][3] scaled coordinates q = x h^-1 - 1/2, sorted order, beside X
+        DevBuf<double> cells_d;    // [rows][SGPR_MD_CELL] cell and strain rate per evaluation of a call (a relaxation's too)
+    } npt;
+    struct {
+        DevBuf<double> state;      // [RLX_LEN] the optimizer's scalars, the cell rows of X and their velocity, the move's coefficients (a band's too)
+        DevBuf<double> ref;        // [N][3] positions referred to the first cell (r = x D^-T), sorted order; their velocity is V's slot 0
+        DevBuf<double> cells;      // [RLX_RING][RLX_CELL] cell and deformation gradient by evaluation index % RLX_RING
+    } relax;
+    struct { DevBuf<unsigned char> mask; } fixed;   // [N][3] (the group of sgpr_md_fix: fix() below is what the launches take)
+    // accumulated force jumps in a ring beside X (sorted order, slot = evaluation index % ring), accumulated stress jumps of a
+    // moving-cell run in a ring of four (evaluation index & 3), the run's own permutation on the device for the pushes
+    struct {
+        DevBuf<double> f, s, in;   // [4][N][3], [4][6], [N][3] a push's caller-order upload
+        DevBuf<int> perm;          // [N] sorted -> caller
+    } filter;
+    struct MetaBufs {
+        DevBuf<double> centre, rows;   // [cap][D] centres (room for 6), [cap][7] CV | V
+        DevBuf<int> key;               // [cap][D] super-block keys (room for 6)
+        DevBuf<unsigned char> sel;     // [ncomp][N] posvar: the atoms of the mean, sorted order
+        // the table of the merged form (md_meta.inc): one entry per occupied bin, room for every row in a bin of its own
+        DevBuf<double> tcentre, tcnt, tlast;
+        DevBuf<int> tkey, tstamp, ctl;
+        bool held() const { return rows.p != nullptr; }   // (every attach allocates the rows)
+    } meta;
+    struct { DevBuf<double> x, v, p; } rec;   // [frames][N][3] x 2, [frames][4N + 11]: one copy per array fetches a call
+    struct {
+        DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
+        DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
+        DevBuf<double> info_d;     // [rows][32] weights | largest covlosses per evaluation of a call
+    } bcm;
+    struct {                       // band, velocity and results in caller atom order
+        DevBuf<double> X;          // [RLX_RING][K][N][3] the band by evaluation index % RLX_RING
+        DevBuf<double> V;          // [K][N][3] FIRE's velocity
+        DevBuf<double> P;          // [RLX_RING][K][4N + 11] packed results of the images' plain steps
+        DevBuf<double> ends;       // [2][N][3] images 0 and K + 1
+        DevBuf<double> sums;       // [K][NEB_SUMS] md_neb_sums_kernel's output
+        DevBuf<double> coef;       // [K][2] the projection's coefficients
+        DevBuf<char> par;          // one NebFirePar: cell, FIRE's keywords, spring constant, climb — md_neb_fire_kernel's constants
+        DevBuf<double> info_d;     // [rows][NEB_INFO] E | covmax per evaluation of a call
+    } neb;
+    NptSlot *slot(long long n) const { return (NptSlot *)npt.ring.p + (n & 3); }
+    const unsigned char *fix() const { return run.fix.n ? fixed.mask.p : nullptr; }
     MetaTab meta_tab(long long want) const
     {
         MetaTab tb;
-        tb.centre = meta_tcentre.p; tb.key = meta_tkey.p; tb.cnt = meta_tcnt.p; tb.last = meta_tlast.p; tb.stamp = meta_tstamp.p;
-        tb.ctl = meta_ctl.p; tb.ch = meta_merge; tb.want = (int)want;
+        tb.centre = meta.tcentre.p; tb.key = meta.tkey.p; tb.cnt = meta.tcnt.p; tb.last = meta.tlast.p; tb.stamp = meta.tstamp.p;
+        tb.ctl = meta.ctl.p; tb.ch = run.meta.merge; tb.want = (int)want;
         return tb;
     }
-    void meta_tab_release() { meta_tcentre.release(); meta_tcnt.release(); meta_tlast.release(); meta_tkey.release(); meta_tstamp.release(); meta_ctl.release(); }
-    static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
-    long long meta_slot(long long n) const { return meta_pre + meta_dep(n, meta_pace) - meta_dep(meta_base, meta_pace); }
-    // the frame record (sgpr_md_record, md_record.inc): every rec_every-th configuration of a call, copied out behind its
-    // evaluation in caller atom order — rec_x always, rec_v / rec_p by the bits of rec_what.  rec_call_*: what the LAST
-    // sgpr_md_run recorded (sgpr_md_frames serves that call: its first trajectory index, its settings, the frames that stand)
-    int rec_every = 0, rec_what = 0;
-    DevBuf<double> rec_x, rec_v, rec_p;   // [frames][N][3] x 2, [frames][4N + 11]: one copy per array fetches a call
-    long long rec_call_t0 = 0;
-    int rec_call_every = 0, rec_call_what = 0, rec_call_count = 0;
-    // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
-    // at every configuration (empty: the run is the one without a committee and launches what it launched before)
-    std::vector<struct sgpr_model *> bcm;
-    DevBuf<double> bcm_P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
-    DevBuf<double> bcm_x;          // [N][3] the current positions in caller atom order: what the members bin
-    DevBuf<double> bcm_info_d;     // [rows][32] weights | largest covlosses per evaluation of a call
-    std::vector<double> bcm_info;  // ... of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
-    // the nudged elastic band (sgpr_md_neb, md_neb.inc): K interior images evaluated by this one handle per evaluation of the band;
-    // band, velocity and results in caller atom order, the optimizer's scalars in rx_state and rp (a relaxation's, cell = 0)
-    bool neb = false;
-    int nb_K = 0;
-    NebCell nb_cell = {};
-    DevBuf<double> nb_X;           // [RLX_RING][K][N][3] the band by evaluation index % RLX_RING
-    DevBuf<double> nb_V;           // [K][N][3] FIRE's velocity
-    DevBuf<double> nb_P;           // [RLX_RING][K][4N + 11] packed results of the images' plain steps
-    DevBuf<double> nb_ends;        // [2][N][3] images 0 and K + 1
-    DevBuf<double> nb_sums;        // [K][NEB_SUMS] md_neb_sums_kernel's output
-    DevBuf<double> nb_coef;        // [K][2] the projection's coefficients
-    DevBuf<char> nb_par;           // one NebFirePar: cell, FIRE's keywords, spring constant, climb — md_neb_fire_kernel's constants
-    DevBuf<double> nb_info_d;      // [rows][NEB_INFO] E | covmax per evaluation of a call
-    std::vector<double> nb_info;   // ... of the last call's evaluations that stand (sgpr_md_neb_info)
-    // multiples of rec_every in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
-    static long long rec_between(long long a, long long b, int every) { return (b + every - 1) / every - (a + every - 1) / every; }
 };
 
 struct sgpr_model {
@@ -394,7 +421,7 @@ struct sgpr_model {
     double skin = 0.5;          // Angstrom; 0: rebuild every step (option "skin_milliangstrom")
     bool lists_valid = false;   // false: the next step is told to rebuild (new frame, capacity change)
     unsigned step_count = 0;
-    unsigned bind_gen = 0, opt_gen = 0;   // sgpr_bind_system calls / option changes that void kept lists (MdState::chain_*)
+    unsigned bind_gen = 0, opt_gen = 0;   // sgpr_bind_system calls / option changes that void kept lists (MdRun::chain)
     DevBuf<int> d_flag, d_ncand, d_cand_j, d_cand_code, d_cidx;
     DevBuf<double> d_pos0, d_cell0;
     DevBuf<unsigned long long> d_hm;
@@ -2744,28 +2771,28 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
     if (nx && nx->mode == 2 && nx->md.filt_cur && !(fuse && gather))
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
-    if (nx && nx->mode == 2 && h->md.meta) {
+    if (nx && nx->mode == 2 && h->md.run.meta.on) {
         // the bias of this configuration (sgpr_md_meta), behind the reverse pass's own sums and in front of the kernel that reads them
         const MdState &m = h->md;
         if (!(fuse && gather))
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
                                             "and sharded frames take the host loop around calculate()");
         const long long n = nx->md.t_index;
-        if (m.meta_merge) {
+        if (m.run.meta.merge) {
             // the chunks that lie below this configuration and are not merged yet: at a crossing, or at the first configuration
             // of a call that is behind
-            const long long want = m.meta_slot(n) / m.meta_merge;
-            for (long long &j = h->md.meta_enq; j < want; j++) {
-                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.mp.D, m.meta_merge, (int)j, (const double *)m.meta_centre.p,
-                                   (const int *)m.meta_key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
+            const long long want = m.run.meta_slot(n) / m.run.meta.merge;
+            for (long long &j = h->md.run.meta.enq; j < want; j++) {
+                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.run.meta.par.D, m.run.meta.merge, (int)j, (const double *)m.meta.centre.p,
+                                   (const int *)m.meta.key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
                 stamp(h, "md_meta_merge", st);
             }
-            hipLaunchKernelGGL(md_meta_merged_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
-                               m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
+            hipLaunchKernelGGL(md_meta_merged_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
+                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
                                h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
         } else
-            hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.mp, nx->md.x_cur, (const unsigned char *)m.meta_sel.p,
-                               m.meta_centre.p, m.meta_key.p, m.meta_rows.p, (int)m.meta_slot(n), n % m.meta_pace == 0 ? (int)m.meta_slot(n) : -1,
+            hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
+                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
                                h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
         stamp(h, "md_meta", st);
     }

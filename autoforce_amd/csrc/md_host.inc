@@ -1,6 +1,11 @@
-// md_host.inc — the host side of the device-resident loops (sgpr_md_*: MD, moving-cell NPT, FIRE relaxation), included by
-// api.hip behind the step's entry points.  The kernels are in api.hip, md_npt.inc, md_relax.inc and md_record.inc (the one
-// small kernel of sgpr_md_filter_push stands beside it, at the end).
+// md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
+// One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
+// sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell), _fix (held components),
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _committee (the Bayesian committee), _neb
+// (the nudged elastic band).  sgpr_md_run drives dynamics itself and hands a relaxation, a committee and a band to md_relax_run,
+// md_committee_run and md_neb_run; the four share the look-ahead driver and the frame of a call (MdCall).  The kernels are in
+// api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc and md_meta.inc (the one small kernel of
+// sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
 // from util/aseutil.py:11-20) and crosses into the calculator once per step.  Here the state (positions, velocities)
@@ -34,15 +39,20 @@ static bool md_same_system(const sgpr_model *h, int N, const int32_t *numbers, c
 static int md_rebind(sgpr_model *h)
 {
     const MdState &m = h->md;
-    if (md_same_system(h, m.N, m.numbers.data(), m.pbc, m.rank, m.world)) return SGPR_OK;
-    return sgpr_bind_system(h, m.N, m.numbers.data(), m.pbc, m.rank, m.world);
+    if (md_same_system(h, m.run.N, m.run.numbers.data(), m.run.pbc, m.run.rank, m.run.world)) return SGPR_OK;
+    return sgpr_bind_system(h, m.run.N, m.run.numbers.data(), m.run.pbc, m.run.rank, m.run.world);
 }
 
 extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const double *positions, const double *cell,
                              const int32_t *pbc, const double *masses, const double *velocities, double dt,
                              double friction, double kT)
 {
-    if (!h || N <= 0 || !numbers || !positions || !cell)   // (masses = NULL: ones — a relaxation, sgpr_md_relax, has no use for them)
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_begin: bad arguments");
+    // The new run is put in place at the very end, whole: whatever fails on the way leaves the handle with NO run (the rings of
+    // the earlier one are overwritten from md_alloc on), and the other entry points answer "call sgpr_md_begin first".
+    MdState &m = h->md;
+    m.active = false;
+    if (N <= 0 || !numbers || !positions || !cell)   // (masses = NULL: ones — a relaxation, sgpr_md_relax, has no use for them)
         return fail(SGPR_E_INVALID, "sgpr_md_begin: bad arguments");
     if (!(dt > 0.0) || friction < 0.0 || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_begin: dt > 0, friction >= 0, kT >= 0");
     HIPCHK(hipSetDevice(h->device));
@@ -53,22 +63,13 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
     if (rc_) return rc_;
     rc_ = md_alloc(h, N);
     if (rc_) return rc_;
-    MdState &m = h->md;
-    m.numbers.assign(numbers, numbers + N);
-    m.perm = h->perm;
-    for (int k = 0; k < 3; k++) m.pbc[k] = pbc ? (pbc[k] != 0) : 1;
-    m.rank = tr; m.world = tw;
-    m.N = N; m.t = 0; m.dt = dt; m.hdt = 0.5 * dt; m.c1 = exp(-friction * dt);
-    m.ring = 3; m.nh = false; m.evaluated = false;
-    m.npt = false; m.npt_started = false; m.cells.clear();
-    m.relax = false; m.relax_started = false;
-    m.neb = false; m.nb_info.clear();
-    m.started = false; m.n_fixed = 0; m.fixed_sorted.clear();
-    m.rec_every = 0; m.rec_what = 0; m.rec_call_every = 0; m.rec_call_what = 0; m.rec_call_count = 0;
-    m.bcm.clear(); m.bcm_info.clear();
-    m.filter = false; m.shrink = 0.0;
-    m.meta = false;
-    const double c2 = sqrt(1.0 - m.c1 * m.c1);
+    MdRun run;   // (every mode off, every setting at its default: no mode is named here)
+    run.numbers.assign(numbers, numbers + N);
+    run.perm = h->perm;
+    for (int k = 0; k < 3; k++) run.pbc[k] = pbc ? (pbc[k] != 0) : 1;
+    run.rank = tr; run.world = tw;
+    run.N = N; run.dt = dt; run.hdt = 0.5 * dt; run.c1 = exp(-friction * dt);
+    const double c2 = sqrt(1.0 - run.c1 * run.c1);
     std::vector<double> xs((size_t)3 * N), vs((size_t)3 * N, 0.0), ms(N), sg(N);
     for (int i = 0; i < N; i++) {
         const int c = h->perm[i];
@@ -80,12 +81,13 @@ extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const
         if (!(ms[i] > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_begin: mass of atom %d is not positive", c);
         sg[i] = friction > 0.0 ? c2 * sqrt(kT / ms[i]) : 0.0;   // (as workloads.langevin_nvt: c2 * np.sqrt(kT / mass))
     }
-    m.mass_sorted = ms;
     HIPCHK(hipMemcpy(m.X.p, xs.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.V.p, vs.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.mass.p, ms.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.sig.p, sg.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.cell.p, cell, sizeof(double) * 9, hipMemcpyHostToDevice));
+    run.mass_sorted = std::move(ms);
+    m.run = std::move(run);
     m.active = true;
     h->pre_valid = false;
     return SGPR_OK;
@@ -108,29 +110,29 @@ extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_fix: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
-    if (m.nh || m.npt || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
-    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_neb");
-    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run has a committee (sgpr_md_committee), which runs without a mask");
-    const int N = m.N;
+    if (m.run.nh.on || m.run.npt.on || m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
+    if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_neb");
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run has a committee (sgpr_md_committee), which runs without a mask");
+    const int N = m.run.N;
     std::vector<unsigned char> fs((size_t)3 * N, 0);
     int n = 0;
     if (fixed3N)
         for (int i = 0; i < N; i++)
             for (int k = 0; k < 3; k++)
-                if (fixed3N[3 * (size_t)m.perm[i] + k]) { fs[3 * (size_t)i + k] = 1; n++; }
+                if (fixed3N[3 * (size_t)m.run.perm[i] + k]) { fs[3 * (size_t)i + k] = 1; n++; }
     if (n == 3 * N) return fail(SGPR_E_INVALID, "sgpr_md_fix: every component is held, nothing is left to move");
-    if (n == 0) { m.n_fixed = 0; m.fixed_sorted.clear(); return SGPR_OK; }
+    if (n == 0) { m.run.fix.n = 0; m.run.fix.sorted.clear(); return SGPR_OK; }
     HIPCHK(hipSetDevice(h->device));
-    if (m.fixed.alloc((size_t)3 * N)) return fail(SGPR_E_NODEVICE, "sgpr_md_fix: device allocation failed");
-    HIPCHK(hipMemcpy(m.fixed.p, fs.data(), (size_t)3 * N, hipMemcpyHostToDevice));
+    if (m.fixed.mask.alloc((size_t)3 * N)) return fail(SGPR_E_NODEVICE, "sgpr_md_fix: device allocation failed");
+    HIPCHK(hipMemcpy(m.fixed.mask.p, fs.data(), (size_t)3 * N, hipMemcpyHostToDevice));
     std::vector<double> v((size_t)3 * N);
     HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     for (size_t e = 0; e < (size_t)3 * N; e++)
         if (fs[e]) v[e] = 0.0;
     HIPCHK(hipMemcpy(m.V.p, v.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
-    m.n_fixed = n;
-    m.fixed_sorted = fs;
+    m.run.fix.n = n;
+    m.run.fix.sorted = fs;
     return SGPR_OK;
 }
 
@@ -144,18 +146,18 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     if (!h || (kind != 0 && kind != 1)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: kind is 0 (Langevin / velocity Verlet) or 1 (Nose-Hoover)");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call sgpr_md_begin first");
-    if (m.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
-    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
-    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a nudged elastic band (sgpr_md_neb)");
-    if (!m.bcm.empty()) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call it before sgpr_md_committee");
-    if (kind == 0) { m.nh = false; m.npt = false; m.ring = 3; return SGPR_OK; }
+    if (m.run.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
+    if (m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
+    if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a nudged elastic band (sgpr_md_neb)");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call it before sgpr_md_committee");
+    if (kind == 0) { m.run.nh.on = false; m.run.npt.on = false; m.run.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
     // (held components, sgpr_md_fix: g = 3N - n_fixed degrees of freedom, none removed for the centre of mass — momentum is
     // not conserved beside a held atom; the project's own definition, ASE's NPT takes no constraints)
-    const double g = (double)(3 * m.N - m.n_fixed);
+    const double g = (double)(3 * m.run.N - m.run.fix.n);
     const double tfact = 2.0 / (g * kT * ttime * ttime);
-    m.nh = true; m.ring = 4;
-    m.nh_c1 = m.dt * tfact; m.nh_c2 = 2.0 * m.dt * tfact; m.nh_K0 = m.n_fixed ? 0.5 * g * kT : 1.5 * (double)(m.N - 1) * kT;
+    m.run.nh.on = true; m.run.ring = 4;
+    m.run.nh.c1 = m.run.dt * tfact; m.run.nh.c2 = 2.0 * m.run.dt * tfact; m.run.nh.K0 = m.run.fix.n ? 0.5 * g * kT : 1.5 * (double)(m.run.N - 1) * kT;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
     return SGPR_OK;
@@ -171,14 +173,14 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
 {
     if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.nh || m.relax) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
-    if (m.t != 0 || m.npt_started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.world);
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell");
-    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
-    if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.n_fixed);
+    if (!m.active || !m.run.nh.on || m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
+    if (m.run.t != 0 || m.run.npt.started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.run.world);
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell");
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
+    if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
-    if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
+    if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
     double c[9];
     HIPCHK(hipMemcpy(c, m.cell.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -186,17 +188,17 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
         return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be upper triangular (h[1][0] = h[2][0] = h[2][1] = 0)");
     const double det = (c[0] * c[4]) * c[8];
     if (!(det > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell's diagonal must be positive");
-    if (m.npt_ring.alloc(4 * sizeof(NptSlot)) || m.Q.alloc((size_t)12 * m.N)) return fail(SGPR_E_NODEVICE, "sgpr_md_barostat: device allocation failed");
-    NptParams &p = m.np;
+    if (m.npt.ring.alloc(4 * sizeof(NptSlot)) || m.npt.Q.alloc((size_t)12 * m.run.N)) return fail(SGPR_E_NODEVICE, "sgpr_md_barostat: device allocation failed");
+    NptParams &p = m.run.npt.par;
     p = NptParams();
-    p.dt = m.dt; p.c1 = m.nh_c1; p.c2 = m.nh_c2; p.K0 = m.nh_K0;
+    p.dt = m.run.dt; p.c1 = m.run.nh.c1; p.c2 = m.run.nh.c2; p.K0 = m.run.nh.K0;
     p.pfact = 1.0 / (pfactor * det);
     for (int k = 0; k < 6; k++) p.ext[k] = externalstress[k];
     for (int k = 0; k < 9; k++) p.mask[k] = mask ? (mask[k] != 0.0 ? 1.0 : 0.0) : 1.0;
     p.frac = frac_traceless;
     for (int k = 0; k < 3; k++) p.pbc[k] = 1;
-    m.npt_pfactor = pfactor;
-    m.npt = true; m.npt_started = false;
+    m.run.npt.pfactor = pfactor;
+    m.run.npt.on = true; m.run.npt.started = false;
     return SGPR_OK;
 }
 
@@ -219,12 +221,12 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
 {
 #pragma clang fp contract(off)
     MdState &m = h->md;
-    const int N = m.N;
+    const int N = m.run.N;
     NptSlot s0 = {};
     HIPCHK(hipMemcpy(s0.h, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
-    npt_matrices(m.np.dt, s0.h, s0.eta, 0.0, s0.hinv, s0.bm1, s0.bp1inv);
+    npt_matrices(m.run.npt.par.dt, s0.h, s0.eta, 0.0, s0.hinv, s0.bm1, s0.bp1inv);
     s0.thr2_keep = s0.thr2_reb = -1.0;
-    HIPCHK(hipMemset(m.npt_ring.p, 0, 4 * sizeof(NptSlot)));
+    HIPCHK(hipMemset(m.npt.ring.p, 0, 4 * sizeof(NptSlot)));
     HIPCHK(hipMemcpy(m.slot(0), &s0, sizeof(NptSlot), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.slot(1)->h, s0.h, 9 * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(m.zeta.p, 0, 8 * sizeof(double)));
@@ -235,16 +237,16 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
     HIPCHK(hipMemcpy(x.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(F.data(), m.P.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));   // (packed forces: caller order)
-    if (m.filter) {   // the forces the integrator sees at configuration 0 (finalize_next_kernel<7>'s operations; slot 0 stays as it is)
+    if (m.run.filter.on) {   // the forces the integrator sees at configuration 0 (finalize_next_kernel<7>'s operations; slot 0 stays as it is)
         std::vector<double> a0((size_t)3 * N);
-        HIPCHK(hipMemcpy(a0.data(), m.filt_f.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(a0.data(), m.filter.f.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
         for (int i = 0; i < N; i++)
             for (int k = 0; k < 3; k++) {
-                const double an = a0[3 * (size_t)i + k] * m.shrink;
-                F[3 * (size_t)m.perm[i] + k] = F[3 * (size_t)m.perm[i] + k] - std::min(std::max(an, -1.0), 1.0);
+                const double an = a0[3 * (size_t)i + k] * m.run.filter.shrink;
+                F[3 * (size_t)m.run.perm[i] + k] = F[3 * (size_t)m.run.perm[i] + k] - std::min(std::max(an, -1.0), 1.0);
             }
     }
-    const double dt = m.np.dt;
+    const double dt = m.run.npt.par.dt;
     auto row_mul = [](const double *r, const double *mat, double *o) {
 #pragma clang fp contract(off)
         for (int k = 0; k < 3; k++) o[k] = (r[0] * mat[k] + r[1] * mat[3 + k]) + r[2] * mat[6 + k];
@@ -257,8 +259,8 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
     std::vector<double> vb = v;
     for (int pass = 0; pass < 2; pass++) {
         for (int i = 0; i < N; i++) {
-            const int c = m.perm[i];
-            const double ms = m.mass_sorted[i];
+            const int c = m.run.perm[i];
+            const double ms = m.run.mass_sorted[i];
             const double *qi = &q[3 * (size_t)i];
             double *qpi = &qp[3 * (size_t)i];
             double t[3], a[3], al[3], num[3], qn[3], dq[3], vc[3];
@@ -277,15 +279,15 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
         }
         if (0.5 * md_host_order_sum(ke) / N < 1e-5) break;
     }
-    HIPCHK(hipMemcpy(m.Q.p, q.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m.Q.p + (size_t)9 * N, qp.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.npt.Q.p, q.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.npt.Q.p + (size_t)9 * N, qp.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     // the grids of h_0 and h_1 and the rebuild rule of evaluation 0 (which rebuilds: the first of its call)
-    hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p, (const double *)nullptr,
+    hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p, (const double *)nullptr,
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)h->d_cell0.p, -1,
                        (const int *)m.halt.p, -1, (double *)nullptr, (double *)nullptr, (const double *)nullptr, (double *)nullptr, 0.0);
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
-    m.npt_started = true;
+    m.run.npt.started = true;
     return SGPR_OK;
 }
 
@@ -296,25 +298,25 @@ extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *ou
 {
     if (!h || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_cells: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !(m.npt || m.relax)) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat (or sgpr_md_relax) first");
+    if (!m.active || !(m.run.npt.on || m.run.relax.on)) return fail(SGPR_E_INVALID, "sgpr_md_cells: call sgpr_md_begin and sgpr_md_barostat (or sgpr_md_relax) first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const long long have = (long long)(m.cells.size() / SGPR_MD_CELL);
+    const long long have = (long long)(m.run.npt.cells.size() / SGPR_MD_CELL);
     for (int r = 0; r < count; r++) {
         const long long n = (long long)first + r;
         double *o = out + (size_t)SGPR_MD_CELL * r;
-        if (n >= m.cells_first && n < m.cells_first + have)
-            memcpy(o, m.cells.data() + (size_t)SGPR_MD_CELL * (n - m.cells_first), sizeof(double) * SGPR_MD_CELL);
-        else if (m.relax && n == m.t)   // a relaxation: the cell and, in the place of eta, the deformation gradient D
-            HIPCHK(hipMemcpy(o, m.rx_cells.p + (size_t)RLX_CELL * (n % RLX_RING), RLX_CELL * sizeof(double), hipMemcpyDeviceToHost));
-        else if (!m.relax && n == m.t && m.npt_started) {
+        if (n >= m.run.npt.cells_first && n < m.run.npt.cells_first + have)
+            memcpy(o, m.run.npt.cells.data() + (size_t)SGPR_MD_CELL * (n - m.run.npt.cells_first), sizeof(double) * SGPR_MD_CELL);
+        else if (m.run.relax.on && n == m.run.t)   // a relaxation: the cell and, in the place of eta, the deformation gradient D
+            HIPCHK(hipMemcpy(o, m.relax.cells.p + (size_t)RLX_CELL * (n % RLX_RING), RLX_CELL * sizeof(double), hipMemcpyDeviceToHost));
+        else if (!m.run.relax.on && n == m.run.t && m.run.npt.started) {
             HIPCHK(hipMemcpy(o, m.slot(n)->h, 9 * sizeof(double), hipMemcpyDeviceToHost));
             HIPCHK(hipMemcpy(o + 9, m.slot(n)->eta, 9 * sizeof(double), hipMemcpyDeviceToHost));
-        } else if (!m.relax && n == 0 && m.t == 0) {
+        } else if (!m.run.relax.on && n == 0 && m.run.t == 0) {
             HIPCHK(hipMemcpy(o, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToHost));
             for (int k = 0; k < 9; k++) o[9 + k] = 0.0;
         } else
-            return fail(SGPR_E_INVALID, "sgpr_md_cells: configuration %lld is neither the current one (%lld) nor one of the last run's", n, m.t);
+            return fail(SGPR_E_INVALID, "sgpr_md_cells: configuration %lld is neither the current one (%lld) nor one of the last run's", n, m.run.t);
     }
     return SGPR_OK;
 }
@@ -328,16 +330,26 @@ extern "C" int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *ou
 // rank only.
 static const double RLX_ASE[8] = {0.1, 0.2, 1.0, 5.0, 1.1, 0.5, 0.1, 0.99};
 
+// The eight FIRE keywords of sgpr_md_relax and sgpr_md_neb (`who`, for the message), checked and copied into p
+static int md_fire_keywords(const char *who, const double *fire, RelaxParams &p)
+{
+    const double *fp = fire ? fire : RLX_ASE;
+    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
+        return fail(SGPR_E_INVALID, "%s: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0", who);
+    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
+    return SGPR_OK;
+}
+
 static int md_relax_init_state(sgpr_model *h)
 {
     MdState &m = h->md;
     double s[RLX_LEN] = {};
-    HIPCHK(hipMemcpy(s, m.rx_state.p, sizeof(s), hipMemcpyDeviceToHost));
-    s[RLX_DT] = m.rp.dt0; s[RLX_A] = m.rp.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
+    HIPCHK(hipMemcpy(s, m.relax.state.p, sizeof(s), hipMemcpyDeviceToHost));
+    s[RLX_DT] = m.run.relax.par.dt0; s[RLX_A] = m.run.relax.par.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
     for (int k = 0; k < 9; k++) s[RLX_VC + k] = 0.0;
     s[RLX_ALPHA] = s[RLX_BETA] = s[RLX_CD] = 0.0;
-    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(m.V.p, 0, sizeof(double) * 3 * (size_t)m.N));
+    HIPCHK(hipMemcpy(m.relax.state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.V.p, 0, sizeof(double) * 3 * (size_t)m.run.N));
     return SGPR_OK;
 }
 
@@ -346,28 +358,25 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_relax: call sgpr_md_begin first");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.world);
-    if (m.t != 0 || m.relax_started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
-    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased relaxation");
-    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
-    if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
-    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run was begun on %d ranks; a relaxation runs on one", m.run.world);
+    if (m.run.t != 0 || m.run.relax.started) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has started");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased relaxation");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
+    if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
-    const double *fp = fire ? fire : RLX_ASE;
-    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
-        return fail(SGPR_E_INVALID, "sgpr_md_relax: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0");
+    RelaxParams p = {};
+    if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int N = m.N;
-    RelaxParams p = {};
+    const int N = m.run.N;
     HIPCHK(hipMemcpy(p.h0, m.cell.p, sizeof(p.h0), hipMemcpyDeviceToHost));
     if (move_cell) {
-        if (!(m.pbc[0] && m.pbc[1] && m.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_relax: a cell that moves must be periodic in all three directions");
+        if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_relax: a cell that moves must be periodic in all three directions");
         if (!(fabs(rlx_det(p.h0)) > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: the cell is singular");
     }
     p.fmax2 = fmax * fmax;
-    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
     double m6[6];
     for (int k = 0; k < 6; k++) m6[k] = mask6 ? (mask6[k] != 0.0 ? 1.0 : 0.0) : 1.0;
     const double M[9] = {m6[0], m6[5], m6[4], m6[5], m6[1], m6[3], m6[4], m6[3], m6[2]};
@@ -377,22 +386,22 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     // rings of RLX_RING slots, every slot a valid configuration from the start (what runs behind a halt evaluates stale slots)
     std::vector<double> x0((size_t)3 * N);
     HIPCHK(hipMemcpy(x0.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
-    if (m.X.alloc((size_t)3 * N * RLX_RING) || m.P.alloc((size_t)RLX_RING * (size_t)sgpr_packed_len(N)) || m.rx_state.alloc(RLX_LEN) ||
-        m.rx_ref.alloc((size_t)3 * N) || m.rx_cells.alloc((size_t)RLX_RING * RLX_CELL))
+    if (m.X.alloc((size_t)3 * N * RLX_RING) || m.P.alloc((size_t)RLX_RING * (size_t)sgpr_packed_len(N)) || m.relax.state.alloc(RLX_LEN) ||
+        m.relax.ref.alloc((size_t)3 * N) || m.relax.cells.alloc((size_t)RLX_RING * RLX_CELL))
         return fail(SGPR_E_NODEVICE, "sgpr_md_relax: device allocation failed");
     double slot[RLX_CELL] = {};
     for (int k = 0; k < 9; k++) { slot[k] = p.h0[k]; slot[9 + k] = (k % 4 == 0) ? 1.0 : 0.0; }
     for (int r = 0; r < RLX_RING; r++) {
         HIPCHK(hipMemcpy(m.X.p + (size_t)3 * N * r, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(m.rx_cells.p + (size_t)RLX_CELL * r, slot, sizeof(slot), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.relax.cells.p + (size_t)RLX_CELL * r, slot, sizeof(slot), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMemcpy(m.rx_ref.p, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.relax.ref.p, x0.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice));
     double s[RLX_LEN] = {};
     for (int k = 0; k < 9; k++) s[RLX_XC + k] = (k % 4 == 0) ? p.cf : 0.0;
-    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
-    m.rp = p;
-    m.relax = true; m.relax_started = false; m.ring = RLX_RING;
-    m.cells.clear(); m.cells_first = 0;
+    HIPCHK(hipMemcpy(m.relax.state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    m.run.relax.par = p;
+    m.run.relax.on = true; m.run.relax.started = false; m.run.ring = RLX_RING;
+    m.run.npt.cells.clear(); m.run.npt.cells_first = 0;
     return md_relax_init_state(h);
 }
 
@@ -401,7 +410,7 @@ extern "C" int sgpr_md_relax_reset(sgpr_model *h)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.relax) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: call sgpr_md_begin and sgpr_md_relax first");
+    if (!m.active || !m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: call sgpr_md_begin and sgpr_md_relax first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     return md_relax_init_state(h);
@@ -429,11 +438,11 @@ static int md_prepare_call(sgpr_model *h, int nevals, hipStream_t st, bool want_
     MdState &m = h->md;
     // the frame record of this call (sgpr_md_record): room for the frames it can record, grown like the scalar ring and not
     // zeroed — before anything is enqueued
-    m.rec_call_t0 = m.t; m.rec_call_every = m.rec_every; m.rec_call_what = m.rec_what; m.rec_call_count = 0;
-    if (m.rec_every) {
-        const size_t fr = (size_t)MdState::rec_between(m.t, m.t + nevals, m.rec_every), N3 = (size_t)3 * m.N;
-        if (m.rec_x.alloc(fr * N3, false) || ((m.rec_what & 1) && m.rec_v.alloc(fr * N3, false)) ||
-            ((m.rec_what & 2) && m.rec_p.alloc(fr * (size_t)sgpr_packed_len(m.N), false)))
+    m.run.rec.call_t0 = m.run.t; m.run.rec.call_every = m.run.rec.every; m.run.rec.call_what = m.run.rec.what; m.run.rec.call_count = 0;
+    if (m.run.rec.every) {
+        const size_t fr = (size_t)MdRun::rec_between(m.run.t, m.run.t + nevals, m.run.rec.every), N3 = (size_t)3 * m.run.N;
+        if (m.rec.x.alloc(fr * N3, false) || ((m.run.rec.what & 1) && m.rec.v.alloc(fr * N3, false)) ||
+            ((m.run.rec.what & 2) && m.rec.p.alloc(fr * (size_t)sgpr_packed_len(m.run.N), false)))
             return fail(SGPR_E_NODEVICE, "sgpr_md_run: no device memory for the record of %zu frames", fr);
     }
     const size_t rows = (size_t)nevals + 1;
@@ -449,8 +458,8 @@ static int md_prepare_call(sgpr_model *h, int nevals, hipStream_t st, bool want_
     HIPCHK(hipMemsetAsync(m.scal_d.p, 0, sizeof(double) * SGPR_MD_SCAL * rows, st));
     memset(m.mark.p, 0, sizeof(int) * rows);
     if (want_cells) {
-        if (m.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-        HIPCHK(hipMemsetAsync(m.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
+        if (m.npt.cells_d.alloc((size_t)SGPR_MD_CELL * (size_t)nevals, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemsetAsync(m.npt.cells_d.p, 0, sizeof(double) * SGPR_MD_CELL * (size_t)nevals, st));
     }
     m.halt_host.p[0] = m.halt_host.p[1] = m.halt_host.p[2] = MD_HALT_NONE;   // (page-locked: the source of the copy outlives the call)
     HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host.p, 2 * sizeof(int), hipMemcpyHostToDevice, st));
@@ -490,7 +499,7 @@ template <typename One>
 static int md_enqueue_ahead(sgpr_model *h, int nevals, hipStream_t st, int *enq, One one)
 {
     const MdState &m = h->md;
-    const int LA = md_look_ahead(m.N);
+    const int LA = md_look_ahead(m.run.N);
     *enq = 0;
     int rc_ = SGPR_OK;
     bool halted = false;
@@ -515,16 +524,16 @@ static int md_collect(sgpr_model *h, int enq, hipStream_t st, const double *scal
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     if (want_cells) {
-        m.cells.assign((size_t)SGPR_MD_CELL * (size_t)enq, 0.0);
-        m.cells_first = m.t;
-        if (enq > 0) HIPCHK(hipMemcpy(m.cells.data(), m.cells_d.p, sizeof(double) * SGPR_MD_CELL * (size_t)enq, hipMemcpyDeviceToHost));
+        m.run.npt.cells.assign((size_t)SGPR_MD_CELL * (size_t)enq, 0.0);
+        m.run.npt.cells_first = m.run.t;
+        if (enq > 0) HIPCHK(hipMemcpy(m.run.npt.cells.data(), m.npt.cells_d.p, sizeof(double) * SGPR_MD_CELL * (size_t)enq, hipMemcpyDeviceToHost));
     }
     return SGPR_OK;
 }
 
 // What a call leaves behind its wait.  k: the evaluation, relative to this call, that halted the run (-1: none); code: 0 none,
 // 1 covloss gate, 2 overflow, 3 converged; done: the evaluations whose results stand, the halting one included unless it
-// overflowed.  m.t moves on: after a halt the state is configuration k, not evaluated as far as the NEXT call goes; otherwise
+// overflowed.  m.run.t moves on: after a halt the state is configuration k, not evaluated as far as the NEXT call goes; otherwise
 // every evaluation stands and the state is the next configuration — with final_eval the last one evaluated.
 struct MdHalt { int k = -1, code = 0, done = 0; };
 static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval, bool want_cells, MdHalt *out)
@@ -538,12 +547,12 @@ static int md_decode_halt(sgpr_model *h, unsigned step0, int enq, int final_eval
         if (r.k < 0 || r.k >= enq) return fail(SGPR_E_INVALID, "sgpr_md_run: inconsistent halt record (%d of %d)", r.k, enq);
         r.code = m.halt_host.p[1] == hv ? 2 : (m.halt_host.p[0] == hv ? 1 : 3);
         r.done = r.k + 1;
-        m.t += r.k;
+        m.run.t += r.k;
         // a capacity overflowed: the next call's checked pass grows it, and the overflowing evaluation's own results are void
         if (r.code == 2) { h->warm = false; r.done -= 1; }
     } else
-        m.t += final_eval ? enq - 1 : enq;
-    if (want_cells) m.cells.resize((size_t)SGPR_MD_CELL * (size_t)std::max(r.done, 0));
+        m.run.t += final_eval ? enq - 1 : enq;
+    if (want_cells) m.run.npt.cells.resize((size_t)SGPR_MD_CELL * (size_t)std::max(r.done, 0));
     return SGPR_OK;
 }
 
@@ -552,10 +561,10 @@ static int md_upload_noise(sgpr_model *h, int nevals, const double *noise, hipSt
 {
     MdState &m = h->md;
     if (!noise) return SGPR_OK;
-    const size_t len = (size_t)nevals * 3 * m.N;
+    const size_t len = (size_t)nevals * 3 * m.run.N;
     if (m.noise.alloc(len) || m.noise_raw.alloc(len)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
     HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * len, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, m.N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
+    hipLaunchKernelGGL(md_sort_rows_kernel, dim3(1024), dim3(256), 0, st, m.run.N, nevals, h->d_perm.p, m.noise_raw.p, m.noise.p);
     return SGPR_OK;
 }
 
@@ -569,64 +578,68 @@ static int md_reset_lists(sgpr_model *h, hipStream_t st)
     return SGPR_OK;
 }
 
-// The integrator's part of the FinNext record of evaluation j of a call (configuration m.t + j), what the fused loop's last
+// The integrator's part of the FinNext record of evaluation j of a call (configuration m.run.t + j), what the fused loop's last
 // kernel and md_bcm_move_kernel both read: ring slots, deviates (noise_dev: the call's sorted upload, null: none — then the
 // run's seed, if it has one), the Nose-Hoover block, the kinetic terms' slot, the halt word.  pend0: the closing half kick of
 // the call's first configuration is due.  Everything else in x is zero.
 static void md_fill_integrator(const MdState &m, int j, const double *noise_dev, bool pend0, FinNext &x)
 {
-    const int RG = m.ring, sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
-    const size_t N3 = (size_t)3 * m.N;
+    const int RG = m.run.ring, sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+    const size_t N3 = (size_t)3 * m.run.N;
     memset(&x, 0, sizeof(x));
     x.x_cur = m.X.p + N3 * sl; x.v_cur = m.V.p + N3 * sl;
     x.x_next = m.X.p + N3 * sn; x.v_next = m.V.p + N3 * sn;
     x.mass = m.mass.p; x.sig = m.sig.p; x.noise = noise_dev ? noise_dev + N3 * (size_t)j : nullptr;
-    x.hdt = m.hdt; x.c1 = m.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
-    if (m.nh) {
-        x.nh = 1; x.nh_first = (m.t + j) == 0 ? 1 : 0;
+    x.hdt = m.run.hdt; x.c1 = m.run.c1; x.pending = (j > 0 || pend0) ? 1 : 0;
+    if (m.run.nh.on) {
+        x.nh = 1; x.nh_first = (m.run.t + j) == 0 ? 1 : 0;
         x.x_prev = m.X.p + N3 * sp; x.v_now = m.V.p + N3 * sl;
         // (v_cur: what the integrator holds when it asks for the forces — ASE sets the momenta of step n after its force
         // call: v_(n-1), the caller's v_0 the first time; its kinetic energy is scalars[13], the calculator's log line)
-        if (m.t + j > 0) x.v_cur = m.V.p + N3 * sp;
-        x.nh_zeta = m.zeta.p + ((m.t + j) & 3);
+        if (m.run.t + j > 0) x.v_cur = m.V.p + N3 * sp;
+        x.nh_zeta = m.zeta.p + ((m.run.t + j) & 3);
     }
-    x.seed = noise_dev ? 0ull : m.seed; x.t_index = m.t + j;
-    x.ke_cur = m.KE.p + (size_t)2 * m.N * sl;
+    x.seed = noise_dev ? 0ull : m.seed; x.t_index = m.run.t + j;
+    x.ke_cur = m.KE.p + (size_t)2 * m.run.N * sl;
     x.halt = m.halt.p;
-    if (m.filter) { x.filt_cur = m.filt_f.p + N3 * sl; x.filt_next = m.filt_f.p + N3 * sn; x.shrink = m.shrink; }
+    if (m.run.filter.on) { x.filt_cur = m.filter.f.p + N3 * sl; x.filt_next = m.filter.f.p + N3 * sn; x.shrink = m.run.filter.shrink; }
 }
 
 // The close of a call: the scalar rows of the evaluations that stand to the caller — columns 14 and 15 are zeta and its time
 // integral under Nose-Hoover, a relaxation's own (keep_14_15), else spare: zeroed — and what the call reports.
-static void md_finish_call(MdState &m, const MdHalt &r, double *scalars, bool keep_14_15, bool evaluated, int *evals_done, int *halt_code)
+// The configuration is evaluated as far as the next call goes behind the covloss gate (1), convergence (3: a relaxation and a band
+// only, no kernel of the dynamics writes that halt word) and a `final` call that ran through.
+static void md_finish_call(sgpr_model *h, const MdHalt &r, double *scalars, bool keep_14_15, int final_eval, int *evals_done, int *halt_code)
 {
+    MdState &m = h->md;
     if (scalars && r.done > 0) {
         memcpy(scalars, m.scal_pin.p, sizeof(double) * SGPR_MD_SCAL * (size_t)r.done);
         if (!keep_14_15)
             for (int e = 0; e < r.done; e++) scalars[(size_t)SGPR_MD_SCAL * e + 14] = scalars[(size_t)SGPR_MD_SCAL * e + 15] = 0.0;
     }
-    m.evaluated = evaluated;
+    m.run.evaluated = r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0);
     *evals_done = r.done;
     if (halt_code) *halt_code = r.code;
+    h->lists_valid = false;
 }
 
-// The frame of evaluation j of a call (configuration n = m.t + j, n % rec_every == 0), behind the evaluation's last launch: the
+// The frame of evaluation j of a call (configuration n = m.run.t + j, n % rec.every == 0), behind the evaluation's last launch: the
 // ring slots sgpr_md_state(which = -1) would read had the call ended with this evaluation — X and P: n % ring; V: that slot
 // (Langevin, velocity Verlet), the slot before it (Nose-Hoover and NPT, n > 0: what the integrator holds when it asks for F_n),
 // slot 0 (a relaxation).  Its place in the record: its ordinal among the call's recorded evaluations.
 static void md_record_frame(sgpr_model *h, int j, int step, hipStream_t st)
 {
     MdState &m = h->md;
-    const long long n = m.t + j;
-    const int N = m.N, RG = m.ring, sl = (int)(n % RG), plen = (int)sgpr_packed_len(N);
-    const size_t f = (size_t)MdState::rec_between(m.t, n, m.rec_every), N3 = (size_t)3 * N;
-    const int sv = m.relax ? 0 : ((m.nh && n > 0) ? (sl + RG - 1) % RG : sl);
-    const bool wv = (m.rec_what & 1) != 0, wp = (m.rec_what & 2) != 0;
+    const long long n = m.run.t + j;
+    const int N = m.run.N, RG = m.run.ring, sl = (int)(n % RG), plen = (int)sgpr_packed_len(N);
+    const size_t f = (size_t)MdRun::rec_between(m.run.t, n, m.run.rec.every), N3 = (size_t)3 * N;
+    const int sv = m.run.relax.on ? 0 : ((m.run.nh.on && n > 0) ? (sl + RG - 1) % RG : sl);
+    const bool wv = (m.run.rec.what & 1) != 0, wp = (m.run.rec.what & 2) != 0;
     const int elems = wp ? std::max(3 * N, plen) : 3 * N;
     hipLaunchKernelGGL(md_record_kernel, dim3((elems + 255) / 256), dim3(256), 0, st, N, plen, (const int *)h->d_perm.p,
                        (const double *)(m.X.p + N3 * sl), wv ? (const double *)(m.V.p + N3 * sv) : (const double *)nullptr,
-                       wp ? (const double *)(m.P.p + (size_t)plen * sl) : (const double *)nullptr, m.rec_x.p + N3 * f,
-                       wv ? m.rec_v.p + N3 * f : (double *)nullptr, wp ? m.rec_p.p + (size_t)plen * f : (double *)nullptr,
+                       wp ? (const double *)(m.P.p + (size_t)plen * sl) : (const double *)nullptr, m.rec.x.p + N3 * f,
+                       wv ? m.rec.v.p + N3 * f : (double *)nullptr, wp ? m.rec.p.p + (size_t)plen * f : (double *)nullptr,
                        (const int *)m.halt.p, step);
 }
 
@@ -636,9 +649,53 @@ static void md_record_frame(sgpr_model *h, int j, int step, hipStream_t st)
 // keeps its frame: the final structure.  Frames that look-ahead evaluations wrote beyond that count are overwritten later.
 static void md_record_close(MdState &m, const MdHalt &r)
 {
-    if (!m.rec_call_every) return;
+    if (!m.run.rec.call_every) return;
     const int lim = std::max(r.code == 1 ? r.done - 1 : r.done, 0);
-    m.rec_call_count = (int)MdState::rec_between(m.rec_call_t0, m.rec_call_t0 + lim, m.rec_call_every);
+    m.run.rec.call_count = (int)MdRun::rec_between(m.run.rec.call_t0, m.run.rec.call_t0 + lim, m.run.rec.call_every);
+}
+
+// ---- the frame of the four run functions: md_call_open | the mode's checks, md_prepare_call, its checked pass | md_call_start |
+// md_enqueue_ahead | md_call_close | the mode's record of the call | md_finish_call ----
+struct MdCall {
+    hipStream_t st = nullptr;
+    int N = 0;
+    size_t plen = 0;      // the packed length 4N + 11
+    double gate = 1e300;  // the covloss that halts the run (ediff <= 0: never)
+    unsigned step0 = 0;   // the handle's step counter at the first evaluation: what the halt words count from
+    int enq = 0;          // evaluations enqueued
+};
+
+// The run's own system bound again on its device, nothing done yet as far as the caller's counters go.
+static int md_call_open(sgpr_model *h, double ediff, int *evals_done, int *halt_code, MdCall &c)
+{
+    HIPCHK(hipSetDevice(h->device));
+    if (const int rb = md_rebind(h)) return rb;
+    c.st = h->stream;
+    c.N = h->md.run.N;
+    c.plen = (size_t)sgpr_packed_len(c.N);
+    c.gate = ediff > 0.0 ? ediff : 1e300;
+    *evals_done = 0;
+    if (halt_code) *halt_code = 0;
+    return SGPR_OK;
+}
+
+// Behind the checked pass (which counts as a step): the record of the last call's continuation is void from here on — sgpr_md_run
+// reads it first and writes a new one at its end — and the evaluations count from the handle's step counter as it stands.
+static void md_call_start(sgpr_model *h, MdCall &c)
+{
+    h->md.run.chain.ok = false;
+    c.step0 = h->step_count;
+}
+
+// The one wait of the call, then what it leaves (md_record_close: a committee and a band refuse an armed record, so it does
+// nothing for them).  sgpr_md_run spells the same three out: peer_check, the chain decision and its md_reset_lists stand between
+// its wait and its decode.
+static int md_call_close(sgpr_model *h, const MdCall &c, int final_eval, const double *scalars, bool want_cells, MdHalt *r)
+{
+    if (const int rc = md_collect(h, c.enq, c.st, scalars, want_cells)) return rc;
+    if (const int rd = md_decode_halt(h, c.step0, c.enq, final_eval, want_cells, r)) return rd;
+    md_record_close(h->md, *r);
+    return SGPR_OK;
 }
 
 // sgpr_md_run for a relaxation: every evaluation is the plain step (its own binning kernel, the plain last kernel) with
@@ -649,61 +706,54 @@ static void md_record_close(MdState &m, const MdHalt &r)
 static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
 {
     MdState &m = h->md;
-    HIPCHK(hipSetDevice(h->device));
-    if (const int rb = md_rebind(h)) return rb;
-    hipStream_t st = h->stream;
-    const int N = m.N, RG = RLX_RING;
-    const size_t plen = (size_t)sgpr_packed_len(N);
-    *evals_done = 0;
-    if (halt_code) *halt_code = 0;
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    hipStream_t st = c.st;
+    const int N = c.N, RG = RLX_RING;
+    const size_t plen = c.plen;
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, true)) return rp;
-    auto cell_of = [&](long long n) -> double * { return m.rx_cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
-    m.relax_started = true; m.started = true;
+    auto cell_of = [&](long long n) -> double * { return m.relax.cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
+    m.run.relax.started = true; m.run.started = true;
     if (!h->warm) {
-        const int sw = (int)(m.t % RG);
-        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.t), m.P.p + plen * sw, st);
+        const int sw = (int)(m.run.t % RG);
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.run.t), m.P.p + plen * sw, st);
         if (rc_) return rc_;
         h->warm = true;
     }
-    m.chain_ok = false;
+    md_call_start(h, c);
     if (const int rl = md_reset_lists(h, st)) return rl;
-    const unsigned step0 = h->step_count;
-    const double gate = ediff > 0.0 ? ediff : 1e300;
-    int enq = 0;
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
-        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG;
+    const unsigned step0 = c.step0; const double gate = c.gate;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const int sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG;
         double *packed = m.P.p + plen * sl;
-        const int re = enqueue_step(h, m.X.p + (size_t)3 * N * sl, cell_of(m.t + j), packed, st, nullptr);
+        const int re = enqueue_step(h, m.X.p + (size_t)3 * N * sl, cell_of(m.run.t + j), packed, st, nullptr);
         if (re) return re;
         h->lists_valid = true;
         const bool stay = final_eval && j == nevals - 1;
         // (held components, sgpr_md_fix: the FIX forms; without a mask the kernels of a run without one)
-        hipLaunchKernelGGL(m.n_fixed ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.rp, m.rx_state.p,
+        hipLaunchKernelGGL(m.run.fix.n ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.run.relax.par, m.relax.state.p,
                            (const double *)packed, (const int *)h->d_perm.p,
-                           (const double *)m.V.p, (const double *)cell_of(m.t + j), cell_of(m.t + j + 1), gate, m.halt.p, m.halt_host.dev,
-                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark.dev + j, stay ? 1 : 0,
+                           (const double *)m.V.p, (const double *)cell_of(m.run.t + j), cell_of(m.run.t + j + 1), gate, m.halt.p, m.halt_host.dev,
+                           (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark.dev + j, stay ? 1 : 0,
                            m.fix());
         if (!stay)
-            hipLaunchKernelGGL(m.n_fixed ? md_fire_move_kernel<true> : md_fire_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, m.rp.cell,
-                               (const double *)m.rx_state.p,
-                               (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.rx_ref.p, m.X.p + (size_t)3 * N * sn,
-                               (const double *)cell_of(m.t + j), (const double *)cell_of(m.t + j + 1), (const int *)m.halt.p, (int)(step0 + j),
+            hipLaunchKernelGGL(m.run.fix.n ? md_fire_move_kernel<true> : md_fire_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, m.run.relax.par.cell,
+                               (const double *)m.relax.state.p,
+                               (const int *)h->d_perm.p, (const double *)packed, m.V.p, m.relax.ref.p, m.X.p + (size_t)3 * N * sn,
+                               (const double *)cell_of(m.run.t + j), (const double *)cell_of(m.run.t + j + 1), (const int *)m.halt.p, (int)(step0 + j),
                                m.fix());
         // (the frame BEHIND the move: sgpr_md_state reads a relaxation's velocity from slot 0, which the move kernel updates in
         // place — after a cut call that moved out of n it returns the moved velocity with the positions of n; where nothing
         // moves — a halt at n, the last evaluation of a `final` call — it returns the one before the move, and so does this.
         // Positions and results of n are in slots the move does not write.)
-        if (m.rec_every && (m.t + j) % m.rec_every == 0) md_record_frame(h, j, (int)(step0 + j), st);
+        if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
-    if (const int rc = md_collect(h, enq, st, scalars, true)) return rc;
     MdHalt r;
-    if (const int rd = md_decode_halt(h, step0, enq, final_eval, true, &r)) return rd;
-    md_record_close(m, r);
-    md_finish_call(m, r, scalars, true, r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
-    h->lists_valid = false;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, true, &r)) return rc;
+    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
     return SGPR_OK;
 }
 
@@ -719,16 +769,16 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (!h || K < 0) return fail(SGPR_E_INVALID, "sgpr_md_committee: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_committee: call sgpr_md_begin first");
-    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
-    if (K == 0 || !members) { m.bcm.clear(); m.bcm_info.clear(); return SGPR_OK; }
-    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a bias (sgpr_md_meta), which the committee's loop does not apply; the host loop around calculate() serves it");
-    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
-    if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
-    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
-    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a nudged elastic band; a committee serves dynamics only");
-    if (m.n_fixed) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.n_fixed);
-    if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.world);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
+    if (K == 0 || !members) { m.run.bcm.members.clear(); m.run.bcm.info.clear(); return SGPR_OK; }
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a bias (sgpr_md_meta), which the committee's loop does not apply; the host loop around calculate() serves it");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a nudged elastic band; a committee serves dynamics only");
+    if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
+    if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
         const sgpr_model *mk = members[k];
@@ -743,14 +793,14 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N3 = (size_t)3 * m.N;
-    if (m.bcm_P.alloc((size_t)(K + 1) * (size_t)sgpr_packed_len(m.N)) || m.bcm_x.alloc(N3))
+    const size_t N3 = (size_t)3 * m.run.N;
+    if (m.bcm.P.alloc((size_t)(K + 1) * (size_t)sgpr_packed_len(m.run.N)) || m.bcm.x.alloc(N3))
         return fail(SGPR_E_NODEVICE, "sgpr_md_committee: device allocation failed");
     // every slot of the ring of positions a valid configuration from the start: what the host has enqueued behind a halt
     // evaluates stale slots (and changes nothing) — zeros there would overflow the live model's lists
     for (int r = 1; r < 4; r++) HIPCHK(hipMemcpy(m.X.p + N3 * r, m.X.p, sizeof(double) * N3, hipMemcpyDeviceToDevice));
-    m.bcm.assign(members, members + K);
-    m.bcm_info.clear();
+    m.run.bcm.members.assign(members, members + K);
+    m.run.bcm.info.clear();
     return SGPR_OK;
 }
 
@@ -760,11 +810,11 @@ extern "C" int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: bad arguments");
     const MdState &m = h->md;
-    if (!m.active || m.bcm.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: call sgpr_md_begin and sgpr_md_committee first");
-    if (m.bcm_info.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: no evaluation of the run stands yet");
-    const size_t K1 = m.bcm.size() + 1;
-    if (w) memcpy(w, m.bcm_info.data(), sizeof(double) * K1);
-    if (covmax) memcpy(covmax, m.bcm_info.data() + BCM_MAX, sizeof(double) * K1);
+    if (!m.active || m.run.bcm.members.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: call sgpr_md_begin and sgpr_md_committee first");
+    if (m.run.bcm.info.empty()) return fail(SGPR_E_INVALID, "sgpr_md_committee_info: no evaluation of the run stands yet");
+    const size_t K1 = m.run.bcm.members.size() + 1;
+    if (w) memcpy(w, m.run.bcm.info.data(), sizeof(double) * K1);
+    if (covmax) memcpy(covmax, m.run.bcm.info.data() + BCM_MAX, sizeof(double) * K1);
     return SGPR_OK;
 }
 
@@ -777,97 +827,92 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
                             int *halt_code)
 {
     MdState &m = h->md;
-    HIPCHK(hipSetDevice(h->device));
-    if (const int rb = md_rebind(h)) return rb;
-    hipStream_t st = h->stream;
-    const int N = m.N, RG = m.ring, K = (int)m.bcm.size(), K1 = K + 1;
-    const size_t plen = (size_t)sgpr_packed_len(N), N3 = (size_t)3 * N;
-    *evals_done = 0;
-    if (halt_code) *halt_code = 0;
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    hipStream_t st = c.st;
+    const int N = c.N, RG = m.run.ring, K = (int)m.run.bcm.members.size(), K1 = K + 1;
+    const size_t plen = c.plen, N3 = (size_t)3 * N;
     for (int k = 0; k < K; k++) {
-        const sgpr_model *mk = m.bcm[k];
+        const sgpr_model *mk = m.run.bcm.members[k];
         if (!(mk->m > 0 && mk->has_mu && mk->has_choli)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: member %d of the committee has lost its weights", k);
         HIPCHK(hipStreamSynchronize(mk->stream));   // (whatever the caller ran on the member between two calls is behind us)
     }
-    m.started = true;
+    m.run.started = true;
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
-    if (m.bcm_info_d.alloc((size_t)BCM_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    if (m.bcm.info_d.alloc((size_t)BCM_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
     if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
-    const int s0 = (int)(m.t % RG);
+    const int s0 = (int)(m.run.t % RG);
     const unsigned step_a = h->step_count;
     // the current configuration in caller order, for the members (the halt words are armed: nothing has halted this call)
     hipLaunchKernelGGL(md_record_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, st, N, 0, (const int *)h->d_perm.p,
-                       (const double *)(m.X.p + N3 * s0), (const double *)nullptr, (const double *)nullptr, m.bcm_x.p, (double *)nullptr,
+                       (const double *)(m.X.p + N3 * s0), (const double *)nullptr, (const double *)nullptr, m.bcm.x.p, (double *)nullptr,
                        (double *)nullptr, (const int *)m.halt.p, (int)step_a);
     // Whatever ran on a handle since the last call — calculate() on a halt evaluates the same members, a model update binds the
     // live one to stored frames — nothing is assumed about bound frame, lists or bin populations: bound again, a checked pass
     // where the capacities are not sized for this system, lists rebuilt by the first evaluation, bin populations cleared
     if (!h->warm) {
-        const int rc_ = run_checked(h, m.X.p + N3 * s0, m.cell.p, m.bcm_P.p + plen * K, st);
+        const int rc_ = run_checked(h, m.X.p + N3 * s0, m.cell.p, m.bcm.P.p + plen * K, st);
         if (rc_) return rc_;
         h->warm = true;
     }
     for (int k = 0; k < K; k++) {
-        sgpr_model *mk = m.bcm[k];
-        if (!md_same_system(mk, N, m.numbers.data(), m.pbc, 0, 1))
-            if (const int rb = sgpr_bind_system(mk, N, m.numbers.data(), m.pbc, 0, 1)) return rb;
+        sgpr_model *mk = m.run.bcm.members[k];
+        if (!md_same_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1))
+            if (const int rb = sgpr_bind_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1)) return rb;
         if (!mk->warm) {
-            const int rc_ = run_checked(mk, m.bcm_x.p, m.cell.p, m.bcm_P.p + plen * k, st);
+            const int rc_ = run_checked(mk, m.bcm.x.p, m.cell.p, m.bcm.P.p + plen * k, st);
             if (rc_) return rc_;
             mk->warm = true;
         }
         if (const int rl = md_reset_lists(mk, st)) return rl;
     }
-    m.chain_ok = false;
+    md_call_start(h, c);
     if (const int rl = md_reset_lists(h, st)) return rl;
-    const unsigned step0 = h->step_count;
-    const double gate = ediff > 0.0 ? ediff : 1e300;
-    const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
-    int enq = 0;
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
-        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+    const unsigned step0 = c.step0; const double gate = c.gate;
+    const bool pend0 = m.run.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const int sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
         for (int k = 0; k < K; k++) {
-            sgpr_model *mk = m.bcm[k];
-            const int re = enqueue_step(mk, m.bcm_x.p, m.cell.p, m.bcm_P.p + plen * k, st, nullptr);
+            sgpr_model *mk = m.run.bcm.members[k];
+            const int re = enqueue_step(mk, m.bcm.x.p, m.cell.p, m.bcm.P.p + plen * k, st, nullptr);
             if (re) return re;
             mk->lists_valid = true;
         }
-        const int re = enqueue_step(h, m.X.p + N3 * sl, m.cell.p, m.bcm_P.p + plen * K, st, nullptr);
+        const int re = enqueue_step(h, m.X.p + N3 * sl, m.cell.p, m.bcm.P.p + plen * K, st, nullptr);
         if (re) return re;
         h->lists_valid = true;
         const int step = (int)(step0 + j);
-        double *packed = m.P.p + plen * sl, *info = m.bcm_info_d.p + (size_t)BCM_INFO * j, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
-        hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, packed, info, gate, m.halt.p,
+        double *packed = m.P.p + plen * sl, *info = m.bcm.info_d.p + (size_t)BCM_INFO * j, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
+        hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm.P.p, packed, info, gate, m.halt.p,
                            m.halt_host.dev, step, row, m.mark.dev + j);
         FinNext x;
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         x.step = step;   // (the fused loop: enqueue_step sets it)
         const bool stay = final_eval && j == nevals - 1;
-        hipLaunchKernelGGL(md_bcm_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm_P.p, (const double *)info,
-                           packed, m.bcm_x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
+        hipLaunchKernelGGL(md_bcm_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm.P.p, (const double *)info,
+                           packed, m.bcm.x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
         hipLaunchKernelGGL(md_bcm_ke_kernel, dim3(1), dim3(256), 0, st, N, (const double *)(m.KE.p + (size_t)2 * N * sl), (const int *)m.halt.p,
                            step, row);
-        if (m.nh)   // zeta of the next configuration from this one's kinetic energy
-            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
-                               m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, step, row);
+        if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy
+            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.run.t + j) & 0x3fffffff),
+                               m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, m.halt.p, step, row);
         return SGPR_OK;
     });
-    for (int k = 0; k < K; k++) m.bcm[k]->lists_valid = false;
+    for (int k = 0; k < K; k++) m.run.bcm.members[k]->lists_valid = false;
     h->lists_valid = false;
     if (rc_) return rc_;
-    if (const int rc = md_collect(h, enq, st, scalars, false)) return rc;
     MdHalt r;
-    if (const int rd = md_decode_halt(h, step0, enq, final_eval, false, &r)) return rd;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
     // a capacity overflowed (md_decode_halt has cleared the live handle's `warm`): the next call's checked pass grows whatever it
     // was, on whichever member
     if (r.code == 2)
-        for (int k = 0; k < K; k++) m.bcm[k]->warm = false;
+        for (int k = 0; k < K; k++) m.run.bcm.members[k]->warm = false;
     if (r.done > 0) {
-        m.bcm_info.assign(BCM_INFO, 0.0);
-        HIPCHK(hipMemcpy(m.bcm_info.data(), m.bcm_info_d.p + (size_t)BCM_INFO * (r.done - 1), sizeof(double) * BCM_INFO, hipMemcpyDeviceToHost));
+        m.run.bcm.info.assign(BCM_INFO, 0.0);
+        HIPCHK(hipMemcpy(m.run.bcm.info.data(), m.bcm.info_d.p + (size_t)BCM_INFO * (r.done - 1), sizeof(double) * BCM_INFO, hipMemcpyDeviceToHost));
     }
-    md_finish_call(m, r, scalars, m.nh, r.code == 1 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
+    md_finish_call(h, r, scalars, m.run.nh.on, final_eval, evals_done, halt_code);
     return SGPR_OK;
 }
 
@@ -881,9 +926,9 @@ static int md_neb_init_state(sgpr_model *h)
 {
     MdState &m = h->md;
     double s[RLX_LEN] = {};
-    s[RLX_DT] = m.rp.dt0; s[RLX_A] = m.rp.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
-    HIPCHK(hipMemcpy(m.rx_state.p, s, sizeof(s), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(m.nb_V.p, 0, sizeof(double) * 3 * (size_t)m.N * (size_t)m.nb_K));
+    s[RLX_DT] = m.run.relax.par.dt0; s[RLX_A] = m.run.relax.par.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
+    HIPCHK(hipMemcpy(m.relax.state.p, s, sizeof(s), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.neb.V.p, 0, sizeof(double) * 3 * (size_t)m.run.N * (size_t)m.run.neb.K));
     return SGPR_OK;
 }
 
@@ -894,25 +939,24 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_neb: call sgpr_md_begin first");
     if (K < 1 || K > NEB_MAX) return fail(SGPR_E_INVALID, "sgpr_md_neb: %d interior images; a band has 1 to %d", K, NEB_MAX);
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run was begun on %d ranks; a band runs on one", m.world);
-    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has started");
-    if (m.nh || m.npt) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has a thermostat or a barostat");
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a committee (sgpr_md_committee), which serves dynamics only");
-    if (m.meta) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased band");
-    if (m.filter) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a filter (sgpr_md_filter), which serves dynamics only");
-    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
-    if (m.rec_every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run was begun on %d ranks; a band runs on one", m.run.world);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has started");
+    if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_neb: the run has a thermostat or a barostat");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a committee (sgpr_md_committee), which serves dynamics only");
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased band");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a filter (sgpr_md_filter), which serves dynamics only");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
+    if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
-    const double *fp = fire ? fire : RLX_ASE;
-    if (!(fp[0] > 0.0 && fp[1] > 0.0 && fp[2] > 0.0 && fp[3] >= 0.0 && fp[4] > 0.0 && fp[5] > 0.0 && fp[6] >= 0.0 && fp[7] > 0.0))
-        return fail(SGPR_E_INVALID, "sgpr_md_neb: dt, maxstep, dtmax, finc, fdec, fa > 0 and nmin, astart >= 0");
+    RelaxParams p = {};
+    if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int N = m.N;
+    const int N = m.run.N;
     const size_t N3 = (size_t)3 * N, plen = (size_t)sgpr_packed_len(N);
     NebCell cl = {};
     HIPCHK(hipMemcpy(cl.h, m.cell.p, sizeof(cl.h), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; k++) cl.pbc[k] = m.pbc[k] ? 1 : 0;
+    for (int k = 0; k < 3; k++) cl.pbc[k] = m.run.pbc[k] ? 1 : 0;
     const bool any_pbc = cl.pbc[0] || cl.pbc[1] || cl.pbc[2];
     if (any_pbc) {
         if (!(fabs(rlx_det(cl.h)) > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: the cell is singular");
@@ -942,26 +986,24 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
                 return fail(SGPR_E_INVALID, "sgpr_md_neb: atom %d moves %.4f between images %d and %d, more than half the smallest perpendicular "
                             "width of the cell (%.4f): the minimum-image rounding cannot recover it; add images", c, len, i - 1, i, wmin);
         }
-    RelaxParams p = {};
     for (int k = 0; k < 9; k++) p.h0[k] = cl.h[k];
     p.fmax2 = fmax * fmax;
-    p.dt0 = fp[0]; p.maxstep = fp[1]; p.dtmax = fp[2]; p.nmin = fp[3]; p.finc = fp[4]; p.fdec = fp[5]; p.astart = fp[6]; p.fa = fp[7];
     p.cf = (double)N; p.cell = 0;
     // rings of RLX_RING slots, every slot the initial band (what runs behind a halt evaluates stale slots)
-    if (m.nb_X.alloc(N3 * (size_t)K * RLX_RING) || m.nb_V.alloc(N3 * (size_t)K) || m.nb_P.alloc(plen * (size_t)K * RLX_RING) || m.nb_ends.alloc(2 * N3) ||
-        m.nb_sums.alloc((size_t)NEB_SUMS * K) || m.nb_coef.alloc((size_t)2 * K) || m.rx_state.alloc(RLX_LEN) || m.nb_par.alloc(sizeof(NebFirePar)))
+    if (m.neb.X.alloc(N3 * (size_t)K * RLX_RING) || m.neb.V.alloc(N3 * (size_t)K) || m.neb.P.alloc(plen * (size_t)K * RLX_RING) || m.neb.ends.alloc(2 * N3) ||
+        m.neb.sums.alloc((size_t)NEB_SUMS * K) || m.neb.coef.alloc((size_t)2 * K) || m.relax.state.alloc(RLX_LEN) || m.neb.par.alloc(sizeof(NebFirePar)))
         return fail(SGPR_E_NODEVICE, "sgpr_md_neb: device allocation failed");
     for (int r = 0; r < RLX_RING; r++)
-        HIPCHK(hipMemcpy(m.nb_X.p + N3 * (size_t)K * r, positions + N3, sizeof(double) * N3 * K, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m.nb_ends.p, positions, sizeof(double) * N3, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m.nb_ends.p + N3, positions + N3 * (size_t)(K + 1), sizeof(double) * N3, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.neb.X.p + N3 * (size_t)K * r, positions + N3, sizeof(double) * N3 * K, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.neb.ends.p, positions, sizeof(double) * N3, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.neb.ends.p + N3, positions + N3 * (size_t)(K + 1), sizeof(double) * N3, hipMemcpyHostToDevice));
     NebFirePar par = {};
     par.cell = cl; par.p = p; par.kspr = k_spring; par.climb = climb ? 1 : 0;
-    HIPCHK(hipMemcpy(m.nb_par.p, &par, sizeof(par), hipMemcpyHostToDevice));
-    m.rp = p;
-    m.nb_cell = cl; m.nb_K = K;
-    m.neb = true; m.ring = RLX_RING;
-    m.nb_info.clear();
+    HIPCHK(hipMemcpy(m.neb.par.p, &par, sizeof(par), hipMemcpyHostToDevice));
+    m.run.relax.par = p;
+    m.run.neb.cell = cl; m.run.neb.K = K;
+    m.run.neb.on = true; m.run.ring = RLX_RING;
+    m.run.neb.info.clear();
     return md_neb_init_state(h);
 }
 
@@ -970,7 +1012,7 @@ extern "C" int sgpr_md_neb_reset(sgpr_model *h)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_neb_reset: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_reset: call sgpr_md_begin and sgpr_md_neb first");
+    if (!m.active || !m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_neb_reset: call sgpr_md_begin and sgpr_md_neb first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     return md_neb_init_state(h);
@@ -983,16 +1025,16 @@ extern "C" int sgpr_md_neb_state(sgpr_model *h, double *positions, double *veloc
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: call sgpr_md_begin and sgpr_md_neb first");
+    if (!m.active || !m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: call sgpr_md_begin and sgpr_md_neb first");
     if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: which = 0 or -1");
-    if (which == -1 && m.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: no earlier band");
+    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: no earlier band");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N3 = (size_t)3 * m.N, plen = (size_t)sgpr_packed_len(m.N), K = (size_t)m.nb_K;
-    const size_t sl = (size_t)((m.t + which + RLX_RING) % RLX_RING);
-    if (positions) HIPCHK(hipMemcpy(positions, m.nb_X.p + N3 * K * sl, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
-    if (velocities) HIPCHK(hipMemcpy(velocities, m.nb_V.p, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
-    if (packed) HIPCHK(hipMemcpy(packed, m.nb_P.p + plen * K * sl, sizeof(double) * plen * K, hipMemcpyDeviceToHost));
+    const size_t N3 = (size_t)3 * m.run.N, plen = (size_t)sgpr_packed_len(m.run.N), K = (size_t)m.run.neb.K;
+    const size_t sl = (size_t)((m.run.t + which + RLX_RING) % RLX_RING);
+    if (positions) HIPCHK(hipMemcpy(positions, m.neb.X.p + N3 * K * sl, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
+    if (velocities) HIPCHK(hipMemcpy(velocities, m.neb.V.p, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.neb.P.p + plen * K * sl, sizeof(double) * plen * K, hipMemcpyDeviceToHost));
     return SGPR_OK;
 }
 
@@ -1002,11 +1044,11 @@ extern "C" int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out
 {
     if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: bad arguments");
     const MdState &m = h->md;
-    if (!m.active || !m.neb) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: call sgpr_md_begin and sgpr_md_neb first");
-    const long long have = (long long)(m.nb_info.size() / NEB_INFO);
+    if (!m.active || !m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: call sgpr_md_begin and sgpr_md_neb first");
+    const long long have = (long long)(m.run.neb.info.size() / NEB_INFO);
     if ((long long)first + count > have)
         return fail(SGPR_E_INVALID, "sgpr_md_neb_info: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", first, (long long)first + count - 1, have);
-    memcpy(out, m.nb_info.data() + (size_t)NEB_INFO * first, sizeof(double) * NEB_INFO * (size_t)count);
+    memcpy(out, m.run.neb.info.data() + (size_t)NEB_INFO * first, sizeof(double) * NEB_INFO * (size_t)count);
     return SGPR_OK;
 }
 
@@ -1021,34 +1063,30 @@ extern "C" int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out
 static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
 {
     MdState &m = h->md;
-    HIPCHK(hipSetDevice(h->device));
-    if (const int rb = md_rebind(h)) return rb;
-    hipStream_t st = h->stream;
-    const int N = m.N, RG = RLX_RING, K = m.nb_K;
-    const size_t plen = (size_t)sgpr_packed_len(N), N3 = (size_t)3 * N;
-    *evals_done = 0;
-    if (halt_code) *halt_code = 0;
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    hipStream_t st = c.st;
+    const int N = c.N, RG = RLX_RING, K = m.run.neb.K;
+    const size_t plen = c.plen, N3 = (size_t)3 * N;
     if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
-    if (m.nb_info_d.alloc((size_t)NEB_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-    HIPCHK(hipMemsetAsync(m.nb_info_d.p, 0, sizeof(double) * NEB_INFO * ((size_t)nevals + 1), st));
-    m.started = true;
-    m.nb_info.clear();
+    if (m.neb.info_d.alloc((size_t)NEB_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemsetAsync(m.neb.info_d.p, 0, sizeof(double) * NEB_INFO * ((size_t)nevals + 1), st));
+    m.run.started = true;
+    m.run.neb.info.clear();
     if (!h->warm) {   // the checked pass grows capacities: over every interior image
-        const size_t sw = (size_t)(m.t % RG);
+        const size_t sw = (size_t)(m.run.t % RG);
         for (int i = 0; i < K; i++) {
-            const int rc_ = run_checked(h, m.nb_X.p + N3 * (K * sw + i), m.cell.p, m.nb_P.p + plen * (K * sw + i), st);
+            const int rc_ = run_checked(h, m.neb.X.p + N3 * (K * sw + i), m.cell.p, m.neb.P.p + plen * (K * sw + i), st);
             if (rc_) return rc_;
         }
         h->warm = true;
     }
-    m.chain_ok = false;
-    const unsigned step0 = h->step_count;
-    const double gate = ediff > 0.0 ? ediff : 1e300;
-    int enq = 0;
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
-        const size_t sl = (size_t)((m.t + j) % RG), sn = (sl + 1) % RG;
-        const double *band = m.nb_X.p + N3 * K * sl;
-        double *Pk = m.nb_P.p + plen * K * sl;
+    md_call_start(h, c);
+    const unsigned step0 = c.step0; const double gate = c.gate;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const size_t sl = (size_t)((m.run.t + j) % RG), sn = (sl + 1) % RG;
+        const double *band = m.neb.X.p + N3 * K * sl;
+        double *Pk = m.neb.P.p + plen * K * sl;
         for (int i = 0; i < K; i++) {
             if (const int rl = md_reset_lists(h, st)) return rl;
             const int re = enqueue_step(h, band + N3 * i, m.cell.p, Pk + plen * i, st, nullptr);
@@ -1056,26 +1094,25 @@ static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, d
         }
         const int step = (int)(step0 + j);
         const bool stay = final_eval && j == nevals - 1;
-        const NebBand b = {N, K, plen, band, m.nb_ends.p, Pk, h->d_perm.p, m.fix()};
-        hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, st, b, m.nb_cell, m.nb_sums.p, (const int *)m.halt.p, step);
-        hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, st, b, (const NebFirePar *)m.nb_par.p, m.rx_state.p, (const double *)m.nb_V.p,
-                           (const double *)m.nb_sums.p, m.nb_coef.p, m.nb_info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host.dev, step,
+        const NebBand b = {N, K, plen, band, m.neb.ends.p, Pk, h->d_perm.p, m.fix()};
+        hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, st, b, m.run.neb.cell, m.neb.sums.p, (const int *)m.halt.p, step);
+        hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, st, b, (const NebFirePar *)m.neb.par.p, m.relax.state.p, (const double *)m.neb.V.p,
+                           (const double *)m.neb.sums.p, m.neb.coef.p, m.neb.info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host.dev, step,
                            m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.mark.dev + j, stay ? 1 : 0);
         if (!stay)
-            hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, st, b, m.nb_cell, (const double *)m.rx_state.p,
-                               (const double *)m.nb_coef.p, m.nb_V.p, m.nb_X.p + N3 * K * sn, (const int *)m.halt.p, step);
+            hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, st, b, m.run.neb.cell, (const double *)m.relax.state.p,
+                               (const double *)m.neb.coef.p, m.neb.V.p, m.neb.X.p + N3 * K * sn, (const int *)m.halt.p, step);
         return SGPR_OK;
     });
     h->lists_valid = false;
     if (rc_) return rc_;
-    if (const int rc = md_collect(h, enq, st, scalars, false)) return rc;
     MdHalt r;
-    if (const int rd = md_decode_halt(h, step0, enq, final_eval, false, &r)) return rd;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
     if (r.done > 0) {
-        m.nb_info.assign((size_t)NEB_INFO * r.done, 0.0);
-        HIPCHK(hipMemcpy(m.nb_info.data(), m.nb_info_d.p, sizeof(double) * NEB_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
+        m.run.neb.info.assign((size_t)NEB_INFO * r.done, 0.0);
+        HIPCHK(hipMemcpy(m.run.neb.info.data(), m.neb.info_d.p, sizeof(double) * NEB_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
     }
-    md_finish_call(m, r, scalars, true, r.code == 1 || r.code == 3 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
+    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
     return SGPR_OK;
 }
 
@@ -1093,51 +1130,49 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_run: call sgpr_md_begin first");
     if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
-    if (m.relax) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
-    if (m.neb) return md_neb_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
-    if (!m.bcm.empty()) return md_committee_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
-    HIPCHK(hipSetDevice(h->device));
-    if (const int rb = md_rebind(h)) return rb;
-    if (m.world > 1 && !(peer_on(h) && h->peer.world == m.world && h->peer.rank == m.rank))
-        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the run was begun on %d ranks, the exchange between them is gone", m.world);
-    hipStream_t st = h->stream;
-    const int N = m.N;
-    const size_t plen = (size_t)sgpr_packed_len(N);
-    *evals_done = 0;
-    if (halt_code) *halt_code = 0;
-    if (m.meta) {
+    if (m.run.relax.on) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    if (m.run.neb.on) return md_neb_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    if (!m.run.bcm.members.empty()) return md_committee_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    if (m.run.world > 1 && !(peer_on(h) && h->peer.world == m.run.world && h->peer.rank == m.run.rank))
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the run was begun on %d ranks, the exchange between them is gone", m.run.world);
+    hipStream_t st = c.st;
+    const int N = c.N;
+    const size_t plen = c.plen;
+    if (m.run.meta.on) {
         // the bias rides in the single-rank gather form of the fused last kernel: what cannot take that form is refused here, before
         // anything is enqueued (enqueue_step keeps its own check for what only a checked pass finds out: lists beyond the gather form)
         if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only (one rank, no graph "
                         "replay, no side-stream fork, a skin > 0): the host loop around calculate() serves this run");
         // the last configuration of the call that deposits a hill must find its row
-        const long long nd = (m.t + nevals - 1) / m.meta_pace * m.meta_pace;
-        if (nd >= m.t && m.meta_slot(nd) >= m.meta_cap)
+        const long long nd = (m.run.t + nevals - 1) / m.run.meta.pace * m.run.meta.pace;
+        if (nd >= m.run.t && m.run.meta_slot(nd) >= m.run.meta.cap)
             return fail(SGPR_E_INVALID, "sgpr_md_run: %d evaluations from configuration %lld deposit hills up to row %lld; the bias holds %lld "
-                        "(sgpr_md_meta again, with a larger capacity and the hills of sgpr_md_meta_hills)", nevals, m.t, m.meta_slot(nd), m.meta_cap);
-        if (m.meta_merge) {
+                        "(sgpr_md_meta again, with a larger capacity and the hills of sgpr_md_meta_hills)", nevals, m.run.t, m.run.meta_slot(nd), m.run.meta.cap);
+        if (m.run.meta.merge) {
             // where the table stands: merges enqueued behind a halt were discarded, the one of the speculative step in front of it was not
             int ctl[META_CTL_LEN];
-            HIPCHK(hipMemcpyAsync(ctl, m.meta_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(ctl, m.meta.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            m.meta_enq = ctl[META_CTL_DONE];
+            m.run.meta.enq = ctl[META_CTL_DONE];
         }
-        m.meta_fresh = false;
+        m.run.meta.fresh = false;
     }
-    m.started = true;
+    m.run.started = true;
     MdBinIdentity guard(h);
-    if (const int rp = md_prepare_call(h, nevals, st, m.npt)) return rp;   // (the cell record: a moving cell only)
+    if (const int rp = md_prepare_call(h, nevals, st, m.run.npt.on)) return rp;   // (the cell record: a moving cell only)
     if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
     // the first evaluation sizes the capacities for this configuration if nothing has yet (synchronised, results discarded)
-    const int RG = m.ring, s0 = (int)(m.t % RG);
-    if (m.npt) { m.np.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.np.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
-    if (m.npt && !m.npt_started)
+    const int RG = m.run.ring, s0 = (int)(m.run.t % RG);
+    if (m.run.npt.on) { m.run.npt.par.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.run.npt.par.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
+    if (m.run.npt.on && !m.run.npt.started)
         if (const int rs = md_npt_start(h, st)) return rs;
     // (moving cell: the cell of configuration n is in the ring)
-    auto cell_of = [&](long long n) -> const double * { return m.npt ? m.slot(n)->h : m.cell.p; };
+    auto cell_of = [&](long long n) -> const double * { return m.run.npt.on ? m.slot(n)->h : m.cell.p; };
     if (!h->warm) {
-        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, cell_of(m.t), m.P.p + plen * s0, st);
+        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, cell_of(m.run.t), m.P.p + plen * s0, st);
         if (rc_) return rc_;
         h->warm = true;
     }
@@ -1145,71 +1180,71 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     // lists stand and its last kernel has binned this call's first configuration.  Otherwise: whatever ran in between — a model
     // update evaluates other frames — may have left other lists and bin populations (a run that halted: those of a step that
     // never ran)
-    const bool chain = m.chain_ok && h->warm && h->step_count == m.chain_step && h->bind_gen == m.chain_bind && h->opt_gen == m.chain_opt &&
-                       m.t == m.chain_t && m.chain_pos == m.X.p + (size_t)3 * N * s0;
-    m.chain_ok = false;
+    const bool chain = m.run.chain.ok && h->warm && h->step_count == m.run.chain.step && h->bind_gen == m.run.chain.bind && h->opt_gen == m.run.chain.opt &&
+                       m.run.t == m.run.chain.t && m.run.chain.pos == m.X.p + (size_t)3 * N * s0;
+    md_call_start(h, c);
     if (chain) {
         h->lists_valid = true;
-        h->pre_valid = true; h->pre_pos = m.chain_pos; h->pre_cell = cell_of(m.t); h->pre_step = h->step_count;
+        h->pre_valid = true; h->pre_pos = m.run.chain.pos; h->pre_cell = cell_of(m.run.t); h->pre_step = h->step_count;
     } else if (const int rl = md_reset_lists(h, st))
         return rl;
-    const unsigned step0 = h->step_count;
+    const unsigned step0 = c.step0;
     const unsigned epoch0 = h->peer.epoch;
-    const bool pend0 = m.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
-    int enq = 0;
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &enq, [&](int j) -> int {
-        const int sl = (int)((m.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+    const bool pend0 = m.run.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const int sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
         StepNext nx;
         nx.mode = 2;
         nx.pos_next = m.X.p + (size_t)3 * N * sn;
         FinNext &x = nx.md;
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
-        if (m.npt) {
-            x.npt_cur = m.slot(m.t + j); x.npt_next = m.slot(m.t + j + 1);
-            x.q_cur = m.Q.p + (size_t)3 * N * sl; x.q_prev = m.Q.p + (size_t)3 * N * sp; x.q_next = m.Q.p + (size_t)3 * N * sn;
+        if (m.run.npt.on) {
+            x.npt_cur = m.slot(m.run.t + j); x.npt_next = m.slot(m.run.t + j + 1);
+            x.q_cur = m.npt.Q.p + (size_t)3 * N * sl; x.q_prev = m.npt.Q.p + (size_t)3 * N * sp; x.q_next = m.npt.Q.p + (size_t)3 * N * sn;
             nx.cell_next = x.npt_next->h;
             h->step_grid = &x.npt_cur->grid;
         }
         x.fixed = m.fix();
         x.ke_prev = j > 0 ? m.KE.p + (size_t)2 * N * sp : nullptr;
         x.packed_prev = j > 0 ? m.P.p + plen * sp : nullptr;
-        x.ediff = ediff > 0.0 ? ediff : 1e300;
+        x.ediff = c.gate;
         x.halt_host = m.halt_host.dev;
         x.scal_cur = m.scal_d.p + (size_t)SGPR_MD_SCAL * j; x.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (j > 0 ? j - 1 : 0);
         x.mark_cur = m.mark.dev + j;
         // (the last evaluation of a `final` run integrates speculatively too: its outcome is not adopted below)
-        const int re = enqueue_step(h, x.x_cur, cell_of(m.t + j), m.P.p + plen * sl, st, &nx);
+        const int re = enqueue_step(h, x.x_cur, cell_of(m.run.t + j), m.P.p + plen * sl, st, &nx);
         if (re) return re;
         h->lists_valid = true;  // (the first evaluation rebuilt the candidates; an overflow halts the run: FinNext)
         if (!h->pre_valid) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the fused last kernel is not available for this model / frame (sharded "
                                         "without the library's own exchange, graph capture or a zero skin)");
-        if (m.npt)  // zeta, eta and the matrices of the next configuration, the cell after it (md_npt.inc)
-            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.np, (NptSlot *)m.npt_ring.p, m.zeta.p,
+        if (m.run.npt.on)  // zeta, eta and the matrices of the next configuration, the cell after it (md_npt.inc)
+            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p,
                                (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + (size_t)3 * N * sl), (const double *)m.mass.p,
-                               (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.t + j) & 0x3fffffff), (const int *)m.halt.p,
-                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.cells_d.p + (size_t)SGPR_MD_CELL * j,
-                               m.filter ? (const double *)(m.filt_s.p + 6 * ((m.t + j) & 3)) : (const double *)nullptr,
-                               m.filter ? m.filt_s.p + 6 * ((m.t + j + 1) & 3) : (double *)nullptr, m.shrink);
-        else if (m.nh)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
-            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.t + j) & 0x3fffffff),
-                               m.dt, m.nh_c1, m.nh_c2, m.nh_K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
+                               (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.run.t + j) & 0x3fffffff), (const int *)m.halt.p,
+                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j,
+                               m.run.filter.on ? (const double *)(m.filter.s.p + 6 * ((m.run.t + j) & 3)) : (const double *)nullptr,
+                               m.run.filter.on ? m.filter.s.p + 6 * ((m.run.t + j + 1) & 3) : (double *)nullptr, m.run.filter.shrink);
+        else if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
+            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.run.t + j) & 0x3fffffff),
+                               m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
         // (the frame: the last kernel has written this evaluation's results and, Nose-Hoover, its centred velocity; the slots
         // read here are written again only when the rings come round)
-        if (m.rec_every && (m.t + j) % m.rec_every == 0) md_record_frame(h, j, (int)(step0 + j), st);
+        if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
+    const int enq = c.enq;
     if (enq > 0) {  // the lagged reductions of the last evaluation enqueued
         FinArgs f = {};
         f.N = N;
-        const int sl = (int)((m.t + enq - 1) % RG);
+        const int sl = (int)((m.run.t + enq - 1) % RG);
         f.nx.mode = 3; f.nx.step = (int)(step0 + enq);
         f.nx.ke_prev = m.KE.p + (size_t)2 * N * sl; f.nx.packed_prev = m.P.p + plen * sl;
-        f.nx.ediff = ediff > 0.0 ? ediff : 1e300; f.nx.halt = m.halt.p; f.nx.halt_host = m.halt_host.dev;
+        f.nx.ediff = c.gate; f.nx.halt = m.halt.p; f.nx.halt_host = m.halt_host.dev;
         f.nx.scal_prev = m.scal_d.p + (size_t)SGPR_MD_SCAL * (enq - 1);
         hipLaunchKernelGGL(finalize_tail_kernel, dim3(2), dim3(256), 0, st, f);
     }
-    if (const int rc = md_collect(h, enq, st, scalars, m.npt)) return rc;
+    if (const int rc = md_collect(h, enq, st, scalars, m.run.npt.on)) return rc;
     if (const int pc = peer_check(h)) return pc;
     // Where the run goes on: when every evaluation stands and the last one was integrated, the handle is left as the last kernel
     // left it — the next sgpr_md_run continues from there (chain, above).  Otherwise the last kernel enqueued has binned a step
@@ -1222,7 +1257,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (!keep_chain)
         if (const int rl = md_reset_lists(h, st)) return rl;
     MdHalt r;
-    if (const int rd = md_decode_halt(h, step0, enq, final_eval, m.npt, &r)) return rd;
+    if (const int rd = md_decode_halt(h, step0, enq, final_eval, m.run.npt.on, &r)) return rd;
     md_record_close(m, r);
     // exchanges that took place: the ranks have enqueued different numbers of evaluations behind the halt, all of them
     // skipped on the device (peer_push_kernel): a covloss halt at evaluation k is seen by evaluation k + 1 (or by the
@@ -1233,11 +1268,10 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
             fprintf(stderr, "[sgpr peer] rank %d md_run halt: code %d k %d enq %d nevals %d -> epoch %u\n", h->peer.rank, r.code, r.k, enq, nevals, h->peer.epoch);
     }
     if (keep_chain) {
-        m.chain_ok = true; m.chain_step = h->step_count; m.chain_bind = h->bind_gen; m.chain_opt = h->opt_gen; m.chain_t = m.t;
-        m.chain_pos = keep_pos;
+        m.run.chain.ok = true; m.run.chain.step = h->step_count; m.run.chain.bind = h->bind_gen; m.run.chain.opt = h->opt_gen; m.run.chain.t = m.run.t;
+        m.run.chain.pos = keep_pos;
     }
-    md_finish_call(m, r, scalars, m.nh, r.code == 1 || (r.code == 0 && final_eval != 0), evals_done, halt_code);
-    h->lists_valid = false;
+    md_finish_call(h, r, scalars, m.run.nh.on, final_eval, evals_done, halt_code);
     return SGPR_OK;
 }
 
@@ -1245,10 +1279,10 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
 // handle may be bound to another frame by now
 static int md_fetch_rows(const MdState &m, const double *slot_dev, double *out)
 {
-    std::vector<double> buf((size_t)3 * m.N);
-    HIPCHK(hipMemcpy(buf.data(), slot_dev, sizeof(double) * 3 * m.N, hipMemcpyDeviceToHost));
-    for (int i = 0; i < m.N; i++)
-        for (int k = 0; k < 3; k++) out[3 * (size_t)m.perm[i] + k] = buf[3 * (size_t)i + k];
+    std::vector<double> buf((size_t)3 * m.run.N);
+    HIPCHK(hipMemcpy(buf.data(), slot_dev, sizeof(double) * 3 * m.run.N, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m.run.N; i++)
+        for (int k = 0; k < 3; k++) out[3 * (size_t)m.run.perm[i] + k] = buf[3 * (size_t)i + k];
     return SGPR_OK;
 }
 
@@ -1261,21 +1295,21 @@ extern "C" int sgpr_md_state(sgpr_model *h, double *positions, double *velocitie
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_state: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_state: call sgpr_md_begin first");
-    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_state: the run is a nudged elastic band; sgpr_md_neb_state returns its images");
+    if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_state: the run is a nudged elastic band; sgpr_md_neb_state returns its images");
     if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_state: which = 0 or -1");
-    if (which == -1 && m.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_state: no earlier configuration");
+    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_state: no earlier configuration");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int N = m.N;
-    const int sl = (int)((m.t + which + m.ring) % m.ring);
+    const int N = m.run.N;
+    const int sl = (int)((m.run.t + which + m.run.ring) % m.run.ring);
     int rc_ = positions ? md_fetch_rows(m, m.X.p + (size_t)3 * N * sl, positions) : SGPR_OK;
     // (a relaxation: the optimizer's velocity of the atoms' coordinates, one slot)
-    if (!rc_ && velocities_pre) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * (m.relax ? 0 : sl), velocities_pre);
+    if (!rc_ && velocities_pre) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * (m.run.relax.on ? 0 : sl), velocities_pre);
     // Nose-Hoover: what the integrator holds when it asks for the forces of configuration n is the centred velocity of
     // configuration n - 1 (ASE sets the momenta of a step after its force call); sgpr_md_velocities has v_n itself
-    if (!rc_ && m.nh && velocities_pre && (m.t + which) > 0) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * ((sl + m.ring - 1) % m.ring), velocities_pre);
+    if (!rc_ && m.run.nh.on && velocities_pre && (m.run.t + which) > 0) rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * ((sl + m.run.ring - 1) % m.run.ring), velocities_pre);
     if (rc_) return rc_;
-    if (pending) *pending = (!m.nh && !m.relax && (m.t + which) > 0) ? 1 : 0;   // (every configuration but the start of the trajectory)
+    if (pending) *pending = (!m.run.nh.on && !m.run.relax.on && (m.run.t + which) > 0) ? 1 : 0;   // (every configuration but the start of the trajectory)
     if (packed) HIPCHK(hipMemcpy(packed, m.P.p + (size_t)sgpr_packed_len(N) * sl, sizeof(double) * sgpr_packed_len(N), hipMemcpyDeviceToHost));
     return SGPR_OK;
 }
@@ -1288,30 +1322,30 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     if (!h || !velocities) return fail(SGPR_E_INVALID, "sgpr_md_velocities: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_velocities: call sgpr_md_begin first");
-    if (m.relax) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
-    if (m.neb) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a nudged elastic band; sgpr_md_neb_state returns its images and FIRE's velocity");
-    if (!m.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
+    if (m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
+    if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a nudged elastic band; sgpr_md_neb_state returns its images and FIRE's velocity");
+    if (!m.run.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int N = m.N, sl = (int)(m.t % m.ring);
+    const int N = m.run.N, sl = (int)(m.run.t % m.run.ring);
     if (const int rc_ = md_fetch_rows(m, m.V.p + (size_t)3 * N * sl, velocities)) return rc_;
     std::vector<double> F;
-    const bool kick = !m.nh && m.t > 0;
+    const bool kick = !m.run.nh.on && m.run.t > 0;
     if (kick) {
         F.resize((size_t)3 * N);   // (packed forces are in caller order)
         HIPCHK(hipMemcpy(F.data(), m.P.p + (size_t)sgpr_packed_len(N) * sl, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
-        if (m.filter) {   // (the kick the filtered integrator gives: finalize_next_kernel<5>'s operations)
+        if (m.run.filter.on) {   // (the kick the filtered integrator gives: finalize_next_kernel<5>'s operations)
 #pragma clang fp contract(off)
             std::vector<double> a((size_t)3 * N);
-            if (const int rc_ = md_fetch_rows(m, m.filt_f.p + (size_t)3 * N * sl, a.data())) return rc_;
-            for (size_t e = 0; e < (size_t)3 * N; e++) F[e] = F[e] - std::min(std::max(a[e] * m.shrink, -1.0), 1.0);
+            if (const int rc_ = md_fetch_rows(m, m.filter.f.p + (size_t)3 * N * sl, a.data())) return rc_;
+            for (size_t e = 0; e < (size_t)3 * N; e++) F[e] = F[e] - std::min(std::max(a[e] * m.run.filter.shrink, -1.0), 1.0);
         }
     }
     for (int i = 0; i < N; i++) {
-        const size_t c = m.perm[i];
+        const size_t c = m.run.perm[i];
         for (int k = 0; k < 3; k++)
-            if (m.n_fixed && m.fixed_sorted[3 * (size_t)i + k]) velocities[3 * c + k] = 0.0;   // (a held component: F = 0, v = 0)
-            else if (kick) velocities[3 * c + k] = velocities[3 * c + k] + m.hdt * F[3 * c + k] / m.mass_sorted[i];
+            if (m.run.fix.n && m.run.fix.sorted[3 * (size_t)i + k]) velocities[3 * c + k] = 0.0;   // (a held component: F = 0, v = 0)
+            else if (kick) velocities[3 * c + k] = velocities[3 * c + k] + m.run.hdt * F[3 * c + k] / m.run.mass_sorted[i];
     }
     return SGPR_OK;
 }
@@ -1328,11 +1362,11 @@ extern "C" int sgpr_md_record(sgpr_model *h, int every, int what)
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_record: call sgpr_md_begin first");
     if (every < 0 || (what & ~3)) return fail(SGPR_E_INVALID, "sgpr_md_record: every >= 0, what = bit 0 (velocities) | bit 1 (results)");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.world);
-    if (every && !m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run has a committee (sgpr_md_committee), which records no frames");
-    if (every && m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run is a nudged elastic band (sgpr_md_neb), which records no frames; sgpr_md_neb_state behind a cut call serves trajectories");
-    m.rec_every = every;
-    m.rec_what = every ? what : 0;
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.run.world);
+    if (every && !m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run has a committee (sgpr_md_committee), which records no frames");
+    if (every && m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run is a nudged elastic band (sgpr_md_neb), which records no frames; sgpr_md_neb_state behind a cut call serves trajectories");
+    m.run.rec.every = every;
+    m.run.rec.what = every ? what : 0;
     return SGPR_OK;
 }
 
@@ -1341,7 +1375,7 @@ extern "C" int sgpr_md_frame_count(sgpr_model *h, int *count)
 {
     if (!h || !count) return fail(SGPR_E_INVALID, "sgpr_md_frame_count: bad arguments");
     if (!h->md.active) return fail(SGPR_E_INVALID, "sgpr_md_frame_count: call sgpr_md_begin first");
-    *count = h->md.rec_call_every ? h->md.rec_call_count : 0;
+    *count = h->md.run.rec.call_every ? h->md.run.rec.call_count : 0;
     return SGPR_OK;
 }
 
@@ -1353,21 +1387,21 @@ extern "C" int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *inde
     if (!h || first < 0 || count <= 0) return fail(SGPR_E_INVALID, "sgpr_md_frames: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_frames: call sgpr_md_begin first");
-    const int have = m.rec_call_every ? m.rec_call_count : 0;
+    const int have = m.run.rec.call_every ? m.run.rec.call_count : 0;
     if ((long long)first + count > have)
         return fail(SGPR_E_INVALID, "sgpr_md_frames: frames %d ... %lld asked for, the last sgpr_md_run recorded %d", first, (long long)first + count - 1, have);
-    if ((velocities_pre && !(m.rec_call_what & 1)) || (packed && !(m.rec_call_what & 2)))
-        return fail(SGPR_E_INVALID, "sgpr_md_frames: %s not recorded (sgpr_md_record's `what`)", velocities_pre && !(m.rec_call_what & 1) ? "velocities were" : "results were");
+    if ((velocities_pre && !(m.run.rec.call_what & 1)) || (packed && !(m.run.rec.call_what & 2)))
+        return fail(SGPR_E_INVALID, "sgpr_md_frames: %s not recorded (sgpr_md_record's `what`)", velocities_pre && !(m.run.rec.call_what & 1) ? "velocities were" : "results were");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N3 = (size_t)3 * m.N, plen = (size_t)sgpr_packed_len(m.N);
+    const size_t N3 = (size_t)3 * m.run.N, plen = (size_t)sgpr_packed_len(m.run.N);
     if (index) {
-        const long long ev = m.rec_call_every, n0 = (m.rec_call_t0 + ev - 1) / ev * ev;
+        const long long ev = m.run.rec.call_every, n0 = (m.run.rec.call_t0 + ev - 1) / ev * ev;
         for (int r = 0; r < count; r++) index[r] = n0 + ((long long)first + r) * ev;
     }
-    if (positions) HIPCHK(hipMemcpy(positions, m.rec_x.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
-    if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.rec_v.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
-    if (packed) HIPCHK(hipMemcpy(packed, m.rec_p.p + plen * first, sizeof(double) * plen * count, hipMemcpyDeviceToHost));
+    if (positions) HIPCHK(hipMemcpy(positions, m.rec.x.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
+    if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.rec.v.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.rec.p.p + plen * first, sizeof(double) * plen * count, hipMemcpyDeviceToHost));
     return SGPR_OK;
 }
 
@@ -1389,9 +1423,9 @@ extern "C" int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, doubl
     if (!m.active || m.seed == 0) return fail(SGPR_E_INVALID, "sgpr_md_deviates: call sgpr_md_begin and sgpr_md_seed first");
     HIPCHK(hipSetDevice(h->device));
     DevBuf<double> d;
-    if (d.alloc((size_t)count * 3 * m.N, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_deviates: device allocation failed");
-    hipLaunchKernelGGL(md_deviates_kernel, dim3(1024), dim3(256), 0, h->stream, m.N, count, m.seed, (long long)t_first, d.p);
-    HIPCHK(hipMemcpy(out, d.p, sizeof(double) * (size_t)count * 3 * m.N, hipMemcpyDeviceToHost));
+    if (d.alloc((size_t)count * 3 * m.run.N, false)) return fail(SGPR_E_NODEVICE, "sgpr_md_deviates: device allocation failed");
+    hipLaunchKernelGGL(md_deviates_kernel, dim3(1024), dim3(256), 0, h->stream, m.run.N, count, m.seed, (long long)t_first, d.p);
+    HIPCHK(hipMemcpy(out, d.p, sizeof(double) * (size_t)count * 3 * m.run.N, hipMemcpyDeviceToHost));
     return SGPR_OK;
 }
 
@@ -1413,29 +1447,29 @@ extern "C" int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, co
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_filter: call sgpr_md_begin first");
-    if (m.t != 0 || m.started) return fail(SGPR_E_INVALID, "sgpr_md_filter: the run has started");
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_filter: the run has started");
     if (!(shrink > 0.0 && shrink < 1.0)) return fail(SGPR_E_INVALID, "sgpr_md_filter: 0 < shrink < 1");
-    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a relaxation (sgpr_md_relax), which applies no filter");
-    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a nudged elastic band (sgpr_md_neb), which applies no filter");
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.world);
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a relaxation (sgpr_md_relax), which applies no filter");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a nudged elastic band (sgpr_md_neb), which applies no filter");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.run.world);
     HIPCHK(hipSetDevice(h->device));
-    const int N = m.N;
+    const int N = m.run.N;
     const size_t N3 = (size_t)3 * N;
-    if (m.filt_f.alloc(4 * N3) || m.filt_s.alloc(32) || m.filt_in.alloc(N3) || m.filt_perm.alloc(N))
+    if (m.filter.f.alloc(4 * N3) || m.filter.s.alloc(32) || m.filter.in.alloc(N3) || m.filter.perm.alloc(N))
         return fail(SGPR_E_NODEVICE, "sgpr_md_filter: device allocation failed");
-    HIPCHK(hipMemset(m.filt_f.p, 0, sizeof(double) * 4 * N3));
-    HIPCHK(hipMemset(m.filt_s.p, 0, sizeof(double) * 32));
-    HIPCHK(hipMemcpy(m.filt_perm.p, m.perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.filter.f.p, 0, sizeof(double) * 4 * N3));
+    HIPCHK(hipMemset(m.filter.s.p, 0, sizeof(double) * 32));
+    HIPCHK(hipMemcpy(m.filter.perm.p, m.run.perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
     if (f0) {
         std::vector<double> fs(N3);
         for (int i = 0; i < N; i++)
-            for (int k = 0; k < 3; k++) fs[3 * (size_t)i + k] = f0[3 * (size_t)m.perm[i] + k];
-        HIPCHK(hipMemcpy(m.filt_f.p, fs.data(), sizeof(double) * N3, hipMemcpyHostToDevice));
+            for (int k = 0; k < 3; k++) fs[3 * (size_t)i + k] = f0[3 * (size_t)m.run.perm[i] + k];
+        HIPCHK(hipMemcpy(m.filter.f.p, fs.data(), sizeof(double) * N3, hipMemcpyHostToDevice));
     }
-    for (int k = 0; k < 6; k++) m.filt_s_host[k] = s0 ? s0[k] : 0.0;
-    HIPCHK(hipMemcpy(m.filt_s.p, m.filt_s_host, sizeof(double) * 6, hipMemcpyHostToDevice));
-    m.filter = true; m.shrink = shrink;
+    for (int k = 0; k < 6; k++) m.run.filter.s_host[k] = s0 ? s0[k] : 0.0;
+    HIPCHK(hipMemcpy(m.filter.s.p, m.run.filter.s_host, sizeof(double) * 6, hipMemcpyHostToDevice));
+    m.run.filter.on = true; m.run.filter.shrink = shrink;
     return SGPR_OK;
 }
 
@@ -1460,19 +1494,19 @@ extern "C" int sgpr_md_filter_push(sgpr_model *h, const double *dF, const double
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter_push: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.filter) return fail(SGPR_E_INVALID, "sgpr_md_filter_push: call sgpr_md_begin and sgpr_md_filter first");
+    if (!m.active || !m.run.filter.on) return fail(SGPR_E_INVALID, "sgpr_md_filter_push: call sgpr_md_begin and sgpr_md_filter first");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     HIPCHK(hipStreamSynchronize(st));
-    const int N = m.N;
+    const int N = m.run.N;
     const size_t N3 = (size_t)3 * N;
     MdSix six = {};
-    const bool ws = m.npt && dS;
+    const bool ws = m.run.npt.on && dS;
     if (ws) for (int k = 0; k < 6; k++) six.v[k] = dS[k];
     if (!dF && !ws) return SGPR_OK;
-    if (dF) HIPCHK(hipMemcpy(m.filt_in.p, dF, sizeof(double) * N3, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(md_filter_push_kernel, dim3(dF ? (unsigned)((N3 + 255) / 256) : 1u), dim3(256), 0, st, dF ? N : 0, (const int *)m.filt_perm.p,
-                       (const double *)m.filt_in.p, m.filt_f.p + N3 * (size_t)(m.t % m.ring), six, ws ? m.filt_s.p + 6 * (m.t & 3) : (double *)nullptr);
+    if (dF) HIPCHK(hipMemcpy(m.filter.in.p, dF, sizeof(double) * N3, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(md_filter_push_kernel, dim3(dF ? (unsigned)((N3 + 255) / 256) : 1u), dim3(256), 0, st, dF ? N : 0, (const int *)m.filter.perm.p,
+                       (const double *)m.filter.in.p, m.filter.f.p + N3 * (size_t)(m.run.t % m.run.ring), six, ws ? m.filter.s.p + 6 * (m.run.t & 3) : (double *)nullptr);
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
     return SGPR_OK;
@@ -1484,14 +1518,14 @@ extern "C" int sgpr_md_filter_state(sgpr_model *h, double *f, double *s)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_filter_state: bad arguments");
     MdState &m = h->md;
-    if (!m.active || !m.filter) return fail(SGPR_E_INVALID, "sgpr_md_filter_state: call sgpr_md_begin and sgpr_md_filter first");
+    if (!m.active || !m.run.filter.on) return fail(SGPR_E_INVALID, "sgpr_md_filter_state: call sgpr_md_begin and sgpr_md_filter first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (f)
-        if (const int rc_ = md_fetch_rows(m, m.filt_f.p + (size_t)3 * m.N * (size_t)(m.t % m.ring), f)) return rc_;
+        if (const int rc_ = md_fetch_rows(m, m.filter.f.p + (size_t)3 * m.run.N * (size_t)(m.run.t % m.run.ring), f)) return rc_;
     if (s) {
-        if (m.npt) HIPCHK(hipMemcpy(s, m.filt_s.p + 6 * (m.t & 3), sizeof(double) * 6, hipMemcpyDeviceToHost));
-        else memcpy(s, m.filt_s_host, sizeof(double) * 6);
+        if (m.run.npt.on) HIPCHK(hipMemcpy(s, m.filter.s.p + 6 * (m.run.t & 3), sizeof(double) * 6, hipMemcpyDeviceToHost));
+        else memcpy(s, m.run.filter.s_host, sizeof(double) * 6);
     }
     return SGPR_OK;
 }
@@ -1511,20 +1545,20 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     if (!h || ncomp < 0) return fail(SGPR_E_INVALID, "sgpr_md_meta: bad arguments");
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_meta: call sgpr_md_begin first");
-    if (ncomp == 0) { m.meta = false; return SGPR_OK; }
+    if (ncomp == 0) { m.run.meta.on = false; return SGPR_OK; }
     if (!cvs || !sigma || ncomp > META_MAXC) return fail(SGPR_E_INVALID, "sgpr_md_meta: 1 to %d components, their list and sigma", META_MAXC);
-    if (m.npt) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a barostat (sgpr_md_barostat); the bias runs at constant cell, the host loop around calculate() serves a biased NPT run");
-    if (m.relax) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a relaxation (sgpr_md_relax); the bias serves dynamics only, the host loop around calculate() serves a biased relaxation");
-    if (m.neb) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a nudged elastic band (sgpr_md_neb); the bias serves dynamics only, the host loop around calculate() serves a biased band");
-    if (!m.bcm.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a committee (sgpr_md_committee), whose loop does not apply a bias; the host loop around calculate() serves it");
-    if (m.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run was begun on %d ranks; the bias runs on one, the host loop around calculate() serves sharded runs", m.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a barostat (sgpr_md_barostat); the bias runs at constant cell, the host loop around calculate() serves a biased NPT run");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a relaxation (sgpr_md_relax); the bias serves dynamics only, the host loop around calculate() serves a biased relaxation");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a nudged elastic band (sgpr_md_neb); the bias serves dynamics only, the host loop around calculate() serves a biased band");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a committee (sgpr_md_committee), whose loop does not apply a bias; the host loop around calculate() serves it");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run was begun on %d ranks; the bias runs on one, the host loop around calculate() serves sharded runs", m.run.world);
     if (pace < 1 || capacity < 1 || capacity > (1 << 28) || nhills < 0 || nhills > capacity || (nhills > 0 && !hills_cv))
         return fail(SGPR_E_INVALID, "sgpr_md_meta: pace >= 1, 1 <= capacity <= 2^28, 0 <= nhills <= capacity");
     if (!(w == w) || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_meta: w a number, kT >= 0");
-    const int N = m.N;
+    const int N = m.run.N;
     MetaPar p = {};
     std::vector<int> inv(N);
-    for (int i = 0; i < N; i++) inv[m.perm[i]] = i;
+    for (int i = 0; i < N; i++) inv[m.run.perm[i]] = i;
     std::vector<unsigned char> sel((size_t)ncomp * N, 0);
     int D = 0;
     for (int q = 0; q < ncomp; q++) {
@@ -1539,8 +1573,8 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
         } else {
             int n = 0;
             for (int i = 0; i < N; i++) {
-                const int cidx = m.perm[i];
-                if (b >= 0 && m.numbers[cidx] != b) continue;
+                const int cidx = m.run.perm[i];
+                if (b >= 0 && m.run.numbers[cidx] != b) continue;
                 n++;
                 if (cidx != a) sel[(size_t)q * N + i] = 1;
             }
@@ -1575,18 +1609,18 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t cap = (size_t)capacity;
-    if (m.meta_centre.alloc(cap * META_MAXD) || m.meta_rows.alloc(cap * (META_MAXD + 1)) || m.meta_key.alloc(cap * META_MAXD) ||
-        m.meta_sel.alloc((size_t)ncomp * N))
+    if (m.meta.centre.alloc(cap * META_MAXD) || m.meta.rows.alloc(cap * (META_MAXD + 1)) || m.meta.key.alloc(cap * META_MAXD) ||
+        m.meta.sel.alloc((size_t)ncomp * N))
         return fail(SGPR_E_NODEVICE, "sgpr_md_meta: device allocation failed");
     if (nhills) {
-        HIPCHK(hipMemcpy(m.meta_centre.p, ce.data(), sizeof(double) * ce.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(m.meta_rows.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(m.meta_key.p, ke.data(), sizeof(int) * ke.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.meta.centre.p, ce.data(), sizeof(double) * ce.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.meta.rows.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m.meta.key.p, ke.data(), sizeof(int) * ke.size(), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMemcpy(m.meta_sel.p, sel.data(), sel.size(), hipMemcpyHostToDevice));
-    m.mp = p; m.meta_pace = pace; m.meta_base = m.t; m.meta_pre = nhills; m.meta_cap = capacity;
-    m.meta = true; m.meta_fresh = true;
-    m.meta_merge = 0; m.meta_enq = 0;   // (every hill on its own until sgpr_md_meta_merge says otherwise)
+    HIPCHK(hipMemcpy(m.meta.sel.p, sel.data(), sel.size(), hipMemcpyHostToDevice));
+    m.run.meta.par = p; m.run.meta.pace = pace; m.run.meta.base = m.run.t; m.run.meta.pre = nhills; m.run.meta.cap = capacity;
+    m.run.meta.on = true; m.run.meta.fresh = true;
+    m.run.meta.merge = 0; m.run.meta.enq = 0;   // (every hill on its own until sgpr_md_meta_merge says otherwise)
     return SGPR_OK;
 }
 
@@ -1599,26 +1633,26 @@ extern "C" int sgpr_md_meta_merge(sgpr_model *h, int64_t chunk)
 {
     if (!h || chunk < 0 || chunk > (1 << 28)) return fail(SGPR_E_INVALID, "sgpr_md_meta_merge: 0 <= chunk <= 2^28");
     MdState &m = h->md;
-    if (!m.active || !m.meta || !m.meta_fresh)
+    if (!m.active || !m.run.meta.on || !m.run.meta.fresh)
         return fail(SGPR_E_INVALID, "sgpr_md_meta_merge: call sgpr_md_meta first, and this before the next sgpr_md_run");
-    m.meta_merge = 0; m.meta_enq = 0;
+    m.run.meta.merge = 0; m.run.meta.enq = 0;
     if (chunk == 0) return SGPR_OK;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t cap = (size_t)m.meta_cap, D = (size_t)m.mp.D;
-    if (m.meta_tcentre.alloc(cap * D) || m.meta_tkey.alloc(cap * D) || m.meta_tcnt.alloc(cap) || m.meta_tlast.alloc(cap) || m.meta_tstamp.alloc(cap) ||
-        m.meta_ctl.alloc(META_CTL_LEN))
+    const size_t cap = (size_t)m.run.meta.cap, D = (size_t)m.run.meta.par.D;
+    if (m.meta.tcentre.alloc(cap * D) || m.meta.tkey.alloc(cap * D) || m.meta.tcnt.alloc(cap) || m.meta.tlast.alloc(cap) || m.meta.tstamp.alloc(cap) ||
+        m.meta.ctl.alloc(META_CTL_LEN))
         return fail(SGPR_E_NODEVICE, "sgpr_md_meta_merge: device allocation failed");
     const int ctl[META_CTL_LEN] = {0, 0, 0, INT_MAX};
-    HIPCHK(hipMemcpy(m.meta_ctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice));
-    m.meta_merge = (int)chunk;
-    const long long pre = m.meta_pre / chunk;
+    HIPCHK(hipMemcpy(m.meta.ctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+    m.run.meta.merge = (int)chunk;
+    const long long pre = m.run.meta.pre / chunk;
     for (long long j = 0; j < pre; j++)
-        hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, h->stream, m.mp.D, m.meta_merge, (int)j, (const double *)m.meta_centre.p,
-                           (const int *)m.meta_key.p, m.meta_tab(pre), (const int *)(m.meta_ctl.p + META_CTL_RUN), 0);
+        hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, h->stream, m.run.meta.par.D, m.run.meta.merge, (int)j, (const double *)m.meta.centre.p,
+                           (const int *)m.meta.key.p, m.meta_tab(pre), (const int *)(m.meta.ctl.p + META_CTL_RUN), 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
-    m.meta_enq = pre;
+    m.run.meta.enq = pre;
     return SGPR_OK;
 }
 
@@ -1629,25 +1663,25 @@ extern "C" int sgpr_md_meta_table(sgpr_model *h, double *centres, double *counts
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_meta_table: bad arguments");
     const MdState &m = h->md;
-    if (!m.active || !m.meta || !m.meta_merge) return fail(SGPR_E_INVALID, "sgpr_md_meta_table: call sgpr_md_begin, sgpr_md_meta and sgpr_md_meta_merge first");
+    if (!m.active || !m.run.meta.on || !m.run.meta.merge) return fail(SGPR_E_INVALID, "sgpr_md_meta_table: call sgpr_md_begin, sgpr_md_meta and sgpr_md_meta_merge first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     int ctl[META_CTL_LEN];
-    HIPCHK(hipMemcpy(ctl, m.meta_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ctl, m.meta.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
     // (behind a halt the table may be one chunk ahead of the current configuration: that chunk is taken off, as its evaluation does)
-    const long long want = std::min<long long>(m.meta_slot(m.t) / m.meta_merge, ctl[META_CTL_DONE]);
+    const long long want = std::min<long long>(m.run.meta_slot(m.run.t) / m.run.meta.merge, ctl[META_CTL_DONE]);
     const bool ahead = ctl[META_CTL_DONE] != want;
-    const size_t T = (size_t)(ahead ? ctl[META_CTL_TPREV] : ctl[META_CTL_T]), D = (size_t)m.mp.D;
+    const size_t T = (size_t)(ahead ? ctl[META_CTL_TPREV] : ctl[META_CTL_T]), D = (size_t)m.run.meta.par.D;
     if (n_entries) *n_entries = (int64_t)T;
-    if (rows_merged) *rows_merged = (int64_t)(want * m.meta_merge);
-    if (centres && T) HIPCHK(hipMemcpy(centres, m.meta_tcentre.p, sizeof(double) * T * D, hipMemcpyDeviceToHost));
+    if (rows_merged) *rows_merged = (int64_t)(want * m.run.meta.merge);
+    if (centres && T) HIPCHK(hipMemcpy(centres, m.meta.tcentre.p, sizeof(double) * T * D, hipMemcpyDeviceToHost));
     if (counts && T) {
-        HIPCHK(hipMemcpy(counts, m.meta_tcnt.p, sizeof(double) * T, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(counts, m.meta.tcnt.p, sizeof(double) * T, hipMemcpyDeviceToHost));
         if (ahead) {
             std::vector<double> last(T);
             std::vector<int> stamp(T);
-            HIPCHK(hipMemcpy(last.data(), m.meta_tlast.p, sizeof(double) * T, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(stamp.data(), m.meta_tstamp.p, sizeof(int) * T, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(last.data(), m.meta.tlast.p, sizeof(double) * T, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(stamp.data(), m.meta.tstamp.p, sizeof(int) * T, hipMemcpyDeviceToHost));
             for (size_t k = 0; k < T; k++)
                 if (stamp[k] == ctl[META_CTL_DONE] - 1) counts[k] -= last[k];
         }
@@ -1658,18 +1692,18 @@ extern "C" int sgpr_md_meta_table(sgpr_model *h, double *centres, double *counts
 // D; `below`: the hills below the current configuration — the rows uploaded at the attach and the deposits of the configurations
 // before it: what sgpr_md_meta takes to go on from here —; `held`: those and the current configuration's own row where the last
 // sgpr_md_run evaluated it (a halted or `final` call): what sgpr_md_meta_hills serves; the capacity.  Any of them NULL.
-// (meta_fresh: no sgpr_md_run since the attach — the current configuration's own row is not in these buffers, whatever an earlier
+// (meta.fresh: no sgpr_md_run since the attach — the current configuration's own row is not in these buffers, whatever an earlier
 // call evaluated)
-static long long md_meta_held(const MdState &m) { return m.meta_slot(m.t) + ((m.evaluated && !m.meta_fresh && m.t % m.meta_pace == 0) ? 1 : 0); }
+static long long md_meta_held(const MdState &m) { return m.run.meta_slot(m.run.t) + ((m.run.evaluated && !m.run.meta.fresh && m.run.t % m.run.meta.pace == 0) ? 1 : 0); }
 extern "C" int sgpr_md_meta_info(sgpr_model *h, int *D, int64_t *below, int64_t *held, int64_t *capacity)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_meta_info: bad arguments");
     const MdState &m = h->md;
-    if (!m.active || !m.meta) return fail(SGPR_E_INVALID, "sgpr_md_meta_info: call sgpr_md_begin and sgpr_md_meta first");
-    if (D) *D = m.mp.D;
-    if (below) *below = m.meta_slot(m.t);
+    if (!m.active || !m.run.meta.on) return fail(SGPR_E_INVALID, "sgpr_md_meta_info: call sgpr_md_begin and sgpr_md_meta first");
+    if (D) *D = m.run.meta.par.D;
+    if (below) *below = m.run.meta_slot(m.run.t);
     if (held) *held = md_meta_held(m);
-    if (capacity) *capacity = m.meta_cap;
+    if (capacity) *capacity = m.run.meta.cap;
     return SGPR_OK;
 }
 
@@ -1679,14 +1713,14 @@ extern "C" int sgpr_md_meta_hills(sgpr_model *h, int64_t first, int64_t count, d
 {
     if (!h || first < 0 || count <= 0) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: bad arguments");
     const MdState &m = h->md;
-    if (!m.active || !m.meta) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: call sgpr_md_begin and sgpr_md_meta first");
+    if (!m.active || !m.run.meta.on) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: call sgpr_md_begin and sgpr_md_meta first");
     const long long held = md_meta_held(m);
     if (first + count > held) return fail(SGPR_E_INVALID, "sgpr_md_meta_hills: rows %lld ... %lld asked for, %lld stand", (long long)first, (long long)(first + count - 1), held);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const int D = m.mp.D;
+    const int D = m.run.meta.par.D;
     std::vector<double> rows((size_t)(META_MAXD + 1) * count);
-    HIPCHK(hipMemcpy(rows.data(), m.meta_rows.p + (size_t)(META_MAXD + 1) * first, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows.data(), m.meta.rows.p + (size_t)(META_MAXD + 1) * first, sizeof(double) * rows.size(), hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < count; r++) {
         if (cv) for (int d = 0; d < D; d++) cv[(size_t)D * r + d] = rows[(size_t)(META_MAXD + 1) * r + d];
         if (V) V[r] = rows[(size_t)(META_MAXD + 1) * r + META_MAXD];
@@ -1697,14 +1731,13 @@ extern "C" int sgpr_md_meta_hills(sgpr_model *h, int64_t first, int64_t count, d
 extern "C" int sgpr_md_end(sgpr_model *h)
 {
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_end: bad arguments");
-    h->md.active = false;
-    if (h->md.meta || h->md.meta_rows.p) {   // (the hills of a bias are the run's: given back with it)
+    MdState &m = h->md;
+    m.active = false;
+    if (m.run.meta.on || m.meta.held()) {   // (the hills of a bias are the run's: given back with it, by a move-assign of the empty group)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
-        h->md.meta = false;
-        h->md.meta_centre.release(); h->md.meta_rows.release(); h->md.meta_key.release(); h->md.meta_sel.release();
-        h->md.meta_merge = 0; h->md.meta_tab_release();
+        m.meta = MdState::MetaBufs();
     }
-    h->md.bcm.clear(); h->md.bcm_info.clear();   // (the borrowed members are let go)
+    m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;
 }

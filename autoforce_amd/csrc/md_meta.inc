@@ -10,7 +10,7 @@
 // sums exp(-|(x - centre) / sigma|^2 / 2) / (2 pi)^(D/2) over the hills whose key differs from floor(x / (5 sigma)) by at most
 // one in every dimension.  V = w kde, or log(1 + w kde gamma) / gamma (well-tempered).
 //
-// Hills are rows in HBM indexed by CONFIGURATION (MdState::meta_slot): the loop evaluates speculatively and discards what it
+// Hills are rows in HBM indexed by CONFIGURATION (MdRun::meta_slot): the loop evaluates speculatively and discards what it
 // evaluated behind a halt; an evaluation that is repeated or discarded overwrites its own row and nothing is rolled back.  The
 // bias of configuration n sums the rows below its own.
 //
