@@ -94,6 +94,7 @@ SIGNATURES = {
     "sgpr_md_filter_push": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_md_filter_state": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_md_meta": (C.c_int, [_vp, C.c_int, _vp, _vp, _dbl, _dbl, C.c_int, _i64, _i64, _vp, _vp]),
+    "sgpr_md_meta_ql": (C.c_int, [_vp, C.c_int, _dbl, C.c_int, _vp]),
     "sgpr_md_meta_info": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sgpr_md_meta_hills": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "sgpr_md_meta_merge": (C.c_int, [_vp, _i64]),

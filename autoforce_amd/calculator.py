@@ -687,6 +687,9 @@ class ActiveCalculator(Calculator):
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
             # every batch the new rows are mirrored into the Meta (meta.hist, and calculate() at a halt sees the same bias)
             meta.species = list(eng.species)   # (the twin's mean of a posvar in the device's order)
+            meta.rc = float(eng.cutoff)        # (a Qlvar reads the model's list)
+            if hasattr(meta, "resolve"):
+                meta.resolve(np.asarray(numbers))
             if meta.pace > 1 and meta.n % meta.pace:
                 # (the device counts configurations from 0 in every run: a run that goes on from a Meta in the middle of its pace
                 # would deposit on another cadence than the Meta's own update())

@@ -263,6 +263,11 @@ struct MdRun {
         long long base = 0, pre = 0, cap = 0;
         int merge = 0;                    // the merged form (sgpr_md_meta_merge): the chunk length (0: every hill on its own)
         long long enq = 0;                // chunks whose merge this call has enqueued or found done (the device word decides)
+        // kind 2 (qlvar): what sgpr_md_meta_ql staged for the next sgpr_md_meta, and what that attach took (nql: its kind-2
+        // components; 0: the kernels of the other kinds, as ever).  ql's pointers are set at every launch.
+        struct QlStage { bool set = false; double cut = 0.0; int nl = 0; int l[META_MAXD] = {0, 0, 0, 0, 0, 0}; } stage[META_MAXC];
+        MetaQl ql = {};
+        int nql = 0;
     } meta;
     // the frame record (sgpr_md_record, md_record.inc): every `every`-th configuration of a call, copied out behind its evaluation
     // in caller atom order — positions always, velocities / results by the bits of `what`.  call_*: what the LAST sgpr_md_run
@@ -2778,7 +2783,29 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
                                             "and sharded frames take the host loop around calculate()");
         const long long n = nx->md.t_index;
-        if (m.run.meta.merge) {
+        MetaQl ql = m.run.meta.ql;
+        if (m.run.meta.nql) {
+            // a qlvar reads this step's list; its rows in LDS are sized for META_QL_MAXT selected neighbours (the list may have grown)
+            if ((long long)m.run.meta.nql * h->maxnn > META_QL_MAXT)
+                return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias has %d qlvar component(s) and the neighbour list holds up to %d entries per atom; together at "
+                                                "most %d (the host loop around calculate() serves longer lists)", m.run.meta.nql, h->maxnn, META_QL_MAXT);
+            ql.nn = h->d_nn.p; ql.nbr_j = h->d_nbr_j.p; ql.nbr_code = h->d_nbr_shift.p; ql.cell = cell_dev; ql.maxnn = h->maxnn;
+        }
+        if (m.run.meta.nql && m.run.meta.merge) {
+            const long long want = m.run.meta_slot(n) / m.run.meta.merge;
+            for (long long &j = h->md.run.meta.enq; j < want; j++) {
+                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.run.meta.par.D, m.run.meta.merge, (int)j, (const double *)m.meta.centre.p,
+                                   (const int *)m.meta.key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
+                stamp(h, "md_meta_merge", st);
+            }
+            hipLaunchKernelGGL(md_meta_merged_ql_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, ql, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
+                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
+                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
+        } else if (m.run.meta.nql) {
+            hipLaunchKernelGGL(md_meta_ql_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, ql, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
+                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
+                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
+        } else if (m.run.meta.merge) {
             // the chunks that lie below this configuration and are not merged yet: at a crossing, or at the first configuration
             // of a call that is behind
             const long long want = m.run.meta_slot(n) / m.run.meta.merge;

@@ -1146,6 +1146,9 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only (one rank, no graph "
                         "replay, no side-stream fork, a skin > 0): the host loop around calculate() serves this run");
+        if ((long long)m.run.meta.nql * h->maxnn > META_QL_MAXT)
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias has %d qlvar component(s) and the neighbour list holds up to %d entries per atom; together at "
+                        "most %d: the host loop around calculate() serves this run", m.run.meta.nql, h->maxnn, META_QL_MAXT);
         // the last configuration of the call that deposits a hill must find its row
         const long long nd = (m.run.t + nevals - 1) / m.run.meta.pace * m.run.meta.pace;
         if (nd >= m.run.t && m.run.meta_slot(nd) >= m.run.meta.cap)
@@ -1560,13 +1563,36 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     std::vector<int> inv(N);
     for (int i = 0; i < N; i++) inv[m.run.perm[i]] = i;
     std::vector<unsigned char> sel((size_t)ncomp * N, 0);
+    // what sgpr_md_meta_ql staged is this call's, whatever becomes of it
+    MdRun::Meta::QlStage stage[META_MAXC];
+    for (int q = 0; q < META_MAXC; q++) { stage[q] = m.run.meta.stage[q]; m.run.meta.stage[q] = MdRun::Meta::QlStage(); }
+    MetaQl ql = {};
+    for (int d = 0; d < META_MAXD; d++) ql.dcomp[d] = -1;
+    int nql = 0;
     int D = 0;
     for (int q = 0; q < ncomp; q++) {
         const int kind = cvs[3 * q], a = cvs[3 * q + 1], b = cvs[3 * q + 2];
-        if (kind != 0 && kind != 1) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: kind 0 (distance) or 1 (posvar)", q);
+        if (kind != 0 && kind != 1 && kind != 2) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: kind 0 (distance), 1 (posvar) or 2 (qlvar)", q);
         if (a < 0 || a >= N) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: atom %d of %d", q, a, N);
         p.kind[q] = kind; p.ia[q] = inv[a]; p.nsel[q] = 1.0;
-        if (kind == 0) {
+        if (kind == 2) {
+            // Q_l of atom a over its neighbours of species b inside the staged cutoff
+            if (!stage[q].set) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d is a qlvar: stage its cutoff and l with sgpr_md_meta_ql first", q);
+            int slot = -1;
+            for (int k = 0; k < h->S; k++)
+                if (h->species[k] == b) slot = k;
+            bool present = false;
+            for (int i = 0; i < N; i++) present = present || m.run.numbers[i] == b;
+            if (slot < 0 || !present) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: no atom of species %d (an environment of nothing)", q, b);
+            if (!(stage[q].cut > 0.0) || stage[q].cut > h->rc)
+                return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: cutoff %g; the list reaches rc = %g and the weight is not zero there: 0 < cutoff <= rc", q,
+                            stage[q].cut, h->rc);
+            if (D + stage[q].nl > META_MAXD) return fail(SGPR_E_INVALID, "sgpr_md_meta: %d dimensions; at most %d", D + stage[q].nl, META_MAXD);
+            ql.slot[q] = slot; ql.cut[q] = stage[q].cut; ql.nl[q] = stage[q].nl;
+            for (int k = 0; k < stage[q].nl; k++) { ql.dcomp[D + k] = q; ql.dl[D + k] = stage[q].l[k]; }
+            D += stage[q].nl;
+            nql++;
+        } else if (kind == 0) {
             if (b < 0 || b >= N || b == a) return fail(SGPR_E_INVALID, "sgpr_md_meta: component %d: distance between atoms %d and %d of %d", q, a, b, N);
             p.ib[q] = inv[b];
             D += 1;
@@ -1584,6 +1610,9 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
         }
     }
     if (D > META_MAXD) return fail(SGPR_E_INVALID, "sgpr_md_meta: %d dimensions; at most %d", D, META_MAXD);
+    if ((long long)nql * h->maxnn > META_QL_MAXT)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: %d qlvar component(s) and a neighbour list of up to %d entries per atom; together at most %d: the host loop "
+                    "around calculate() serves this model", nql, h->maxnn, META_QL_MAXT);
     p.D = D; p.ncomp = ncomp; p.wt = kT > 0.0 ? 1 : 0;
     p.w = w; p.gamma = kT > 0.0 ? 1.0 / kT : 0.0;
     p.norm = 1.0;
@@ -1621,6 +1650,28 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     m.run.meta.par = p; m.run.meta.pace = pace; m.run.meta.base = m.run.t; m.run.meta.pre = nhills; m.run.meta.cap = capacity;
     m.run.meta.on = true; m.run.meta.fresh = true;
     m.run.meta.merge = 0; m.run.meta.enq = 0;   // (every hill on its own until sgpr_md_meta_merge says otherwise)
+    m.run.meta.ql = ql; m.run.meta.nql = nql;
+    return SGPR_OK;
+}
+
+// Stages the parameters of component `comp` of the NEXT sgpr_md_meta, whose cvs triple (2, index, Zj) consumes them: the
+// Steinhardt Q_l (md_meta.inc, kind 2) of atom `index` over its neighbours of species Zj with r < cutoff <= rc, one dimension per
+// l[k], 0 <= l <= 12, 1 <= n_l <= 6.  After sgpr_md_begin; sgpr_md_meta takes what is staged and clears it, whether it succeeds or not.
+extern "C" int sgpr_md_meta_ql(sgpr_model *h, int comp, double cutoff, int n_l, const int32_t *l)
+{
+    if (!h || !l) return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: call sgpr_md_begin first");
+    if (comp < 0 || comp >= META_MAXC) return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: component %d; 0 ... %d", comp, META_MAXC - 1);
+    if (n_l < 1 || n_l > META_MAXD) return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: %d values of l; 1 ... %d (one dimension each)", n_l, META_MAXD);
+    for (int k = 0; k < n_l; k++)
+        if (l[k] < 0 || l[k] > META_QL_MAXL) return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: l = %d; 0 ... %d", l[k], META_QL_MAXL);
+    if (!(cutoff > 0.0) || cutoff > h->rc)
+        return fail(SGPR_E_INVALID, "sgpr_md_meta_ql: cutoff %g; the list reaches rc = %g and the weight is not zero there: 0 < cutoff <= rc", cutoff, h->rc);
+    MdRun::Meta::QlStage &s = m.run.meta.stage[comp];
+    s = MdRun::Meta::QlStage();
+    s.set = true; s.cut = cutoff; s.nl = n_l;
+    for (int k = 0; k < n_l; k++) s.l[k] = l[k];
     return SGPR_OK;
 }
 

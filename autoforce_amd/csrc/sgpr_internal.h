@@ -115,13 +115,29 @@ struct NptParams {
 
 struct MetaPar {
     int D, ncomp, wt, pad_;
-    int kind[META_MAXC];            // 0: distance, 1: posvar
-    int ia[META_MAXC];              // sorted index of atom i (distance) / of the index atom (posvar)
+    int kind[META_MAXC];            // 0: distance, 1: posvar, 2: qlvar (with a MetaQl)
+    int ia[META_MAXC];              // sorted index of atom i (distance) / of the index atom (posvar, qlvar)
     int ib[META_MAXC];              // sorted index of atom j (distance)
     double nsel[META_MAXC];         // posvar: n = |sel|
     double sigma[META_MAXD];
     double sigma5[META_MAXD];       // 5 sigma, a product
     double w, gamma, norm;          // height, 1 / kT (well-tempered), sqrt(2 pi)^D as a product of D factors
+};
+
+// kind 2, the Steinhardt Q_l of one atom's shell of one species (sgpr_md_meta_ql): the kernels of a spec that has one take this
+// beside MetaPar, which stays what the other kinds' kernels were built with
+#define META_QL_MAXL 12    // 0 <= l <= 12: the Legendre recurrence serves any l, the bound keeps a typo out
+#define META_QL_TINY_ANGLE 1e-2   // the reference's shear near the z axis (descriptor/ylm.py:10-23), as SGPR_TINY_ANGLE
+#define META_QL_MAXT 256   // selected neighbours of all kind-2 components together: one thread each (and NL_SORT_MAX: a longer list has no defined order)
+struct MetaQl {
+    const int *nn, *nbr_j, *nbr_code;   // this step's list (the forward pass): [N], [N][maxnn] x2, code = image triple | species slot << 24
+    const double *cell;                 // [9] rows
+    int maxnn, pad_;
+    int slot[META_MAXC];                // species slot of the environment
+    int nl[META_MAXC];                  // dimensions of the component (0: of another kind)
+    double cut[META_MAXC];
+    int dcomp[META_MAXD];               // dimension d of the CV: its component (-1: of another kind) and its l
+    int dl[META_MAXD];
 };
 
 // the hills merged by bin (sgpr_md_meta_merge): one entry per occupied bin, in the order of the first row that occupied it

@@ -9,7 +9,8 @@ A Meta adds V(cv) = w kde(cv) — with tem the well-tempered log(1 + w kde gamma
 -dV/dx to the forces and -(1/V_cell) sum_i x_i (x) F_i to the stress of every calculate(), as the reference's post_calculate does
 with op="+=" (calculator/active.py:510-516, :557-580), and update() deposits a hill where the last bias was evaluated (the
 reference: dyn.attach(meta.update)) and appends the CV to meta.hist.  workloads.meta_bias is the definition of the built-in
-collective variables Distance, Posvar and Catvar; for these the device MD loop evaluates the bias itself (device_spec()).
+collective variables Distance, Posvar, Qlvar and Catvar; for these the device MD loop evaluates the bias itself
+(device_spec()).
 Any other colvar — a function (numbers, xyz, cell, pbc, nl) -> 1-d torch tensor of xyz, the reference's interface — is
 differentiated with torch.autograd on the host path.
 """
@@ -51,6 +52,46 @@ class Posvar:
         return x[self.index] - x[a].sum(axis=0) / float(sel.sum())
 
 
+class Qlvar:
+    """The reference's Qlvar(i, j, index=None, cutoff=4.0, l=[6]): the Steinhardt bond-order parameters Q_l of atom `index` (of
+    species i; None: the first atom with numbers == i, resolved at the first use; RuntimeError where numbers[index] != i) over
+    its neighbours t of species j with r_t < cutoff, r_t = x_j - x_index + shift.cell:
+        w_t = (1 - r_t / cutoff)^2, W = sum w_t, q_lm = sum_t w_t Y_lm(r^_t) / W, Q_l = sqrt(4 pi / (2l + 1) sum_m |q_lm|^2)
+    evaluated by the addition theorem, Q_l^2 = sum_{t,t'} w_t w_t' P_l(r^_t . r^_t') / W^2 (workloads.ql_dim is the definition:
+    no Y_lm, no pole on the z axis, 0 <= l <= 12).  len(l) dimensions, in the order of l.  The device loop reads the model's own
+    neighbour list, which ends at the model's rc: cutoff <= rc is required (Meta.bias refuses a larger one).
+      Like the reference's Ylm, the whole environment is sheared by 1e-2 when a selected neighbour lies within 1e-2 of the z axis
+    (workloads.ql_rows): Q_l then differs from the unsheared value by up to a few 1e-5, as the reference's does.
+      Where this departs from the reference: an empty environment gives Q_l = 0 with zero gradient (there: NaN, 0 / 0), and
+    where Q_l = 0 the gradient is 0 (there: NaN, which nan_to_num turns into 0)."""
+
+    def __init__(self, i, j, index=None, cutoff=4.0, l=[6]):
+        self.i, self.j, self.index = int(i), int(j), (None if index is None else int(index))
+        self.cutoff, self.l = float(cutoff), tuple(int(v) for v in l)
+        self.dim = len(self.l)
+
+    def resolve(self, numbers):
+        numbers = np.asarray(numbers)
+        if self.index is None:
+            found = np.where(numbers == self.i)[0]
+            if not len(found):
+                raise RuntimeError(f"Qlvar: no atom with numbers == {self.i}")
+            self.index = int(found[0])
+        if numbers[self.index] != self.i:
+            raise RuntimeError(f"numbers[{self.index}] != {self.i}")
+        return self.index
+
+    def spec(self):
+        return [("qlvar", self.index, self.j, self.cutoff, self.l)]
+
+    def __call__(self, numbers, xyz, cell, pbc, nl=None):
+        from .workloads import ql_dim, ql_environment, ql_rows
+        idx = self.resolve(numbers)
+        _, _, r, ln = ql_environment(numbers, xyz, cell, pbc, idx, self.j, self.cutoff, nl=nl)
+        rows = ql_rows(r, ln, self.cutoff)
+        return np.array([ql_dim(l, *rows)[0] for l in self.l])
+
+
 class Catvar:
     """Components concatenated (the reference's Catvar)."""
 
@@ -65,6 +106,11 @@ class Catvar:
                 return None
             out += s
         return out
+
+    def resolve(self, numbers):
+        for v in self.var:
+            if hasattr(v, "resolve"):
+                v.resolve(numbers)
 
     def __call__(self, *args):
         return np.concatenate([np.asarray(v(*args), float).reshape(-1) for v in self.var])
@@ -83,6 +129,7 @@ class Meta:
         if self.merge is not None and self.merge < 1:
             raise ValueError(f"Meta: merge is a chunk length >= 1 or None, not {merge}")
         self.species = None   # the model's species table: the order in which a posvar's mean is summed (None: sorted numbers)
+        self.rc = None        # the model's cutoff: a Qlvar reads the model's list (ActiveCalculator and run_md set it)
         self.hills = []     # CV values of the deposits, in order
         self.n = 0          # configurations update() has seen
         self._cv = None
@@ -92,12 +139,18 @@ class Meta:
                 hst.write(f"# {sigma}\n")
 
     def device_spec(self):
-        """The components as SGPRModel.md_meta takes them, or None when one is not built in (Distance, Posvar, Catvar of
-        them; at most 4 components and 6 dimensions)."""
+        """The components as SGPRModel.md_meta takes them, or None when one is not built in (Distance, Posvar, Qlvar, Catvar
+        of them; at most 4 components and 6 dimensions).  A Qlvar(index=None) stands with index None until resolve(numbers)."""
+        from .workloads import meta_cv_dim
         s = self.colvar.spec() if hasattr(self.colvar, "spec") else None
-        if not s or len(s) > 4 or sum(1 if c[0] == "distance" else 3 for c in s) > 6:
+        if not s or len(s) > 4 or meta_cv_dim(s) > 6:
             return None
         return s
+
+    def resolve(self, numbers):
+        """Fixes the atom of every Qlvar(index=None) (the first of its species) and checks the species at the index."""
+        if hasattr(self.colvar, "resolve"):
+            self.colvar.resolve(numbers)
 
     def hills_array(self, D=None):
         return np.asarray(self.hills, float).reshape(len(self.hills), -1) if self.hills else np.zeros((0, D or 0))
@@ -114,15 +167,17 @@ class Meta:
         centres, _, counts, _ = meta_table(H, sg if len(sg) > 1 else sg[0], self.merge or 1)
         return centres, counts
 
-    def bias(self, positions, cell, numbers=None):
+    def bias(self, positions, cell, numbers=None, pbc=None, rc=None):
         """(V, forces [N, 3], stress [6]) of the bias at this configuration with the hills deposited so far; the CV is kept
-        for update()."""
+        for update().  pbc and rc (the model's cutoff; default: self.rc): what a Qlvar needs."""
         from .workloads import meta_bias
         x = np.asarray(positions, float)
         numbers = np.zeros(len(x), int) if numbers is None else np.asarray(numbers)
+        self.resolve(numbers)
         spec = self.device_spec()
         if spec is not None:
-            out = meta_bias(spec, self.sigma, self.w, numbers, x, cell, self.hills_array(), tem=self.tem, species=self.species, merge=self.merge)
+            kw = dict(pbc=pbc, rc=self.rc if rc is None else rc) if any(c[0] == "qlvar" for c in spec) else {}
+            out = meta_bias(spec, self.sigma, self.w, numbers, x, cell, self.hills_array(), tem=self.tem, species=self.species, merge=self.merge, **kw)
             self._cv, self.energy, self.margin = out["cv"], out["energy"], out["margin"]
             return out["energy"], out["forces"], out["stress"]
         return self._bias_autograd(numbers, x, cell)
@@ -172,6 +227,7 @@ class Meta:
         """The calculator's hook (the reference's Meta.__call__): the bias energy of calc.atoms; post_calculate adds energy,
         forces and stress to calc.results."""
         at = calc.atoms
-        V, F, S = self.bias(at.positions, getattr(at.cell, "array", at.cell), at.numbers)
+        eng = getattr(calc, "engine", None)
+        V, F, S = self.bias(at.positions, getattr(at.cell, "array", at.cell), at.numbers, pbc=at.pbc, rc=getattr(eng, "cutoff", None))
         self._last = (V, F, S)
         return np.array([V]), {"op": "+=", "is_meta": True}

@@ -666,7 +666,7 @@ class SGPRModel:
         check(_lib.load().sgpr_md_filter_state(self._h, ptr(f), ptr(s_)))
         return f, s_
 
-    META_KINDS = {"distance": 0, "posvar": 1}
+    META_KINDS = {"distance": 0, "posvar": 1, "qlvar": 2}
 
     def md_meta(self, cvs, sigma, w, tem=None, pace=1, hills=None, capacity=None, merge=None):
         """Metadynamics for the run begun by md_begin (sgpr_md_meta; md_meta.inc has the scheme, workloads.meta_bias is the host
@@ -676,7 +676,10 @@ class SGPRModel:
         forces and stress of the rows, md_state and the frame record include the bias; the covloss gate does not see it.
           cvs: the components of the collective variable in the order they are concatenated, ("distance", i, j) = |x_j - x_i|
         and ("posvar", index, select) = x_index - (1/n) sum of the other atoms of species `select` (None: all atoms; n counts
-        the index atom where it is among them) — at most 4 components and 6 dimensions, raw coordinates, no minimum image.
+        the index atom where it is among them) — raw coordinates, no minimum image —, and ("qlvar", index, j, cutoff, l) = the
+        Steinhardt bond-order parameters Q_l, one dimension per entry of l (0 ... 12), of atom `index` over its neighbours of
+        species j with r < cutoff <= the model's cutoff, from the step's own neighbour list (sgpr_md_meta_ql; kind 2 of
+        md_meta.inc; workloads.ql_dim) — at most 4 components and 6 dimensions.
         sigma: a scalar or [D].  hills: [H, D] CV values (or (cv [H, D], V [H])) that stand from the start — a restart, or
         md_meta_hills() of this run when it needs more room; capacity: rows of hills (default: those given + 4096) — md_run
         refuses a call that would pass it before it enqueues anything, md_meta again with the rows of md_meta_hills(count=
@@ -696,8 +699,17 @@ class SGPRModel:
             raise ValueError(f"md_meta: merge is a chunk length >= 1 or None, not {merge}")
         from .ase_shim import kB
         spec, D = [], 0
-        for c in cvs:
+        for q, c in enumerate(cvs):
             kind = self.META_KINDS[c[0]]
+            if kind == 2:
+                # (the parameters of a qlvar are staged for the attach below)
+                if c[1] is None:
+                    raise ValueError("md_meta: a qlvar names its atom (Meta.resolve(numbers) fixes a Qlvar(index=None))")
+                ls = i32(np.asarray([int(l) for l in c[4]], np.int32))
+                check(lib.sgpr_md_meta_ql(self._h, q, float(c[3]), len(ls), ptr(ls)))
+                spec.append((2, int(c[1]), int(c[2])))
+                D += len(ls)
+                continue
             spec.append((kind, int(c[1]), int(c[2]) if kind == 0 else (-1 if c[2] is None else int(c[2]))))
             D += 1 if kind == 0 else 3
         sg = f64(np.broadcast_to(np.asarray(sigma, float).reshape(-1), (D,)) if np.size(sigma) == 1 else np.asarray(sigma, float).reshape(-1))

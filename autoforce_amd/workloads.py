@@ -216,8 +216,131 @@ def _block_order_sum(p256):
 META_TRIP = 1024   # hills per trip of md_meta_kernel's strided sum (four partial sums per thread)
 
 
+META_QL_MAXT = 256   # selected neighbours of all qlvar components together (md_meta.inc: one thread each)
+META_QL_MAXL = 12
+
+
 def meta_cv_dim(cvs):
-    return sum(1 if c[0] == "distance" else 3 for c in cvs)
+    return sum(1 if c[0] == "distance" else len(c[4]) if c[0] == "qlvar" else 3 for c in cvs)
+
+
+def ql_environment(numbers, x, cell, pbc, index, zj, cutoff, order=None, nl=None):
+    """The environment of a qlvar in the order of the device's neighbour list: the neighbours t of atom `index` that have species zj
+    and r_t < cutoff, r_t = (x_j - x_index) + ((s0 a + s1 b) + s2 c) with the image triple s of the entry — sorted by the position
+    of j in the library's species-sorted atom order (`order`: sorted -> caller; None: caller order), then by the image triple,
+    as the forward kernel sorts an atom's list (descriptor.hip: key = neighbour | image).  nl: a neighbour list with
+    get_neighbors(i) -> (indices, offsets) (the reference's interface; entries beyond cutoff are dropped); None: every image
+    inside the cutoff along the periodic directions, by enumeration.  Returns (j [T], shifts [T, 3], r [T, 3], |r| [T])."""
+    numbers = np.asarray(numbers)
+    x = np.asarray(x, float)
+    N = len(numbers)
+    h = np.asarray(cell, float).reshape(3, 3)
+    rank = np.arange(N)
+    if order is not None:
+        rank = np.empty(N, int)
+        rank[np.asarray(order)] = np.arange(N)
+    cand = []
+    if nl is not None:
+        jj, off = nl.get_neighbors(index)
+        cand = [(int(j), int(o[0]), int(o[1]), int(o[2])) for j, o in zip(np.asarray(jj), np.asarray(off).reshape(-1, 3))]
+    else:
+        per = np.zeros(3, bool) if pbc is None else np.broadcast_to(np.asarray(pbc, bool), (3,))
+        inv = np.linalg.inv(h) if per.any() else np.zeros((3, 3))
+        reach = [cutoff * float(np.linalg.norm(inv[:, k])) for k in range(3)]   # cutoff over the height along axis k
+        # (atom j under image s can be inside the cutoff only where |df_k + s_k| <= reach_k along every periodic axis)
+        js = np.nonzero(numbers == zj)[0]
+        df = (x[js] - x[index]) @ inv
+        lo = np.where(per, np.ceil(-np.asarray(reach) - df - 1e-9), 0.0).astype(int)
+        hi = np.where(per, np.floor(np.asarray(reach) - df + 1e-9), 0.0).astype(int)
+        if len(js):
+            for s0 in range(lo[:, 0].min(), hi[:, 0].max() + 1):
+                for s1 in range(lo[:, 1].min(), hi[:, 1].max() + 1):
+                    for s2 in range(lo[:, 2].min(), hi[:, 2].max() + 1):
+                        s = np.array([s0, s1, s2])
+                        cand += [(int(j), s0, s1, s2) for j in js[((lo <= s) & (s <= hi)).all(axis=1)]]
+    ent = []
+    for j, s0, s1, s2 in cand:
+        if numbers[j] != zj or (j == index and s0 == 0 and s1 == 0 and s2 == 0):
+            continue
+        r = (x[j] - x[index]) + ((float(s0) * h[0] + float(s1) * h[1]) + float(s2) * h[2])
+        ln = float(np.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]))
+        if ln < cutoff:
+            ent.append((int(rank[j]), s0, s1, s2, j, r, ln))
+    ent.sort(key=lambda e: e[:4])
+    T = len(ent)
+    return (np.array([e[4] for e in ent], int), np.array([e[1:4] for e in ent], int).reshape(T, 3),
+            np.array([e[5] for e in ent], float).reshape(T, 3), np.array([e[6] for e in ent], float))
+
+
+QL_TINY_ANGLE = 1e-2   # the reference's split_and_rotate_tiny_if_too_close_to_zaxis (descriptor/ylm.py:10-23)
+
+
+def ql_rows(r, ln, cutoff):
+    """The rows of a qlvar: (u, w, w', rhat, vlen, eps) — weights w = (1 - r / cutoff)^2 and their derivatives
+    -2 (1 - r / cutoff) / cutoff from the lengths as they are, rhat = r / |r|, and the directions u = v / |v| the harmonics see:
+    the reference's Ylm shears the WHOLE environment, v = (x, y - eps z, eps y + z) with eps = 1e-2, when any selected neighbour
+    lies inside the cone |x|, |y| < eps |z| around the z axis (its Q_l then differs from the unsheared one by up to a few 1e-5: x
+    keeps its scale, y and z gain sqrt(1 + eps^2)); eps = 0 otherwise, and then v is r, bit for bit."""
+    tol = QL_TINY_ANGLE * np.abs(r[:, 2])
+    eps = QL_TINY_ANGLE if bool(((np.abs(r[:, 0]) < tol) & (np.abs(r[:, 1]) < tol)).any()) else 0.0
+    v = np.stack([r[:, 0], r[:, 1] - eps * r[:, 2], eps * r[:, 1] + r[:, 2]], axis=1)
+    vlen = np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+    a = 1.0 - ln / cutoff
+    return v / vlen[:, None], a * a, -((2.0 * a) / cutoff), r / ln[:, None], vlen, eps
+
+
+def ql_dim(l, u, wt, wp, rhat, vlen, eps, base=0):
+    """Q_l of one environment and dQ_l / dr_t [T, 3] in the operations and the order of md_meta.inc's meta_ql_dim (the definition):
+    Q_l^2 = S / W^2, S = sum_t w_t A_t, A_t = sum_t' w_t' P_l(c), B_t = sum_t' w_t' P_l'(c) (u_t' - c u_t), c = u_t . u_t' — the
+    addition theorem, P_l and P_l' by the three-term recurrence —,
+        dQ_l^2 / dr_t = 2 (w'_t rhat_t A_t + w_t B_t / r_t) / W^2 - 2 Q_l^2 w'_t rhat_t / W,   dQ_l / dr_t = dQ_l^2 / dr_t / (2 Q_l)
+    (u, rhat, vlen, eps of ql_rows: with the reference's shear, B_t / |v_t| is the derivative by v_t and goes through the shear).
+    The pair sums of a row are formed by K = min(64, 256 / T rounded up to a power of two) lanes — lane k adds t' = k, k + K, ...
+    one after the other, the K partial sums meet in a butterfly (^ 1, ^ 2, ...) —, S and W over the workgroup in fin_wave_sum's
+    tree with row t in thread base + t.  An empty environment, or Q_l^2 <= 0: Q_l = 0 and no gradient (the reference: NaN)."""
+    T = len(vlen)
+    if T == 0:
+        return 0.0, np.zeros((0, 3))
+    Tp = 1
+    while Tp < T:
+        Tp <<= 1
+    K = min(64, 256 // Tp)
+    c = (u[:, None, 0] * u[None, :, 0] + u[:, None, 1] * u[None, :, 1]) + u[:, None, 2] * u[None, :, 2]
+    p0, p1, e1 = np.ones_like(c), c.copy(), np.ones_like(c)
+    if l == 0:
+        p1, e1 = np.ones_like(c), np.zeros_like(c)
+    for n in range(2, l + 1):
+        pn = ((float(2 * n - 1) * c) * p1 - float(n - 1) * p0) / float(n)
+        en = float(n) * p1 + c * e1
+        p0, p1, e1 = p1, pn, en
+    we = wt[None, :] * e1
+    nit = -(-T // K)
+    terms = np.zeros((T, nit * K, 4))
+    terms[:, :T, 0] = wt[None, :] * p1
+    for k in range(3):
+        terms[:, :T, 1 + k] = we * (u[None, :, k] - c * u[:, None, k])
+    acc = np.zeros((T, K, 4))
+    for it in range(nit):
+        acc = acc + terms[:, it * K:(it + 1) * K]
+    lanes, m = np.arange(K), 1
+    while m < K:
+        acc = acc + acc[:, lanes ^ m]
+        m <<= 1
+    A, B = acc[:, 0, 0], acc[:, 0, 1:]
+    v = np.zeros((256, 2))
+    v[base:base + T, 0] = wt * A
+    v[base:base + T, 1] = wt
+    S, W = _block_order_sum(v[:, 0]), _block_order_sum(v[:, 1])
+    W2 = W * W
+    Q2 = S / W2
+    if not Q2 > 0.0:
+        return 0.0, np.zeros((T, 3))
+    Q = float(np.sqrt(Q2))
+    wu = wp[:, None] * rhat
+    ang = (wt[:, None] * B) / vlen[:, None]   # d / dv; d / dr is its product with the shear from the right
+    ang = np.stack([ang[:, 0], ang[:, 1] + eps * ang[:, 2], ang[:, 2] - eps * ang[:, 1]], axis=1)
+    t1 = wu * A[:, None] + ang
+    return Q, ((2.0 * t1) / W2 - ((2.0 * Q2) * wu) / W) / (2.0 * Q)
 
 
 def meta_table(hills, sigma, merge):
@@ -322,13 +445,22 @@ def meta_density(c, sigma, w, hills, tem=None, merge=None):
     return float(V), g, float(kde)
 
 
-def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=None, merge=None):
+def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=None, merge=None, pbc=None, rc=None, nl=None):
     """The bias potential of metadynamics at one configuration, in the operations of the device loop's md_meta_kernel
     (md_meta.inc; SGPRModel.md_meta) — the reference's calculator/meta.py (Meta.energy over analysis/kde.py's Gaussian_kde)
     restated for the built-in collective variables.  This function is the definition:
       cvs: components concatenated like the reference's Catvar, ("distance", i, j) = |x_j - x_i| and ("posvar", index, select)
     = x_index - (1/n) sum_{k in sel, k != index} x_k with sel all atoms (select None) or the atoms of species `select`, n = |sel|
     (the index atom counts in n where it is in sel: the reference's Posvar) — raw coordinates, no minimum image;
+    ("qlvar", index, j, cutoff, (l, ...)) = the Steinhardt bond-order parameters Q_l of atom `index` over its neighbours of
+    species j with r < cutoff (the reference's Qlvar over descriptor/ql.py), one dimension per l, 0 <= l <= 12 — ql_environment
+    has the environment and its order, ql_dim the sums; it needs pbc and rc, the model's cutoff: the device reads the model's
+    own list, which ends at rc where the weight (1 - r / cutoff)^2 is not zero, so cutoff <= rc (ValueError otherwise).  Unlike
+    the reference, an empty environment gives Q_l = 0 with zero gradient (there: NaN), and so does Q_l = 0 (there: NaN, zeroed
+    by nan_to_num).  Atom j_t takes -G_t = -sum_d dV/dQ_d dQ_d/dr_t once per image it stands under, the index atom the sum over
+    the rows of the other atoms (its own images cancel), and the virial is sum_t r_t (x) G_t over the images — not the
+    raw-coordinate -sum x (x) F of the other kinds, which an atom that stands under several images makes wrong;  nl: a
+    neighbour list for the qlvars (the reference's interface) in place of the enumeration;
       a hill deposited at c (a row of `hills` [H, D]) is centred at (floor(c / sigma) + 0.5) sigma and carries the key
     floor(c / (5 sigma)) — 5 sigma a product, the divisions IEEE —; kde(x) = sum exp(-|(x - centre) / sigma|^2 / 2) / sqrt(2 pi)^D
     over the hills whose key differs from floor(x / (5 sigma)) by at most 1 in every dimension; sigma a scalar or [D];
@@ -353,6 +485,7 @@ def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=
     c = np.zeros(D)
     parts = []   # per component: (kind, d0, ...) what the forces need
     d0 = 0
+    qbase = 0    # rows of the qlvars that stand
     for comp in cvs:
         if comp[0] == "distance":
             i, j = int(comp[1]), int(comp[2])
@@ -379,13 +512,49 @@ def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=
             c[d0:d0 + 3] = x[idx] - mean_sum / n
             parts.append(("posvar", d0, idx, a, n))
             d0 += 3
+        elif comp[0] == "qlvar":
+            idx, zj, cut, ls = int(comp[1]), int(comp[2]), float(comp[3]), [int(l) for l in comp[4]]
+            if pbc is None or rc is None:
+                raise ValueError("meta_bias: a qlvar needs pbc= and rc=, the model's cutoff")
+            if not 0.0 < cut <= float(rc):
+                raise ValueError(f"meta_bias: qlvar cutoff {cut}; the model's list ends at rc = {rc}, where the weight is not zero: 0 < cutoff <= rc")
+            if not ls or any(l < 0 or l > META_QL_MAXL for l in ls):
+                raise ValueError(f"meta_bias: qlvar l = {ls}; one or more of 0 ... {META_QL_MAXL}")
+            jn, sh, r, ln = ql_environment(numbers, x, cell, pbc, idx, zj, cut, order=order, nl=nl)
+            keep = min(len(ln), META_QL_MAXT - qbase)
+            jn, sh, r, ln = jn[:keep], sh[:keep], r[:keep], ln[:keep]
+            u, wt, wp, rhat, vlen, eps = ql_rows(r, ln, cut)
+            dq = []
+            for k, l in enumerate(ls):
+                c[d0 + k], dql = ql_dim(l, u, wt, wp, rhat, vlen, eps, qbase)
+                dq.append(dql)
+            parts.append(("qlvar", d0, idx, jn, r, dq, qbase))
+            qbase += keep
+            d0 += len(ls)
         else:
-            raise ValueError(f"meta_bias: a component is ('distance', i, j) or ('posvar', index, select), not {comp!r}")
+            raise ValueError(f"meta_bias: a component is ('distance', i, j), ('posvar', index, select) or ('qlvar', index, j, cutoff, l), not {comp!r}")
     V, g, kde = meta_density(c, sg, w, hills, tem=tem, merge=merge)
     F = np.zeros((N, 3))
     vir = np.zeros(9)
+    qvir = np.zeros(9)
     for part in parts:
-        if part[0] == "distance":
+        if part[0] == "qlvar":
+            _, q, idx, jn, r, dq, base = part
+            T = len(jn)
+            G = np.zeros((T, 3))
+            for k, dql in enumerate(dq):
+                G = G + g[q + k] * dql
+            other = jn != idx
+            v = np.zeros((256, 3))
+            v[base:base + T] = np.where(other[:, None], G, 0.0)
+            F[idx] = F[idx] + np.array([_block_order_sum(v[:, k]) for k in range(3)])
+            for t in np.nonzero(other)[0]:
+                F[jn[t]] = F[jn[t]] - G[t]
+            for a in range(3):
+                v = np.zeros((256, 3))
+                v[base:base + T] = r[:, a:a + 1] * G
+                qvir[3 * a:3 * a + 3] = qvir[3 * a:3 * a + 3] + np.array([_block_order_sum(v[:, b]) for b in range(3)])
+        elif part[0] == "distance":
             _, q, i, j, d, r = part
             fi = (g[q] * d) / r
             F[i] = F[i] + fi
@@ -396,6 +565,8 @@ def meta_bias(cvs, sigma, w, numbers, positions, cell, hills, tem=None, species=
             F[idx] = F[idx] - g[q:q + 3]
             F[a] = F[a] + g[q:q + 3] / n
             vir = vir + np.outer(c[q:q + 3], g[q:q + 3]).reshape(9)
+    if qbase or any(part[0] == "qlvar" for part in parts):
+        vir = vir + qvir
     cl = np.asarray(cell, float).reshape(3, 3)
     vol = abs(float(np.linalg.det(cl)))
     if not vol > 0.0:
@@ -457,7 +628,7 @@ def langevin_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=
         F = at.get_forces(apply_constraint=False)
         E = at.get_potential_energy()
         if meta is not None:   # (the bias of this configuration, then its own hill)
-            V, Fb, _ = meta.bias(p, cell, numbers)
+            V, Fb, _ = meta.bias(p, cell, numbers, pbc=pbc)
             F, E = F + Fb, E + V
             meta.update()
         if flt is not None:   # (once per configuration)
@@ -558,7 +729,7 @@ def nose_hoover_nvt(calc, numbers, pos, cell, pbc, steps, temperature=600.0, dt_
         at.calc = calc
         F, E = at.get_forces(apply_constraint=False), at.get_potential_energy()
         if meta is not None:   # (the bias of this configuration, then its own hill)
-            V, Fb, _ = meta.bias(p, cell, numbers)
+            V, Fb, _ = meta.bias(p, cell, numbers, pbc=pbc)
             F, E = F + Fb, E + V
             meta.update()
         return F, E

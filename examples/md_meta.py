@@ -5,7 +5,7 @@ is handed to ActiveCalculator(meta=...) and a hill is deposited per configuratio
     python examples/md_meta.py --side 6 6 6 --steps 400 --sigma 0.1 --w 0.01 [--tem 2000] [--thermostat nose-hoover]
 
 * collective variables: the position of atom 0 relative to the mean of the other atoms of its species (Posvar) and its distance
-  from atom 1 (Distance), concatenated (Catvar) — built in, so the bias runs inside the device loop (ActiveCalculator.run_md ->
+  from atom 1 (Distance), concatenated (Catvar) — built in, as is the Steinhardt Qlvar (a commented variant below), so the bias runs inside the device loop (ActiveCalculator.run_md ->
   SGPRModel.md_meta: one small launch per step, no crossing into the host).  A colvar of your own, a function
   (numbers, xyz, cell, pbc, nl) -> 1-d torch tensor as in the reference, works too: the run then takes the host loop around
   calculate(), where the bias is added to energy, forces and stress;
@@ -49,6 +49,11 @@ def main():
     N = len(numbers)
     meta = Meta(Catvar(Posvar(0, select=int(numbers[0])), Distance(0, 1)), sigma=args.sigma, w=args.w, tem=args.tem,
                 hist=f"{args.out}/meta.hist", merge=1024)
+    # The Steinhardt Q6 of atom 0 over its neighbours of the other species inside 4 A — the reference's Qlvar, the colvar of melting
+    # and nucleation — runs inside the device loop too (cutoff <= the model's cutoff; sigma of order 0.01: Q6 lives in [0, 1]):
+    # from autoforce_amd.meta import Qlvar
+    # meta = Meta(Qlvar(int(numbers[0]), int(numbers[1]), index=0, cutoff=4.0, l=[6]), sigma=0.01, w=args.w, tem=args.tem,
+    #             hist=f"{args.out}/meta.hist", merge=1024)
     teacher = PairTeacher(species)
     calc = ActiveCalculator(calculator=teacher, kernel_kw=dict(species=species), meta=meta, logfile=f"{args.out}/active.log",   # <- meta
                             tape=None, pckl=None, ediff=0.086, fdiff=0.129)

@@ -572,8 +572,8 @@ int sgpr_md_filter_state(sgpr_model *h, double *f, double *s);
  * and virial of everything the run reports and integrates include the bias; the covloss gate does not see it.  Hills are rows
  * indexed by configuration: what a halt discards or a cut repeats overwrites its own row.
  *
- * sgpr_md_meta        after sgpr_md_begin, between any two sgpr_md_run calls.  cvs[ncomp][3] = kind (0 distance, 1 posvar), atom
- *                     (i | index), second (j | select: an atomic number, -1: all atoms), caller atom order; sigma[D]; w; kT > 0:
+ * sgpr_md_meta        after sgpr_md_begin, between any two sgpr_md_run calls.  cvs[ncomp][3] = kind (0 distance, 1 posvar, 2 qlvar), atom
+ *                     (i | index), second (j | select: an atomic number, -1: all atoms | Zj), caller atom order; sigma[D]; w; kT > 0:
  *                     well-tempered, 0: plain; pace >= 1; capacity: rows of hills; nhills rows hills_cv[nhills][D] and
  *                     hills_V[nhills] (NULL: zeros) stand from the start, for the deposits of the configurations below the
  *                     current one (a restart; the rows of sgpr_md_meta_hills when a run needs more room).  ncomp = 0 detaches.
@@ -603,7 +603,17 @@ int sgpr_md_filter_state(sgpr_model *h, double *f, double *s);
  * sgpr_md_meta_table  the table as the current configuration sees it (Gaussian_kde.histogram()): *n_entries entries in the order
  *                     of the first row that occupied each, centres[*n_entries][D], counts[*n_entries], from the first
  *                     *rows_merged rows.  Any of them NULL: ask for *n_entries first (at most the capacity).
+ * sgpr_md_meta_ql     stages the parameters of component `comp` of the NEXT sgpr_md_meta, whose cvs triple (2, index, Zj) consumes
+ *                     them (taken and cleared by that call, whether it succeeds or not): kind 2, the Steinhardt bond-order
+ *                     parameters Q_l of atom `index` over its neighbours t of species Zj with r_t < cutoff in the step's own
+ *                     neighbour list (r_t = x_j - x_index + shift.cell), weights w_t = (1 - r_t / cutoff)^2, W = sum w_t,
+ *                     Q_l^2 = sum_{t,t'} w_t w_t' P_l(r^_t . r^_t') / W^2: one dimension per l[k], 0 <= l <= 12, 1 <= n_l <= 6, in
+ *                     the order given.  0 < cutoff <= rc (the list ends at rc, where the weight is not zero).  An empty environment
+ *                     gives Q_l = 0 and no force; so does Q_l = 0.  The virial is sum_t r_t (x) dV/dr_t over the images.
+ *                     SGPR_E_INVALID from sgpr_md_meta: a kind-2 component without staged parameters, a species no atom has;
+ *                     SGPR_E_UNSUPPORTED, there or from sgpr_md_run: (kind-2 components) x (list entries per atom) > 256.
  * sgpr_md_end releases the hills. */
+int sgpr_md_meta_ql(sgpr_model *h, int comp, double cutoff, int n_l, const int32_t *l);
 int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const double *sigma, double w, double kT, int pace, int64_t capacity,
                  int64_t nhills, const double *hills_cv, const double *hills_V);
 int sgpr_md_meta_info(sgpr_model *h, int *D, int64_t *below, int64_t *held, int64_t *capacity);
