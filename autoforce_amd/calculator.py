@@ -600,7 +600,10 @@ class ActiveCalculator(Calculator):
         new hill rows are appended to meta.hist and mirrored into the Meta — calculate() at a halt adds the same bias — and
         `meta: V` goes on the log lines — with pace > 1 on the lines of the depositing configurations only: the device keeps V
         per hill row, and a run goes on from a Meta only at a multiple of its pace (ValueError otherwise).  With a barostat, a committee or several ranks, and for any other meta, the host loops
-        around calculate(), which adds a Meta's bias itself; there meta.update() runs once per configuration."""
+        around calculate(), which adds a Meta's bias itself; there meta.update() runs once per configuration.
+        A committee with members (BCMActiveCalculator) and a barostat: the device loop integrates and gates the committee in the
+        moving cell (SGPRModel.md_committee on a run begun with pfactor=); such a run records no frames, so its batches end at the
+        multiples of sync_every, where atoms.cell is set with atoms.positions."""
         from .ase_shim import kB
         from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
@@ -643,12 +646,13 @@ class ActiveCalculator(Calculator):
             # sees — and logs — the velocities the loops start from)
             vel = np.where(fx, 0.0, vel)
             atoms.set_velocities(vel)
-        # (a committee with members — BCMActiveCalculator — runs on the device at constant cell and without a mask; under a
-        # barostat or constraints the host loops around calculate(), which answers with the committee, take it)
+        # (a committee with members — BCMActiveCalculator — runs on the device without a mask, at constant cell or under a
+        # barostat (SGPRModel.md_begin(pfactor=) + md_committee: the moving cell integrates the committee's stress); with
+        # constraints the host loops around calculate(), which answers with the committee, take it)
         committee = bool(getattr(self, "model_dict", None))
 
         def on_device():
-            return (self.md_on_device_ok() and not (committee and (npt or fx is not None))
+            return (self.md_on_device_ok() and not (committee and fx is not None)
                     and not (flt is not None and (committee or self._dist()[1] > 1))
                     and not (self.meta is not None and (npt or committee or self._dist()[1] > 1)))
         first_on_host = self._needs_seed() or not on_device()

@@ -208,7 +208,9 @@ class BCMActiveCalculator(ActiveCalculator):
         neither the combination nor the member-wise minimum), in model_dict order."""
         keys = self._ready_members()
         if keys:
-            eng.md_committee([self.model_dict[k].engine for k in keys])
+            # (a run begun with a barostat takes the committee only when asked to: SGPRModel.md_committee(moving_cell=True))
+            npt = bool((getattr(eng, "_md", None) or {}).get("npt"))
+            eng.md_committee([self.model_dict[k].engine for k in keys], **({"moving_cell": True} if npt else {}))
         return tuple(keys)
 
     def _md_attached_done(self, eng, keys):

@@ -282,6 +282,7 @@ struct MdRun {
     struct Bcm {
         std::vector<struct sgpr_model *> members;
         std::vector<double> info;  // weights | largest covlosses of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
+        bool cell = false;         // option "md_committee_cell" of THIS run: a committee and a barostat may meet on it (off: each refuses the other)
     } bcm;
     // the nudged elastic band (sgpr_md_neb, md_neb.inc): K interior images evaluated by this one handle per evaluation of the band
     struct Neb {
@@ -1167,6 +1168,33 @@ __device__ __forceinline__ double md_nh_advance(const FinNext &x, bool held, dou
     return held ? 0.0 : vnow;
 }
 
+// Row vector (a component on each of lanes 0..2 of a quad) times the 3 x 3 matrix whose column `lane` is c:
+// (v_0 c_0 + v_1 c_1) + v_2 c_2
+__device__ __forceinline__ double md_row_mul(double v, const double (&c)[3])
+{
+#pragma clang fp contract(off)
+    return (fin_quad_lane<0>(v) * c[0] + fin_quad_lane<1>(v) * c[1]) + fin_quad_lane<2>(v) * c[2];
+}
+
+// One moving-cell step of a coordinate (sgpr_md_barostat; md_npt.inc has the scheme), every lane of the quad taking part in the
+// row products: workloads.npt_moving_cell's operations in its order, no contraction, true divisions.  qc, qp: q_n, q_(n-1);
+// the columns of h_n^-1, B_n - 1, (B_n + 1)^-1, h_n and h_(n+1) as md_npt_kernel left them.  qn: q_(n+1); xn: x_(n+1) in the
+// next cell.  Returns v_n (the first time v_0 is the caller's own, as at constant cell).
+__device__ __forceinline__ double md_npt_advance(const FinNext &x, double F, double ms, double qc, double qp, double v0, const double (&c_hinv)[3],
+                                                 const double (&c_bm1)[3], const double (&c_bp1)[3], const double (&c_h)[3], const double (&c_hn)[3],
+                                                 double &qn, double &xn)
+{
+#pragma clang fp contract(off)
+    const double dt = 2.0 * x.hdt;
+    const double a = __ddiv_rn((dt * dt) * F, ms);
+    const double num = ((2.0 * qc) + md_row_mul(qp, c_bm1)) + md_row_mul(a, c_hinv);
+    qn = md_row_mul(num, c_bp1);
+    const double vcen = __ddiv_rn(md_row_mul(qn - qp, c_h), 2.0 * dt);
+    const double vnow = x.nh_first ? v0 : vcen;
+    xn = md_row_mul(qn + 0.5, c_hn);
+    return vnow;
+}
+
 // One BAOAB step of a coordinate (Langevin; without friction and deviates: velocity Verlet), exactly the operations (and their
 // order) of workloads.langevin_nvt: no contraction into fused multiply-adds, a true division.  F: the force of this step, vc:
 // the velocity BEFORE this step's closing half kick, nz: the uploaded deviate (drawn here for (caller atom c, component comp)
@@ -1442,15 +1470,9 @@ __global__ __launch_bounds__(256) void finalize_next_kernel(FinArgs f)
         Fi = Fv - fmin(fmax(an, -1.0), 1.0);
     }
     if (CELL) {
-        // workloads.npt_moving_cell's operations in its order (md_npt.inc has the scheme): no contraction, true divisions
-#pragma clang fp contract(off)
-        const double dt = 2.0 * x.hdt;
-        const double a = __ddiv_rn((dt * dt) * Fi, ms);
-        const double num = ((2.0 * qc) + row_mul(qp, c_bm1)) + row_mul(a, c_hinv);
-        const double qn = row_mul(num, c_bp1);
-        const double vcen = __ddiv_rn(row_mul(qn - qp, c_h), 2.0 * dt);
-        const double vnow = x.nh_first ? vc : vcen;   // (the first time v_0 is the caller's own, as at constant cell)
-        xn = row_mul(qn + 0.5, c_hn);
+        // workloads.npt_moving_cell's operations in its order (md_npt.inc has the scheme): md_npt_advance, shared with the committee's move
+        double qn;
+        const double vnow = md_npt_advance(x, Fi, ms, qc, qp, vc, c_hinv, c_bm1, c_bp1, c_h, c_hn, qn, xn);
         if (lane < 3) {
             ke = ms * (vnow * vnow);
             kp = ke;
@@ -3349,6 +3371,15 @@ extern "C" int sgpr_set_option(sgpr_model *h, const char *name, int value)
         return SGPR_OK;
     }
     if (!strcmp(name, "ignore_unknown_species")) { h->ignore_unknown = value != 0; return SGPR_OK; }
+    if (!strcmp(name, "md_committee_cell")) {
+        // of the run begun by sgpr_md_begin, which switches it off again: sgpr_md_committee accepts a run with a barostat and
+        // sgpr_md_barostat a run with a committee (md_committee_run then integrates the committee in the moving cell); off, the
+        // default, each refuses the other as before
+        if (!h->md.active) return fail(SGPR_E_INVALID, "sgpr_set_option: md_committee_cell belongs to a run: call sgpr_md_begin first");
+        if (h->md.run.t != 0 || h->md.run.started) return fail(SGPR_E_INVALID, "sgpr_set_option: md_committee_cell: the run has started");
+        h->md.run.bcm.cell = value != 0;
+        return SGPR_OK;
+    }
     if (!strcmp(name, "lone_atom_weight")) {
         if (value < 1) return fail(SGPR_E_INVALID, "sgpr_set_option: lone_atom_weight >= 1");
         if (h->m > 0 && (double)value != h->lone_w) return fail(SGPR_E_INVALID, "sgpr_set_option: lone_atom_weight is set before the inducing set");

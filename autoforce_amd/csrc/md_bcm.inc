@@ -20,6 +20,10 @@
 //     order) and the caller-order copy the members read;
 //   * md_bcm_ke_kernel, ONE workgroup: the two kinetic sums of the evaluation in md_nh_kernel's fixed order (no lag: the row
 //     of an evaluation is complete behind its own launches); under Nose-Hoover md_nh_kernel follows as in the fused loop.
+// With a barostat (sgpr_md_barostat; md_npt.inc has the scheme) the K + 1 plain steps run in the cell h_n of the evaluation,
+// md_bcm_move_kernel<true> moves the atoms in scaled coordinates — md_npt_advance, the function finalize_next_kernel<3> calls; no
+// binning here: every handle bins through its own binning kernel in the next evaluation — and md_npt_kernel takes md_nh_kernel's
+// place, reading the combined virial md_bcm_kernel wrote into the run's ring slot: the barostat integrates the committee's stress.
 // No float atomics, no contraction in the combination: two runs give the same bits.
 #pragma once
 
@@ -115,6 +119,12 @@ __global__ __launch_bounds__(256) void md_bcm_kernel(int N, int K1, size_t plen,
 // BEFORE this evaluation is left untouched; at the halting evaluation itself, and where `stay` is set (the last evaluation of
 // a `final` call), the results are written and the kinetic terms of the evaluation with them — Nose-Hoover: its centred
 // velocity too, which IS the evaluation's velocity — but no position or velocity of the next configuration.
+//   CELL (its own instantiation: the constant-cell one stays the code it was): the moving cell.  q_n, q_(n-1) from the ring of
+// scaled coordinates and column l3 of h_n^-1, B - 1, (B + 1)^-1, h_n, h_(n+1) from the ring of NptSlots (wave-uniform addresses),
+// requested with everything else; the centred velocity v_n and the kinetic terms are written wherever the results are — md_state
+// and md_npt_kernel read them at a halting evaluation too —, q_(n+1), x_(n+1) in the cell h_(n+1) and its caller-order copy only
+// when the run moves on.
+template <bool CELL>
 __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t plen, const double *P, const double *w, double *packed, double *x_caller,
                                                           const int *perm, FinNext x, int stay)
 {
@@ -130,7 +140,19 @@ __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t 
     const double ms = x.mass[ia], sg = x.sig[ia];
     const double nz = x.noise ? x.noise[3 * (size_t)ia + l3] : 0.0;   // (uniform condition)
     double xpv = 0.0, zeta = 0.0;
-    if (x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (uniform condition)
+    if (!CELL && x.nh) { xpv = x.x_prev[3 * (size_t)ia + l3]; zeta = *x.nh_zeta; }   // (uniform condition)
+    // CELL: q_n, q_(n-1), and column l3 of h_n^-1, B - 1, (B + 1)^-1, h_n of this evaluation's slot and of h_(n+1) (uniform addresses)
+    double qc = 0.0, qp = 0.0, c_hinv[3], c_bm1[3], c_bp1[3], c_h[3], c_hn[3];
+    if (CELL) {
+        const NptSlot *nc = x.npt_cur, *nn = x.npt_next;
+        qc = x.q_cur[3 * (size_t)ia + l3];
+        qp = x.q_prev[3 * (size_t)ia + l3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            c_hinv[j] = nc->hinv[3 * j + l3]; c_bm1[j] = nc->bm1[3 * j + l3]; c_bp1[j] = nc->bp1inv[3 * j + l3];
+            c_h[j] = nc->h[3 * j + l3]; c_hn[j] = nn->h[3 * j + l3];
+        }
+    }
     double F = 0.0, bmin = 1e300;
 #pragma unroll
     for (int k = 0; k < BCM_MAX; k++)
@@ -144,7 +166,20 @@ __global__ __launch_bounds__(256) void md_bcm_move_kernel(int N, int K1, size_t 
     if (act && lane < 3) packed[3 * (size_t)c + lane] = F;
     if (act && lane == 3) packed[3 * (size_t)N + c] = bmin;
     double ke, kp, xn;
-    if (x.nh) {
+    if (CELL) {
+        // (every lane of the quad takes part in the row products; lane 3 holds lane 2's values and stores nothing)
+        double qn;
+        const double vnow = md_npt_advance(x, F, ms, qc, qp, vc, c_hinv, c_bm1, c_bp1, c_h, c_hn, qn, xn);
+        ke = ms * (vnow * vnow);
+        kp = ke;
+        if (act && lane < 3) {
+            x.v_now[3 * (size_t)i + lane] = vnow;
+            if (move) {
+                x.q_next[3 * (size_t)i + lane] = qn;
+                x.x_next[3 * (size_t)i + lane] = xn;
+            }
+        }
+    } else if (x.nh) {
         const double vnow = md_nh_advance(x, false, F, ms, xc, vc, xpv, zeta, xn);
         ke = ms * (vnow * vnow);
         kp = ke;

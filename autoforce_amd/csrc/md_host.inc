@@ -168,7 +168,10 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
 // triangular (ASE's own condition) and periodic in all three directions.  pfactor = ptime^2 x bulk modulus and the external
 // stress (six Voigt components; a pressure P is (-P, -P, -P, 0, 0, 0)) in the units of the run; mask: nine zeros / ones (which
 // cell components may move); frac_traceless: 1 = all of the strain rate (with the mask), 0 = its trace only (`iso`).
-// Single rank only: the sharded last kernel (peer.inc) integrates at constant cell.
+// Single rank only: the sharded last kernel (peer.inc) integrates at constant cell.  A run that has a committee
+// (sgpr_md_committee, attached before or after this call) is refused unless the run's option "md_committee_cell" is set
+// (sgpr_set_option after sgpr_md_begin): it then integrates the committee's forces and stress in the moving cell
+// (md_committee_run); a bias or held components beside the barostat stay refused.
 extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *externalstress, const double *mask, double frac_traceless)
 {
     if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
@@ -176,7 +179,9 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (!m.active || !m.run.nh.on || m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
     if (m.run.t != 0 || m.run.npt.started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.run.world);
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell");
+    if (!m.run.bcm.members.empty() && !m.run.bcm.cell)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a committee (sgpr_md_committee), which runs at constant cell unless the run's option "
+                    "md_committee_cell is set (sgpr_set_option)");
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
@@ -213,11 +218,15 @@ static double md_host_order_sum(const std::vector<double> &x)
     return p[0];
 }
 
+static int md_committee_forces0(sgpr_model *h, int spare_row, hipStream_t st, std::vector<double> &F);
+
 // Start of a moving-cell trajectory (NPT.initialize(), autoforce_amd/npt.py): one synchronised evaluation of configuration 0,
 // then q_0 = x_0 h^-1 - 1/2 and q_(-1) by the backward step that is corrected twice (with ASE's test on the mean kinetic
 // energy per atom between the two corrections) on the host, in the operations of workloads.npt_moving_cell — once per
 // trajectory.  eta_0 = zeta_0 = 0 and therefore h_(-1) = h_1 = h_0; eta_(-1), zeta_(-1) are md_npt_kernel's (n = 0).
-static int md_npt_start(sgpr_model *h, hipStream_t st)
+// A run with a committee (bcm_row >= 0: the spare row of the call's scalar ring, md_committee_run): the forces of the backward
+// step are the committee's — md_committee_forces0 —, as the host twin's calculator answers with them at configuration 0.
+static int md_npt_start(sgpr_model *h, hipStream_t st, int bcm_row = -1)
 {
 #pragma clang fp contract(off)
     MdState &m = h->md;
@@ -237,6 +246,8 @@ static int md_npt_start(sgpr_model *h, hipStream_t st)
     HIPCHK(hipMemcpy(x.data(), m.X.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(v.data(), m.V.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(F.data(), m.P.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));   // (packed forces: caller order)
+    if (bcm_row >= 0)
+        if (const int rb = md_committee_forces0(h, bcm_row, st, F)) return rb;
     if (m.run.filter.on) {   // the forces the integrator sees at configuration 0 (finalize_next_kernel<7>'s operations; slot 0 stays as it is)
         std::vector<double> a0((size_t)3 * N);
         HIPCHK(hipMemcpy(a0.data(), m.filter.f.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost));
@@ -763,7 +774,10 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
 // sgpr_md_thermostat; before the first sgpr_md_run — a detach (K = 0 or members = NULL: the run is the one without this call)
 // too: a run that has started keeps what it has.
 // The members are BORROWED: the caller keeps them alive until sgpr_md_end or a detach, and may use them between two
-// sgpr_md_run calls (every call binds them to the run's system again).  Constant cell, one rank, no mask, no frame record.
+// sgpr_md_run calls (every call binds them to the run's system again).  One rank, no mask, no filter, no bias, no frame record;
+// constant cell or — the run's option "md_committee_cell" set (sgpr_set_option; off, a committee and a barostat refuse each
+// other), with sgpr_md_barostat before or after this call — the moving cell: every member is then evaluated in the cell of the
+// configuration, and the barostat integrates the committee's stress.
 extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *members)
 {
     if (!h || K < 0) return fail(SGPR_E_INVALID, "sgpr_md_committee: bad arguments");
@@ -772,8 +786,10 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_committee: the run has started");
     if (K == 0 || !members) { m.run.bcm.members.clear(); m.run.bcm.info.clear(); return SGPR_OK; }
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a bias (sgpr_md_meta), which the committee's loop does not apply; the host loop around calculate() serves it");
-    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee integrates unfiltered forces");
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a filter (sgpr_md_filter); a committee, with or without a barostat, integrates unfiltered forces");
+    if (m.run.npt.on && !m.run.bcm.cell)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run has a barostat; a committee runs at constant cell unless the run's option "
+                    "md_committee_cell is set (sgpr_set_option)");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a nudged elastic band; a committee serves dynamics only");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
@@ -818,11 +834,55 @@ extern "C" int sgpr_md_committee_info(sgpr_model *h, double *w, double *covmax)
     return SGPR_OK;
 }
 
+// The committee's forces at configuration 0 of a moving-cell trajectory, for md_npt_start's backward step: every member's
+// synchronised evaluation in the cell h_0 (the live model's is in slot 0 of the run's packed ring already), the weights by
+// md_bcm_kernel — the device's log, as in every evaluation of the run; row `spare_row` of the call's scalar ring, marks and
+// committee record takes what else it writes —, then the combination on the host in md_bcm_move_kernel's operations: member
+// order, no contraction.  F: [N][3] caller order; in: the live model's forces, out: the committee's.
+static int md_committee_forces0(sgpr_model *h, int spare_row, hipStream_t st, std::vector<double> &F)
+{
+#pragma clang fp contract(off)
+    MdState &m = h->md;
+    const int N = m.run.N, K = (int)m.run.bcm.members.size(), K1 = K + 1;
+    const size_t plen = (size_t)sgpr_packed_len(N);
+    for (int k = 0; k < K; k++) {
+        sgpr_model *mk = m.run.bcm.members[k];
+        const int rc_ = run_checked(mk, m.bcm.x.p, m.slot(0)->h, m.bcm.P.p + plen * k, st);
+        if (rc_) return rc_;
+        mk->warm = true;
+    }
+    HIPCHK(hipMemcpyAsync(m.bcm.P.p + plen * K, m.P.p, sizeof(double) * plen, hipMemcpyDeviceToDevice, st));
+    double *info = m.bcm.info_d.p + (size_t)BCM_INFO * spare_row;
+    hipLaunchKernelGGL(md_bcm_kernel, dim3(1), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm.P.p, m.P.p, info, 1e300, m.halt.p, m.halt_host.dev,
+                       (int)h->step_count, m.scal_d.p + (size_t)SGPR_MD_SCAL * spare_row, m.mark.dev + spare_row);
+    std::vector<double> w(BCM_INFO), P((size_t)K1 * plen);
+    HIPCHK(hipMemcpyAsync(w.data(), info, sizeof(double) * BCM_INFO, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(P.data(), m.bcm.P.p, sizeof(double) * K1 * plen, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    // (the checked passes have sized every capacity, so no overflow word has halted anything; the halts are armed as md_prepare_call left them)
+    m.halt_host.p[0] = m.halt_host.p[1] = m.halt_host.p[2] = MD_HALT_NONE;
+    HIPCHK(hipMemcpyAsync(m.halt.p, m.halt_host.p, 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    for (size_t e = 0; e < (size_t)3 * N; e++) {
+        double acc = 0.0;
+        for (int k = 0; k < K1; k++) acc = acc + w[k] * P[(size_t)k * plen + e];
+        F[e] = acc;
+    }
+    return SGPR_OK;
+}
+
 // sgpr_md_run for a run with a committee, in the shape of md_relax_run: every evaluation is K + 1 plain steps on the live
 // handle's stream — each member on the caller-order copy of the positions through its own binning kernel and permutation, the
 // live handle on its sorted ring slot — with md_bcm_kernel, md_bcm_move_kernel and md_bcm_ke_kernel behind them (Nose-Hoover:
 // md_nh_kernel too).  The halts — covloss gate (1), capacity overflow of any member (2) — are decided by md_bcm_kernel on the
 // evaluation itself, before anything moves: what the host has enqueued behind a halt evaluates stale slots and changes nothing.
+//   With a barostat (sgpr_md_barostat): the K + 1 plain steps of evaluation n run in the cell h_n of the ring (as a relaxation's
+// plain steps run in a cell that changes every evaluation: each handle's binning kernel keeps or rebuilds its lists by its own
+// affine rule), md_bcm_move_kernel<true> integrates in scaled coordinates, and md_npt_kernel takes md_nh_kernel's place: it
+// reads the combined virial md_bcm_kernel left in the run's packed ring slot, so the barostat integrates the committee's stress.
+// md_npt_kernel runs at a halting evaluation too (it exits only behind one): of the ring slots n - 1, n, n + 1, n + 2 it reads
+// h, eta, zeta of n - 1 and n and h of n + 1, and writes eta, zeta and the matrices of n + 1 and h and the grid of n + 2 —
+// nothing it reads —, so the repeat of the halted configuration with the updated model overwrites all of it.
 static int md_committee_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars, int *evals_done,
                             int *halt_code)
 {
@@ -839,7 +899,8 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     }
     m.run.started = true;
     MdBinIdentity guard(h);
-    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
+    const bool cellrun = m.run.npt.on;   // (a barostat: the cell record, the ring of cells)
+    if (const int rp = md_prepare_call(h, nevals, st, cellrun)) return rp;
     if (m.bcm.info_d.alloc((size_t)BCM_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
     if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
     const int s0 = (int)(m.run.t % RG);
@@ -851,8 +912,13 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     // Whatever ran on a handle since the last call — calculate() on a halt evaluates the same members, a model update binds the
     // live one to stored frames — nothing is assumed about bound frame, lists or bin populations: bound again, a checked pass
     // where the capacities are not sized for this system, lists rebuilt by the first evaluation, bin populations cleared
-    if (!h->warm) {
-        const int rc_ = run_checked(h, m.X.p + N3 * s0, m.cell.p, m.bcm.P.p + plen * K, st);
+    // (moving cell: the cell of configuration n is in the ring once the trajectory has started — md_npt_start, below, whose own
+    // checked passes size the capacities of every handle; the cell of sgpr_md_begin until then)
+    if (cellrun) { m.run.npt.par.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.run.npt.par.rc_phys = h->rc; }   // (as sgpr_md_run sets them)
+    const bool start = cellrun && !m.run.npt.started;
+    auto cell_of = [&](long long n) -> const double * { return (cellrun && m.run.npt.started) ? m.slot(n)->h : m.cell.p; };
+    if (!h->warm && !start) {
+        const int rc_ = run_checked(h, m.X.p + N3 * s0, cell_of(m.run.t), m.bcm.P.p + plen * K, st);
         if (rc_) return rc_;
         h->warm = true;
     }
@@ -860,13 +926,20 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         sgpr_model *mk = m.run.bcm.members[k];
         if (!md_same_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1))
             if (const int rb = sgpr_bind_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1)) return rb;
-        if (!mk->warm) {
-            const int rc_ = run_checked(mk, m.bcm.x.p, m.cell.p, m.bcm.P.p + plen * k, st);
+        if (!mk->warm && !start) {
+            const int rc_ = run_checked(mk, m.bcm.x.p, cell_of(m.run.t), m.bcm.P.p + plen * k, st);
             if (rc_) return rc_;
             mk->warm = true;
         }
-        if (const int rl = md_reset_lists(mk, st)) return rl;
     }
+    if (start) {
+        if (const int rs = md_npt_start(h, st, nevals)) return rs;
+        // every slot of the ring of cells a valid cell from the start, as the ring of positions is (sgpr_md_committee): what the
+        // host has enqueued behind a halt at the first evaluations bins stale slots in them
+        for (int r = 2; r < 4; r++) HIPCHK(hipMemcpy(m.slot(r)->h, m.cell.p, 9 * sizeof(double), hipMemcpyDeviceToDevice));
+    }
+    for (int k = 0; k < K; k++)
+        if (const int rl = md_reset_lists(m.run.bcm.members[k], st)) return rl;
     md_call_start(h, c);
     if (const int rl = md_reset_lists(h, st)) return rl;
     const unsigned step0 = c.step0; const double gate = c.gate;
@@ -875,11 +948,11 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         const int sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
         for (int k = 0; k < K; k++) {
             sgpr_model *mk = m.run.bcm.members[k];
-            const int re = enqueue_step(mk, m.bcm.x.p, m.cell.p, m.bcm.P.p + plen * k, st, nullptr);
+            const int re = enqueue_step(mk, m.bcm.x.p, cell_of(m.run.t + j), m.bcm.P.p + plen * k, st, nullptr);
             if (re) return re;
             mk->lists_valid = true;
         }
-        const int re = enqueue_step(h, m.X.p + N3 * sl, m.cell.p, m.bcm.P.p + plen * K, st, nullptr);
+        const int re = enqueue_step(h, m.X.p + N3 * sl, cell_of(m.run.t + j), m.bcm.P.p + plen * K, st, nullptr);
         if (re) return re;
         h->lists_valid = true;
         const int step = (int)(step0 + j);
@@ -890,11 +963,20 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         x.step = step;   // (the fused loop: enqueue_step sets it)
         const bool stay = final_eval && j == nevals - 1;
-        hipLaunchKernelGGL(md_bcm_move_kernel, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen, (const double *)m.bcm.P.p, (const double *)info,
-                           packed, m.bcm.x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
+        if (cellrun) {   // (the ring slots of this evaluation and the next, the scaled coordinates: as sgpr_md_run fills them)
+            x.npt_cur = m.slot(m.run.t + j); x.npt_next = m.slot(m.run.t + j + 1);
+            x.q_cur = m.npt.Q.p + N3 * sl; x.q_prev = m.npt.Q.p + N3 * sp; x.q_next = m.npt.Q.p + N3 * sn;
+        }
+        hipLaunchKernelGGL(cellrun ? md_bcm_move_kernel<true> : md_bcm_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen,
+                           (const double *)m.bcm.P.p, (const double *)info, packed, m.bcm.x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
         hipLaunchKernelGGL(md_bcm_ke_kernel, dim3(1), dim3(256), 0, st, N, (const double *)(m.KE.p + (size_t)2 * N * sl), (const int *)m.halt.p,
                            step, row);
-        if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy
+        if (cellrun)   // zeta, eta and the matrices of the next configuration, the cell after it, from the committee's virial in `packed`
+            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p,
+                               (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + N3 * sl), (const double *)m.mass.p,
+                               (const double *)packed, (const double *)h->d_cell0.p, (int)((m.run.t + j) & 0x3fffffff), (const int *)m.halt.p, step, row,
+                               m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j, (const double *)nullptr, (double *)nullptr, 0.0);
+        else if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy
             hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.run.t + j) & 0x3fffffff),
                                m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, m.halt.p, step, row);
         return SGPR_OK;
@@ -903,7 +985,7 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     h->lists_valid = false;
     if (rc_) return rc_;
     MdHalt r;
-    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, cellrun, &r)) return rc;
     // a capacity overflowed (md_decode_halt has cleared the live handle's `warm`): the next call's checked pass grows whatever it
     // was, on whichever member
     if (r.code == 2)

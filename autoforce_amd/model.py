@@ -595,6 +595,8 @@ class SGPRModel:
         """State of an MD run into device memory (cl/md.py:117-128 drives ase.md.langevin around calculate();
         here the integrator is part of the step's last kernel).  dt, friction and kT in the caller's units
         (workloads.FS / ase_shim.kB for fs / K).
+          pfactor (with ttime): a barostat, the moving cell of ase.md.npt.NPT (sgpr_md_barostat); md_committee(members,
+        moving_cell=True) may follow: the committee then runs in the moving cell.
           fixed: held atoms ([N] booleans: ase.constraints.FixAtoms) or Cartesian components ([N, 3]: FixCartesian), True =
         held (sgpr_md_fix; None or nothing held: the run without a mask).  The integrator sees F = 0 on a held component — the
         forces md_state reports stay the model's —, its velocity is exactly 0 from here on (the caller's value is dropped), it
@@ -1035,15 +1037,20 @@ class SGPRModel:
                 out["velocities"] = vel
         return out
 
-    def md_committee(self, members):
+    def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every
         configuration of md_run, in the order given with this model last — the run integrates the weighted forces, gates on
         the largest member-wise minimum covloss, and its rows and md_state(results=True) carry the committee's energy,
         forces, stress and covloss.  After md_begin (and its thermostat), before the first md_run; an empty list detaches.
-        Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, no mask, no frame record.  The model keeps
-        references to the members until md_end, the next md_begin or a detach."""
+        Langevin, velocity Verlet and Nose-Hoover at constant cell, and — moving_cell=True: the run's option "md_committee_cell",
+        without which a run with a barostat refuses a committee as before — Nose-Hoover with a barostat (md_begin(pfactor=): every
+        member is evaluated in the cell of the configuration, the moving cell integrates the committee's stress, md_cells() and
+        md_state() return the cell as for a single model); one rank, no mask, no filter, no bias, no frame record.  The model
+        keeps references to the members until md_end, the next md_begin or a detach."""
         members = list(members or ())
+        if moving_cell is not None:   # (the run's option: md_begin switches it off again)
+            check(_lib.load().sgpr_set_option(self._h, b"md_committee_cell", 1 if moving_cell else 0))
         arr = (C.c_void_p * max(len(members), 1))(*[None if mm is None else mm._h.value for mm in members])
         check(_lib.load().sgpr_md_committee(self._h, len(members), arr if members else None))
         self._md["members"] = members

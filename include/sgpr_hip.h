@@ -387,7 +387,10 @@ int sgpr_md_deviates(sgpr_model *h, int64_t t_first, int count, double *out);
  * 0 = its trace only (an isotropic cell; ASE applies no mask then).  Units as given to sgpr_md_begin.
  * SGPR_E_INVALID: a cell that is not upper triangular (h[1][0] = h[2][0] = h[2][1] = 0 exactly), a direction that is not
  * periodic, pfactor <= 0, no Nose-Hoover thermostat, a run that has started.  SGPR_E_UNSUPPORTED: a run begun on more than one
- * rank (the sharded last kernel integrates at constant cell).  The handle goes on working after any of them.
+ * rank (the sharded last kernel integrates at constant cell), held components, a bias.  The handle goes on working after any of
+ * them.  A run with a committee (sgpr_md_committee before or after this call) is refused likewise unless the run's option
+ * "md_committee_cell" is set (sgpr_set_option, after sgpr_md_begin); with it it is accepted: every member is evaluated in the cell
+ * of the configuration and the barostat integrates the committee's combined stress.
  * scalars of sgpr_md_run as for Nose-Hoover (14 / 15: zeta and its integral).  sgpr_md_state returns the positions of the
  * current configuration in ITS cell:
  * sgpr_md_cells   out[count][18] = cell h[9] (rows = cell vectors) and strain rate eta[9] of the configurations first ...
@@ -523,9 +526,14 @@ int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *
  *                         The members are BORROWED: the caller keeps them alive until sgpr_md_end, the next sgpr_md_begin or a
  *                         detach (each lets them go), and may use them between two sgpr_md_run calls (every call binds them to the run's system
  *                         again and repeats the capacity-checked pass where needed).  Langevin with uploaded or counter-based
- *                         deviates, velocity Verlet, Nose-Hoover NVT.  SGPR_E_UNSUPPORTED: a run with a barostat, a relaxation,
- *                         held components, an armed frame record (and sgpr_md_record, sgpr_md_fix, sgpr_md_barostat,
- *                         sgpr_md_relax behind an attached committee), a run begun on more than one rank, a member on another
+ *                         deviates, velocity Verlet, Nose-Hoover NVT, and — with the run's option
+ *                         "md_committee_cell" set first — Nose-Hoover with a barostat (sgpr_md_barostat before
+ *                         or after this call: the members are evaluated in the moving cell, whose strain rate follows the
+ *                         committee's stress; sgpr_md_cells and sgpr_md_state as for a single model).  SGPR_E_UNSUPPORTED: a
+ *                         barostat without that option, a
+ *                         relaxation, a band, a filter, a bias, held components, an armed frame record (and sgpr_md_record,
+ *                         sgpr_md_fix, sgpr_md_filter, sgpr_md_meta, sgpr_md_relax behind an attached committee) — with or
+ *                         without a barostat —, a run begun on more than one rank, a member on another
  *                         device, K > 15.  SGPR_E_INVALID: a member that is h itself, a null or duplicate member, a member
  *                         without weights or without choli, a run that has started (a detach too: a started run keeps
  *                         what it has), and sgpr_md_thermostat behind an attached committee.
@@ -708,7 +716,11 @@ int sgpr_sync_check(sgpr_model *h, void *stream);
  *                           single rank too: the twin a sharded run is compared with bit for bit (default 0: gather form)
  *  "spin_wait" = 1/0        sgpr_compute polls its stream for the end of a step instead of a blocking wait
  *                           (default 1: one host thread spins for the ~0.1 ms of a step, 16 us less wall time per
- *                           call on a 4096-atom frame; 0: hipStreamSynchronize).  Environment: SGPR_SPIN_WAIT */
+ *                           call on a 4096-atom frame; 0: hipStreamSynchronize).  Environment: SGPR_SPIN_WAIT
+ *  "md_committee_cell" = 0/1  of the RUN begun by sgpr_md_begin (which switches it off again; SGPR_E_INVALID without a run
+ *                           or on one that has started): 1 lets a committee and a barostat meet on the run —
+ *                           sgpr_md_committee accepts a run with a barostat, sgpr_md_barostat a run with a committee, and
+ *                           sgpr_md_run integrates the committee in the moving cell.  0 (default): each refuses the other. */
 int sgpr_set_option(sgpr_model *h, const char *name, int value);
 /* How many times the neighbour candidates were rebuilt since sgpr_create (see "skin_milliangstrom"). */
 int sgpr_get_list_rebuilds(sgpr_model *h, int64_t *count);
