@@ -33,7 +33,8 @@ except ImportError:
     GPa = 1.0 / 160.21766208
     HAVE_ASE = False
 
-from .model import Local, SGPRModel, recorded_indices
+from .device_loop import batches, first_on_host, hand_over, held, log_rows, put_state, record_cap, recorded_frames, sync_cap
+from .model import Local, SGPRModel
 from .posterior import EPS, Frame, PosteriorPotential
 from .sgprio import SgprIO
 from .sharding import pack_partial, rank_of_atoms, unpack_total
@@ -614,17 +615,7 @@ class ActiveCalculator(Calculator):
             raise ValueError("run_md: a barostat (pfactor) needs the Nose-Hoover thermostat (tdamp_fs)")
         baro = dict(pfactor=pfactor, externalstress=externalstress, mask=mask, iso=iso) if npt else {}
 
-        def put(st, vkey):
-            if npt:
-                if hasattr(atoms.cell, "array"):
-                    atoms.set_cell(st["cell"])
-                else:
-                    atoms.cell = np.array(st["cell"], float)
-            atoms.positions = st["positions"]
-            atoms.set_velocities(st[vkey])
-        fx = self.constraint_mask(atoms)
-        if fx is not None and not fx.any():
-            fx = None
+        fx = held(self.constraint_mask(atoms))
         if fx is not None and npt:
             raise NotImplementedError("run_md: atoms.constraints with a barostat (pfactor): the moving-cell dynamics run "
                                       "unconstrained; drive calculate() from an ASE dynamics object instead")
@@ -655,16 +646,14 @@ class ActiveCalculator(Calculator):
             return (self.md_on_device_ok() and not (committee and fx is not None)
                     and not (flt is not None and (committee or self._dist()[1] > 1))
                     and not (self.meta is not None and (npt or committee or self._dist()[1] > 1)))
-        first_on_host = self._needs_seed() or not on_device()
+        seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
             # logs — those velocities; md_begin and the host twin are handed the caller's and remove it themselves)
             from .npt import zero_mean_momentum
             atoms.set_velocities(zero_mean_momentum(vel, masses))
-        if first_on_host:
-            # (an empty model is seeded by its first calculate(); then the device loop can take over)
-            atoms.calc = self
-            atoms.get_forces()
+        if seeded:
+            first_on_host(self, atoms)   # (an empty model is seeded by its first calculate(); then the device loop can take over)
             if not on_device():
                 loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro, **filt) if npt else
                         nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold, **filt) if nh else
@@ -672,21 +661,18 @@ class ActiveCalculator(Calculator):
                 for st, E, T, _, p, v, *rest in loop:
                     if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
                         self.meta.update()
-                    put(dict(positions=p, velocities=v, cell=rest[0] if npt else None), "velocities")
+                    put_state(atoms, dict(positions=p, velocities=v, cell=rest[0] if npt else None), npt, "velocities")
                     if flt is not None:   # (the accumulators as this configuration found them: what a run that goes on from it takes)
                         flt.f, flt.s = rest[-1]
                     yield st, E, T, bool(self.updated), _
                 return
         eng = self.engine
-        kT = kB * temperature_K
+        kT, dof_kB = kB * temperature_K, dof * kB
         self._peer_fit(eng, N)
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
                      seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold, **filt)
-        # (skip_gate: the configuration has been through calculate() — logged, counted, the model updated if need be —
-        # and is evaluated once more on the device, whatever its covloss, to move on from it)
-        done, rows, skip_gate, t_host = 0, np.empty((0, N, 3)), first_on_host, 0.0
         attached = self._md_attach(eng)
-        meta = self.meta
+        meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
             # every batch the new rows are mirrored into the Meta (meta.hist, and calculate() at a halt sees the same bias)
@@ -703,88 +689,70 @@ class ActiveCalculator(Calculator):
             eng.md_meta(self._meta_spec(), meta.sigma, meta.w, tem=meta.tem, pace=meta.pace, hills=hills0 if len(hills0) else None,
                         capacity=len(hills0) + (steps + 1) // meta.pace + 2, **({"merge": meta.merge} if getattr(meta, "merge", None) else {}))
             meta_seen, meta_n0 = len(hills0), meta.n
+
+        def hills(b):
+            # the rows of the configurations below the current one (a halted one deposits when it is repeated): V by the index
+            # of the configuration that deposited
+            nonlocal meta_seen
+            info = eng.md_meta_info()   # (the run's last configuration stands evaluated: its own row too)
+            below = info["held"] if (b.final and b.code == 0) else info["below"]
+            cvn, Vn = eng.md_meta_hills(meta_seen, below - meta_seen)
+            first_dep = -(-b.first // meta.pace) * meta.pace
+            meta.absorb(cvn, meta_n0 + b.done)
+            meta_seen = below
+            return {first_dep + k * meta.pace: float(v) for k, v in enumerate(Vn)}
         # (a run with members attached records no frames: batches end at the multiples of sync_every)
         rec = bool(record and sync_every and hasattr(eng, "md_record") and self._dist()[1] == 1 and not attached)
-        if rec:   # (positions and the velocities the integrator holds; a batch of at most rec_max frames)
+        if rec:   # (positions and the velocities the integrator holds; a batch of at most RECORD_BYTES of them)
             eng.md_record(sync_every, velocities=True, results=False)
-            rec_max = max(1, self.RECORD_BYTES // (48 * N))
-        ke_before = None   # (moving cell: sum m v^2 of the configuration before the row at hand — the velocities calculate() is handed)
-        batch = min(8, chunk)   # evaluations per md_run call: grows while nothing halts the device, shrinks back after a halt
-        while done <= steps:    # (every call uploads its rows of deviates; a halt throws the unused ones' upload away)
-            n = 1 if skip_gate else min(batch, steps + 1 - done)
-            if rec:
-                n = max(1, min(n, rec_max * sync_every - done % sync_every))
-            elif sync_every and not skip_gate:
-                n = min(n, sync_every - done % sync_every if done % sync_every else 1)   # (… a batch ends on a multiple)
-            final = done + n == steps + 1
-            need = 0 if (on_device_rng or nh) else (n - 1 if final else n)
+        cap = record_cap(self.RECORD_BYTES, 48 * N, sync_every) if rec else sync_cap(sync_every) if sync_every else None
+        rows = np.empty((0, N, 3))   # deviates drawn and not yet used: a halt leaves the rows behind it for the next call
+
+        def deviates(n, final):   # (a `final` call moves nothing behind its last evaluation: one row fewer, zeros in its place)
+            nonlocal rows
+            need = n - 1 if final else n
             if len(rows) < need:
                 rows = np.concatenate([rows, rng.normal(size=(need - len(rows), N, 3))])
-            noise = None if (on_device_rng or nh) else (rows[:n] if len(rows) >= n else np.concatenate([rows, np.zeros((n - len(rows), N, 3))]))
-            gate = 0.0 if skip_gate else self._md_gate(numbers)
-            t_run = time.time()
-            sc, code = eng.md_run(n, noise, ediff=gate, final=final)
-            accepted = len(sc) - 1 if code == 1 else len(sc)
-            share = (time.time() - t_run) / max(accepted, 1)
-            lines, out, counts, step_now = [], [], [], self.step
-            meta_V = {}
-            if meta is not None:   # the rows of the configurations below the current one (a halted one deposits when it is repeated)
-                info = eng.md_meta_info()   # (the run's last configuration stands evaluated: its own row too)
-                below = info["held"] if (final and code == 0) else info["below"]
-                cvn, Vn = eng.md_meta_hills(meta_seen, below - meta_seen)
-                first_dep = -(-done // meta.pace) * meta.pace
-                meta_V = {first_dep + k * meta.pace: float(v) for k, v in enumerate(Vn)}
-                meta.absorb(cvn, meta_n0 + done + accepted)
-                meta_seen = below
-            for r in sc[:accepted]:
-                upd, wall = False, share
-                if skip_gate:      # (the configuration calculate() has just dealt with, evaluated again with the new model:
-                    skip_gate, upd, wall = False, bool(self.updated), share + t_host   # its line is written, its step counted)
-                else:
-                    # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a
-                    # moving cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
-                    ke_line = r[13] if (not npt or ke_before is None) else ke_before
-                    lines.append((step_now, "{} {} {} {}".format(float(r[0]), float(ke_line / (dof * kB)), float(r[11]),
-                                                                 f"meta: {meta_V[done]}" if done in meta_V else "")))
-                    step_now += 1
-                ke_before = r[12]
-                out.append((done, float(r[0]), float(r[12] / (dof * kB)), upd, wall))
-                counts.append(step_now)
-                done += 1
-            self._log_lines(lines)
+            return rows[:n] if len(rows) >= n else np.concatenate([rows, np.zeros((n - len(rows), N, 3))])
+
+        def line(t, r, prev):
+            # (the line's temperature is that of the velocities the integrator holds when it asks for the forces: with a moving
+            # cell the centred velocities of the configuration before, as npt.NPT hands them to calculate())
+            ke = r[13] if (not npt or prev is None) else prev[12]
+            return "{} {} {} {}".format(r[0], ke / dof_kB, r[11], f"meta: {meta_V[t]}" if t in meta_V else "")
+
+        def halt(b):
+            put_state(atoms, eng.md_state(results=True), npt, "velocities_pre")   # (what the integrator holds when it asks for forces)
+            hand_over(self, atoms)
+            if flt is not None and self.deltas:   # (the jump of this update: FilterDeltas reads it at its next call)
+                eng.md_filter_push(self.deltas["forces"], self.deltas["stress"])
+                flt.pushes += 1
+        for b in batches(self, eng, numbers, steps, chunk, seeded, cap, None if (on_device_rng or nh) else deviates, halt):
+            if meta is not None:
+                meta_V = hills(b)
+            counts = log_rows(self, b, line)
+            out = [(t, r[0], r[12] / dof_kB, False, b.share) for t, r in enumerate(b.rows, b.first)]
+            if b.resumed and out:   # (the configuration calculate() has just dealt with, evaluated again with the new model)
+                out[0] = out[0][:3] + (bool(self.updated), b.share + b.t_host)
             if rec:
                 # the frames of the accepted rows at multiples of sync_every, each put before its row is yielded; self.step is
                 # what it is behind that row (on the cutting path a batch ends there)
-                fr = eng.md_frames(reuse=True) if recorded_indices(done - accepted, len(sc), code, sync_every) else dict(index=())
-                at = {int(i): k for k, i in enumerate(fr["index"])}
+                fr = recorded_frames(eng, b, sync_every)
+                at = {int(i): k for k, i in enumerate(fr["index"])} if fr else {}
                 for o, cnt in zip(out, counts):
                     self.step = cnt
                     if o[0] % sync_every == 0:
                         k = at[o[0]]
-                        put(dict(positions=fr["positions"][k].copy(), velocities_pre=fr["velocities_pre"][k].copy(), cell=fr["cell"][k] if npt else None),
-                            "velocities_pre")
+                        put_state(atoms, dict(positions=fr["positions"][k].copy(), velocities_pre=fr["velocities_pre"][k].copy(),
+                                              cell=fr["cell"][k] if npt else None), npt, "velocities_pre")
                     yield o
             else:
-                self.step = step_now
-                if sync_every and out and out[-1][0] % sync_every == 0 and code != 1:
+                if sync_every and out and out[-1][0] % sync_every == 0 and b.code != 1:
                     # the configuration of the batch's last row: the device has moved on to the next one unless the run is over
-                    put(eng.md_state(which=0 if final else -1), "velocities_pre")
+                    put_state(atoms, eng.md_state(which=0 if b.final else -1), npt, "velocities_pre")
                 yield from out
-            self.step = step_now
-            rows = rows[accepted:]
-            batch = min(8, chunk) if code else min(2 * batch, chunk)
-            if code == 1:
-                t_host = time.time()
-                put(eng.md_state(results=True), "velocities_pre")   # (what the integrator holds when it asks for forces)
-                atoms.calc = self
-                self.results = {}
-                self.calculate(atoms)        # update_results + update + the log line, as inside an ASE loop
-                if flt is not None and self.deltas:   # (the jump of this update: FilterDeltas reads it at its next call)
-                    eng.md_filter_push(self.deltas["forces"], self.deltas["stress"])
-                    flt.pushes += 1
-                skip_gate = True
-                t_host = time.time() - t_host
-        put(eng.md_state(results=True), "velocities")
+            rows = rows[len(b.rows):]
+        put_state(atoms, eng.md_state(results=True), npt, "velocities")
         if flt is not None:
             flt.f, flt.s = eng.md_filter_state()
         if attached:
@@ -815,28 +783,17 @@ class ActiveCalculator(Calculator):
         coordinate keeps its bits at constant cell, and with cell=True keeps its undeformed coordinate while x follows the cell,
         as FixAtoms inside UnitCellFilter.  Any other constraint kind: NotImplementedError."""
         from .cl.relax import FIRE, UnitCellFilter, force_max
-        fx = self.constraint_mask(atoms)
-        if fx is not None and not fx.any():
-            fx = None
+        fx = held(self.constraint_mask(atoms))
         hold = {} if fx is None else dict(fixed=fx)
-
-        def put(st):
-            if cell:
-                if hasattr(atoms.cell, "array"):
-                    atoms.set_cell(st["cell"])
-                else:
-                    atoms.cell = np.array(st["cell"], float)
-            atoms.positions = st["positions"]
 
         def device_ok():
             # (a committee with members — BCMActiveCalculator — relaxes through the host loop around calculate(): the device
             # relaxation evaluates one model)
             return (self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "relax_begin")
                     and not getattr(self, "model_dict", None) and self.meta is None)   # (a bias: the host loop around calculate())
-        first_on_host = self._needs_seed() or not device_ok()
-        if first_on_host:
-            atoms.calc = self
-            atoms.get_forces()
+        seeded = self._needs_seed() or not device_ok()
+        if seeded:
+            first_on_host(self, atoms)
             if not device_ok():
                 target = UnitCellFilter(atoms, mask=mask) if cell else atoms
                 opt = FIRE(target, **fire)
@@ -858,46 +815,28 @@ class ActiveCalculator(Calculator):
         numbers, pos, cell0, pbc = self._system(atoms)
         eng = self.engine
         eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **hold, **fire)
-        done, skip_gate, converged = 0, first_on_host, False
-        batch = min(8, chunk)
+        done, converged, cap = 0, False, None
         rec, reported = on_frame is not None, -1
-        if rec:   # (positions and the packed results; a batch of at most rec_max frames)
+        if rec:   # (positions and the packed results; a batch of at most RECORD_BYTES of them)
             interval = max(1, int(interval))
             eng.md_record(interval, velocities=False, results=True)
-            rec_max = max(1, self.RECORD_BYTES // (8 * (7 * len(numbers) + 11)))
-        while done <= steps and not converged:
-            n = 1 if skip_gate else min(batch, steps + 1 - done)
-            if rec:
-                n = max(1, min(n, rec_max * interval - done % interval))
-            gate = 0.0 if skip_gate else self._md_gate(numbers)
-            sc, code = eng.md_run(n, None, ediff=gate, final=(done + n == steps + 1))
-            accepted = len(sc) - 1 if code == 1 else len(sc)
-            lines = []
-            for r in sc[:accepted]:
-                if skip_gate:      # (the configuration calculate() has just dealt with: its line is written, its step counted)
-                    skip_gate = False
-                else:
-                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), 0.0, float(r[11]), "")))
-                    self.step += 1
-                done += 1
-            self._log_lines(lines)
-            if rec and recorded_indices(done - accepted, len(sc), code, interval):   # (the accepted evaluations' frames: a halted one is recorded by its re-evaluation)
-                fr = eng.md_frames(reuse=True)
+            cap = record_cap(self.RECORD_BYTES, 8 * (7 * len(numbers) + 11), interval)
+
+        def halt(b):
+            put_state(atoms, eng.md_state(), cell)
+            hand_over(self, atoms)
+            if clear_hist and self.updated:
+                eng.relax_reset()
+        for b in batches(self, eng, numbers, steps, chunk, seeded, cap, hand_over=halt):
+            log_rows(self, b, lambda t, r, prev: "{} {} {} {}".format(r[0], 0.0, r[11], ""))
+            fr = recorded_frames(eng, b, interval) if rec else None   # (the accepted evaluations' frames: a halted one is recorded by its re-evaluation)
+            if fr:
                 for k, i in enumerate(fr["index"]):
                     on_frame(int(i), dict(positions=fr["positions"][k].copy(), cell=fr["cell"][k], energy=float(fr["energy"][k]), forces=fr["forces"][k].copy()))
                     reported = int(i)
-            batch = min(8, chunk) if code else min(2 * batch, chunk)
-            if code == 1:
-                put(eng.md_state())
-                atoms.calc = self
-                self.results = {}
-                self.calculate(atoms)        # update_results + update + the log line, as inside an ASE loop
-                if clear_hist and self.updated:
-                    eng.relax_reset()
-                skip_gate = True
-            converged = code == 3
+            done, converged = b.done, b.code == 3
         st = eng.md_state(results=True)
-        put(st)
+        put_state(atoms, st, cell)
         if rec and reported != done - 1:   # (the final structure, where its index is no multiple of the interval)
             on_frame(done - 1, dict(positions=st["positions"], cell=np.array(st["cell"], float), energy=float(st["energy"]), forces=st["forces"]))
         # (the calculator answers for the final configuration from what the device has just computed)
@@ -941,8 +880,7 @@ class ActiveCalculator(Calculator):
         for mk in masks[1:]:
             if (mk is None) != (fx is None) or (fx is not None and not np.array_equal(mk, fx)):
                 raise NotImplementedError("run_neb: the interior images hold different components (atoms.constraints); one mask serves every image")
-        if fx is not None and not fx.any():
-            fx = None
+        fx = held(fx)
         hold = {} if fx is None else dict(fixed=fx)
         numbers, _, cell0, pbc = self._system(images[1])
         for im in images:
@@ -954,8 +892,7 @@ class ActiveCalculator(Calculator):
         def device_ok():
             return self.md_on_device_ok() and self._dist()[1] == 1 and hasattr(self.engine, "neb_begin") and self.meta is None
         if self._needs_seed() or not device_ok():
-            images[1].calc = self
-            images[1].get_forces()
+            first_on_host(self, images[1])
         if not device_ok():   # the host loop: calculate() per image, a restart of the optimizer whenever the model grew
             size = [self.size]
 
@@ -972,39 +909,21 @@ class ActiveCalculator(Calculator):
             return dict(converged=last["converged"], steps=last["n"], evaluations=last["n"] + 1, energies=last["energies"], forces=last["forces"])
         eng = self.engine
         eng.neb_begin(numbers, R, cell0, pbc, fmax, k=k, climb=climb, **hold, **fire)
-        done, skip_gate, converged = 0, False, False
-        batch = min(8, chunk)
-        while done <= steps and not converged:
-            n = 1 if skip_gate else min(batch, steps + 1 - done)
-            gate = 0.0 if skip_gate else self._md_gate(numbers)
-            final = done + n == steps + 1
-            sc, code = eng.md_run(n, None, ediff=gate, final=final)
-            accepted = len(sc) - 1 if code == 1 else len(sc)
-            lines = []
-            for r in sc[:accepted]:
-                if skip_gate:      # (the band calculate() has just dealt with: its line is written, its step counted — as run_relax)
-                    skip_gate = False
-                else:
-                    lines.append((self.step, "{} {} {} {}".format(float(r[0]), 0.0, float(r[11]), f"neb: highest image {int(r[1])}")))
-                    self.step += 1
-                done += 1
-            self._log_lines(lines)
-            batch = min(8, chunk) if code else min(2 * batch, chunk)
-            if on_band is not None and accepted:   # (the last accepted band: the current one where nothing moved behind it)
-                on_band(done - 1, eng.neb_state(which=0 if (code == 3 or (code == 0 and final)) else -1, results=True))
-            if code == 1:   # the image that carried the largest covloss goes to calculate(), as inside an ASE loop
-                i = int(sc[-1, 2])
-                img = images[i]
-                img.positions = eng.neb_state()["positions"][i - 1]
-                size = self.size
-                img.calc = self
-                self.results = {}
-                self.calculate(img)
-                if self.size != size:
-                    self.log("model updated -> restart!")
-                    eng.neb_reset()
-                skip_gate = True
-            converged = code == 3
+        done, converged = 0, False
+
+        def halt(b):   # the image that carried the largest covloss goes to calculate(), as inside an ASE loop
+            i = int(b.sc[-1, 2])
+            images[i].positions = eng.neb_state()["positions"][i - 1]
+            size = self.size
+            hand_over(self, images[i])
+            if self.size != size:
+                self.log("model updated -> restart!")
+                eng.neb_reset()
+        for b in batches(self, eng, numbers, steps, chunk, hand_over=halt):
+            log_rows(self, b, lambda t, r, prev: "{} {} {} {}".format(r[0], 0.0, r[11], f"neb: highest image {int(r[1])}"))
+            done, converged = b.done, b.code == 3
+            if on_band is not None and b.rows:   # (the last accepted band: the current one where nothing moved behind it)
+                on_band(done - 1, eng.neb_state(which=0 if (b.code == 3 or (b.code == 0 and b.final)) else -1, results=True))
         st = eng.neb_state(results=True)
         for im, x in zip(images[1:-1], st["positions"]):
             im.positions = x
