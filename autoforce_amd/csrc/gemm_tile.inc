@@ -495,7 +495,9 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
                         } else
                             pm1 = pow(v, p.eta - 1.0);
                         const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                        double k = (!rl && !cl) ? pm1 * v : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
+                        // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
+                        double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
+                                                : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
                         const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
                         if (same && row < p.M && col < p.N) {
                             if constexpr (FUSED) {
@@ -725,7 +727,9 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
                 } else
                     pm1 = pow(v, p.eta - 1.0);
                 const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                const double k = (!rl && !cl) ? pm1 * v : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
+                // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
+                const double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
+                                              : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
                 const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
                 if (same && row < p.M && col < p.N) {
                     // (K and Aw are read by the next launch only: write-through, sgpr_internal.h)
@@ -962,7 +966,9 @@ __device__ __forceinline__ void gemm_tile_body8r64(const GemmArgs &g, const int 
                     } else
                         pm1 = pow(v, p.eta - 1.0);
                     const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                    const double k = (!rl && !cl) ? pm1 * v : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
+                    // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
+                    const double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
+                                                  : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
                     const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
                     if (same && row < p.M && col < p.N) {
                         p.C[(size_t)row * p.ldc + col] = k;

@@ -60,6 +60,9 @@ void sgpr_live_device_memory(int64_t *bytes, int64_t *buffers);
  * species_z[S]: atomic numbers the model knows (the reference's 120-wide wildcard table,
  *   sesoap.py:134, restricted to those that occur); radii[S]: length unit per species
  *   (sesoap.py:84-99; DefaultRadii = 0.5 for H, 1.0 otherwise).
+ * eta > 0: the exponent of k(i, q) = [Z_i == Z_q] (p_i . p_q)^eta.  4 has a branch of its own, the other integers 1 ... 64 a
+ *   multiply loop, everything else (non-integers, integers above 64) pow(); an orthogonal pair (p_i . p_q = 0) has k = 0 at
+ *   every exponent, and below 1 its derivative eta v^(eta - 1) is unbounded there, as in the reference.
  */
 int sgpr_create(int lmax, int nmax, double eta, double rc, int S, const int32_t *species_z,
                 const double *radii, int device, sgpr_model **out);

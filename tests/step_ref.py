@@ -41,6 +41,18 @@ def gamma(n):
     return n / (1.0 - n)
 
 
+def _dpow(av, dv, eta):
+    """Bound of |x^eta - v^eta| for |x - v| <= dv, x and v >= 0, av = |v|.  eta >= 1: the derivative eta x^(eta-1) grows with
+    x, so its value at av + dv times dv.  eta < 1: the derivative falls with x, so its value at av - dv where that is
+    positive, and never more than dv^eta (|x^eta - v^eta| <= |x - v|^eta for a concave power).  dv = 0 (a pair of
+    descriptors with disjoint blocks: every product of the dot is an exact zero) gives 0 at every exponent."""
+    if eta >= 1.0:
+        return eta * (av + dv) ** (eta - 1.0) * dv
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lo = np.where(av > dv, eta * np.maximum(av - dv, 1e-300) ** (eta - 1.0) * dv, np.inf)
+    return np.minimum(lo, dv ** eta)
+
+
 # ---------------------------------------------------------------------------------------------- references
 def knm(P, Q, zi, zq, lone_i, lone_q, eta, lone_weight=1.0):
     """P [n, ...] and Q [m, ...] descriptors (flattened to rows), zi [n] / zq [m] species slots (-1: a ghost, no kernel),
@@ -61,7 +73,7 @@ def knm(P, Q, zi, zq, lone_i, lone_q, eta, lone_weight=1.0):
         a = np.abs(P[rows]) @ np.abs(Q[cols]).T
         dv = g * a + host
         k = v ** LD(eta)
-        bk = eta * (np.abs(v).astype(float) + dv) ** (eta - 1.0) * dv + gamma(int(np.ceil(eta)) + 2) * np.abs(k).astype(float)
+        bk = _dpow(np.abs(v).astype(float), dv, eta) + gamma(int(np.ceil(eta)) + 2) * np.abs(k).astype(float)
         li, lq = lone_i[rows][:, None], lone_q[cols][None, :]
         k = np.where(li & lq, LD(lone_weight), np.where(li | lq, LD(0), k))
         bk = np.where(li | lq, 0.0, bk)

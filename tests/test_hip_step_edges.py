@@ -67,9 +67,9 @@ def inducing(species, counts, seed):
     return X
 
 
-def model(species, ind_counts, seed=0, ghosts=False):
+def model(species, ind_counts, seed=0, ghosts=False, eta=ETA):
     from autoforce_amd import SGPRModel
-    mdl = SGPRModel(3, 3, ETA, RC, species=species, unknown_species="ignore" if ghosts else "error")
+    mdl = SGPRModel(3, 3, eta, RC, species=species, unknown_species="ignore" if ghosts else "error")
     mdl.set_inducing(inducing(species, ind_counts, seed))
     return mdl
 
@@ -111,9 +111,9 @@ def step_form(mdl):
 
 
 # ---------------------------------------------------------------------------------------------- the check
-def check(mdl, fr, mu, mean, C, what="", rank_world=None, view=False, oracle=True):
+def check(mdl, fr, mu, mean, C, what="", rank_world=None, view=False, oracle=True, eta=ETA):
     """Predict `fr` on `mdl` (weights mu / mean / C installed here, C rescaled so that max c = 0.9) and check every
-    output against the references.  Returns the device output."""
+    output against the references (eta: the exponent `mdl` was created with).  Returns the device output."""
     numbers, pos, cell, pbc = fr
     N = len(numbers)
     install(mdl, mu, mean, C)
@@ -125,7 +125,7 @@ def check(mdl, fr, mu, mean, C, what="", rank_world=None, view=False, oracle=Tru
     nptr = mdl.neighbors(N)[0]
     lone_i = np.diff(nptr) == 0
     lone_q = np.array([not np.isin(x._b, mdl.species).any() for x in mdl.X])
-    K, bK = ref.knm(P, Q, zi, zq, lone_i, lone_q, ETA)
+    K, bK = ref.knm(P, Q, zi, zq, lone_i, lone_q, eta)
     c0 = ref.covloss(K, bK, C, zi, zq)[0]
     alpha = ref.scale_for_c(c0)
     Ca = alpha * C
@@ -155,7 +155,7 @@ def check(mdl, fr, mu, mean, C, what="", rank_world=None, view=False, oracle=Tru
         Pm, nnm = orc.inducing_descriptors(3, 3, RC, sp, ind_z, ind_ptr, np.concatenate([x._b for x in X]).astype(np.int32),
                                            np.concatenate([x._r for x in X]))
         nl = orc.neighbors(pos[keep], cell, pbc, RC)
-        o = orc.frame(3, 3, RC, ETA, sp, numbers[keep], pos[keep], cell, nl, ind_z, nnm, Pm, mu, want_p=False)
+        o = orc.frame(3, 3, RC, eta, sp, numbers[keep], pos[keep], cell, nl, ind_z, nnm, Pm, mu, want_p=False)
         fmax = np.abs(o["forces"]).max()
         assert np.abs(out["forces"][keep] - o["forces"]).max() <= 1e-8 * fmax, what
         assert np.abs(out["stress"] - o["stress"]).max() <= 1e-8 * max(np.abs(o["stress"]).max(), 1e-12), what
