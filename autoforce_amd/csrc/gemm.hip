@@ -84,6 +84,12 @@ __global__ __launch_bounds__(512, 6) void gemm_nt_kernel8r64x3(GemmArgs g)
     gemm_tile_body8r64<EPI, 3>(g, (int)blockIdx.x, As, Bs);
 }
 
+// GemmArgs::ieta: an integer exponent from 1 to 64 (the epilogue multiplies), or -1 (it calls pow)
+static int integer_exponent(double eta)
+{
+    return (eta == (double)(int)eta && eta >= 1.0 && eta <= 64.0) ? (int)eta : -1;
+}
+
 void launch_gemm_wcov(const GemmParams &pw, const GemmParams &pc, const int4 *tiles, int ntiles, hipStream_t st, int grid)
 {
     if (ntiles <= 0) return;
@@ -111,7 +117,7 @@ void launch_gemm_fused(const GemmParams &pk, const GemmParams &pw, const GemmPar
     g.p = pw; g.p2 = pc; g.p3 = pk;
     g.p.tiles = tiles;
     g.p.ntiles = ntiles;
-    g.ieta = (pk.eta == (double)(int)pk.eta && pk.eta >= 1.0 && pk.eta <= 64.0) ? (int)pk.eta : -1;
+    g.ieta = integer_exponent(pk.eta);
     g.row_slot = pk.row_slot;
     g.col_slot = pk.col_slot;
     g.Epart = Epart;
@@ -124,7 +130,7 @@ void launch_gemm_nt(const GemmParams &p, GemmEpilogue epi, hipStream_t st)
     if (p.M <= 0 || p.N <= 0) return;
     GemmArgs g = {};
     g.p = p;
-    g.ieta = (p.eta == (double)(int)p.eta && p.eta >= 1.0 && p.eta <= 64.0) ? (int)p.eta : -1;
+    g.ieta = integer_exponent(p.eta);
     g.row_slot = p.row_slot;
     g.col_slot = p.col_slot;
     g.Epart = p.Esum;
@@ -132,39 +138,32 @@ void launch_gemm_nt(const GemmParams &p, GemmEpilogue epi, hipStream_t st)
     g.row_tiles = (p.M + BM - 1) / BM;
     g.col_tiles = (p.N + BN - 1) / BN;
     g.rows_pad = (g.row_tiles + 7) / 8 * 8;
-    dim3 grid(p.tiles ? p.ntiles : g.rows_pad * g.col_tiles), block(256);
+    dim3 grid(p.tiles ? p.ntiles : g.rows_pad * g.col_tiles);
     if (p.tiles && p.ntiles <= 0) return;
-    if (p.bm == 16 && p.tiles && (epi == EPI_KERNEL || epi == EPI_STORE || epi == EPI_ROWSQ)) {
-        if (epi == EPI_KERNEL) hipLaunchKernelGGL(gemm_nt_kernel4h<EPI_KERNEL>, grid, dim3(256), 0, st, g);
-        else if (epi == EPI_STORE) hipLaunchKernelGGL(gemm_nt_kernel4h<EPI_STORE>, grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL(gemm_nt_kernel4h<EPI_ROWSQ>, grid, dim3(256), 0, st, g);
-        return;
-    }
-    if (p.waves == 8 && p.bm == 64 && p.wgs == 3 && p.tiles && (epi == EPI_KERNEL || epi == EPI_STORE || epi == EPI_ROWSQ)) {
-        if (epi == EPI_KERNEL) hipLaunchKernelGGL(gemm_nt_kernel8r64x3<EPI_KERNEL>, grid, dim3(512), 0, st, g);
-        else if (epi == EPI_STORE) hipLaunchKernelGGL(gemm_nt_kernel8r64x3<EPI_STORE>, grid, dim3(512), 0, st, g);
-        else hipLaunchKernelGGL(gemm_nt_kernel8r64x3<EPI_ROWSQ>, grid, dim3(512), 0, st, g);
-        return;
-    }
-    if (p.waves == 8 && p.bm == 64 && p.tiles && (epi == EPI_KERNEL || epi == EPI_STORE || epi == EPI_ROWSQ)) {
-        if (epi == EPI_KERNEL) hipLaunchKernelGGL(gemm_nt_kernel8r64<EPI_KERNEL>, grid, dim3(512), 0, st, g);
-        else if (epi == EPI_STORE) hipLaunchKernelGGL(gemm_nt_kernel8r64<EPI_STORE>, grid, dim3(512), 0, st, g);
-        else hipLaunchKernelGGL(gemm_nt_kernel8r64<EPI_ROWSQ>, grid, dim3(512), 0, st, g);
-        return;
-    }
-    if (p.waves == 8 && p.bm == 32 && p.tiles && p.kd == 16 && (epi == EPI_KERNEL || epi == EPI_STORE)) {
-        if (epi == EPI_KERNEL) hipLaunchKernelGGL(gemm_nt_kernel8<EPI_KERNEL>, grid, dim3(512), 0, st, g);
-        else hipLaunchKernelGGL(gemm_nt_kernel8<EPI_STORE>, grid, dim3(512), 0, st, g);
-        return;
-    }
-    if (epi == EPI_STORE && p.bm == 32 && p.tiles && p.kd == 16) hipLaunchKernelGGL((gemm_nt_kernel<EPI_STORE, 1, 16>), grid, block, 0, st, g);
-    else if (epi == EPI_ROWSQ && p.bm == 32 && p.tiles && p.kd == 16) hipLaunchKernelGGL((gemm_nt_kernel<EPI_ROWSQ, 1, 16>), grid, block, 0, st, g);
-    else if (epi == EPI_STORE && p.bm == 32 && p.tiles) hipLaunchKernelGGL((gemm_nt_kernel<EPI_STORE, 1>), grid, block, 0, st, g);
-    else if (epi == EPI_ROWSQ && p.bm == 32 && p.tiles) hipLaunchKernelGGL((gemm_nt_kernel<EPI_ROWSQ, 1>), grid, block, 0, st, g);
-    else if (epi == EPI_STORE) hipLaunchKernelGGL(gemm_nt_kernel<EPI_STORE>, grid, block, 0, st, g);
-    else if (epi == EPI_KERNEL && p.bm == 32 && p.tiles && p.kd == 16) hipLaunchKernelGGL((gemm_nt_kernel<EPI_KERNEL, 1, 16>), grid, block, 0, st, g);
-    else if (epi == EPI_KERNEL && p.bm == 32 && p.tiles) hipLaunchKernelGGL((gemm_nt_kernel<EPI_KERNEL, 1>), grid, block, 0, st, g);
-    else if (epi == EPI_KERNEL) hipLaunchKernelGGL(gemm_nt_kernel<EPI_KERNEL>, grid, block, 0, st, g);
-    else if (epi == EPI_SUBLOWER) hipLaunchKernelGGL(gemm_nt_kernel<EPI_SUBLOWER>, grid, block, 0, st, g);
-    else hipLaunchKernelGGL(gemm_nt_kernel<EPI_ROWSQ>, grid, block, 0, st, g);
+    // (the kernel comes last: its template arguments carry commas)
+#define LAUNCH(THREADS, ...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(THREADS), 0, st, g)
+    // KERNEL<epi, ...> for the three epilogues of a step's products (the trailing arguments: TM and KD of gemm_nt_kernel)
+#define LAUNCH_STEP(THREADS, KERNEL, ...)                                                        \
+    do {                                                                                         \
+        if (epi == EPI_KERNEL) LAUNCH(THREADS, KERNEL<EPI_KERNEL, ##__VA_ARGS__>);               \
+        else if (epi == EPI_STORE) LAUNCH(THREADS, KERNEL<EPI_STORE, ##__VA_ARGS__>);            \
+        else LAUNCH(THREADS, KERNEL<EPI_ROWSQ, ##__VA_ARGS__>);                                  \
+    } while (0)
+    const bool step = epi == EPI_KERNEL || epi == EPI_STORE || epi == EPI_ROWSQ;
+    const bool t32 = p.tiles && p.bm == 32;
+    // (form, epilogue) -> kernel, first match.  Half tiles and eight waves: with a tile table and a step's epilogues only
+    if (step && p.tiles && p.bm == 16)                               LAUNCH_STEP(256, gemm_nt_kernel4h);
+    else if (step && p.tiles && p.bm == 64 && p.waves == 8 && p.wgs == 3) LAUNCH_STEP(512, gemm_nt_kernel8r64x3);
+    else if (step && p.tiles && p.bm == 64 && p.waves == 8)          LAUNCH_STEP(512, gemm_nt_kernel8r64);
+    else if (epi == EPI_KERNEL && t32 && p.kd == 16 && p.waves == 8) LAUNCH(512, gemm_nt_kernel8<EPI_KERNEL>);
+    else if (epi == EPI_STORE && t32 && p.kd == 16 && p.waves == 8)  LAUNCH(512, gemm_nt_kernel8<EPI_STORE>);
+    // Four waves: every other form, and whatever the rows above do not take — a request without a table, a covloss product
+    // asking for eight waves on 32 rows, and any epilogue outside a step's three whatever form the request names:
+    else if (epi == EPI_SUBLOWER)                                    LAUNCH(256, gemm_nt_kernel<EPI_SUBLOWER>);  // (linalg.hip: dense, 64 rows)
+    else if (!step)                                                  LAUNCH(256, gemm_nt_kernel<EPI_ROWSQ>);  // (EPI_WCOV, EPI_FUSED: launchers of their own, no caller passes them here)
+    else if (t32 && p.kd == 16)                                      LAUNCH_STEP(256, gemm_nt_kernel, 1, 16);
+    else if (t32)                                                    LAUNCH_STEP(256, gemm_nt_kernel, 1, 32);
+    else                                                             LAUNCH_STEP(256, gemm_nt_kernel, 2, 32);
+#undef LAUNCH
+#undef LAUNCH_STEP
 }

@@ -2,6 +2,15 @@
 // epilogues and what was measured).  Included by gemm.hip (the GEMM launches) and by descriptor.hip (the reverse kernel
 // runs the covloss tiles of a step in its own launch: MFMA-bound tiles beside VALU-bound waves, one launch less
 // on the critical path).
+// The three tile bodies differ in their main loops; around them they share row_sum16 / wave_sum64, the kernel value
+// (kernel_pm1 + KERNEL_VALUE), the tile entry (TILE_ENTRY_OR_RETURN), the stamps (stamp_entry / stamp_record) and the metadata
+// prefetch (fetch_row_meta / fetch_col_meta).  Every kernel's VGPR / SGPR / scratch / LDS figures (tools/kres.py) are those of
+// the copies these replaced; the shapes that were not neutral: k and kp from functions — gemm_nt_kernel<EPI_FUSED, 1, 16>
+// 24 B and gemm_nt_kernel8r64x3<EPI_KERNEL> 36 B of scratch per lane, gemm_nt_kernel8r64<EPI_KERNEL> 110 -> 118 VGPRs; the
+// tile entry as a function — gemm_nt_kernel<EPI_ROWSQ, 1, 32> 120 -> 124; the prefetch helpers in gemm_tile_body8 —
+// gemm_nt_kernel8<EPI_KERNEL> 70 -> 72 SGPRs, and with the four rows in one call 84 -> 86 VGPRs (in the other bodies that
+// form kept the figures and reordered 600 lines of the fused kernel); stamp_record testing g.stamps itself —
+// gemm_nt_kernel8r64<EPI_WCOV> 44 -> 48 SGPRs.
 #pragma once
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -50,11 +59,105 @@ __device__ __forceinline__ double2 load_a2(const double *q)
         return *(const double2 *)q;
 }
 
-__device__ __forceinline__ double ipow_d(double x, int n)
+// the sum over the 16 lanes of a row, in every lane of it: the same pairs, in the same order, as xor 1, 2, 4, 8
+__device__ __forceinline__ double row_sum16(double s)
 {
-    double y = 1.0;
-    for (int k = 0; k < n; k++) y *= x;
-    return y;
+    s += row_dpp<0xB1>(s);
+    s += row_dpp<0x4E>(s);
+    s += row_dpp<0x141>(s);
+    s += row_dpp<0x140>(s);
+    return s;
+}
+
+// the sum over the wave, in every lane: the row sums, then the four of them through SGPRs
+__device__ __forceinline__ double wave_sum64(double s)
+{
+    s = row_sum16(s);
+    const int lo = __double2loint(s), hi = __double2hiint(s);
+    double r4[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        r4[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * q), __builtin_amdgcn_readlane(lo, 16 * q));
+    return (r4[0] + r4[1]) + (r4[2] + r4[3]);
+}
+
+// ---- the kernel value of EPI_KERNEL: k = v^eta and kp = eta v^(eta - 1) of a dot product v, with the lone-atom rule of
+// similarity.py:94-103 (rl / cl: the row's / the column's atom has no neighbour).  ieta: the integer exponent or -1.
+// v^(eta - 1): the reference's default exponent 4 without a loop, the other integers by multiplication, the rest by pow
+__device__ __forceinline__ double kernel_pm1(double v, int ieta, double eta)
+{
+    if (ieta == 4) return v * v * v;
+    if (ieta >= 1) {
+        double pm1 = 1.0;
+        for (int q = 1; q < ieta; q++) pm1 *= v;
+        return pm1;
+    }
+    return pow(v, eta - 1.0);
+}
+
+// Declares K and KP from the dot product V; IETA = g.ieta, P = the product's GemmParams.  (A macro: functions for the
+// selects spilled, see the head of this file.)
+// (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
+#define KERNEL_VALUE(K, KP, V, RL, CL, IETA, P)                                                                      \
+    const double pm1_ = kernel_pm1(V, IETA, (P).eta);                                                                \
+    const double eta_d_ = (IETA) >= 1 ? (double)(IETA) : (P).eta;                                                    \
+    const double K = (!(RL) && !(CL)) ? (((IETA) < 1 && (V) == 0.0) ? 0.0 : pm1_ * (V))                              \
+                                      : (((RL) && (CL)) ? 1.0 + (P).lone_m1 : 0.0);                                  \
+    const double KP = (!(RL) && !(CL)) ? eta_d_ * pm1_ : 0.0;
+
+// ---- tile entry.  With a host-built tile table (species-sorted operands: K_nm, K_mm, choli are block-diagonal) only the
+// working tiles are launched, each with its trimmed reduction range; the table is ordered so that list position p sits on
+// XCD p % 8 together with the other column tiles of the same row panel of A (one L2 fetches the panel once).  Without a
+// table the grid is dense, row tile fastest (same XCD property), and the reduction runs over 0 .. K.
+// Declares rt, ct, kbeg, kend of tile `bid` of the tile function it stands in, and LEAVES that function at a padding entry.
+// TABLE_ONLY: a form that is never launched without a table carries no dense branch.
+// (A macro: as a function — returning a struct, or filling references and returning "live" or "leave" — it moved the
+// registers of gemm_nt_kernel<EPI_ROWSQ, 1, 32> and <EPI_SUBLOWER, 2, 32>, see the head of this file.)
+#define TILE_ENTRY_OR_RETURN(TABLE_ONLY)                                                         \
+    int rt, ct, kbeg = 0, kend = p.K;                                                            \
+    if ((TABLE_ONLY) || g.p.tiles) {                                                             \
+        const int4 t = g.p.tiles[bid];                                                           \
+        rt = t.x & 0xffff; ct = t.y & 0xffff; kbeg = t.z; kend = t.w;                            \
+        if (kend <= kbeg) return;  /* padding entry */                                           \
+    } else {                                                                                     \
+        rt = bid % g.rows_pad;                                                                   \
+        ct = bid / g.rows_pad;                                                                   \
+        if (rt >= g.row_tiles) return;                                                           \
+    }
+
+// SGPR_STAMPS=1 (diagnostic): the s_memtime stamp taken once the tile entry has arrived (`dep` = rt + ct)
+__device__ __forceinline__ long long stamp_entry(const GemmArgs &g, int dep)
+{
+    long long t = 0;
+    if (g.stamps) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t) : "s"(dep));
+    return t;
+}
+
+// ... and the tile's record of eight words at `o` (tools/stamps_*.py): start, end of the main loop, now,
+// `klen_flags` (reduction length | second-problem flag << 20) | XCC_ID << 24 | HW_ID << 32, tile entry, end of the prologue
+__device__ __forceinline__ void stamp_record(long long *o, long long t_start, long long t_entry, long long t_pro, long long t_loop,
+                                             long long klen_flags)
+{
+    o[4] = t_entry; o[5] = t_pro;
+    const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));
+    o[0] = t_start; o[1] = t_loop; o[2] = (long long)__builtin_amdgcn_s_memtime();
+    o[3] = klen_flags | ((long long)xcc << 24) | ((long long)hw << 32);
+}
+
+// ---- EPI_KERNEL metadata, requested in front of the main loop so that the latency hides under it (all arrays are padded
+// to whole tiles by the allocator).  Species slot / neighbour count of a row (a lane has four per 16-row block) ...
+__device__ __forceinline__ void fetch_row_meta(const GemmArgs &g, const GemmParams &pk, int row, int &rs, int &rn)
+{
+    rs = g.row_slot[row];
+    rn = pk.row_nn ? pk.row_nn[row] : 1;
+}
+
+// ... and slot / count / weight of a column (one per 16-column block)
+__device__ __forceinline__ void fetch_col_meta(const GemmArgs &g, const GemmParams &pk, int col, int &cs, int &cn, double &mu)
+{
+    cs = g.col_slot[col];
+    cn = pk.col_nn ? pk.col_nn[col] : 1;
+    mu = pk.mu ? pk.mu[col] : 0.0;
 }
 
 // TM = MFMA row tiles per wave: 2 -> 64-row workgroup tiles, 1 -> 32-row tiles.
@@ -93,29 +196,15 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
     // 64-row tiles: two stages of A and B (68 KB, two workgroups per CU); 32-row tiles: three (76.5 KB, two per CU)
     // LDS rows: 32-deep stages are padded by two doubles (conflict-free fragment reads); 16-deep stages are XOR-swizzled
     // instead (16-B chunk c of row r sits at chunk c ^ ((r >> 1) & 7)): 36 KB for three stages, four workgroups per CU
-    constexpr bool SWZ = KD == 16;
-    constexpr int LDR = SWZ ? KD : KD + 2;
-    constexpr int NBUF = TM == 1 ? 3 : 2, ASZ = BMT * LDR, BSZ = BN * LDR;
+    using L = GemmLds<EPI, TM, KD>;
+    constexpr bool SWZ = L::SWZ;
+    constexpr int LDR = L::LDR, ASZ = L::ASZ, BSZ = L::BSZ;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1;
-    // Tile selection.  With a host-built tile table (species-sorted operands: K_nm, K_mm, choli are
-    // block-diagonal) only the working tiles are launched, each with its trimmed reduction range;
-    // the table is ordered so that list position p sits on XCD p % 8 together with the other
-    // column tiles of the same row panel of A (one L2 fetches the panel once).  Without a table
-    // the grid is dense, row tile fastest (same XCD property).
     const long long t_start = g.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    int rt, ct, kbeg = 0, kend = p.K;
-    if (g.p.tiles) {
-        const int4 t = g.p.tiles[bid];
-        rt = t.x & 0xffff; ct = t.y & 0xffff; kbeg = t.z; kend = t.w;
-        if (kend <= kbeg) return;  // padding entry
-    } else {
-        rt = bid % g.rows_pad;
-        ct = bid / g.rows_pad;
-        if (rt >= g.row_tiles) return;
-    }
-    long long t_entry = 0, t_pro = 0;
-    if (g.stamps) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_entry) : "s"(rt + ct));  // tile entry has arrived
+    TILE_ENTRY_OR_RETURN(false)
+    const long long t_entry = stamp_entry(g, rt + ct);
+    long long t_pro = 0;
     const int row0 = rt * BMT, col0 = ct * BN;
     const bool skip = (EPI == EPI_SUBLOWER && col0 > row0);  // symmetric update: lower tiles only
 
@@ -125,9 +214,6 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
 #pragma unroll
         for (int j = 0; j < 2; j++) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
 
-    // EPI_KERNEL: species slot / neighbour count per row, slot / count / weight per column of this
-    // lane's 8 rows and 2 columns, requested now so the latency hides under the main loop
-    // (all arrays are padded to whole tiles by the allocator).
     if constexpr (FUSED) {
         // A W or covloss tile consumes the K / Aw rows of its row panel: it waits until every K_nm tile of that panel —
         // `need` of them, earlier in this launch's tile list, hence dispatched before it — has counted itself in.  One lane
@@ -156,18 +242,10 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int row = row0 + wr * 16 * TM + tm * 16 + (lane >> 4) + 4 * r;
-                e_rs[tm][r] = g.row_slot[row];
-                e_rn[tm][r] = pk.row_nn ? pk.row_nn[row] : 1;
-            }
+            for (int r = 0; r < 4; r++) fetch_row_meta(g, pk, row0 + wr * 16 * TM + tm * 16 + (lane >> 4) + 4 * r, e_rs[tm][r], e_rn[tm][r]);
 #pragma unroll
-        for (int tn = 0; tn < 2; tn++) {
-            const int col = (FUSED && !third) ? 0 : col0 + wc * 32 + tn * 16 + (lane & 15);
-            e_cs[tn] = g.col_slot[col];
-            e_cn[tn] = pk.col_nn ? pk.col_nn[col] : 1;
-            e_mu[tn] = pk.mu ? pk.mu[col] : 0.0;
-        }
+        for (int tn = 0; tn < 2; tn++)
+            fetch_col_meta(g, pk, (FUSED && !third) ? 0 : col0 + wc * 32 + tn * 16 + (lane & 15), e_cs[tn], e_cn[tn], e_mu[tn]);
     }
 
     if constexpr (TM == 2) {
@@ -486,19 +564,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
                         // element: 24.7k cycles of epilogue, measured with s_memtime stamps)
                         const bool same = e_rs[tm][r] == e_cs[tn];
                         const bool rl = e_rn[tm][r] == 0, cl = e_cn[tn] == 0;
-                        double pm1;
-                        if (g.ieta == 4)  // the reference's default exponent: no loop
-                            pm1 = v * v * v;
-                        else if (g.ieta >= 1) {
-                            pm1 = 1.0;
-                            for (int q = 1; q < g.ieta; q++) pm1 *= v;
-                        } else
-                            pm1 = pow(v, p.eta - 1.0);
-                        const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                        // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
-                        double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
-                                                : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
-                        const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
+                        KERNEL_VALUE(k, kp, v, rl, cl, g.ieta, p)
                         if (same && row < p.M && col < p.N) {
                             if constexpr (FUSED) {
                                 // (write-through, device scope: read by other workgroups of this launch)
@@ -518,11 +584,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
             if (EPI == EPI_ROWSQ || ((EPI == EPI_WCOV || FUSED) && second)) {
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    double s = rsq[r];
-                    s += row_dpp<0xB1>(s);   // the same pairs, in the same order, as xor 1, 2, 4, 8
-                    s += row_dpp<0x4E>(s);
-                    s += row_dpp<0x141>(s);
-                    s += row_dpp<0x140>(s);
+                    const double s = row_sum16(rsq[r]);
                     const int row = row0 + wr * 16 * TM + tm * 16 + (lane >> 4) + 4 * r;
                     if ((lane & 15) == 0 && row < p.M && s != 0.0) {
                         if constexpr (EPI == EPI_WCOV) st_wt(&p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + wc], s);
@@ -534,18 +596,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
     }
     if (do_kern && g.Epart) {
         // one energy partial per WAVE (no workgroup barrier: the waves retire independently)
-        esum += row_dpp<0xB1>(esum);
-        esum += row_dpp<0x4E>(esum);
-        esum += row_dpp<0x141>(esum);
-        esum += row_dpp<0x140>(esum);  // every lane holds the sum of its row of 16; the four row sums through SGPRs
-        {
-            const int lo = __double2loint(esum), hi = __double2hiint(esum);
-            double r4[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                r4[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * q), __builtin_amdgcn_readlane(lo, 16 * q));
-            esum = (r4[0] + r4[1]) + (r4[2] + r4[3]);
-        }
+        esum = wave_sum64(esum);
         if (lane == 0) g.Epart[(size_t)(g.p.tiles ? bid : rt * g.col_tiles + ct) * 4 + wave] = esum;
     }
     if constexpr (FUSED) {
@@ -556,14 +607,8 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs &g, const int bid,
             if (tid == 0) __hip_atomic_fetch_add(g.panel_cnt + rt * 32, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (g.stamps && threadIdx.x == 0) {
-        long long *o = g.stamps + (size_t)bid * 8;
-        o[4] = t_entry; o[5] = t_pro;
-        // reduction length | second-problem flag << 20 | XCC_ID << 24 | HW_ID << 32
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));
-        o[0] = t_start; o[1] = t_loop; o[2] = (long long)__builtin_amdgcn_s_memtime();
-        o[3] = (long long)(kend - kbeg) | ((long long)second << 20) | ((long long)xcc << 24) | ((long long)hw << 32);
-    }
+    if (g.stamps && threadIdx.x == 0)
+        stamp_record(g.stamps + (size_t)bid * 8, t_start, t_entry, t_pro, t_loop, (long long)(kend - kbeg) | ((long long)second << 20));
 }
 
 
@@ -594,23 +639,15 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = HALF ? 0 : wave >> 2, wc = wave & 3;
     const long long t_start = g.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    int rt, ct, kbeg = 0, kend = p.K;
-    if (g.p.tiles) {
-        const int4 t = g.p.tiles[bid];
-        rt = t.x & 0xffff; ct = t.y & 0xffff; kbeg = t.z; kend = t.w;
-        if (kend <= kbeg) return;  // padding entry
-    } else {
-        rt = bid % g.rows_pad;
-        ct = bid / g.rows_pad;
-        if (rt >= g.row_tiles) return;
-    }
-    long long t_entry = 0, t_pro = 0;
-    if (g.stamps) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_entry) : "s"(rt + ct));
+    TILE_ENTRY_OR_RETURN(false)
+    const long long t_entry = stamp_entry(g, rt + ct);
+    long long t_pro = 0;
     const int row0 = rt * BMT, col0 = ct * BN;
     v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
     int e_rs[4], e_rn[4], e_cs = 0, e_cn = 1;
     double e_mu = 0.0;
     if (EPI == EPI_KERNEL) {
+        // (this form's own text: through fetch_row_meta / fetch_col_meta its two EPI_KERNEL kernels changed their registers)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int row = row0 + wr * 16 + (lane >> 4) + 4 * r;
@@ -718,19 +755,7 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
             } else if (EPI == EPI_KERNEL) {
                 const bool same = e_rs[r] == e_cs;
                 const bool rl = e_rn[r] == 0, cl = e_cn == 0;
-                double pm1;
-                if (g.ieta == 4)
-                    pm1 = v * v * v;
-                else if (g.ieta >= 1) {
-                    pm1 = 1.0;
-                    for (int q = 1; q < g.ieta; q++) pm1 *= v;
-                } else
-                    pm1 = pow(v, p.eta - 1.0);
-                const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
-                const double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
-                                              : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
-                const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
+                KERNEL_VALUE(k, kp, v, rl, cl, g.ieta, p)
                 if (same && row < p.M && col < p.N) {
                     // (K and Aw are read by the next launch only: write-through, sgpr_internal.h)
                     st_wt(&p.C[(size_t)row * p.ldc + col], k);
@@ -758,11 +783,7 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
                     for (int r = 0; r < 4; r++) {
                         // (rsq += v * v of the other forms is a fused multiply-add: block 0 squared, block 1 fused onto it)
                         const double v1 = xs[((wc >> 1) * 64 + lane) * 4 + r];
-                        double sq = fma(v1, v1, rsq[r] * rsq[r]);
-                        sq += row_dpp<0xB1>(sq);
-                        sq += row_dpp<0x4E>(sq);
-                        sq += row_dpp<0x141>(sq);
-                        sq += row_dpp<0x140>(sq);
+                        const double sq = row_sum16(fma(v1, v1, rsq[r] * rsq[r]));
                         const int row = row0 + (lane >> 4) + 4 * r;
                         if ((lane & 15) == 0 && row < p.M && sq != 0.0) p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + (wc >> 1)] = sq;
                     }
@@ -771,31 +792,15 @@ __device__ __forceinline__ void gemm_tile_body8(const GemmArgs &g, const int bid
         }
     }
     if (EPI == EPI_KERNEL && g.Epart) {
-        esum += row_dpp<0xB1>(esum);
-        esum += row_dpp<0x4E>(esum);
-        esum += row_dpp<0x141>(esum);
-        esum += row_dpp<0x140>(esum);
-        {
-            const int lo = __double2loint(esum), hi = __double2hiint(esum);
-            double r4[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                r4[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * q), __builtin_amdgcn_readlane(lo, 16 * q));
-            esum = (r4[0] + r4[1]) + (r4[2] + r4[3]);
-        }
+        esum = wave_sum64(esum);
         if (lane == 0) {
             double *ep = g.Epart + (size_t)(g.p.tiles ? bid : rt * g.col_tiles + ct) * 8;
             st_wt(&ep[wave], esum);
             if constexpr (HALF) st_wt(&ep[wave + 4], 0.0);   // (the reducer sums eight partials per tile)
         }
     }
-    if (g.stamps && threadIdx.x == 0) {
-        long long *o = g.stamps + (size_t)bid * 8;
-        o[4] = t_entry; o[5] = t_pro;
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));
-        o[0] = t_start; o[1] = t_loop; o[2] = (long long)__builtin_amdgcn_s_memtime();
-        o[3] = (long long)(kend - kbeg) | ((long long)xcc << 24) | ((long long)hw << 32);
-    }
+    if (g.stamps && threadIdx.x == 0)   // (this form's record carries no second-problem flag)
+        stamp_record(g.stamps + (size_t)bid * 8, t_start, t_entry, t_pro, t_loop, (long long)(kend - kbeg));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -820,14 +825,9 @@ __device__ __forceinline__ void gemm_tile_body8r64(const GemmArgs &g, const int 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wr = wave >> 1, wc = wave & 1;
     const long long t_start = g.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    int rt, ct, kbeg = 0, kend = p.K;
-    {
-        const int4 t = g.p.tiles[bid];
-        rt = t.x & 0xffff; ct = t.y & 0xffff; kbeg = t.z; kend = t.w;
-        if (kend <= kbeg) return;  // padding entry
-    }
-    long long t_entry = 0, t_pro = 0;
-    if (g.stamps) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_entry) : "s"(rt + ct));
+    TILE_ENTRY_OR_RETURN(true)   // (always launched with a table)
+    const long long t_entry = stamp_entry(g, rt + ct);
+    long long t_pro = 0;
     const int row0 = rt * 64, col0 = ct * BN;
     v4d acc[2];
     acc[0] = acc[1] = (v4d){0.0, 0.0, 0.0, 0.0};
@@ -835,18 +835,9 @@ __device__ __forceinline__ void gemm_tile_body8r64(const GemmArgs &g, const int 
     double e_mu[2];
     if (EPI == EPI_KERNEL) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int row = row0 + wr * 16 + (lane >> 4) + 4 * r;
-            e_rs[r] = g.row_slot[row];
-            e_rn[r] = p.row_nn ? p.row_nn[row] : 1;
-        }
+        for (int r = 0; r < 4; r++) fetch_row_meta(g, p, row0 + wr * 16 + (lane >> 4) + 4 * r, e_rs[r], e_rn[r]);
 #pragma unroll
-        for (int tn = 0; tn < 2; tn++) {
-            const int col = col0 + wc * 32 + tn * 16 + (lane & 15);
-            e_cs[tn] = g.col_slot[col];
-            e_cn[tn] = p.col_nn ? p.col_nn[col] : 1;
-            e_mu[tn] = p.mu ? p.mu[col] : 0.0;
-        }
+        for (int tn = 0; tn < 2; tn++) fetch_col_meta(g, p, col0 + wc * 32 + tn * 16 + (lane & 15), e_cs[tn], e_cn[tn], e_mu[tn]);
     }
     // global side: 64 rows x 16 doubles of A and of B per stage, one 16-byte chunk of each per thread
     const int lr = tid >> 3, lc = tid & 7;
@@ -957,19 +948,7 @@ __device__ __forceinline__ void gemm_tile_body8r64(const GemmArgs &g, const int 
                 } else if (EPI == EPI_KERNEL) {
                     const bool same = e_rs[r] == e_cs[tn];
                     const bool rl = e_rn[r] == 0, cl = e_cn[tn] == 0;
-                    double pm1;
-                    if (g.ieta == 4)
-                        pm1 = v * v * v;
-                    else if (g.ieta >= 1) {
-                        pm1 = 1.0;
-                        for (int q = 1; q < g.ieta; q++) pm1 *= v;
-                    } else
-                        pm1 = pow(v, p.eta - 1.0);
-                    const double eta_d = g.ieta >= 1 ? (double)g.ieta : p.eta;
-                    // (pow branch, exponent below 1: pm1 = +inf at v = 0, an orthogonal pair; k = 0^eta = 0, kp stays unbounded)
-                    const double k = (!rl && !cl) ? ((g.ieta < 1 && v == 0.0) ? 0.0 : pm1 * v)
-                                                  : ((rl && cl) ? 1.0 + p.lone_m1 : 0.0);  // similarity.py:94-103
-                    const double kp = (!rl && !cl) ? eta_d * pm1 : 0.0;
+                    KERNEL_VALUE(k, kp, v, rl, cl, g.ieta, p)
                     if (same && row < p.M && col < p.N) {
                         p.C[(size_t)row * p.ldc + col] = k;
                         if (p.Aw) p.Aw[(size_t)row * p.ldc + col] = e_mu[tn] * kp;
@@ -983,36 +962,16 @@ __device__ __forceinline__ void gemm_tile_body8r64(const GemmArgs &g, const int 
         if (EPI == EPI_ROWSQ || (EPI == EPI_WCOV && second)) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                double sq = rsq[r];
-                sq += row_dpp<0xB1>(sq);
-                sq += row_dpp<0x4E>(sq);
-                sq += row_dpp<0x141>(sq);
-                sq += row_dpp<0x140>(sq);
+                const double sq = row_sum16(rsq[r]);
                 const int row = row0 + wr * 16 + (lane >> 4) + 4 * r;
                 if ((lane & 15) == 0 && row < p.M && sq != 0.0) p.rowsq[(size_t)row * p.rowsq_ld + 2 * ct + wc] = sq;
             }
         }
     }
     if (EPI == EPI_KERNEL && g.Epart) {
-        esum += row_dpp<0xB1>(esum);
-        esum += row_dpp<0x4E>(esum);
-        esum += row_dpp<0x141>(esum);
-        esum += row_dpp<0x140>(esum);
-        {
-            const int lo = __double2loint(esum), hi = __double2hiint(esum);
-            double r4[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                r4[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * q), __builtin_amdgcn_readlane(lo, 16 * q));
-            esum = (r4[0] + r4[1]) + (r4[2] + r4[3]);
-        }
+        esum = wave_sum64(esum);
         if (lane == 0) g.Epart[(size_t)bid * 8 + wave] = esum;
     }
-    if (g.stamps && threadIdx.x == 0) {
-        long long *o = g.stamps + (size_t)bid * 8;
-        o[4] = t_entry; o[5] = t_pro;
-        const unsigned hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));
-        o[0] = t_start; o[1] = t_loop; o[2] = (long long)__builtin_amdgcn_s_memtime();
-        o[3] = (long long)(kend - kbeg) | ((long long)second << 20) | ((long long)xcc << 24) | ((long long)hw << 32);
-    }
+    if (g.stamps && threadIdx.x == 0)
+        stamp_record(g.stamps + (size_t)bid * 8, t_start, t_entry, t_pro, t_loop, (long long)(kend - kbeg) | ((long long)second << 20));
 }

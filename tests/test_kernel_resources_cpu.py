@@ -26,6 +26,12 @@ LIMITS = {
     r"tsqr_leaf_wave_kernel": (0, 128),
     r"gemm_nt_kernel8r64x3ILi[0-4]E": (0, 80),      # (three workgroups of 512 per CU: six waves per SIMD)
     r"gemm_nt_kernel4hILi[0-4]E": (0, 128),
+    # every kernel of gemm.o: no scratch, and the registers its __launch_bounds__ leave a wave (512 per SIMD lane, over the
+    # waves of that SIMD: threads / 64 x workgroups per CU / 4) — from the bounds, not from a build
+    r"gemm_nt_kernelILi[0-5]ELi1ELi16E": (0, 128),       # (256, 4)
+    r"gemm_nt_kernelILi[0-4]ELi[12]ELi32E": (0, 256),    # (256, 2)
+    r"gemm_nt_kernel8ILi[01]E": (0, 128),                # (512, 2)
+    r"gemm_nt_kernel8r64ILi[0-4]E": (0, 128),            # (512, 2); gemm_nt_kernel8r64x3 (512, 6) and gemm_nt_kernel4h above
 }
 
 
@@ -66,3 +72,5 @@ def test_hot_kernels_do_not_spill(tmp_path):
                 assert md["private_segment_fixed_size"] <= scratch, (name, md)
                 assert md.get("vgpr_count", 0) <= vgpr, (name, md)
     assert seen >= 8, sorted(meta)[:20]
+    gemm = [name for name in meta if "gemm_nt_kernel" in name]
+    assert all(any(re.search(pat, name) for pat in LIMITS) for name in gemm), sorted(gemm)

@@ -11,14 +11,16 @@ with tempfile.TemporaryDirectory() as tmp:
     subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
     notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-cur, rows = None, {}
+cur, key, recs = None, None, []
 for line in notes.splitlines():
-    m = re.match(r"\s*\.name:\s+(\S+)", line)
-    if m:
-        cur = m.group(1); rows.setdefault(cur, {})
-    m = re.match(r"\s*\.(private_segment_fixed_size|vgpr_count|sgpr_count|group_segment_fixed_size|agpr_count):\s+(\d+)", line)
-    if m and cur:
-        rows[cur][m.group(1)] = int(m.group(2))
+    m = re.match(r"(\s*)- \.(agpr_count|args):", line)
+    if m and (cur is None or len(m.group(1)) + 2 == key):  # a kernel's record opens: its keys are sorted, .name sits in the middle
+        cur, key = {}, len(m.group(1)) + 2
+        recs.append(cur)
+    m = re.match(r"([\s-]*)\.(name|private_segment_fixed_size|vgpr_count|sgpr_count|group_segment_fixed_size|agpr_count):\s+(\S+)", line)
+    if m and cur is not None and len(m.group(1)) == key:   # (deeper ones belong to the arguments)
+        cur[m.group(2)] = m.group(3) if m.group(2) == "name" else int(m.group(3))
+rows = {r["name"]: r for r in recs if "name" in r}
 for k, v in sorted(rows.items()):
     if pat in k and v:
         print(f"{k[:70]:70s} vgpr={v.get('vgpr_count')} agpr={v.get('agpr_count')} sgpr={v.get('sgpr_count')} scratch={v.get('private_segment_fixed_size')} lds={v.get('group_segment_fixed_size')}")
