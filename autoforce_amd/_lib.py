@@ -80,6 +80,7 @@ SIGNATURES = {
     "sgpr_md_cells": (C.c_int, [_vp, _i64, C.c_int, _vp]),
     "sgpr_md_relax": (C.c_int, [_vp, _dbl, _vp, C.c_int, _vp]),
     "sgpr_md_relax_reset": (C.c_int, [_vp]),
+    "sgpr_md_relax_lbfgs": (C.c_int, [_vp, C.c_int, _dbl, _dbl, _dbl]),
     "sgpr_md_neb": (C.c_int, [_vp, C.c_int, _vp, _dbl, _dbl, C.c_int, _vp]),
     "sgpr_md_neb_reset": (C.c_int, [_vp]),
     "sgpr_md_neb_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),

@@ -759,7 +759,7 @@ class ActiveCalculator(Calculator):
             self._md_attached_done(eng, attached)
 
     def run_relax(self, atoms, fmax=0.01, steps=100000, cell=False, mask=None, clear_hist=False, chunk=256, on_frame=None, interval=1,
-                  **fire):
+                  optimizer="FIRE", **fire):
         """FIRE relaxation of atoms.positions — with cell=True also of atoms.cell, through the coordinates of
         ase.constraints.UnitCellFilter(atoms, mask=mask) — as theforce/cl/relax.py minimises around this calculator, but with
         the state in device memory between model updates: run_md's loop with the optimizer in the place of the integrator
@@ -781,8 +781,14 @@ class ActiveCalculator(Calculator):
         SGPRModel.relax_begin(fixed=); the host loop through the atoms' own set_positions / get_forces): the optimizer sees F = 0
         on a held component and convergence is judged on the free ones — self.results["forces"] stay the model's own —; a held
         coordinate keeps its bits at constant cell, and with cell=True keeps its undeformed coordinate while x follows the cell,
-        as FixAtoms inside UnitCellFilter.  Any other constraint kind: NotImplementedError."""
+        as FixAtoms inside UnitCellFilter.  Any other constraint kind: NotImplementedError.
+        optimizer = "LBFGS": L-BFGS without line search (ase/optimize/lbfgs.py; SGPRModel.relax_begin(optimizer="LBFGS"),
+        md_lbfgs.inc) in the place of FIRE, `fire` then being its keywords memory, maxstep, alpha, damping; clear_hist empties
+        the history through relax_reset; everything else as above.  Its host loop is workloads.lbfgs_relax — the twin of the
+        device kernels — around calculate()."""
         from .cl.relax import FIRE, UnitCellFilter, force_max
+        if optimizer not in ("FIRE", "LBFGS"):
+            raise ValueError(f"run_relax: optimizer = 'FIRE' or 'LBFGS', not {optimizer!r}")
         fx = held(self.constraint_mask(atoms))
         hold = {} if fx is None else dict(fixed=fx)
 
@@ -795,13 +801,23 @@ class ActiveCalculator(Calculator):
         if seeded:
             first_on_host(self, atoms)
             if not device_ok():
-                target = UnitCellFilter(atoms, mask=mask) if cell else atoms
-                opt = FIRE(target, **fire)
-
                 def report(n, last=False):
                     if on_frame is not None and (n % interval == 0 or last):
                         on_frame(n, dict(positions=np.array(atoms.positions), cell=np.array(getattr(atoms.cell, "array", atoms.cell), float),
                                          energy=float(self.results["energy"]), forces=np.array(self.results["forces"])))
+                if optimizer == "LBFGS":
+                    from .workloads import lbfgs_relax
+                    numbers, pos, cell0, pbc = self._system(atoms)
+                    o = None
+                    for o in lbfgs_relax(self, numbers, pos, cell0, pbc, steps, fmax, cell_relax=cell, mask=mask,
+                                         species=getattr(self.engine, "species", None), fixed=fx,
+                                         reset_if=(lambda: bool(self.updated)) if clear_hist else None, **fire):
+                        put_state(atoms, o, cell)
+                        report(o["n"], last=o["converged"] or o["n"] == steps)
+                    atoms.calc = self
+                    return dict(converged=o["converged"], steps=o["n"], evaluations=o["n"] + 1)
+                target = UnitCellFilter(atoms, mask=mask) if cell else atoms
+                opt = FIRE(target, **fire)
                 forces, n = target.get_forces(), 0
                 while force_max(forces) >= fmax and n < steps:
                     report(n)
@@ -814,7 +830,7 @@ class ActiveCalculator(Calculator):
                 return dict(converged=force_max(forces) < fmax, steps=n, evaluations=n + 1)
         numbers, pos, cell0, pbc = self._system(atoms)
         eng = self.engine
-        eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **hold, **fire)
+        eng.relax_begin(numbers, pos, cell0, pbc, fmax, cell_relax=cell, mask=mask, **hold, **fire, **({} if optimizer == "FIRE" else dict(optimizer=optimizer)))
         done, converged, cap = 0, False, None
         rec, reported = on_frame is not None, -1
         if rec:   # (positions and the packed results; a batch of at most RECORD_BYTES of them)

@@ -12,9 +12,13 @@ and is absent from the build image: without it two of its optimizers are restate
 eigen-decomposition with |omega|, the longest atomic step scaled down to 0.2 A) and `FIRE` — and so is the cell filter of
 `cell = True` (ase/constraints.py::UnitCellFilter with a mask, ASE 3.22, LGPL: `UnitCellFilter` below) — through this driver
 with `algo = 'FIRE'`; `cell = True` with `'BFGS'` still asks for ASE.
-  Only `FIRE` runs on the device (ActiveCalculator.run_relax: the state stays in HBM between model updates): it is per-atom
-arithmetic and three global sums.  `BFGS`, the reference's default and therefore the default here, keeps a dense 3N x 3N
-Hessian and takes its eigen-decomposition every step — 12288^2 at 4096 atoms — and stays on the host, for small systems.
+  `FIRE` and `LBFGS` run on the device (ActiveCalculator.run_relax: the state stays in HBM between model updates): FIRE is
+per-atom arithmetic and three global sums; L-BFGS without line search (ase/optimize/lbfgs.py, restated in md_lbfgs.inc and
+workloads.lbfgs_relax) is two passes over a history of at most 128 pairs and a small solve.  `LBFGS` is a device-loop optimizer
+only — BUILT_IN stays BFGS and FIRE: with a calculator that cannot hand the loop over, and without ASE, the driver answers as for
+any other ase.optimize name; with ASE installed and a device-capable calculator it takes the device loop rather than
+ase.optimize.LBFGS, exactly as FIRE does.  It has no curvature test: set clear_hist, so that no pair spans a model update.
+`BFGS`, the reference's default and therefore the default here, keeps a dense 3N x 3N Hessian and takes its eigen-decomposition every step — 12288^2 at 4096 atoms — and stays on the host, for small systems.
 Structures and the trajectory are extended XYZ."""
 import argparse
 
@@ -203,11 +207,13 @@ class _Runner:
 
 
 class _DeviceRunner:
-    """The same surface around ActiveCalculator.run_relax: FIRE with the state in device memory between model updates.  Every
-    run starts the optimizer afresh (relax_begin); clear_hist re-initialises it behind every model update inside a run."""
+    """The same surface around ActiveCalculator.run_relax: FIRE or L-BFGS (`algo`) with the state in device memory between model
+    updates.  Every run starts the optimizer afresh (relax_begin); clear_hist re-initialises it behind every model update inside
+    a run."""
 
-    def __init__(self, atoms, calc, cell, mask, trajectory, master, clear_hist, max_steps=100000):
+    def __init__(self, atoms, calc, cell, mask, trajectory, master, clear_hist, max_steps=100000, algo="FIRE"):
         self.atoms, self.calc, self.cell, self.mask, self.master, self.clear_hist, self.max_steps = atoms, calc, cell, mask, master, clear_hist, max_steps
+        self.algo = algo
         self.out = open(trajectory, "w") if (trajectory and master) else None
         self.nsteps = 0
 
@@ -222,13 +228,13 @@ class _DeviceRunner:
         # (a frame per evaluation, as _Runner writes them: from the device loop's frame record, the run is not cut for it; the last
         # one is the final structure with the results the calculator then answers with)
         res = self.calc.run_relax(self.atoms, fmax=fmax, steps=self.max_steps, cell=self.cell, mask=self.mask, clear_hist=self.clear_hist,
-                                  on_frame=self._write if self.out is not None else None)
+                                  on_frame=self._write if self.out is not None else None, **({} if self.algo == "FIRE" else dict(optimizer=self.algo)))
         self.nsteps += res["steps"]
         a, r = self.atoms, self.calc.results
         if self.out is not None:
             self.out.flush()
         if self.master:
-            print(f"FIRE (device): {self.nsteps:4d}  energy {float(r['energy']):.6f}  fmax {force_max(r['forces']):.4f}")
+            print(f"{self.algo} (device): {self.nsteps:4d}  energy {float(r['energy']):.6f}  fmax {force_max(r['forces']):.4f}")
         return res["converged"]
 
     def irun(self, fmax):
@@ -238,12 +244,14 @@ class _DeviceRunner:
 
 def _optimizer(atoms, algo, cell, mask, trajectory, master, clear_hist=False):
     calc = atoms.calc
-    # FIRE is per-atom arithmetic and three global sums: it runs inside the device loop where the calculator can hand the loop
-    # over (BFGS, the default, needs a dense Hessian's eigen-decomposition per step and stays on the host)
+    # FIRE is per-atom arithmetic and three global sums, L-BFGS two passes over its history and a memory x memory solve: they run
+    # inside the device loop where the calculator can hand the loop over (BFGS, the default, needs a dense Hessian's
+    # eigen-decomposition per step and stays on the host).  LBFGS is a device-loop optimizer only: without such a calculator
+    # (and without ASE) the driver answers as it does for any name outside BUILT_IN
     # (atoms.constraints: FixAtoms and FixCartesian are held inside the device loop; any other kind stays with the host optimizer)
-    if algo == "FIRE" and hasattr(calc, "run_relax") and hasattr(calc, "md_on_device_ok") and (calc.md_on_device_ok() or calc._needs_seed()) \
+    if algo in ("FIRE", "LBFGS") and hasattr(calc, "run_relax") and hasattr(calc, "md_on_device_ok") and (calc.md_on_device_ok() or calc._needs_seed()) \
             and all(type(c).__name__ in ("FixAtoms", "FixCartesian") for c in (getattr(atoms, "constraints", None) or ())):
-        return _DeviceRunner(atoms, calc, cell, mask, trajectory, master, clear_hist)
+        return _DeviceRunner(atoms, calc, cell, mask, trajectory, master, clear_hist, algo=algo)
     try:
         from ase import optimize
         from ase.constraints import UnitCellFilter as AseUnitCellFilter
@@ -264,7 +272,7 @@ def relax(atoms, fmax=0.01, cell=False, mask=None, algo="BFGS", trajectory="rela
           calc=None, seed=None):
     """The keywords of theforce/cl/relax.py::relax (same names and defaults; the trajectory is extended XYZ unless ASE
     writes it).  Returns the number of exact (teacher) calculations the run asked for.
-      algo = "FIRE" with a calculator whose md_on_device_ok() holds: the minimisation and every re-run of the confirm loop go
+      algo = "FIRE" or "LBFGS" with a calculator whose md_on_device_ok() holds: the minimisation and every re-run of the confirm loop go
     through ActiveCalculator.run_relax — the state stays on the device between model updates, cell = True included.  The default
     stays the reference's "BFGS", which does not scale (a dense 3N x 3N Hessian and its eigen-decomposition every step) and
     runs on the host only."""

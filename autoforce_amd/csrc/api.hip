@@ -245,6 +245,9 @@ struct MdRun {
     } npt;
     // FIRE relaxation (sgpr_md_relax, md_relax.inc): the run is a minimisation, not dynamics — rings of RLX_RING slots
     struct Relax { bool on = false, started = false; RelaxParams par = {}; } relax;   // (par: a band's FIRE too, cell = 0)
+    // L-BFGS in the place of FIRE (sgpr_md_relax_lbfgs, md_lbfgs.inc): ASE's keywords, H0 = 1 / alpha, and the evaluation the
+    // history starts at (the start, or the last sgpr_md_relax_reset)
+    struct Lbfgs { bool on = false; int mem = 0; double maxstep = 0.0, h0 = 0.0, damping = 0.0; long long base = 0; } lbfgs;
     // held components (sgpr_md_fix): the mask in sorted atom order, here and in MdState::fixed; n = 0: nothing is held and every
     // launch is the one of a run without a mask
     struct Fix { int n = 0; std::vector<unsigned char> sorted; } fix;
@@ -324,6 +327,12 @@ struct MdState {
         DevBuf<double> ref;        // [N][3] positions referred to the first cell (r = x D^-T), sorted order; their velocity is V's slot 0
         DevBuf<double> cells;      // [RLX_RING][RLX_CELL] cell and deformation gradient by evaluation index % RLX_RING
     } relax;
+    // the history of L-BFGS by evaluation index (LbfgsBuf, md_lbfgs.inc, has the shapes); `hist` is S | Y, the 2 memory (3N + 9)
+    // doubles that sgpr_md_relax_lbfgs answers for; given back by sgpr_md_end
+    struct LbfgsBufs {
+        DevBuf<double> hist, work;
+        bool held() const { return hist.p != nullptr; }
+    } lbfgs;
     struct { DevBuf<unsigned char> mask; } fixed;   // [N][3] (the group of sgpr_md_fix: fix() below is what the launches take)
     // accumulated force jumps in a ring beside X (sorted order, slot = evaluation index % ring), accumulated stress jumps of a
     // moving-cell run in a ring of four (evaluation index & 3), the run's own permutation on the device for the pushes
@@ -1251,6 +1260,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 
 #include "md_npt.inc"
 #include "md_relax.inc"
+#include "md_lbfgs.inc"
 #include "md_bcm.inc"
 #include "md_neb.inc"
 #include "md_record.inc"

@@ -1,6 +1,6 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
-// sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell), _fix (held components),
+// sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
 // _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _committee (the Bayesian committee), _neb
 // (the nudged elastic band).  sgpr_md_run drives dynamics itself and hands a relaxation, a committee and a band to md_relax_run,
 // md_committee_run and md_neb_run; the four share the look-ahead driver and the frame of a call (MdCall).  The kernels are in
@@ -412,6 +412,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     HIPCHK(hipMemcpy(m.relax.state.p, s, sizeof(s), hipMemcpyHostToDevice));
     m.run.relax.par = p;
     m.run.relax.on = true; m.run.relax.started = false; m.run.ring = RLX_RING;
+    m.run.lbfgs = MdRun::Lbfgs();   // (FIRE, until sgpr_md_relax_lbfgs says otherwise)
     m.run.npt.cells.clear(); m.run.npt.cells_first = 0;
     return md_relax_init_state(h);
 }
@@ -424,7 +425,68 @@ extern "C" int sgpr_md_relax_reset(sgpr_model *h)
     if (!m.active || !m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_relax_reset: call sgpr_md_begin and sgpr_md_relax first");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
+    m.run.lbfgs.base = m.run.t;   // (L-BFGS: the history is indexed by evaluation — the next one is the first of an empty one)
     return md_relax_init_state(h);
+}
+
+// ---- L-BFGS in the place of FIRE (sgpr_md_relax_lbfgs; md_lbfgs.inc has the scheme, workloads.lbfgs_relax is the host twin) ----
+// Everything but the history S | Y in one allocation, carved by md_lbfgs_buf in the order of LbfgsBuf's members.
+static size_t md_lbfgs_work_len(int N, int mem)
+{
+    const size_t R3 = (size_t)3 * N + 9, B = (size_t)(N + 255) / 256, B3 = (size_t)(N + 3 + 63) / 64, M = (size_t)mem;
+    return 3 * R3 + 3 * M * M + 2 * M + 4 * M * B + 3 * B + 3 * M + B3 + 18;
+}
+
+static LbfgsBuf md_lbfgs_buf(const MdState &m)
+{
+    const int N = m.run.N;
+    const size_t R3 = (size_t)3 * N + 9, B = (size_t)(N + 255) / 256, B3 = (size_t)(N + 3 + 63) / 64, M = (size_t)m.run.lbfgs.mem;
+    LbfgsBuf b;
+    b.S = m.lbfgs.hist.p; b.Y = b.S + M * R3;
+    double *w = m.lbfgs.work.p;
+    b.G = w; w += 2 * R3;
+    b.dir = w; w += R3;
+    b.Rinv = w; w += M * M;
+    b.RinvT = w; w += M * M;
+    b.YY = w; w += M * M;
+    b.Dg = w; w += M;
+    b.valid = w; w += M;
+    b.part = w; w += 4 * M * B;
+    b.pgg = w; w += B;
+    b.pgmx = w; w += B;
+    b.pbmx = w; w += B;
+    b.coef = w; w += 3 * M;
+    b.pmax = w; w += B3;
+    b.xc = w;
+    return b;
+}
+
+// L-BFGS without line search in the place of FIRE for the relaxation set up by sgpr_md_relax (whose fmax, cell and mask hold; its
+// FIRE keywords are not used), before the first sgpr_md_run: ase/optimize/lbfgs.py on the same generalised coordinates.
+// memory: pairs kept at most, 1 ... 128; maxstep, alpha (H0 = 1 / alpha), damping: ASE's keywords (its defaults: 100, 0.2, 70,
+// 1).  The history, 2 memory (3N + 9) doubles, is held until sgpr_md_end; sgpr_md_relax_reset empties it.  The scalar columns
+// 12..15 of a row: largest |G_row|^2, p.G, the scale applied to the step, valid pairs in use.
+extern "C" int sgpr_md_relax_lbfgs(sgpr_model *h, int memory, double maxstep, double alpha, double damping)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_relax_lbfgs: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_relax_lbfgs: call sgpr_md_begin and sgpr_md_relax first");
+    if (m.run.t != 0 || m.run.relax.started) return fail(SGPR_E_INVALID, "sgpr_md_relax_lbfgs: the run has started");
+    if (memory < 1 || memory > 128) return fail(SGPR_E_INVALID, "sgpr_md_relax_lbfgs: 1 <= memory <= 128");
+    if (!(maxstep > 0.0 && alpha > 0.0 && damping > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax_lbfgs: maxstep, alpha, damping > 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.run.N;
+    if (m.lbfgs.hist.alloc((size_t)2 * memory * ((size_t)3 * N + 9)))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_relax_lbfgs: no device memory for a history of %d pairs (%zu doubles)", memory,
+                    (size_t)2 * memory * ((size_t)3 * N + 9));
+    if (m.lbfgs.work.alloc(md_lbfgs_work_len(N, memory))) return fail(SGPR_E_NODEVICE, "sgpr_md_relax_lbfgs: device allocation failed");
+    m.run.lbfgs = MdRun::Lbfgs();
+    m.run.lbfgs.on = true; m.run.lbfgs.mem = memory; m.run.lbfgs.maxstep = maxstep; m.run.lbfgs.h0 = 1.0 / alpha; m.run.lbfgs.damping = damping;
+    double xc[18];
+    for (int k = 0; k < 18; k++) xc[k] = ((k % 9) % 4 == 0) ? m.run.relax.par.cf : 0.0;   // (c D at the start, both slots)
+    HIPCHK(hipMemcpy(md_lbfgs_buf(m).xc, xc, sizeof(xc), hipMemcpyHostToDevice));
+    return SGPR_OK;
 }
 
 // ---- the look-ahead driver of the run functions (sgpr_md_run and md_relax_run, its form for a relaxation) ----
@@ -742,6 +804,29 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
         if (re) return re;
         h->lists_valid = true;
         const bool stay = final_eval && j == nevals - 1;
+        if (m.run.lbfgs.on) {   // (sgpr_md_relax_lbfgs: md_lbfgs.inc's four kernels in the place of FIRE's two)
+            const MdRun::Lbfgs &lb = m.run.lbfgs;
+            const RelaxParams &rp = m.run.relax.par;
+            const LbfgsBuf b = md_lbfgs_buf(m);
+            const long long n = m.run.t + j;
+            const int cnt = (int)std::min<long long>(n - lb.base, lb.mem), B = (N + 255) / 256, NR = N + (rp.cell ? 3 : 0), B3 = (NR + 63) / 64;
+            const int stp = (int)(step0 + j);
+            const bool fx = m.run.fix.n != 0;
+            hipLaunchKernelGGL(fx ? md_lbfgs_dots_kernel<true> : md_lbfgs_dots_kernel<false>, dim3(B, std::max(cnt, 1)), dim3(256), 0, st, N, rp.cell, lb.mem, b, n,
+                               cnt, (const double *)packed, (const int *)h->d_perm.p, (const double *)cell_of(n), (const int *)m.halt.p, stp, m.fix());
+            hipLaunchKernelGGL(md_lbfgs_solve_kernel, dim3(1), dim3(256), 0, st, N, rp, lb.mem, lb.h0, b, n, cnt, B, (const double *)packed,
+                               (const double *)cell_of(n), gate, m.halt.p, m.halt_host.dev, stp, m.scal_d.p + (size_t)SGPR_MD_SCAL * j,
+                               m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j, m.mark.dev + j, stay ? 1 : 0);
+            if (!stay) {
+                hipLaunchKernelGGL(fx ? md_lbfgs_dir_kernel<true> : md_lbfgs_dir_kernel<false>, dim3(B3), dim3(64), 0, st, N, NR, lb.mem, lb.h0, b, n, cnt,
+                                   (const int *)m.halt.p, stp, m.fix());
+                hipLaunchKernelGGL(fx ? md_lbfgs_move_kernel<true> : md_lbfgs_move_kernel<false>, dim3((NR + 255) / 256), dim3(256), 0, st, N, rp, lb.mem,
+                                   lb.maxstep, lb.damping, b, n, B3, m.relax.ref.p, m.X.p + (size_t)3 * N * sn, cell_of(n + 1), (const int *)m.halt.p, stp,
+                                   m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.fix());
+            }
+            if (m.run.rec.every && n % m.run.rec.every == 0) md_record_frame(h, j, stp, st);
+            return SGPR_OK;
+        }
         // (held components, sgpr_md_fix: the FIX forms; without a mask the kernels of a run without one)
         hipLaunchKernelGGL(m.run.fix.n ? md_fire_kernel<true> : md_fire_kernel<false>, dim3(1), dim3(256), 0, st, N, m.run.relax.par, m.relax.state.p,
                            (const double *)packed, (const int *)h->d_perm.p,
@@ -1870,6 +1955,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.meta = MdState::MetaBufs();
+    }
+    if (m.lbfgs.held()) {   // (and so is the history of L-BFGS)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.lbfgs = MdState::LbfgsBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

@@ -62,6 +62,57 @@ __host__ __device__ inline double rlx_det(const double *c)
     return c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
 }
 
+// ---- what the optimizers of a relaxation share: rlx_g_row serves md_fire_kernel and md_lbfgs.inc; rlx_cell_g and rlx_next_cell
+// serve md_lbfgs.inc, and md_fire_kernel keeps its own copy of their lines below (calling them moved its compiled form from 122
+// to 106 VGPRs: a FIRE run launches the kernels it launched before); md_fire_move_kernel spreads an atom over a quad of lanes ----
+// The row of G of one atom: G = F D with a moving cell, else F — the force as the optimizer sees it (held components zero
+// on entry) — with the held components of G zero again.
+template <bool FIX>
+__device__ __forceinline__ void rlx_g_row(int cell, const double *D, double f0, double f1, double f2, bool h0, bool h1, bool h2,
+                                          double &g0, double &g1, double &g2)
+{
+#pragma clang fp contract(off)
+    g0 = f0; g1 = f1; g2 = f2;
+    if (cell) {
+        g0 = (f0 * D[0] + f1 * D[3]) + f2 * D[6];
+        g1 = (f0 * D[1] + f1 * D[4]) + f2 * D[7];
+        g2 = (f0 * D[2] + f1 * D[5]) + f2 * D[8];
+        if (FIX) {
+            if (h0) g0 = 0.0;
+            if (h1) g1 = 0.0;
+            if (h2) g2 = 0.0;
+        }
+    }
+}
+
+// The cell rows of G: (W D^-T o M) / c with W = -V stress, the stress as sgpr_stress_from_virial gives it.  h: the cell of
+// the configuration, sc: the eleven scalars of its evaluation.
+__device__ __forceinline__ void rlx_cell_g(const RelaxParams &p, const double *h, const double *D, const double *sc, double *Gc)
+{
+#pragma clang fp contract(off)
+    double Di[9], T[9];
+    const double vol = fabs(rlx_det(h));
+    const double vq = vol > 0.0 ? vol : -2.0;
+    const int voigt[6] = {0, 4, 8, 5, 2, 1};
+    double w6[6];
+    for (int k = 0; k < 6; k++) w6[k] = -(vol * RLX_DIV(sc[1 + voigt[k]], vq));
+    const double W[9] = {w6[0], w6[5], w6[4], w6[5], w6[1], w6[3], w6[4], w6[3], w6[2]};
+    rlx_m3_inv(D, Di);
+    rlx_m3_mul_t(W, Di, T);
+    for (int k = 0; k < 9; k++) Gc[k] = RLX_DIV(T[k] * p.mask[k], p.cf);
+}
+
+// The next configuration's deformation gradient D' = Xc / c and cell h0 D'^T from the cell rows Xc of X, into its slot of
+// the ring of cells.
+__device__ __forceinline__ void rlx_next_cell(const RelaxParams &p, const double *Xc, double *nxt)
+{
+#pragma clang fp contract(off)
+    double Dn[9], hn[9];
+    for (int k = 0; k < 9; k++) Dn[k] = RLX_DIV(Xc[k], p.cf);
+    rlx_m3_mul_t(p.h0, Dn, hn);
+    for (int k = 0; k < 9; k++) { nxt[k] = hn[k]; nxt[9 + k] = Dn[k]; }
+}
+
 // Behind evaluation n of a relaxation (see above).  packed: the results of this evaluation (caller atom order), vel: the
 // velocities of the atoms' coordinates (sorted order), cur / nxt: this configuration's and the next one's slot of the ring of
 // cells.  The sixteen scalars: 0..10 as the last kernel left them in `packed`, 11 the largest covloss, 12 the largest |G_row|^2,
@@ -90,17 +141,8 @@ __global__ __launch_bounds__(256) void md_fire_kernel(int N, RelaxParams p, doub
             if (h2) f2 = 0.0;
         }
         const double v0 = vel[3 * (size_t)k], v1 = vel[3 * (size_t)k + 1], v2 = vel[3 * (size_t)k + 2];
-        double g0 = f0, g1 = f1, g2 = f2;
-        if (p.cell) {
-            g0 = (f0 * D[0] + f1 * D[3]) + f2 * D[6];
-            g1 = (f0 * D[1] + f1 * D[4]) + f2 * D[7];
-            g2 = (f0 * D[2] + f1 * D[5]) + f2 * D[8];
-            if (FIX) {
-                if (h0) g0 = 0.0;
-                if (h1) g1 = 0.0;
-                if (h2) g2 = 0.0;
-            }
-        }
+        double g0, g1, g2;
+        rlx_g_row<FIX>(p.cell, D, f0, f1, f2, h0, h1, h2, g0, g1, g2);
         const double gg = (g0 * g0 + g1 * g1) + g2 * g2;
         s_gv += (g0 * v0 + g1 * v1) + g2 * v2;
         s_gg += gg;

@@ -775,7 +775,7 @@ class SGPRModel:
         fx = self._md.get("fixed")
         return 3 * self._md["N"] - (0 if fx is None else int(fx.sum()))
 
-    def relax_begin(self, numbers, positions, cell, pbc, fmax, cell_relax=False, mask=None, fixed=None, **fire):
+    def relax_begin(self, numbers, positions, cell, pbc, fmax, cell_relax=False, mask=None, fixed=None, optimizer="FIRE", **fire):
         """State of a FIRE relaxation into device memory (sgpr_md_relax: ase/optimize/fire.py on the positions and, with
         cell_relax, on the cell through ase.constraints.UnitCellFilter(atoms, mask=mask)'s coordinates; workloads.fire_relax is
         the host twin).  fire: dt, maxstep, dtmax, nmin, finc, fdec, astart, fa (ASE's defaults).  md_run / md_state / md_cells /
@@ -784,8 +784,20 @@ class SGPRModel:
           fixed: held atoms ([N]) or components ([N, 3]), True = held (sgpr_md_fix): the optimizer sees F = 0 there, the entries
         of G are zero in FIRE's sums and in max |G_row|^2 — convergence is judged on the free components, the forces reported
         stay the model's —, and the coordinate stays: x itself at constant cell, bit for bit; with cell_relax the undeformed
-        r, x = r D^T following the cell (FixAtoms inside UnitCellFilter)."""
-        from .workloads import FIRE_DEFAULTS, fixed_mask
+        r, x = r D^T following the cell (FixAtoms inside UnitCellFilter).
+          optimizer = "LBFGS": L-BFGS without line search in the place of FIRE (sgpr_md_relax_lbfgs, md_lbfgs.inc;
+        workloads.lbfgs_relax is the host twin), with ASE's keywords memory (1 ... 128), maxstep, alpha, damping in the place
+        of FIRE's; the columns 12..15 are then max |G_row|^2, p.G, the scale applied to the step and the valid pairs in use,
+        and relax_reset empties the history."""
+        from .workloads import FIRE_DEFAULTS, LBFGS_DEFAULTS, fixed_mask
+        if optimizer not in ("FIRE", "LBFGS"):
+            raise ValueError(f"relax_begin: optimizer = 'FIRE' or 'LBFGS', not {optimizer!r}")
+        lbfgs = None
+        if optimizer == "LBFGS":
+            unknown = set(fire) - set(LBFGS_DEFAULTS)
+            if unknown:
+                raise TypeError(f"relax_begin: unknown L-BFGS keywords {sorted(unknown)}")
+            lbfgs, fire = dict(LBFGS_DEFAULTS, **fire), {}
         unknown = set(fire) - set(FIRE_DEFAULTS)
         if unknown:
             raise TypeError(f"relax_begin: unknown FIRE keywords {sorted(unknown)}")
@@ -804,10 +816,13 @@ class SGPRModel:
         mk = None if mask is None else f64(np.asarray(mask, float).reshape(6))
         self._md_fix(fx)
         check(lib.sgpr_md_relax(self._h, float(fmax), ptr(fp), int(bool(cell_relax)), ptr(mk)))
+        if lbfgs is not None:
+            check(lib.sgpr_md_relax_lbfgs(self._h, int(lbfgs["memory"]), float(lbfgs["maxstep"]), float(lbfgs["alpha"]), float(lbfgs["damping"])))
         self._md["t"] = 0
 
     def relax_reset(self):
-        """optimizer.initialize() of the relaxation on the device: v = 0; dt, a, nsteps back to their start."""
+        """optimizer.initialize() of the relaxation on the device: v = 0; dt, a, nsteps back to their start (FIRE); the history
+        emptied (L-BFGS)."""
         check(_lib.load().sgpr_md_relax_reset(self._h))
 
     def neb_begin(self, numbers, images, cell, pbc, fmax, k=0.1, climb=False, fixed=None, **fire):

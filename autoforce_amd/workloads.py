@@ -1097,6 +1097,270 @@ def fire_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mas
             x = r
 
 
+# ---- limited-memory BFGS on the same generalised coordinates in the device's operations (lbfgs_relax; md_lbfgs.inc:
+# md_lbfgs_dots_kernel, md_lbfgs_solve_kernel, md_lbfgs_dir_kernel and md_lbfgs_move_kernel)
+LBFGS_DEFAULTS = dict(memory=100, maxstep=0.2, alpha=70.0, damping=1.0)   # ase/optimize/lbfgs.py, ASE 3.22
+LBFGS_MAX_MEMORY = 128   # pairs kept at most (md_lbfgs.inc: one thread of the one-workgroup kernel per pair)
+
+
+def _block_partials(vals):
+    """Per-row values [..., N] in sorted atom order -> [..., B]: one sum per workgroup of 256 rows, each _block_order_sum
+    (zeros beyond N), for all leading indices at once — the same operations element by element."""
+    vals = np.asarray(vals, float)
+    pad = (-vals.shape[-1]) % 256
+    if pad:
+        vals = np.concatenate([vals, np.zeros(vals.shape[:-1] + (pad,))], axis=-1)
+    v = vals.reshape(vals.shape[:-1] + (-1, 4, 64))
+    i = np.arange(64)
+    v = v + v[..., i ^ 1]
+    v = v + v[..., i ^ 2]
+    v = v + v[..., (i & ~7) | (7 - (i & 7))]
+    v = v + v[..., (i & ~15) | (15 - (i & 15))]
+    w = (v[..., 0] + v[..., 16]) + (v[..., 32] + v[..., 48])
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+def _index_order_sum(parts):
+    """Per-workgroup partial sums [..., B] added one after the other in index order, from zero."""
+    parts = np.asarray(parts, float)
+    acc = np.zeros(parts.shape[:-1])
+    for w in range(parts.shape[-1]):
+        acc = acc + parts[..., w]
+    return acc
+
+
+def _rows3(u, w):
+    """The three-component dot of every row: (u0 w0 + u1 w1) + u2 w2."""
+    return (u[..., 0] * w[..., 0] + u[..., 1] * w[..., 1]) + u[..., 2] * w[..., 2]
+
+
+class LbfgsTwin:
+    """The history of the device's L-BFGS (md_lbfgs.inc) and the product p = H G in its compact form (Byrd, Nocedal & Schnabel,
+    Math. Program. 63, 129 (1994)), operation for operation.  Everything is indexed by evaluation: pair i (formed at evaluation
+    i: s_i = X_i - X_(i-1), y_i = G_(i-1) - G_i) lives in slot i % memory of S and Y, column i of R^-1 and row / column i of
+    Y^T Y in row / column i % memory of two memory x memory arrays, G_i in slot i % 2 — an evaluation that is repeated writes
+    its own slots again and nothing else.  At evaluation n behind a start or reset at `base` the window is the pairs
+    max(base + 1, n - memory + 1) ... n, oldest first; a pair whose s.y is zero or not finite keeps its slot and is left out of
+    every product (valid = False).  With R the upper triangle of S^T Y over the valid pairs, Dg its diagonal, H0 = 1 / alpha:
+        u = S^T G,  v = H0 Y^T G,  t = R^-1 u,  top = R^-T ((Dg + H0 Y^T Y) t - v),  p = H0 G + S top - H0 Y t
+    R^-1 is never solved for: pair n adds the column [-R^-1 c / d ; 1 / d] (c_i = s_i.y_n, d = s_n.y_n), the oldest pair leaves
+    with its row and column.  Sums over the atoms: per workgroup of 256 rows in sorted order (_block_partials), the workgroups
+    in index order (_index_order_sum), the three cell rows behind them; sums over pairs: oldest first.
+    Rows: the N atoms in CALLER order (`order`: sorted -> caller), then — cell — the three cell rows.  held: bool [rows, 3]."""
+
+    def __init__(self, N, order, memory, alpha, cell=False, held=None):
+        self.N, self.NR, self.order, self.m, self.cell = N, N + (3 if cell else 0), np.asarray(order), int(memory), bool(cell)
+        if not 1 <= self.m <= LBFGS_MAX_MEMORY:
+            raise ValueError(f"memory: 1 ... {LBFGS_MAX_MEMORY}")
+        self.H0 = 1.0 / float(alpha)
+        self.held = held
+        m = self.m
+        self.S, self.Y, self.G = np.zeros((m, self.NR, 3)), np.zeros((m, self.NR, 3)), np.zeros((2, self.NR, 3))
+        self.Rinv, self.YY, self.Dg, self.valid = np.zeros((m, m)), np.zeros((m, m)), np.zeros(m), np.zeros(m, bool)
+        self.base = 0
+        self._ev = None
+
+    def reset(self, n):
+        """Evaluation n is the first of a fresh history."""
+        self.base = int(n)
+
+    def _dot(self, A, b):
+        """A [K, rows, 3] . b [rows, 3] -> [K] in the device's order."""
+        N = self.N
+        s = _index_order_sum(_block_partials(_rows3(A[:, :N], b[None, :N])[:, self.order]))
+        if self.cell:
+            r = _rows3(A[:, N:], b[None, N:])
+            s = s + ((r[:, 0] + r[:, 1]) + r[:, 2])
+        return s
+
+    def evaluate(self, n, G):
+        """Evaluation n with the generalised forces G [rows, 3] (held entries zero): stores G_n and y_n, forms the sums.
+        Returns dict(cnt: pairs in the window, pairs: the valid ones, GG, gmax2)."""
+        m, n = self.m, int(n)
+        G = np.array(G, float)
+        cnt = min(n - self.base, m)
+        lo = n - cnt + 1
+        self.G[n % 2] = G
+        GG = float(self._dot(G[None], G)[0])
+        g2 = _rows3(G, G)
+        ev = dict(n=n, cnt=cnt, lo=lo, GG=GG, gmax2=float(g2.max()), G=G)
+        if cnt:
+            y = self.G[(n - 1) % 2] - G
+            self.Y[n % m] = y
+            sl = [i % m for i in range(lo, n + 1)]
+            S, Y = self.S[sl], self.Y[sl]
+            ev.update(c=self._dot(S, y), yy=self._dot(Y, y), u=self._dot(S, G), yg=self._dot(Y, G), sl=sl)
+            d = float(ev["c"][-1])
+            self.valid[n % m] = bool(np.isfinite(d) and d != 0.0)
+        ev["pairs"] = int(sum(bool(self.valid[i % m]) for i in range(lo, n + 1)))
+        self._ev = ev
+        return dict(cnt=cnt, pairs=ev["pairs"], GG=GG, gmax2=ev["gmax2"])
+
+    def direction(self):
+        """p = H G [rows, 3] of the evaluation just evaluated, and p.G in closed form (H0 G.G + top.u - t.v)."""
+        ev, m, H0 = self._ev, self.m, self.H0
+        n, cnt, G = ev["n"], ev["cnt"], ev["G"]
+        p = H0 * G
+        pG = H0 * ev["GG"]
+        if cnt:
+            sl, c, u = ev["sl"], [float(x) for x in ev["c"]], [float(x) for x in ev["u"]]
+            v = [H0 * float(x) for x in ev["yg"]]
+            val = [bool(self.valid[s]) for s in sl]
+            new, sn = cnt - 1, sl[cnt - 1]
+            d = c[new]
+            Rinv, YY, Dg = self.Rinv, self.YY, self.Dg
+            for a in range(new):                       # the new column of R^-1
+                col = 0.0
+                if val[new] and val[a]:
+                    acc = 0.0
+                    for l in range(a, new):
+                        if val[l]:
+                            acc = acc + Rinv[sl[a], sl[l]] * c[l]
+                    col = (-acc) / d
+                Rinv[sl[a], sn] = col
+            Rinv[sn, sn] = 1.0 / d if val[new] else 0.0
+            for a in range(cnt):
+                YY[sl[a], sn] = YY[sn, sl[a]] = float(ev["yy"][a])
+            Dg[sn] = d
+            t, w, top = [0.0] * cnt, [0.0] * cnt, [0.0] * cnt
+            for a in range(cnt):
+                if val[a]:
+                    acc = 0.0
+                    for l in range(a, cnt):
+                        if val[l]:
+                            acc = acc + Rinv[sl[a], sl[l]] * u[l]
+                    t[a] = acc
+            for a in range(cnt):
+                if val[a]:
+                    acc = 0.0
+                    for j in range(cnt):
+                        if val[j]:
+                            mij = H0 * YY[sl[a], sl[j]]
+                            if j == a:
+                                mij = Dg[sl[a]] + mij
+                            acc = acc + mij * t[j]
+                    w[a] = acc - v[a]
+            for a in range(cnt):
+                if val[a]:
+                    acc = 0.0
+                    for i in range(a + 1):
+                        if val[i]:
+                            acc = acc + Rinv[sl[i], sl[a]] * w[i]
+                    top[a] = acc
+            for a in range(cnt):
+                if val[a]:
+                    pG = (pG + top[a] * u[a]) - t[a] * v[a]
+                    p = (p + top[a] * self.S[sl[a]]) - (H0 * t[a]) * self.Y[sl[a]]
+        if self.held is not None:
+            p = np.where(self.held, 0.0, p)
+        return p, float(pG)
+
+    def moved(self, n, s):
+        """The move out of evaluation n: s = X_(n+1) - X_n, the pair evaluation n + 1 completes."""
+        self.S[(int(n) + 1) % self.m] = s
+
+
+def lbfgs_relax(calc, numbers, pos, cell, pbc, steps, fmax, cell_relax=False, mask=None, species=None, reset_at=(), fixed=None, reset_if=None,
+                **lbfgs):
+    """L-BFGS without line search (ase/optimize/lbfgs.py, ASE 3.22, LGPL; Nocedal, Math. Comp. 35, 773 (1980)) on the
+    generalised coordinates and forces of fire_relax — X = [r ; c D], G = [F D ; (W D^-T o M) / c] — in numpy around any
+    calculator with the ASE surface, in the operations and the summation order of the device loop (sgpr_md_relax_lbfgs:
+    md_lbfgs.inc): its host twin and the definition.  lbfgs: memory (pairs kept at most, 1 ... 128), maxstep, alpha (H0 =
+    1 / alpha), damping — ASE's keywords and defaults.  Per evaluation n:
+        max over rows |G_row|^2 < fmax^2:  converged, nothing moves
+        behind a start or reset:  a pair s_n = X_n - X_(n-1) (the rounded difference of the stored coordinates, as ASE takes
+            r - r0), y_n = G_(n-1) - G_n; at most `memory` pairs are kept, no curvature test — but a pair whose s.y is zero or
+            not finite is left out (ASE would divide by it)
+        p = H G through the compact form (LbfgsTwin), which is the two-loop recursion over the same pairs up to rounding
+        step = damping * p, scaled by maxstep / longest when the longest row (atoms and cell rows) reaches maxstep (ASE's >=)
+    reset_at: evaluation indices in front of which the history is emptied (optimizer.initialize()); reset_if: called behind
+    the calculator's answer of every evaluation, true empties the history in front of that evaluation too (an active
+    calculator that has just updated its model: the device loop's relax_reset behind a hand-over).  fixed: as in fire_relax — G = 0, the step is 0 and r keeps its bits, selected.
+      Yields a dict per evaluated configuration: n, energy, positions, cell, D, gmax2, pG (p.G; 0 where nothing moves),
+    scale (the factor applied to p; 0 where nothing moves), pairs (valid pairs in the window), converged.  The generator ends
+    behind a converged configuration."""
+    from .ase_shim import Atoms, constraints_from_mask
+    unknown = set(lbfgs) - set(LBFGS_DEFAULTS)
+    if unknown:
+        raise TypeError(f"lbfgs_relax: unknown L-BFGS keywords {sorted(unknown)}")
+    p = dict(LBFGS_DEFAULTS)
+    p.update(lbfgs)
+    maxstep, damping = float(p["maxstep"]), float(p["damping"])
+    N = len(numbers)
+    cf = float(N)
+    h0 = [[float(v) for v in row] for row in np.asarray(cell, float).reshape(3, 3)]
+    if mask is None:
+        mask = [1.0] * 6
+    mk6 = [1.0 if float(v) != 0.0 else 0.0 for v in np.asarray(mask, float).reshape(6)]
+    M = [[mk6[0], mk6[5], mk6[4]], [mk6[5], mk6[1], mk6[3]], [mk6[4], mk6[3], mk6[2]]]
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    eye = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    r = np.array(pos, float)
+    x = r.copy()
+    Xc = np.array([[cf * eye[a][b] for b in range(3)] for a in range(3)])     # the cell rows of X: c D
+    D, h = eye, h0
+    fmax2 = float(fmax) * float(fmax)
+    fx = fixed_mask(fixed, N)
+    cons = constraints_from_mask(fx)
+    held = None if fx is None else (np.concatenate([fx, np.zeros((3, 3), bool)]) if cell_relax else fx)
+    tw = LbfgsTwin(N, order, p["memory"], p["alpha"], cell=cell_relax, held=held)
+    for n in range(steps + 1):
+        if n in reset_at:
+            tw.reset(n)
+        at = Atoms(numbers, x, np.array(h), pbc, constraint=cons)
+        at.calc = calc
+        F, E = np.asarray(at.get_forces(apply_constraint=False), float), float(at.get_potential_energy())
+        if reset_if is not None and reset_if():
+            tw.reset(n)
+        if fx is not None:
+            F = np.where(fx, 0.0, F)
+        if cell_relax:
+            s6 = [float(t) for t in np.asarray(at.get_stress(), float)]
+            vol = _cell_volume(h)
+            w6 = [-(vol * t) for t in s6]
+            W = [[w6[0], w6[5], w6[4]], [w6[5], w6[1], w6[3]], [w6[4], w6[3], w6[2]]]
+            T = _m3_mul_t(W, _m3_inv(D))
+            Gc = [[(T[a_][b] * M[a_][b]) / cf for b in range(3)] for a_ in range(3)]
+            G = _row_mul(F, D)
+            if fx is not None:
+                G = np.where(fx, 0.0, G)
+            G = np.concatenate([G, np.array(Gc)])
+        else:
+            G = F
+        ev = tw.evaluate(n, G)
+        out = dict(n=n, energy=E, positions=x, cell=np.array(h), D=np.array(D), gmax2=ev["gmax2"], pG=0.0, scale=0.0, pairs=ev["pairs"])
+        if ev["gmax2"] < fmax2:
+            out.update(converged=True)
+            yield out
+            return
+        if n == steps:   # (the last evaluation: nothing moves behind it)
+            out.update(converged=False)
+            yield out
+            return
+        pdir, pG = tw.direction()
+        longest = float(np.sqrt(_rows3(pdir, pdir).max()))
+        sc = maxstep / longest if longest >= maxstep else 1.0
+        out.update(pG=pG, scale=sc, converged=False)
+        yield out
+        dr = (pdir * sc) * damping
+        rn = r + dr[:N]
+        if fx is not None:   # (selected, not computed)
+            rn = np.where(fx, r, rn)
+        s = rn - r
+        r = rn
+        if cell_relax:
+            Xn = Xc + dr[N:]
+            s = np.concatenate([s, Xn - Xc])
+            Xc = Xn
+            D = [[float(Xc[a_][b]) / cf for b in range(3)] for a_ in range(3)]
+            h = _m3_mul_t(h0, D)
+            x = _row_mul(r, [[D[b][a_] for b in range(3)] for a_ in range(3)])
+        else:
+            x = r
+        tw.moved(n, s)
+
+
 # ---- the nudged elastic band under FIRE in the device's operations (neb_fire; md_neb.inc: md_neb_sums_kernel, md_neb_fire_kernel
 # and md_neb_move_kernel)
 NEB_MAX = 16   # interior images of a band (md_neb.inc)

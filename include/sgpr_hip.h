@@ -423,6 +423,18 @@ int sgpr_md_cells(sgpr_model *h, int64_t first, int count, double *out);
  * sgpr_md_relax_reset  optimizer.initialize(): v = 0 and dt, a, nsteps back to their start (between two sgpr_md_run calls). */
 int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int move_cell, const double *mask6);
 int sgpr_md_relax_reset(sgpr_model *h);
+/* L-BFGS without line search in the place of FIRE (md_lbfgs.inc; ase/optimize/lbfgs.py, ASE 3.22, restated): between sgpr_md_relax
+ * — whose fmax, move_cell and mask6 hold, whose refusals apply as they are and whose FIRE keywords go unused — and the first
+ * sgpr_md_run.  memory: pairs (s, y) kept at most, 1 ... 128; maxstep, alpha (H0 = 1 / alpha), damping: ASE's keywords
+ * (defaults 100, 0.2, 70, 1).  p = H G is formed in the compact representation of Byrd, Nocedal and Schnabel (1994) from one
+ * pass of sums over the history; a pair whose s.y is zero or not finite is left out (ASE would divide by it).  The history,
+ * 2 memory (3N + 9) doubles of device memory, is indexed by evaluation: a cut run gives the bits of an uncut one, and an
+ * evaluation repeated behind a covloss halt writes its own pair again.  sgpr_md_relax_reset empties it; sgpr_md_end gives it back.
+ * The columns 12..15 of a row of sgpr_md_run: [12] = largest |G_row|^2, [13] = p.G, [14] = the scale applied to the step
+ * (maxstep / longest, or 1), [15] = valid pairs in use; [13] and [14] are 0 where nothing moves.
+ * SGPR_E_INVALID: no relaxation set up, a run that has started, memory outside 1 ... 128, a keyword <= 0.  SGPR_E_NODEVICE: no
+ * room for the history.  The handle goes on working after any of them. */
+int sgpr_md_relax_lbfgs(sgpr_model *h, int memory, double maxstep, double alpha, double damping);
 /* Nudged elastic band with FIRE inside the device loop (md_neb.inc; the reference's cl/neb.py drives ase.neb.NEB under an
  * ase.optimize optimizer and crosses into the calculator once per image per step).  ASE's default `aseneb` method, restated:
  * images 0 ... K + 1 share numbers, cell (constant) and pbc; the ends never move and are never evaluated; with the model's
