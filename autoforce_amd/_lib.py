@@ -85,6 +85,9 @@ SIGNATURES = {
     "sgpr_md_neb_reset": (C.c_int, [_vp]),
     "sgpr_md_neb_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
     "sgpr_md_neb_info": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sgpr_md_pimd": (C.c_int, [_vp, C.c_int, _vp, _vp, _dbl, _dbl, _dbl]),
+    "sgpr_md_pimd_state": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "sgpr_md_pimd_info": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sgpr_md_fix": (C.c_int, [_vp, _vp]),
     "sgpr_md_record": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sgpr_md_frame_count": (C.c_int, [_vp, _vp]),

@@ -4,10 +4,11 @@
 
 Langevin dynamics (the reference's `dynamics = 'Langevin'`, cl/md.py:117-128) and the reference's DEFAULT — `dynamics =
 'NPT'` without a bulk modulus: Nose-Hoover NVT, ase.md.npt.NPT(pfactor=None, ttime=tdamp fs), cl/md.py:17, :131-166 — run with
-positions and velocities in device memory (ActiveCalculator.run_md); NPT with a bulk modulus (a cell that moves, cl/md.py:147-166)
-is the same ASE integrator restated in `autoforce_amd/npt.py` (Melchionna's combined Nose-Hoover / Parrinello-Rahman scheme,
-`mask`, `iso`, `stress`, `pdamp`, the `ml_filter` wrapper) driving calculate() once per step, as ASE's object does in the
-reference.  Structures are read and written as extended XYZ (ASE's own format; without ASE no other reader exists
+positions and velocities in device memory (ActiveCalculator.run_md), and so does NPT with a bulk modulus (a cell that moves,
+cl/md.py:147-166: `mask`, `iso`, `stress`, `pdamp`, `ml_filter` as run_md's pfactor, externalstress, mask, iso and ml_filter)
+where the atoms carry no constraints; with constraints the same ASE integrator restated in `autoforce_amd/npt.py` (Melchionna's
+combined Nose-Hoover / Parrinello-Rahman scheme, the `ml_filter` wrapper) drives calculate() once per step, as ASE's object does
+in the reference.  Structures are read and written as extended XYZ (ASE's own format; without ASE no other reader exists
 here), the trajectory likewise (`trajectory = 'md.xyz'`)."""
 import argparse
 
@@ -94,12 +95,10 @@ def manual_steps(atoms, calc, eps, rng, eps2=0.0, npt=False):
     calc._logpref = ""
 
 
-def npt_dynamics(atoms, calc, dt, tem, bulk_modulus, stress, mask, iso, tdamp, pdamp, ml_filter):
-    """cl/md.py:131-166 with a bulk modulus: ase.md.npt.NPT(atoms, dt fs, temperature_K, externalstress = stress GPa, ttime =
-    tdamp fs, pfactor = (pdamp fs)^2 * bulk_modulus GPa, mask) on the upper-triangular cell (`configure_cell`, :169-172;
-    an all-zero cell would need ASE's `center(vacuum=6)`: a periodic cell is asked for here), `iso` = no traceless strain."""
-    from ..npt import GPA, NPT, FilterDeltas, make_cell_upper_triangular
-    from ..workloads import FS
+def configure_cell(atoms):
+    """cl/md.py:169-172: the cell of a run whose cell moves, rotated to upper-triangular form with the atoms and their velocities
+    (an all-zero cell would need ASE's `center(vacuum=6)`: a periodic cell is asked for here)."""
+    from ..npt import make_cell_upper_triangular
     cell = np.array(getattr(atoms.cell, "array", atoms.cell), float)
     if np.allclose(cell, 0.0) or abs(np.linalg.det(cell)) < 1e-12:
         raise ValueError("NPT needs a three-dimensional cell (the reference puts a cluster into a box with 6 A of vacuum around it, "
@@ -111,6 +110,15 @@ def npt_dynamics(atoms, calc, dt, tem, bulk_modulus, stress, mask, iso, tdamp, p
         atoms.positions = pos
         if v is not None:
             atoms.set_velocities(np.asarray(v) @ R)
+
+
+def npt_dynamics(atoms, calc, dt, tem, bulk_modulus, stress, mask, iso, tdamp, pdamp, ml_filter):
+    """cl/md.py:131-166 with a bulk modulus: ase.md.npt.NPT(atoms, dt fs, temperature_K, externalstress = stress GPa, ttime =
+    tdamp fs, pfactor = (pdamp fs)^2 * bulk_modulus GPa, mask) on the upper-triangular cell (configure_cell), `iso` = no
+    traceless strain — the integrator around calculate(): what md() falls back to where the atoms carry constraints."""
+    from ..npt import GPA, NPT, FilterDeltas
+    from ..workloads import FS
+    configure_cell(atoms)
     md_atoms = FilterDeltas(atoms, shrink=ml_filter) if ml_filter else atoms
     dyn = NPT(md_atoms, dt * FS, tem, externalstress=stress * GPA, ttime=tdamp * FS, pfactor=(pdamp * FS) ** 2 * bulk_modulus * GPA,
               mask=mask)
@@ -150,15 +158,23 @@ def md(atoms, calc=None, dynamics="NPT", dt=None, tem=300.0, picos=100, trajecto
     tdamp_fs = float(tdamp) if dynamics.upper() == "NPT" else None
     out = open(trajectory, "a" if append else "w") if (trajectory and calc.rank == 0) else None
     # ONE filter of model-update jumps for all temperatures, as the reference wraps its atoms in one FilterDeltas before the
-    # loop (cl/md.py:76-79): run_md reads the holder's accumulators at its start and fills them at its end (the moving-cell
-    # branch below still wraps the atoms itself, per temperature)
-    from ..workloads import FilterState
+    # loop (cl/md.py:76-79): run_md reads the holder's accumulators at its start and fills them at its end (the fallback of
+    # the moving-cell branch below still wraps the atoms itself, per temperature)
+    from ..workloads import FS, FilterState
     filt = FilterState(ml_filter) if ml_filter else None
+    baro = {}
+    held = calc.constraint_mask(atoms) if moving_cell else None
+    constrained = held is not None and bool(held.any())
+    if moving_cell and not constrained:
+        # the moving cell inside run_md: ase.md.npt.NPT's keywords as the reference sets them (cl/md.py:155-166)
+        from ..npt import GPA
+        configure_cell(atoms)
+        baro = dict(pfactor=(pdamp * FS) ** 2 * bulk_modulus * GPA, externalstress=stress * GPA, mask=mask, iso=iso)
     for T in temperatures:
         steps = int(picos * 1000 / dt) if picos > 0 else int(-picos)
-        if moving_cell:
-            # the barostat's integrator around calculate(), one call per step (the log line, the covloss gate and the model
-            # updates are calculate()'s own, as in the reference)
+        if constrained:
+            # constraints: the barostat's integrator around calculate(), one call per step (the log line, the covloss gate and
+            # the model updates are calculate()'s own, as in the reference)
             dyn = npt_dynamics(atoms, calc, dt, T, bulk_modulus, stress, mask, iso, tdamp, pdamp, ml_filter)
             for step, energy, temperature, wall in dyn.run(steps):
                 if out is not None and loginterval and step % loginterval == 0:
@@ -166,7 +182,7 @@ def md(atoms, calc=None, dynamics="NPT", dt=None, tem=300.0, picos=100, trajecto
             continue
         for step, energy, temperature, updated, wall in calc.run_md(atoms, steps, T, dt_fs=dt, friction=friction, rng=None,
                                                                     seed=int(rng.integers(1, 2 ** 62)), sync_every=loginterval or None,
-                                                                    tdamp_fs=tdamp_fs, ml_filter=filt):
+                                                                    tdamp_fs=tdamp_fs, ml_filter=filt, **baro):
             if out is not None and loginterval and step % loginterval == 0:
                 # (the state lives on the device: run_md brings the positions back at the steps a trajectory wants them)
                 out.writelines(format_extxyz(Frame(numbers, atoms.positions, atoms.cell, atoms.pbc, energy, None, None)))

@@ -294,6 +294,13 @@ struct MdRun {
         NebCell cell = {};
         std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_neb_info)
     } neb;
+    // path-integral MD (sgpr_md_pimd, md_pimd.inc): P beads of a ring polymer evaluated by this one handle per evaluation
+    struct Pimd {
+        bool on = false;
+        int P = 0;
+        double kT = 0.0, wP2 = 0.0;   // the physical kT; w_P^2 = (P kT / hbar)^2
+        std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_pimd_info)
+    } pimd;
     static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
     long long meta_slot(long long n) const { return meta.pre + meta_dep(n, meta.pace) - meta_dep(meta.base, meta.pace); }
     // multiples of `every` in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
@@ -365,6 +372,14 @@ struct MdState {
         DevBuf<char> par;          // one NebFirePar: cell, FIRE's keywords, spring constant, climb — md_neb_fire_kernel's constants
         DevBuf<double> info_d;     // [rows][NEB_INFO] E | covmax per evaluation of a call
     } neb;
+    struct {                       // beads, velocities and results in caller atom order
+        DevBuf<double> X, V;       // [RLX_RING][P][N][3] by evaluation index % RLX_RING; V: before the closing half kick
+        DevBuf<double> P;          // [RLX_RING][P][4N + 11] packed results of the beads' plain steps
+        DevBuf<double> sums;       // [P][PIMD_SUMS] md_pimd_sums_kernel's output
+        DevBuf<double> tab;        // C[P][P] | cos | sin / w | w sin | c1 | c2: the host's tables (sgpr_md_pimd)
+        DevBuf<double> sq;         // [N] sqrt(kT_P / m), sorted order
+        DevBuf<double> info_d;     // [rows][PIMD_INFO] E | covmax per evaluation of a call
+    } pimd;
     NptSlot *slot(long long n) const { return (NptSlot *)npt.ring.p + (n & 3); }
     const unsigned char *fix() const { return run.fix.n ? fixed.mask.p : nullptr; }
     MetaTab meta_tab(long long want) const
@@ -1263,6 +1278,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_lbfgs.inc"
 #include "md_bcm.inc"
 #include "md_neb.inc"
+#include "md_pimd.inc"
 #include "md_record.inc"
 #include "md_meta.inc"
 

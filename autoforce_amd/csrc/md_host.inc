@@ -2,9 +2,10 @@
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
 // _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _committee (the Bayesian committee), _neb
-// (the nudged elastic band).  sgpr_md_run drives dynamics itself and hands a relaxation, a committee and a band to md_relax_run,
-// md_committee_run and md_neb_run; the four share the look-ahead driver and the frame of a call (MdCall).  The kernels are in
-// api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc and md_meta.inc (the one small kernel of
+// (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation, a committee, a
+// band and a polymer to md_relax_run, md_committee_run, md_neb_run and md_pimd_run; the five share the look-ahead driver and the
+// frame of a call (MdCall).  The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc,
+// md_pimd.inc and md_meta.inc (the one small kernel of
 // sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -112,6 +113,7 @@ extern "C" int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N)
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_fix: call sgpr_md_begin first");
     if (m.run.nh.on || m.run.npt.on || m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_thermostat and sgpr_md_relax");
     if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_fix: call it before sgpr_md_neb");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run is a ring polymer (sgpr_md_pimd), which runs without a mask");
     if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_fix: the run has started");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_fix: the run has a committee (sgpr_md_committee), which runs without a mask");
     const int N = m.run.N;
@@ -149,6 +151,7 @@ extern "C" int sgpr_md_thermostat(sgpr_model *h, int kind, double ttime, double 
     if (m.run.t != 0) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run has started");
     if (m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a nudged elastic band (sgpr_md_neb)");
+    if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: the run is a ring polymer (sgpr_md_pimd), which has its own thermostat");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: call it before sgpr_md_committee");
     if (kind == 0) { m.run.nh.on = false; m.run.npt.on = false; m.run.ring = 3; return SGPR_OK; }
     if (!(ttime > 0.0) || !(kT > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_thermostat: ttime > 0 and kT > 0");
@@ -176,6 +179,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
 {
     if (!h || !externalstress) return fail(SGPR_E_INVALID, "sgpr_md_barostat: bad arguments");
     MdState &m = h->md;
+    if (m.active && m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run is a ring polymer (sgpr_md_pimd), which runs at constant cell");
     if (!m.active || !m.run.nh.on || m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_barostat: call sgpr_md_begin and sgpr_md_thermostat(kind = 1) first");
     if (m.run.t != 0 || m.run.npt.started) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the run has started");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run was begun on %d ranks; the moving cell runs on one", m.run.world);
@@ -376,6 +380,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a ring polymer (sgpr_md_pimd), which serves dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -877,6 +882,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
                     "md_committee_cell is set (sgpr_set_option)");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a relaxation; a committee serves dynamics only");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a nudged elastic band; a committee serves dynamics only");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a ring polymer (sgpr_md_pimd), which is evaluated by one model");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
@@ -1113,6 +1119,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a bias (sgpr_md_meta), which serves dynamics only; the host loop around calculate() serves a biased band");
     if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run has a filter (sgpr_md_filter), which serves dynamics only");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a ring polymer (sgpr_md_pimd)");
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
@@ -1283,6 +1290,186 @@ static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, d
     return SGPR_OK;
 }
 
+// ---- path-integral MD (sgpr_md_pimd; md_pimd.inc has the scheme, workloads.pimd_baoab is the host twin) ----
+// For the run begun by sgpr_md_begin (any bead as its positions: they bind the system; its masses and dt hold, its velocities,
+// friction and kT are replaced by what is given here), before the first sgpr_md_run.  positions[P][N][3], velocities[P][N][3]
+// (NULL: zeros): the beads in caller atom order; kT: the physical one — the polymer is sampled at P kT with w_P = P kT / hbar,
+// hbar in the units of eV, A and amu (PIMD_HBAR); friction: the centroid's, lambda: gamma_k = 2 lambda w_k of the other modes.
+// The tables of the run — C, the free ring polymer's propagator over dt / 2, c1_k and c2_k — are computed here, once, in the
+// operations of workloads.pimd_tables.  sgpr_md_run then evaluates the P beads with this one handle and moves them; its noise
+// is [nevals][P][N][3] (mode k, caller atom order).  Constant cell, one rank, nothing else attached.
+extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const double *velocities, double kT, double friction, double lambda)
+{
+#pragma clang fp contract(off)
+    if (!h || !positions) return fail(SGPR_E_INVALID, "sgpr_md_pimd: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_pimd: call sgpr_md_begin first");
+    if (P < 1 || P > PIMD_MAX) return fail(SGPR_E_INVALID, "sgpr_md_pimd: %d beads; a polymer has 1 to %d", P, PIMD_MAX);
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run was begun on %d ranks; a polymer runs on one", m.run.world);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run has started");
+    if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run has a thermostat or a barostat; a polymer runs at constant cell under its own thermostat");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run has a committee (sgpr_md_committee); a polymer is evaluated by one model");
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run has a bias (sgpr_md_meta), which the polymer's loop does not apply; the host loop around calculate() serves it");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run has a filter (sgpr_md_filter); a polymer integrates unfiltered forces");
+    if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: %d components are held (sgpr_md_fix); a polymer runs without a mask", m.run.fix.n);
+    if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: a frame record is armed (sgpr_md_record); a polymer records no frames");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
+    if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
+    if (!(kT > 0.0) || friction < 0.0 || lambda < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_pimd: kT > 0, friction >= 0, lambda >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const int N = m.run.N;
+    const size_t N3 = (size_t)3 * N, plen = (size_t)sgpr_packed_len(N), PN3 = N3 * (size_t)P;
+    const double dt = m.run.dt, hdt = m.run.hdt, dP = (double)P;
+    const double kTP = dP * kT, wP = kTP / PIMD_HBAR;
+    std::vector<double> tab((size_t)P * P + 5 * (size_t)P);
+    for (int j = 0; j < P; j++)
+        for (int k = 0; k < P; k++) {
+            const double arg = (2.0 * M_PI * (double)((j * k) % P)) / dP;
+            double c;
+            if (k == 0) c = sqrt(1.0 / dP);
+            else if (2 * k < P) c = sqrt(2.0 / dP) * cos(arg);
+            else if (2 * k == P) c = (j & 1) ? -sqrt(1.0 / dP) : sqrt(1.0 / dP);
+            else c = sqrt(2.0 / dP) * sin(arg);
+            tab[(size_t)j * P + k] = c;
+        }
+    double *cs = tab.data() + (size_t)P * P, *sn = cs + P, *wsn = sn + P, *c1 = wsn + P, *c2 = c1 + P;
+    for (int k = 0; k < P; k++) {
+        const double wk = k ? (2.0 * wP) * sin(((double)k * M_PI) / dP) : 0.0;
+        const double s = sin(wk * hdt);
+        cs[k] = cos(wk * hdt);
+        sn[k] = k ? s / wk : hdt;
+        wsn[k] = wk * s;
+        const double g = k ? (2.0 * lambda) * wk : friction;
+        c1[k] = exp(-(g * dt));
+        c2[k] = sqrt(1.0 - c1[k] * c1[k]);
+    }
+    std::vector<double> sq(N);
+    for (int i = 0; i < N; i++) sq[i] = sqrt(kTP / m.run.mass_sorted[i]);
+    // rings of RLX_RING slots, every slot the initial polymer (what runs behind a halt evaluates stale slots)
+    if (m.pimd.X.alloc(PN3 * RLX_RING) || m.pimd.V.alloc(PN3 * RLX_RING) || m.pimd.P.alloc(plen * (size_t)P * RLX_RING) ||
+        m.pimd.sums.alloc((size_t)PIMD_SUMS * P) || m.pimd.tab.alloc(tab.size()) || m.pimd.sq.alloc(N))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_pimd: device allocation failed");
+    HIPCHK(hipMemset(m.pimd.V.p, 0, sizeof(double) * PN3 * RLX_RING));
+    for (int r = 0; r < RLX_RING; r++)
+        HIPCHK(hipMemcpy(m.pimd.X.p + PN3 * r, positions, sizeof(double) * PN3, hipMemcpyHostToDevice));
+    if (velocities) HIPCHK(hipMemcpy(m.pimd.V.p, velocities, sizeof(double) * PN3, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.pimd.tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.pimd.sq.p, sq.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    m.run.pimd.P = P; m.run.pimd.kT = kT; m.run.pimd.wP2 = wP * wP;
+    m.run.pimd.on = true; m.run.ring = RLX_RING;
+    m.run.pimd.info.clear();
+    return SGPR_OK;
+}
+
+// The P beads in caller atom order: positions[P][N][3] of the current configuration (which = 0) or the one evaluated before it
+// (-1), velocities_pre[P][N][3] BEFORE its closing half kick (due at every configuration but the start of the trajectory:
+// v = v_pre + (dt/2) F / m once F is known), packed[P][4N + 11] the beads' results where the last sgpr_md_run evaluated that
+// configuration (a halted or `final` call: which = 0; a call that ran through: which = -1).  Any of them NULL.
+extern "C" int sgpr_md_pimd_state(sgpr_model *h, double *positions, double *velocities_pre, double *packed, int which)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: call sgpr_md_begin and sgpr_md_pimd first");
+    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: which = 0 or -1");
+    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: no earlier configuration");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N3 = (size_t)3 * m.run.N, plen = (size_t)sgpr_packed_len(m.run.N), P = (size_t)m.run.pimd.P;
+    const size_t sl = (size_t)((m.run.t + which + RLX_RING) % RLX_RING);
+    if (positions) HIPCHK(hipMemcpy(positions, m.pimd.X.p + N3 * P * sl, sizeof(double) * N3 * P, hipMemcpyDeviceToHost));
+    if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.pimd.V.p + N3 * P * sl, sizeof(double) * N3 * P, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.pimd.P.p + plen * P * sl, sizeof(double) * plen * P, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// The record of the last sgpr_md_run: out[count][64] = E[32] | covmax[32] (bead j at entry j, the rest zero) of its evaluations
+// first ... first + count - 1 (0 = the call's first) among those that stand.
+extern "C" int sgpr_md_pimd_info(sgpr_model *h, int first, int count, double *out)
+{
+    if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: bad arguments");
+    const MdState &m = h->md;
+    if (!m.active || !m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: call sgpr_md_begin and sgpr_md_pimd first");
+    const long long have = (long long)(m.run.pimd.info.size() / PIMD_INFO);
+    if ((long long)first + count > have)
+        return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", first, (long long)first + count - 1, have);
+    memcpy(out, m.run.pimd.info.data() + (size_t)PIMD_INFO * first, sizeof(double) * PIMD_INFO * (size_t)count);
+    return SGPR_OK;
+}
+
+// sgpr_md_run for a polymer, in the shape of md_neb_run: every evaluation is P plain steps of the live handle — bead j's
+// caller-order positions in the ring through the handle's own binning kernel, into its own packed buffer; before each the handle
+// is as md_reset_lists leaves it: every bead rebuilds its candidate lists (one list set per bead would save that: not done) —
+// with md_pimd_sums_kernel, md_pimd_gate_kernel and md_pimd_move_kernel behind them.  The halts — covloss gate (1), capacity
+// overflow at any bead (2) — are decided by md_pimd_gate_kernel on the evaluation itself, before anything moves: what the host
+// has enqueued behind a halt evaluates stale slots and changes nothing, and the repeat of a halted evaluation finds x and v of
+// its slot as they were.  The halt words count evaluations of the polymer from the handle's step counter at the call's start.
+// noise: [nevals][P][N][3], caller atom order, uploaded as it is (the move kernel goes through the permutation anyway).
+static int md_pimd_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
+{
+    MdState &m = h->md;
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    hipStream_t st = c.st;
+    const int N = c.N, RG = RLX_RING, P = m.run.pimd.P;
+    const size_t plen = c.plen, N3 = (size_t)3 * N, PN3 = N3 * (size_t)P;
+    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
+    if (m.pimd.info_d.alloc((size_t)PIMD_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemsetAsync(m.pimd.info_d.p, 0, sizeof(double) * PIMD_INFO * ((size_t)nevals + 1), st));
+    if (noise) {
+        if (m.noise_raw.alloc(PN3 * (size_t)nevals)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * PN3 * (size_t)nevals, hipMemcpyHostToDevice, st));
+    }
+    m.run.started = true;
+    m.run.pimd.info.clear();
+    if (!h->warm) {   // the checked pass grows capacities: over every bead
+        const size_t sw = (size_t)(m.run.t % RG);
+        for (int i = 0; i < P; i++) {
+            const int rc_ = run_checked(h, m.pimd.X.p + PN3 * sw + N3 * i, m.cell.p, m.pimd.P.p + plen * (P * sw + i), st);
+            if (rc_) return rc_;
+        }
+        h->warm = true;
+    }
+    md_call_start(h, c);
+    const unsigned step0 = c.step0; const double gate = c.gate;
+    const bool pend0 = m.run.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
+    const size_t lds = sizeof(double) * ((size_t)4 * P * 3 * PIMD_TILE + (size_t)P * P);
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const size_t sl = (size_t)((m.run.t + j) % RG), sn = (sl + 1) % RG;
+        const double *beads = m.pimd.X.p + PN3 * sl;
+        double *Pk = m.pimd.P.p + plen * P * sl;
+        for (int i = 0; i < P; i++) {
+            if (const int rl = md_reset_lists(h, st)) return rl;
+            const int re = enqueue_step(h, beads + N3 * i, m.cell.p, Pk + plen * i, st, nullptr);
+            if (re) return re;
+        }
+        const int step = (int)(step0 + j);
+        const bool stay = final_eval && j == nevals - 1;
+        const PimdRing b = {N, P, plen, beads, m.pimd.V.p + PN3 * sl, Pk, h->d_perm.p, m.mass.p, m.run.hdt, (j > 0 || pend0) ? 1 : 0};
+        hipLaunchKernelGGL(md_pimd_sums_kernel, dim3(P), dim3(256), 0, st, b, m.pimd.sums.p, (const int *)m.halt.p, step);
+        hipLaunchKernelGGL(md_pimd_gate_kernel, dim3(1), dim3(64), 0, st, N, P, (const double *)m.pimd.sums.p, m.run.pimd.kT, m.run.pimd.wP2,
+                           m.pimd.info_d.p + (size_t)PIMD_INFO * j, gate, m.halt.p, m.halt_host.dev, step, m.scal_d.p + (size_t)SGPR_MD_SCAL * j,
+                           m.mark.dev + j);
+        if (!stay) {
+            const PimdMove a = {m.pimd.sq.p, m.pimd.tab.p, noise ? m.noise_raw.p + PN3 * (size_t)j : nullptr, m.pimd.X.p + PN3 * sn, m.pimd.V.p + PN3 * sn,
+                                noise ? 0ull : m.seed, m.run.t + j};
+            hipLaunchKernelGGL(md_pimd_move_kernel, dim3((N + PIMD_TILE - 1) / PIMD_TILE), dim3(256), lds, st, b, a, (const int *)m.halt.p, step);
+        }
+        return SGPR_OK;
+    });
+    h->lists_valid = false;
+    if (rc_) return rc_;
+    MdHalt r;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
+    if (r.done > 0) {
+        m.run.pimd.info.assign((size_t)PIMD_INFO * r.done, 0.0);
+        HIPCHK(hipMemcpy(m.run.pimd.info.data(), m.pimd.info_d.p, sizeof(double) * PIMD_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
+    }
+    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
+    return SGPR_OK;
+}
+
 // Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last
 // the integrator moves on with the next row of `noise` ([nevals][N][3] standard normal deviates, caller atom order; null:
 // velocity Verlet).  Stops at the first evaluation whose largest covloss reaches `ediff` (<= 0: never): *evals_done
@@ -1299,6 +1486,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     if (!(h->m > 0 && h->has_mu)) return fail(SGPR_E_NOMODEL, "sgpr_md_run: the model has no weights");
     if (m.run.relax.on) return md_relax_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
     if (m.run.neb.on) return md_neb_run(h, nevals, ediff, final_eval, scalars, evals_done, halt_code);
+    if (m.run.pimd.on) return md_pimd_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
     if (!m.run.bcm.members.empty()) return md_committee_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code);
     MdCall c;
     if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
@@ -1466,6 +1654,7 @@ extern "C" int sgpr_md_state(sgpr_model *h, double *positions, double *velocitie
     MdState &m = h->md;
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_state: call sgpr_md_begin first");
     if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_state: the run is a nudged elastic band; sgpr_md_neb_state returns its images");
+    if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_state: the run is a ring polymer; sgpr_md_pimd_state returns its beads");
     if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_state: which = 0 or -1");
     if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_state: no earlier configuration");
     HIPCHK(hipSetDevice(h->device));
@@ -1494,6 +1683,7 @@ extern "C" int sgpr_md_velocities(sgpr_model *h, double *velocities)
     if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_velocities: call sgpr_md_begin first");
     if (m.run.relax.on) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a relaxation");
     if (m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a nudged elastic band; sgpr_md_neb_state returns its images and FIRE's velocity");
+    if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the run is a ring polymer; sgpr_md_pimd_state returns its beads and their velocities");
     if (!m.run.evaluated) return fail(SGPR_E_INVALID, "sgpr_md_velocities: the current configuration has not been evaluated (run with final_eval, or after a halt)");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1535,6 +1725,7 @@ extern "C" int sgpr_md_record(sgpr_model *h, int every, int what)
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run was begun on %d ranks; frames are recorded on one", m.run.world);
     if (every && !m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run has a committee (sgpr_md_committee), which records no frames");
     if (every && m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run is a nudged elastic band (sgpr_md_neb), which records no frames; sgpr_md_neb_state behind a cut call serves trajectories");
+    if (every && m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_record: the run is a ring polymer (sgpr_md_pimd), which records no frames; sgpr_md_pimd_state behind a cut call serves trajectories");
     m.run.rec.every = every;
     m.run.rec.what = every ? what : 0;
     return SGPR_OK;
@@ -1621,6 +1812,7 @@ extern "C" int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, co
     if (!(shrink > 0.0 && shrink < 1.0)) return fail(SGPR_E_INVALID, "sgpr_md_filter: 0 < shrink < 1");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a relaxation (sgpr_md_relax), which applies no filter");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a nudged elastic band (sgpr_md_neb), which applies no filter");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a ring polymer (sgpr_md_pimd), which integrates unfiltered forces");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.run.world);
     HIPCHK(hipSetDevice(h->device));
@@ -1720,6 +1912,7 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a barostat (sgpr_md_barostat); the bias runs at constant cell, the host loop around calculate() serves a biased NPT run");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a relaxation (sgpr_md_relax); the bias serves dynamics only, the host loop around calculate() serves a biased relaxation");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a nudged elastic band (sgpr_md_neb); the bias serves dynamics only, the host loop around calculate() serves a biased band");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a ring polymer (sgpr_md_pimd), whose loop does not apply a bias; the host loop around calculate() serves it");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a committee (sgpr_md_committee), whose loop does not apply a bias; the host loop around calculate() serves it");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run was begun on %d ranks; the bias runs on one, the host loop around calculate() serves sharded runs", m.run.world);
     if (pace < 1 || capacity < 1 || capacity > (1 << 28) || nhills < 0 || nhills > capacity || (nhills > 0 && !hills_cv))

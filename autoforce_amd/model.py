@@ -901,6 +901,79 @@ class SGPRModel:
             check(_lib.load().sgpr_md_neb_info(self._h, 0, done, ptr(out)))
         return out[:, :K].copy(), out[:, 16:16 + K].copy()
 
+    PIMD_MAX = 32   # beads of a polymer (md_pimd.inc)
+
+    def pimd_begin(self, numbers, beads, cell, pbc, masses, velocities=None, dt=1.0, kT=0.0, friction=1e-3, pile_lambda=1.0, seed=0):
+        """A ring polymer of P beads into device memory (sgpr_md_pimd: path-integral MD under BAOAB with the PILE-L thermostat,
+        md_pimd.inc; workloads.pimd_baoab is the host twin and the definition).  beads [P, N, 3], velocities [P, N, 3] (None:
+        zeros): the P <= 32 beads share numbers, cell (constant), pbc and masses and are evaluated by this one model, one plain
+        step each per evaluation of the polymer.  kT: the physical one (the polymer is sampled at P kT); dt, kT, friction in the
+        units of workloads.FS / ase_shim.kB, as md_begin takes them; friction: the centroid's, pile_lambda: gamma_k =
+        2 pile_lambda w_k of the other modes (friction = 0 with 1/2: TRPMD, with 0: microcanonical RPMD).  seed != 0:
+        md_run(noise=None) draws the deviates on the device — those md_deviates returns for t = n P + k.
+          md_run then serves the polymer — noise [nevals, P, N, 3] (mode k, caller atom order); rows carry the mean energy of
+        the beads in column 0, the bead (1 ... P) with the largest covloss in 1, overflow, largest covloss, sum m v^2 over all
+        beads (closed | before the closing half kick) in 10..13, the centroid-virial kinetic energy in 14, the spring energy in
+        15; code 1 = the covloss gate (nothing moved) —; pimd_state returns the beads, pimd_info the energies and largest
+        covlosses per bead of the last call's evaluations.  One rank, constant cell; no other thermostat, committee, bias,
+        filter, mask or frame record."""
+        numbers = i32(numbers)
+        N = len(numbers)
+        R = f64(np.asarray(beads, float))
+        if R.ndim != 3 or R.shape[1:] != (N, 3):
+            raise ValueError(f"pimd_begin: beads is [P, N, 3] for N = {N} atoms, not {R.shape}")
+        P = len(R)
+        if P < 1:
+            raise ValueError("pimd_begin: a polymer has at least one bead")
+        v = None if velocities is None else f64(np.asarray(velocities, float)).reshape(P, N, 3)
+        md = dict(N=N, numbers=numbers, cell=f64(np.asarray(cell, float).reshape(3, 3)), masses=f64(masses), hdt=0.5 * dt, pimd=P, fixed=None)
+        self._md = None   # (no run until sgpr_md_pimd has accepted the polymer)
+        self.generation += 1
+        lib = _lib.load()
+        check(lib.sgpr_md_begin(self._h, N, ptr(numbers), ptr(f64(R[0])), ptr(md["cell"]), ptr(i32(np.asarray(pbc, bool).astype(np.int32))),
+                                ptr(md["masses"]), None, float(dt), float(friction), float(kT)))
+        try:
+            check(lib.sgpr_md_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+            check(lib.sgpr_md_pimd(self._h, P, ptr(R), ptr(v), float(kT), float(friction), float(pile_lambda)))
+        except Exception:
+            lib.sgpr_md_end(self._h)   # (a refused polymer leaves no half-begun run behind: _md stays None and md_run says so)
+            raise
+        md["t"] = 0
+        self._md = md
+
+    def pimd_state(self, which=0, results=False):
+        """The P beads of the current configuration (which = -1: the one evaluated before it): dict(positions [P, N, 3],
+        velocities_pre [P, N, 3] before the closing half kick, pending: whether one is due); with results=True — where the last
+        md_run evaluated that configuration: which = 0 after a halted or `final` call, -1 after one that ran through — also
+        forces [P, N, 3], beta [P, N], energy [P], stress [P, 6] and velocities [P, N, 3], the closing half kick applied."""
+        if not (getattr(self, "_md", None) and self._md.get("pimd")):
+            raise RuntimeError("pimd_state: no polymer on this model: pimd_begin first (a refused pimd_begin leaves none)")
+        N, P = self._md["N"], self._md["pimd"]
+        x, v = np.empty((P, N, 3)), np.empty((P, N, 3))
+        packed = np.empty((P, 4 * N + 11)) if results else None
+        check(_lib.load().sgpr_md_pimd_state(self._h, ptr(x), ptr(v), ptr(packed), int(which)))
+        pending = self._md["t"] + which > 0
+        out = dict(positions=x, velocities_pre=v, pending=pending)
+        if results:
+            stress = np.zeros((P, 6))
+            for i in range(P):
+                check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[i, 4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress[i])))
+            F = packed[:, :3 * N].reshape(P, N, 3).copy()
+            out.update(forces=F, beta=packed[:, 3 * N:4 * N].copy(), energy=packed[:, 4 * N].copy(), stress=stress,
+                       velocities=v + self._md["hdt"] * F / self._md["masses"][None, :, None] if pending else v.copy())
+        return out
+
+    def pimd_info(self):
+        """(E [done, P], covmax [done, P]): energy and largest covloss of every bead at the evaluations of the last md_run that
+        stand (sgpr_md_pimd_info)."""
+        if not (getattr(self, "_md", None) and self._md.get("pimd")):
+            raise RuntimeError("pimd_info: no polymer on this model: pimd_begin first (a refused pimd_begin leaves none)")
+        P, done = self._md["pimd"], self._md.get("pimd_done", 0)
+        out = np.zeros((done, 64))
+        if done:
+            check(_lib.load().sgpr_md_pimd_info(self._h, 0, done, ptr(out)))
+        return out[:, :P].copy(), out[:, 32:32 + P].copy()
+
     def md_deviates(self, t_first, count):
         out = np.empty((int(count), self._md["N"], 3))
         check(_lib.load().sgpr_md_deviates(self._h, int(t_first), int(count), ptr(out)))
@@ -908,7 +981,7 @@ class SGPRModel:
 
     def md_run(self, nevals, noise=None, ediff=0.0, final=False):
         """Evaluate `nevals` configurations starting with the current one, integrating between them on the device
-        (noise: [nevals, N, 3] standard normal deviates or None).  Returns (scalars [done, 16], halt code): code 1 =
+        (noise: [nevals, N, 3] standard normal deviates or None; a polymer, pimd_begin: [nevals, P, N, 3]).  Returns (scalars [done, 16], halt code): code 1 =
         the last row's largest covloss reached ediff and the state is that configuration (calculator/active.py:492-499),
         2 = a neighbour capacity overflowed at evaluation `done` (repeat the call), 3 (a relaxation, relax_begin) = the last
         row's configuration has converged and is the state."""
@@ -916,7 +989,7 @@ class SGPRModel:
             raise RuntimeError("md_run: no run on this model: md_begin, relax_begin or neb_begin first (a refused begin leaves none)")
         N = self._md["N"]
         if noise is not None:
-            noise = f64(noise).reshape(-1, N, 3)
+            noise = f64(noise).reshape((-1, self._md["pimd"], N, 3) if self._md.get("pimd") else (-1, N, 3))
             assert len(noise) >= nevals, "one row of noise per evaluation"
         sc = np.zeros((nevals, self.MD_SCALARS))
         done, code = C.c_int(0), C.c_int(0)
@@ -926,7 +999,9 @@ class SGPRModel:
         self._md["record_call"] = self._md.get("record")   # (what this call recorded: md_frames)
         if self._md.get("neb"):   # (the rows of the band record that stand: neb_info)
             self._md["neb_done"] = done.value
-        if self._md.get("npt"):   # (where the state is now: sgpr_md_run's rules)
+        if self._md.get("pimd"):   # (the rows of the polymer's record that stand: pimd_info)
+            self._md["pimd_done"] = done.value
+        if self._md.get("npt") or self._md.get("pimd"):   # (where the state is now: sgpr_md_run's rules)
             t0 = self._md["t"]
             self._md["run"] = (t0, done.value)
             self._md["t"] = t0 + (done.value - 1 if (code.value in (1, 3) or (code.value == 0 and final)) else done.value)

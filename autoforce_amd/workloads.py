@@ -139,6 +139,8 @@ class PairTeacher:
 
 
 FS = 0.09822694788464063  # ase.units.fs: 1 fs in A sqrt(amu/eV)
+# hbar in eV (A sqrt(amu/eV)), from the CODATA-2014 numbers of ase.units: h / 2 pi / e * 1e10 sqrt(e / amu) (md_pimd.inc: PIMD_HBAR)
+HBAR = 0.06465415105180661
 MASS = {1: 1.008, 3: 6.94, 8: 15.999, 9: 18.998, 11: 22.99, 12: 24.305, 14: 28.085, 15: 30.974, 16: 32.06, 17: 35.45,
         40: 91.224, 57: 138.905}
 
@@ -1547,6 +1549,168 @@ def neb_fire(calc, numbers, images, cell, pbc, evals, fmax, k=0.1, climb=False, 
         else:   # (selected, not computed)
             v = np.where(fx[None], 0.0, v)
             R[1:-1] = np.where(fx[None], R[1:-1], R[1:-1] + cd * v)
+        n += 1
+
+
+# ---- path-integral MD: a ring polymer under BAOAB with the PILE-L thermostat in the device's operations (pimd_baoab; md_pimd.inc:
+# md_pimd_sums_kernel, md_pimd_gate_kernel and md_pimd_move_kernel)
+PIMD_MAX = 32   # beads of a polymer
+
+
+def pimd_tables(P, kT, dt, friction, pile_lambda):
+    """The tables of a polymer run as sgpr_md_pimd computes them, once, on the host — scalar by scalar through the C library's
+    sqrt, cos, sin and exp (the math module), in its operations: C [P, P], the orthonormal real DFT of the PILE paper's eq. 18
+    (column 0: sqrt(1/P); 1 <= k < P/2: sqrt(2/P) cos(2 pi jk / P); k = P/2: sqrt(1/P) (-1)^j; k > P/2: sqrt(2/P) sin(2 pi jk / P),
+    the argument reduced: jk mod P), w_k = 2 w_P sin(k pi / P) with w_P = P kT / hbar, the free ring polymer's propagator over
+    dt / 2 — cs = cos(w_k dt/2), sn = sin(w_k dt/2) / w_k (k = 0: dt/2), wsn = w_k sin(w_k dt/2) — and the thermostat's
+    c1_k = exp(-gamma_k dt), c2_k = sqrt(1 - c1_k^2) with gamma_0 = friction, gamma_k = 2 pile_lambda w_k."""
+    import math
+    dP, hdt = float(P), 0.5 * dt
+    wP = (dP * kT) / HBAR
+    C = np.zeros((P, P))
+    for j in range(P):
+        for k in range(P):
+            arg = (2.0 * math.pi * float((j * k) % P)) / dP
+            if k == 0:
+                c = math.sqrt(1.0 / dP)
+            elif 2 * k < P:
+                c = math.sqrt(2.0 / dP) * math.cos(arg)
+            elif 2 * k == P:
+                c = -math.sqrt(1.0 / dP) if j & 1 else math.sqrt(1.0 / dP)
+            else:
+                c = math.sqrt(2.0 / dP) * math.sin(arg)
+            C[j, k] = c
+    w, cs, sn, wsn, c1, c2 = (np.zeros(P) for _ in range(6))
+    for k in range(P):
+        w[k] = (2.0 * wP) * math.sin((float(k) * math.pi) / dP) if k else 0.0
+        s = math.sin(w[k] * hdt)
+        cs[k] = math.cos(w[k] * hdt)
+        sn[k] = s / w[k] if k else hdt
+        wsn[k] = w[k] * s
+        g = (2.0 * pile_lambda) * w[k] if k else friction
+        c1[k] = math.exp(-(g * dt))
+        c2[k] = math.sqrt(1.0 - c1[k] * c1[k])
+    return dict(C=C, w=w, cs=cs, sn=sn, wsn=wsn, c1=c1, c2=c2, wP=wP)
+
+
+def _pimd_modes(C, a, inverse=False):
+    """a [P, N, 3] to normal modes, out_k = sum_j C[j][k] a_j (inverse: out_j = sum_k C[j][k] a_k), every sum sequentially in
+    the order 0, 1, ..., P - 1: s = C a_0; s = s + C a_q."""
+    M = C if inverse else C.T    # M[o][q]: the coefficient of input q in output o
+    s = M[:, 0][:, None, None] * a[0][None]
+    for q in range(1, len(a)):
+        s = s + M[:, q][:, None, None] * a[q][None]
+    return s
+
+
+def _pimd_free(tb, hdt, x, v):
+    """A(dt / 2): the exact free ring polymer in normal modes — mode 0 drifts, mode k >= 1 rotates."""
+    cs, sn, wsn = (tb[q][:, None, None] for q in ("cs", "sn", "wsn"))
+    xa, va = cs * x + sn * v, cs * v - wsn * x
+    xa[0], va[0] = x[0] + hdt * v[0], v[0]
+    return xa, va
+
+
+def pimd_baoab(calc, numbers, beads, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, pile_lambda=1.0, vel=None, rng=None, seed=1,
+               masses=None, species=None, noise=None, update=None):
+    """Path-integral MD in numpy around any calculator with the ASE surface (forces and energy through the atoms; calc.get_covloss()
+    where it has one), one call per bead per evaluation: a ring polymer of P beads (beads [P, N, 3], raw coordinates, no minimum
+    image in the springs) at the physical temperature T, sampled at kT_P = P kB T with w_P = kT_P / hbar,
+        H_P = sum_j sum_i [ m_i v_ij^2 / 2 + m_i w_P^2 / 2 |x_ij - x_i,j+1|^2 ] + sum_j V(x_j),
+    integrated by BAOAB with the PILE-L thermostat (Ceriotti, Parrinello, Markland, Manolopoulos, J. Chem. Phys. 133, 124104; Liu,
+    Li, Liu, J. Chem. Phys. 145, 024103) — the host twin of the device loop (sgpr_md_pimd: md_pimd.inc) in its operations and
+    summation order, bit for bit, and the definition.  By evaluation index n, behind the forces F_n of every bead: the closing half
+    kick of step n - 1 (not at the start), the opening half kick v += (dt/2) F_n / m, to normal modes (pimd_tables' C), A(dt/2),
+    O: v~_k <- c1_k v~_k + c2_k sqrt(kT_P / m) xi, A(dt/2), and back.  friction: the centroid's gamma_0; gamma_k = 2 pile_lambda w_k
+    (friction = 0 with pile_lambda = 1/2: TRPMD, with 0: microcanonical RPMD).  At P = 1 (C = 1) this is langevin_nvt's loop,
+    operation for operation, on the same random stream.
+      vel [P, N, 3]: the beads' velocities (None: Maxwell-Boltzmann at P T from rng, the mean momentum of every bead removed);
+    one rng.normal(size=(P, N, 3)) per step (mode k, atom, component) — or noise(n): the deviates that move evaluation n on;
+    masses: [N] (None: the MASS table); species: the model's table (the order of the sums over atoms: species-sorted, stable).
+    update(out): called with every evaluation's dict before anything moves; a true return means the model behind `calc` has
+    been dealt with (the covloss gate of the device loop and calculate() behind it): the same configuration is evaluated again
+    — the repeat is not offered to update.
+      Yields a dict per evaluation n = 0 ... steps: n, energy (the mean of the beads'), energies [P], covmax [P], cbead (1 ... P:
+    the largest covloss, the earlier bead on a tie), mv2 and mv2_pre (sum m v^2 over all beads after | before the closing half
+    kick), cv (the centroid-virial kinetic energy 3 N kT / 2 - (1 / 2P) sum (x - xbar).F), spring (the spring energy), beads,
+    forces, velocities_pre and velocities (closed) [P, N, 3] (copies)."""
+    from .ase_shim import Atoms, kB
+    rng = np.random.default_rng(seed) if rng is None else rng
+    R = np.array(beads, float)
+    P, N = R.shape[0], len(numbers)
+    if R.shape != (P, N, 3) or P < 1 or P > PIMD_MAX:
+        raise ValueError(f"pimd: beads is [P, N, 3] with 1 <= P <= {PIMD_MAX} for N = {N} atoms, not {R.shape}")
+    mass = (np.array([MASS[int(z)] for z in numbers]) if masses is None else np.asarray(masses, float)).reshape(N, 1)
+    kT = kB * temperature
+    dP = float(P)
+    kTP = dP * kT
+    dt = dt_fs * FS
+    hdt = 0.5 * dt
+    tb = pimd_tables(P, kT, dt, friction, pile_lambda)
+    C = tb["C"]
+    wP2 = tb["wP"] * tb["wP"]
+    sq = np.sqrt(kTP / mass)
+    if vel is None:
+        vel = rng.normal(size=(P, N, 3)) * sq
+        for j in range(P):
+            vel[j] -= (mass * vel[j]).sum(0) / mass.sum()
+    v = np.array(vel, float).reshape(P, N, 3)
+    table = sorted(set(int(z) for z in numbers)) if species is None else [int(z) for z in species]
+    order = np.argsort([table.index(int(z)) if int(z) in table else len(table) for z in numbers], kind="stable")
+    m1 = mass[:, 0]
+
+    def dsum(vals):
+        return _device_order_sum(vals[order])
+
+    def rows(u, w):
+        t = u * w
+        return (t[:, 0] + t[:, 1]) + t[:, 2]
+
+    n, repeat = 0, False
+    while n <= steps:
+        F, E, cov = np.zeros((P, N, 3)), [0.0] * P, [0.0] * P
+        for j in range(P):
+            at = Atoms(numbers, R[j].copy(), np.array(cell, float), pbc, velocities=v[j], masses=m1)
+            at.calc = calc
+            F[j] = np.asarray(at.get_forces(apply_constraint=False), float)
+            E[j] = float(at.get_potential_energy())
+            c = np.asarray(calc.get_covloss(), float) if hasattr(calc, "get_covloss") else np.zeros(0)
+            cov[j] = float(c.max()) if c.size else 0.0
+        kick = (hdt * F) / mass
+        vc = v + kick if n > 0 else v       # closes step n - 1: the velocity an observer sees at evaluation n
+        xbar = R[0]
+        for j in range(1, P):
+            xbar = xbar + R[j]
+        xbar = xbar / dP
+        Es, kc, kp, cv, sp = E[0], 0.0, 0.0, 0.0, 0.0
+        cbead = 0
+        for j in range(P):
+            if j:
+                Es = Es + E[j]
+                if cov[j] > cov[cbead]:
+                    cbead = j
+            d, e = R[j] - xbar, R[j] - R[(j + 1) % P]
+            # (the device combines the beads from the first one: x = s_0, x = x + s_j)
+            parts = (dsum(m1 * rows(vc[j], vc[j])), dsum(m1 * rows(v[j], v[j])), dsum(rows(d, F[j])), dsum(m1 * rows(e, e)))
+            kc, kp, cv, sp = parts if j == 0 else (kc + parts[0], kp + parts[1], cv + parts[2], sp + parts[3])
+        out = dict(n=n, energy=Es / dP, energies=np.array(E), covmax=np.array(cov), cbead=cbead + 1, mv2=kc, mv2_pre=kp,
+                   cv=(1.5 * float(N)) * kT - cv / (2.0 * dP), spring=(0.5 * wP2) * sp, beads=R.copy(), forces=F, velocities_pre=v.copy(),
+                   velocities=np.array(vc))
+        if update is not None and not repeat:
+            if update(out):
+                repeat = True
+                continue
+        repeat = False
+        yield out
+        if n == steps:
+            return
+        v2 = vc + kick                                                   # B
+        xt, vt = _pimd_modes(C, R), _pimd_modes(C, v2)
+        xt, vt = _pimd_free(tb, hdt, xt, vt)                             # A
+        xi = rng.normal(size=(P, N, 3)) if noise is None else np.asarray(noise(n), float).reshape(P, N, 3)
+        vt = tb["c1"][:, None, None] * vt + (tb["c2"][:, None, None] * sq[None]) * xi   # O
+        xt, vt = _pimd_free(tb, hdt, xt, vt)                             # A
+        R, v = _pimd_modes(C, xt, inverse=True), _pimd_modes(C, vt, inverse=True)
         n += 1
 
 

@@ -473,6 +473,40 @@ int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double fmax, doub
 int sgpr_md_neb_reset(sgpr_model *h);
 int sgpr_md_neb_state(sgpr_model *h, double *positions, double *velocities, double *packed, int which);
 int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out);
+/* Path-integral molecular dynamics inside the device loop (md_pimd.inc; the reference's calculators declare the mode —
+ * ActiveCalculator(nbeads=P) — and are driven bead by bead from outside).  A ring polymer of P beads, 1 <= P <= 32, all
+ * evaluated by this one handle; physical temperature T, the polymer sampled at kT_P = P kT with w_P = kT_P / hbar (the RPMD
+ * convention; hbar = 0.06465415105180661 in eV, A, amu: the units of the run):
+ *     H_P = sum_j sum_i [ m_i v_ij^2 / 2 + m_i w_P^2 / 2 |x_ij - x_i,j+1|^2 ] + sum_j V(x_j)       (raw coordinates, no minimum image)
+ * integrated by BAOAB with the PILE-L thermostat (Ceriotti et al., J. Chem. Phys. 133, 124104; Liu, Li, Liu, J. Chem. Phys.
+ * 145, 024103): behind the forces of evaluation n the closing half kick of step n - 1, the opening half kick, then in the normal
+ * modes of the free ring polymer (x~_k = sum_j C[j][k] x_j, w_k = 2 w_P sin(k pi / P)) the exact free propagation over dt / 2,
+ * v~_k <- c1_k v~_k + c2_k sqrt(kT_P / m) xi with c1_k = exp(-gamma_k dt), gamma_0 = friction, gamma_k = 2 lambda w_k, and the
+ * free propagation over dt / 2 again.  friction = 0, lambda = 1/2: TRPMD; friction = lambda = 0: microcanonical RPMD.  At P = 1
+ * the scheme is sgpr_md_begin's Langevin step, operation for operation.
+ * sgpr_md_pimd        after sgpr_md_begin (positions: any bead — they bind the system; its masses and dt hold; its velocities,
+ *                     friction and kT are replaced by this call's), before the first sgpr_md_run.  positions[P][N][3],
+ *                     velocities[P][N][3] (NULL: zeros), caller atom order.  SGPR_E_INVALID: P < 1 or P > 32, a thermostat or
+ *                     barostat, a run that has started, kT <= 0, friction < 0, lambda < 0.  SGPR_E_UNSUPPORTED: more than one
+ *                     rank, a committee, a bias, a filter, held components, an armed frame record, a relaxation, a band.
+ * sgpr_md_run         evaluates the polymer (P plain steps of this handle, each rebuilding its candidate lists) and moves it;
+ *                     noise[nevals][P][N][3]: the deviates of mode k, caller atom order (NULL: none, or — sgpr_md_seed — those
+ *                     sgpr_md_deviates returns for t = n P + k).  Halt code 1: the largest covloss over all beads reached ediff
+ *                     (nothing moved), 2: a capacity overflowed at some bead.  scalars[.][0] = the mean of the beads' energies,
+ *                     [1] = the bead (1 ... P) that carried the largest covloss, [10] overflow, [11] largest covloss, [12] | [13]
+ *                     sum m v^2 over all beads after | before the closing half kick, [14] the centroid-virial kinetic energy
+ *                     3 N kT / 2 - (1 / 2P) sum_j sum_i (x_ij - xbar_i).F_ij, [15] the spring energy; the others zero.
+ * sgpr_md_pimd_state  the P beads, caller atom order: positions[P][N][3] of the current configuration (which = 0) or the one
+ *                     before it (-1), velocities_pre[P][N][3] before its closing half kick, packed[P][4N + 11] the beads'
+ *                     results where the last sgpr_md_run evaluated that configuration; any of them NULL.  sgpr_md_state and
+ *                     sgpr_md_velocities refuse a polymer.
+ * sgpr_md_pimd_info   out[count][64] = E[32] | covmax[32] per evaluation first ... first + count - 1 of the last sgpr_md_run
+ *                     (0 = its first) among those that stand.
+ * sgpr_md_fix, sgpr_md_thermostat, sgpr_md_barostat, sgpr_md_relax, sgpr_md_neb, sgpr_md_committee, sgpr_md_filter, sgpr_md_meta
+ * and sgpr_md_record behind sgpr_md_pimd are refused. */
+int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const double *velocities, double kT, double friction, double lambda);
+int sgpr_md_pimd_state(sgpr_model *h, double *positions, double *velocities_pre, double *packed, int which);
+int sgpr_md_pimd_info(sgpr_model *h, int first, int count, double *out);
 /* Held atoms and components (after sgpr_md_begin; before sgpr_md_thermostat, sgpr_md_relax and the first sgpr_md_run):
  * fixed3N[N][3] in caller atom order, nonzero = that Cartesian component of that atom is held — all three of an atom for
  * ase.constraints.FixAtoms, the chosen ones for FixCartesian.  NULL or all zeros: nothing is held, and the run launches what a
