@@ -287,20 +287,17 @@ struct MdRun {
         std::vector<double> info;  // weights | largest covlosses of the last evaluation whose results stand (sgpr_md_committee_info; empty: none)
         bool cell = false;         // option "md_committee_cell" of THIS run: a committee and a barostat may meet on it (off: each refuses the other)
     } bcm;
-    // the nudged elastic band (sgpr_md_neb, md_neb.inc): K interior images evaluated by this one handle per evaluation of the band
-    struct Neb {
-        bool on = false;
-        int K = 0;
-        NebCell cell = {};
-        std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_neb_info)
-    } neb;
-    // path-integral MD (sgpr_md_pimd, md_pimd.inc): P beads of a ring polymer evaluated by this one handle per evaluation
-    struct Pimd {
-        bool on = false;
-        int P = 0;
-        double kT = 0.0, wP2 = 0.0;   // the physical kT; w_P^2 = (P kT / hbar)^2
-        std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_pimd_info)
-    } pimd;
+    // a run whose configuration is R replicas evaluated by this one handle per evaluation (md_replica_run, md_host.inc): the
+    // interior images of a band or the beads of a polymer.  What follows in `neb` and `pimd` is the mode's own.
+    struct Rep {
+        enum Kind { NONE, BAND, POLYMER } kind = NONE;
+        int R = 0, width = 0;       // replicas; doubles in a row of the record: NEB_INFO = 16 | 16, PIMD_INFO = 32 | 32
+        std::vector<double> info;   // E | covmax per evaluation of the last call that stands (sgpr_md_neb_info, sgpr_md_pimd_info)
+    } rep;
+    // the nudged elastic band (sgpr_md_neb, md_neb.inc): rep.R interior images
+    struct Neb { bool on = false; NebCell cell = {}; } neb;
+    // path-integral MD (sgpr_md_pimd, md_pimd.inc): rep.R beads of a ring polymer
+    struct Pimd { bool on = false; double kT = 0.0, wP2 = 0.0; } pimd;   // the physical kT; w_P^2 = (P kT / hbar)^2
     static long long meta_dep(long long n, long long pace) { return (n + pace - 1) / pace; }   // deposits of the configurations below n
     long long meta_slot(long long n) const { return meta.pre + meta_dep(n, meta.pace) - meta_dep(meta.base, meta.pace); }
     // multiples of `every` in [a, b): the slot of a frame is its ordinal among the call's recorded evaluations
@@ -362,23 +359,23 @@ struct MdState {
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
         DevBuf<double> info_d;     // [rows][32] weights | largest covlosses per evaluation of a call
     } bcm;
-    struct {                       // band, velocity and results in caller atom order
-        DevBuf<double> X;          // [RLX_RING][K][N][3] the band by evaluation index % RLX_RING
+    struct {                       // the R replicas of a band or a polymer (MdRun::Rep) and their results, in caller atom order
+        DevBuf<double> X;          // [RLX_RING][R][N][3] the replicas by evaluation index % RLX_RING
+        DevBuf<double> P;          // [RLX_RING][R][4N + 11] packed results of the replicas' plain steps
+        DevBuf<double> info_d;     // [rows][width] E | covmax per evaluation of a call
+    } rep;
+    struct {                       // the band's own, caller atom order
         DevBuf<double> V;          // [K][N][3] FIRE's velocity
-        DevBuf<double> P;          // [RLX_RING][K][4N + 11] packed results of the images' plain steps
         DevBuf<double> ends;       // [2][N][3] images 0 and K + 1
         DevBuf<double> sums;       // [K][NEB_SUMS] md_neb_sums_kernel's output
         DevBuf<double> coef;       // [K][2] the projection's coefficients
         DevBuf<char> par;          // one NebFirePar: cell, FIRE's keywords, spring constant, climb — md_neb_fire_kernel's constants
-        DevBuf<double> info_d;     // [rows][NEB_INFO] E | covmax per evaluation of a call
     } neb;
-    struct {                       // beads, velocities and results in caller atom order
-        DevBuf<double> X, V;       // [RLX_RING][P][N][3] by evaluation index % RLX_RING; V: before the closing half kick
-        DevBuf<double> P;          // [RLX_RING][P][4N + 11] packed results of the beads' plain steps
+    struct {                       // the polymer's own
+        DevBuf<double> V;          // [RLX_RING][P][N][3] beside rep.X, caller atom order: before the closing half kick
         DevBuf<double> sums;       // [P][PIMD_SUMS] md_pimd_sums_kernel's output
         DevBuf<double> tab;        // C[P][P] | cos | sin / w | w sin | c1 | c2: the host's tables (sgpr_md_pimd)
         DevBuf<double> sq;         // [N] sqrt(kT_P / m), sorted order
-        DevBuf<double> info_d;     // [rows][PIMD_INFO] E | covmax per evaluation of a call
     } pimd;
     NptSlot *slot(long long n) const { return (NptSlot *)npt.ring.p + (n & 3); }
     const unsigned char *fix() const { return run.fix.n ? fixed.mask.p : nullptr; }

@@ -2,11 +2,11 @@
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
 // _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _committee (the Bayesian committee), _neb
-// (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation, a committee, a
-// band and a polymer to md_relax_run, md_committee_run, md_neb_run and md_pimd_run; the five share the look-ahead driver and the
-// frame of a call (MdCall).  The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc,
-// md_pimd.inc and md_meta.inc (the one small kernel of
-// sgpr_md_filter_push stands beside it, further down).
+// (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
+// to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
+// the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
 // from util/aseutil.py:11-20) and crosses into the calculator once per step.  Here the state (positions, velocities)
@@ -732,7 +732,7 @@ static void md_record_close(MdState &m, const MdHalt &r)
     m.run.rec.call_count = (int)MdRun::rec_between(m.run.rec.call_t0, m.run.rec.call_t0 + lim, m.run.rec.call_every);
 }
 
-// ---- the frame of the four run functions: md_call_open | the mode's checks, md_prepare_call, its checked pass | md_call_start |
+// ---- the frame of the three run functions (md_relax_run, md_committee_run, md_replica_run): md_call_open | the mode's checks, md_prepare_call, its checked pass | md_call_start |
 // md_enqueue_ahead | md_call_close | the mode's record of the call | md_finish_call ----
 struct MdCall {
     hipStream_t st = nullptr;
@@ -1089,6 +1089,136 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     return SGPR_OK;
 }
 
+// ---- replicas: a run whose configuration is R copies of the system evaluated by this one handle (MdRun::Rep) — the interior
+// images of a band, the beads of a polymer.  Positions and packed results lie in rings of RLX_RING slots in caller atom order
+// (MdState::rep); attach, readers and the frame of sgpr_md_run are here, the mode's own buffers and launches with the mode ----
+typedef MdRun::Rep::Kind RepKind;
+static const char *rep_attach_name(RepKind kind) { return kind == MdRun::Rep::BAND ? "sgpr_md_neb" : "sgpr_md_pimd"; }
+
+// The close of an attach function (`who`): the rings, every slot the R initial replicas x0[R][N][3] (what runs behind a halt
+// evaluates stale slots), and the run is one of `kind` with rows of `width` in its record.
+static int md_replica_attach(sgpr_model *h, const char *who, RepKind kind, int R, int width, const double *x0)
+{
+    MdState &m = h->md;
+    const size_t RN3 = (size_t)3 * m.run.N * (size_t)R;
+    if (m.rep.X.alloc(RN3 * RLX_RING) || m.rep.P.alloc((size_t)sgpr_packed_len(m.run.N) * (size_t)R * RLX_RING))
+        return fail(SGPR_E_NODEVICE, "%s: device allocation failed", who);
+    for (int r = 0; r < RLX_RING; r++) HIPCHK(hipMemcpy(m.rep.X.p + RN3 * r, x0, sizeof(double) * RN3, hipMemcpyHostToDevice));
+    m.run.rep.kind = kind; m.run.rep.R = R; m.run.rep.width = width;
+    m.run.rep.info.clear();
+    m.run.ring = RLX_RING;
+    return SGPR_OK;
+}
+
+// Behind sgpr_md_neb_state and sgpr_md_pimd_state (`who`): positions[R][N][3] of the current configuration (which = 0) or the one
+// evaluated before it (-1), packed[R][4N + 11] the replicas' results where the last sgpr_md_run evaluated that configuration, and
+// the mode's velocity — one slot (FIRE's, a band) or a ring beside the positions (a polymer).  Any of them NULL.
+static int md_replica_state(sgpr_model *h, const char *who, RepKind kind, double *positions, double *velocities, double *packed, int which)
+{
+    if (!h) return fail(SGPR_E_INVALID, "%s: bad arguments", who);
+    MdState &m = h->md;
+    const bool band = kind == MdRun::Rep::BAND;
+    if (!m.active || m.run.rep.kind != kind) return fail(SGPR_E_INVALID, "%s: call sgpr_md_begin and %s first", who, rep_attach_name(kind));
+    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "%s: which = 0 or -1", who);
+    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "%s: no earlier %s", who, band ? "band" : "configuration");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t R = (size_t)m.run.rep.R, RN3 = (size_t)3 * m.run.N * R, plen = (size_t)sgpr_packed_len(m.run.N);
+    const size_t sl = (size_t)((m.run.t + which + RLX_RING) % RLX_RING);
+    if (positions) HIPCHK(hipMemcpy(positions, m.rep.X.p + RN3 * sl, sizeof(double) * RN3, hipMemcpyDeviceToHost));
+    if (velocities) HIPCHK(hipMemcpy(velocities, band ? m.neb.V.p : m.pimd.V.p + RN3 * sl, sizeof(double) * RN3, hipMemcpyDeviceToHost));
+    if (packed) HIPCHK(hipMemcpy(packed, m.rep.P.p + plen * R * sl, sizeof(double) * plen * R, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// Behind sgpr_md_neb_info and sgpr_md_pimd_info (`who`): out[count][width] = E | covmax, half a row each, of the evaluations
+// first ... first + count - 1 (0 = the call's first) of the last sgpr_md_run among those that stand.
+static int md_replica_info(sgpr_model *h, const char *who, RepKind kind, int first, int count, double *out)
+{
+    if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "%s: bad arguments", who);
+    const MdRun::Rep &rep = h->md.run.rep;
+    if (!h->md.active || rep.kind != kind) return fail(SGPR_E_INVALID, "%s: call sgpr_md_begin and %s first", who, rep_attach_name(kind));
+    const long long have = (long long)(rep.info.size() / (size_t)rep.width);
+    if ((long long)first + count > have)
+        return fail(SGPR_E_INVALID, "%s: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", who, first, (long long)first + count - 1, have);
+    memcpy(out, rep.info.data() + (size_t)rep.width * first, sizeof(double) * (size_t)rep.width * (size_t)count);
+    return SGPR_OK;
+}
+
+// What the mode's launches of one evaluation are given: evaluation j of the call, the value the halt words take for it, whether
+// it is a `final` call's last (nothing moves), the gate, and where its replicas lie.
+struct RepEval {
+    hipStream_t st;
+    int j, step;
+    bool stay;
+    double gate;
+    size_t sl, sn;      // the ring slots of this configuration and the next: those of the mode's own rings too
+    const double *X;    // [R][N][3] the replicas
+    double *P, *Xn;     // [R][4N + 11] their packed results, filled by the plain steps in front; [R][N][3] the next configuration
+    double *info;       // the evaluation's row of the record
+};
+
+// sgpr_md_run for replicas, in the shape of md_relax_run and md_committee_run: every evaluation is R plain steps of the live
+// handle — replica i's caller-order positions in the ring through the handle's own binning kernel, into its own packed buffer;
+// before each the handle is as md_reset_lists leaves it: every replica rebuilds its candidate lists (one list set per replica
+// would save that: not done) — with the mode's kernels behind them: launch(e), a callable inlined here as md_enqueue_ahead inlines
+// its own.  The halts are decided by the second of them on the evaluation itself, before anything moves: what the host has
+// enqueued behind a halt evaluates stale slots and changes nothing.  The halt words count evaluations of the R replicas from the
+// handle's step counter at the call's start (the handle's own counter advances R per evaluation; no plain step reads the words).
+// noise: [nevals][R][N][3] uploaded as it comes into m.noise_raw, or null.
+template <typename Launch>
+static int md_replica_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code,
+                          Launch launch)
+{
+    MdState &m = h->md;
+    MdCall c;
+    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
+    hipStream_t st = c.st;
+    const int RG = RLX_RING, R = m.run.rep.R;
+    const size_t plen = c.plen, N3 = (size_t)3 * c.N, RN3 = N3 * (size_t)R, width = (size_t)m.run.rep.width;
+    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
+    if (m.rep.info_d.alloc(width * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+    HIPCHK(hipMemsetAsync(m.rep.info_d.p, 0, sizeof(double) * width * ((size_t)nevals + 1), st));
+    if (noise) {
+        if (m.noise_raw.alloc(RN3 * (size_t)nevals)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
+        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * RN3 * (size_t)nevals, hipMemcpyHostToDevice, st));
+    }
+    m.run.started = true;
+    m.run.rep.info.clear();
+    if (!h->warm) {   // the checked pass grows capacities: over every replica
+        const size_t sw = (size_t)(m.run.t % RG);
+        for (int i = 0; i < R; i++) {
+            const int rc_ = run_checked(h, m.rep.X.p + RN3 * sw + N3 * i, m.cell.p, m.rep.P.p + plen * (R * sw + i), st);
+            if (rc_) return rc_;
+        }
+        h->warm = true;
+    }
+    md_call_start(h, c);
+    const unsigned step0 = c.step0; const double gate = c.gate;
+    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
+        const size_t sl = (size_t)((m.run.t + j) % RG), sn = (sl + 1) % RG;
+        const RepEval e = {st, j, (int)(step0 + j), final_eval && j == nevals - 1, gate, sl, sn,
+                           m.rep.X.p + RN3 * sl, m.rep.P.p + plen * R * sl, m.rep.X.p + RN3 * sn, m.rep.info_d.p + width * j};
+        for (int i = 0; i < R; i++) {
+            if (const int rl = md_reset_lists(h, st)) return rl;
+            const int re = enqueue_step(h, e.X + N3 * i, m.cell.p, e.P + plen * i, st, nullptr);
+            if (re) return re;
+        }
+        launch(e);
+        return SGPR_OK;
+    });
+    h->lists_valid = false;
+    if (rc_) return rc_;
+    MdHalt r;
+    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
+    if (r.done > 0) {
+        m.run.rep.info.assign(width * r.done, 0.0);
+        HIPCHK(hipMemcpy(m.run.rep.info.data(), m.rep.info_d.p, sizeof(double) * width * (size_t)r.done, hipMemcpyDeviceToHost));
+    }
+    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
+    return SGPR_OK;
+}
+
 // ---- the nudged elastic band (sgpr_md_neb; md_neb.inc has the scheme, workloads.neb_fire is the host twin) ----
 // For the run begun by sgpr_md_begin (any interior image as its positions: they bind the system; masses, velocities, dt,
 // friction and kT are ignored) and, if used, sgpr_md_fix — one mask for every image —, before the first sgpr_md_run.
@@ -1101,7 +1231,7 @@ static int md_neb_init_state(sgpr_model *h)
     double s[RLX_LEN] = {};
     s[RLX_DT] = m.run.relax.par.dt0; s[RLX_A] = m.run.relax.par.astart; s[RLX_NSTEPS] = 0.0; s[RLX_FRESH] = 1.0;
     HIPCHK(hipMemcpy(m.relax.state.p, s, sizeof(s), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(m.neb.V.p, 0, sizeof(double) * 3 * (size_t)m.run.N * (size_t)m.run.neb.K));
+    HIPCHK(hipMemset(m.neb.V.p, 0, sizeof(double) * 3 * (size_t)m.run.N * (size_t)m.run.rep.R));
     return SGPR_OK;
 }
 
@@ -1127,7 +1257,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const int N = m.run.N;
-    const size_t N3 = (size_t)3 * N, plen = (size_t)sgpr_packed_len(N);
+    const size_t N3 = (size_t)3 * N;
     NebCell cl = {};
     HIPCHK(hipMemcpy(cl.h, m.cell.p, sizeof(cl.h), hipMemcpyDeviceToHost));
     for (int k = 0; k < 3; k++) cl.pbc[k] = m.run.pbc[k] ? 1 : 0;
@@ -1163,21 +1293,17 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     for (int k = 0; k < 9; k++) p.h0[k] = cl.h[k];
     p.fmax2 = fmax * fmax;
     p.cf = (double)N; p.cell = 0;
-    // rings of RLX_RING slots, every slot the initial band (what runs behind a halt evaluates stale slots)
-    if (m.neb.X.alloc(N3 * (size_t)K * RLX_RING) || m.neb.V.alloc(N3 * (size_t)K) || m.neb.P.alloc(plen * (size_t)K * RLX_RING) || m.neb.ends.alloc(2 * N3) ||
-        m.neb.sums.alloc((size_t)NEB_SUMS * K) || m.neb.coef.alloc((size_t)2 * K) || m.relax.state.alloc(RLX_LEN) || m.neb.par.alloc(sizeof(NebFirePar)))
+    if (m.neb.V.alloc(N3 * (size_t)K) || m.neb.ends.alloc(2 * N3) || m.neb.sums.alloc((size_t)NEB_SUMS * K) || m.neb.coef.alloc((size_t)2 * K) ||
+        m.relax.state.alloc(RLX_LEN) || m.neb.par.alloc(sizeof(NebFirePar)))
         return fail(SGPR_E_NODEVICE, "sgpr_md_neb: device allocation failed");
-    for (int r = 0; r < RLX_RING; r++)
-        HIPCHK(hipMemcpy(m.neb.X.p + N3 * (size_t)K * r, positions + N3, sizeof(double) * N3 * K, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.neb.ends.p, positions, sizeof(double) * N3, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.neb.ends.p + N3, positions + N3 * (size_t)(K + 1), sizeof(double) * N3, hipMemcpyHostToDevice));
     NebFirePar par = {};
     par.cell = cl; par.p = p; par.kspr = k_spring; par.climb = climb ? 1 : 0;
     HIPCHK(hipMemcpy(m.neb.par.p, &par, sizeof(par), hipMemcpyHostToDevice));
+    if (const int ra = md_replica_attach(h, "sgpr_md_neb", MdRun::Rep::BAND, K, NEB_INFO, positions + N3)) return ra;
     m.run.relax.par = p;
-    m.run.neb.cell = cl; m.run.neb.K = K;
-    m.run.neb.on = true; m.run.ring = RLX_RING;
-    m.run.neb.info.clear();
+    m.run.neb.cell = cl; m.run.neb.on = true;
     return md_neb_init_state(h);
 }
 
@@ -1197,97 +1323,33 @@ extern "C" int sgpr_md_neb_reset(sgpr_model *h)
 // (a halted or `final` call: which = 0; a call that ran through: which = -1).  Any of them NULL.
 extern "C" int sgpr_md_neb_state(sgpr_model *h, double *positions, double *velocities, double *packed, int which)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: bad arguments");
-    MdState &m = h->md;
-    if (!m.active || !m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: call sgpr_md_begin and sgpr_md_neb first");
-    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: which = 0 or -1");
-    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_neb_state: no earlier band");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N3 = (size_t)3 * m.run.N, plen = (size_t)sgpr_packed_len(m.run.N), K = (size_t)m.run.neb.K;
-    const size_t sl = (size_t)((m.run.t + which + RLX_RING) % RLX_RING);
-    if (positions) HIPCHK(hipMemcpy(positions, m.neb.X.p + N3 * K * sl, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
-    if (velocities) HIPCHK(hipMemcpy(velocities, m.neb.V.p, sizeof(double) * N3 * K, hipMemcpyDeviceToHost));
-    if (packed) HIPCHK(hipMemcpy(packed, m.neb.P.p + plen * K * sl, sizeof(double) * plen * K, hipMemcpyDeviceToHost));
-    return SGPR_OK;
+    return md_replica_state(h, "sgpr_md_neb_state", MdRun::Rep::BAND, positions, velocities, packed, which);
 }
 
 // The band record of the last sgpr_md_run: out[count][32] = E[16] | covmax[16] (image i at entry i - 1, the rest zero) of its
 // evaluations first ... first + count - 1 (0 = the call's first) among those that stand.
 extern "C" int sgpr_md_neb_info(sgpr_model *h, int first, int count, double *out)
 {
-    if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: bad arguments");
-    const MdState &m = h->md;
-    if (!m.active || !m.run.neb.on) return fail(SGPR_E_INVALID, "sgpr_md_neb_info: call sgpr_md_begin and sgpr_md_neb first");
-    const long long have = (long long)(m.run.neb.info.size() / NEB_INFO);
-    if ((long long)first + count > have)
-        return fail(SGPR_E_INVALID, "sgpr_md_neb_info: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", first, (long long)first + count - 1, have);
-    memcpy(out, m.run.neb.info.data() + (size_t)NEB_INFO * first, sizeof(double) * NEB_INFO * (size_t)count);
-    return SGPR_OK;
+    return md_replica_info(h, "sgpr_md_neb_info", MdRun::Rep::BAND, first, count, out);
 }
 
-// sgpr_md_run for a band, in the shape of md_relax_run and md_committee_run: every evaluation is K plain steps of the live
-// handle — image i's caller-order positions in the band ring through the handle's own binning kernel, into its own packed
-// buffer; before each the handle is as md_reset_lists leaves it: every image rebuilds its candidate lists (one list set per
-// image would save that: not done) — with md_neb_sums_kernel, md_neb_fire_kernel and md_neb_move_kernel behind them.  The
-// halts — covloss gate (1), capacity overflow at any image (2), convergence (3) — are decided by md_neb_fire_kernel on the
-// evaluation itself, before anything moves: what the host has enqueued behind a halt evaluates stale slots and changes nothing.
-// The halt words count evaluations of the band from the handle's step counter at the call's start (the handle's own counter
-// advances K per evaluation; no plain step reads the words).
+// sgpr_md_run for a band: md_replica_run over the K interior images with md_neb_sums_kernel, md_neb_fire_kernel — it decides the
+// halts: covloss gate (1), capacity overflow at any image (2), convergence (3) — and md_neb_move_kernel behind them.
 static int md_neb_run(sgpr_model *h, int nevals, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
 {
     MdState &m = h->md;
-    MdCall c;
-    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
-    hipStream_t st = c.st;
-    const int N = c.N, RG = RLX_RING, K = m.run.neb.K;
-    const size_t plen = c.plen, N3 = (size_t)3 * N;
-    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
-    if (m.neb.info_d.alloc((size_t)NEB_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-    HIPCHK(hipMemsetAsync(m.neb.info_d.p, 0, sizeof(double) * NEB_INFO * ((size_t)nevals + 1), st));
-    m.run.started = true;
-    m.run.neb.info.clear();
-    if (!h->warm) {   // the checked pass grows capacities: over every interior image
-        const size_t sw = (size_t)(m.run.t % RG);
-        for (int i = 0; i < K; i++) {
-            const int rc_ = run_checked(h, m.neb.X.p + N3 * (K * sw + i), m.cell.p, m.neb.P.p + plen * (K * sw + i), st);
-            if (rc_) return rc_;
-        }
-        h->warm = true;
-    }
-    md_call_start(h, c);
-    const unsigned step0 = c.step0; const double gate = c.gate;
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
-        const size_t sl = (size_t)((m.run.t + j) % RG), sn = (sl + 1) % RG;
-        const double *band = m.neb.X.p + N3 * K * sl;
-        double *Pk = m.neb.P.p + plen * K * sl;
-        for (int i = 0; i < K; i++) {
-            if (const int rl = md_reset_lists(h, st)) return rl;
-            const int re = enqueue_step(h, band + N3 * i, m.cell.p, Pk + plen * i, st, nullptr);
-            if (re) return re;
-        }
-        const int step = (int)(step0 + j);
-        const bool stay = final_eval && j == nevals - 1;
-        const NebBand b = {N, K, plen, band, m.neb.ends.p, Pk, h->d_perm.p, m.fix()};
-        hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, st, b, m.run.neb.cell, m.neb.sums.p, (const int *)m.halt.p, step);
-        hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, st, b, (const NebFirePar *)m.neb.par.p, m.relax.state.p, (const double *)m.neb.V.p,
-                           (const double *)m.neb.sums.p, m.neb.coef.p, m.neb.info_d.p + (size_t)NEB_INFO * j, gate, m.halt.p, m.halt_host.dev, step,
-                           m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.mark.dev + j, stay ? 1 : 0);
-        if (!stay)
-            hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, st, b, m.run.neb.cell, (const double *)m.relax.state.p,
-                               (const double *)m.neb.coef.p, m.neb.V.p, m.neb.X.p + N3 * K * sn, (const int *)m.halt.p, step);
-        return SGPR_OK;
+    const int N = m.run.N, K = m.run.rep.R;
+    const size_t plen = (size_t)sgpr_packed_len(N);
+    return md_replica_run(h, nevals, nullptr, ediff, final_eval, scalars, evals_done, halt_code, [&](const RepEval &e) {
+        const NebBand b = {N, K, plen, e.X, m.neb.ends.p, e.P, h->d_perm.p, m.fix()};
+        hipLaunchKernelGGL(md_neb_sums_kernel, dim3(K), dim3(256), 0, e.st, b, m.run.neb.cell, m.neb.sums.p, (const int *)m.halt.p, e.step);
+        hipLaunchKernelGGL(md_neb_fire_kernel, dim3(1), dim3(256), 0, e.st, b, (const NebFirePar *)m.neb.par.p, m.relax.state.p, (const double *)m.neb.V.p,
+                           (const double *)m.neb.sums.p, m.neb.coef.p, e.info, e.gate, m.halt.p, m.halt_host.dev, e.step,
+                           m.scal_d.p + (size_t)SGPR_MD_SCAL * e.j, m.mark.dev + e.j, e.stay ? 1 : 0);
+        if (!e.stay)
+            hipLaunchKernelGGL(md_neb_move_kernel, dim3((N + 63) / 64, K), dim3(256), 0, e.st, b, m.run.neb.cell, (const double *)m.relax.state.p,
+                               (const double *)m.neb.coef.p, m.neb.V.p, e.Xn, (const int *)m.halt.p, e.step);
     });
-    h->lists_valid = false;
-    if (rc_) return rc_;
-    MdHalt r;
-    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
-    if (r.done > 0) {
-        m.run.neb.info.assign((size_t)NEB_INFO * r.done, 0.0);
-        HIPCHK(hipMemcpy(m.run.neb.info.data(), m.neb.info_d.p, sizeof(double) * NEB_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
-    }
-    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
-    return SGPR_OK;
 }
 
 // ---- path-integral MD (sgpr_md_pimd; md_pimd.inc has the scheme, workloads.pimd_baoab is the host twin) ----
@@ -1320,7 +1382,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const int N = m.run.N;
-    const size_t N3 = (size_t)3 * N, plen = (size_t)sgpr_packed_len(N), PN3 = N3 * (size_t)P;
+    const size_t N3 = (size_t)3 * N, PN3 = N3 * (size_t)P;
     const double dt = m.run.dt, hdt = m.run.hdt, dP = (double)P;
     const double kTP = dP * kT, wP = kTP / PIMD_HBAR;
     std::vector<double> tab((size_t)P * P + 5 * (size_t)P);
@@ -1347,19 +1409,15 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     }
     std::vector<double> sq(N);
     for (int i = 0; i < N; i++) sq[i] = sqrt(kTP / m.run.mass_sorted[i]);
-    // rings of RLX_RING slots, every slot the initial polymer (what runs behind a halt evaluates stale slots)
-    if (m.pimd.X.alloc(PN3 * RLX_RING) || m.pimd.V.alloc(PN3 * RLX_RING) || m.pimd.P.alloc(plen * (size_t)P * RLX_RING) ||
-        m.pimd.sums.alloc((size_t)PIMD_SUMS * P) || m.pimd.tab.alloc(tab.size()) || m.pimd.sq.alloc(N))
+    if (m.pimd.V.alloc(PN3 * RLX_RING) || m.pimd.sums.alloc((size_t)PIMD_SUMS * P) || m.pimd.tab.alloc(tab.size()) || m.pimd.sq.alloc(N))
         return fail(SGPR_E_NODEVICE, "sgpr_md_pimd: device allocation failed");
     HIPCHK(hipMemset(m.pimd.V.p, 0, sizeof(double) * PN3 * RLX_RING));
-    for (int r = 0; r < RLX_RING; r++)
-        HIPCHK(hipMemcpy(m.pimd.X.p + PN3 * r, positions, sizeof(double) * PN3, hipMemcpyHostToDevice));
     if (velocities) HIPCHK(hipMemcpy(m.pimd.V.p, velocities, sizeof(double) * PN3, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.pimd.tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(m.pimd.sq.p, sq.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-    m.run.pimd.P = P; m.run.pimd.kT = kT; m.run.pimd.wP2 = wP * wP;
-    m.run.pimd.on = true; m.run.ring = RLX_RING;
-    m.run.pimd.info.clear();
+    if (const int ra = md_replica_attach(h, "sgpr_md_pimd", MdRun::Rep::POLYMER, P, PIMD_INFO, positions)) return ra;
+    m.run.pimd.kT = kT; m.run.pimd.wP2 = wP * wP;
+    m.run.pimd.on = true;
     return SGPR_OK;
 }
 
@@ -1369,105 +1427,38 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
 // configuration (a halted or `final` call: which = 0; a call that ran through: which = -1).  Any of them NULL.
 extern "C" int sgpr_md_pimd_state(sgpr_model *h, double *positions, double *velocities_pre, double *packed, int which)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: bad arguments");
-    MdState &m = h->md;
-    if (!m.active || !m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: call sgpr_md_begin and sgpr_md_pimd first");
-    if (which != 0 && which != -1) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: which = 0 or -1");
-    if (which == -1 && m.run.t == 0) return fail(SGPR_E_INVALID, "sgpr_md_pimd_state: no earlier configuration");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N3 = (size_t)3 * m.run.N, plen = (size_t)sgpr_packed_len(m.run.N), P = (size_t)m.run.pimd.P;
-    const size_t sl = (size_t)((m.run.t + which + RLX_RING) % RLX_RING);
-    if (positions) HIPCHK(hipMemcpy(positions, m.pimd.X.p + N3 * P * sl, sizeof(double) * N3 * P, hipMemcpyDeviceToHost));
-    if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.pimd.V.p + N3 * P * sl, sizeof(double) * N3 * P, hipMemcpyDeviceToHost));
-    if (packed) HIPCHK(hipMemcpy(packed, m.pimd.P.p + plen * P * sl, sizeof(double) * plen * P, hipMemcpyDeviceToHost));
-    return SGPR_OK;
+    return md_replica_state(h, "sgpr_md_pimd_state", MdRun::Rep::POLYMER, positions, velocities_pre, packed, which);
 }
 
 // The record of the last sgpr_md_run: out[count][64] = E[32] | covmax[32] (bead j at entry j, the rest zero) of its evaluations
 // first ... first + count - 1 (0 = the call's first) among those that stand.
 extern "C" int sgpr_md_pimd_info(sgpr_model *h, int first, int count, double *out)
 {
-    if (!h || first < 0 || count <= 0 || !out) return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: bad arguments");
-    const MdState &m = h->md;
-    if (!m.active || !m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: call sgpr_md_begin and sgpr_md_pimd first");
-    const long long have = (long long)(m.run.pimd.info.size() / PIMD_INFO);
-    if ((long long)first + count > have)
-        return fail(SGPR_E_INVALID, "sgpr_md_pimd_info: evaluations %d ... %lld asked for, %lld of the last sgpr_md_run stand", first, (long long)first + count - 1, have);
-    memcpy(out, m.run.pimd.info.data() + (size_t)PIMD_INFO * first, sizeof(double) * PIMD_INFO * (size_t)count);
-    return SGPR_OK;
+    return md_replica_info(h, "sgpr_md_pimd_info", MdRun::Rep::POLYMER, first, count, out);
 }
 
-// sgpr_md_run for a polymer, in the shape of md_neb_run: every evaluation is P plain steps of the live handle — bead j's
-// caller-order positions in the ring through the handle's own binning kernel, into its own packed buffer; before each the handle
-// is as md_reset_lists leaves it: every bead rebuilds its candidate lists (one list set per bead would save that: not done) —
-// with md_pimd_sums_kernel, md_pimd_gate_kernel and md_pimd_move_kernel behind them.  The halts — covloss gate (1), capacity
-// overflow at any bead (2) — are decided by md_pimd_gate_kernel on the evaluation itself, before anything moves: what the host
-// has enqueued behind a halt evaluates stale slots and changes nothing, and the repeat of a halted evaluation finds x and v of
-// its slot as they were.  The halt words count evaluations of the polymer from the handle's step counter at the call's start.
-// noise: [nevals][P][N][3], caller atom order, uploaded as it is (the move kernel goes through the permutation anyway).
+// sgpr_md_run for a polymer: md_replica_run over the P beads with md_pimd_sums_kernel, md_pimd_gate_kernel — it decides the
+// halts: covloss gate (1), capacity overflow at any bead (2) — and md_pimd_move_kernel behind them; the repeat of a halted
+// evaluation finds x and v of its slot as they were.  noise: [nevals][P][N][3], caller atom order (the move kernel goes through
+// the permutation anyway).
 static int md_pimd_run(sgpr_model *h, int nevals, const double *noise, double ediff, int final_eval, double *scalars, int *evals_done, int *halt_code)
 {
     MdState &m = h->md;
-    MdCall c;
-    if (const int ro = md_call_open(h, ediff, evals_done, halt_code, c)) return ro;
-    hipStream_t st = c.st;
-    const int N = c.N, RG = RLX_RING, P = m.run.pimd.P;
-    const size_t plen = c.plen, N3 = (size_t)3 * N, PN3 = N3 * (size_t)P;
-    if (const int rp = md_prepare_call(h, nevals, st, false)) return rp;
-    if (m.pimd.info_d.alloc((size_t)PIMD_INFO * ((size_t)nevals + 1), false)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-    HIPCHK(hipMemsetAsync(m.pimd.info_d.p, 0, sizeof(double) * PIMD_INFO * ((size_t)nevals + 1), st));
-    if (noise) {
-        if (m.noise_raw.alloc(PN3 * (size_t)nevals)) return fail(SGPR_E_NODEVICE, "sgpr_md_run: device allocation failed");
-        HIPCHK(hipMemcpyAsync(m.noise_raw.p, noise, sizeof(double) * PN3 * (size_t)nevals, hipMemcpyHostToDevice, st));
-    }
-    m.run.started = true;
-    m.run.pimd.info.clear();
-    if (!h->warm) {   // the checked pass grows capacities: over every bead
-        const size_t sw = (size_t)(m.run.t % RG);
-        for (int i = 0; i < P; i++) {
-            const int rc_ = run_checked(h, m.pimd.X.p + PN3 * sw + N3 * i, m.cell.p, m.pimd.P.p + plen * (P * sw + i), st);
-            if (rc_) return rc_;
-        }
-        h->warm = true;
-    }
-    md_call_start(h, c);
-    const unsigned step0 = c.step0; const double gate = c.gate;
+    const int N = m.run.N, P = m.run.rep.R;
+    const size_t plen = (size_t)sgpr_packed_len(N), PN3 = (size_t)3 * N * (size_t)P;
     const bool pend0 = m.run.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
     const size_t lds = sizeof(double) * ((size_t)4 * P * 3 * PIMD_TILE + (size_t)P * P);
-    const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
-        const size_t sl = (size_t)((m.run.t + j) % RG), sn = (sl + 1) % RG;
-        const double *beads = m.pimd.X.p + PN3 * sl;
-        double *Pk = m.pimd.P.p + plen * P * sl;
-        for (int i = 0; i < P; i++) {
-            if (const int rl = md_reset_lists(h, st)) return rl;
-            const int re = enqueue_step(h, beads + N3 * i, m.cell.p, Pk + plen * i, st, nullptr);
-            if (re) return re;
+    return md_replica_run(h, nevals, noise, ediff, final_eval, scalars, evals_done, halt_code, [&](const RepEval &e) {
+        const PimdRing b = {N, P, plen, e.X, m.pimd.V.p + PN3 * e.sl, e.P, h->d_perm.p, m.mass.p, m.run.hdt, (e.j > 0 || pend0) ? 1 : 0};
+        hipLaunchKernelGGL(md_pimd_sums_kernel, dim3(P), dim3(256), 0, e.st, b, m.pimd.sums.p, (const int *)m.halt.p, e.step);
+        hipLaunchKernelGGL(md_pimd_gate_kernel, dim3(1), dim3(64), 0, e.st, N, P, (const double *)m.pimd.sums.p, m.run.pimd.kT, m.run.pimd.wP2,
+                           e.info, e.gate, m.halt.p, m.halt_host.dev, e.step, m.scal_d.p + (size_t)SGPR_MD_SCAL * e.j, m.mark.dev + e.j);
+        if (!e.stay) {
+            const PimdMove a = {m.pimd.sq.p, m.pimd.tab.p, noise ? m.noise_raw.p + PN3 * (size_t)e.j : nullptr, e.Xn, m.pimd.V.p + PN3 * e.sn,
+                                noise ? 0ull : m.seed, m.run.t + e.j};
+            hipLaunchKernelGGL(md_pimd_move_kernel, dim3((N + PIMD_TILE - 1) / PIMD_TILE), dim3(256), lds, e.st, b, a, (const int *)m.halt.p, e.step);
         }
-        const int step = (int)(step0 + j);
-        const bool stay = final_eval && j == nevals - 1;
-        const PimdRing b = {N, P, plen, beads, m.pimd.V.p + PN3 * sl, Pk, h->d_perm.p, m.mass.p, m.run.hdt, (j > 0 || pend0) ? 1 : 0};
-        hipLaunchKernelGGL(md_pimd_sums_kernel, dim3(P), dim3(256), 0, st, b, m.pimd.sums.p, (const int *)m.halt.p, step);
-        hipLaunchKernelGGL(md_pimd_gate_kernel, dim3(1), dim3(64), 0, st, N, P, (const double *)m.pimd.sums.p, m.run.pimd.kT, m.run.pimd.wP2,
-                           m.pimd.info_d.p + (size_t)PIMD_INFO * j, gate, m.halt.p, m.halt_host.dev, step, m.scal_d.p + (size_t)SGPR_MD_SCAL * j,
-                           m.mark.dev + j);
-        if (!stay) {
-            const PimdMove a = {m.pimd.sq.p, m.pimd.tab.p, noise ? m.noise_raw.p + PN3 * (size_t)j : nullptr, m.pimd.X.p + PN3 * sn, m.pimd.V.p + PN3 * sn,
-                                noise ? 0ull : m.seed, m.run.t + j};
-            hipLaunchKernelGGL(md_pimd_move_kernel, dim3((N + PIMD_TILE - 1) / PIMD_TILE), dim3(256), lds, st, b, a, (const int *)m.halt.p, step);
-        }
-        return SGPR_OK;
     });
-    h->lists_valid = false;
-    if (rc_) return rc_;
-    MdHalt r;
-    if (const int rc = md_call_close(h, c, final_eval, scalars, false, &r)) return rc;
-    if (r.done > 0) {
-        m.run.pimd.info.assign((size_t)PIMD_INFO * r.done, 0.0);
-        HIPCHK(hipMemcpy(m.run.pimd.info.data(), m.pimd.info_d.p, sizeof(double) * PIMD_INFO * (size_t)r.done, hipMemcpyDeviceToHost));
-    }
-    md_finish_call(h, r, scalars, true, final_eval, evals_done, halt_code);
-    return SGPR_OK;
 }
 
 // Evaluates `nevals` configurations starting with the current one; after each evaluation but (with `final`) the last

@@ -871,35 +871,48 @@ class SGPRModel:
         """optimizer.initialize() of the band on the device: v = 0; dt, a, nsteps back to their start."""
         check(_lib.load().sgpr_md_neb_reset(self._h))
 
+    def _replicas(self, who, key, noun):
+        """R of the run whose configuration is R replicas under `key` ("neb": a band's interior images, "pimd": a polymer's beads)."""
+        if not (getattr(self, "_md", None) and self._md.get(key)):
+            raise RuntimeError(f"{who}: no {noun} on this model: {key}_begin first (a refused {key}_begin leaves none)")
+        return self._md[key]
+
+    def _replica_state(self, key, noun, which, results, vname, **more):
+        """What neb_state and pimd_state share: positions [R, N, 3], the mode's velocity under `vname`, what the mode adds
+        (`more`), and with results=True forces [R, N, 3], beta [R, N], energy [R], stress [R, 6] off the replicas' packed results."""
+        R = self._replicas(f"{key}_state", key, noun)
+        N = self._md["N"]
+        x, v = np.empty((R, N, 3)), np.empty((R, N, 3))
+        packed = np.empty((R, 4 * N + 11)) if results else None
+        check(getattr(_lib.load(), f"sgpr_md_{key}_state")(self._h, ptr(x), ptr(v), ptr(packed), int(which)))
+        out = {"positions": x, vname: v, **more}
+        if results:
+            stress = np.zeros((R, 6))
+            for i in range(R):
+                check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[i, 4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress[i])))
+            out.update(forces=packed[:, :3 * N].reshape(R, N, 3).copy(), beta=packed[:, 3 * N:4 * N].copy(), energy=packed[:, 4 * N].copy(),
+                       stress=stress)
+        return out
+
+    def _replica_info(self, key, noun, half):
+        """(E [done, R], covmax [done, R]) off the rows E[half] | covmax[half] of the last md_run that stand."""
+        R = self._replicas(f"{key}_info", key, noun)
+        done = self._md.get("rep_done", 0)
+        out = np.zeros((done, 2 * half))
+        if done:
+            check(getattr(_lib.load(), f"sgpr_md_{key}_info")(self._h, 0, done, ptr(out)))
+        return out[:, :R].copy(), out[:, half:half + R].copy()
+
     def neb_state(self, which=0, results=False):
         """The K interior images of the current band (which = -1: the one evaluated before it): dict(positions [K, N, 3],
         velocities [K, N, 3] FIRE's); with results=True — where the last md_run evaluated that band: which = 0 after a halted or
         `final` call, -1 after one that ran through — also forces [K, N, 3], beta [K, N], energy [K], stress [K, 6]."""
-        if not (getattr(self, "_md", None) and self._md.get("neb")):
-            raise RuntimeError("neb_state: no band on this model: neb_begin first (a refused neb_begin leaves none)")
-        N, K = self._md["N"], self._md["neb"]
-        x, v = np.empty((K, N, 3)), np.empty((K, N, 3))
-        packed = np.empty((K, 4 * N + 11)) if results else None
-        check(_lib.load().sgpr_md_neb_state(self._h, ptr(x), ptr(v), ptr(packed), int(which)))
-        out = dict(positions=x, velocities=v)
-        if results:
-            stress = np.zeros((K, 6))
-            for i in range(K):
-                check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[i, 4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress[i])))
-            out.update(forces=packed[:, :3 * N].reshape(K, N, 3).copy(), beta=packed[:, 3 * N:4 * N].copy(), energy=packed[:, 4 * N].copy(),
-                       stress=stress)
-        return out
+        return self._replica_state("neb", "band", which, results, "velocities")
 
     def neb_info(self):
         """(E [done, K], covmax [done, K]): energy and largest covloss of every interior image at the evaluations of the last
         md_run that stand (sgpr_md_neb_info)."""
-        if not (getattr(self, "_md", None) and self._md.get("neb")):
-            raise RuntimeError("neb_info: no band on this model: neb_begin first (a refused neb_begin leaves none)")
-        K, done = self._md["neb"], self._md.get("neb_done", 0)
-        out = np.zeros((done, 32))
-        if done:
-            check(_lib.load().sgpr_md_neb_info(self._h, 0, done, ptr(out)))
-        return out[:, :K].copy(), out[:, 16:16 + K].copy()
+        return self._replica_info("neb", "band", 16)
 
     PIMD_MAX = 32   # beads of a polymer (md_pimd.inc)
 
@@ -946,33 +959,18 @@ class SGPRModel:
         velocities_pre [P, N, 3] before the closing half kick, pending: whether one is due); with results=True — where the last
         md_run evaluated that configuration: which = 0 after a halted or `final` call, -1 after one that ran through — also
         forces [P, N, 3], beta [P, N], energy [P], stress [P, 6] and velocities [P, N, 3], the closing half kick applied."""
-        if not (getattr(self, "_md", None) and self._md.get("pimd")):
-            raise RuntimeError("pimd_state: no polymer on this model: pimd_begin first (a refused pimd_begin leaves none)")
-        N, P = self._md["N"], self._md["pimd"]
-        x, v = np.empty((P, N, 3)), np.empty((P, N, 3))
-        packed = np.empty((P, 4 * N + 11)) if results else None
-        check(_lib.load().sgpr_md_pimd_state(self._h, ptr(x), ptr(v), ptr(packed), int(which)))
+        self._replicas("pimd_state", "pimd", "polymer")   # (no polymer: said before _md is read)
         pending = self._md["t"] + which > 0
-        out = dict(positions=x, velocities_pre=v, pending=pending)
+        out = self._replica_state("pimd", "polymer", which, results, "velocities_pre", pending=pending)
         if results:
-            stress = np.zeros((P, 6))
-            for i in range(P):
-                check(_lib.load().sgpr_stress_from_virial(ptr(f64(packed[i, 4 * N + 1:4 * N + 10])), ptr(self._md["cell"]), ptr(stress[i])))
-            F = packed[:, :3 * N].reshape(P, N, 3).copy()
-            out.update(forces=F, beta=packed[:, 3 * N:4 * N].copy(), energy=packed[:, 4 * N].copy(), stress=stress,
-                       velocities=v + self._md["hdt"] * F / self._md["masses"][None, :, None] if pending else v.copy())
+            v = out["velocities_pre"]
+            out["velocities"] = v + self._md["hdt"] * out["forces"] / self._md["masses"][None, :, None] if pending else v.copy()
         return out
 
     def pimd_info(self):
         """(E [done, P], covmax [done, P]): energy and largest covloss of every bead at the evaluations of the last md_run that
         stand (sgpr_md_pimd_info)."""
-        if not (getattr(self, "_md", None) and self._md.get("pimd")):
-            raise RuntimeError("pimd_info: no polymer on this model: pimd_begin first (a refused pimd_begin leaves none)")
-        P, done = self._md["pimd"], self._md.get("pimd_done", 0)
-        out = np.zeros((done, 64))
-        if done:
-            check(_lib.load().sgpr_md_pimd_info(self._h, 0, done, ptr(out)))
-        return out[:, :P].copy(), out[:, 32:32 + P].copy()
+        return self._replica_info("pimd", "polymer", 32)
 
     def md_deviates(self, t_first, count):
         out = np.empty((int(count), self._md["N"], 3))
@@ -997,10 +995,7 @@ class SGPRModel:
         check(_lib.load().sgpr_md_run(self._h, int(nevals), ptr(noise), float(ediff), int(bool(final)), ptr(sc),
                                       C.addressof(done), C.addressof(code)))
         self._md["record_call"] = self._md.get("record")   # (what this call recorded: md_frames)
-        if self._md.get("neb"):   # (the rows of the band record that stand: neb_info)
-            self._md["neb_done"] = done.value
-        if self._md.get("pimd"):   # (the rows of the polymer's record that stand: pimd_info)
-            self._md["pimd_done"] = done.value
+        self._md["rep_done"] = done.value   # (the rows of a band's or a polymer's record that stand: neb_info, pimd_info)
         if self._md.get("npt") or self._md.get("pimd"):   # (where the state is now: sgpr_md_run's rules)
             t0 = self._md["t"]
             self._md["run"] = (t0, done.value)

@@ -109,6 +109,13 @@ def _neb(mdl, s):
     _run(mdl, 3, final=False)
 
 
+def _pimd(mdl, s):
+    from test_hip_pimd_device import _begin as _begin_pimd, _polymer
+    numbers, beads, vel, mass = _polymer(s[1], s[2], 3)
+    _begin_pimd(mdl, numbers, beads, vel, mass, s[3], s[4], seed=7)
+    _run(mdl, 3, final=False)
+
+
 def _data(mdl, s):
     """The resident matrix and the kept first-stage factorisation: a refit, an appended and a popped column (QrKeep::ops), a
     frame pushed on top of a kept factor and popped again (r1_cache), a re-solve."""
@@ -146,7 +153,7 @@ def _inducing(mdl, s):
 
 
 FEATURES = dict(predict=_predict, langevin=_langevin, nose_hoover=_nose_hoover, barostat=_barostat, relax=_relax, relax_cell=_relax_cell,
-                ml_filter=_filter, fixed=_fixed, record=_record, meta_merge=_meta, committee=_committee, neb=_neb, data=_data,
+                ml_filter=_filter, fixed=_fixed, record=_record, meta_merge=_meta, committee=_committee, neb=_neb, pimd=_pimd, data=_data,
                 inducing=_inducing)
 
 
