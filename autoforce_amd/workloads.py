@@ -1714,6 +1714,69 @@ def pimd_baoab(calc, numbers, beads, cell, pbc, steps, temperature=600.0, dt_fs=
         n += 1
 
 
+def philox4x32_10(counter, key):
+    """Philox4x32 with ten rounds (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11, section
+    3.3 and the constants of its table): counter[..., 4] and key[..., 2] 32-bit words -> uint32[..., 4].  One round takes
+    (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)) with the 32 x 32 -> 64 bit
+    products of M0 = D2511F53 and M1 = CD9E8D57; between two rounds the key moves on by the Weyl constants (9E3779B9: the
+    golden ratio, BB67AE85: sqrt(3) - 1).  The statement of the stream the device loop draws from (md_deviate, api.hip), in
+    numpy alone: nothing of the library is called."""
+    m32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    c = np.asarray(counter, dtype=np.uint64) & m32
+    k = np.asarray(key, dtype=np.uint64) & m32
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead) for i in range(2))
+    for rnd in range(10):
+        if rnd:
+            k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2   # (32 x 32 bits: no overflow of the 64)
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def uniforms_of_words(words):
+    """(u1, u2) of four 32-bit words [..., 4], the conversion of md_deviate: the 53 leading bits of the 64-bit numbers
+    c0 2^32 + c1 and c2 2^32 + c3,  u1 = ((c0 2^32 + c1 >> 11) + 1) 2^-53 in (0, 1]  and  u2 = (c2 2^32 + c3 >> 11) 2^-53
+    in [0, 1): every value is a double, exactly."""
+    w = np.asarray(words, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    a = (w[..., 0] << np.uint64(32)) | w[..., 1]
+    b = (w[..., 2] << np.uint64(32)) | w[..., 3]
+    scale = 2.0 ** -53
+    return ((a >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * scale, (b >> np.uint64(11)).astype(np.float64) * scale
+
+
+def box_muller(u1, u2):
+    """sqrt(-2 ln u1) cos(6.283185307179586 u2): the cosine branch of Box-Muller with the angle factor md_deviate uses, that
+    double literal (the double nearest 2 pi), operation by operation in float64."""
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * np.asarray(u2, dtype=np.float64))
+
+
+def md_deviate_uniforms(seed, t, atom, comp):
+    """The two uniforms behind deviate (t, atom, comp) of the stream `seed` (sgpr_md_seed): Philox4x32-10 on the counter
+    (t low word, t high word, atom, comp) with the key (seed low word, seed high word) — t a 64-bit two's-complement
+    word (a negative t is its bit pattern), seed an unsigned one, atom and comp 32-bit words — then uniforms_of_words.
+    The arguments broadcast against each other."""
+    m32 = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    sd = np.asarray(seed, dtype=np.uint64)
+    tt = np.asarray(t, dtype=np.int64).astype(np.uint64)
+    at = np.asarray(atom, dtype=np.int64).astype(np.uint64) & m32
+    cp = np.asarray(comp, dtype=np.int64).astype(np.uint64) & m32
+    sd, tt, at, cp = np.broadcast_arrays(sd, tt, at, cp)
+    counter = np.stack([tt & m32, tt >> s32, at, cp], axis=-1)
+    key = np.stack([sd & m32, sd >> s32], axis=-1)
+    return uniforms_of_words(philox4x32_10(counter, key))
+
+
+def md_deviate(seed, t, atom, comp):
+    """The standard normal deviate (t, atom, comp) of the stream `seed` as the device loop draws it (md_deviate in api.hip;
+    SGPRModel.md_deviates returns out[r, a, c] = md_deviate(seed, t_first + r, a, c), a in caller order): the host twin of
+    the stream, float64.  Equal to the device's up to the roundings of log, sqrt and cos — the integer part is exact."""
+    return box_muller(*md_deviate_uniforms(seed, t, atom, comp))
+
+
 def langevin_nvt_device(model, numbers, pos, cell, pbc, steps, temperature=600.0, dt_fs=1.0, friction=1e-3, seed=1, vel=None,
                         ediff=0.0, chunk=256, on_halt=None, device_rng=False, fixed=None):
     """langevin_nvt with the state in device memory (SGPRModel.md_begin / md_run): same scheme, same random stream
