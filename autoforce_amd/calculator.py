@@ -552,7 +552,7 @@ class ActiveCalculator(Calculator):
     RECORD_BYTES = 256 << 20   # the frame record of one md_run call (run_md, run_relax) stays within this much device memory
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -604,9 +604,14 @@ class ActiveCalculator(Calculator):
         around calculate(), which adds a Meta's bias itself; there meta.update() runs once per configuration.
         A committee with members (BCMActiveCalculator) and a barostat: the device loop integrates and gates the committee in the
         moving cell (SGPRModel.md_committee on a run begun with pfactor=); such a run records no frames, so its batches end at the
-        multiples of sync_every, where atoms.cell is set with atoms.positions."""
+        multiples of sync_every, where atoms.cell is set with atoms.positions.
+        msd: a transport.Msd(every, levels, com) holder — the mean-square displacements of the run's configurations 0 ... steps
+        are added to it at the end (transport.diffusion_constants reads it; one holder carries several runs).  The device loop
+        accumulates them itself (SGPRModel.md_msd: two small launches behind a sampled evaluation, the table read once at the
+        end); with a barostat, a committee or several ranks, and in the host loops, workloads.MsdBlocks — the same operations
+        in the same order — is fed the positions of every step.  None: nothing is accumulated, today's run."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, FilterState, MsdBlocks, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
         filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
@@ -645,7 +650,8 @@ class ActiveCalculator(Calculator):
         def on_device():
             return (self.md_on_device_ok() and not (committee and fx is not None)
                     and not (flt is not None and (committee or self._dist()[1] > 1))
-                    and not (self.meta is not None and (npt or committee or self._dist()[1] > 1)))
+                    and not (self.meta is not None and (npt or committee or self._dist()[1] > 1))
+                    and not (msd is not None and (npt or committee or self._dist()[1] > 1)))
         seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -658,13 +664,19 @@ class ActiveCalculator(Calculator):
                 loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro, **filt) if npt else
                         nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold, **filt) if nh else
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold, **filt))
+                blocks = None if msd is None else MsdBlocks(msd.every, msd.levels, msd.com, masses, numbers,
+                                                            getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
                 for st, E, T, _, p, v, *rest in loop:
+                    if blocks is not None:
+                        blocks.add(p)
                     if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
                         self.meta.update()
                     put_state(atoms, dict(positions=p, velocities=v, cell=rest[0] if npt else None), npt, "velocities")
                     if flt is not None:   # (the accumulators as this configuration found them: what a run that goes on from it takes)
                         flt.f, flt.s = rest[-1]
                     yield st, E, T, bool(self.updated), _
+                if blocks is not None:
+                    msd.add(blocks.table())
                 return
         eng = self.engine
         kT, dof_kB = kB * temperature_K, dof * kB
@@ -672,6 +684,8 @@ class ActiveCalculator(Calculator):
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
                      seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold, **filt)
         attached = self._md_attach(eng)
+        if msd is not None:
+            eng.md_msd(msd.every, msd.levels, msd.com)
         meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
@@ -755,6 +769,8 @@ class ActiveCalculator(Calculator):
         put_state(atoms, eng.md_state(results=True), npt, "velocities")
         if flt is not None:
             flt.f, flt.s = eng.md_filter_state()
+        if msd is not None:
+            msd.add(eng.md_msd_table())
         if attached:
             self._md_attached_done(eng, attached)
 

@@ -280,6 +280,9 @@ struct MdRun {
         long long call_t0 = 0;
         int call_every = 0, call_what = 0, call_count = 0;
     } rec;
+    // the mean-square displacements (sgpr_md_msd, md_msd.inc): every `every`-th configuration is a sample, `levels` lags in
+    // powers of two; nch chunks of one species each, S species of the model's table, the frame's total mass
+    struct Msd { int every = 0, levels = 0, com = 0, nch = 0, S = 0; double mtot = 0.0; } msd;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -354,6 +357,12 @@ struct MdState {
         bool held() const { return rows.p != nullptr; }   // (every attach allocates the rows)
     } meta;
     struct { DevBuf<double> x, v, p; } rec;   // [frames][N][3] x 2, [frames][4N + 11]: one copy per array fetches a call
+    struct MsdBufs {
+        DevBuf<double> origin, part, table;   // [L][N][3] sorted order, [L][nch][MSD_PART], [L][S][4]
+        DevBuf<long long> ctl;                // next_due | count[L]
+        DevBuf<int> tab;                      // [nch][2] the chunks | [S + 1] a species' chunks | [S] its atoms
+        bool held() const { return ctl.p != nullptr; }
+    } msd;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1277,6 +1286,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_neb.inc"
 #include "md_pimd.inc"
 #include "md_record.inc"
+#include "md_msd.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next

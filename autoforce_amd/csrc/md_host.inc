@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -188,6 +188,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
                     "md_committee_cell is set (sgpr_set_option)");
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
+    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates displacements (sgpr_md_msd), which are defined at constant cell");
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -381,6 +382,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a ring polymer (sgpr_md_pimd), which serves dynamics only");
+    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -721,6 +723,25 @@ static void md_record_frame(sgpr_model *h, int j, int step, hipStream_t st)
                        (const int *)m.halt.p, step);
 }
 
+// The sample of evaluation j of a call (configuration n = m.run.t + j, n % msd.every == 0), behind the evaluation's last launch
+// like the frame: the two launches of md_msd.inc on the X slot of n.  The due levels follow from n alone; whether n is the
+// sample the table waits for (next_due) is the device's decision.
+static void md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::Msd &a = m.run.msd;
+    const long long n = m.run.t + j, s = n / a.every;
+    unsigned due = 0;
+    for (int l = 0; l < a.levels && (s & ((1ll << l) - 1)) == 0; l++) due |= 1u << l;
+    const int acc = s > 0 ? 1 : 0, N = m.run.N;
+    const size_t N3 = (size_t)3 * N;
+    const int *chunk = m.msd.tab.p, *coff = chunk + 2 * a.nch, *nz = coff + a.S + 1;
+    hipLaunchKernelGGL(md_msd_part_kernel, dim3(a.nch), dim3(256), 0, st, chunk, a.nch, (const double *)(m.X.p + N3 * (size_t)(n % m.run.ring)),
+                       (const double *)m.mass.p, m.msd.origin.p, N3, due, acc, m.msd.part.p, (const long long *)m.msd.ctl.p, n, (const int *)m.halt.p, step);
+    hipLaunchKernelGGL(md_msd_fold_kernel, dim3(1), dim3(256), sizeof(double) * a.levels * a.S * MSD_PART, st, coff, nz, a.nch, a.S, a.levels, a.mtot,
+                       a.com, due, acc, (const double *)m.msd.part.p, m.msd.table.p, m.msd.ctl.p, n, a.every, (const int *)m.halt.p, step);
+}
+
 // Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
 // one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
 // again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
@@ -885,6 +906,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a ring polymer (sgpr_md_pimd), which is evaluated by one model");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
+    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates displacements (sgpr_md_msd), which the committee's loop does not sample");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1251,6 +1273,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a ring polymer (sgpr_md_pimd)");
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
+    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1375,6 +1398,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run has a filter (sgpr_md_filter); a polymer integrates unfiltered forces");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: %d components are held (sgpr_md_fix); a polymer runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: a frame record is armed (sgpr_md_record); a polymer records no frames");
+    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates displacements (sgpr_md_msd); a polymer's centroid is not sampled");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1579,6 +1603,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         // (the frame: the last kernel has written this evaluation's results and, Nose-Hoover, its centred velocity; the slots
         // read here are written again only when the rings come round)
         if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
+        if (m.run.msd.every && (m.run.t + j) % m.run.msd.every == 0) md_msd_sample(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -1754,6 +1779,80 @@ extern "C" int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *inde
     if (positions) HIPCHK(hipMemcpy(positions, m.rec.x.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
     if (velocities_pre) HIPCHK(hipMemcpy(velocities_pre, m.rec.v.p + N3 * first, sizeof(double) * N3 * count, hipMemcpyDeviceToHost));
     if (packed) HIPCHK(hipMemcpy(packed, m.rec.p.p + plen * first, sizeof(double) * plen * count, hipMemcpyDeviceToHost));
+    return SGPR_OK;
+}
+
+// Mean-square displacements of the run (md_msd.inc has the definition; workloads.MsdBlocks is the host twin): every >= 1 —
+// configuration n with n % every == 0 is sample n / every, and behind its evaluation two launches update a table in device
+// memory: per level l < levels (lag 2^l samples, one origin, windows that do not overlap) and species of the model's table the
+// sums of msd, msd^2, smd, smd^2 and the number of windows.  com: displacements relative to the frame's centre of mass.  After
+// sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record), before the first sgpr_md_run; every = 0 detaches.  The attach
+// zeroes the table.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, beside a mask, the filter, a bias
+// and the frame record; a barostat, a committee, a relaxation, a band, a polymer and several ranks: SGPR_E_UNSUPPORTED, from
+// here and from their attach functions.
+extern "C" int sgpr_md_msd(sgpr_model *h, int every, int levels, int com)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_msd: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_msd: call sgpr_md_begin first");
+    if (every == 0) { m.run.msd = MdRun::Msd(); return SGPR_OK; }
+    if (every < 0 || levels < 1 || levels > MSD_MAXL || (com != 0 && com != 1))
+        return fail(SGPR_E_INVALID, "sgpr_md_msd: every >= 0, 1 <= levels <= %d, com = 0 or 1", MSD_MAXL);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_msd: the run has started");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run was begun on %d ranks; displacements are accumulated on one", m.run.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run has a barostat; a displacement in a moving cell mixes in the strain");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run has a committee (sgpr_md_committee), whose loop does not sample displacements");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a relaxation; displacements are accumulated over dynamics");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a nudged elastic band; displacements are accumulated over dynamics");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a ring polymer (sgpr_md_pimd); its centroid is not sampled");
+    const int N = m.run.N, S = h->S;
+    if (sizeof(double) * (size_t)levels * S * MSD_PART > 65536)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: %d levels of %d species: the sums of a sample must fit 64 KiB of LDS", levels, S);
+    // the chunks: runs of at most MSD_CHUNK consecutive sorted atoms of one species (the sort is by species in table order)
+    std::vector<int> nz(S, 0), zi(N);
+    for (int i = 0; i < N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
+        if (z == S || (i > 0 && z < zi[i - 1])) return fail(SGPR_E_INVALID, "sgpr_md_msd: the run's atoms are not sorted by the model's species");
+        zi[i] = z; nz[z]++;
+    }
+    std::vector<int> tab, coff(S + 1, 0);
+    for (int z = 0, first = 0; z < S; first += nz[z], z++) {
+        for (int o = 0; o < nz[z]; o += MSD_CHUNK) { tab.push_back(first + o); tab.push_back(std::min(MSD_CHUNK, nz[z] - o)); }
+        coff[z + 1] = (int)tab.size() / 2;
+    }
+    const int nch = coff[S];
+    tab.insert(tab.end(), coff.begin(), coff.end());
+    tab.insert(tab.end(), nz.begin(), nz.end());
+    double mtot = 0.0;
+    for (int i = 0; i < N; i++) mtot += m.run.mass_sorted[i];
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (m.msd.origin.alloc((size_t)levels * 3 * N) || m.msd.part.alloc((size_t)levels * nch * MSD_PART) || m.msd.table.alloc((size_t)levels * S * 4) ||
+        m.msd.ctl.alloc((size_t)1 + levels) || m.msd.tab.alloc(tab.size(), false))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_msd: device allocation failed");
+    HIPCHK(hipMemcpy(m.msd.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    MdRun::Msd &a = m.run.msd;
+    a.every = every; a.levels = levels; a.com = com; a.nch = nch; a.S = S; a.mtot = mtot;
+    return SGPR_OK;
+}
+
+// The table as it stands (between two calls of a run; the stream is synchronised): table [levels][S][4] the sums of msd, msd^2,
+// smd, smd^2 per level and species of the model's table, counts [levels] the windows of a level, info [2] = samples taken,
+// next_due (the configuration the table waits for).  Any pointer may be NULL.
+extern "C" int sgpr_md_msd_read(sgpr_model *h, double *table, int64_t *counts, int64_t *info)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_msd_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.msd.every) return fail(SGPR_E_INVALID, "sgpr_md_msd_read: call sgpr_md_begin and sgpr_md_msd first");
+    const MdRun::Msd &a = m.run.msd;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<long long> ctl((size_t)1 + a.levels);
+    HIPCHK(hipMemcpy(ctl.data(), m.msd.ctl.p, sizeof(long long) * ctl.size(), hipMemcpyDeviceToHost));
+    if (table) HIPCHK(hipMemcpy(table, m.msd.table.p, sizeof(double) * (size_t)a.levels * a.S * 4, hipMemcpyDeviceToHost));
+    if (counts) for (int l = 0; l < a.levels; l++) counts[l] = ctl[1 + l];
+    if (info) { info[0] = ctl[0] / a.every; info[1] = ctl[0]; }
     return SGPR_OK;
 }
 
@@ -2144,6 +2243,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.lbfgs = MdState::LbfgsBufs();
+    }
+    if (m.msd.held()) {   // (and the origins and the table of the displacements)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.msd = MdState::MsdBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

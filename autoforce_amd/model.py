@@ -1122,6 +1122,38 @@ class SGPRModel:
                 out["velocities"] = vel
         return out
 
+    def md_msd(self, every, levels, com=False):
+        """Accumulate mean-square displacements inside the loop (sgpr_md_msd; md_msd.inc has the scheme, workloads.MsdBlocks is
+        the host twin and the definition): configuration n with n % every == 0 is sample n / every; level l < levels has the
+        lag 2^l samples, one origin and windows that do not overlap, and per species of the model's table gains the tracer
+        msd = mean |d_i - c|^2 and the collective smd = |sum (d_i - c)|^2 / n_z of every window (c: the displacement of the
+        frame's centre of mass with com=True, else 0) — what theforce/analysis/analysis.py's `correlator` works out of a stored
+        trajectory.  After md_begin, before the first md_run; every = 0 detaches.  md_msd_table() reads the table.  Langevin,
+        velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter=, md_meta and md_record;
+        a barostat, a committee, a relaxation, a band, a polymer and several ranks: NotImplementedError."""
+        try:
+            check(_lib.load().sgpr_md_msd(self._h, int(every), int(levels), 1 if com else 0))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        self._md["msd"] = (int(every), int(levels)) if every else None
+
+    def md_msd_table(self):
+        """The table of md_msd as it stands (sgpr_md_msd_read; between two md_run calls): dict(lags [L] in evaluations,
+        count [L] windows per level, msd, msd_sq, smd, smd_sq [L, S] the sums over a level's windows per species, species [S]
+        the model's table, n [S] its atoms in the frame, samples, next_due)."""
+        if not self._md.get("msd"):
+            raise RuntimeError("md_msd_table: no accumulator on this run (md_msd)")
+        every, L = self._md["msd"]
+        S = len(self.species)
+        tab, cnt, info = np.zeros((L, S, 4)), np.zeros(L, dtype=np.int64), np.zeros(2, dtype=np.int64)
+        check(_lib.load().sgpr_md_msd_read(self._h, ptr(tab), ptr(cnt), ptr(info)))
+        numbers = np.asarray(self._md["numbers"])
+        return dict(lags=every * 2 ** np.arange(L, dtype=np.int64), count=cnt, msd=tab[:, :, 0].copy(), msd_sq=tab[:, :, 1].copy(),
+                    smd=tab[:, :, 2].copy(), smd_sq=tab[:, :, 3].copy(), species=np.array([int(z) for z in self.species]),
+                    n=np.array([int(np.sum(numbers == int(z))) for z in self.species]), samples=int(info[0]), next_due=int(info[1]))
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

@@ -1714,6 +1714,110 @@ def pimd_baoab(calc, numbers, beads, cell, pbc, steps, temperature=600.0, dt_fs=
         n += 1
 
 
+MSD_CHUNK = 256   # sorted atoms of one species per workgroup of md_msd_part_kernel (md_msd.inc)
+
+
+def _block_order_sums(p):
+    """_block_order_sum along the last axis of p[..., 256], every row at once: the same additions in the same order."""
+    v = np.asarray(p, float).reshape(p.shape[:-1] + (4, 64))
+    i = np.arange(64)
+    v = v + v[..., i ^ 1]
+    v = v + v[..., i ^ 2]
+    v = v + v[..., (i & ~7) | (7 - (i & 7))]
+    v = v + v[..., (i & ~15) | (15 - (i & 15))]
+    w = (v[..., 0] + v[..., 16]) + (v[..., 32] + v[..., 48])
+    return (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+
+
+class MsdBlocks:
+    """Mean-square displacements by blocked multiple origins — the host twin of the accumulator inside the device loop
+    (SGPRModel.md_msd, md_msd.inc) and its definition: the same operations in the same order, so the two tables agree bit
+    for bit.  What theforce/analysis/analysis.py:109-176 (`correlator`: the tracer msd mean_i |dr_i|^2 and the collective
+    smd |sum_i dr_i|^2 / n of a species) works out of a stored trajectory, taken as the run goes.
+      add(x) is fed the configurations 0, 1, 2, ... of a run ([N, 3], caller atom order, never wrapped).  Configuration n with
+    n % every == 0 is sample s = n / every.  Level l < levels has the lag 2^l samples and keeps ONE origin O_l; at sample s
+    every level with s mod 2^l == 0 measures, if s >= 2^l, d_i = x_i - O_l,i and then sets O_l <- x:
+        c   = sum_all m_i d_i / sum_all m_i  (com; else 0)
+        msd = ((A - 2 c.B) + n_z |c|^2) / n_z,  A = sum_z |d_i|^2,  B = sum_z d_i      (mean |d_i - c|^2)
+        smd = |B - n_z c|^2 / n_z
+    per species z of `species` (the model's table; one absent from the frame keeps zeros); the row (l, z) gains msd, msd^2, smd,
+    smd^2 and count[l] gains 1.  The windows of a level do not overlap: its samples are independent blocks.
+      Order: atoms sorted by species (stable), a species cut into chunks of MSD_CHUNK atoms; per chunk the seven sums A, B, sum m d
+    in the workgroup's order (_block_order_sum, one atom per thread, the per-atom term (d0 d0 + d1 d1) + d2 d2); the chunks of a
+    species ascending; sum m d over the species in table order; the total mass atom by atom in sorted order."""
+
+    def __init__(self, every, levels, com, masses, numbers, species):
+        if every < 1 or not 1 <= levels <= 32:
+            raise ValueError("MsdBlocks: every >= 1, 1 <= levels <= 32")
+        self.every, self.levels, self.com = int(every), int(levels), bool(com)
+        numbers = np.asarray(numbers)
+        self.species = [int(z) for z in species]
+        zi = np.array([self.species.index(int(z)) for z in numbers])
+        self.perm = np.argsort(zi, kind="stable")
+        self.nz = np.array([int(np.sum(zi == z)) for z in range(len(self.species))])
+        self.mass = np.asarray(masses, float)[self.perm]
+        self.mtot = 0.0
+        for v in self.mass:
+            self.mtot = self.mtot + float(v)
+        self.chunks, first = [], 0   # (species, first atom, atoms)
+        for z, nz in enumerate(self.nz):
+            self.chunks += [(z, first + o, min(MSD_CHUNK, nz - o)) for o in range(0, nz, MSD_CHUNK)]
+            first += nz
+        self.origin = [None] * self.levels
+        self.count = np.zeros(self.levels, dtype=np.int64)
+        self.sums = np.zeros((self.levels, len(self.species), 4))
+        self.n = 0   # configurations seen
+
+    def _measure(self, l, x):
+        d = x - self.origin[l]
+        terms = np.concatenate([((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None], d, self.mass[:, None] * d], axis=1)
+        pad = np.zeros((len(self.chunks), 7, MSD_CHUNK))
+        for c, (_, a, k) in enumerate(self.chunks):
+            pad[c, :, :k] = terms[a:a + k].T
+        part = _block_order_sums(pad)   # [chunks, 7]
+        S = len(self.species)
+        sums = np.zeros((S, 7))
+        for c, (z, _, _) in enumerate(self.chunks):
+            sums[z] = sums[z] + part[c]
+        cm = np.zeros(3)
+        if self.com:
+            for z in range(S):
+                cm = cm + sums[z, 4:7]
+            cm = cm / self.mtot
+        for z in range(S):
+            if self.nz[z] == 0:
+                continue
+            fn, A, B = float(self.nz[z]), sums[z, 0], sums[z, 1:4]
+            cB = (cm[0] * B[0] + cm[1] * B[1]) + cm[2] * B[2]
+            cc = (cm[0] * cm[0] + cm[1] * cm[1]) + cm[2] * cm[2]
+            msd = ((A - 2.0 * cB) + fn * cc) / fn
+            e = B - fn * cm
+            smd = ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) / fn
+            self.sums[l, z] = self.sums[l, z] + np.array([msd, msd * msd, smd, smd * smd])
+        self.count[l] += 1
+
+    def add(self, positions):
+        """The next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        s = n // self.every
+        x = np.asarray(positions, float).reshape(-1, 3)[self.perm]
+        for l in range(self.levels):
+            if s % (1 << l):
+                break
+            if s >= (1 << l):
+                self._measure(l, x)
+            self.origin[l] = x.copy()
+
+    def table(self):
+        """What SGPRModel.md_msd_table returns."""
+        return dict(lags=self.every * 2 ** np.arange(self.levels, dtype=np.int64), count=self.count.copy(), msd=self.sums[:, :, 0].copy(),
+                    msd_sq=self.sums[:, :, 1].copy(), smd=self.sums[:, :, 2].copy(), smd_sq=self.sums[:, :, 3].copy(),
+                    species=np.array(self.species), n=self.nz.copy(), samples=-(-self.n // self.every), next_due=-(-self.n // self.every) * self.every)
+
+
 def philox4x32_10(counter, key):
     """Philox4x32 with ten rounds (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11, section
     3.3 and the constants of its table): counter[..., 4] and key[..., 2] 32-bit words -> uint32[..., 4].  One round takes

@@ -559,6 +559,29 @@ int sgpr_md_fix(sgpr_model *h, const uint8_t *fixed3N);
 int sgpr_md_record(sgpr_model *h, int every, int what);
 int sgpr_md_frame_count(sgpr_model *h, int *count);
 int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *positions, double *velocities_pre, double *packed);
+/* Mean-square displacements accumulated inside the loop: what the reference computes from a stored trajectory
+ * (theforce/analysis/analysis.py:109-176 `correlator`, :296-338 `diffusion_constants`) without the trajectory leaving the device.
+ * Sample s is configuration n = s every.  Level l < levels has the lag 2^l samples and ONE origin O_l; at sample s every level
+ * with s mod 2^l == 0 measures, if s >= 2^l, d_i = x_i - O_l,i (the positions of the run are never wrapped; a held component
+ * has d = 0) and then sets O_l <- x.  With c = sum m_i d_i / sum m_i over all atoms (com = 1; else 0), per species z of the
+ * model's table with n_z atoms in the frame, A = sum |d_i|^2 and B = sum d_i:
+ *     msd = (A - 2 c.B + n_z |c|^2) / n_z  (= mean |d_i - c|^2),     smd = |B - n_z c|^2 / n_z
+ * and the row (l, z) of the table gains msd, msd^2, smd, smd^2, count[l] gains 1.  The windows of a level do not overlap, so
+ * sqrt(var / count) is an error bar.  A species absent from the frame keeps zeros.  Fixed summation order, no float atomics:
+ * two runs give the same bits, however the run is cut into calls; a configuration evaluated twice (the repeat behind a covloss
+ * halt or an overflow) counts once, the speculative evaluation behind a halt not at all.
+ *
+ * sgpr_md_msd       every >= 1, 1 <= levels <= 32, com 0 / 1: after sgpr_md_begin (and sgpr_md_fix, _thermostat, _filter, _meta,
+ *                   _record, if used), before the first sgpr_md_run; zeroes the table.  every = 0 detaches: the run launches what
+ *                   it launched before.  Two small launches behind a sampled evaluation, levels x 3N doubles of device memory.
+ *                   SGPR_E_INVALID: no run begun, a run that has started, values out of range.  SGPR_E_UNSUPPORTED: several
+ *                   ranks, a barostat, a committee, a relaxation, a band, a polymer — and from sgpr_md_barostat, _committee,
+ *                   _relax, _neb and _pimd on a run that has the accumulator.
+ * sgpr_md_msd_read  between two calls of the run (synchronises the stream): table[levels][S][4] (S: the model's species),
+ *                   counts[levels], info[2] = samples taken, the configuration the table waits for next.  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_msd(sgpr_model *h, int every, int levels, int com);
+int sgpr_md_msd_read(sgpr_model *h, double *table, int64_t *counts, int64_t *info);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
