@@ -552,7 +552,7 @@ class ActiveCalculator(Calculator):
     RECORD_BYTES = 256 << 20   # the frame record of one md_run call (run_md, run_relax) stays within this much device memory
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None, rdf=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -609,15 +609,22 @@ class ActiveCalculator(Calculator):
         are added to it at the end (transport.diffusion_constants reads it; one holder carries several runs).  The device loop
         accumulates them itself (SGPRModel.md_msd: two small launches behind a sampled evaluation, the table read once at the
         end); with a barostat, a committee or several ranks, and in the host loops, workloads.MsdBlocks — the same operations
-        in the same order — is fed the positions of every step.  None: nothing is accumulated, today's run."""
+        in the same order — is fed the positions of every step.  None: nothing is accumulated, today's run.
+        rdf: a transport.Rdf(every, rmax, bins, rmin) holder — the pair-distance counts of the run's configurations 0 ... steps
+        are added to it at the end (transport.radial_distribution forms g(r); one holder carries several runs), by the same
+        conventions: the device loop counts them itself (SGPRModel.md_rdf: a pair sweep behind a sampled evaluation, the table
+        read once at the end); with a committee or several ranks, and in the host loops, workloads.RdfCounts — the same integers —
+        is fed the positions of every step.  The cell is constant: with a barostat NotImplementedError."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, FilterState, MsdBlocks, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, FilterState, MsdBlocks, RdfCounts, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
         filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
         npt = pfactor is not None
         if npt and not nh:
             raise ValueError("run_md: a barostat (pfactor) needs the Nose-Hoover thermostat (tdamp_fs)")
+        if npt and rdf is not None:
+            raise NotImplementedError("run_md: rdf= with a barostat (pfactor): pair distances are counted at constant cell")
         baro = dict(pfactor=pfactor, externalstress=externalstress, mask=mask, iso=iso) if npt else {}
 
         fx = held(self.constraint_mask(atoms))
@@ -651,7 +658,8 @@ class ActiveCalculator(Calculator):
             return (self.md_on_device_ok() and not (committee and fx is not None)
                     and not (flt is not None and (committee or self._dist()[1] > 1))
                     and not (self.meta is not None and (npt or committee or self._dist()[1] > 1))
-                    and not (msd is not None and (npt or committee or self._dist()[1] > 1)))
+                    and not (msd is not None and (npt or committee or self._dist()[1] > 1))
+                    and not (rdf is not None and (committee or self._dist()[1] > 1)))
         seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -666,9 +674,13 @@ class ActiveCalculator(Calculator):
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold, **filt))
                 blocks = None if msd is None else MsdBlocks(msd.every, msd.levels, msd.com, masses, numbers,
                                                             getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
+                counts = None if rdf is None else RdfCounts(rdf.every, rdf.rmax, rdf.bins, rdf.rmin, numbers,
+                                                            getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
                 for st, E, T, _, p, v, *rest in loop:
                     if blocks is not None:
                         blocks.add(p)
+                    if counts is not None:
+                        counts.add(p)
                     if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
                         self.meta.update()
                     put_state(atoms, dict(positions=p, velocities=v, cell=rest[0] if npt else None), npt, "velocities")
@@ -677,6 +689,8 @@ class ActiveCalculator(Calculator):
                     yield st, E, T, bool(self.updated), _
                 if blocks is not None:
                     msd.add(blocks.table())
+                if counts is not None:
+                    rdf.add(counts.table())
                 return
         eng = self.engine
         kT, dof_kB = kB * temperature_K, dof * kB
@@ -686,6 +700,8 @@ class ActiveCalculator(Calculator):
         attached = self._md_attach(eng)
         if msd is not None:
             eng.md_msd(msd.every, msd.levels, msd.com)
+        if rdf is not None:
+            eng.md_rdf(rdf.every, rdf.rmax, rdf.bins, rdf.rmin)
         meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
@@ -771,6 +787,8 @@ class ActiveCalculator(Calculator):
             flt.f, flt.s = eng.md_filter_state()
         if msd is not None:
             msd.add(eng.md_msd_table())
+        if rdf is not None:
+            rdf.add(eng.md_rdf_table())
         if attached:
             self._md_attached_done(eng, attached)
 

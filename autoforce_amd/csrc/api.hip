@@ -283,6 +283,9 @@ struct MdRun {
     // the mean-square displacements (sgpr_md_msd, md_msd.inc): every `every`-th configuration is a sample, `levels` lags in
     // powers of two; nch chunks of one species each, S species of the model's table, the frame's total mass
     struct Msd { int every = 0, levels = 0, com = 0, nch = 0, S = 0; double mtot = 0.0; } msd;
+    // the radial distribution functions (sgpr_md_rdf, md_rdf.inc): every `every`-th configuration is a sample; npairs tile pairs of
+    // one species pair each, S species of the model's table, the constant cell with its image block, its volume
+    struct Rdf { int every = 0, npairs = 0, split = 1, S = 0; bool images = false; RdfGeom g = {}; double volume = 0.0; } rdf;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -363,6 +366,12 @@ struct MdState {
         DevBuf<int> tab;                      // [nch][2] the chunks | [S + 1] a species' chunks | [S] its atoms
         bool held() const { return ctl.p != nullptr; }
     } msd;
+    struct RdfBufs {
+        DevBuf<unsigned long long> table;     // [S][S][bins], a <= b filled
+        DevBuf<long long> ctl;                // next_due | samples
+        DevBuf<int> tab;                      // [npairs][RDF_PAIR] the tile pairs | [S] a species' atoms
+        bool held() const { return ctl.p != nullptr; }
+    } rdf;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1287,6 +1296,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_pimd.inc"
 #include "md_record.inc"
 #include "md_msd.inc"
+#include "md_rdf.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next

@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -189,6 +189,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates displacements (sgpr_md_msd), which are defined at constant cell");
+    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates pair distances (sgpr_md_rdf), whose image block and densities are those of a constant cell");
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -383,6 +384,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a ring polymer (sgpr_md_pimd), which serves dynamics only");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
+    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -742,6 +744,20 @@ static void md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st)
                        a.com, due, acc, (const double *)m.msd.part.p, m.msd.table.p, m.msd.ctl.p, n, a.every, (const int *)m.halt.p, step);
 }
 
+// The same for the pair distances (md_rdf.inc): the pair sweep over the X slot of configuration n — the R = 0 form where no
+// image but the nearest can come within rmax — and the launch that counts the sample.
+static void md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::Rdf &a = m.run.rdf;
+    const long long n = m.run.t + j;
+    const double *x = m.X.p + (size_t)3 * m.run.N * (size_t)(n % m.run.ring);
+    if (a.npairs)
+        hipLaunchKernelGGL(a.images ? md_rdf_pair_kernel<true> : md_rdf_pair_kernel<false>, dim3(a.npairs, a.split), dim3(256), 0, st, (const int *)m.rdf.tab.p, x,
+                           a.g, m.rdf.table.p, (const long long *)m.rdf.ctl.p, n, (const int *)m.halt.p, step);
+    hipLaunchKernelGGL(md_rdf_done_kernel, dim3(1), dim3(64), 0, st, m.rdf.ctl.p, n, a.every, (const int *)m.halt.p, step);
+}
+
 // Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
 // one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
 // again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
@@ -907,6 +923,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates displacements (sgpr_md_msd), which the committee's loop does not sample");
+    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates pair distances (sgpr_md_rdf), which the committee's loop does not sample");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1274,6 +1291,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a ring polymer (sgpr_md_pimd)");
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
+    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1399,6 +1417,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: %d components are held (sgpr_md_fix); a polymer runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: a frame record is armed (sgpr_md_record); a polymer records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates displacements (sgpr_md_msd); a polymer's centroid is not sampled");
+    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates pair distances (sgpr_md_rdf); a polymer's beads are not sampled");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1604,6 +1623,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         // read here are written again only when the rings come round)
         if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         if (m.run.msd.every && (m.run.t + j) % m.run.msd.every == 0) md_msd_sample(h, j, (int)(step0 + j), st);
+        if (m.run.rdf.every && (m.run.t + j) % m.run.rdf.every == 0) md_rdf_sample(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -1853,6 +1873,140 @@ extern "C" int sgpr_md_msd_read(sgpr_model *h, double *table, int64_t *counts, i
     if (table) HIPCHK(hipMemcpy(table, m.msd.table.p, sizeof(double) * (size_t)a.levels * a.S * 4, hipMemcpyDeviceToHost));
     if (counts) for (int l = 0; l < a.levels; l++) counts[l] = ctl[1 + l];
     if (info) { info[0] = ctl[0] / a.every; info[1] = ctl[0]; }
+    return SGPR_OK;
+}
+
+// The cell of the pair sweep, on the host at the attach: the inverse by the cofactor formula of nl_make_grid (restated in
+// workloads.RdfCounts, operation for operation), the volume |det|, the heights V / |cross| and the image block
+// R_k = floor(rmax / height_k + 1/2) along the periodic directions.  false: no volume.
+static bool md_rdf_geometry(const double *cell, const int32_t *pbc, double rmax, RdfGeom &g, double &volume, double *height)
+{
+#pragma clang fp contract(off)
+    const double *p = cell, *q = cell + 3, *r = cell + 6;
+    const double dt = p[0] * (q[1] * r[2] - q[2] * r[1]) - p[1] * (q[0] * r[2] - q[2] * r[0]) + p[2] * (q[0] * r[1] - q[1] * r[0]);
+    if (!(fabs(dt) > 1e-12)) return false;
+    const double bc[3] = {q[1] * r[2] - q[2] * r[1], q[2] * r[0] - q[0] * r[2], q[0] * r[1] - q[1] * r[0]};
+    const double ca[3] = {r[1] * p[2] - r[2] * p[1], r[2] * p[0] - r[0] * p[2], r[0] * p[1] - r[1] * p[0]};
+    const double ab[3] = {p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]};
+    for (int k = 0; k < 3; k++) {
+        g.inv[3 * k + 0] = bc[k] / dt;
+        g.inv[3 * k + 1] = ca[k] / dt;
+        g.inv[3 * k + 2] = ab[k] / dt;
+    }
+    for (int k = 0; k < 9; k++) g.h[k] = cell[k];
+    volume = fabs(dt);
+    height[0] = volume / sqrt((bc[0] * bc[0] + bc[1] * bc[1]) + bc[2] * bc[2]);
+    height[1] = volume / sqrt((ca[0] * ca[0] + ca[1] * ca[1]) + ca[2] * ca[2]);
+    height[2] = volume / sqrt((ab[0] * ab[0] + ab[1] * ab[1]) + ab[2] * ab[2]);
+    for (int k = 0; k < 3; k++) {
+        g.pbc[k] = pbc[k] ? 1 : 0;
+        const double f = floor(rmax / height[k] + 0.5);
+        g.R[k] = pbc[k] ? (f > 1e6 ? 1000000 : (int)f) : 0;
+    }
+    return true;
+}
+
+// Radial distribution functions of the run (md_rdf.inc has the definition; workloads.RdfCounts is the host twin): every >= 1 —
+// behind the evaluation of configuration n with n % every == 0 two launches add the configuration's pair distances in
+// [rmin, rmax) to a table of integers in device memory, `bins` bins per pair of species of the model's table, periodic images
+// and self-images included (rmax may exceed the model's cutoff and half the cell: up to two images either way per direction).
+// After sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record, _msd), before the first sgpr_md_run; every = 0 detaches.
+// The attach zeroes the table.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, beside a mask, the
+// filter, a bias, the frame record and sgpr_md_msd (each keeps its own next_due); a barostat, a committee, a relaxation, a
+// band, a polymer and several ranks: SGPR_E_UNSUPPORTED, from here and from their attach functions.
+extern "C" int sgpr_md_rdf(sgpr_model *h, int every, double rmin, double rmax, int bins)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_rdf: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_rdf: call sgpr_md_begin first");
+    if (every == 0) {   // (a detach gives the table back: nothing of it is launched or read from here on)
+        m.run.rdf = MdRun::Rdf();
+        if (m.rdf.held()) {
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            m.rdf = MdState::RdfBufs();
+        }
+        return SGPR_OK;
+    }
+    if (every < 0 || bins < 1 || bins > RDF_MAXBINS || !(rmin >= 0.0) || !(rmin < rmax) || !(rmax < 1e300))
+        return fail(SGPR_E_INVALID, "sgpr_md_rdf: every >= 0, 1 <= bins <= %d, 0 <= rmin < rmax", RDF_MAXBINS);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_rdf: the run has started");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run was begun on %d ranks; pair distances are accumulated on one", m.run.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run has a barostat; the image block and the densities are those of a constant cell");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run has a committee (sgpr_md_committee), whose loop does not sample pair distances");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a relaxation; pair distances are accumulated over dynamics");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a nudged elastic band; pair distances are accumulated over dynamics");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
+    const int N = m.run.N, S = h->S;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double cell[9], height[3], volume = 0.0;
+    HIPCHK(hipMemcpy(cell, m.cell.p, sizeof(double) * 9, hipMemcpyDeviceToHost));
+    RdfGeom g = {};
+    if (!md_rdf_geometry(cell, m.run.pbc, rmax, g, volume, height)) return fail(SGPR_E_INVALID, "sgpr_md_rdf: the cell has no volume; densities need one");
+    for (int k = 0; k < 3; k++)
+        if (g.R[k] > RDF_MAXR)
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: rmax = %g against the cell height %g along direction %d needs images %d cells away; at most %d (125 shifts)",
+                        rmax, height[k], k, g.R[k], RDF_MAXR);
+    g.rmin = rmin; g.rmax = rmax; g.bins = bins;
+    // the tiles: runs of at most RDF_TILE consecutive sorted atoms of one species (the sort is by species in table order), and
+    // the tile pairs I <= J
+    std::vector<int> nz(S, 0), first(S, 0);
+    for (int i = 0, last = 0; i < N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
+        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_rdf: the run's atoms are not sorted by the model's species");
+        last = z; nz[z]++;
+    }
+    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
+    std::vector<int> tab;
+    for (int a = 0; a < S; a++)
+        for (int oa = 0; oa < nz[a]; oa += RDF_TILE)
+            for (int b = a; b < S; b++)
+                for (int ob = (b == a ? oa : 0); ob < nz[b]; ob += RDF_TILE) {
+                    const int rec[RDF_PAIR] = {first[a] + oa, std::min(RDF_TILE, nz[a] - oa), first[b] + ob, std::min(RDF_TILE, nz[b] - ob),
+                                               a * S + b, (a == b && ob != oa) ? 2 : 1};
+                    tab.insert(tab.end(), rec, rec + RDF_PAIR);
+                }
+    const int npairs = (int)tab.size() / RDF_PAIR;
+    tab.insert(tab.end(), nz.begin(), nz.end());
+    if (m.rdf.table.alloc((size_t)S * S * bins) || m.rdf.ctl.alloc(2) || m.rdf.tab.alloc(tab.size(), false))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_rdf: device allocation failed");
+    HIPCHK(hipMemcpy(m.rdf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    MdRun::Rdf &a = m.run.rdf;
+    // (workgroups for every SIMD of the chip: a tile pair of a small frame is cut along J into up to 8 parts of 16 atoms or more)
+    a.split = std::max(1, std::min(RDF_SPLIT_MAX, RDF_WORKGROUPS / std::max(1, npairs)));
+    a.every = every; a.npairs = npairs; a.S = S; a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.volume = volume;
+    return SGPR_OK;
+}
+
+// The table as it stands (between two calls of a run; the stream is synchronised): hist [S][S][bins] the counts per ordered pair
+// of species slots, symmetric and filled out; info [4 + S] = samples taken, next_due (the configuration the table waits for),
+// bins, S, and the atoms of every species in the frame; geom [3] = the volume |det cell|, rmin, rmax.  Any pointer may be NULL.
+extern "C" int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, double *geom)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_rdf_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.rdf.every) return fail(SGPR_E_INVALID, "sgpr_md_rdf_read: call sgpr_md_begin and sgpr_md_rdf first");
+    const MdRun::Rdf &a = m.run.rdf;
+    const int S = a.S, bins = a.g.bins;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (hist) {
+        HIPCHK(hipMemcpy(hist, m.rdf.table.p, sizeof(uint64_t) * (size_t)S * S * bins, hipMemcpyDeviceToHost));
+        for (int p = 0; p < S; p++)
+            for (int q = 0; q < p; q++)
+                for (int k = 0; k < bins; k++) hist[((size_t)p * S + q) * bins + k] = hist[((size_t)q * S + p) * bins + k];
+    }
+    if (info) {
+        long long ctl[2];
+        std::vector<int> nz(S);
+        HIPCHK(hipMemcpy(ctl, m.rdf.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nz.data(), m.rdf.tab.p + (size_t)RDF_PAIR * a.npairs, sizeof(int) * S, hipMemcpyDeviceToHost));
+        info[0] = ctl[1]; info[1] = ctl[0]; info[2] = bins; info[3] = S;
+        for (int z = 0; z < S; z++) info[4 + z] = nz[z];
+    }
+    if (geom) { geom[0] = a.volume; geom[1] = a.g.rmin; geom[2] = a.g.rmax; }
     return SGPR_OK;
 }
 
@@ -2248,6 +2402,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.msd = MdState::MsdBufs();
+    }
+    if (m.rdf.held()) {   // (and the table of the pair distances)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.rdf = MdState::RdfBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

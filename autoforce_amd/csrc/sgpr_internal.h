@@ -175,6 +175,11 @@ enum { RLX_DT = 0, RLX_A = 1, RLX_NSTEPS = 2, RLX_FRESH = 3, RLX_XC = 4 /* [9] c
 // computed once on the host), pbc
 struct NebCell { double h[9], hi[9]; int pbc[3]; };
 
+// what the pair sweep of the radial distribution functions (sgpr_md_rdf; md_rdf.inc) knows of the run's constant cell and of its
+// histogram: h (rows = vectors), its inverse by the cofactor formula of nl_make_grid (computed once on the host), the image block
+// |s_k| <= R[k] around a pair's nearest image (0 along an open direction), the range and the number of bins
+struct RdfGeom { double h[9], inv[9], rmin, rmax; int R[3], pbc[3], bins; };
+
 // Bin populations sit SGPR_BIN_STRIDE ints apart: one counter per 128-byte line.  Packed, the ~350 counters of a 4096-atom
 // frame are eleven lines, and the returning atomics of the binning (one per atom, device scope: they execute at the
 // memory side, one after the other per line) were most of the binning kernel's 7 us.

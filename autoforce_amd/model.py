@@ -1154,6 +1154,36 @@ class SGPRModel:
                     smd=tab[:, :, 2].copy(), smd_sq=tab[:, :, 3].copy(), species=np.array([int(z) for z in self.species]),
                     n=np.array([int(np.sum(numbers == int(z))) for z in self.species]), samples=int(info[0]), next_due=int(info[1]))
 
+    def md_rdf(self, every, rmax, bins=100, rmin=0.0):
+        """Accumulate radial distribution functions inside the loop (sgpr_md_rdf; md_rdf.inc has the scheme, workloads.RdfCounts
+        is the host twin and the definition): behind the evaluation of every configuration n with n % every == 0 the distances
+        rmin <= r < rmax of all pairs — periodic images and self-images included; rmax may exceed the model's cutoff and half
+        the cell — are counted into `bins` bins per pair of species of the model's table, as integers: what
+        theforce/analysis/rdf.py's `rdf` works out of a stored trajectory.  After md_begin, before the first md_run; every = 0
+        detaches.  md_rdf_table() reads the counts, transport.radial_distribution forms g(r).  Langevin, velocity Verlet and
+        Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter=, md_meta, md_record and md_msd; a barostat,
+        a committee, a relaxation, a band, a polymer, several ranks and an rmax beyond 2.5 cell heights: NotImplementedError."""
+        try:
+            check(_lib.load().sgpr_md_rdf(self._h, int(every), float(rmin), float(rmax), int(bins)))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        self._md["rdf"] = (int(every), int(bins)) if every else None
+
+    def md_rdf_table(self):
+        """The table of md_rdf as it stands (sgpr_md_rdf_read; between two md_run calls): dict(hist [S, S, bins] uint64 the
+        counts per ordered pair of species slots (symmetric), species [S] the model's table, n [S] its atoms in the frame,
+        samples, next_due, every, bins, rmin, rmax, volume)."""
+        if not self._md.get("rdf"):
+            raise RuntimeError("md_rdf_table: no accumulator on this run (md_rdf)")
+        every, bins = self._md["rdf"]
+        S = len(self.species)
+        hist, info, geom = np.zeros((S, S, bins), dtype=np.uint64), np.zeros(4 + S, dtype=np.int64), np.zeros(3)
+        check(_lib.load().sgpr_md_rdf_read(self._h, ptr(hist), ptr(info), ptr(geom)))
+        return dict(hist=hist, species=np.array([int(z) for z in self.species]), n=info[4:].copy(), samples=int(info[0]), next_due=int(info[1]),
+                    every=every, bins=int(info[2]), rmin=float(geom[1]), rmax=float(geom[2]), volume=float(geom[0]))
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

@@ -1818,6 +1818,107 @@ class MsdBlocks:
                     species=np.array(self.species), n=self.nz.copy(), samples=-(-self.n // self.every), next_due=-(-self.n // self.every) * self.every)
 
 
+RDF_MAXR = 2      # images |s_k| <= 2 around a pair's nearest one: at most 125 shifts (md_rdf.inc)
+RDF_MAXBINS = 2048
+
+
+def rdf_geometry(cell, pbc, rmax):
+    """What sgpr_md_rdf works out of the run's cell at the attach, operation for operation: (inv [3, 3] with frac_c = sum_k
+    x_k inv[k, c], by the cofactor formula of nl_make_grid; volume |det|; heights [3] = V / |cross|; R [3] = floor(rmax /
+    height_k + 1/2), 0 along an open direction — every image of a pair that can come within rmax lies within R of its nearest)."""
+    h = [[float(v) for v in row] for row in np.asarray(cell, float).reshape(3, 3)]
+    p, q, r = h
+    dt = p[0] * (q[1] * r[2] - q[2] * r[1]) - p[1] * (q[0] * r[2] - q[2] * r[0]) + p[2] * (q[0] * r[1] - q[1] * r[0])
+    if not abs(dt) > 1e-12:
+        raise ValueError("rdf_geometry: the cell has no volume; densities need one")
+    bc = [q[1] * r[2] - q[2] * r[1], q[2] * r[0] - q[0] * r[2], q[0] * r[1] - q[1] * r[0]]
+    ca = [r[1] * p[2] - r[2] * p[1], r[2] * p[0] - r[0] * p[2], r[0] * p[1] - r[1] * p[0]]
+    ab = [p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]]
+    inv = np.array([[bc[k] / dt, ca[k] / dt, ab[k] / dt] for k in range(3)])
+    V = abs(dt)
+    heights = np.array([V / np.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) for c in (bc, ca, ab)])
+    R = np.array([int(np.floor(float(rmax) / heights[k] + 0.5)) if pbc[k] else 0 for k in range(3)])
+    return inv, V, heights, R
+
+
+class RdfCounts:
+    """Pair-distance histograms per species pair — the host twin of the accumulator inside the device loop (SGPRModel.md_rdf,
+    md_rdf.inc) and its definition; the counts are integers, so the two tables are equal.  What theforce/analysis/rdf.py's
+    `rdf` takes from every atom's neighbour list at cutoff rmax, from the configurations as the run goes.
+      add(x) is fed the configurations 0, 1, 2, ... of a run ([N, 3], caller atom order, wrapped or not); those with n % every
+    == 0 are samples.  For a sample, species slots a, b of `species` (the model's table) and k < bins, hist[a, b, k] gains the
+    number of triples (i of a, j of b, s in Z^3) with (j, s) != (i, 0) — periodic self-images count — and
+        d = (x_j - x_i) + ((s0 h0 + s1 h1) + s2 h2),  r = sqrt((d0 d0 + d1 d1) + d2 d2),  rmin <= r < rmax,
+        k = (int)(((r - rmin) / (rmax - rmin)) bins)   (torch.histc's rule; a quotient that rounds up to `bins`: the last bin)
+    with s = 0 along an open direction.  Enumeration: a pair goes to its nearest image by n_k = rint((dx0 inv[0, k] + dx1
+    inv[1, k]) + dx2 inv[2, k]) (rdf_geometry's inverse), then s = t - n over the block |t_k| <= R_k.  d depends on (i, j, s)
+    alone: brute force over all pairs here, tiles on the device, the same integers.  hist[b, a] = hist[a, b] exactly (i <-> j
+    negates every intermediate), so a <= b is swept and the table filled out."""
+
+    def __init__(self, every, rmax, bins, rmin, numbers, species, cell, pbc):
+        if every < 1 or not 1 <= bins <= RDF_MAXBINS or not 0.0 <= rmin < rmax:
+            raise ValueError(f"RdfCounts: every >= 1, 1 <= bins <= {RDF_MAXBINS}, 0 <= rmin < rmax")
+        self.every, self.bins, self.rmin, self.rmax = int(every), int(bins), float(rmin), float(rmax)
+        self.h = np.asarray(cell, float).reshape(3, 3).copy()
+        self.pbc = np.broadcast_to(np.asarray(pbc, bool), (3,)).copy()
+        self.inv, self.volume, self.heights, self.R = rdf_geometry(self.h, self.pbc, self.rmax)
+        for k in range(3):
+            if self.R[k] > RDF_MAXR:
+                raise NotImplementedError(f"RdfCounts: rmax = {self.rmax:g} against the cell height {self.heights[k]:g} along direction {k} needs "
+                                          f"images {self.R[k]} cells away; at most {RDF_MAXR} (125 shifts)")
+        numbers = np.asarray(numbers)
+        self.species = [int(z) for z in species]
+        self.idx = [np.flatnonzero(numbers == z) for z in self.species]
+        self.nz = np.array([len(i) for i in self.idx])
+        self.hist = np.zeros((len(self.species), len(self.species), self.bins), dtype=np.uint64)
+        self.n = 0   # configurations seen
+
+    def _pairs(self, xi, xj, same):
+        """The counts [bins] of the i-atoms xi against the j-atoms xj (same: they are one list, (j, 0) == (i, 0) stays out)."""
+        h, inv, out = self.h, self.inv, np.zeros(self.bins, dtype=np.int64)
+        width, fbins = self.rmax - self.rmin, float(self.bins)
+        for o in range(0, len(xi), 256):
+            dx = xj[None, :, :] - xi[o:o + 256, None, :]
+            dx0, dx1, dx2 = dx[..., 0], dx[..., 1], dx[..., 2]
+            n = [np.rint((dx0 * inv[0, k] + dx1 * inv[1, k]) + dx2 * inv[2, k]) if self.pbc[k] else np.zeros_like(dx0) for k in range(3)]
+            for t0 in range(-self.R[0], self.R[0] + 1):
+                for t1 in range(-self.R[1], self.R[1] + 1):
+                    for t2 in range(-self.R[2], self.R[2] + 1):
+                        s0, s1, s2 = float(t0) - n[0], float(t1) - n[1], float(t2) - n[2]
+                        d0 = dx0 + ((s0 * h[0, 0] + s1 * h[1, 0]) + s2 * h[2, 0])
+                        d1 = dx1 + ((s0 * h[0, 1] + s1 * h[1, 1]) + s2 * h[2, 1])
+                        d2 = dx2 + ((s0 * h[0, 2] + s1 * h[1, 2]) + s2 * h[2, 2])
+                        r = np.sqrt((d0 * d0 + d1 * d1) + d2 * d2)
+                        ok = (r >= self.rmin) & (r < self.rmax)
+                        if same and t0 == 0 and t1 == 0 and t2 == 0:
+                            rows = np.arange(dx.shape[0])
+                            ok[rows, o + rows] = False
+                        k = np.minimum((((r[ok] - self.rmin) / width) * fbins).astype(np.int64), self.bins - 1)
+                        out += np.bincount(k, minlength=self.bins)
+        return out
+
+    def add(self, positions):
+        """The next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        x = np.asarray(positions, float).reshape(-1, 3)
+        for a in range(len(self.species)):
+            for b in range(a, len(self.species)):
+                if self.nz[a] and self.nz[b]:
+                    c = self._pairs(x[self.idx[a]], x[self.idx[b]], a == b).astype(np.uint64)
+                    self.hist[a, b] += c
+                    if b != a:
+                        self.hist[b, a] += c
+
+    def table(self):
+        """What SGPRModel.md_rdf_table returns."""
+        samples = -(-self.n // self.every)
+        return dict(hist=self.hist.copy(), species=np.array(self.species), n=self.nz.copy(), samples=samples, next_due=samples * self.every,
+                    every=self.every, bins=self.bins, rmin=self.rmin, rmax=self.rmax, volume=self.volume)
+
+
 def philox4x32_10(counter, key):
     """Philox4x32 with ten rounds (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11, section
     3.3 and the constants of its table): counter[..., 4] and key[..., 2] 32-bit words -> uint32[..., 4].  One round takes

@@ -582,6 +582,33 @@ int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *
  * The handle stays usable after every error above. */
 int sgpr_md_msd(sgpr_model *h, int every, int levels, int com);
 int sgpr_md_msd_read(sgpr_model *h, double *table, int64_t *counts, int64_t *info);
+/* Radial distribution functions accumulated inside the loop: the pair-distance histograms the reference takes from a stored
+ * trajectory (theforce/analysis/rdf.py `rdf`), as integers in device memory.  Behind the evaluation of every configuration n
+ * with n % every == 0, for the species slots a, b of the model's table and k < bins, H[a][b][k] gains the number of triples
+ * (i of species a, j of species b, s in Z^3) with (j, s) != (i, 0) — periodic self-images count — and
+ *     d = (x_j - x_i) + ((s0 h0 + s1 h1) + s2 h2),  r = sqrt((d0 d0 + d1 d1) + d2 d2),  rmin <= r < rmax,
+ *     k = (int)(((r - rmin) / (rmax - rmin)) bins)     (a quotient that rounds up to `bins` stays in the last bin),
+ * h0, h1, h2 the cell vectors, s = 0 along an open direction.  rmax may exceed the model's cutoff and half the cell: every
+ * image within rmax is enumerated, up to two cells either way per direction.  Integer counts: the table is the same bits
+ * however the atoms were wrapped and however the run is cut; a configuration evaluated twice (the repeat behind a covloss halt
+ * or an overflow) counts once, the speculative evaluation behind a halt not at all.  g(r) is formed by the caller:
+ *     g_ab(k) = H[a][b][k] / (samples n_a shell_k n_b / V).
+ *
+ * sgpr_md_rdf       every >= 1, 0 <= rmin < rmax, 1 <= bins <= 2048: after sgpr_md_begin (and sgpr_md_fix, _thermostat, _filter,
+ *                   _meta, _record, _msd, if used), before the first sgpr_md_run; zeroes the table.  every = 0 detaches and
+ *                   frees the table: the run launches what it launched before.  Two launches behind a sampled evaluation, one
+ *                   workgroup per pair of 128-atom tiles: O(N^2) per sample.  SGPR_E_INVALID: no run begun, a run that has
+ *                   started, values out of range, a cell without volume, atoms not sorted by the model's species.
+ *                   SGPR_E_UNSUPPORTED: rmax beyond 2.5 heights of the cell along a periodic direction (the message names the
+ *                   height), several ranks, a barostat, a committee, a relaxation, a band, a polymer — and from
+ *                   sgpr_md_barostat, _committee, _relax, _neb and _pimd on a run that has the accumulator.
+ * sgpr_md_rdf_read  between two calls of the run (synchronises the stream): hist[S][S][bins] (S: the model's species; symmetric,
+ *                   filled out), info[4 + S] = samples taken, the configuration the table waits for next, bins, S, the atoms
+ *                   of every species in the frame; geom[3] = the volume |det cell|, rmin, rmax (bin k is
+ *                   [rmin + k w, rmin + (k + 1) w), w = (rmax - rmin) / bins).  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_rdf(sgpr_model *h, int every, double rmin, double rmax, int bins);
+int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, double *geom);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
