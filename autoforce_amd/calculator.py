@@ -552,7 +552,8 @@ class ActiveCalculator(Calculator):
     RECORD_BYTES = 256 << 20   # the frame record of one md_run call (run_md, run_relax) stays within this much device memory
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
-               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None, rdf=None):
+               tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None, rdf=None,
+               vacf=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -614,9 +615,15 @@ class ActiveCalculator(Calculator):
         are added to it at the end (transport.radial_distribution forms g(r); one holder carries several runs), by the same
         conventions: the device loop counts them itself (SGPRModel.md_rdf: a pair sweep behind a sampled evaluation, the table
         read once at the end); with a committee or several ranks, and in the host loops, workloads.RdfCounts — the same integers —
-        is fed the positions of every step.  The cell is constant: with a barostat NotImplementedError."""
+        is fed the positions of every step.  The cell is constant: with a barostat NotImplementedError.
+        vacf: a transport.Vacf(every, lags, origin_every, com) holder — the velocity correlations of the run's configurations
+        0 ... steps are added to it at the end (transport.green_kubo, onsager and vibrational_dos read it), by the same
+        conventions: the device loop accumulates them itself (SGPRModel.md_vacf: a store and a correlation behind a sampled
+        evaluation, the table read once at the end); with a barostat, a committee, several ranks, ml_filter= or a Meta, and in
+        the host loops, workloads.VacfRing — the same operations in the same order — is fed the velocities of every step.  The
+        last sample of a run stays pending (it counts when a later one arrives), in both."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, FilterState, MsdBlocks, RdfCounts, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, FilterState, MsdBlocks, RdfCounts, VacfRing, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
         filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
@@ -659,7 +666,8 @@ class ActiveCalculator(Calculator):
                     and not (flt is not None and (committee or self._dist()[1] > 1))
                     and not (self.meta is not None and (npt or committee or self._dist()[1] > 1))
                     and not (msd is not None and (npt or committee or self._dist()[1] > 1))
-                    and not (rdf is not None and (committee or self._dist()[1] > 1)))
+                    and not (rdf is not None and (committee or self._dist()[1] > 1))
+                    and not (vacf is not None and (npt or committee or self._dist()[1] > 1 or flt is not None or self.meta is not None)))
         seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -676,9 +684,13 @@ class ActiveCalculator(Calculator):
                                                             getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
                 counts = None if rdf is None else RdfCounts(rdf.every, rdf.rmax, rdf.bins, rdf.rmin, numbers,
                                                             getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
+                corr = None if vacf is None else VacfRing(vacf.every, vacf.nlags, vacf.origin_every, vacf.com, masses, numbers,
+                                                          getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
                 for st, E, T, _, p, v, *rest in loop:
                     if blocks is not None:
                         blocks.add(p)
+                    if corr is not None:
+                        corr.add(v)
                     if counts is not None:
                         counts.add(p)
                     if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
@@ -691,6 +703,8 @@ class ActiveCalculator(Calculator):
                     msd.add(blocks.table())
                 if counts is not None:
                     rdf.add(counts.table())
+                if corr is not None:
+                    vacf.add(corr.table())
                 return
         eng = self.engine
         kT, dof_kB = kB * temperature_K, dof * kB
@@ -702,6 +716,8 @@ class ActiveCalculator(Calculator):
             eng.md_msd(msd.every, msd.levels, msd.com)
         if rdf is not None:
             eng.md_rdf(rdf.every, rdf.rmax, rdf.bins, rdf.rmin)
+        if vacf is not None:
+            eng.md_vacf(vacf.every, vacf.nlags, vacf.origin_every, vacf.com)
         meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
@@ -789,6 +805,8 @@ class ActiveCalculator(Calculator):
             msd.add(eng.md_msd_table())
         if rdf is not None:
             rdf.add(eng.md_rdf_table())
+        if vacf is not None:
+            vacf.add(eng.md_vacf_table())
         if attached:
             self._md_attached_done(eng, attached)
 

@@ -286,6 +286,9 @@ struct MdRun {
     // the radial distribution functions (sgpr_md_rdf, md_rdf.inc): every `every`-th configuration is a sample; npairs tile pairs of
     // one species pair each, S species of the model's table, the constant cell with its image block, its volume
     struct Rdf { int every = 0, npairs = 0, split = 1, S = 0; bool images = false; RdfGeom g = {}; double volume = 0.0; } rdf;
+    // the velocity autocorrelations (sgpr_md_vacf, md_vacf.inc): every `every`-th configuration is a sample, `lags` lags of one
+    // sample each, origins every `origin_every`-th sample; nch chunks of one species each, S species, the frame's total mass
+    struct Vacf { int every = 0, lags = 0, origin_every = 1, com = 0, nch = 0, S = 0; double mtot = 0.0; } vacf;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -372,6 +375,13 @@ struct MdState {
         DevBuf<int> tab;                      // [npairs][RDF_PAIR] the tile pairs | [S] a species' atoms
         bool held() const { return ctl.p != nullptr; }
     } rdf;
+    struct VacfBufs {
+        DevBuf<double> ring, vpart, part;     // [lags + 1][N][3] sorted order, [lags + 1][nch][6], [lags][nch]
+        DevBuf<double> jring, cring, tr, col; // [lags + 1][S][3], [lags + 1][3], [lags][S], [lags][S][S]
+        DevBuf<long long> ctl;                // next_due | samples | count[lags]
+        DevBuf<int> tab;                      // [nch][2] the chunks | [S + 1] a species' chunks | [S] its atoms
+        bool held() const { return ctl.p != nullptr; }
+    } vacf;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1297,6 +1307,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_record.inc"
 #include "md_msd.inc"
 #include "md_rdf.inc"
+#include "md_vacf.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next

@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -190,6 +190,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates displacements (sgpr_md_msd), which are defined at constant cell");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates pair distances (sgpr_md_rdf), whose image block and densities are those of a constant cell");
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates velocity correlations (sgpr_md_vacf), which are not sampled in a moving cell");
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -385,6 +386,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a ring polymer (sgpr_md_pimd), which serves dynamics only");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -758,6 +760,33 @@ static void md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st)
     hipLaunchKernelGGL(md_rdf_done_kernel, dim3(1), dim3(64), 0, st, m.rdf.ctl.p, n, a.every, (const int *)m.halt.p, step);
 }
 
+// The same for the velocity autocorrelations (md_vacf.inc): the store of sample s = n / every — V slot n, under Langevin and
+// velocity Verlet with the closing half kick of the evaluation's packed force (n > 0) — and, for s > 0, the correlation of sample
+// s - 1 with its due origins; the launch that advances next_due.  Which lags are due follows from s and origin_every alone;
+// whether n is the awaited sample is the device's decision.
+static void md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::Vacf &a = m.run.vacf;
+    const long long n = m.run.t + j, s = n / a.every, p = s - 1;
+    const int N = m.run.N, slots = a.lags + 1, sl = (int)(n % m.run.ring);
+    const size_t N3 = (size_t)3 * N, ss = (size_t)(s % slots);
+    const int *chunk = m.vacf.tab.p, *coff = chunk + 2 * a.nch, *nz = coff + a.S + 1;
+    const bool kick = !m.run.nh.on && n > 0;
+    const int *halt = m.halt.p;
+    hipLaunchKernelGGL(md_vacf_store_kernel, dim3(a.nch), dim3(256), 0, st, chunk, (const double *)(m.V.p + N3 * sl),
+                       kick ? (const double *)(m.P.p + (size_t)sgpr_packed_len(N) * sl) : (const double *)nullptr, (const int *)h->d_perm.p,
+                       (const double *)m.mass.p, m.fix(), m.run.hdt, m.vacf.ring.p + N3 * ss, m.vacf.vpart.p + (size_t)6 * a.nch * ss, halt, step);
+    if (s > 0) {
+        hipLaunchKernelGGL(md_vacf_corr_kernel, dim3(a.nch, (a.lags + VACF_GROUP - 1) / VACF_GROUP), dim3(256), 0, st, chunk, a.nch,
+                           (const double *)m.vacf.ring.p, N3, slots, p, a.lags, a.origin_every, m.vacf.part.p, (const long long *)m.vacf.ctl.p, n, halt, step);
+        hipLaunchKernelGGL(md_vacf_fold_kernel, dim3((a.lags + VACF_FOLD - 1) / VACF_FOLD), dim3(256), sizeof(double) * (6 * a.S + 3), st, coff, nz,
+                           a.nch, a.S, a.lags, a.origin_every, slots, p, a.mtot, a.com, (const double *)m.vacf.vpart.p, (const double *)m.vacf.part.p,
+                           m.vacf.jring.p, m.vacf.cring.p, m.vacf.tr.p, m.vacf.col.p, m.vacf.ctl.p, n, halt, step);
+    }
+    hipLaunchKernelGGL(md_vacf_done_kernel, dim3(1), dim3(64), 0, st, m.vacf.ctl.p, n, a.every, s > 0 ? 1 : 0, halt, step);
+}
+
 // Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
 // one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
 // again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
@@ -924,6 +953,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates displacements (sgpr_md_msd), which the committee's loop does not sample");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates pair distances (sgpr_md_rdf), which the committee's loop does not sample");
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates velocity correlations (sgpr_md_vacf), which the committee's loop does not sample");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1292,6 +1322,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1418,6 +1449,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: a frame record is armed (sgpr_md_record); a polymer records no frames");
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates displacements (sgpr_md_msd); a polymer's centroid is not sampled");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates pair distances (sgpr_md_rdf); a polymer's beads are not sampled");
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates velocity correlations (sgpr_md_vacf); a polymer's centroid is not sampled");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1624,6 +1656,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
         if (m.run.msd.every && (m.run.t + j) % m.run.msd.every == 0) md_msd_sample(h, j, (int)(step0 + j), st);
         if (m.run.rdf.every && (m.run.t + j) % m.run.rdf.every == 0) md_rdf_sample(h, j, (int)(step0 + j), st);
+        if (m.run.vacf.every && (m.run.t + j) % m.run.vacf.every == 0) md_vacf_sample(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -2010,6 +2043,102 @@ extern "C" int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, do
     return SGPR_OK;
 }
 
+// Velocity autocorrelations of the run (md_vacf.inc has the definition; workloads.VacfRing is the host twin): every >= 1 —
+// configuration n with n % every == 0 is sample n / every; behind its evaluation its observer's velocity is stored in a ring of
+// lags + 1 slots and the sample before it is correlated with its origins o = s - k, k < lags, o % origin_every == 0: per species
+// of the model's table the tracer sums tr [lags][S], the collective block col [lags][S][S], count [lags].  com: velocities relative
+// to the frame's centre of mass.  After sgpr_md_begin (and _fix, _thermostat, _record, _msd, _rdf), before the first sgpr_md_run;
+// every = 0 detaches and frees.  The attach zeroes the tables.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one
+// rank, beside a mask, the frame record, sgpr_md_msd and sgpr_md_rdf (each keeps its own next_due); a barostat, a committee, a
+// relaxation, a band, a polymer, several ranks, the filter and a bias (there the closing kick uses a force other than the packed
+// one): SGPR_E_UNSUPPORTED, from here and from their attach functions.  Limits: lags <= VACF_MAXLAGS, the ring
+// (lags + 1) 24 N bytes <= VACF_MAXBYTES.
+extern "C" int sgpr_md_vacf(sgpr_model *h, int every, int lags, int origin_every, int com)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vacf: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_vacf: call sgpr_md_begin first");
+    if (every == 0) {   // (a detach gives the rings back: nothing of them is launched or read from here on)
+        m.run.vacf = MdRun::Vacf();
+        if (m.vacf.held()) {
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            m.vacf = MdState::VacfBufs();
+        }
+        return SGPR_OK;
+    }
+    if (every < 0 || lags < 1 || origin_every < 1 || (com != 0 && com != 1))
+        return fail(SGPR_E_INVALID, "sgpr_md_vacf: every >= 0, lags >= 1, origin_every >= 1, com = 0 or 1");
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_vacf: the run has started");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run was begun on %d ranks; velocity correlations are accumulated on one", m.run.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a barostat; velocities in a moving cell are not sampled");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a committee (sgpr_md_committee), whose loop does not sample velocities");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a relaxation; velocity correlations are accumulated over dynamics");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a nudged elastic band; velocity correlations are accumulated over dynamics");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a ring polymer (sgpr_md_pimd); its centroid is not sampled");
+    if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a filter (sgpr_md_filter): its closing kick uses the filtered force, not the packed one the sample takes");
+    if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a bias (sgpr_md_meta): its closing kick uses the biased force, not the packed one the sample takes");
+    const int N = m.run.N, S = h->S;
+    if (lags > VACF_MAXLAGS || (unsigned long long)(lags + 1) * 24ull * (unsigned long long)N > VACF_MAXBYTES)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: %d lags of %d atoms: at most %d lags and a ring of (lags + 1) 24 N = %llu bytes",
+                    lags, N, VACF_MAXLAGS, (unsigned long long)VACF_MAXBYTES);
+    // the chunks: runs of at most VACF_CHUNK consecutive sorted atoms of one species (the sort is by species in table order)
+    std::vector<int> nz(S, 0);
+    for (int i = 0, last = 0; i < N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
+        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_vacf: the run's atoms are not sorted by the model's species");
+        last = z; nz[z]++;
+    }
+    std::vector<int> tab, coff(S + 1, 0);
+    for (int z = 0, first = 0; z < S; first += nz[z], z++) {
+        for (int o = 0; o < nz[z]; o += VACF_CHUNK) { tab.push_back(first + o); tab.push_back(std::min(VACF_CHUNK, nz[z] - o)); }
+        coff[z + 1] = (int)tab.size() / 2;
+    }
+    const int nch = coff[S];
+    tab.insert(tab.end(), coff.begin(), coff.end());
+    tab.insert(tab.end(), nz.begin(), nz.end());
+    double mtot = 0.0;
+    for (int i = 0; i < N; i++) mtot += m.run.mass_sorted[i];
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t slots = (size_t)lags + 1;
+    // (ring slots are stored before they are read: only the tables and the control words start from zero)
+    if (m.vacf.ring.alloc(slots * 3 * N, false) || m.vacf.vpart.alloc(slots * nch * 6, false) || m.vacf.part.alloc((size_t)lags * nch, false) ||
+        m.vacf.jring.alloc(slots * S * 3, false) || m.vacf.cring.alloc(slots * 3, false) || m.vacf.tr.alloc((size_t)lags * S) ||
+        m.vacf.col.alloc((size_t)lags * S * S) || m.vacf.ctl.alloc((size_t)2 + lags) || m.vacf.tab.alloc(tab.size(), false))
+        return fail(SGPR_E_NODEVICE, "sgpr_md_vacf: device allocation failed");
+    HIPCHK(hipMemcpy(m.vacf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    MdRun::Vacf &a = m.run.vacf;
+    a.every = every; a.lags = lags; a.origin_every = origin_every; a.com = com; a.nch = nch; a.S = S; a.mtot = mtot;
+    return SGPR_OK;
+}
+
+// The tables as they stand (between two calls of a run; the stream is synchronised): tracer [lags][S], collective [lags][S][S],
+// counts [lags], info [3 + S] = samples correlated, pending (0 / 1: a stored sample waits for the next one), next_due (the
+// configuration the table waits for), and the atoms of every species in the frame.  Any pointer may be NULL.
+extern "C" int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collective, int64_t *counts, int64_t *info)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vacf_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.vacf.every) return fail(SGPR_E_INVALID, "sgpr_md_vacf_read: call sgpr_md_begin and sgpr_md_vacf first");
+    const MdRun::Vacf &a = m.run.vacf;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<long long> ctl((size_t)2 + a.lags);
+    HIPCHK(hipMemcpy(ctl.data(), m.vacf.ctl.p, sizeof(long long) * ctl.size(), hipMemcpyDeviceToHost));
+    if (tracer) HIPCHK(hipMemcpy(tracer, m.vacf.tr.p, sizeof(double) * (size_t)a.lags * a.S, hipMemcpyDeviceToHost));
+    if (collective) HIPCHK(hipMemcpy(collective, m.vacf.col.p, sizeof(double) * (size_t)a.lags * a.S * a.S, hipMemcpyDeviceToHost));
+    if (counts) for (int k = 0; k < a.lags; k++) counts[k] = ctl[2 + k];
+    if (info) {
+        std::vector<int> nz(a.S);
+        HIPCHK(hipMemcpy(nz.data(), m.vacf.tab.p + (size_t)2 * a.nch + a.S + 1, sizeof(int) * a.S, hipMemcpyDeviceToHost));
+        info[0] = ctl[1]; info[1] = ctl[0] > 0 ? 1 : 0; info[2] = ctl[0];
+        for (int z = 0; z < a.S; z++) info[3 + z] = nz[z];
+    }
+    return SGPR_OK;
+}
+
 // Deviates of the integrator on the device: seed != 0 makes sgpr_md_run (called with noise = NULL) draw the standard
 // normal deviate of (configuration index, atom, component) from a counter-based generator; 0 switches that off.
 extern "C" int sgpr_md_seed(sgpr_model *h, uint64_t seed)
@@ -2059,6 +2188,7 @@ extern "C" int sgpr_md_filter(sgpr_model *h, double shrink, const double *f0, co
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run is a ring polymer (sgpr_md_pimd), which integrates unfiltered forces");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run has a committee (sgpr_md_committee), which integrates unfiltered forces");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run was begun on %d ranks; the filter runs on one", m.run.world);
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_filter: the run accumulates velocity correlations (sgpr_md_vacf), whose closing kick uses the packed force; the filtered integrator kicks with another");
     HIPCHK(hipSetDevice(h->device));
     const int N = m.run.N;
     const size_t N3 = (size_t)3 * N;
@@ -2159,6 +2289,7 @@ extern "C" int sgpr_md_meta(sgpr_model *h, int ncomp, const int32_t *cvs, const 
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run is a ring polymer (sgpr_md_pimd), whose loop does not apply a bias; the host loop around calculate() serves it");
     if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run has a committee (sgpr_md_committee), whose loop does not apply a bias; the host loop around calculate() serves it");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run was begun on %d ranks; the bias runs on one, the host loop around calculate() serves sharded runs", m.run.world);
+    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_meta: the run accumulates velocity correlations (sgpr_md_vacf), whose closing kick uses the packed force; the biased integrator kicks with another");
     if (pace < 1 || capacity < 1 || capacity > (1 << 28) || nhills < 0 || nhills > capacity || (nhills > 0 && !hills_cv))
         return fail(SGPR_E_INVALID, "sgpr_md_meta: pace >= 1, 1 <= capacity <= 2^28, 0 <= nhills <= capacity");
     if (!(w == w) || kT < 0.0) return fail(SGPR_E_INVALID, "sgpr_md_meta: w a number, kT >= 0");
@@ -2407,6 +2538,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.rdf = MdState::RdfBufs();
+    }
+    if (m.vacf.held()) {   // (and the rings and the tables of the velocity correlations)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.vacf = MdState::VacfBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

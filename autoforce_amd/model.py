@@ -1184,6 +1184,39 @@ class SGPRModel:
         return dict(hist=hist, species=np.array([int(z) for z in self.species]), n=info[4:].copy(), samples=int(info[0]), next_due=int(info[1]),
                     every=every, bins=int(info[2]), rmin=float(geom[1]), rmax=float(geom[2]), volume=float(geom[0]))
 
+    def md_vacf(self, every, lags, origin_every=1, com=False):
+        """Accumulate velocity autocorrelations inside the loop (sgpr_md_vacf; md_vacf.inc has the scheme, workloads.VacfRing is
+        the host twin and the definition): configuration n with n % every == 0 is sample n / every, its velocity the one
+        md_state(results=True)["velocities"] shows; for every lag k < lags and origin o = s - k with o % origin_every == 0, per
+        species of the model's table, the tracer correlation mean_i (v_i(s) - c_s).(v_i(o) - c_o) and the collective block
+        e_a(s).e_b(o) of the species' currents (c: the velocity of the frame's centre of mass with com=True, else 0) are added
+        to a table.  A sample is stored behind its evaluation and correlated when the next one arrives: the last one of a run is
+        pending.  After md_begin, before the first md_run; every = 0 detaches.  md_vacf_table() reads the table.  Langevin,
+        velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, md_record, md_msd and md_rdf; a
+        barostat, a committee, a relaxation, a band, a polymer, several ranks, ml_filter= and md_meta (their closing kick uses
+        a force other than the packed one), more than 8192 lags or a ring (lags + 1) * 24 N over 4 GiB: NotImplementedError."""
+        try:
+            check(_lib.load().sgpr_md_vacf(self._h, int(every), int(lags), int(origin_every), 1 if com else 0))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        self._md["vacf"] = (int(every), int(lags)) if every else None
+
+    def md_vacf_table(self):
+        """The table of md_vacf as it stands (sgpr_md_vacf_read; between two md_run calls): dict(tracer [lags, S], collective
+        [lags, S, S] the sums over the pairs (s, o) of a lag, count [lags] their number, lags [lags] in configurations, species [S]
+        the model's table, n [S] its atoms in the frame, samples (correlated), pending (0 / 1), next_due)."""
+        if not self._md.get("vacf"):
+            raise RuntimeError("md_vacf_table: no accumulator on this run (md_vacf)")
+        every, L = self._md["vacf"]
+        S = len(self.species)
+        tr, col, cnt, info = np.zeros((L, S)), np.zeros((L, S, S)), np.zeros(L, dtype=np.int64), np.zeros(3 + S, dtype=np.int64)
+        check(_lib.load().sgpr_md_vacf_read(self._h, ptr(tr), ptr(col), ptr(cnt), ptr(info)))
+        return dict(tracer=tr, collective=col, count=cnt, lags=every * np.arange(L, dtype=np.int64),
+                    species=np.array([int(z) for z in self.species]), n=info[3:].copy(), samples=int(info[0]), pending=int(info[1]),
+                    next_due=int(info[2]))
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

@@ -4,7 +4,9 @@ the run itself accumulates — SGPRModel.md_msd on the device, workloads.MsdBloc
 species the table holds the sums of the tracer msd = mean_i |d_i|^2 and of the collective smd = |sum_i d_i|^2 / n over the
 level's windows, and of their squares; the windows of a level do not overlap, so their scatter gives an error bar.
   And the structure beside it: `Rdf` holds the pair-distance counts of SGPRModel.md_rdf / workloads.RdfCounts, and
-`radial_distribution` forms the g(r) per species pair of theforce/analysis/rdf.py's `rdf` from them."""
+`radial_distribution` forms the g(r) per species pair of theforce/analysis/rdf.py's `rdf` from them.
+  And the dynamics: `Vacf` holds the velocity correlations of SGPRModel.md_vacf / workloads.VacfRing; `green_kubo`, `onsager` and
+`vibrational_dos` read a diffusion constant, the species' current correlations and a density of states off them."""
 import numpy as np
 
 KEYS = ("msd", "msd_sq", "smd", "smd_sq")
@@ -137,3 +139,112 @@ def radial_distribution(rdf, shells=False):
         a, b = slot[za], slot[zb]
         g[(za, zb)] = rdf.hist[a, b].astype(float) / (rdf.samples * float(rdf.n[a]) * shell * (float(rdf.n[b]) / rdf.volume))
     return r, g
+
+
+class Vacf:
+    """Holder of a velocity-correlation table: ActiveCalculator.run_md(vacf=Vacf(every, lags, origin_every, com)) fills it, as
+    msd= fills an Msd; add(table) adds the table of a run (SGPRModel.md_vacf_table(), VacfRing.table()) — the tables of several
+    runs of one frame with the same settings add up, pair by pair.  mean() gives the curves per species; green_kubo, onsager and
+    vibrational_dos read them."""
+
+    def __init__(self, every, lags, origin_every=1, com=False):
+        self.every, self.nlags, self.origin_every, self.com = int(every), int(lags), int(origin_every), bool(com)
+        self.lags = self.every * np.arange(self.nlags, dtype=np.int64)   # in configurations
+        self.count = np.zeros(self.nlags, dtype=np.int64)
+        self.samples = 0
+        self.tracer = self.collective = self.species = self.n = None
+
+    def add(self, table):
+        if not np.array_equal(np.asarray(table["lags"]), self.lags):
+            raise ValueError("Vacf.add: the table was taken with other settings (every, lags)")
+        species, n = np.asarray(table["species"]), np.asarray(table["n"])
+        if self.species is None:
+            self.species, self.n = species.copy(), n.copy()
+            self.tracer, self.collective = np.zeros((self.nlags, len(species))), np.zeros((self.nlags, len(species), len(species)))
+        elif not (np.array_equal(species, self.species) and np.array_equal(n, self.n)):
+            raise ValueError("Vacf.add: the table is of another frame (species, atoms per species)")
+        self.count = self.count + np.asarray(table["count"], dtype=np.int64)
+        self.tracer = self.tracer + np.asarray(table["tracer"], float)
+        self.collective = self.collective + np.asarray(table["collective"], float)
+        self.samples += int(table["samples"])
+        return self
+
+    def table(self):
+        return dict(tracer=self.tracer.copy(), collective=self.collective.copy(), count=self.count.copy(), lags=self.lags.copy(),
+                    species=self.species, n=self.n, samples=self.samples)
+
+    def mean(self):
+        """dict(tracer [lags, S], collective [lags, S, S]): the means over a lag's pairs of samples (nan where a lag has none)."""
+        if self.tracer is None:
+            raise ValueError("Vacf.mean: the holder has no table")
+        c = np.where(self.count > 0, self.count, 1).astype(float)
+        ok = self.count > 0
+        return dict(tracer=np.where(ok[:, None], self.tracer / c[:, None], np.nan),
+                    collective=np.where(ok[:, None, None], self.collective / c[:, None, None], np.nan))
+
+
+ASE_FS = 0.09822694788464063   # one femtosecond in the time unit of the velocities, A sqrt(amu / eV) (workloads.FS, ase.units.fs)
+
+
+def _running_integral(y, dt):
+    """Trapezoid rule along axis 0 from the first point: [0, (y0 + y1) dt / 2, ...]."""
+    out = np.zeros_like(y)
+    out[1:] = np.cumsum(0.5 * (y[1:] + y[:-1]), axis=0) * dt
+    return out
+
+
+def green_kubo(vacf, dt_fs, at_fs=None):
+    """{Z: dict(t [lags] fs, D [lags], value)} per species of the holder `vacf` present in the frame: the running Green-Kubo
+    integral D_z(t) = (1/3) int_0^t C_z of the tracer curve C_z(k) = mean (v_i(s) - c_s).(v_i(s - k) - c) by the trapezoid rule,
+    in Angstrom^2 / fs like transport.diffusion_constants (velocities are in Angstrom per ASE time unit), and its value at the
+    lag nearest to at_fs (None: the last lag).  Lags without a pair of samples end the curve."""
+    C = vacf.mean()["tracer"]
+    t = vacf.lags * float(dt_fs)
+    use = int(np.argmin(vacf.count > 0)) if not np.all(vacf.count > 0) else len(t)
+    if use < 1:
+        raise ValueError("green_kubo: the holder has no samples")
+    step = vacf.every * float(dt_fs) * ASE_FS ** 2
+    k = use - 1 if at_fs is None else int(np.argmin(np.abs(t[:use] - float(at_fs))))
+    out = {}
+    for q, z in enumerate(vacf.species):
+        if vacf.n[q] == 0:
+            continue
+        D = _running_integral(C[:use, q], step) / 3.0
+        out[int(z)] = dict(t=t[:use].copy(), D=D, value=float(D[k]))
+    return out
+
+
+def onsager(vacf, dt_fs):
+    """(t [lags] fs, L [lags, S, S]): the running integrals L_ab(t) = (1 / 3N) int_0^t e_a(s).e_b(s - k) of the collective block
+    (e_z: the species' current sum_z (v_i - c); N: the atoms of the frame), trapezoid rule, Angstrom^2 / fs — the Onsager
+    coefficients behind an ionic conductivity; L_aa of a single tracer species is its Green-Kubo D."""
+    col = vacf.mean()["collective"]
+    use = int(np.argmin(vacf.count > 0)) if not np.all(vacf.count > 0) else len(vacf.lags)
+    if use < 1:
+        raise ValueError("onsager: the holder has no samples")
+    step = vacf.every * float(dt_fs) * ASE_FS ** 2
+    return vacf.lags[:use] * float(dt_fs), _running_integral(col[:use], step) / (3.0 * float(np.sum(vacf.n)))
+
+
+def vibrational_dos(vacf, dt_fs, window="hann"):
+    """(f [lags] THz, {Z: g [lags]}): the cosine transform of the normalised tracer curve C_z(k) / C_z(0),
+        g(f_j) = sum_k a_k w_k C_z(k) / C_z(0) cos(2 pi f_j t_k),   f_j = j / (2 L every dt),   a_0 = 1/2, else 1,
+    with w the falling half of a Hann window (window="hann") or 1 (None): the vibrational density of states up to a factor."""
+    C = vacf.mean()["tracer"]
+    L = int(np.argmin(vacf.count > 0)) if not np.all(vacf.count > 0) else vacf.nlags
+    if L < 2:
+        raise ValueError("vibrational_dos: fewer than two lags with samples")
+    if window not in ("hann", None):
+        raise ValueError("vibrational_dos: window = 'hann' or None")
+    k = np.arange(L)
+    w = 0.5 * (1.0 + np.cos(np.pi * k / L)) if window == "hann" else np.ones(L)
+    w[0] *= 0.5
+    step_fs = vacf.every * float(dt_fs)
+    f = k / (2.0 * L * step_fs) * 1e3   # 1 / fs = 1000 THz
+    kern = np.cos(np.pi * np.outer(k, k) / L)   # [j, k]: 2 pi f_j t_k
+    out = {}
+    for q, z in enumerate(vacf.species):
+        if vacf.n[q] == 0 or not C[0, q] > 0.0:
+            continue
+        out[int(z)] = kern @ (w * C[:L, q] / C[0, q])
+    return f, out

@@ -1818,6 +1818,142 @@ class MsdBlocks:
                     species=np.array(self.species), n=self.nz.copy(), samples=-(-self.n // self.every), next_due=-(-self.n // self.every) * self.every)
 
 
+VACF_CHUNK = 256   # sorted atoms of one species per workgroup of md_vacf_store_kernel and md_vacf_corr_kernel (md_vacf.inc)
+
+
+def observer_velocities(v_pre, F, mass, hdt, pending, fixed=None):
+    """The velocities an observer of the trajectory sees at a configuration — what sgpr_md_velocities returns, operation for
+    operation: v_pre + hdt * F / m where the closing half kick is due (pending: every configuration of a Langevin / velocity
+    Verlet run but the first), v_pre as it is otherwise (pending = 0: configuration 0, and Nose-Hoover, whose v_pre is the
+    centred velocity already); a held component (fixed [N, 3] bool) exactly 0.  [N, 3], caller atom order."""
+    v = np.array(v_pre, float).reshape(-1, 3)
+    if pending:
+        v = v + float(hdt) * np.asarray(F, float).reshape(-1, 3) / np.asarray(mass, float)[:, None]
+    if fixed is not None:
+        v[np.asarray(fixed, bool).reshape(-1, 3)] = 0.0
+    return v
+
+
+class VacfRing:
+    """Velocity autocorrelations over a ring of stored samples — the host twin of the accumulator inside the device loop
+    (SGPRModel.md_vacf, md_vacf.inc) and its definition: the same operations in the same order, so the two tables agree bit for
+    bit.  The reference has no velocity autocorrelation; the definition is ours.
+      add(v) is fed the observer's velocities (observer_velocities) of the configurations 0, 1, 2, ... of a run ([N, 3], caller
+    atom order).  Configuration n with n % every == 0 is sample s = n / every.  For every sample s, lag k < lags and origin
+    o = s - k with o >= 0 and o % origin_every == 0, per species z of `species` (the model's table, n_z atoms in the frame; one
+    absent from the frame keeps zeros), J_z(s) = sum_z v_i(s) and c_s = sum_all m_i v_i(s) / sum_all m_i (com; else 0):
+        A            = sum_z ((v_i0(s) v_i0(o) + v_i1(s) v_i1(o)) + v_i2(s) v_i2(o))
+        tr[k, z]    += ((A - (c_s.J_z(o) + c_o.J_z(s))) + n_z (c_s.c_o)) / n_z     (mean over z of (v_i(s) - c_s).(v_i(o) - c_o))
+        col[k, a, b] += e_a(s).e_b(o),  e_z = J_z - n_z c
+        count[k]    += 1
+      A sample is taken in two parts, as the device must take it (a configuration behind a covloss halt is evaluated again, with
+    other forces): add(v) STORES sample s in slot s % (lags + 1) of a ring — v and the chunk parts of J and sum m v — and
+    CORRELATES sample s - 1, which is final: its J and c go into their own rings, its due lags are accumulated.  Sample 0 only
+    stores; the last sample fed stays pending.
+      Order: atoms sorted by species (stable), a species cut into chunks of VACF_CHUNK atoms; per chunk the block sums in the
+    workgroup's order (_block_order_sums, one atom per thread); the chunks of a species ascending; sum m v over the species in
+    table order; the total mass atom by atom in sorted order; dot products (a0 b0 + a1 b1) + a2 b2."""
+
+    def __init__(self, every, lags, origin_every, com, masses, numbers, species):
+        if every < 1 or lags < 1 or origin_every < 1:
+            raise ValueError("VacfRing: every >= 1, lags >= 1, origin_every >= 1")
+        self.every, self.lags, self.origin_every, self.com = int(every), int(lags), int(origin_every), bool(com)
+        numbers = np.asarray(numbers)
+        self.species = [int(z) for z in species]
+        zi = np.array([self.species.index(int(z)) for z in numbers])
+        self.perm = np.argsort(zi, kind="stable")
+        self.nz = np.array([int(np.sum(zi == z)) for z in range(len(self.species))])
+        self.mass = np.asarray(masses, float)[self.perm]
+        self.mtot = 0.0
+        for v in self.mass:
+            self.mtot = self.mtot + float(v)
+        self.chunks, first = [], 0   # (species, first atom, atoms)
+        for z, nz in enumerate(self.nz):
+            self.chunks += [(z, first + o, min(VACF_CHUNK, nz - o)) for o in range(0, nz, VACF_CHUNK)]
+            first += nz
+        S, self.slots = len(self.species), self.lags + 1
+        self.ring = [None] * self.slots                    # v [N, 3] sorted
+        self.vpart = [None] * self.slots                   # [chunks, 6]
+        self.J = np.zeros((self.slots, S, 3))
+        self.c = np.zeros((self.slots, 3))
+        self.tr = np.zeros((self.lags, S))
+        self.col = np.zeros((self.lags, S, S))
+        self.count = np.zeros(self.lags, dtype=np.int64)
+        self.samples = 0   # correlated
+        self.n = 0         # configurations seen
+
+    def _chunk_sums(self, terms):
+        """terms [N, q] per sorted atom -> [chunks, q] in the workgroup's order."""
+        pad = np.zeros((len(self.chunks), terms.shape[1], VACF_CHUNK))
+        for c, (_, a, k) in enumerate(self.chunks):
+            pad[c, :, :k] = terms[a:a + k].T
+        return _block_order_sums(pad)
+
+    def _species_sums(self, part):
+        sums = np.zeros((len(self.species), part.shape[1]))
+        for c, (z, _, _) in enumerate(self.chunks):
+            sums[z] = sums[z] + part[c]
+        return sums
+
+    @staticmethod
+    def _dot(a, b):
+        return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+    def _store(self, s, v):
+        q = s % self.slots
+        self.ring[q] = v
+        self.vpart[q] = self._chunk_sums(np.concatenate([v, self.mass[:, None] * v], axis=1))
+
+    def _correlate(self, p):
+        S, qp = len(self.species), p % self.slots
+        sums = self._species_sums(self.vpart[qp])
+        cp = np.zeros(3)
+        if self.com:
+            for z in range(S):
+                cp = cp + sums[z, 3:6]
+            cp = cp / self.mtot
+        self.J[qp], self.c[qp] = sums[:, :3], cp
+        vp, Jp = self.ring[qp], self.J[qp]
+        fn = self.nz.astype(float)
+        ep = Jp - fn[:, None] * cp[None]
+        for k in range(self.lags):
+            o = p - k
+            if o < 0:
+                break
+            if o % self.origin_every:
+                continue
+            qo = o % self.slots
+            vo, Jo, co = self.ring[qo], self.J[qo], self.c[qo]
+            A = self._species_sums(self._chunk_sums(((vp[:, 0] * vo[:, 0] + vp[:, 1] * vo[:, 1]) + vp[:, 2] * vo[:, 2])[:, None]))[:, 0]
+            eo = Jo - fn[:, None] * co[None]
+            cc = self._dot(cp, co)
+            for a in range(S):
+                for b in range(S):
+                    self.col[k, a, b] = self.col[k, a, b] + self._dot(ep[a], eo[b])
+                if self.nz[a] > 0:
+                    self.tr[k, a] = self.tr[k, a] + ((A[a] - (self._dot(cp, Jo[a]) + self._dot(co, Jp[a]))) + fn[a] * cc) / fn[a]
+            self.count[k] += 1
+        self.samples += 1
+
+    def add(self, velocities):
+        """The observer's velocities of the next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        s = n // self.every
+        self._store(s, np.array(velocities, float).reshape(-1, 3)[self.perm])
+        if s > 0:
+            self._correlate(s - 1)
+
+    def table(self):
+        """What SGPRModel.md_vacf_table returns."""
+        due = -(-self.n // self.every)
+        return dict(tracer=self.tr.copy(), collective=self.col.copy(), count=self.count.copy(),
+                    lags=self.every * np.arange(self.lags, dtype=np.int64), species=np.array(self.species), n=self.nz.copy(),
+                    samples=self.samples, pending=1 if due > 0 else 0, next_due=due * self.every)
+
+
 RDF_MAXR = 2      # images |s_k| <= 2 around a pair's nearest one: at most 125 shifts (md_rdf.inc)
 RDF_MAXBINS = 2048
 

@@ -609,6 +609,34 @@ int sgpr_md_msd_read(sgpr_model *h, double *table, int64_t *counts, int64_t *inf
  * The handle stays usable after every error above. */
 int sgpr_md_rdf(sgpr_model *h, int every, double rmin, double rmax, int bins);
 int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, double *geom);
+/* Velocity autocorrelations accumulated inside the loop.  The reference has none (theforce/analysis correlates displacements
+ * only): the definition is this library's, workloads.VacfRing is its host twin, and the device equals the twin bit for bit.
+ * Sample s is configuration n = s every; its velocity v(s) is the one sgpr_md_velocities returns had the call ended with that
+ * evaluation (Langevin / velocity Verlet: v_pre + (dt/2) F / m with the evaluation's packed force, v_pre at n = 0; Nose-Hoover:
+ * the centred velocity; a held component exactly 0).  For every sample s, lag k < lags and origin o = s - k >= 0 with
+ * o mod origin_every == 0, per species z of the model's table (n_z atoms), J_z = sum_z v_i, c = sum m_i v_i / sum m_i (com = 1;
+ * else 0):
+ *     tracer[k][z]        += mean over z of (v_i(s) - c_s).(v_i(o) - c_o)
+ *     collective[k][a][b] += e_a(s).e_b(o),  e_z = J_z - n_z c         (not symmetric at k > 0: the full block is kept)
+ *     counts[k]           += 1
+ * Fixed summation order, no float atomics.  v(s) depends on the forces, and a configuration behind a covloss halt is evaluated
+ * again with the updated model: a sample is STORED behind every evaluation of its configuration (the repeat overwrites it) and
+ * CORRELATED once, when the next sample arrives — so the last stored sample of a run is pending, and counts once the run goes on.
+ *
+ * sgpr_md_vacf       every >= 1, lags >= 1, origin_every >= 1, com 0 / 1: after sgpr_md_begin (and sgpr_md_fix, _thermostat,
+ *                    _record, _msd, _rdf, if used), before the first sgpr_md_run; zeroes the tables.  every = 0 detaches and
+ *                    frees: the run launches what it launched before.  Four small launches behind a sampled evaluation; device
+ *                    memory: a ring of (lags + 1) x 24 N bytes.  SGPR_E_INVALID: no run begun, a run that has started, values out
+ *                    of range.  SGPR_E_UNSUPPORTED: more than 8192 lags or a ring over 4 GiB; several ranks, a barostat, a
+ *                    committee, a relaxation, a band, a polymer; the filter and a bias (their closing kick uses a force other than
+ *                    the packed one) — and from sgpr_md_barostat, _committee, _relax, _neb, _pimd, _filter and _meta on a run that
+ *                    has the accumulator.
+ * sgpr_md_vacf_read  between two calls of the run (synchronises the stream): tracer[lags][S], collective[lags][S][S] (S: the
+ *                    model's species), counts[lags], info[3 + S] = samples correlated, pending (0 / 1), the configuration the
+ *                    table waits for next, the atoms of every species in the frame.  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_vacf(sgpr_model *h, int every, int lags, int origin_every, int com);
+int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collective, int64_t *counts, int64_t *info);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
