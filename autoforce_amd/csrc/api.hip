@@ -1783,8 +1783,8 @@ extern "C" void sgpr_destroy(sgpr_model *h)
                 for (int i = 0; i < h->cnt; i++) {
                     const size_t gi = (size_t)h->rank + (size_t)i * h->world;
                     const long long *fw = st.data() + (size_t)i * 8, *rv = st.data() + ((size_t)N + i) * 8;
-                    fprintf(f, "%d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", i, gi < nnh.size() ? nnh[gi] : -1, fw[0], fw[1], fw[2],
-                            fw[3], fw[4], fw[5], rv[0], rv[1], rv[2]);
+                    fprintf(f, "%d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", i, gi < nnh.size() ? nnh[gi] : -1, fw[0], fw[1], fw[2],
+                            fw[3], fw[4], fw[5], rv[0], rv[1], rv[2], rv[3] /* head of the pair phase: slot and units of tile 0 resolved */);
                 }
                 fclose(f);
             }

@@ -296,6 +296,51 @@ __device__ __forceinline__ double inv_unit_of(const DescArgs &a, int s)
     return u;
 }
 
+// The same lookups as selects among VALUES held in scalar registers.  unit_of over the kernel arguments compiles to a select
+// of the table OFFSET and a vector load from the kernarg segment behind it — a memory round trip, with its wait, in front of
+// the first arithmetic of every tile of the reverse pass.  Up to four slots the table is read once, outside the tile loop,
+// each entry behind an opaque scalar copy so that the select cannot be folded back into an address; more slots keep the
+// lookup above.  (The forward kernel keeps unit_of: with this form it measured slower)
+__device__ __forceinline__ double scalar_copy(double v)
+{
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+template <int ST>
+struct UnitRegs {
+    static constexpr bool REGS = ST <= 4;
+    double u0, u1, u2, u3, i0, i1, i2, i3;   // (named members, no array: nothing here may end up indexed in memory)
+    __device__ __forceinline__ explicit UnitRegs(const DescArgs &a)
+    {
+        u0 = u1 = u2 = u3 = i0 = i1 = i2 = i3 = 0.0;
+        if constexpr (REGS) {
+            u0 = scalar_copy(a.radii_v[0]); i0 = scalar_copy(a.radii_iv[0]);
+            if constexpr (ST > 1) { u1 = scalar_copy(a.radii_v[1]); i1 = scalar_copy(a.radii_iv[1]); }
+            if constexpr (ST > 2) { u2 = scalar_copy(a.radii_v[2]); i2 = scalar_copy(a.radii_iv[2]); }
+            if constexpr (ST > 3) { u3 = scalar_copy(a.radii_v[3]); i3 = scalar_copy(a.radii_iv[3]); }
+        }
+    }
+    static __device__ __forceinline__ double pick(int s, double v0, double v1, double v2, double v3)
+    {
+        double r = v0;
+        if constexpr (ST > 1) r = (s == 1) ? v1 : r;
+        if constexpr (ST > 2) r = (s == 2) ? v2 : r;
+        if constexpr (ST > 3) r = (s == 3) ? v3 : r;
+        return r;
+    }
+    __device__ __forceinline__ double unit(const DescArgs &a, int s) const
+    {
+        if constexpr (REGS) return pick(s, u0, u1, u2, u3);
+        else return unit_of<ST>(a, s);
+    }
+    __device__ __forceinline__ double inv_unit(const DescArgs &a, int s) const
+    {
+        if constexpr (REGS) return pick(s, i0, i1, i2, i3);
+        else return inv_unit_of<ST>(a, s);
+    }
+};
+
 // Species slots in use.  The default instantiations (lmax = nmax = 3, up to four slots) are dispatched one per species
 // count (DISPATCH_LNS: st_of(S) = S), so there the count is a COMPILE-TIME constant: the loops over species and channels
 // unroll and the `v < channels` guards fold away — they were scalar branches around single LDS reads (a third of the
@@ -1424,6 +1469,7 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
         PHASE_STAMP(1);
         // ---------------------------------------------------------------- phase B: pair terms
         const double ang = a.shear[ia] ? SGPR_TINY_ANGLE : 0.0;
+        const UnitRegs<ST> units(a);  // the length units in scalar registers, read once for all tiles
         double *stage = R;  // [CH] rows at RD::at: one staged row set (hY, then gY); earlier in a tile: [CH][FS] radial rows
         // training rows: an atom of another species than the column's has k(i,q) = 0 identically: no pair terms, and
         // nothing to hand over — the finalize of a rows batch only adds the hand-overs of neighbours of the column's
@@ -1470,8 +1516,15 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
                 }
                 continue;
             }
-            const double u = unit_of<ST>(a, s);
-            const double iu = inv_unit_of<ST>(a, s);
+            const double u = units.unit(a, s);
+            const double iu = units.inv_unit(a, s);
+#ifdef SGPR_PHASE_STAMPS
+            // head of the pair phase: tile 0's hand-over slot and units are resolved (every lane's: the stamp waits on them)
+            if (t0 == 0) {
+                const unsigned long long head = __ballot(rvp >= 0 && u * iu > 0.0);   // (never empty: lane 0 has a pair)
+                if (a.stamps && lane == 0 && head != 0ull) a.stamps[(size_t)ia * 8 + 3] = (long long)__builtin_amdgcn_s_memtime();
+            }
+#endif
             const double x = r[0] * iu, y = r[1] * iu, z = r[2] * iu;
             const double d = sqrt(x * x + y * y + z * z);
             const double id = 1.0 / d;
@@ -1561,7 +1614,7 @@ __global__ __launch_bounds__(256, 4) void desc_rev_kernel(DescArgs a, GemmArgs g
             // kernel has no registers to spare, tests/test_kernel_resources_cpu.py.)
             int s_again = s;
             asm volatile("" : "+v"(s_again));
-            const double u_e = unit_of<ST>(a, s_again), iu_e = inv_unit_of<ST>(a, s_again);
+            const double u_e = units.unit(a, s_again), iu_e = units.inv_unit(a, s_again);
             double gr[3];
             gr[0] = (gxs + rad * x) * iu_e;
             gr[1] = (gys + ang * gzs + rad * y) * iu_e;

@@ -4,7 +4,8 @@
 returns, and splits the per-wave phase stamps of the LAST step's nl_fwd / desc_rev by list length.
 Needs the -DSGPR_PHASE_STAMPS build (tools/build_stamps.sh):
   SGPR_HIP_LIB=$PWD/autoforce_amd/libsgpr_hip_stamps.so python3 tools/stamps_tiles.py [extra_steps] [out.json] [raw.npy]
-(out.json: the figures printed; raw.npy: the per-wave records — atom, list length, forward stamps 0-5, reverse stamps 0-2)."""
+(out.json: the figures printed; raw.npy: the per-wave records — atom, list length, forward stamps 0-5, reverse stamps 0-3; reverse stamp 3 is the head of the pair phase, reported as desc_rev_pairs_head =
+cycles from stamp 1 to it)."""
 import json
 import os
 import sys
@@ -40,9 +41,12 @@ out = {"steps": 221 + extra, "rebuilds": r1 - r0, "last_step_rebuilt": bool(last
        "mean_neighbors": float(nn.mean()), "max_neighbors": int(nn.max()),
        "atoms_over_48": int((nn > 48).sum()), "atoms_over_64": int((nn > 64).sum())}
 mdl.close()   # writes the per-wave records
-rec = np.loadtxt(dump)   # ia, nn, forward stamps 0..5, reverse stamps 0..2
+rec = np.loadtxt(dump)   # ia, nn, forward stamps 0..5, reverse stamps 0..3
 ia, wn = rec[:, 0].astype(int), rec[:, 1].astype(int)
-fw, rv = rec[:, 2:8], rec[:, 8:11]
+fw, rv = rec[:, 2:8], rec[:, 8:12]
+# reverse stamp 3, the head of the pair phase: tile 0's hand-over slot and length units are resolved (a wave without pair
+# terms writes none)
+headed = rv[:, 3] > rv[:, 1]
 quad_two = np.zeros(len(ia), bool)
 for q in range(0, len(ia), 4):
     quad_two[q:q + 4] = (wn[q:q + 4] > 48).any()
@@ -56,6 +60,8 @@ for name, two in (("one_tile", wn <= 48), ("two_tile", wn > 48)):
         k["nl_fwd_wave_total"] = float((fw[two, 5] - fw[two, 0]).mean())
         k["desc_rev_phase_a"] = float((rv[two, 1] - rv[two, 0]).mean())
         k["desc_rev_pairs"] = float((rv[two, 2] - rv[two, 1]).mean())
+        if (two & headed).any():
+            k["desc_rev_pairs_head"] = float((rv[two & headed, 3] - rv[two & headed, 1]).mean())
         k["desc_rev_wave_total"] = float((rv[two, 2] - rv[two, 0]).mean())
     out[name + "_cycles"] = k
 # s_memtime counts per CU (the 16 waves of a CU share a counter; the counters of different CUs are up to 1e12 apart, a
