@@ -98,6 +98,9 @@ SIGNATURES = {
     "sgpr_md_rdf_read": (C.c_int, [_vp, _vp, _vp, _vp]),
     "sgpr_md_vacf": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sgpr_md_vacf_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "sgpr_md_vanhove": (C.c_int, [_vp, C.c_int, C.c_int, _dbl, C.c_int, C.c_int, C.c_int, _dbl, C.c_int]),
+    "sgpr_md_vanhove_edges": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "sgpr_md_vanhove_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgpr_md_committee": (C.c_int, [_vp, C.c_int, _vp]),
     "sgpr_md_committee_info": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_md_filter": (C.c_int, [_vp, _dbl, _vp, _vp]),

@@ -289,6 +289,15 @@ struct MdRun {
     // the velocity autocorrelations (sgpr_md_vacf, md_vacf.inc): every `every`-th configuration is a sample, `lags` lags of one
     // sample each, origins every `origin_every`-th sample; nch chunks of one species each, S species, the frame's total mass
     struct Vacf { int every = 0, lags = 0, origin_every = 1, com = 0, nch = 0, S = 0; double mtot = 0.0; } vacf;
+    // the van Hove functions (sgpr_md_vanhove, md_vanhove.inc): md_msd's samples and levels; the self part over rbins x tbins x
+    // pbins bins up to rmax, nch chunks of one species each; the distinct part (dbins > 0) over npairs ORDERED tile pairs, tile J
+    // cut into `split` parts, in the constant cell g (rmin = 0, rmax = dmax, bins = dbins) with its image block; the cell's volume
+    struct VanHove {
+        int every = 0, levels = 0, rbins = 0, tbins = 0, pbins = 0, dbins = 0, nch = 0, npairs = 0, split = 1, S = 0;
+        bool images = false;
+        RdfGeom g = {};
+        double rmax = 0.0, dmax = 0.0, volume = 0.0;
+    } vh;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -382,6 +391,13 @@ struct MdState {
         DevBuf<int> tab;                      // [nch][2] the chunks | [S + 1] a species' chunks | [S] its atoms
         bool held() const { return ctl.p != nullptr; }
     } vacf;
+    struct VanHoveBufs {
+        DevBuf<double> origin, edges;             // [L][N][3] sorted order, ct [tbins] | cu [pbins] | su [pbins]
+        DevBuf<unsigned long long> hs, over, hd;  // [L][S][rbins][tbins][pbins], [L][S], [L][S][S][dbins]
+        DevBuf<long long> ctl;                    // next_due | samples | count[L]
+        DevBuf<int> tab;                          // [nch][VH_CHUNK] the chunks | [npairs][RDF_PAIR] the ordered tile pairs | [S] a species' atoms
+        bool held() const { return ctl.p != nullptr; }
+    } vh;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1308,6 +1324,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_msd.inc"
 #include "md_rdf.inc"
 #include "md_vacf.inc"
+#include "md_vanhove.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next

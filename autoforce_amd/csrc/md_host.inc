@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _vanhove (displacement and pair histograms per lag), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_vanhove.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -191,6 +191,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates displacements (sgpr_md_msd), which are defined at constant cell");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates pair distances (sgpr_md_rdf), whose image block and densities are those of a constant cell");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates velocity correlations (sgpr_md_vacf), which are not sampled in a moving cell");
+    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates van Hove functions (sgpr_md_vanhove), which are defined at constant cell");
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -387,6 +388,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
+    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -787,6 +789,32 @@ static void md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st)
     hipLaunchKernelGGL(md_vacf_done_kernel, dim3(1), dim3(64), 0, st, m.vacf.ctl.p, n, a.every, s > 0 ? 1 : 0, halt, step);
 }
 
+// The same for the van Hove functions (md_vanhove.inc): md_msd's due levels; the pair sweep of the distinct part — one grid layer
+// per due level, origins against the X slot of n — BEFORE the self part, which measures the displacements and overwrites the
+// origins; the launch that counts.  Sample 0 only sets origins.
+static void md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::VanHove &a = m.run.vh;
+    const long long n = m.run.t + j, s = n / a.every;
+    unsigned due = 0;
+    int ndue = 0;
+    for (int l = 0; l < a.levels && (s & ((1ll << l) - 1)) == 0; l++) { due |= 1u << l; ndue++; }
+    const int acc = s > 0 ? 1 : 0, N = m.run.N;
+    const size_t N3 = (size_t)3 * N;
+    const double *x = m.X.p + N3 * (size_t)(n % m.run.ring);
+    const int *chunk = m.vh.tab.p, *pair = chunk + VH_CHUNK * a.nch, *halt = m.halt.p;
+    if (a.dbins && a.npairs && acc)
+        hipLaunchKernelGGL(a.images ? md_vh_pair_kernel<true> : md_vh_pair_kernel<false>, dim3(a.npairs, a.split, ndue), dim3(256), 0, st, pair,
+                           (const double *)m.vh.origin.p, N3, x, a.g, due, m.vh.hd.p, (size_t)a.S * a.S * a.dbins, (const long long *)m.vh.ctl.p, n,
+                           halt, step);
+    if (a.nch)
+        hipLaunchKernelGGL(md_vh_self_kernel, dim3(a.nch), dim3(256), 0, st, chunk, x, m.vh.origin.p, N3, (const double *)m.vh.edges.p, a.rmax,
+                           a.rbins, a.tbins, a.pbins, a.S, due, acc, m.vh.hs.p, (size_t)a.rbins * a.tbins * a.pbins, m.vh.over.p,
+                           (const long long *)m.vh.ctl.p, n, halt, step);
+    hipLaunchKernelGGL(md_vh_done_kernel, dim3(1), dim3(64), 0, st, m.vh.ctl.p, n, a.every, due, acc, halt, step);
+}
+
 // Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
 // one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
 // again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
@@ -954,6 +982,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates displacements (sgpr_md_msd), which the committee's loop does not sample");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates pair distances (sgpr_md_rdf), which the committee's loop does not sample");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates velocity correlations (sgpr_md_vacf), which the committee's loop does not sample");
+    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates van Hove functions (sgpr_md_vanhove), which the committee's loop does not sample");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1323,6 +1352,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
+    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1450,6 +1480,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates displacements (sgpr_md_msd); a polymer's centroid is not sampled");
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates pair distances (sgpr_md_rdf); a polymer's beads are not sampled");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates velocity correlations (sgpr_md_vacf); a polymer's centroid is not sampled");
+    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates van Hove functions (sgpr_md_vanhove); a polymer's beads are not sampled");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1657,6 +1688,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         if (m.run.msd.every && (m.run.t + j) % m.run.msd.every == 0) md_msd_sample(h, j, (int)(step0 + j), st);
         if (m.run.rdf.every && (m.run.t + j) % m.run.rdf.every == 0) md_rdf_sample(h, j, (int)(step0 + j), st);
         if (m.run.vacf.every && (m.run.t + j) % m.run.vacf.every == 0) md_vacf_sample(h, j, (int)(step0 + j), st);
+        if (m.run.vh.every && (m.run.t + j) % m.run.vh.every == 0) md_vh_sample(h, j, (int)(step0 + j), st);
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -2139,6 +2171,158 @@ extern "C" int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collecti
     return SGPR_OK;
 }
 
+// Van Hove functions of the run (md_vanhove.inc has the definition; workloads.VanHoveCounts is the host twin): every >= 1 —
+// configuration n with n % every == 0 is sample n / every, levels and origins as sgpr_md_msd's; behind a sampled evaluation at
+// most three launches add, per due level, every atom's displacement to a histogram over (r < rmax, theta, phi) per species of
+// the model's table (rbins x tbins x pbins; beyond rmax: `over`) and, with dbins > 0, every distance r < dmax between an origin
+// and a present position, periodic images included, to dbins bins per ORDERED pair of species.  All entries are integers.
+// After sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record, _msd, _rdf, _vacf), before the first sgpr_md_run; every =
+// 0 detaches and frees.  The attach zeroes the tables and sets the angular edges with cos and sin of this library;
+// sgpr_md_vanhove_edges replaces them by the caller's doubles.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one
+// rank, beside a mask, the filter, a bias, the frame record and the other accumulators (each keeps its own next_due); a
+// barostat, a committee, a relaxation, a band, a polymer and several ranks: SGPR_E_UNSUPPORTED, from here and from their attach
+// functions.
+extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax, int rbins, int tbins, int pbins, double dmax, int dbins)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: call sgpr_md_begin first");
+    if (every == 0) {   // (a detach gives the origins and the tables back: nothing of them is launched or read from here on)
+        m.run.vh = MdRun::VanHove();
+        if (m.vh.held()) {
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            m.vh = MdState::VanHoveBufs();
+        }
+        return SGPR_OK;
+    }
+    if (every < 0 || levels < 1 || levels > MSD_MAXL) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: every >= 0, 1 <= levels <= %d", MSD_MAXL);
+    if (rbins < 1 || rbins > VH_MAXRBINS || !(rmax > 0.0) || !(rmax < 1e300))
+        return fail(SGPR_E_INVALID, "sgpr_md_vanhove: rmax > 0, 1 <= rbins <= %d (rbins = %d)", VH_MAXRBINS, rbins);
+    if (tbins < 1 || tbins > VH_MAXABINS || pbins < 1 || pbins > VH_MAXABINS)
+        return fail(SGPR_E_INVALID, "sgpr_md_vanhove: 1 <= tbins, pbins <= %d (tbins = %d, pbins = %d)", VH_MAXABINS, tbins, pbins);
+    if (dbins < 0 || dbins > RDF_MAXBINS || (dbins > 0 && (!(dmax > 0.0) || !(dmax < 1e300))))
+        return fail(SGPR_E_INVALID, "sgpr_md_vanhove: 0 <= dbins <= %d (dbins = %d), dmax > 0 with dbins > 0", RDF_MAXBINS, dbins);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: the run has started");
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run was begun on %d ranks; van Hove functions are accumulated on one", m.run.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run has a barostat; displacements and the image block are those of a constant cell");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run has a committee (sgpr_md_committee), whose loop does not sample displacements");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a relaxation; van Hove functions are accumulated over dynamics");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a nudged elastic band; van Hove functions are accumulated over dynamics");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
+    const int N = m.run.N, S = h->S;
+    const size_t zstride = (size_t)rbins * tbins * pbins;
+    if ((unsigned long long)levels * S * zstride * 8ull > (1ull << 30))
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: a self table of %d levels x %d species x %d x %d x %d bins is %llu bytes; at most 1 GiB",
+                    levels, S, rbins, tbins, pbins, (unsigned long long)levels * S * zstride * 8ull);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double cell[9], height[3] = {0.0, 0.0, 0.0}, volume = 0.0;
+    HIPCHK(hipMemcpy(cell, m.cell.p, sizeof(double) * 9, hipMemcpyDeviceToHost));
+    RdfGeom g = {};
+    const bool has_volume = md_rdf_geometry(cell, m.run.pbc, dbins ? dmax : 0.0, g, volume, height);
+    if (dbins) {
+        if (!has_volume) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: the cell has no volume; the distinct part needs one");
+        for (int k = 0; k < 3; k++)
+            if (g.R[k] > RDF_MAXR)
+                return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: dmax = %g against the cell height %g along direction %d needs images %d cells away; at most %d (125 shifts)",
+                            dmax, height[k], k, g.R[k], RDF_MAXR);
+    }
+    g.rmin = 0.0; g.rmax = dbins ? dmax : 0.0; g.bins = dbins;
+    // the chunks of the self part and the tiles of the distinct part: runs of consecutive sorted atoms of one species (the sort is
+    // by species in table order); every ordered pair of tiles
+    std::vector<int> nz(S, 0), first(S, 0);
+    for (int i = 0, last = 0; i < N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
+        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: the run's atoms are not sorted by the model's species");
+        last = z; nz[z]++;
+    }
+    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
+    std::vector<int> tab;
+    for (int z = 0; z < S; z++)
+        for (int o = 0; o < nz[z]; o += MSD_CHUNK) { tab.push_back(first[z] + o); tab.push_back(std::min(MSD_CHUNK, nz[z] - o)); tab.push_back(z); }
+    const int nch = (int)tab.size() / VH_CHUNK;
+    int npairs = 0;
+    if (dbins)
+        for (int a = 0; a < S; a++)
+            for (int oa = 0; oa < nz[a]; oa += RDF_TILE)
+                for (int b = 0; b < S; b++)
+                    for (int ob = 0; ob < nz[b]; ob += RDF_TILE, npairs++) {
+                        const int rec[RDF_PAIR] = {first[a] + oa, std::min(RDF_TILE, nz[a] - oa), first[b] + ob, std::min(RDF_TILE, nz[b] - ob), a * S + b, 1};
+                        tab.insert(tab.end(), rec, rec + RDF_PAIR);
+                    }
+    tab.insert(tab.end(), nz.begin(), nz.end());
+    std::vector<double> edges((size_t)tbins + 2 * pbins);
+    for (int k = 0; k < tbins; k++) edges[k] = cos((double)k * M_PI / (double)tbins);
+    for (int k = 0; k < pbins; k++) {
+        const double f = -M_PI + 2.0 * M_PI * (double)k / (double)pbins;
+        edges[tbins + k] = cos(f); edges[tbins + pbins + k] = sin(f);
+    }
+    if (m.vh.origin.alloc((size_t)levels * 3 * N, false) || m.vh.edges.alloc(edges.size(), false) || m.vh.hs.alloc((size_t)levels * S * zstride) ||
+        m.vh.over.alloc((size_t)levels * S) || m.vh.hd.alloc((size_t)levels * S * S * dbins) || m.vh.ctl.alloc((size_t)VH_CTL + levels) ||
+        m.vh.tab.alloc(tab.size(), false)) {
+        m.vh = MdState::VanHoveBufs();
+        return fail(SGPR_E_NODEVICE, "sgpr_md_vanhove: device allocation failed");
+    }
+    HIPCHK(hipMemcpy(m.vh.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.vh.edges.p, edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice));
+    MdRun::VanHove &a = m.run.vh;
+    a = MdRun::VanHove();
+    a.split = std::max(1, std::min(RDF_SPLIT_MAX, RDF_WORKGROUPS / std::max(1, npairs)));
+    a.every = every; a.levels = levels; a.rbins = rbins; a.tbins = tbins; a.pbins = pbins; a.dbins = dbins; a.nch = nch; a.npairs = npairs; a.S = S;
+    a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.rmax = rmax; a.dmax = dbins ? dmax : 0.0; a.volume = has_volume ? volume : 0.0;
+    return SGPR_OK;
+}
+
+// The angular edges of the self part as the caller made them: ct [tbins] = cos(k pi / tbins), cu, su [pbins] = cos, sin of
+// -pi + 2 pi k / pbins (entry 0 of each is never compared).  A host twin that compares with the same doubles gives the same
+// counts whatever the two libraries' cos and sin do to a last bit.  After sgpr_md_vanhove, before the first sgpr_md_run.
+extern "C" int sgpr_md_vanhove_edges(sgpr_model *h, const double *ct, const double *cu, const double *su)
+{
+    if (!h || !ct || !cu || !su) return fail(SGPR_E_INVALID, "sgpr_md_vanhove_edges: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.vh.every) return fail(SGPR_E_INVALID, "sgpr_md_vanhove_edges: call sgpr_md_begin and sgpr_md_vanhove first");
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_vanhove_edges: the run has started");
+    const MdRun::VanHove &a = m.run.vh;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(m.vh.edges.p, ct, sizeof(double) * a.tbins, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.vh.edges.p + a.tbins, cu, sizeof(double) * a.pbins, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.vh.edges.p + a.tbins + a.pbins, su, sizeof(double) * a.pbins, hipMemcpyHostToDevice));
+    return SGPR_OK;
+}
+
+// The tables as they stand (between two calls of a run; the stream is synchronised): self_hist [levels][S][rbins][tbins][pbins],
+// over [levels][S], distinct_hist [levels][S][S][dbins] (origin's species first), counts [levels] the windows of a level, info
+// [8 + S] = samples taken, next_due (the configuration the tables wait for), levels, S, rbins, tbins, pbins, dbins, and the atoms
+// of every species in the frame; geom [3] = the volume |det cell| (0: none), rmax, dmax.  Any pointer may be NULL.
+extern "C" int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t *over, uint64_t *distinct_hist, int64_t *counts, int64_t *info,
+                                    double *geom)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vanhove_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.vh.every) return fail(SGPR_E_INVALID, "sgpr_md_vanhove_read: call sgpr_md_begin and sgpr_md_vanhove first");
+    const MdRun::VanHove &a = m.run.vh;
+    const size_t LS = (size_t)a.levels * a.S;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<long long> ctl((size_t)VH_CTL + a.levels);
+    HIPCHK(hipMemcpy(ctl.data(), m.vh.ctl.p, sizeof(long long) * ctl.size(), hipMemcpyDeviceToHost));
+    if (self_hist) HIPCHK(hipMemcpy(self_hist, m.vh.hs.p, sizeof(uint64_t) * LS * a.rbins * a.tbins * a.pbins, hipMemcpyDeviceToHost));
+    if (over) HIPCHK(hipMemcpy(over, m.vh.over.p, sizeof(uint64_t) * LS, hipMemcpyDeviceToHost));
+    if (distinct_hist && a.dbins) HIPCHK(hipMemcpy(distinct_hist, m.vh.hd.p, sizeof(uint64_t) * LS * a.S * a.dbins, hipMemcpyDeviceToHost));
+    if (counts) for (int l = 0; l < a.levels; l++) counts[l] = ctl[VH_CTL + l];
+    if (info) {
+        std::vector<int> nz(a.S);
+        HIPCHK(hipMemcpy(nz.data(), m.vh.tab.p + (size_t)VH_CHUNK * a.nch + (size_t)RDF_PAIR * a.npairs, sizeof(int) * a.S, hipMemcpyDeviceToHost));
+        info[0] = ctl[1]; info[1] = ctl[0]; info[2] = a.levels; info[3] = a.S; info[4] = a.rbins; info[5] = a.tbins; info[6] = a.pbins; info[7] = a.dbins;
+        for (int z = 0; z < a.S; z++) info[8 + z] = nz[z];
+    }
+    if (geom) { geom[0] = a.volume; geom[1] = a.rmax; geom[2] = a.dmax; }
+    return SGPR_OK;
+}
+
 // Deviates of the integrator on the device: seed != 0 makes sgpr_md_run (called with noise = NULL) draw the standard
 // normal deviate of (configuration index, atom, component) from a counter-based generator; 0 switches that off.
 extern "C" int sgpr_md_seed(sgpr_model *h, uint64_t seed)
@@ -2543,6 +2727,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.vacf = MdState::VacfBufs();
+    }
+    if (m.vh.held()) {   // (and the origins and the tables of the van Hove functions)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.vh = MdState::VanHoveBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

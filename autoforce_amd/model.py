@@ -1217,6 +1217,53 @@ class SGPRModel:
                     species=np.array([int(z) for z in self.species]), n=info[3:].copy(), samples=int(info[0]), pending=int(info[1]),
                     next_due=int(info[2]))
 
+    def md_vanhove(self, every, levels, rmax, rbins, tbins=1, pbins=1, dmax=None, dbins=0):
+        """Accumulate van Hove correlation functions inside the loop (sgpr_md_vanhove; md_vanhove.inc has the scheme,
+        workloads.VanHoveCounts is the host twin and the definition; all entries are counts, the two are equal).  Samples and
+        levels as md_msd: configuration n with n % every == 0 is sample n / every; level l < levels has the lag 2^l samples,
+        one origin and windows that do not overlap.  Self part: per species of the model's table the histogram of the atoms'
+        raw displacements over (r < rmax, theta, phi) in rbins x tbins x pbins bins — what
+        theforce/analysis/analysis.py's `hist_rtp_displacements` takes from a stored trajectory at one lag; tbins = pbins = 1 is
+        the radial G_s(r, t); displacements of rmax and more are counted in `over`.  Distinct part (dbins > 0): per ordered pair
+        of species the distances r < dmax between an atom's origin and the other atoms' present positions, periodic images
+        included (the atom's own image at shift 0 left out), in dbins bins.  After md_begin, before the first md_run; every = 0
+        detaches and frees.  md_vanhove_table() reads the tables.  Langevin, velocity Verlet and Nose-Hoover at constant cell on
+        one rank, with or without fixed=, ml_filter=, md_meta, md_record, md_msd, md_rdf and md_vacf; a barostat, a committee, a
+        relaxation, a band, a polymer, several ranks, a self table over 1 GiB and a dmax beyond 2.5 cell heights:
+        NotImplementedError."""
+        from .workloads import vanhove_edges
+        lib = _lib.load()
+        try:
+            check(lib.sgpr_md_vanhove(self._h, int(every), int(levels), float(rmax), int(rbins), int(tbins), int(pbins),
+                                      float(dmax) if dbins else 0.0, int(dbins)))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        if every:   # (the edges the twin compares with: numpy's doubles, not this library's)
+            ct, cu, su = (np.ascontiguousarray(a, dtype=np.float64) for a in vanhove_edges(tbins, pbins))
+            check(lib.sgpr_md_vanhove_edges(self._h, ptr(ct), ptr(cu), ptr(su)))
+        self._md["vanhove"] = (int(every), int(levels), int(rbins), int(tbins), int(pbins), int(dbins)) if every else None
+
+    def md_vanhove_table(self):
+        """The tables of md_vanhove as they stand (sgpr_md_vanhove_read; between two md_run calls): a dict with "self" [L, S, rbins,
+        tbins, pbins], over [L, S], distinct [L, S, S, dbins] (origin's species first), all uint64; count [L] windows per level,
+        lags [L] in configurations, species [S] the model's table, n [S] its atoms in the frame, samples, next_due, every, levels,
+        rmax, rbins, tbins, pbins, dmax, dbins, volume."""
+        if not self._md.get("vanhove"):
+            raise RuntimeError("md_vanhove_table: no accumulator on this run (md_vanhove)")
+        every, L, rbins, tbins, pbins, dbins = self._md["vanhove"]
+        S = len(self.species)
+        hs, over, hd = (np.zeros(shape, dtype=np.uint64) for shape in ((L, S, rbins, tbins, pbins), (L, S), (L, S, S, dbins)))
+        cnt, info, geom = np.zeros(L, dtype=np.int64), np.zeros(8 + S, dtype=np.int64), np.zeros(3)
+        check(_lib.load().sgpr_md_vanhove_read(self._h, ptr(hs), ptr(over), ptr(hd) if dbins else None, ptr(cnt), ptr(info), ptr(geom)))
+        tab = dict(over=over, distinct=hd, count=cnt, lags=every * 2 ** np.arange(L, dtype=np.int64),
+                   species=np.array([int(z) for z in self.species]), n=info[8:].copy(), samples=int(info[0]), next_due=int(info[1]),
+                   every=every, levels=L, rmax=float(geom[1]), rbins=rbins, tbins=tbins, pbins=pbins, dmax=float(geom[2]), dbins=dbins,
+                   volume=float(geom[0]))
+        tab["self"] = hs
+        return tab
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

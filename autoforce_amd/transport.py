@@ -6,7 +6,10 @@ level's windows, and of their squares; the windows of a level do not overlap, so
   And the structure beside it: `Rdf` holds the pair-distance counts of SGPRModel.md_rdf / workloads.RdfCounts, and
 `radial_distribution` forms the g(r) per species pair of theforce/analysis/rdf.py's `rdf` from them.
   And the dynamics: `Vacf` holds the velocity correlations of SGPRModel.md_vacf / workloads.VacfRing; `green_kubo`, `onsager` and
-`vibrational_dos` read a diffusion constant, the species' current correlations and a density of states off them."""
+`vibrational_dos` read a diffusion constant, the species' current correlations and a density of states off them.
+  And the distributions behind the moments: `VanHove` holds the displacement and pair histograms per lag of SGPRModel.md_vanhove /
+workloads.VanHoveCounts; `displacement_histogram` is the return of analysis.py:178-210 (`hist_rtp_displacements`), `self_van_hove`,
+`distinct_van_hove` and `non_gaussian` form G_s(r, t), G_d(r, t) and alpha_2(t)."""
 import numpy as np
 
 KEYS = ("msd", "msd_sq", "smd", "smd_sq")
@@ -248,3 +251,135 @@ def vibrational_dos(vacf, dt_fs, window="hann"):
             continue
         out[int(z)] = kern @ (w * C[:L, q] / C[0, q])
     return f, out
+
+
+class VanHove:
+    """Holder of van Hove tables: ActiveCalculator.run_md(vanhove=VanHove(every, levels, rmax, rbins, tbins, pbins, dmax, dbins))
+    fills it, as msd= fills an Msd; add(table) adds the tables of a run (SGPRModel.md_vanhove_table(), VanHoveCounts.table()) —
+    the tables of several runs of one frame with the same settings add up, count by count.  displacement_histogram,
+    self_van_hove, distinct_van_hove and non_gaussian read them."""
+
+    def __init__(self, every, levels, rmax, rbins, tbins=1, pbins=1, dmax=None, dbins=0):
+        self.every, self.levels, self.rmax = int(every), int(levels), float(rmax)
+        self.rbins, self.tbins, self.pbins, self.dbins = int(rbins), int(tbins), int(pbins), int(dbins)
+        self.dmax = float(dmax) if self.dbins else 0.0
+        self.lags = self.every * 2 ** np.arange(self.levels, dtype=np.int64)   # in configurations
+        self.count = np.zeros(self.levels, dtype=np.int64)
+        self.samples = 0
+        self.hist = self.over = self.distinct = self.species = self.n = self.volume = None
+
+    def _settings(self):
+        return (self.every, self.levels, self.rmax, self.rbins, self.tbins, self.pbins, self.dmax, self.dbins)
+
+    def add(self, table):
+        got = (int(table["every"]), int(table["levels"]), float(table["rmax"]), int(table["rbins"]), int(table["tbins"]), int(table["pbins"]),
+               float(table["dmax"]), int(table["dbins"]))
+        if got != self._settings():
+            raise ValueError("VanHove.add: the table was taken with other settings (every, levels, rmax, bins, dmax)")
+        species, n = np.asarray(table["species"]), np.asarray(table["n"])
+        if self.species is None:
+            self.species, self.n, self.volume = species.copy(), n.copy(), float(table["volume"])
+            S = len(species)
+            self.hist = np.zeros((self.levels, S, self.rbins, self.tbins, self.pbins), dtype=np.uint64)
+            self.over = np.zeros((self.levels, S), dtype=np.uint64)
+            self.distinct = np.zeros((self.levels, S, S, self.dbins), dtype=np.uint64)
+        elif not (np.array_equal(species, self.species) and np.array_equal(n, self.n) and float(table["volume"]) == self.volume):
+            raise ValueError("VanHove.add: the table is of another frame (species, atoms per species, volume)")
+        self.hist = self.hist + np.asarray(table["self"], dtype=np.uint64)
+        self.over = self.over + np.asarray(table["over"], dtype=np.uint64)
+        self.distinct = self.distinct + np.asarray(table["distinct"], dtype=np.uint64)
+        self.count = self.count + np.asarray(table["count"], dtype=np.int64)
+        self.samples += int(table["samples"])
+        return self
+
+    def table(self):
+        tab = dict(over=self.over.copy(), distinct=self.distinct.copy(), count=self.count.copy(), lags=self.lags.copy(), species=self.species,
+                   n=self.n, samples=self.samples, next_due=self.samples * self.every, every=self.every, levels=self.levels, rmax=self.rmax,
+                   rbins=self.rbins, tbins=self.tbins, pbins=self.pbins, dmax=self.dmax, dbins=self.dbins, volume=self.volume)
+        tab["self"] = self.hist.copy()
+        return tab
+
+    def slot(self, species):
+        """The slot of atomic number `species` in the table."""
+        if self.species is None:
+            raise ValueError("VanHove: the holder has no table")
+        k = np.flatnonzero(self.species == int(species))
+        if len(k) == 0 or self.n[k[0]] == 0:
+            raise ValueError(f"VanHove: no atoms of species {species} in the frame")
+        return int(k[0])
+
+
+def _centres(lo, hi, bins):
+    """The reference's axis: the edges linspace(lo, hi, bins + 1) less the last, plus half the first step."""
+    a = np.linspace(lo, hi, bins + 1)
+    return a[:-1] + (a[1] - a[0]) / 2
+
+
+def displacement_histogram(vh, level, species):
+    """(r [rbins], theta [tbins], phi [pbins], h [rbins, tbins, pbins], rho) — the return of the reference's
+    TrajAnalyser.hist_rtp_displacements(delta = vh.lags[level], rmax, bins=[rbins + 1, tbins + 1, pbins + 1], select=species)
+    with the level's non-overlapping windows for its random pairs: the bin centres, the histogram of the displacements over
+    N windows, and the density N / V of the selected atoms (0 for a cell without volume)."""
+    z = vh.slot(species)
+    if vh.count[level] == 0:
+        raise ValueError("displacement_histogram: the level has no window yet")
+    h = vh.hist[level, z].astype(float) / (float(vh.n[z]) * float(vh.count[level]))
+    rho = float(vh.n[z]) / vh.volume if vh.volume else 0.0
+    return _centres(0.0, vh.rmax, vh.rbins), _centres(0.0, np.pi, vh.tbins), _centres(-np.pi, np.pi, vh.pbins), h, rho
+
+
+def self_van_hove(vh):
+    """(r [rbins], {Z: G [levels, rbins]}) per species present in the frame: the self part G_s(r, t_l) = P_l(k) / (4 pi r_k^2 dr),
+    P_l(k) the fraction of the level's displacements in radial bin k (the table summed over the angles), at the bin centres r_k;
+    4 pi int G_s r^2 dr = 1 less the fraction beyond rmax (vh.over).  nan where a level has no window."""
+    if vh.hist is None:
+        raise ValueError("self_van_hove: the holder has no table")
+    r = _centres(0.0, vh.rmax, vh.rbins)
+    shell = 4.0 * np.pi * r ** 2 * (vh.rmax / vh.rbins)
+    c = np.where(vh.count > 0, vh.count, 1).astype(float)[:, None]
+    out = {}
+    for z, Z in enumerate(vh.species):
+        if vh.n[z] == 0:
+            continue
+        P = vh.hist[:, z].sum(axis=(2, 3)).astype(float) / (float(vh.n[z]) * c)
+        out[int(Z)] = np.where(vh.count[:, None] > 0, P / shell, np.nan)
+    return r, out
+
+
+def distinct_van_hove(vh):
+    """(r [dbins], {(Za, Zb): G [levels, dbins]}) for every ordered pair of species present in the frame: the distinct part over
+    the density of b, G_d(r, t_l) / rho_b = H[l][a][b][k] / (windows n_a 4 pi r_k^2 dr n_b / V) — a (origin) at time 0, b at
+    t_l; at t -> 0 the g_ab(r) of transport.radial_distribution, at large t and r it tends to 1."""
+    if vh.hist is None or not vh.dbins:
+        raise ValueError("distinct_van_hove: the holder has no distinct part (dbins > 0)")
+    r = _centres(0.0, vh.dmax, vh.dbins)
+    shell = 4.0 * np.pi * r ** 2 * (vh.dmax / vh.dbins)
+    c = np.where(vh.count > 0, vh.count, 1).astype(float)[:, None]
+    out = {}
+    for a, Za in enumerate(vh.species):
+        for b, Zb in enumerate(vh.species):
+            if vh.n[a] == 0 or vh.n[b] == 0:
+                continue
+            G = vh.distinct[:, a, b].astype(float) / (c * float(vh.n[a]) * shell * (float(vh.n[b]) / vh.volume))
+            out[(int(Za), int(Zb))] = np.where(vh.count[:, None] > 0, G, np.nan)
+    return r, out
+
+
+def non_gaussian(vh):
+    """{Z: alpha_2 [levels]} per species present in the frame: alpha_2(t_l) = 3 <r^4> / (5 <r^2>^2) - 1 of the level's
+    displacements, 0 for a Gaussian (flow), positive where a few atoms hop while the rest rattle.  BINNED: the moments are taken
+    from the radial marginal at the bin centres, with a relative error O((dr / r)^2) in each, and displacements beyond rmax
+    (vh.over) are left out — choose rmax so that `over` stays empty.  nan where a level has no window or no displacement."""
+    if vh.hist is None:
+        raise ValueError("non_gaussian: the holder has no table")
+    r = _centres(0.0, vh.rmax, vh.rbins)
+    out = {}
+    for z, Z in enumerate(vh.species):
+        if vh.n[z] == 0:
+            continue
+        P = vh.hist[:, z].sum(axis=(2, 3)).astype(float)
+        tot = P.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m2, m4 = (P * r ** 2).sum(axis=1) / tot, (P * r ** 4).sum(axis=1) / tot
+            out[int(Z)] = 3.0 * m4 / (5.0 * m2 * m2) - 1.0
+    return out

@@ -2055,6 +2055,175 @@ class RdfCounts:
                     every=self.every, bins=self.bins, rmin=self.rmin, rmax=self.rmax, volume=self.volume)
 
 
+VH_MAXRBINS = 2048   # radial bins of the self part (md_vanhove.inc)
+VH_MAXABINS = 64     # polar and azimuthal bins: the edge tables sit in LDS
+VH_MAXBYTES = 1 << 30   # the self table levels S rbins tbins pbins 8 B
+
+
+def vanhove_edges(tbins, pbins):
+    """The angular edges of the van Hove self part as the comparisons take them: ct [tbins] = cos(k pi / tbins), cu, su [pbins] =
+    cos, sin of f_k = -pi + 2 pi k / pbins (entry 0 of each is never compared).  Made here once, with numpy; SGPRModel.md_vanhove
+    uploads these doubles and VanHoveCounts compares with the same ones."""
+    kt, kp = np.arange(int(tbins), dtype=float), np.arange(int(pbins), dtype=float)
+    f = -np.pi + 2.0 * np.pi * kp / float(pbins)
+    return np.cos(kt * np.pi / float(tbins)), np.cos(f), np.sin(f)
+
+
+def vanhove_self_bins(d, rmax, rbins, tbins, pbins, ct, cu, su):
+    """The bin rule of the self part for displacements d [n, 3]: (inside [n] bool, kr, kt, kp [n]) — r = sqrt((d0 d0 + d1 d1) +
+    d2 d2) as the reference's cart_coord_to_sph forms it; r >= rmax is outside; kr = min((int)((r / rmax) rbins), rbins - 1); kt
+    counts the polar edges k = 1 ... tbins - 1 with d2 <= ct[k] r (theta >= k pi / tbins); kp counts the azimuthal edges
+    k = 1 ... pbins - 1 that atan2(d1, d0) has passed, decided by the sign of d1 and of cu[k] d1 - su[k] d0; r == 0 is bin
+    (0, 0, pbins / 2), where the reference's atan2(0, 0) = 0 lands.  Only + - x / sqrt and comparisons: no acos, no atan2."""
+    d = np.asarray(d, float).reshape(-1, 3)
+    d0, d1, d2 = d[:, 0], d[:, 1], d[:, 2]
+    q = d0 * d0 + d1 * d1
+    r = np.sqrt(q + d2 * d2)
+    inside = r < rmax
+    kr = np.minimum(((r / rmax) * float(rbins)).astype(np.int64), rbins - 1)
+    kt = np.zeros(len(d), dtype=np.int64)
+    for k in range(1, tbins):
+        kt += d2 <= ct[k] * r
+    kp = np.zeros(len(d), dtype=np.int64)
+    for k in range(1, pbins):
+        cross = cu[k] * d1 - su[k] * d0 >= 0.0
+        if 2 * k < pbins:
+            kp += (d1 >= 0.0) | cross
+        elif 2 * k == pbins:
+            kp += d1 >= 0.0
+        else:
+            kp += (d1 >= 0.0) & cross
+    held = r == 0.0
+    kr[held], kt[held], kp[held] = 0, 0, pbins // 2
+    return inside, kr, kt, kp
+
+
+class VanHoveCounts:
+    """Van Hove correlation functions as tables of integers — the host twin of the accumulator inside the device loop
+    (SGPRModel.md_vanhove, md_vanhove.inc) and its definition; every entry is a count, so the two are equal.  The self part is
+    what theforce/analysis/analysis.py:178-210 (`hist_rtp_displacements`: np.histogramdd of the displacements over (r, theta,
+    phi) at one lag) takes from a stored trajectory; the reference has no distinct part.
+      add(x) is fed the configurations 0, 1, 2, ... of a run ([N, 3], caller atom order, never wrapped).  Samples and levels are
+    MsdBlocks': configuration n with n % every == 0 is sample s = n / every; level l < levels has the lag 2^l samples and ONE
+    origin O_l; at sample s every level with s mod 2^l == 0 is due, measures if s >= 2^l (count[l] += 1) and then sets O_l <- x.
+      Self: per atom i of species slot z, d = x_i - O_l,i goes through vanhove_self_bins; self[l, z, kr, kt, kp] or over[l, z]
+    gains 1, so self[l, z].sum() + over[l, z] == n_z count[l].  Displacements are raw: no centre of mass is taken out.
+      Distinct (dbins > 0): distinct[l, a, b, k] gains the number of triples (i of a, j of b, s in Z^3) with (j, s) != (i, 0) and
+        d = (x_j - O_l,i) + ((s0 h0 + s1 h1) + s2 h2),  r = sqrt((d0 d0 + d1 d1) + d2 d2) < dmax,  k = (int)((r / dmax) dbins)
+    — RdfCounts' enumeration with rmin = 0: the pair goes to its nearest image by n = rint(dx inv), s = t - n over the block
+    |t_k| <= R_k, and for j == i the image left out is s == 0, that is t == n (an atom that has moved more than half a cell has
+    n != 0).  Origin and present are not interchangeable: the full S x S is kept.  A frozen trajectory gives RdfCounts' table
+    per window."""
+
+    def __init__(self, every, levels, rmax, rbins, tbins, pbins, dmax, dbins, numbers, species, cell, pbc):
+        if every < 1 or not 1 <= levels <= 32:
+            raise ValueError("VanHoveCounts: every >= 1, 1 <= levels <= 32")
+        if not (1 <= rbins <= VH_MAXRBINS and 1 <= tbins <= VH_MAXABINS and 1 <= pbins <= VH_MAXABINS and 0.0 < rmax < 1e300):
+            raise ValueError(f"VanHoveCounts: rmax > 0, 1 <= rbins <= {VH_MAXRBINS}, 1 <= tbins, pbins <= {VH_MAXABINS}")
+        if not 0 <= dbins <= RDF_MAXBINS or (dbins and not 0.0 < float(dmax) < 1e300):
+            raise ValueError(f"VanHoveCounts: 0 <= dbins <= {RDF_MAXBINS}, dmax > 0 with dbins > 0")
+        self.every, self.levels, self.rmax = int(every), int(levels), float(rmax)
+        self.rbins, self.tbins, self.pbins = int(rbins), int(tbins), int(pbins)
+        self.dbins, self.dmax = int(dbins), float(dmax) if dbins else 0.0
+        self.species = [int(z) for z in species]
+        S = len(self.species)
+        if self.levels * S * self.rbins * self.tbins * self.pbins * 8 > VH_MAXBYTES:
+            raise NotImplementedError(f"VanHoveCounts: a self table of {self.levels} x {S} x {self.rbins} x {self.tbins} x {self.pbins} counts; at most 1 GiB")
+        self.ct, self.cu, self.su = vanhove_edges(self.tbins, self.pbins)
+        self.h = np.asarray(cell, float).reshape(3, 3).copy()
+        self.pbc = np.broadcast_to(np.asarray(pbc, bool), (3,)).copy()
+        self.volume = 0.0
+        if self.dbins:
+            self.inv, self.volume, self.heights, self.R = rdf_geometry(self.h, self.pbc, self.dmax)
+            for k in range(3):
+                if self.R[k] > RDF_MAXR:
+                    raise NotImplementedError(f"VanHoveCounts: dmax = {self.dmax:g} against the cell height {self.heights[k]:g} along direction {k} "
+                                              f"needs images {self.R[k]} cells away; at most {RDF_MAXR} (125 shifts)")
+        else:
+            try:
+                self.volume = rdf_geometry(self.h, self.pbc, 0.0)[1]
+            except ValueError:   # (a cell without volume: the self part needs none, the density is then 0)
+                pass
+        numbers = np.asarray(numbers)
+        self.idx = [np.flatnonzero(numbers == z) for z in self.species]
+        self.nz = np.array([len(i) for i in self.idx])
+        self.origin = [None] * self.levels
+        self.count = np.zeros(self.levels, dtype=np.int64)
+        self.hs = np.zeros((self.levels, S, self.rbins, self.tbins, self.pbins), dtype=np.uint64)
+        self.over = np.zeros((self.levels, S), dtype=np.uint64)
+        self.hd = np.zeros((self.levels, S, S, self.dbins), dtype=np.uint64)
+        self.n = 0   # configurations seen
+
+    def _self(self, l, x):
+        shape = (self.rbins, self.tbins, self.pbins)
+        for z, I in enumerate(self.idx):
+            if len(I) == 0:
+                continue
+            inside, kr, kt, kp = vanhove_self_bins(x[I] - self.origin[l][I], self.rmax, self.rbins, self.tbins, self.pbins, self.ct, self.cu, self.su)
+            flat = np.ravel_multi_index((kr[inside], kt[inside], kp[inside]), shape)
+            self.hs[l, z] += np.bincount(flat, minlength=self.rbins * self.tbins * self.pbins).reshape(shape).astype(np.uint64)
+            self.over[l, z] += np.uint64(np.sum(~inside))
+
+    def _pairs(self, xi, xj, same):
+        """The counts [dbins] of the origins xi against the present positions xj (same: one list of atoms, (i, 0) stays out)."""
+        h, inv, out = self.h, self.inv, np.zeros(self.dbins, dtype=np.int64)
+        rmin, width, fbins = 0.0, self.dmax - 0.0, float(self.dbins)
+        for o in range(0, len(xi), 256):
+            dx = xj[None, :, :] - xi[o:o + 256, None, :]
+            dx0, dx1, dx2 = dx[..., 0], dx[..., 1], dx[..., 2]
+            n = [np.rint((dx0 * inv[0, k] + dx1 * inv[1, k]) + dx2 * inv[2, k]) if self.pbc[k] else np.zeros_like(dx0) for k in range(3)]
+            rows = np.arange(dx.shape[0])
+            for t0 in range(-self.R[0], self.R[0] + 1):
+                for t1 in range(-self.R[1], self.R[1] + 1):
+                    for t2 in range(-self.R[2], self.R[2] + 1):
+                        s0, s1, s2 = float(t0) - n[0], float(t1) - n[1], float(t2) - n[2]
+                        d0 = dx0 + ((s0 * h[0, 0] + s1 * h[1, 0]) + s2 * h[2, 0])
+                        d1 = dx1 + ((s0 * h[0, 1] + s1 * h[1, 1]) + s2 * h[2, 1])
+                        d2 = dx2 + ((s0 * h[0, 2] + s1 * h[1, 2]) + s2 * h[2, 2])
+                        r = np.sqrt((d0 * d0 + d1 * d1) + d2 * d2)
+                        ok = (r >= rmin) & (r < self.dmax)
+                        if same:   # (the image of i itself with s == 0: t == n)
+                            own = (s0[rows, o + rows] == 0.0) & (s1[rows, o + rows] == 0.0) & (s2[rows, o + rows] == 0.0)
+                            ok[rows[own], o + rows[own]] = False
+                        k = np.minimum((((r[ok] - rmin) / width) * fbins).astype(np.int64), self.dbins - 1)
+                        out += np.bincount(k, minlength=self.dbins)
+        return out
+
+    def _distinct(self, l, x):
+        for a, Ia in enumerate(self.idx):
+            for b, Ib in enumerate(self.idx):
+                if len(Ia) and len(Ib):
+                    self.hd[l, a, b] += self._pairs(self.origin[l][Ia], x[Ib], a == b).astype(np.uint64)
+
+    def add(self, positions):
+        """The next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        s = n // self.every
+        x = np.array(positions, float).reshape(-1, 3)
+        for l in range(self.levels):
+            if s % (1 << l):
+                break
+            if s >= (1 << l):
+                self._self(l, x)
+                if self.dbins:
+                    self._distinct(l, x)
+                self.count[l] += 1
+            self.origin[l] = x.copy()
+
+    def table(self):
+        """What SGPRModel.md_vanhove_table returns."""
+        samples = -(-self.n // self.every)
+        tab = dict(over=self.over.copy(), distinct=self.hd.copy(), count=self.count.copy(),
+                   lags=self.every * 2 ** np.arange(self.levels, dtype=np.int64), species=np.array(self.species), n=self.nz.copy(),
+                   samples=samples, next_due=samples * self.every, every=self.every, levels=self.levels, rmax=self.rmax, rbins=self.rbins,
+                   tbins=self.tbins, pbins=self.pbins, dmax=self.dmax, dbins=self.dbins, volume=self.volume)
+        tab["self"] = self.hs.copy()
+        return tab
+
+
 def philox4x32_10(counter, key):
     """Philox4x32 with ten rounds (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11, section
     3.3 and the constants of its table): counter[..., 4] and key[..., 2] 32-bit words -> uint32[..., 4].  One round takes

@@ -637,6 +637,46 @@ int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, double *geom)
  * The handle stays usable after every error above. */
 int sgpr_md_vacf(sgpr_model *h, int every, int lags, int origin_every, int com);
 int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collective, int64_t *counts, int64_t *info);
+/* Van Hove correlation functions accumulated inside the loop, as integers in device memory.  The self part is the histogram the
+ * reference takes from a stored trajectory at one lag (theforce/analysis/analysis.py:178-210 `hist_rtp_displacements`); the
+ * reference has no distinct part.  workloads.VanHoveCounts is the host twin and the definition; the device equals it exactly.
+ * Samples and levels are sgpr_md_msd's: sample s is configuration n = s every, level l < levels has the lag 2^l samples and ONE
+ * origin O_l; at sample s every level with s mod 2^l == 0 measures, if s >= 2^l (counts[l] += 1), and then sets O_l <- x.
+ * Self, atom i of species slot z: d = x_i - O_l,i (raw: no centre of mass is taken out), q = d0 d0 + d1 d1, r = sqrt(q + d2 d2).
+ *     r >= rmax: over[l][z] += 1.   r == 0 (a held atom): bin (0, 0, pbins / 2), where atan2(0, 0) = 0 lands.   Else
+ *     kr = min((int)((r / rmax) rbins), rbins - 1)
+ *     kt = the number of k in 1 ... tbins - 1 with d2 <= ct[k] r,              ct[k] = cos(k pi / tbins)
+ *     kp = the number of k in 1 ... pbins - 1 that pass, (cu, su)[k] = (cos, sin)(-pi + 2 pi k / pbins), c = cu[k] d1 - su[k] d0:
+ *          2k < pbins: d1 >= 0 or c >= 0;   2k == pbins: d1 >= 0;   2k > pbins: d1 >= 0 and c >= 0
+ * and self_hist[l][z][kr][kt][kp] += 1: np.histogramdd over linspace(0, rmax), linspace(0, pi), linspace(-pi, pi) without an acos
+ * or atan2 deciding a bin.  self_hist[l][z] summed plus over[l][z] equals n_z counts[l].
+ * Distinct (dbins > 0): distinct_hist[l][a][b][k] gains the triples (i of a, j of b, s in Z^3) with (j, s) != (i, 0) and
+ *     d = (x_j - O_l,i) + ((s0 h0 + s1 h1) + s2 h2),  0 <= r < dmax,  k = min((int)((r / dmax) dbins), dbins - 1)
+ * by sgpr_md_rdf's enumeration (nearest image by rounding, then the block of shifts that can come within dmax).  Origin and
+ * present are not interchangeable: the table is the full S x S.  A frozen trajectory gives sgpr_md_rdf's table per window.
+ * A configuration evaluated twice (the repeat behind a covloss halt or an overflow) counts once, the speculative evaluation
+ * behind a halt not at all.
+ *
+ * sgpr_md_vanhove        every >= 1, 1 <= levels <= 32, rmax > 0, 1 <= rbins <= 2048, 1 <= tbins, pbins <= 64, 0 <= dbins <= 2048
+ *                        (0: no distinct part; dmax is then ignored): after sgpr_md_begin (and sgpr_md_fix, _thermostat, _filter,
+ *                        _meta, _record, _msd, _rdf, _vacf, if used), before the first sgpr_md_run; zeroes the tables.  every = 0
+ *                        detaches and frees: the run launches what it launched before.  At most three launches behind a sampled
+ *                        evaluation; the distinct part is O(N^2) per due level.  SGPR_E_INVALID: no run begun, a run that has
+ *                        started, values out of range, a cell without volume with dbins > 0.  SGPR_E_UNSUPPORTED: a self table
+ *                        levels S rbins tbins pbins 8 B over 1 GiB, dmax beyond 2.5 heights of the cell along a periodic
+ *                        direction, several ranks, a barostat, a committee, a relaxation, a band, a polymer — and from
+ *                        sgpr_md_barostat, _committee, _relax, _neb and _pimd on a run that has the accumulator.
+ * sgpr_md_vanhove_edges  replaces the tables ct[tbins], cu[pbins], su[pbins] the attach made with this library's cos and sin by
+ *                        the caller's, so that a host twin compares with the same doubles.  Before the first sgpr_md_run.
+ * sgpr_md_vanhove_read   between two calls of the run (synchronises the stream): self_hist[levels][S][rbins][tbins][pbins],
+ *                        over[levels][S], distinct_hist[levels][S][S][dbins], counts[levels], info[8 + S] = samples taken, the
+ *                        configuration the tables wait for next, levels, S, rbins, tbins, pbins, dbins, the atoms of every
+ *                        species in the frame; geom[3] = the volume |det cell| (0: none), rmax, dmax.  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax, int rbins, int tbins, int pbins, double dmax, int dbins);
+int sgpr_md_vanhove_edges(sgpr_model *h, const double *ct, const double *cu, const double *su);
+int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t *over, uint64_t *distinct_hist, int64_t *counts, int64_t *info,
+                         double *geom);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
