@@ -553,7 +553,7 @@ class ActiveCalculator(Calculator):
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
                tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None, rdf=None,
-               vacf=None, vanhove=None):
+               vacf=None, vanhove=None, adf=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -628,9 +628,15 @@ class ActiveCalculator(Calculator):
         the same conventions: the device loop counts them itself (SGPRModel.md_vanhove: at most three launches behind a sampled
         evaluation, the tables read once at the end); with a committee or several ranks, and in the host loops,
         workloads.VanHoveCounts — the same integers — is fed the positions of every step.  The cell is constant: with a barostat
-        NotImplementedError."""
+        NotImplementedError.
+        adf: a transport.Adf(every, bins, cutoffs) holder — the bond-angle counts per (centre, end, end) of species and the
+        coordination counts of the run's configurations 0 ... steps are added to it at the end (transport.angle_distribution and
+        coordination read it), by the same conventions: the device loop counts them itself from the step's neighbour list
+        (SGPRModel.md_adf: two launches behind a sampled evaluation, the tables read once at the end; every cutoff at most the
+        model's); with a committee or several ranks, and in the host loops, workloads.AdfCounts — the same integers — is fed the
+        positions of every step.  The cell is constant: with a barostat NotImplementedError."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, FilterState, MsdBlocks, RdfCounts, VacfRing, VanHoveCounts, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, AdfCounts, FilterState, MsdBlocks, RdfCounts, VacfRing, VanHoveCounts, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
         filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
@@ -641,6 +647,8 @@ class ActiveCalculator(Calculator):
             raise NotImplementedError("run_md: rdf= with a barostat (pfactor): pair distances are counted at constant cell")
         if npt and vanhove is not None:
             raise NotImplementedError("run_md: vanhove= with a barostat (pfactor): displacements and pair distances are counted at constant cell")
+        if npt and adf is not None:
+            raise NotImplementedError("run_md: adf= with a barostat (pfactor): bond angles are counted at constant cell")
         baro = dict(pfactor=pfactor, externalstress=externalstress, mask=mask, iso=iso) if npt else {}
 
         fx = held(self.constraint_mask(atoms))
@@ -677,7 +685,8 @@ class ActiveCalculator(Calculator):
                     and not (msd is not None and (npt or committee or self._dist()[1] > 1))
                     and not (rdf is not None and (committee or self._dist()[1] > 1))
                     and not (vacf is not None and (npt or committee or self._dist()[1] > 1 or flt is not None or self.meta is not None))
-                    and not (vanhove is not None and (committee or self._dist()[1] > 1)))
+                    and not (vanhove is not None and (committee or self._dist()[1] > 1))
+                    and not (adf is not None and (committee or self._dist()[1] > 1)))
         seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -699,9 +708,13 @@ class ActiveCalculator(Calculator):
                 hove = None if vanhove is None else VanHoveCounts(vanhove.every, vanhove.levels, vanhove.rmax, vanhove.rbins, vanhove.tbins,
                                                                   vanhove.pbins, vanhove.dmax, vanhove.dbins, numbers,
                                                                   getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
+                bonds = None if adf is None else AdfCounts(adf.every, adf.bins, adf.cutoffs, numbers,
+                                                           getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
                 for st, E, T, _, p, v, *rest in loop:
                     if blocks is not None:
                         blocks.add(p)
+                    if bonds is not None:
+                        bonds.add(p)
                     if hove is not None:
                         hove.add(p)
                     if corr is not None:
@@ -722,6 +735,8 @@ class ActiveCalculator(Calculator):
                     vacf.add(corr.table())
                 if hove is not None:
                     vanhove.add(hove.table())
+                if bonds is not None:
+                    adf.add(bonds.table())
                 return
         eng = self.engine
         kT, dof_kB = kB * temperature_K, dof * kB
@@ -737,6 +752,8 @@ class ActiveCalculator(Calculator):
             eng.md_vacf(vacf.every, vacf.nlags, vacf.origin_every, vacf.com)
         if vanhove is not None:
             eng.md_vanhove(vanhove.every, vanhove.levels, vanhove.rmax, vanhove.rbins, vanhove.tbins, vanhove.pbins, vanhove.dmax, vanhove.dbins)
+        if adf is not None:
+            eng.md_adf(adf.every, adf.bins, adf.cutoffs)
         meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
@@ -828,6 +845,8 @@ class ActiveCalculator(Calculator):
             vacf.add(eng.md_vacf_table())
         if vanhove is not None:
             vanhove.add(eng.md_vanhove_table())
+        if adf is not None:
+            adf.add(eng.md_adf_table())
         if attached:
             self._md_attached_done(eng, attached)
 

@@ -298,6 +298,10 @@ struct MdRun {
         RdfGeom g = {};
         double rmax = 0.0, dmax = 0.0, volume = 0.0;
     } vh;
+    // the bond-angle and coordination distributions (sgpr_md_adf, md_adf.inc): every `every`-th configuration is a sample; `bins`
+    // angle bins per (centre, end, end) of the S species of the model's table, nch chunks of centres of one species each; lds: the
+    // form with LDS counters
+    struct Adf { int every = 0, bins = 0, nch = 0, S = 0; bool lds = true; } adf;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -398,6 +402,13 @@ struct MdState {
         DevBuf<int> tab;                          // [nch][VH_CHUNK] the chunks | [npairs][RDF_PAIR] the ordered tile pairs | [S] a species' atoms
         bool held() const { return ctl.p != nullptr; }
     } vh;
+    struct AdfBufs {
+        DevBuf<unsigned long long> angles, coord;   // [S][S][S][bins] (ends b <= c filled), [S][S][ADF_MAXCOORD]
+        DevBuf<double> par;                         // cut [S][S] | ct [bins]
+        DevBuf<long long> ctl;                      // next_due | samples
+        DevBuf<int> tab;                            // [nch][3] the chunks | [S] a species' atoms
+        bool held() const { return ctl.p != nullptr; }
+    } adf;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1325,6 +1336,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_rdf.inc"
 #include "md_vacf.inc"
 #include "md_vanhove.inc"
+#include "md_adf.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next
@@ -2869,6 +2881,9 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
     if (nx && nx->mode == 2 && nx->md.filt_cur && !(fuse && gather))
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
+    if (nx && nx->mode == 2 && h->md.run.adf.every && !(fuse && gather))
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) read the step's list and its overflow word behind the gather form of the "
+                                        "fused last kernel only");
     if (nx && nx->mode == 2 && h->md.run.meta.on) {
         // the bias of this configuration (sgpr_md_meta), behind the reverse pass's own sums and in front of the kernel that reads them
         const MdState &m = h->md;

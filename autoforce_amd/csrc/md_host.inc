@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _vanhove (displacement and pair histograms per lag), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _vanhove (displacement and pair histograms per lag), _adf (bond angles and coordination), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_vanhove.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_vanhove.inc, md_adf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -192,6 +192,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates pair distances (sgpr_md_rdf), whose image block and densities are those of a constant cell");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates velocity correlations (sgpr_md_vacf), which are not sampled in a moving cell");
     if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates van Hove functions (sgpr_md_vanhove), which are defined at constant cell");
+    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates bond angles (sgpr_md_adf), whose neighbours are read from the list of a constant cell");
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -389,6 +390,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
     if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
+    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates bond angles (sgpr_md_adf), which serve dynamics only");
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -815,6 +817,45 @@ static void md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st)
     hipLaunchKernelGGL(md_vh_done_kernel, dim3(1), dim3(64), 0, st, m.vh.ctl.p, n, a.every, due, acc, halt, step);
 }
 
+// The LDS of md_adf_kernel for a list of capacity maxnn: the waves of a workgroup (4 ... 1, 0: one centre's rows alone do not fit)
+// and the bytes.
+static int md_adf_waves(const MdRun::Adf &a, int maxnn, size_t &bytes)
+{
+    const size_t fixed = adf_lds_fixed(a.S, a.bins, a.lds);
+    for (int w = 4; w >= 1; w--) {
+        bytes = fixed + (size_t)w * (size_t)std::max(maxnn, 1) * ADF_ROW_BYTES;
+        if (bytes <= ADF_LDS_BYTES) return w;
+    }
+    return 0;
+}
+
+// The same for the bond angles (md_adf.inc): the pass over the list that this evaluation's forward pass has left, for the X slot
+// of configuration n, and the launch that counts the sample.  The rows are sized for the list's capacity as it stands now.
+static int md_adf_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::Adf &a = m.run.adf;
+    const long long n = m.run.t + j;
+    size_t bytes = 0;
+    const int waves = md_adf_waves(a, h->maxnn, bytes);
+    if (!waves)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) keep a centre's neighbours in LDS; a list of up to %d entries per atom with "
+                    "%d bins and %d species does not fit %d bytes", h->maxnn, a.bins, a.S, ADF_LDS_BYTES);
+    if (a.nch) {
+        AdfArgs f = {};
+        f.chunk = m.adf.tab.p; f.x = m.X.p + (size_t)3 * m.run.N * (size_t)(n % m.run.ring); f.cell = m.cell.p;
+        f.nn = h->d_nn.p; f.nbr_j = h->d_nbr_j.p; f.nbr_code = h->d_nbr_shift.p;
+        f.cut = m.adf.par.p; f.ct = m.adf.par.p + (size_t)a.S * a.S;
+        f.angles = m.adf.angles.p; f.coord = m.adf.coord.p; f.ctl = m.adf.ctl.p; f.halt = m.halt.p;
+        f.ov = m.scal_d.p + (size_t)SGPR_MD_SCAL * j + 10;
+        f.n = n; f.maxnn = h->maxnn; f.S = a.S; f.bins = a.bins; f.step = step;
+        hipLaunchKernelGGL(a.lds ? md_adf_kernel<true> : md_adf_kernel<false>, dim3(a.nch), dim3(64 * waves), bytes, st, f);
+    }
+    hipLaunchKernelGGL(md_adf_done_kernel, dim3(1), dim3(64), 0, st, m.adf.ctl.p, n, a.every, (const int *)m.halt.p, step,
+                       (const double *)(m.scal_d.p + (size_t)SGPR_MD_SCAL * j + 10));
+    return SGPR_OK;
+}
+
 // Which frames of a call stand (t0: its first configuration): those of the evaluations whose results stand — less the halting
 // one when the covloss gate fired (code 1): that configuration goes to the caller's calculate() and is evaluated, and recorded,
 // again by the next call.  An overflow (2) has left the halting evaluation out of `done` already; a converged relaxation (3)
@@ -983,6 +1024,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates pair distances (sgpr_md_rdf), which the committee's loop does not sample");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates velocity correlations (sgpr_md_vacf), which the committee's loop does not sample");
     if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates van Hove functions (sgpr_md_vanhove), which the committee's loop does not sample");
+    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates bond angles (sgpr_md_adf), which the committee's loop does not sample");
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1353,6 +1395,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
     if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
+    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates bond angles (sgpr_md_adf), which serve dynamics only");
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1481,6 +1524,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates pair distances (sgpr_md_rdf); a polymer's beads are not sampled");
     if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates velocity correlations (sgpr_md_vacf); a polymer's centroid is not sampled");
     if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates van Hove functions (sgpr_md_vanhove); a polymer's beads are not sampled");
+    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates bond angles (sgpr_md_adf); a polymer's beads are not sampled");
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1615,6 +1659,16 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         }
         m.run.meta.fresh = false;
     }
+    if (m.run.adf.every) {
+        // the bond angles read the list that the forward pass leaves behind the fused last kernel: the forms md_meta's qlvar takes
+        if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) read the step's neighbour list behind the gather form of the fused last "
+                        "kernel only (one rank, no graph replay, no side-stream fork, a skin > 0): the frame record and workloads.AdfCounts serve this run");
+        size_t bytes = 0;
+        if (h->maxnn > 0 && !md_adf_waves(m.run.adf, h->maxnn, bytes))
+            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) keep a centre's neighbours in LDS; a list of up to %d entries per atom with "
+                        "%d bins and %d species does not fit %d bytes", h->maxnn, m.run.adf.bins, m.run.adf.S, ADF_LDS_BYTES);
+    }
     m.run.started = true;
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, m.run.npt.on)) return rp;   // (the cell record: a moving cell only)
@@ -1689,6 +1743,8 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         if (m.run.rdf.every && (m.run.t + j) % m.run.rdf.every == 0) md_rdf_sample(h, j, (int)(step0 + j), st);
         if (m.run.vacf.every && (m.run.t + j) % m.run.vacf.every == 0) md_vacf_sample(h, j, (int)(step0 + j), st);
         if (m.run.vh.every && (m.run.t + j) % m.run.vh.every == 0) md_vh_sample(h, j, (int)(step0 + j), st);
+        if (m.run.adf.every && (m.run.t + j) % m.run.adf.every == 0)
+            if (const int ra = md_adf_sample(h, j, (int)(step0 + j), st)) return ra;
         return SGPR_OK;
     });
     if (rc_) return rc_;
@@ -2323,6 +2379,117 @@ extern "C" int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t
     return SGPR_OK;
 }
 
+// Bond-angle and coordination distributions of the run (md_adf.inc has the definition; workloads.AdfCounts is the host twin):
+// every >= 1 — behind the evaluation of configuration n with n % every == 0 two launches count, per centre, the angles between the
+// pairs of its neighbours within cut[a][b] and its neighbours per species, from the neighbour list the step has just built.
+// cut: [S][S] over the species slots of the model's table, symmetric, 0 = the pair never bonds, every entry <= rc; ct: [bins] the
+// caller's cos(e pi / bins) (entry 0 is never compared; they must not increase).  After sgpr_md_begin (and _fix, _thermostat,
+// _filter, _meta, _record, _msd, _rdf, _vacf, _vanhove), before the first sgpr_md_run; every = 0 detaches and frees.  The attach
+// zeroes the tables.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, beside a mask, the filter, a bias,
+// the frame record and the other accumulators (each keeps its own next_due); a barostat, a committee, a relaxation, a band, a
+// polymer and several ranks: SGPR_E_UNSUPPORTED, from here and from their attach functions.
+extern "C" int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut, const double *ct)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_adf: bad arguments");
+    MdState &m = h->md;
+    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_adf: call sgpr_md_begin first");
+    if (every == 0) {   // (a detach gives the tables back: nothing of them is launched or read from here on)
+        m.run.adf = MdRun::Adf();
+        if (m.adf.held()) {
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            m.adf = MdState::AdfBufs();
+        }
+        return SGPR_OK;
+    }
+    if (every < 0 || bins < 1 || bins > ADF_MAXBINS || !cut || !ct)
+        return fail(SGPR_E_INVALID, "sgpr_md_adf: every >= 0, 1 <= bins <= %d, a cutoff table and an edge table", ADF_MAXBINS);
+    const int N = m.run.N, S = h->S;
+    double cmax = 0.0;
+    for (int a = 0; a < S; a++)
+        for (int b = 0; b < S; b++) {
+            const double c = cut[a * S + b];
+            if (!(c >= 0.0) || !(c < 1e300) || c != cut[b * S + a])
+                return fail(SGPR_E_INVALID, "sgpr_md_adf: the cutoff table must be symmetric and >= 0 (slots %d, %d: %g against %g)", a, b, c, cut[b * S + a]);
+            cmax = std::max(cmax, c);
+        }
+    if (!(cmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_adf: every cutoff is 0: no pair bonds");
+    for (int e = 0; e < bins; e++)
+        if (!(fabs(ct[e]) <= 1.0) || (e > 0 && ct[e] > ct[e - 1]))
+            return fail(SGPR_E_INVALID, "sgpr_md_adf: the edges ct[e] = cos(e pi / bins) lie in [-1, 1] and do not increase (entry %d)", e);
+    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_adf: the run has started");
+    if (cmax > h->rc)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: a bond cutoff of %g lies beyond the model's cutoff %g; the step's neighbour list holds no further neighbours", cmax, h->rc);
+    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run was begun on %d ranks; bond angles are accumulated on one", m.run.world);
+    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run has a barostat; the neighbours are read from the list of a constant cell");
+    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run has a committee (sgpr_md_committee), whose loop does not sample bond angles");
+    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a relaxation; bond angles are accumulated over dynamics");
+    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a nudged elastic band; bond angles are accumulated over dynamics");
+    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // the chunks: runs of at most ADF_CHUNK consecutive sorted centres of one species (the sort is by species in table order)
+    std::vector<int> nz(S, 0), first(S, 0);
+    for (int i = 0, last = 0; i < N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
+        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_adf: the run's atoms are not sorted by the model's species");
+        last = z; nz[z]++;
+    }
+    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
+    std::vector<int> tab;
+    for (int z = 0; z < S; z++)
+        for (int o = 0; o < nz[z]; o += ADF_CHUNK) { tab.push_back(first[z] + o); tab.push_back(std::min(ADF_CHUNK, nz[z] - o)); tab.push_back(z); }
+    const int nch = (int)tab.size() / 3;
+    tab.insert(tab.end(), nz.begin(), nz.end());
+    std::vector<double> par(cut, cut + (size_t)S * S);
+    par.insert(par.end(), ct, ct + bins);
+    if (m.adf.angles.alloc((size_t)S * S * S * bins) || m.adf.coord.alloc((size_t)S * S * ADF_MAXCOORD) || m.adf.par.alloc(par.size(), false) ||
+        m.adf.ctl.alloc(2) || m.adf.tab.alloc(tab.size(), false)) {
+        m.adf = MdState::AdfBufs();
+        return fail(SGPR_E_NODEVICE, "sgpr_md_adf: device allocation failed");
+    }
+    HIPCHK(hipMemcpy(m.adf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.adf.par.p, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
+    MdRun::Adf &a = m.run.adf;
+    a = MdRun::Adf();
+    a.every = every; a.bins = bins; a.nch = nch; a.S = S;
+    a.lds = (long long)(S * (S + 1) / 2) * bins <= ADF_LDS_COUNTERS;
+    return SGPR_OK;
+}
+
+// The tables as they stand (between two calls of a run; the stream is synchronised): angles [S][S][S][bins] the counts per (centre,
+// end, end) of species slots, symmetric in the ends and filled out; coord [S][S][64] per (centre, neighbour) the centres with n
+// neighbours (63: that many or more); info [4 + S] = samples taken, next_due (the configuration the tables wait for), bins, S,
+// and the atoms of every species in the frame.  Any pointer may be NULL.
+extern "C" int sgpr_md_adf_read(sgpr_model *h, uint64_t *angles, uint64_t *coord, int64_t *info)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_adf_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.adf.every) return fail(SGPR_E_INVALID, "sgpr_md_adf_read: call sgpr_md_begin and sgpr_md_adf first");
+    const MdRun::Adf &a = m.run.adf;
+    const int S = a.S, bins = a.bins;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (angles) {
+        HIPCHK(hipMemcpy(angles, m.adf.angles.p, sizeof(uint64_t) * (size_t)S * S * S * bins, hipMemcpyDeviceToHost));
+        for (int c = 0; c < S; c++)
+            for (int p = 0; p < S; p++)
+                for (int q = 0; q < p; q++)
+                    for (int k = 0; k < bins; k++) angles[(((size_t)c * S + p) * S + q) * bins + k] = angles[(((size_t)c * S + q) * S + p) * bins + k];
+    }
+    if (coord) HIPCHK(hipMemcpy(coord, m.adf.coord.p, sizeof(uint64_t) * (size_t)S * S * ADF_MAXCOORD, hipMemcpyDeviceToHost));
+    if (info) {
+        long long ctl[2];
+        std::vector<int> nz(S);
+        HIPCHK(hipMemcpy(ctl, m.adf.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nz.data(), m.adf.tab.p + (size_t)3 * a.nch, sizeof(int) * S, hipMemcpyDeviceToHost));
+        info[0] = ctl[1]; info[1] = ctl[0]; info[2] = bins; info[3] = S;
+        for (int z = 0; z < S; z++) info[4 + z] = nz[z];
+    }
+    return SGPR_OK;
+}
+
 // Deviates of the integrator on the device: seed != 0 makes sgpr_md_run (called with noise = NULL) draw the standard
 // normal deviate of (configuration index, atom, component) from a counter-based generator; 0 switches that off.
 extern "C" int sgpr_md_seed(sgpr_model *h, uint64_t seed)
@@ -2732,6 +2899,11 @@ extern "C" int sgpr_md_end(sgpr_model *h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         m.vh = MdState::VanHoveBufs();
+    }
+    if (m.adf.held()) {   // (and the tables of the bond angles)
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        m.adf = MdState::AdfBufs();
     }
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;

@@ -1264,6 +1264,55 @@ class SGPRModel:
         tab["self"] = hs
         return tab
 
+    def md_adf(self, every, bins=180, cutoffs=None):
+        """Accumulate bond-angle and coordination distributions inside the loop (sgpr_md_adf; md_adf.inc has the scheme,
+        workloads.AdfCounts is the host twin and the definition; all entries are counts, the two are equal).  `cutoffs`: the bond
+        cutoffs, a scalar (all pairs) or a dict {(Z1, Z2): r} over the model's species (pairs that are absent never bond), each
+        at most the model's cutoff.  Behind the evaluation of every configuration n with n % every == 0, for every centre the
+        angles between all pairs of its neighbours within the cutoffs — periodic images and self-images included, read from the
+        neighbour list the step has just built — are counted into `bins` bins over [0, pi] per (centre, end, end) of species, and
+        its number of neighbours per species into 64 bins (the last: 63 and above).  After md_begin, before the first md_run;
+        every = 0 detaches and frees.  md_adf_table() reads the tables; transport.angle_distribution and transport.coordination
+        form P(theta) and P(n).  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=,
+        ml_filter=, md_meta, md_record, md_msd, md_rdf, md_vacf and md_vanhove; a barostat, a committee, a relaxation, a band, a
+        polymer, several ranks and a cutoff beyond the model's: NotImplementedError."""
+        from .workloads import adf_cutoffs, adf_edges
+        lib = _lib.load()
+        if not every:
+            check(lib.sgpr_md_adf(self._h, 0, 0, None, None))
+            self._md["adf"] = None
+            return
+        if cutoffs is None:
+            raise ValueError("md_adf: cutoffs= (a scalar or {(Z1, Z2): r}) says which pairs bond")
+        species = [int(z) for z in self.species]
+        cut = np.ascontiguousarray(adf_cutoffs(cutoffs, species), dtype=np.float64)
+        if cut.shape != (len(species), len(species)):
+            raise ValueError(f"md_adf: the cutoff table is [{len(species)}, {len(species)}] over the model's species")
+        if not 1 <= int(bins) <= 1024:
+            raise ValueError("md_adf: 1 <= bins <= 1024")
+        ct = np.ascontiguousarray(adf_edges(bins), dtype=np.float64)
+        try:
+            check(lib.sgpr_md_adf(self._h, int(every), int(bins), ptr(cut), ptr(ct)))
+        except _lib.SgprError as e:
+            if e.code == -6:   # SGPR_E_UNSUPPORTED
+                raise NotImplementedError(str(e)) from None
+            raise
+        self._md["adf"] = (int(every), int(bins), cut)
+
+    def md_adf_table(self):
+        """The tables of md_adf as they stand (sgpr_md_adf_read; between two md_run calls): dict(angles [S, S, S, bins] uint64 the
+        counts per (centre, end, end) of species slots (symmetric in the ends), coord [S, S, 64] uint64 per (centre, neighbour)
+        the centres with n neighbours, species [S] the model's table, n [S] its atoms in the frame, samples, next_due, every,
+        bins, cut [S, S])."""
+        if not self._md.get("adf"):
+            raise RuntimeError("md_adf_table: no accumulator on this run (md_adf)")
+        every, bins, cut = self._md["adf"]
+        S = len(self.species)
+        angles, coord, info = np.zeros((S, S, S, bins), dtype=np.uint64), np.zeros((S, S, 64), dtype=np.uint64), np.zeros(4 + S, dtype=np.int64)
+        check(_lib.load().sgpr_md_adf_read(self._h, ptr(angles), ptr(coord), ptr(info)))
+        return dict(angles=angles, coord=coord, species=np.array([int(z) for z in self.species]), n=info[4:].copy(), samples=int(info[0]),
+                    next_due=int(info[1]), every=every, bins=int(info[2]), cut=cut.copy())
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

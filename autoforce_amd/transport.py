@@ -9,7 +9,9 @@ level's windows, and of their squares; the windows of a level do not overlap, so
 `vibrational_dos` read a diffusion constant, the species' current correlations and a density of states off them.
   And the distributions behind the moments: `VanHove` holds the displacement and pair histograms per lag of SGPRModel.md_vanhove /
 workloads.VanHoveCounts; `displacement_histogram` is the return of analysis.py:178-210 (`hist_rtp_displacements`), `self_van_hove`,
-`distinct_van_hove` and `non_gaussian` form G_s(r, t), G_d(r, t) and alpha_2(t)."""
+`distinct_van_hove` and `non_gaussian` form G_s(r, t), G_d(r, t) and alpha_2(t).
+  And the three-body structure: `Adf` holds the bond-angle and coordination counts of SGPRModel.md_adf / workloads.AdfCounts (the
+reference has no angular analysis); `angle_distribution` and `coordination` form P(theta) and P(n) per species."""
 import numpy as np
 
 KEYS = ("msd", "msd_sq", "smd", "smd_sq")
@@ -142,6 +144,81 @@ def radial_distribution(rdf, shells=False):
         a, b = slot[za], slot[zb]
         g[(za, zb)] = rdf.hist[a, b].astype(float) / (rdf.samples * float(rdf.n[a]) * shell * (float(rdf.n[b]) / rdf.volume))
     return r, g
+
+
+class Adf:
+    """Holder of bond-angle and coordination counts: ActiveCalculator.run_md(adf=Adf(every, bins, cutoffs)) fills it, as rdf= fills
+    an Rdf; `cutoffs` is a scalar (all pairs) or a dict {(Z1, Z2): r} of bond cutoffs (pairs that are absent never bond).
+    add(table) adds the tables of a run (SGPRModel.md_adf_table(), AdfCounts.table()) — those of several runs of one frame with
+    the same settings add up, count by count.  angle_distribution(holder, ...) and coordination(holder, ...) read it."""
+
+    def __init__(self, every, bins=180, cutoffs=None):
+        if cutoffs is None:
+            raise ValueError("Adf: cutoffs= (a scalar or {(Z1, Z2): r}) says which pairs bond")
+        self.every, self.bins, self.cutoffs = int(every), int(bins), cutoffs
+        self.samples = 0
+        self.angles = self.coord = self.species = self.n = self.cut = None
+
+    def add(self, table):
+        if int(table["bins"]) != self.bins:
+            raise ValueError("Adf.add: the table was taken with other settings (bins)")
+        species, n, cut = np.asarray(table["species"]), np.asarray(table["n"]), np.asarray(table["cut"], float)
+        if self.species is None:
+            self.species, self.n, self.cut = species.copy(), n.copy(), cut.copy()
+            self.angles = np.zeros((len(species),) * 3 + (self.bins,), dtype=np.uint64)
+            self.coord = np.zeros((len(species), len(species), np.asarray(table["coord"]).shape[-1]), dtype=np.uint64)
+        elif not (np.array_equal(species, self.species) and np.array_equal(n, self.n) and np.array_equal(cut, self.cut)):
+            raise ValueError("Adf.add: the table is of another frame or other cutoffs (species, atoms per species, cut)")
+        self.angles = self.angles + np.asarray(table["angles"], dtype=np.uint64)
+        self.coord = self.coord + np.asarray(table["coord"], dtype=np.uint64)
+        self.samples += int(table["samples"])
+        return self
+
+    def table(self):
+        return dict(angles=self.angles.copy(), coord=self.coord.copy(), species=self.species, n=self.n, samples=self.samples,
+                    next_due=self.samples * self.every, every=self.every, bins=self.bins, cut=self.cut)
+
+
+def _adf_slot(table, z, what):
+    species = [int(s) for s in table["species"]]
+    if int(z) not in species:
+        raise ValueError(f"{what}: no species {z} in the table ({species})")
+    return species.index(int(z))
+
+
+def angle_distribution(table, centre, ends, degrees=True, solid_angle=False):
+    """(theta [bins], P [bins]) of the angles end-centre-end from an Adf holder or a table (md_adf_table(), AdfCounts.table()):
+    centre an atomic number, ends a pair of them (either order).  theta: the centres of the bins [k pi / bins, (k + 1) pi / bins),
+    in degrees or radians; P(theta) normalised to unit area over that axis.  solid_angle=True: the counts divided by sin(theta)
+    first — the density per solid angle, flat for directions without correlation — then normalised the same way."""
+    t = table.table() if hasattr(table, "table") else table
+    a = _adf_slot(t, centre, "angle_distribution")
+    b, c = (_adf_slot(t, z, "angle_distribution") for z in ends)
+    bins = int(t["bins"])
+    h = np.asarray(t["angles"])[a, b, c].astype(float)
+    th = (np.arange(bins) + 0.5) * np.pi / bins
+    if solid_angle:
+        h = h / np.sin(th)
+    axis = np.degrees(th) if degrees else th
+    width = (180.0 if degrees else np.pi) / bins
+    total = h.sum() * width
+    if not total > 0.0:
+        raise ValueError("angle_distribution: no angle was counted for these species")
+    return axis, h / total
+
+
+def coordination(table, centre, neighbour):
+    """(n [M], P [M], mean) of the number of neighbours of species `neighbour` around the centres of species `centre` (atomic
+    numbers) from an Adf holder or a table: P(n) over the sampled centres; the last entry, n = M - 1 = 63, stands for that many
+    and more (the mean takes it as 63)."""
+    t = table.table() if hasattr(table, "table") else table
+    a, b = _adf_slot(t, centre, "coordination"), _adf_slot(t, neighbour, "coordination")
+    c = np.asarray(t["coord"])[a, b].astype(float)
+    if not c.sum() > 0.0:
+        raise ValueError("coordination: no centre of this species was sampled")
+    n = np.arange(len(c))
+    P = c / c.sum()
+    return n, P, float(np.sum(n * P))
 
 
 class Vacf:

@@ -2055,6 +2055,142 @@ class RdfCounts:
                     every=self.every, bins=self.bins, rmin=self.rmin, rmax=self.rmax, volume=self.volume)
 
 
+ADF_MAXCOORD = 64    # coordination numbers 0 ... 62, and 63 and above (md_adf.inc)
+ADF_MAXBINS = 1024
+
+
+def adf_edges(bins):
+    """The edges of the angle bins as the comparisons take them: ct [bins] = cos(e pi / bins) (entry 0 is never compared).  Made
+    here once, with numpy; SGPRModel.md_adf uploads these doubles and AdfCounts compares with the same ones."""
+    return np.cos(np.arange(int(bins), dtype=float) * np.pi / float(bins))
+
+
+def adf_cutoffs(cutoffs, species):
+    """The table cut [S, S] over the slots of `species` from a scalar (all pairs) or a dict {(Z1, Z2): r} (either order; pairs
+    that are absent never bond: 0)."""
+    S = len(species)
+    if isinstance(cutoffs, dict):
+        slot = {int(z): k for k, z in enumerate(species)}
+        cut = np.zeros((S, S))
+        for (z1, z2), r in cutoffs.items():
+            if int(z1) not in slot or int(z2) not in slot:
+                raise ValueError(f"adf_cutoffs: the pair ({z1}, {z2}) names a species outside the model's table {list(species)}")
+            a, b = slot[int(z1)], slot[int(z2)]
+            if (int(z2), int(z1)) in cutoffs and float(cutoffs[(int(z2), int(z1))]) != float(r):
+                raise ValueError(f"adf_cutoffs: ({z1}, {z2}) and ({z2}, {z1}) differ")
+            cut[a, b] = cut[b, a] = float(r)
+        return cut
+    cut = np.array(cutoffs, dtype=float)
+    return np.full((S, S), float(cut)) if cut.ndim == 0 else cut.reshape(S, S).copy()
+
+
+class AdfCounts:
+    """Bond-angle and coordination distributions per species triple — the host twin of the accumulator inside the device loop
+    (SGPRModel.md_adf, md_adf.inc) and its definition (the reference has no angular analysis); all entries are integer counts,
+    so the two sets of tables are equal.
+      add(x) is fed the configurations 0, 1, 2, ... of a run ([N, 3], caller atom order, wrapped or not); those with n % every
+    == 0 are samples.  cut [S, S] is the symmetric table of bond cutoffs over the slots of `species` (the model's table; 0: the
+    pair never bonds).  For a sample and a centre i of species a, its neighbours are all (j of species b, s in Z^3) with (j, s)
+    != (i, 0) — periodic self-images and several images of one atom are distinct neighbours — and
+        d = (x_j - x_i) + ((s0 h0 + s1 h1) + s2 h2),  r = sqrt((d0 d0 + d1 d1) + d2 d2),  r < cut[a, b]
+    with s = 0 along an open direction, enumerated as RdfCounts does: nearest image by rint, then the block |t_k| <= R_k for the
+    largest cutoff.  For every unordered pair {t, t'} of distinct neighbours, species b <= c after ordering,
+        q = (d_t0 d_t'0 + d_t1 d_t'1) + d_t2 d_t'2,  p = r_t r_t',  k = #{e in 1 ... bins - 1 : q <= ct[e] p},  angles[a, b, c, k] += 1
+    with ct = adf_edges(bins): no arccos, no division (bin k holds the angles in [k pi / bins, (k + 1) pi / bins): an angle on
+    an edge belongs to the bin above it).  And for every species b, n_ib the neighbours of i of species b:
+    coord[a, b, min(n_ib, ADF_MAXCOORD - 1)] += 1.  table() fills angles[a, c, b] = angles[a, b, c]."""
+
+    def __init__(self, every, bins, cut, numbers, species, cell, pbc, ct=None):
+        if every < 1 or not 1 <= bins <= ADF_MAXBINS:
+            raise ValueError(f"AdfCounts: every >= 1, 1 <= bins <= {ADF_MAXBINS}")
+        self.every, self.bins = int(every), int(bins)
+        self.species = [int(z) for z in species]
+        S = len(self.species)
+        self.cut = adf_cutoffs(cut, self.species)
+        if not (np.all(self.cut >= 0.0) and np.all(np.isfinite(self.cut)) and np.array_equal(self.cut, self.cut.T)):
+            raise ValueError("AdfCounts: the cutoff table must be symmetric and >= 0")
+        if not self.cut.max() > 0.0:
+            raise ValueError("AdfCounts: every cutoff is 0: no pair bonds")
+        self.ct = adf_edges(self.bins) if ct is None else np.asarray(ct, float).copy()
+        self.h = np.asarray(cell, float).reshape(3, 3).copy()
+        self.pbc = np.broadcast_to(np.asarray(pbc, bool), (3,)).copy()
+        if self.pbc.any():
+            # (an open direction of a cell without volume: any vector that gives one serves, it is never a shift)
+            self.inv, _, self.heights, self.R = rdf_geometry(self.h, self.pbc, float(self.cut.max()))
+        else:
+            self.inv, self.R = np.zeros((3, 3)), np.zeros(3, dtype=int)
+        for k in range(3):
+            if self.R[k] > 127:
+                raise NotImplementedError(f"AdfCounts: a cutoff of {self.cut.max():g} needs images {self.R[k]} cells away along direction {k}")
+        self.block = np.array([[float(t0), float(t1), float(t2)] for t0 in range(-self.R[0], self.R[0] + 1)
+                               for t1 in range(-self.R[1], self.R[1] + 1) for t2 in range(-self.R[2], self.R[2] + 1)])
+        self.block0 = int(np.flatnonzero(np.all(self.block == 0.0, axis=1))[0])
+        numbers = np.asarray(numbers)
+        self.slot = np.full(len(numbers), -1)
+        for k, z in enumerate(self.species):
+            self.slot[numbers == z] = k
+        if (self.slot < 0).any():
+            raise ValueError("AdfCounts: an atom's species is not in the table")
+        self.nz = np.array([int(np.sum(self.slot == k)) for k in range(S)])
+        self.angles = np.zeros((S, S, S, self.bins), dtype=np.uint64)   # b <= c filled
+        self.coord = np.zeros((S, S, ADF_MAXCOORD), dtype=np.uint64)
+        self.n = 0   # configurations seen
+
+    def neighbours(self, x, i):
+        """(d [T, 3], r [T], b [T]) of centre i in the configuration x: the definition's neighbours, in the order (image, atom)."""
+        h, inv, a = self.h, self.inv, self.slot[i]
+        dx = x - x[i]
+        dx0, dx1, dx2 = dx[:, 0], dx[:, 1], dx[:, 2]
+        n = [np.rint((dx0 * inv[0, k] + dx1 * inv[1, k]) + dx2 * inv[2, k]) if self.pbc[k] else np.zeros_like(dx0) for k in range(3)]
+        cutj = self.cut[a][self.slot]
+        # the block of images, all at once: t [M, 1] against the atoms [N]
+        t = self.block
+        s0, s1, s2 = t[:, 0:1] - n[0][None, :], t[:, 1:2] - n[1][None, :], t[:, 2:3] - n[2][None, :]
+        d0 = dx0[None, :] + ((s0 * h[0, 0] + s1 * h[1, 0]) + s2 * h[2, 0])
+        d1 = dx1[None, :] + ((s0 * h[0, 1] + s1 * h[1, 1]) + s2 * h[2, 1])
+        d2 = dx2[None, :] + ((s0 * h[0, 2] + s1 * h[1, 2]) + s2 * h[2, 2])
+        r = np.sqrt((d0 * d0 + d1 * d1) + d2 * d2)
+        ok = r < cutj[None, :]
+        ok[self.block0, i] = False   # (i, 0) is the centre itself
+        return np.stack([d0[ok], d1[ok], d2[ok]], axis=1), r[ok], np.broadcast_to(self.slot[None, :], ok.shape)[ok]
+
+    def add(self, positions):
+        """The next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        x = np.asarray(positions, float).reshape(-1, 3)
+        S, bins, edges = len(self.species), self.bins, self.ct[1:]
+        for i in range(len(x)):
+            a = self.slot[i]
+            d, r, b = self.neighbours(x, i)
+            nib = np.bincount(b, minlength=S)
+            for s in range(S):
+                self.coord[a, s, min(int(nib[s]), ADF_MAXCOORD - 1)] += np.uint64(1)
+            if len(r) < 2:
+                continue
+            t, u = np.triu_indices(len(r), 1)
+            q = (d[t, 0] * d[u, 0] + d[t, 1] * d[u, 1]) + d[t, 2] * d[u, 2]
+            p = r[t] * r[u]
+            k = np.zeros(len(q), dtype=np.int64)
+            for o in range(0, len(q), 4096):   # (the linear count, a block of pairs at a time)
+                k[o:o + 4096] = np.sum(q[o:o + 4096, None] <= edges[None, :] * p[o:o + 4096, None], axis=1)
+            lo, hi = np.minimum(b[t], b[u]), np.maximum(b[t], b[u])
+            flat = np.bincount((lo * S + hi) * bins + k, minlength=S * S * bins).astype(np.uint64)
+            self.angles[a] += flat.reshape(S, S, bins)
+
+    def table(self):
+        """What SGPRModel.md_adf_table returns."""
+        samples = -(-self.n // self.every)
+        angles = self.angles.copy()
+        for b in range(len(self.species)):
+            for c in range(b):
+                angles[:, b, c] = angles[:, c, b]
+        return dict(angles=angles, coord=self.coord.copy(), species=np.array(self.species), n=self.nz.copy(), samples=samples,
+                    next_due=samples * self.every, every=self.every, bins=self.bins, cut=self.cut.copy())
+
+
 VH_MAXRBINS = 2048   # radial bins of the self part (md_vanhove.inc)
 VH_MAXABINS = 64     # polar and azimuthal bins: the edge tables sit in LDS
 VH_MAXBYTES = 1 << 30   # the self table levels S rbins tbins pbins 8 B

@@ -677,6 +677,39 @@ int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax, int rbins
 int sgpr_md_vanhove_edges(sgpr_model *h, const double *ct, const double *cu, const double *su);
 int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t *over, uint64_t *distinct_hist, int64_t *counts, int64_t *info,
                          double *geom);
+/* Bond-angle and coordination distributions accumulated inside the loop: the three-body structure of the run (is a tetrahedron
+ * intact, which corners do two share, how many neighbours sit around an ion), as integers in device memory.  The reference has
+ * no angular analysis; workloads.AdfCounts is the definition.  cut[S][S] is a symmetric table of bond cutoffs over the species
+ * slots of the model's table (0: the pair never bonds).  Behind the evaluation of every configuration n with n % every == 0, for
+ * every centre i of species a, its neighbours are all (j of species b, s in Z^3) with (j, s) != (i, 0) and
+ *     d = (x_j - x_i) + ((s0 h0 + s1 h1) + s2 h2),  r = sqrt((d0 d0 + d1 d1) + d2 d2),  r < cut[a][b]
+ * (s = 0 along an open direction; periodic self-images and several images of one atom are distinct neighbours).  For every
+ * unordered pair {t, t'} of them, with species b <= c after ordering,
+ *     q = (d_t0 d_t'0 + d_t1 d_t'1) + d_t2 d_t'2,  p = r_t r_t',  k = the number of e in 1 ... bins - 1 with q <= ct[e] p,
+ * and angles[a][b][c][k] gains 1: bin k holds the angles in [k pi / bins, (k + 1) pi / bins), decided by comparisons with the
+ * caller's ct[e] = cos(e pi / bins), never by acos.  With n_ib the neighbours of species b, coord[a][b][min(n_ib, 63)] gains 1.
+ * The neighbours are read from the neighbour list the step has just built: the cost is linear in the number of atoms.  Integer
+ * counts: the tables are the same bits however the run is cut; a configuration evaluated twice (the repeat behind a covloss halt
+ * or an overflow) counts once — behind an overflow (halt code 2: its list was clamped) the repeat is the one that counts —, the
+ * speculative evaluation behind a halt not at all.
+ *
+ * sgpr_md_adf       every >= 1, 1 <= bins <= 1024, cut[S * S], ct[bins] (entry 0 is never compared): after sgpr_md_begin (and
+ *                   sgpr_md_fix, _thermostat, _filter, _meta, _record, _msd, _rdf, _vacf, _vanhove, if used), before the first
+ *                   sgpr_md_run; zeroes the tables.  every = 0 detaches and frees them: the run launches what it launched
+ *                   before.  Two launches behind a sampled evaluation.  SGPR_E_INVALID: no run begun, a run that has started,
+ *                   values out of range, a table that is asymmetric, negative or all zero, edges that increase, atoms not
+ *                   sorted by the model's species.  SGPR_E_UNSUPPORTED: a cutoff above the model's rc (the list holds nothing
+ *                   beyond it), several ranks, a barostat, a committee, a relaxation, a band, a polymer — and from
+ *                   sgpr_md_barostat, _committee, _relax, _neb and _pimd on a run that has the accumulator.  sgpr_md_run
+ *                   answers SGPR_E_UNSUPPORTED for a step form that does not end in the gather form of the fused last kernel
+ *                   (the forms a qlvar bias refuses) and for a neighbour list so long that one centre's neighbours do not fit
+ *                   the LDS of a workgroup.
+ * sgpr_md_adf_read  between two calls of the run (synchronises the stream): angles[S][S][S][bins] (symmetric in the two ends,
+ *                   filled out), coord[S][S][64], info[4 + S] = samples taken, the configuration the tables wait for next, bins,
+ *                   S, the atoms of every species in the frame.  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut, const double *ct);
+int sgpr_md_adf_read(sgpr_model *h, uint64_t *angles, uint64_t *coord, int64_t *info);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the
