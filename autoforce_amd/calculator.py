@@ -636,19 +636,18 @@ class ActiveCalculator(Calculator):
         model's); with a committee or several ranks, and in the host loops, workloads.AdfCounts — the same integers — is fed the
         positions of every step.  The cell is constant: with a barostat NotImplementedError."""
         from .ase_shim import kB
-        from .workloads import FS, MASS, AdfCounts, FilterState, MsdBlocks, RdfCounts, VacfRing, VanHoveCounts, langevin_nvt, nose_hoover_nvt, npt_moving_cell
+        from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
         filt = {} if flt is None else dict(ml_filter=flt.shrink, filter_init=(flt.f, flt.s))
         nh = tdamp_fs is not None
         npt = pfactor is not None
         if npt and not nh:
             raise ValueError("run_md: a barostat (pfactor) needs the Nose-Hoover thermostat (tdamp_fs)")
-        if npt and rdf is not None:
-            raise NotImplementedError("run_md: rdf= with a barostat (pfactor): pair distances are counted at constant cell")
-        if npt and vanhove is not None:
-            raise NotImplementedError("run_md: vanhove= with a barostat (pfactor): displacements and pair distances are counted at constant cell")
-        if npt and adf is not None:
-            raise NotImplementedError("run_md: adf= with a barostat (pfactor): bond angles are counted at constant cell")
+        # the holders given, by keyword, driven through the face they share (transport._InLoop)
+        holders = {k: a for k, a in dict(msd=msd, rdf=rdf, vacf=vacf, vanhove=vanhove, adf=adf).items() if a is not None}
+        for k, a in holders.items():
+            if npt and a.constant_cell:
+                raise NotImplementedError(f"run_md: {k}= with a barostat (pfactor): {a.constant_cell} at constant cell")
         baro = dict(pfactor=pfactor, externalstress=externalstress, mask=mask, iso=iso) if npt else {}
 
         fx = held(self.constraint_mask(atoms))
@@ -682,11 +681,7 @@ class ActiveCalculator(Calculator):
             return (self.md_on_device_ok() and not (committee and fx is not None)
                     and not (flt is not None and (committee or self._dist()[1] > 1))
                     and not (self.meta is not None and (npt or committee or self._dist()[1] > 1))
-                    and not (msd is not None and (npt or committee or self._dist()[1] > 1))
-                    and not (rdf is not None and (committee or self._dist()[1] > 1))
-                    and not (vacf is not None and (npt or committee or self._dist()[1] > 1 or flt is not None or self.meta is not None))
-                    and not (vanhove is not None and (committee or self._dist()[1] > 1))
-                    and not (adf is not None and (committee or self._dist()[1] > 1)))
+                    and not any(a.host_only(npt, committee, self._dist()[1], flt is not None, self.meta is not None) for a in holders.values()))
         seeded = self._needs_seed() or not on_device()
         if npt:
             # (NPT.__init__ removes the mean momentum before anything is evaluated: a first calculate() on the host sees — and
@@ -699,44 +694,19 @@ class ActiveCalculator(Calculator):
                 loop = (npt_moving_cell(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **baro, **filt) if npt else
                         nose_hoover_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, tdamp_fs, vel=vel, **hold, **filt) if nh else
                         langevin_nvt(self, numbers, pos, cell, pbc, steps, temperature_K, dt_fs, friction, vel=vel, rng=rng, **hold, **filt))
-                blocks = None if msd is None else MsdBlocks(msd.every, msd.levels, msd.com, masses, numbers,
-                                                            getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
-                counts = None if rdf is None else RdfCounts(rdf.every, rdf.rmax, rdf.bins, rdf.rmin, numbers,
-                                                            getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
-                corr = None if vacf is None else VacfRing(vacf.every, vacf.nlags, vacf.origin_every, vacf.com, masses, numbers,
-                                                          getattr(self.engine, "species", sorted(set(int(z) for z in numbers))))
-                hove = None if vanhove is None else VanHoveCounts(vanhove.every, vanhove.levels, vanhove.rmax, vanhove.rbins, vanhove.tbins,
-                                                                  vanhove.pbins, vanhove.dmax, vanhove.dbins, numbers,
-                                                                  getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
-                bonds = None if adf is None else AdfCounts(adf.every, adf.bins, adf.cutoffs, numbers,
-                                                           getattr(self.engine, "species", sorted(set(int(z) for z in numbers))), cell, pbc)
+                species = getattr(self.engine, "species", sorted(set(int(z) for z in numbers)))
+                twins = [(a, a.twin(masses, numbers, species, cell, pbc)) for a in holders.values()]
                 for st, E, T, _, p, v, *rest in loop:
-                    if blocks is not None:
-                        blocks.add(p)
-                    if bonds is not None:
-                        bonds.add(p)
-                    if hove is not None:
-                        hove.add(p)
-                    if corr is not None:
-                        corr.add(v)
-                    if counts is not None:
-                        counts.add(p)
+                    for a, twin in twins:
+                        twin.add(v if a.feeds == "velocities" else p)
                     if hasattr(self.meta, "update"):   # (the reference's dyn.attach(meta.update): calculate() has added the bias)
                         self.meta.update()
                     put_state(atoms, dict(positions=p, velocities=v, cell=rest[0] if npt else None), npt, "velocities")
                     if flt is not None:   # (the accumulators as this configuration found them: what a run that goes on from it takes)
                         flt.f, flt.s = rest[-1]
                     yield st, E, T, bool(self.updated), _
-                if blocks is not None:
-                    msd.add(blocks.table())
-                if counts is not None:
-                    rdf.add(counts.table())
-                if corr is not None:
-                    vacf.add(corr.table())
-                if hove is not None:
-                    vanhove.add(hove.table())
-                if bonds is not None:
-                    adf.add(bonds.table())
+                for a, twin in twins:
+                    a.add(twin.table())
                 return
         eng = self.engine
         kT, dof_kB = kB * temperature_K, dof * kB
@@ -744,16 +714,8 @@ class ActiveCalculator(Calculator):
         eng.md_begin(numbers, pos, cell, pbc, masses, vel, dt=dt_fs * FS, friction=0.0 if nh else friction, kT=kT,
                      seed=(int(seed) or 1) if on_device_rng else 0, ttime=tdamp_fs * FS if nh else None, **baro, **hold, **filt)
         attached = self._md_attach(eng)
-        if msd is not None:
-            eng.md_msd(msd.every, msd.levels, msd.com)
-        if rdf is not None:
-            eng.md_rdf(rdf.every, rdf.rmax, rdf.bins, rdf.rmin)
-        if vacf is not None:
-            eng.md_vacf(vacf.every, vacf.nlags, vacf.origin_every, vacf.com)
-        if vanhove is not None:
-            eng.md_vanhove(vanhove.every, vanhove.levels, vanhove.rmax, vanhove.rbins, vanhove.tbins, vanhove.pbins, vanhove.dmax, vanhove.dbins)
-        if adf is not None:
-            eng.md_adf(adf.every, adf.bins, adf.cutoffs)
+        for a in holders.values():
+            a.attach(eng)
         meta, meta_V = self.meta, {}
         if meta is not None:
             # the bias inside the loop: the hills the Meta holds stand from the start, room for every deposit of the run; after
@@ -837,16 +799,8 @@ class ActiveCalculator(Calculator):
         put_state(atoms, eng.md_state(results=True), npt, "velocities")
         if flt is not None:
             flt.f, flt.s = eng.md_filter_state()
-        if msd is not None:
-            msd.add(eng.md_msd_table())
-        if rdf is not None:
-            rdf.add(eng.md_rdf_table())
-        if vacf is not None:
-            vacf.add(eng.md_vacf_table())
-        if vanhove is not None:
-            vanhove.add(eng.md_vanhove_table())
-        if adf is not None:
-            adf.add(eng.md_adf_table())
+        for a in holders.values():
+            a.add(a.read(eng))
         if attached:
             self._md_attached_done(eng, attached)
 

@@ -280,15 +280,17 @@ struct MdRun {
         long long call_t0 = 0;
         int call_every = 0, call_what = 0, call_count = 0;
     } rec;
+    // The accumulators (MD_ACC, md_host.inc, has one row for each, in this order).  nz: the atoms of every species in the frame, which
+    // the *_read functions report.
     // the mean-square displacements (sgpr_md_msd, md_msd.inc): every `every`-th configuration is a sample, `levels` lags in
     // powers of two; nch chunks of one species each, S species of the model's table, the frame's total mass
     struct Msd { int every = 0, levels = 0, com = 0, nch = 0, S = 0; double mtot = 0.0; } msd;
     // the radial distribution functions (sgpr_md_rdf, md_rdf.inc): every `every`-th configuration is a sample; npairs tile pairs of
     // one species pair each, S species of the model's table, the constant cell with its image block, its volume
-    struct Rdf { int every = 0, npairs = 0, split = 1, S = 0; bool images = false; RdfGeom g = {}; double volume = 0.0; } rdf;
+    struct Rdf { int every = 0, npairs = 0, split = 1, S = 0; bool images = false; RdfGeom g = {}; double volume = 0.0; std::vector<int> nz; } rdf;
     // the velocity autocorrelations (sgpr_md_vacf, md_vacf.inc): every `every`-th configuration is a sample, `lags` lags of one
     // sample each, origins every `origin_every`-th sample; nch chunks of one species each, S species, the frame's total mass
-    struct Vacf { int every = 0, lags = 0, origin_every = 1, com = 0, nch = 0, S = 0; double mtot = 0.0; } vacf;
+    struct Vacf { int every = 0, lags = 0, origin_every = 1, com = 0, nch = 0, S = 0; double mtot = 0.0; std::vector<int> nz; } vacf;
     // the van Hove functions (sgpr_md_vanhove, md_vanhove.inc): md_msd's samples and levels; the self part over rbins x tbins x
     // pbins bins up to rmax, nch chunks of one species each; the distinct part (dbins > 0) over npairs ORDERED tile pairs, tile J
     // cut into `split` parts, in the constant cell g (rmin = 0, rmax = dmax, bins = dbins) with its image block; the cell's volume
@@ -297,11 +299,12 @@ struct MdRun {
         bool images = false;
         RdfGeom g = {};
         double rmax = 0.0, dmax = 0.0, volume = 0.0;
+        std::vector<int> nz;
     } vh;
     // the bond-angle and coordination distributions (sgpr_md_adf, md_adf.inc): every `every`-th configuration is a sample; `bins`
     // angle bins per (centre, end, end) of the S species of the model's table, nch chunks of centres of one species each; lds: the
     // form with LDS counters
-    struct Adf { int every = 0, bins = 0, nch = 0, S = 0; bool lds = true; } adf;
+    struct Adf { int every = 0, bins = 0, nch = 0, S = 0; bool lds = true; std::vector<int> nz; } adf;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {

@@ -44,6 +44,138 @@ static int md_rebind(sgpr_model *h)
     return sgpr_bind_system(h, m.run.N, m.run.numbers.data(), m.run.pbc, m.run.rank, m.run.world);
 }
 
+// ---- the accumulators of the MD loop: one row each, in the order their launches follow an evaluation.  The attach functions
+// (md_acc_run | md_acc_unstarted | md_acc_modes), the modes that exclude them (md_acc_attached) and the run loop
+// (md_sample_due) read this table; a further accumulator adds a row, a sampler and its own attach body. ----
+static int md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st);
+static int md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st);
+static int md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st);
+static int md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st);
+static int md_adf_sample(sgpr_model *h, int j, int step, hipStream_t st);
+struct MdAcc {
+    const char *fn, *noun;      // the attach function; what it accumulates, as the messages name it
+    const char *moving_cell;    // why a barostat and the accumulator exclude each other
+    const char *polymer;        // what of a ring polymer it would have to sample: "... not sampled"
+    int (*every)(const MdRun &);
+    int (*sample)(sgpr_model *h, int j, int step, hipStream_t st);   // the launches behind evaluation j of a call
+};
+static const MdAcc MD_ACC[] = {
+    {"sgpr_md_msd", "displacements", "a displacement in a moving cell mixes in the strain", "centroid is",
+     [](const MdRun &r) { return r.msd.every; }, md_msd_sample},
+    {"sgpr_md_rdf", "pair distances", "the image block and the densities are those of a constant cell", "beads are",
+     [](const MdRun &r) { return r.rdf.every; }, md_rdf_sample},
+    {"sgpr_md_vacf", "velocity correlations", "velocities in a moving cell are not sampled", "centroid is",
+     [](const MdRun &r) { return r.vacf.every; }, md_vacf_sample},
+    {"sgpr_md_vanhove", "van Hove functions", "displacements and the image block are those of a constant cell", "beads are",
+     [](const MdRun &r) { return r.vh.every; }, md_vh_sample},
+    {"sgpr_md_adf", "bond angles", "the neighbours are read from the list of a constant cell", "beads are",
+     [](const MdRun &r) { return r.adf.every; }, md_adf_sample},
+};
+enum { MD_MSD, MD_RDF, MD_VACF, MD_VH, MD_ADF };
+
+// The first accumulator attached to the run (NULL: none): what a mode that excludes them refuses with.
+static const MdAcc *md_acc_attached(const MdRun &r)
+{
+    for (const MdAcc &a : MD_ACC)
+        if (a.every(r)) return &a;
+    return nullptr;
+}
+
+// The refusals every attach function shares, in three steps (an attach function puts its own argument checks between them where
+// a caller can tell the order): a handle with a run; a run that has not started; a run of no mode that excludes the accumulators.
+static int md_acc_run(const sgpr_model *h, const MdAcc &a)
+{
+    if (!h) return fail(SGPR_E_INVALID, "%s: bad arguments", a.fn);
+    if (!h->md.active) return fail(SGPR_E_INVALID, "%s: call sgpr_md_begin first", a.fn);
+    return SGPR_OK;
+}
+static int md_acc_unstarted(const sgpr_model *h, const MdAcc &a)
+{
+    if (h->md.run.t != 0 || h->md.run.started) return fail(SGPR_E_INVALID, "%s: the run has started", a.fn);
+    return SGPR_OK;
+}
+static int md_acc_modes(const sgpr_model *h, const MdAcc &a)
+{
+    const MdRun &r = h->md.run;
+    if (r.world > 1) return fail(SGPR_E_UNSUPPORTED, "%s: the run was begun on %d ranks; %s are accumulated on one", a.fn, r.world, a.noun);
+    if (r.npt.on) return fail(SGPR_E_UNSUPPORTED, "%s: the run has a barostat; %s", a.fn, a.moving_cell);
+    if (!r.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "%s: the run has a committee (sgpr_md_committee), whose loop does not sample %s", a.fn, a.noun);
+    if (r.relax.on) return fail(SGPR_E_UNSUPPORTED, "%s: the run is a relaxation; %s are accumulated over dynamics", a.fn, a.noun);
+    if (r.neb.on) return fail(SGPR_E_UNSUPPORTED, "%s: the run is a nudged elastic band; %s are accumulated over dynamics", a.fn, a.noun);
+    if (r.pimd.on) return fail(SGPR_E_UNSUPPORTED, "%s: the run is a ring polymer (sgpr_md_pimd); its %s not sampled", a.fn, a.polymer);
+    return SGPR_OK;
+}
+
+// Give a group of device buffers back, if it holds any: behind whatever the stream still runs, by a move-assign of the empty
+// group.  The memory goes whatever the wait says.
+template <typename Bufs>
+static int md_release(sgpr_model *h, Bufs &b)
+{
+    if (!b.held()) return SGPR_OK;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    b = Bufs();
+    return e == hipSuccess ? SGPR_OK : fail(SGPR_E_NODEVICE, "md_release: %s", hipGetErrorString(e));
+}
+
+// The run's sorted atoms by species of the model's table (the sort is by species in table order; anything else is `who`'s
+// failure): nz[z] atoms from first[z] on.  With width > 0 also the chunks — runs of at most `width` consecutive atoms of one
+// species, one record (first atom, atoms[, species]) each in `tab`; coff[z] ... coff[z + 1]: the chunks of species z.
+struct MdSpecies {
+    std::vector<int> nz, first, coff, tab;
+    int nch = 0;
+};
+static int md_species_chunks(const sgpr_model *h, const char *who, int width, bool with_species, MdSpecies &s)
+{
+    const MdRun &r = h->md.run;
+    const int S = h->S;
+    s.nz.assign(S, 0); s.first.assign(S, 0); s.coff.assign(S + 1, 0);
+    for (int i = 0, last = 0; i < r.N; i++) {
+        int z = 0;
+        while (z < S && h->species[z] != r.numbers[r.perm[i]]) z++;
+        if (z == S || z < last) return fail(SGPR_E_INVALID, "%s: the run's atoms are not sorted by the model's species", who);
+        last = z; s.nz[z]++;
+    }
+    for (int z = 1; z < S; z++) s.first[z] = s.first[z - 1] + s.nz[z - 1];
+    for (int z = 0; z < S; z++) {
+        for (int o = 0; width > 0 && o < s.nz[z]; o += width, s.nch++) {
+            s.tab.push_back(s.first[z] + o); s.tab.push_back(std::min(width, s.nz[z] - o));
+            if (with_species) s.tab.push_back(z);
+        }
+        s.coff[z + 1] = s.nch;
+    }
+    return SGPR_OK;
+}
+
+// The tile pairs of a pair sweep, RDF_PAIR ints each, appended to `tab`: tiles are runs of at most RDF_TILE atoms of one species;
+// ordered: every ordered pair of tiles, weight 1 (the distinct part of the van Hove functions); else the pairs I <= J, an
+// off-diagonal pair of one species with weight 2 (the radial distributions).  Returns the number of pairs.
+static int md_tile_pairs(const std::vector<int> &nz, const std::vector<int> &first, bool ordered, std::vector<int> &tab)
+{
+    const int S = (int)nz.size();
+    int npairs = 0;
+    for (int a = 0; a < S; a++)
+        for (int oa = 0; oa < nz[a]; oa += RDF_TILE)
+            for (int b = ordered ? 0 : a; b < S; b++)
+                for (int ob = (!ordered && b == a) ? oa : 0; ob < nz[b]; ob += RDF_TILE, npairs++) {
+                    const int rec[RDF_PAIR] = {first[a] + oa, std::min(RDF_TILE, nz[a] - oa), first[b] + ob, std::min(RDF_TILE, nz[b] - ob),
+                                               a * S + b, (!ordered && a == b && ob != oa) ? 2 : 1};
+                    tab.insert(tab.end(), rec, rec + RDF_PAIR);
+                }
+    return npairs;
+}
+
+// The levels of md_msd's scheme that sample s closes (level l: lag 2^l samples, due when 2^l divides s), as a mask; *ndue:
+// how many.
+static unsigned md_due_levels(long long s, int levels, int *ndue)
+{
+    unsigned due = 0;
+    int n = 0;
+    for (int l = 0; l < levels && (s & ((1ll << l) - 1)) == 0; l++, n++) due |= 1u << l;
+    if (ndue) *ndue = n;
+    return due;
+}
+
 extern "C" int sgpr_md_begin(sgpr_model *h, int N, const int32_t *numbers, const double *positions, const double *cell,
                              const int32_t *pbc, const double *masses, const double *velocities, double dt,
                              double friction, double kT)
@@ -188,11 +320,7 @@ extern "C" int sgpr_md_barostat(sgpr_model *h, double pfactor, const double *ext
                     "md_committee_cell is set (sgpr_set_option)");
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run has a bias (sgpr_md_meta), which runs at constant cell; the host loop around calculate() serves a biased NPT run");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: %d components are held (sgpr_md_fix); the moving cell runs without a mask", m.run.fix.n);
-    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates displacements (sgpr_md_msd), which are defined at constant cell");
-    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates pair distances (sgpr_md_rdf), whose image block and densities are those of a constant cell");
-    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates velocity correlations (sgpr_md_vacf), which are not sampled in a moving cell");
-    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates van Hove functions (sgpr_md_vanhove), which are defined at constant cell");
-    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates bond angles (sgpr_md_adf), whose neighbours are read from the list of a constant cell");
+    if (const MdAcc *a = md_acc_attached(m.run)) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_barostat: the run accumulates %s (%s) at constant cell: %s", a->noun, a->fn, a->moving_cell);
     if (!(pfactor > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_barostat: pfactor > 0");
     if (!(m.run.pbc[0] && m.run.pbc[1] && m.run.pbc[2])) return fail(SGPR_E_INVALID, "sgpr_md_barostat: the cell must be periodic in all three directions");
     HIPCHK(hipSetDevice(h->device));
@@ -386,11 +514,7 @@ extern "C" int sgpr_md_relax(sgpr_model *h, double fmax, const double *fire, int
     if (m.run.nh.on || m.run.npt.on) return fail(SGPR_E_INVALID, "sgpr_md_relax: the run has a thermostat or a barostat");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a nudged elastic band (sgpr_md_neb), which has its own optimizer");
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run is a ring polymer (sgpr_md_pimd), which serves dynamics only");
-    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
-    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
-    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
-    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
-    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates bond angles (sgpr_md_adf), which serve dynamics only");
+    if (const MdAcc *a = md_acc_attached(m.run)) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_relax: the run accumulates %s (%s), which serve dynamics only", a->noun, a->fn);
     if (!(fmax > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_relax: fmax > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_relax", fire, p)) return rf;
@@ -734,13 +858,12 @@ static void md_record_frame(sgpr_model *h, int j, int step, hipStream_t st)
 // The sample of evaluation j of a call (configuration n = m.run.t + j, n % msd.every == 0), behind the evaluation's last launch
 // like the frame: the two launches of md_msd.inc on the X slot of n.  The due levels follow from n alone; whether n is the
 // sample the table waits for (next_due) is the device's decision.
-static void md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st)
+static int md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st)
 {
     MdState &m = h->md;
     const MdRun::Msd &a = m.run.msd;
     const long long n = m.run.t + j, s = n / a.every;
-    unsigned due = 0;
-    for (int l = 0; l < a.levels && (s & ((1ll << l) - 1)) == 0; l++) due |= 1u << l;
+    const unsigned due = md_due_levels(s, a.levels, nullptr);
     const int acc = s > 0 ? 1 : 0, N = m.run.N;
     const size_t N3 = (size_t)3 * N;
     const int *chunk = m.msd.tab.p, *coff = chunk + 2 * a.nch, *nz = coff + a.S + 1;
@@ -748,11 +871,12 @@ static void md_msd_sample(sgpr_model *h, int j, int step, hipStream_t st)
                        (const double *)m.mass.p, m.msd.origin.p, N3, due, acc, m.msd.part.p, (const long long *)m.msd.ctl.p, n, (const int *)m.halt.p, step);
     hipLaunchKernelGGL(md_msd_fold_kernel, dim3(1), dim3(256), sizeof(double) * a.levels * a.S * MSD_PART, st, coff, nz, a.nch, a.S, a.levels, a.mtot,
                        a.com, due, acc, (const double *)m.msd.part.p, m.msd.table.p, m.msd.ctl.p, n, a.every, (const int *)m.halt.p, step);
+    return SGPR_OK;
 }
 
 // The same for the pair distances (md_rdf.inc): the pair sweep over the X slot of configuration n — the R = 0 form where no
 // image but the nearest can come within rmax — and the launch that counts the sample.
-static void md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st)
+static int md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st)
 {
     MdState &m = h->md;
     const MdRun::Rdf &a = m.run.rdf;
@@ -762,13 +886,14 @@ static void md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st)
         hipLaunchKernelGGL(a.images ? md_rdf_pair_kernel<true> : md_rdf_pair_kernel<false>, dim3(a.npairs, a.split), dim3(256), 0, st, (const int *)m.rdf.tab.p, x,
                            a.g, m.rdf.table.p, (const long long *)m.rdf.ctl.p, n, (const int *)m.halt.p, step);
     hipLaunchKernelGGL(md_rdf_done_kernel, dim3(1), dim3(64), 0, st, m.rdf.ctl.p, n, a.every, (const int *)m.halt.p, step);
+    return SGPR_OK;
 }
 
 // The same for the velocity autocorrelations (md_vacf.inc): the store of sample s = n / every — V slot n, under Langevin and
 // velocity Verlet with the closing half kick of the evaluation's packed force (n > 0) — and, for s > 0, the correlation of sample
 // s - 1 with its due origins; the launch that advances next_due.  Which lags are due follows from s and origin_every alone;
 // whether n is the awaited sample is the device's decision.
-static void md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st)
+static int md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st)
 {
     MdState &m = h->md;
     const MdRun::Vacf &a = m.run.vacf;
@@ -789,19 +914,19 @@ static void md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st)
                            m.vacf.jring.p, m.vacf.cring.p, m.vacf.tr.p, m.vacf.col.p, m.vacf.ctl.p, n, halt, step);
     }
     hipLaunchKernelGGL(md_vacf_done_kernel, dim3(1), dim3(64), 0, st, m.vacf.ctl.p, n, a.every, s > 0 ? 1 : 0, halt, step);
+    return SGPR_OK;
 }
 
 // The same for the van Hove functions (md_vanhove.inc): md_msd's due levels; the pair sweep of the distinct part — one grid layer
 // per due level, origins against the X slot of n — BEFORE the self part, which measures the displacements and overwrites the
 // origins; the launch that counts.  Sample 0 only sets origins.
-static void md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st)
+static int md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st)
 {
     MdState &m = h->md;
     const MdRun::VanHove &a = m.run.vh;
     const long long n = m.run.t + j, s = n / a.every;
-    unsigned due = 0;
     int ndue = 0;
-    for (int l = 0; l < a.levels && (s & ((1ll << l) - 1)) == 0; l++) { due |= 1u << l; ndue++; }
+    const unsigned due = md_due_levels(s, a.levels, &ndue);
     const int acc = s > 0 ? 1 : 0, N = m.run.N;
     const size_t N3 = (size_t)3 * N;
     const double *x = m.X.p + N3 * (size_t)(n % m.run.ring);
@@ -815,6 +940,7 @@ static void md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st)
                            a.rbins, a.tbins, a.pbins, a.S, due, acc, m.vh.hs.p, (size_t)a.rbins * a.tbins * a.pbins, m.vh.over.p,
                            (const long long *)m.vh.ctl.p, n, halt, step);
     hipLaunchKernelGGL(md_vh_done_kernel, dim3(1), dim3(64), 0, st, m.vh.ctl.p, n, a.every, due, acc, halt, step);
+    return SGPR_OK;
 }
 
 // The LDS of md_adf_kernel for a list of capacity maxnn: the waves of a workgroup (4 ... 1, 0: one centre's rows alone do not fit)
@@ -853,6 +979,19 @@ static int md_adf_sample(sgpr_model *h, int j, int step, hipStream_t st)
     }
     hipLaunchKernelGGL(md_adf_done_kernel, dim3(1), dim3(64), 0, st, m.adf.ctl.p, n, a.every, (const int *)m.halt.p, step,
                        (const double *)(m.scal_d.p + (size_t)SGPR_MD_SCAL * j + 10));
+    return SGPR_OK;
+}
+
+// Behind evaluation j of a call (and its frame): the samples of the accumulators whose interval divides the configuration's
+// index, in the table's order.  A run without accumulators tests five integers and launches nothing.
+static int md_sample_due(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    const MdRun &r = h->md.run;
+    for (const MdAcc &a : MD_ACC) {
+        const int every = a.every(r);
+        if (every && (r.t + j) % every == 0)
+            if (const int rs = a.sample(h, j, step, st)) return rs;
+    }
     return SGPR_OK;
 }
 
@@ -1020,11 +1159,7 @@ extern "C" int sgpr_md_committee(sgpr_model *h, int K, sgpr_model *const *member
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run is a ring polymer (sgpr_md_pimd), which is evaluated by one model");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d components are held (sgpr_md_fix); a committee runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: a frame record is armed (sgpr_md_record); a committee records no frames");
-    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates displacements (sgpr_md_msd), which the committee's loop does not sample");
-    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates pair distances (sgpr_md_rdf), which the committee's loop does not sample");
-    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates velocity correlations (sgpr_md_vacf), which the committee's loop does not sample");
-    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates van Hove functions (sgpr_md_vanhove), which the committee's loop does not sample");
-    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates bond angles (sgpr_md_adf), which the committee's loop does not sample");
+    if (const MdAcc *a = md_acc_attached(m.run)) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run accumulates %s (%s), which the committee's loop does not sample", a->noun, a->fn);
     if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: the run was begun on %d ranks; a committee runs on one", m.run.world);
     if (K > BCM_MAX - 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_committee: %d members; at most %d beside the live model", K, BCM_MAX - 1);
     for (int k = 0; k < K; k++) {
@@ -1391,11 +1526,7 @@ extern "C" int sgpr_md_neb(sgpr_model *h, int K, const double *positions, double
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a relaxation (sgpr_md_relax); a band moves at constant cell under its own FIRE");
     if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run is a ring polymer (sgpr_md_pimd)");
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: a frame record is armed (sgpr_md_record); a band records no frames");
-    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates displacements (sgpr_md_msd), which serve dynamics only");
-    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates pair distances (sgpr_md_rdf), which serve dynamics only");
-    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates velocity correlations (sgpr_md_vacf), which serve dynamics only");
-    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates van Hove functions (sgpr_md_vanhove), which serve dynamics only");
-    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates bond angles (sgpr_md_adf), which serve dynamics only");
+    if (const MdAcc *a = md_acc_attached(m.run)) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_neb: the run accumulates %s (%s), which serve dynamics only", a->noun, a->fn);
     if (!(fmax > 0.0) || !(k_spring > 0.0)) return fail(SGPR_E_INVALID, "sgpr_md_neb: fmax > 0 and k_spring > 0");
     RelaxParams p = {};
     if (const int rf = md_fire_keywords("sgpr_md_neb", fire, p)) return rf;
@@ -1520,11 +1651,7 @@ extern "C" int sgpr_md_pimd(sgpr_model *h, int P, const double *positions, const
     if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run has a filter (sgpr_md_filter); a polymer integrates unfiltered forces");
     if (m.run.fix.n) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: %d components are held (sgpr_md_fix); a polymer runs without a mask", m.run.fix.n);
     if (m.run.rec.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: a frame record is armed (sgpr_md_record); a polymer records no frames");
-    if (m.run.msd.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates displacements (sgpr_md_msd); a polymer's centroid is not sampled");
-    if (m.run.rdf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates pair distances (sgpr_md_rdf); a polymer's beads are not sampled");
-    if (m.run.vacf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates velocity correlations (sgpr_md_vacf); a polymer's centroid is not sampled");
-    if (m.run.vh.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates van Hove functions (sgpr_md_vanhove); a polymer's beads are not sampled");
-    if (m.run.adf.every) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates bond angles (sgpr_md_adf); a polymer's beads are not sampled");
+    if (const MdAcc *a = md_acc_attached(m.run)) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run accumulates %s (%s); a polymer's %s not sampled", a->noun, a->fn, a->polymer);
     if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a relaxation (sgpr_md_relax)");
     if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_pimd: the run is a nudged elastic band (sgpr_md_neb)");
     if (m.run.pimd.on) return fail(SGPR_E_INVALID, "sgpr_md_pimd: the run is a polymer already");
@@ -1739,13 +1866,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         // (the frame: the last kernel has written this evaluation's results and, Nose-Hoover, its centred velocity; the slots
         // read here are written again only when the rings come round)
         if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);
-        if (m.run.msd.every && (m.run.t + j) % m.run.msd.every == 0) md_msd_sample(h, j, (int)(step0 + j), st);
-        if (m.run.rdf.every && (m.run.t + j) % m.run.rdf.every == 0) md_rdf_sample(h, j, (int)(step0 + j), st);
-        if (m.run.vacf.every && (m.run.t + j) % m.run.vacf.every == 0) md_vacf_sample(h, j, (int)(step0 + j), st);
-        if (m.run.vh.every && (m.run.t + j) % m.run.vh.every == 0) md_vh_sample(h, j, (int)(step0 + j), st);
-        if (m.run.adf.every && (m.run.t + j) % m.run.adf.every == 0)
-            if (const int ra = md_adf_sample(h, j, (int)(step0 + j), st)) return ra;
-        return SGPR_OK;
+        return md_sample_due(h, j, (int)(step0 + j), st);
     });
     if (rc_) return rc_;
     const int enq = c.enq;
@@ -1927,44 +2048,29 @@ extern "C" int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *inde
 // configuration n with n % every == 0 is sample n / every, and behind its evaluation two launches update a table in device
 // memory: per level l < levels (lag 2^l samples, one origin, windows that do not overlap) and species of the model's table the
 // sums of msd, msd^2, smd, smd^2 and the number of windows.  com: displacements relative to the frame's centre of mass.  After
-// sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record), before the first sgpr_md_run; every = 0 detaches.  The attach
+// sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record), before the first sgpr_md_run; every = 0 detaches and frees.  The attach
 // zeroes the table.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, beside a mask, the filter, a bias
 // and the frame record; a barostat, a committee, a relaxation, a band, a polymer and several ranks: SGPR_E_UNSUPPORTED, from
 // here and from their attach functions.
 extern "C" int sgpr_md_msd(sgpr_model *h, int every, int levels, int com)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_msd: bad arguments");
+    const MdAcc &acc = MD_ACC[MD_MSD];
+    if (const int rr = md_acc_run(h, acc)) return rr;
     MdState &m = h->md;
-    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_msd: call sgpr_md_begin first");
-    if (every == 0) { m.run.msd = MdRun::Msd(); return SGPR_OK; }
+    if (every == 0) { m.run.msd = MdRun::Msd(); return md_release(h, m.msd); }   // (a detach gives the memory back)
     if (every < 0 || levels < 1 || levels > MSD_MAXL || (com != 0 && com != 1))
         return fail(SGPR_E_INVALID, "sgpr_md_msd: every >= 0, 1 <= levels <= %d, com = 0 or 1", MSD_MAXL);
-    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_msd: the run has started");
-    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run was begun on %d ranks; displacements are accumulated on one", m.run.world);
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run has a barostat; a displacement in a moving cell mixes in the strain");
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run has a committee (sgpr_md_committee), whose loop does not sample displacements");
-    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a relaxation; displacements are accumulated over dynamics");
-    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a nudged elastic band; displacements are accumulated over dynamics");
-    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: the run is a ring polymer (sgpr_md_pimd); its centroid is not sampled");
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
+    if (const int rm = md_acc_modes(h, acc)) return rm;
     const int N = m.run.N, S = h->S;
     if (sizeof(double) * (size_t)levels * S * MSD_PART > 65536)
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_msd: %d levels of %d species: the sums of a sample must fit 64 KiB of LDS", levels, S);
-    // the chunks: runs of at most MSD_CHUNK consecutive sorted atoms of one species (the sort is by species in table order)
-    std::vector<int> nz(S, 0), zi(N);
-    for (int i = 0; i < N; i++) {
-        int z = 0;
-        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
-        if (z == S || (i > 0 && z < zi[i - 1])) return fail(SGPR_E_INVALID, "sgpr_md_msd: the run's atoms are not sorted by the model's species");
-        zi[i] = z; nz[z]++;
-    }
-    std::vector<int> tab, coff(S + 1, 0);
-    for (int z = 0, first = 0; z < S; first += nz[z], z++) {
-        for (int o = 0; o < nz[z]; o += MSD_CHUNK) { tab.push_back(first + o); tab.push_back(std::min(MSD_CHUNK, nz[z] - o)); }
-        coff[z + 1] = (int)tab.size() / 2;
-    }
-    const int nch = coff[S];
-    tab.insert(tab.end(), coff.begin(), coff.end());
-    tab.insert(tab.end(), nz.begin(), nz.end());
+    MdSpecies sp;   // the chunks | a species' chunks | its atoms
+    if (const int rs = md_species_chunks(h, acc.fn, MSD_CHUNK, false, sp)) return rs;
+    std::vector<int> &tab = sp.tab;
+    const int nch = sp.nch;
+    tab.insert(tab.end(), sp.coff.begin(), sp.coff.end());
+    tab.insert(tab.end(), sp.nz.begin(), sp.nz.end());
     double mtot = 0.0;
     for (int i = 0; i < N; i++) mtot += m.run.mass_sorted[i];
     HIPCHK(hipSetDevice(h->device));
@@ -2037,28 +2143,15 @@ static bool md_rdf_geometry(const double *cell, const int32_t *pbc, double rmax,
 // band, a polymer and several ranks: SGPR_E_UNSUPPORTED, from here and from their attach functions.
 extern "C" int sgpr_md_rdf(sgpr_model *h, int every, double rmin, double rmax, int bins)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_rdf: bad arguments");
+    const MdAcc &acc = MD_ACC[MD_RDF];
+    if (const int rr = md_acc_run(h, acc)) return rr;
     MdState &m = h->md;
-    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_rdf: call sgpr_md_begin first");
-    if (every == 0) {   // (a detach gives the table back: nothing of it is launched or read from here on)
-        m.run.rdf = MdRun::Rdf();
-        if (m.rdf.held()) {
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            m.rdf = MdState::RdfBufs();
-        }
-        return SGPR_OK;
-    }
+    if (every == 0) { m.run.rdf = MdRun::Rdf(); return md_release(h, m.rdf); }
     if (every < 0 || bins < 1 || bins > RDF_MAXBINS || !(rmin >= 0.0) || !(rmin < rmax) || !(rmax < 1e300))
         return fail(SGPR_E_INVALID, "sgpr_md_rdf: every >= 0, 1 <= bins <= %d, 0 <= rmin < rmax", RDF_MAXBINS);
-    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_rdf: the run has started");
-    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run was begun on %d ranks; pair distances are accumulated on one", m.run.world);
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run has a barostat; the image block and the densities are those of a constant cell");
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run has a committee (sgpr_md_committee), whose loop does not sample pair distances");
-    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a relaxation; pair distances are accumulated over dynamics");
-    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a nudged elastic band; pair distances are accumulated over dynamics");
-    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
-    const int N = m.run.N, S = h->S;
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
+    if (const int rm = md_acc_modes(h, acc)) return rm;
+    const int S = h->S;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     double cell[9], height[3], volume = 0.0;
@@ -2070,34 +2163,18 @@ extern "C" int sgpr_md_rdf(sgpr_model *h, int every, double rmin, double rmax, i
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_rdf: rmax = %g against the cell height %g along direction %d needs images %d cells away; at most %d (125 shifts)",
                         rmax, height[k], k, g.R[k], RDF_MAXR);
     g.rmin = rmin; g.rmax = rmax; g.bins = bins;
-    // the tiles: runs of at most RDF_TILE consecutive sorted atoms of one species (the sort is by species in table order), and
-    // the tile pairs I <= J
-    std::vector<int> nz(S, 0), first(S, 0);
-    for (int i = 0, last = 0; i < N; i++) {
-        int z = 0;
-        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
-        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_rdf: the run's atoms are not sorted by the model's species");
-        last = z; nz[z]++;
-    }
-    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
-    std::vector<int> tab;
-    for (int a = 0; a < S; a++)
-        for (int oa = 0; oa < nz[a]; oa += RDF_TILE)
-            for (int b = a; b < S; b++)
-                for (int ob = (b == a ? oa : 0); ob < nz[b]; ob += RDF_TILE) {
-                    const int rec[RDF_PAIR] = {first[a] + oa, std::min(RDF_TILE, nz[a] - oa), first[b] + ob, std::min(RDF_TILE, nz[b] - ob),
-                                               a * S + b, (a == b && ob != oa) ? 2 : 1};
-                    tab.insert(tab.end(), rec, rec + RDF_PAIR);
-                }
-    const int npairs = (int)tab.size() / RDF_PAIR;
-    tab.insert(tab.end(), nz.begin(), nz.end());
+    MdSpecies sp;   // the tile pairs I <= J | a species' atoms
+    if (const int rs = md_species_chunks(h, acc.fn, 0, false, sp)) return rs;
+    std::vector<int> &tab = sp.tab;
+    const int npairs = md_tile_pairs(sp.nz, sp.first, false, tab);
+    tab.insert(tab.end(), sp.nz.begin(), sp.nz.end());
     if (m.rdf.table.alloc((size_t)S * S * bins) || m.rdf.ctl.alloc(2) || m.rdf.tab.alloc(tab.size(), false))
         return fail(SGPR_E_NODEVICE, "sgpr_md_rdf: device allocation failed");
     HIPCHK(hipMemcpy(m.rdf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
     MdRun::Rdf &a = m.run.rdf;
     // (workgroups for every SIMD of the chip: a tile pair of a small frame is cut along J into up to 8 parts of 16 atoms or more)
     a.split = std::max(1, std::min(RDF_SPLIT_MAX, RDF_WORKGROUPS / std::max(1, npairs)));
-    a.every = every; a.npairs = npairs; a.S = S; a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.volume = volume;
+    a.every = every; a.npairs = npairs; a.S = S; a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.volume = volume; a.nz = sp.nz;
     return SGPR_OK;
 }
 
@@ -2121,11 +2198,9 @@ extern "C" int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, do
     }
     if (info) {
         long long ctl[2];
-        std::vector<int> nz(S);
         HIPCHK(hipMemcpy(ctl, m.rdf.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(nz.data(), m.rdf.tab.p + (size_t)RDF_PAIR * a.npairs, sizeof(int) * S, hipMemcpyDeviceToHost));
         info[0] = ctl[1]; info[1] = ctl[0]; info[2] = bins; info[3] = S;
-        for (int z = 0; z < S; z++) info[4 + z] = nz[z];
+        for (int z = 0; z < S; z++) info[4 + z] = a.nz[z];
     }
     if (geom) { geom[0] = a.volume; geom[1] = a.g.rmin; geom[2] = a.g.rmax; }
     return SGPR_OK;
@@ -2143,49 +2218,26 @@ extern "C" int sgpr_md_rdf_read(sgpr_model *h, uint64_t *hist, int64_t *info, do
 // (lags + 1) 24 N bytes <= VACF_MAXBYTES.
 extern "C" int sgpr_md_vacf(sgpr_model *h, int every, int lags, int origin_every, int com)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vacf: bad arguments");
+    const MdAcc &acc = MD_ACC[MD_VACF];
+    if (const int rr = md_acc_run(h, acc)) return rr;
     MdState &m = h->md;
-    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_vacf: call sgpr_md_begin first");
-    if (every == 0) {   // (a detach gives the rings back: nothing of them is launched or read from here on)
-        m.run.vacf = MdRun::Vacf();
-        if (m.vacf.held()) {
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            m.vacf = MdState::VacfBufs();
-        }
-        return SGPR_OK;
-    }
+    if (every == 0) { m.run.vacf = MdRun::Vacf(); return md_release(h, m.vacf); }
     if (every < 0 || lags < 1 || origin_every < 1 || (com != 0 && com != 1))
         return fail(SGPR_E_INVALID, "sgpr_md_vacf: every >= 0, lags >= 1, origin_every >= 1, com = 0 or 1");
-    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_vacf: the run has started");
-    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run was begun on %d ranks; velocity correlations are accumulated on one", m.run.world);
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a barostat; velocities in a moving cell are not sampled");
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a committee (sgpr_md_committee), whose loop does not sample velocities");
-    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a relaxation; velocity correlations are accumulated over dynamics");
-    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a nudged elastic band; velocity correlations are accumulated over dynamics");
-    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run is a ring polymer (sgpr_md_pimd); its centroid is not sampled");
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
+    if (const int rm = md_acc_modes(h, acc)) return rm;
     if (m.run.filter.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a filter (sgpr_md_filter): its closing kick uses the filtered force, not the packed one the sample takes");
     if (m.run.meta.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: the run has a bias (sgpr_md_meta): its closing kick uses the biased force, not the packed one the sample takes");
     const int N = m.run.N, S = h->S;
     if (lags > VACF_MAXLAGS || (unsigned long long)(lags + 1) * 24ull * (unsigned long long)N > VACF_MAXBYTES)
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vacf: %d lags of %d atoms: at most %d lags and a ring of (lags + 1) 24 N = %llu bytes",
                     lags, N, VACF_MAXLAGS, (unsigned long long)VACF_MAXBYTES);
-    // the chunks: runs of at most VACF_CHUNK consecutive sorted atoms of one species (the sort is by species in table order)
-    std::vector<int> nz(S, 0);
-    for (int i = 0, last = 0; i < N; i++) {
-        int z = 0;
-        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
-        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_vacf: the run's atoms are not sorted by the model's species");
-        last = z; nz[z]++;
-    }
-    std::vector<int> tab, coff(S + 1, 0);
-    for (int z = 0, first = 0; z < S; first += nz[z], z++) {
-        for (int o = 0; o < nz[z]; o += VACF_CHUNK) { tab.push_back(first + o); tab.push_back(std::min(VACF_CHUNK, nz[z] - o)); }
-        coff[z + 1] = (int)tab.size() / 2;
-    }
-    const int nch = coff[S];
-    tab.insert(tab.end(), coff.begin(), coff.end());
-    tab.insert(tab.end(), nz.begin(), nz.end());
+    MdSpecies sp;   // the chunks | a species' chunks | its atoms
+    if (const int rs = md_species_chunks(h, acc.fn, VACF_CHUNK, false, sp)) return rs;
+    std::vector<int> &tab = sp.tab;
+    const int nch = sp.nch;
+    tab.insert(tab.end(), sp.coff.begin(), sp.coff.end());
+    tab.insert(tab.end(), sp.nz.begin(), sp.nz.end());
     double mtot = 0.0;
     for (int i = 0; i < N; i++) mtot += m.run.mass_sorted[i];
     HIPCHK(hipSetDevice(h->device));
@@ -2198,7 +2250,7 @@ extern "C" int sgpr_md_vacf(sgpr_model *h, int every, int lags, int origin_every
         return fail(SGPR_E_NODEVICE, "sgpr_md_vacf: device allocation failed");
     HIPCHK(hipMemcpy(m.vacf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
     MdRun::Vacf &a = m.run.vacf;
-    a.every = every; a.lags = lags; a.origin_every = origin_every; a.com = com; a.nch = nch; a.S = S; a.mtot = mtot;
+    a.every = every; a.lags = lags; a.origin_every = origin_every; a.com = com; a.nch = nch; a.S = S; a.mtot = mtot; a.nz = sp.nz;
     return SGPR_OK;
 }
 
@@ -2219,10 +2271,8 @@ extern "C" int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collecti
     if (collective) HIPCHK(hipMemcpy(collective, m.vacf.col.p, sizeof(double) * (size_t)a.lags * a.S * a.S, hipMemcpyDeviceToHost));
     if (counts) for (int k = 0; k < a.lags; k++) counts[k] = ctl[2 + k];
     if (info) {
-        std::vector<int> nz(a.S);
-        HIPCHK(hipMemcpy(nz.data(), m.vacf.tab.p + (size_t)2 * a.nch + a.S + 1, sizeof(int) * a.S, hipMemcpyDeviceToHost));
         info[0] = ctl[1]; info[1] = ctl[0] > 0 ? 1 : 0; info[2] = ctl[0];
-        for (int z = 0; z < a.S; z++) info[3 + z] = nz[z];
+        for (int z = 0; z < a.S; z++) info[3 + z] = a.nz[z];
     }
     return SGPR_OK;
 }
@@ -2240,18 +2290,10 @@ extern "C" int sgpr_md_vacf_read(sgpr_model *h, double *tracer, double *collecti
 // functions.
 extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax, int rbins, int tbins, int pbins, double dmax, int dbins)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: bad arguments");
+    const MdAcc &acc = MD_ACC[MD_VH];
+    if (const int rr = md_acc_run(h, acc)) return rr;
     MdState &m = h->md;
-    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: call sgpr_md_begin first");
-    if (every == 0) {   // (a detach gives the origins and the tables back: nothing of them is launched or read from here on)
-        m.run.vh = MdRun::VanHove();
-        if (m.vh.held()) {
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            m.vh = MdState::VanHoveBufs();
-        }
-        return SGPR_OK;
-    }
+    if (every == 0) { m.run.vh = MdRun::VanHove(); return md_release(h, m.vh); }
     if (every < 0 || levels < 1 || levels > MSD_MAXL) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: every >= 0, 1 <= levels <= %d", MSD_MAXL);
     if (rbins < 1 || rbins > VH_MAXRBINS || !(rmax > 0.0) || !(rmax < 1e300))
         return fail(SGPR_E_INVALID, "sgpr_md_vanhove: rmax > 0, 1 <= rbins <= %d (rbins = %d)", VH_MAXRBINS, rbins);
@@ -2259,13 +2301,8 @@ extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax
         return fail(SGPR_E_INVALID, "sgpr_md_vanhove: 1 <= tbins, pbins <= %d (tbins = %d, pbins = %d)", VH_MAXABINS, tbins, pbins);
     if (dbins < 0 || dbins > RDF_MAXBINS || (dbins > 0 && (!(dmax > 0.0) || !(dmax < 1e300))))
         return fail(SGPR_E_INVALID, "sgpr_md_vanhove: 0 <= dbins <= %d (dbins = %d), dmax > 0 with dbins > 0", RDF_MAXBINS, dbins);
-    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: the run has started");
-    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run was begun on %d ranks; van Hove functions are accumulated on one", m.run.world);
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run has a barostat; displacements and the image block are those of a constant cell");
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run has a committee (sgpr_md_committee), whose loop does not sample displacements");
-    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a relaxation; van Hove functions are accumulated over dynamics");
-    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a nudged elastic band; van Hove functions are accumulated over dynamics");
-    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_vanhove: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
+    if (const int rm = md_acc_modes(h, acc)) return rm;
     const int N = m.run.N, S = h->S;
     const size_t zstride = (size_t)rbins * tbins * pbins;
     if ((unsigned long long)levels * S * zstride * 8ull > (1ull << 30))
@@ -2287,28 +2324,12 @@ extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax
     g.rmin = 0.0; g.rmax = dbins ? dmax : 0.0; g.bins = dbins;
     // the chunks of the self part and the tiles of the distinct part: runs of consecutive sorted atoms of one species (the sort is
     // by species in table order); every ordered pair of tiles
-    std::vector<int> nz(S, 0), first(S, 0);
-    for (int i = 0, last = 0; i < N; i++) {
-        int z = 0;
-        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
-        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_vanhove: the run's atoms are not sorted by the model's species");
-        last = z; nz[z]++;
-    }
-    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
-    std::vector<int> tab;
-    for (int z = 0; z < S; z++)
-        for (int o = 0; o < nz[z]; o += MSD_CHUNK) { tab.push_back(first[z] + o); tab.push_back(std::min(MSD_CHUNK, nz[z] - o)); tab.push_back(z); }
-    const int nch = (int)tab.size() / VH_CHUNK;
-    int npairs = 0;
-    if (dbins)
-        for (int a = 0; a < S; a++)
-            for (int oa = 0; oa < nz[a]; oa += RDF_TILE)
-                for (int b = 0; b < S; b++)
-                    for (int ob = 0; ob < nz[b]; ob += RDF_TILE, npairs++) {
-                        const int rec[RDF_PAIR] = {first[a] + oa, std::min(RDF_TILE, nz[a] - oa), first[b] + ob, std::min(RDF_TILE, nz[b] - ob), a * S + b, 1};
-                        tab.insert(tab.end(), rec, rec + RDF_PAIR);
-                    }
-    tab.insert(tab.end(), nz.begin(), nz.end());
+    MdSpecies sp;
+    if (const int rs = md_species_chunks(h, acc.fn, MSD_CHUNK, true, sp)) return rs;
+    static_assert(VH_CHUNK == 3, "a chunk record of the self part: first atom, atoms, species");
+    std::vector<int> &tab = sp.tab;
+    const int nch = sp.nch, npairs = dbins ? md_tile_pairs(sp.nz, sp.first, true, tab) : 0;
+    tab.insert(tab.end(), sp.nz.begin(), sp.nz.end());
     std::vector<double> edges((size_t)tbins + 2 * pbins);
     for (int k = 0; k < tbins; k++) edges[k] = cos((double)k * M_PI / (double)tbins);
     for (int k = 0; k < pbins; k++) {
@@ -2327,7 +2348,7 @@ extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax
     a = MdRun::VanHove();
     a.split = std::max(1, std::min(RDF_SPLIT_MAX, RDF_WORKGROUPS / std::max(1, npairs)));
     a.every = every; a.levels = levels; a.rbins = rbins; a.tbins = tbins; a.pbins = pbins; a.dbins = dbins; a.nch = nch; a.npairs = npairs; a.S = S;
-    a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.rmax = rmax; a.dmax = dbins ? dmax : 0.0; a.volume = has_volume ? volume : 0.0;
+    a.images = g.R[0] || g.R[1] || g.R[2]; a.g = g; a.rmax = rmax; a.dmax = dbins ? dmax : 0.0; a.volume = has_volume ? volume : 0.0; a.nz = sp.nz;
     return SGPR_OK;
 }
 
@@ -2370,10 +2391,8 @@ extern "C" int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t
     if (distinct_hist && a.dbins) HIPCHK(hipMemcpy(distinct_hist, m.vh.hd.p, sizeof(uint64_t) * LS * a.S * a.dbins, hipMemcpyDeviceToHost));
     if (counts) for (int l = 0; l < a.levels; l++) counts[l] = ctl[VH_CTL + l];
     if (info) {
-        std::vector<int> nz(a.S);
-        HIPCHK(hipMemcpy(nz.data(), m.vh.tab.p + (size_t)VH_CHUNK * a.nch + (size_t)RDF_PAIR * a.npairs, sizeof(int) * a.S, hipMemcpyDeviceToHost));
         info[0] = ctl[1]; info[1] = ctl[0]; info[2] = a.levels; info[3] = a.S; info[4] = a.rbins; info[5] = a.tbins; info[6] = a.pbins; info[7] = a.dbins;
-        for (int z = 0; z < a.S; z++) info[8 + z] = nz[z];
+        for (int z = 0; z < a.S; z++) info[8 + z] = a.nz[z];
     }
     if (geom) { geom[0] = a.volume; geom[1] = a.rmax; geom[2] = a.dmax; }
     return SGPR_OK;
@@ -2390,21 +2409,13 @@ extern "C" int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t
 // polymer and several ranks: SGPR_E_UNSUPPORTED, from here and from their attach functions.
 extern "C" int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut, const double *ct)
 {
-    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_adf: bad arguments");
+    const MdAcc &acc = MD_ACC[MD_ADF];
+    if (const int rr = md_acc_run(h, acc)) return rr;
     MdState &m = h->md;
-    if (!m.active) return fail(SGPR_E_INVALID, "sgpr_md_adf: call sgpr_md_begin first");
-    if (every == 0) {   // (a detach gives the tables back: nothing of them is launched or read from here on)
-        m.run.adf = MdRun::Adf();
-        if (m.adf.held()) {
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            m.adf = MdState::AdfBufs();
-        }
-        return SGPR_OK;
-    }
+    if (every == 0) { m.run.adf = MdRun::Adf(); return md_release(h, m.adf); }
     if (every < 0 || bins < 1 || bins > ADF_MAXBINS || !cut || !ct)
         return fail(SGPR_E_INVALID, "sgpr_md_adf: every >= 0, 1 <= bins <= %d, a cutoff table and an edge table", ADF_MAXBINS);
-    const int N = m.run.N, S = h->S;
+    const int S = h->S;
     double cmax = 0.0;
     for (int a = 0; a < S; a++)
         for (int b = 0; b < S; b++) {
@@ -2417,31 +2428,17 @@ extern "C" int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut
     for (int e = 0; e < bins; e++)
         if (!(fabs(ct[e]) <= 1.0) || (e > 0 && ct[e] > ct[e - 1]))
             return fail(SGPR_E_INVALID, "sgpr_md_adf: the edges ct[e] = cos(e pi / bins) lie in [-1, 1] and do not increase (entry %d)", e);
-    if (m.run.t != 0 || m.run.started) return fail(SGPR_E_INVALID, "sgpr_md_adf: the run has started");
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
     if (cmax > h->rc)
         return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: a bond cutoff of %g lies beyond the model's cutoff %g; the step's neighbour list holds no further neighbours", cmax, h->rc);
-    if (m.run.world > 1) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run was begun on %d ranks; bond angles are accumulated on one", m.run.world);
-    if (m.run.npt.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run has a barostat; the neighbours are read from the list of a constant cell");
-    if (!m.run.bcm.members.empty()) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run has a committee (sgpr_md_committee), whose loop does not sample bond angles");
-    if (m.run.relax.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a relaxation; bond angles are accumulated over dynamics");
-    if (m.run.neb.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a nudged elastic band; bond angles are accumulated over dynamics");
-    if (m.run.pimd.on) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_adf: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled");
+    if (const int rm = md_acc_modes(h, acc)) return rm;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    // the chunks: runs of at most ADF_CHUNK consecutive sorted centres of one species (the sort is by species in table order)
-    std::vector<int> nz(S, 0), first(S, 0);
-    for (int i = 0, last = 0; i < N; i++) {
-        int z = 0;
-        while (z < S && h->species[z] != m.run.numbers[m.run.perm[i]]) z++;
-        if (z == S || z < last) return fail(SGPR_E_INVALID, "sgpr_md_adf: the run's atoms are not sorted by the model's species");
-        last = z; nz[z]++;
-    }
-    for (int z = 1; z < S; z++) first[z] = first[z - 1] + nz[z - 1];
-    std::vector<int> tab;
-    for (int z = 0; z < S; z++)
-        for (int o = 0; o < nz[z]; o += ADF_CHUNK) { tab.push_back(first[z] + o); tab.push_back(std::min(ADF_CHUNK, nz[z] - o)); tab.push_back(z); }
-    const int nch = (int)tab.size() / 3;
-    tab.insert(tab.end(), nz.begin(), nz.end());
+    MdSpecies sp;   // the chunks of centres | a species' atoms
+    if (const int rs = md_species_chunks(h, acc.fn, ADF_CHUNK, true, sp)) return rs;
+    std::vector<int> &tab = sp.tab;
+    const int nch = sp.nch;
+    tab.insert(tab.end(), sp.nz.begin(), sp.nz.end());
     std::vector<double> par(cut, cut + (size_t)S * S);
     par.insert(par.end(), ct, ct + bins);
     if (m.adf.angles.alloc((size_t)S * S * S * bins) || m.adf.coord.alloc((size_t)S * S * ADF_MAXCOORD) || m.adf.par.alloc(par.size(), false) ||
@@ -2453,7 +2450,7 @@ extern "C" int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut
     HIPCHK(hipMemcpy(m.adf.par.p, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice));
     MdRun::Adf &a = m.run.adf;
     a = MdRun::Adf();
-    a.every = every; a.bins = bins; a.nch = nch; a.S = S;
+    a.every = every; a.bins = bins; a.nch = nch; a.S = S; a.nz = sp.nz;
     a.lds = (long long)(S * (S + 1) / 2) * bins <= ADF_LDS_COUNTERS;
     return SGPR_OK;
 }
@@ -2481,11 +2478,9 @@ extern "C" int sgpr_md_adf_read(sgpr_model *h, uint64_t *angles, uint64_t *coord
     if (coord) HIPCHK(hipMemcpy(coord, m.adf.coord.p, sizeof(uint64_t) * (size_t)S * S * ADF_MAXCOORD, hipMemcpyDeviceToHost));
     if (info) {
         long long ctl[2];
-        std::vector<int> nz(S);
         HIPCHK(hipMemcpy(ctl, m.adf.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(nz.data(), m.adf.tab.p + (size_t)3 * a.nch, sizeof(int) * S, hipMemcpyDeviceToHost));
         info[0] = ctl[1]; info[1] = ctl[0]; info[2] = bins; info[3] = S;
-        for (int z = 0; z < S; z++) info[4 + z] = nz[z];
+        for (int z = 0; z < S; z++) info[4 + z] = a.nz[z];
     }
     return SGPR_OK;
 }
@@ -2870,41 +2865,15 @@ extern "C" int sgpr_md_end(sgpr_model *h)
     if (!h) return fail(SGPR_E_INVALID, "sgpr_md_end: bad arguments");
     MdState &m = h->md;
     m.active = false;
-    if (m.run.meta.on || m.meta.held()) {   // (the hills of a bias are the run's: given back with it, by a move-assign of the empty group)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.meta = MdState::MetaBufs();
-    }
-    if (m.lbfgs.held()) {   // (and so is the history of L-BFGS)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.lbfgs = MdState::LbfgsBufs();
-    }
-    if (m.msd.held()) {   // (and the origins and the table of the displacements)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.msd = MdState::MsdBufs();
-    }
-    if (m.rdf.held()) {   // (and the table of the pair distances)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.rdf = MdState::RdfBufs();
-    }
-    if (m.vacf.held()) {   // (and the rings and the tables of the velocity correlations)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.vacf = MdState::VacfBufs();
-    }
-    if (m.vh.held()) {   // (and the origins and the tables of the van Hove functions)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.vh = MdState::VanHoveBufs();
-    }
-    if (m.adf.held()) {   // (and the tables of the bond angles)
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        m.adf = MdState::AdfBufs();
-    }
+    // what the run's modes and accumulators hold on the device is the run's: given back with it (the hills of a bias, the history
+    // of L-BFGS, the origins, rings and tables of the accumulators).  The run ends whatever the waits say.
+    (void)md_release(h, m.meta);
+    (void)md_release(h, m.lbfgs);
+    (void)md_release(h, m.msd);
+    (void)md_release(h, m.rdf);
+    (void)md_release(h, m.vacf);
+    (void)md_release(h, m.vh);
+    (void)md_release(h, m.adf);
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;
 }

@@ -30,6 +30,17 @@ class Local:
         return f"Local(Z={self.number}, nn={len(self._b)})"
 
 
+def _attach(code):
+    """check() for the attach functions of the device loop: what the loop does not serve (SGPR_E_UNSUPPORTED) is a
+    NotImplementedError — the host loop around calculate() serves it."""
+    try:
+        check(code)
+    except _lib.SgprError as e:
+        if e.code == -6:   # SGPR_E_UNSUPPORTED
+            raise NotImplementedError(str(e)) from None
+        raise
+
+
 def default_radii(species):
     """DefaultRadii (theforce/descriptor/sesoap.py:84-99): 0.5 for H, else 1.0."""
     return np.array([0.5 if int(z) == 1 else 1.0 for z in species])
@@ -723,13 +734,8 @@ class SGPRModel:
         hc = np.zeros((0, D)) if hills is None else f64(np.asarray(hills, float)).reshape(-1, D)
         hv = None if hv is None else f64(np.asarray(hv, float)).reshape(len(hc))
         cap = len(hc) + 4096 if capacity is None else int(capacity)
-        try:
-            check(lib.sgpr_md_meta(self._h, len(spec), ptr(i32(np.asarray(spec, np.int32).reshape(-1))), ptr(sg), float(w),
-                                   0.0 if tem is None else float(kB * tem), int(pace), cap, len(hc), ptr(hc) if len(hc) else None, ptr(hv)))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(lib.sgpr_md_meta(self._h, len(spec), ptr(i32(np.asarray(spec, np.int32).reshape(-1))), ptr(sg), float(w),
+                                 0.0 if tem is None else float(kB * tem), int(pace), cap, len(hc), ptr(hc) if len(hc) else None, ptr(hv)))
         self._md["meta_D"] = D
         if merge is not None:
             check(lib.sgpr_md_meta_merge(self._h, int(merge)))
@@ -1122,21 +1128,24 @@ class SGPRModel:
                 out["velocities"] = vel
         return out
 
+    def _md_species(self, n=None):
+        """The `species` and `n` entries of an accumulator's table: the model's table and its atoms in the run's frame — as the
+        library reports them, or (None) counted from the run's numbers."""
+        if n is None:
+            numbers = np.asarray(self._md["numbers"])
+            n = [int(np.sum(numbers == int(z))) for z in self.species]
+        return dict(species=np.array([int(z) for z in self.species]), n=np.array(n))
+
     def md_msd(self, every, levels, com=False):
         """Accumulate mean-square displacements inside the loop (sgpr_md_msd; md_msd.inc has the scheme, workloads.MsdBlocks is
         the host twin and the definition): configuration n with n % every == 0 is sample n / every; level l < levels has the
         lag 2^l samples, one origin and windows that do not overlap, and per species of the model's table gains the tracer
         msd = mean |d_i - c|^2 and the collective smd = |sum (d_i - c)|^2 / n_z of every window (c: the displacement of the
         frame's centre of mass with com=True, else 0) — what theforce/analysis/analysis.py's `correlator` works out of a stored
-        trajectory.  After md_begin, before the first md_run; every = 0 detaches.  md_msd_table() reads the table.  Langevin,
+        trajectory.  After md_begin, before the first md_run; every = 0 detaches and frees.  md_msd_table() reads the table.  Langevin,
         velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter=, md_meta and md_record;
         a barostat, a committee, a relaxation, a band, a polymer and several ranks: NotImplementedError."""
-        try:
-            check(_lib.load().sgpr_md_msd(self._h, int(every), int(levels), 1 if com else 0))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(_lib.load().sgpr_md_msd(self._h, int(every), int(levels), 1 if com else 0))
         self._md["msd"] = (int(every), int(levels)) if every else None
 
     def md_msd_table(self):
@@ -1149,10 +1158,8 @@ class SGPRModel:
         S = len(self.species)
         tab, cnt, info = np.zeros((L, S, 4)), np.zeros(L, dtype=np.int64), np.zeros(2, dtype=np.int64)
         check(_lib.load().sgpr_md_msd_read(self._h, ptr(tab), ptr(cnt), ptr(info)))
-        numbers = np.asarray(self._md["numbers"])
         return dict(lags=every * 2 ** np.arange(L, dtype=np.int64), count=cnt, msd=tab[:, :, 0].copy(), msd_sq=tab[:, :, 1].copy(),
-                    smd=tab[:, :, 2].copy(), smd_sq=tab[:, :, 3].copy(), species=np.array([int(z) for z in self.species]),
-                    n=np.array([int(np.sum(numbers == int(z))) for z in self.species]), samples=int(info[0]), next_due=int(info[1]))
+                    smd=tab[:, :, 2].copy(), smd_sq=tab[:, :, 3].copy(), samples=int(info[0]), next_due=int(info[1]), **self._md_species())
 
     def md_rdf(self, every, rmax, bins=100, rmin=0.0):
         """Accumulate radial distribution functions inside the loop (sgpr_md_rdf; md_rdf.inc has the scheme, workloads.RdfCounts
@@ -1163,12 +1170,7 @@ class SGPRModel:
         detaches.  md_rdf_table() reads the counts, transport.radial_distribution forms g(r).  Langevin, velocity Verlet and
         Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter=, md_meta, md_record and md_msd; a barostat,
         a committee, a relaxation, a band, a polymer, several ranks and an rmax beyond 2.5 cell heights: NotImplementedError."""
-        try:
-            check(_lib.load().sgpr_md_rdf(self._h, int(every), float(rmin), float(rmax), int(bins)))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(_lib.load().sgpr_md_rdf(self._h, int(every), float(rmin), float(rmax), int(bins)))
         self._md["rdf"] = (int(every), int(bins)) if every else None
 
     def md_rdf_table(self):
@@ -1181,8 +1183,8 @@ class SGPRModel:
         S = len(self.species)
         hist, info, geom = np.zeros((S, S, bins), dtype=np.uint64), np.zeros(4 + S, dtype=np.int64), np.zeros(3)
         check(_lib.load().sgpr_md_rdf_read(self._h, ptr(hist), ptr(info), ptr(geom)))
-        return dict(hist=hist, species=np.array([int(z) for z in self.species]), n=info[4:].copy(), samples=int(info[0]), next_due=int(info[1]),
-                    every=every, bins=int(info[2]), rmin=float(geom[1]), rmax=float(geom[2]), volume=float(geom[0]))
+        return dict(hist=hist, samples=int(info[0]), next_due=int(info[1]), every=every, bins=int(info[2]), rmin=float(geom[1]),
+                    rmax=float(geom[2]), volume=float(geom[0]), **self._md_species(info[4:]))
 
     def md_vacf(self, every, lags, origin_every=1, com=False):
         """Accumulate velocity autocorrelations inside the loop (sgpr_md_vacf; md_vacf.inc has the scheme, workloads.VacfRing is
@@ -1195,12 +1197,7 @@ class SGPRModel:
         velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, md_record, md_msd and md_rdf; a
         barostat, a committee, a relaxation, a band, a polymer, several ranks, ml_filter= and md_meta (their closing kick uses
         a force other than the packed one), more than 8192 lags or a ring (lags + 1) * 24 N over 4 GiB: NotImplementedError."""
-        try:
-            check(_lib.load().sgpr_md_vacf(self._h, int(every), int(lags), int(origin_every), 1 if com else 0))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(_lib.load().sgpr_md_vacf(self._h, int(every), int(lags), int(origin_every), 1 if com else 0))
         self._md["vacf"] = (int(every), int(lags)) if every else None
 
     def md_vacf_table(self):
@@ -1213,9 +1210,8 @@ class SGPRModel:
         S = len(self.species)
         tr, col, cnt, info = np.zeros((L, S)), np.zeros((L, S, S)), np.zeros(L, dtype=np.int64), np.zeros(3 + S, dtype=np.int64)
         check(_lib.load().sgpr_md_vacf_read(self._h, ptr(tr), ptr(col), ptr(cnt), ptr(info)))
-        return dict(tracer=tr, collective=col, count=cnt, lags=every * np.arange(L, dtype=np.int64),
-                    species=np.array([int(z) for z in self.species]), n=info[3:].copy(), samples=int(info[0]), pending=int(info[1]),
-                    next_due=int(info[2]))
+        return dict(tracer=tr, collective=col, count=cnt, lags=every * np.arange(L, dtype=np.int64), samples=int(info[0]),
+                    pending=int(info[1]), next_due=int(info[2]), **self._md_species(info[3:]))
 
     def md_vanhove(self, every, levels, rmax, rbins, tbins=1, pbins=1, dmax=None, dbins=0):
         """Accumulate van Hove correlation functions inside the loop (sgpr_md_vanhove; md_vanhove.inc has the scheme,
@@ -1233,13 +1229,8 @@ class SGPRModel:
         NotImplementedError."""
         from .workloads import vanhove_edges
         lib = _lib.load()
-        try:
-            check(lib.sgpr_md_vanhove(self._h, int(every), int(levels), float(rmax), int(rbins), int(tbins), int(pbins),
-                                      float(dmax) if dbins else 0.0, int(dbins)))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(lib.sgpr_md_vanhove(self._h, int(every), int(levels), float(rmax), int(rbins), int(tbins), int(pbins),
+                                    float(dmax) if dbins else 0.0, int(dbins)))
         if every:   # (the edges the twin compares with: numpy's doubles, not this library's)
             ct, cu, su = (np.ascontiguousarray(a, dtype=np.float64) for a in vanhove_edges(tbins, pbins))
             check(lib.sgpr_md_vanhove_edges(self._h, ptr(ct), ptr(cu), ptr(su)))
@@ -1257,10 +1248,9 @@ class SGPRModel:
         hs, over, hd = (np.zeros(shape, dtype=np.uint64) for shape in ((L, S, rbins, tbins, pbins), (L, S), (L, S, S, dbins)))
         cnt, info, geom = np.zeros(L, dtype=np.int64), np.zeros(8 + S, dtype=np.int64), np.zeros(3)
         check(_lib.load().sgpr_md_vanhove_read(self._h, ptr(hs), ptr(over), ptr(hd) if dbins else None, ptr(cnt), ptr(info), ptr(geom)))
-        tab = dict(over=over, distinct=hd, count=cnt, lags=every * 2 ** np.arange(L, dtype=np.int64),
-                   species=np.array([int(z) for z in self.species]), n=info[8:].copy(), samples=int(info[0]), next_due=int(info[1]),
-                   every=every, levels=L, rmax=float(geom[1]), rbins=rbins, tbins=tbins, pbins=pbins, dmax=float(geom[2]), dbins=dbins,
-                   volume=float(geom[0]))
+        tab = dict(over=over, distinct=hd, count=cnt, lags=every * 2 ** np.arange(L, dtype=np.int64), samples=int(info[0]),
+                   next_due=int(info[1]), every=every, levels=L, rmax=float(geom[1]), rbins=rbins, tbins=tbins, pbins=pbins,
+                   dmax=float(geom[2]), dbins=dbins, volume=float(geom[0]), **self._md_species(info[8:]))
         tab["self"] = hs
         return tab
 
@@ -1291,12 +1281,7 @@ class SGPRModel:
         if not 1 <= int(bins) <= 1024:
             raise ValueError("md_adf: 1 <= bins <= 1024")
         ct = np.ascontiguousarray(adf_edges(bins), dtype=np.float64)
-        try:
-            check(lib.sgpr_md_adf(self._h, int(every), int(bins), ptr(cut), ptr(ct)))
-        except _lib.SgprError as e:
-            if e.code == -6:   # SGPR_E_UNSUPPORTED
-                raise NotImplementedError(str(e)) from None
-            raise
+        _attach(lib.sgpr_md_adf(self._h, int(every), int(bins), ptr(cut), ptr(ct)))
         self._md["adf"] = (int(every), int(bins), cut)
 
     def md_adf_table(self):
@@ -1310,8 +1295,8 @@ class SGPRModel:
         S = len(self.species)
         angles, coord, info = np.zeros((S, S, S, bins), dtype=np.uint64), np.zeros((S, S, 64), dtype=np.uint64), np.zeros(4 + S, dtype=np.int64)
         check(_lib.load().sgpr_md_adf_read(self._h, ptr(angles), ptr(coord), ptr(info)))
-        return dict(angles=angles, coord=coord, species=np.array([int(z) for z in self.species]), n=info[4:].copy(), samples=int(info[0]),
-                    next_due=int(info[1]), every=every, bins=int(info[2]), cut=cut.copy())
+        return dict(angles=angles, coord=coord, samples=int(info[0]), next_due=int(info[1]), every=every, bins=int(info[2]), cut=cut.copy(),
+                    **self._md_species(info[4:]))
 
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen

@@ -17,10 +17,34 @@ import numpy as np
 KEYS = ("msd", "msd_sq", "smd", "smd_sq")
 
 
-class Msd:
+class _InLoop:
+    """The face ActiveCalculator.run_md drives every holder through, its only coupling to them.  A holder names the SGPRModel
+    method that attaches its accumulator (`md`; md + "_table" reads it) and its host twin in workloads (`twin_of`), both taking
+    settings() first; the twin is built with the masses or with the cell (`with_masses`) and fed a step's `feeds`.  Where the
+    device loop does not serve the holder: constant_cell (run_md's refusal under a barostat; None: the twin serves one) and
+    host_only() (the host loop feeds the twin)."""
+    feeds, with_masses, constant_cell = "positions", False, None
+
+    def twin(self, masses, numbers, species, cell, pbc):
+        from . import workloads
+        frame = (masses, numbers, species) if self.with_masses else (numbers, species, cell, pbc)
+        return getattr(workloads, self.twin_of)(*self.settings(), *frame)
+
+    def attach(self, engine):
+        getattr(engine, self.md)(*self.settings())
+
+    def read(self, engine):
+        return getattr(engine, self.md + "_table")()
+
+    def host_only(self, npt, committee, ranks, filtered, biased):
+        return bool(npt or committee or ranks > 1)
+
+
+class Msd(_InLoop):
     """Holder of a displacement table: ActiveCalculator.run_md(msd=Msd(every, levels, com)) fills it, the way ml_filter= takes a
     FilterState; add(table) adds the table of a run (SGPRModel.md_msd_table(), MsdBlocks.table()) — the tables of several runs
     with the same settings add up, window by window.  mean() and stderr() are the reference's mean_var per lag."""
+    md, twin_of, with_masses = "md_msd", "MsdBlocks", True
 
     def __init__(self, every, levels, com=False):
         self.every, self.levels, self.com = int(every), int(levels), bool(com)
@@ -29,6 +53,9 @@ class Msd:
         self.species = self.n = None
         for k in KEYS:
             setattr(self, k, None)
+
+    def settings(self):
+        return (self.every, self.levels, self.com)
 
     def add(self, table):
         if not np.array_equal(np.asarray(table["lags"]), self.lags):
@@ -88,15 +115,19 @@ def diffusion_constants(msd, dt_fs):
     return out
 
 
-class Rdf:
+class Rdf(_InLoop):
     """Holder of pair-distance counts: ActiveCalculator.run_md(rdf=Rdf(every, rmax, bins, rmin)) fills it, as msd= fills an Msd;
     add(table) adds the table of a run (SGPRModel.md_rdf_table(), RdfCounts.table()) — the tables of several runs of one frame
     with the same settings add up, count by count.  radial_distribution(holder) forms g(r)."""
+    md, twin_of, constant_cell = "md_rdf", "RdfCounts", "pair distances are counted"
 
     def __init__(self, every, rmax, bins=100, rmin=0.0):
         self.every, self.rmax, self.bins, self.rmin = int(every), float(rmax), int(bins), float(rmin)
         self.samples = 0
         self.hist = self.species = self.n = self.volume = None
+
+    def settings(self):
+        return (self.every, self.rmax, self.bins, self.rmin)
 
     def add(self, table):
         if (int(table["bins"]), float(table["rmin"]), float(table["rmax"])) != (self.bins, self.rmin, self.rmax):
@@ -146,11 +177,12 @@ def radial_distribution(rdf, shells=False):
     return r, g
 
 
-class Adf:
+class Adf(_InLoop):
     """Holder of bond-angle and coordination counts: ActiveCalculator.run_md(adf=Adf(every, bins, cutoffs)) fills it, as rdf= fills
     an Rdf; `cutoffs` is a scalar (all pairs) or a dict {(Z1, Z2): r} of bond cutoffs (pairs that are absent never bond).
     add(table) adds the tables of a run (SGPRModel.md_adf_table(), AdfCounts.table()) — those of several runs of one frame with
     the same settings add up, count by count.  angle_distribution(holder, ...) and coordination(holder, ...) read it."""
+    md, twin_of, constant_cell = "md_adf", "AdfCounts", "bond angles are counted"
 
     def __init__(self, every, bins=180, cutoffs=None):
         if cutoffs is None:
@@ -158,6 +190,9 @@ class Adf:
         self.every, self.bins, self.cutoffs = int(every), int(bins), cutoffs
         self.samples = 0
         self.angles = self.coord = self.species = self.n = self.cut = None
+
+    def settings(self):
+        return (self.every, self.bins, self.cutoffs)
 
     def add(self, table):
         if int(table["bins"]) != self.bins:
@@ -221,11 +256,12 @@ def coordination(table, centre, neighbour):
     return n, P, float(np.sum(n * P))
 
 
-class Vacf:
+class Vacf(_InLoop):
     """Holder of a velocity-correlation table: ActiveCalculator.run_md(vacf=Vacf(every, lags, origin_every, com)) fills it, as
     msd= fills an Msd; add(table) adds the table of a run (SGPRModel.md_vacf_table(), VacfRing.table()) — the tables of several
     runs of one frame with the same settings add up, pair by pair.  mean() gives the curves per species; green_kubo, onsager and
     vibrational_dos read them."""
+    md, twin_of, with_masses, feeds = "md_vacf", "VacfRing", True, "velocities"
 
     def __init__(self, every, lags, origin_every=1, com=False):
         self.every, self.nlags, self.origin_every, self.com = int(every), int(lags), int(origin_every), bool(com)
@@ -233,6 +269,12 @@ class Vacf:
         self.count = np.zeros(self.nlags, dtype=np.int64)
         self.samples = 0
         self.tracer = self.collective = self.species = self.n = None
+
+    def settings(self):
+        return (self.every, self.nlags, self.origin_every, self.com)
+
+    def host_only(self, npt, committee, ranks, filtered, biased):   # (a filtered or a biased run's closing kick is not the packed force's)
+        return bool(super().host_only(npt, committee, ranks, filtered, biased) or filtered or biased)
 
     def add(self, table):
         if not np.array_equal(np.asarray(table["lags"]), self.lags):
@@ -330,11 +372,12 @@ def vibrational_dos(vacf, dt_fs, window="hann"):
     return f, out
 
 
-class VanHove:
+class VanHove(_InLoop):
     """Holder of van Hove tables: ActiveCalculator.run_md(vanhove=VanHove(every, levels, rmax, rbins, tbins, pbins, dmax, dbins))
     fills it, as msd= fills an Msd; add(table) adds the tables of a run (SGPRModel.md_vanhove_table(), VanHoveCounts.table()) —
     the tables of several runs of one frame with the same settings add up, count by count.  displacement_histogram,
     self_van_hove, distinct_van_hove and non_gaussian read them."""
+    md, twin_of, constant_cell = "md_vanhove", "VanHoveCounts", "displacements and pair distances are counted"
 
     def __init__(self, every, levels, rmax, rbins, tbins=1, pbins=1, dmax=None, dbins=0):
         self.every, self.levels, self.rmax = int(every), int(levels), float(rmax)
@@ -345,13 +388,13 @@ class VanHove:
         self.samples = 0
         self.hist = self.over = self.distinct = self.species = self.n = self.volume = None
 
-    def _settings(self):
+    def settings(self):
         return (self.every, self.levels, self.rmax, self.rbins, self.tbins, self.pbins, self.dmax, self.dbins)
 
     def add(self, table):
         got = (int(table["every"]), int(table["levels"]), float(table["rmax"]), int(table["rbins"]), int(table["tbins"]), int(table["pbins"]),
                float(table["dmax"]), int(table["dbins"]))
-        if got != self._settings():
+        if got != self.settings():
             raise ValueError("VanHove.add: the table was taken with other settings (every, levels, rmax, bins, dmax)")
         species, n = np.asarray(table["species"]), np.asarray(table["n"])
         if self.species is None:

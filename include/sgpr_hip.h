@@ -572,8 +572,8 @@ int sgpr_md_frames(sgpr_model *h, int first, int count, int64_t *index, double *
  * halt or an overflow) counts once, the speculative evaluation behind a halt not at all.
  *
  * sgpr_md_msd       every >= 1, 1 <= levels <= 32, com 0 / 1: after sgpr_md_begin (and sgpr_md_fix, _thermostat, _filter, _meta,
- *                   _record, if used), before the first sgpr_md_run; zeroes the table.  every = 0 detaches: the run launches what
- *                   it launched before.  Two small launches behind a sampled evaluation, levels x 3N doubles of device memory.
+ *                   _record, if used), before the first sgpr_md_run; zeroes the table.  every = 0 detaches and frees: the run
+ *                   launches what it launched before.  Two small launches behind a sampled evaluation, levels x 3N doubles of device memory.
  *                   SGPR_E_INVALID: no run begun, a run that has started, values out of range.  SGPR_E_UNSUPPORTED: several
  *                   ranks, a barostat, a committee, a relaxation, a band, a polymer — and from sgpr_md_barostat, _committee,
  *                   _relax, _neb and _pimd on a run that has the accumulator.

@@ -212,6 +212,41 @@ def test_a_later_run_and_the_memory_owe_it_nothing():
     assert np.array_equal(_live() - before, [0, 0])
 
 
+def test_a_detach_gives_the_memory_back_and_a_fresh_attach_starts_from_zeros():
+    """md_msd(0, ...) on a begun run — before its first call and behind one — gives back exactly what the attach took (the way
+    test_hip_vanhove_device.py's detach is checked), md_msd_table then refuses, and the next attach owes the table that went
+    nothing: zeros before the first call, the twin's table behind a run."""
+    from test_hip_teardown import _live
+    mdl, fr, msd = _shared()[0], _frame(), (1, 6, True)
+    _begin(mdl, fr, seed=7)
+    mdl.md_msd(0, 0)                  # (the buffers of the run before are the handle's until a detach or md_end)
+    plain = _live()
+    mdl.md_msd(*msd)
+    held = _live()
+    assert held[0] > plain[0] and held[1] > plain[1]
+    mdl.md_msd(0, 0)
+    assert np.array_equal(_live(), plain)
+    mdl.md_msd(*msd)
+    assert np.array_equal(_live(), held)
+    sc, code = mdl.md_run(6, None)
+    assert code == 0 and mdl.md_msd_table()["count"][0] == 5
+    running = _live()                 # (the call has sized the run's own buffers)
+    mdl.md_msd(0, 0)
+    print(f"live memory plain {list(plain)}, attached {list(held)}, behind a call {list(running)}, detached {list(_live())}")
+    assert np.array_equal(running - _live(), held - plain)
+    with pytest.raises(RuntimeError, match="no accumulator"):
+        mdl.md_msd_table()
+    _begin(mdl, fr, seed=7)
+    mdl.md_record(1, velocities=False, results=False)
+    mdl.md_msd(*msd)
+    zero = mdl.md_msd_table()
+    assert zero["samples"] == 0 and zero["next_due"] == 0 and not np.any(zero["count"])
+    assert not any(np.any(zero[k]) for k in KEYS)
+    sc, code = mdl.md_run(10, None)
+    assert code == 0
+    _same(mdl.md_msd_table(), _twin(fr, msd, mdl.md_frames()["positions"]), "a fresh attach behind a detach")
+
+
 def test_refusals_in_both_directions_leave_the_handle_working():
     from autoforce_amd import _lib
     from autoforce_amd.ase_shim import kB
