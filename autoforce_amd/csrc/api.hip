@@ -2652,6 +2652,9 @@ struct StepNext {
     FinNext md;                        // mode 2: the integrator's fields (the binning fields are filled in launch_finalize)
 };
 
+// md_host.inc: what an MD run's features (filter, bond angles, bias) refuse and enqueue in a mode-2 step; fused_gather: it takes the gather form of the fused last kernel
+static int md_before_last(sgpr_model *h, const StepNext &nx, bool fused_gather, const double *cell_dev, unsigned step, hipStream_t st);
+
 static void launch_finalize(sgpr_model *h, bool gather, int nE, int nV, bool beta, double mean_energy,
                             double *packed_dev, hipStream_t st, const FinBatch *fb = nullptr, const StepNext *nx = nullptr,
                             unsigned step = 0, bool xp = false, const ShardSrc *consume = nullptr)
@@ -2882,58 +2885,8 @@ static int enqueue_step(sgpr_model *h, const double *pos_dev, const double *cell
     const bool shard_next = can_next && !gather && (px || (nx->mode == 2 && h->world == 1)) && !no_exchange;
     const bool fuse = can_next && !shard_next &&
                       ((gather && h->comm == nullptr) || (nx->mode == 1 && !gather && h->world > 1 && !px));
-    if (nx && nx->mode == 2 && nx->md.filt_cur && !(fuse && gather))
-        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
-    if (nx && nx->mode == 2 && h->md.run.adf.every && !(fuse && gather))
-        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) read the step's list and its overflow word behind the gather form of the "
-                                        "fused last kernel only");
-    if (nx && nx->mode == 2 && h->md.run.meta.on) {
-        // the bias of this configuration (sgpr_md_meta), behind the reverse pass's own sums and in front of the kernel that reads them
-        const MdState &m = h->md;
-        if (!(fuse && gather))
-            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
-                                            "and sharded frames take the host loop around calculate()");
-        const long long n = nx->md.t_index;
-        MetaQl ql = m.run.meta.ql;
-        if (m.run.meta.nql) {
-            // a qlvar reads this step's list; its rows in LDS are sized for META_QL_MAXT selected neighbours (the list may have grown)
-            if ((long long)m.run.meta.nql * h->maxnn > META_QL_MAXT)
-                return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias has %d qlvar component(s) and the neighbour list holds up to %d entries per atom; together at "
-                                                "most %d (the host loop around calculate() serves longer lists)", m.run.meta.nql, h->maxnn, META_QL_MAXT);
-            ql.nn = h->d_nn.p; ql.nbr_j = h->d_nbr_j.p; ql.nbr_code = h->d_nbr_shift.p; ql.cell = cell_dev; ql.maxnn = h->maxnn;
-        }
-        if (m.run.meta.nql && m.run.meta.merge) {
-            const long long want = m.run.meta_slot(n) / m.run.meta.merge;
-            for (long long &j = h->md.run.meta.enq; j < want; j++) {
-                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.run.meta.par.D, m.run.meta.merge, (int)j, (const double *)m.meta.centre.p,
-                                   (const int *)m.meta.key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
-                stamp(h, "md_meta_merge", st);
-            }
-            hipLaunchKernelGGL(md_meta_merged_ql_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, ql, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
-                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
-                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
-        } else if (m.run.meta.nql) {
-            hipLaunchKernelGGL(md_meta_ql_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, ql, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
-                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
-                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
-        } else if (m.run.meta.merge) {
-            // the chunks that lie below this configuration and are not merged yet: at a crossing, or at the first configuration
-            // of a call that is behind
-            const long long want = m.run.meta_slot(n) / m.run.meta.merge;
-            for (long long &j = h->md.run.meta.enq; j < want; j++) {
-                hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, m.run.meta.par.D, m.run.meta.merge, (int)j, (const double *)m.meta.centre.p,
-                                   (const int *)m.meta.key.p, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
-                stamp(h, "md_meta_merge", st);
-            }
-            hipLaunchKernelGGL(md_meta_merged_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
-                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
-                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, m.meta_tab(want), (const int *)nx->md.halt, (int)step);
-        } else
-            hipLaunchKernelGGL(md_meta_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, m.run.meta.par, nx->md.x_cur, (const unsigned char *)m.meta.sel.p,
-                               m.meta.centre.p, m.meta.key.p, m.meta.rows.p, (int)m.run.meta_slot(n), n % m.run.meta.pace == 0 ? (int)m.run.meta_slot(n) : -1,
-                               h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, (const int *)nx->md.halt, (int)step);
-        stamp(h, "md_meta", st);
-    }
+    if (nx && nx->mode == 2)
+        if (const int rm = md_before_last(h, *nx, fuse && gather, cell_dev, step, st)) return rm;
     const bool xp = !gather && (px || shard_next);
     const size_t xlen = peer_xlen(N, h->world);
     if (xp && h->d_xpacked.n < xlen + 1 && h->d_xpacked.alloc(xlen + 1)) return fail(SGPR_E_NODEVICE, "hipMalloc failed (exchange buffer)");

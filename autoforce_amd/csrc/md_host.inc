@@ -817,6 +817,92 @@ static void md_fill_integrator(const MdState &m, int j, const double *noise_dev,
     if (m.run.filter.on) { x.filt_cur = m.filter.f.p + N3 * sl; x.filt_next = m.filter.f.p + N3 * sn; x.shrink = m.run.filter.shrink; }
 }
 
+// The moving-cell fields of the same record: the ring slots of this evaluation's cell and the next one's, the scaled coordinates.
+static void md_fill_moving_cell(const MdState &m, int j, FinNext &x)
+{
+    const size_t N3 = (size_t)3 * m.run.N, RG = (size_t)m.run.ring, sl = (size_t)(m.run.t + j) % RG, sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+    x.npt_cur = m.slot(m.run.t + j); x.npt_next = m.slot(m.run.t + j + 1);
+    x.q_cur = m.npt.Q.p + N3 * sl; x.q_prev = m.npt.Q.p + N3 * sp; x.q_next = m.npt.Q.p + N3 * sn;
+}
+
+// The cutoffs md_npt_kernel's grids and rebuild rule go by: the lists' as enqueue_step sets it, the model's.
+static void md_npt_cutoffs(sgpr_model *h) { NptParams &p = h->md.run.npt.par; p.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); p.rc_phys = h->rc; }
+
+// The thermostat behind evaluation j of a call, whose results are in `packed`.  Moving cell: zeta, eta and the matrices of the next configuration, the cell after
+// it (md_npt.inc; a filter's stress jumps too).  Else Nose-Hoover: zeta of the next configuration from this one's kinetic energy (the next launch's waves need it).
+static void md_thermostat_launch(sgpr_model *h, int j, int step, const double *packed, hipStream_t st)
+{
+    const MdState &m = h->md;
+    const int N = m.run.N, sl = (int)((m.run.t + j) % m.run.ring), n30 = (int)((m.run.t + j) & 0x3fffffff);
+    double *ke = m.KE.p + (size_t)2 * N * sl, *row = m.scal_d.p + (size_t)SGPR_MD_SCAL * j;
+    if (m.run.npt.on)
+        hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p, ke, (const double *)(m.V.p + (size_t)3 * N * sl),
+                           (const double *)m.mass.p, packed, (const double *)h->d_cell0.p, n30, (const int *)m.halt.p, step, row, m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j,
+                           m.run.filter.on ? (const double *)(m.filter.s.p + 6 * ((m.run.t + j) & 3)) : (const double *)nullptr,
+                           m.run.filter.on ? m.filter.s.p + 6 * ((m.run.t + j + 1) & 3) : (double *)nullptr, m.run.filter.shrink);
+    else if (m.run.nh.on)
+        hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, ke, m.zeta.p, n30, m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, (const int *)m.halt.p, step, row);
+}
+
+// The checked pass of a handle nothing has sized for its bound system yet (synchronised, capacities grown, results discarded).
+static int md_warm(sgpr_model *h, const double *pos, const double *cell, double *packed, hipStream_t st)
+{
+    const int rc_ = h->warm ? SGPR_OK : run_checked(h, pos, cell, packed, st);
+    if (!rc_) h->warm = true;
+    return rc_;
+}
+
+// What the bias and the bond angles ask of a handle's settings before anything is enqueued (what a step then takes is md_before_last's fused_gather, not this).
+static bool md_gather_form(const sgpr_model *h) { return !(h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile)); }
+
+// A qlvar's rows in LDS are sized for META_QL_MAXT selected neighbours over its components.  `tail`: how the caller's message ends.
+static int md_meta_ql_fits(const sgpr_model *h, const char *tail)
+{
+    if ((long long)h->md.run.meta.nql * h->maxnn <= META_QL_MAXT) return SGPR_OK;
+    return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias has %d qlvar component(s) and the neighbour list holds up to %d entries per atom; together at "
+                                    "most %d%s", h->md.run.meta.nql, h->maxnn, META_QL_MAXT, tail);
+}
+
+// enqueue_step's one call for a step of sgpr_md_run: what the run's features refuse when the step did not take the gather form of the fused last kernel,
+// then the bias of this configuration (sgpr_md_meta), behind the reverse pass's own sums and in front of the kernel that reads them.
+static int md_before_last(sgpr_model *h, const StepNext &nx, bool fused_gather, const double *cell_dev, unsigned step, hipStream_t st)
+{
+    MdState &m = h->md;
+    MdRun::Meta &b = m.run.meta;
+    if (nx.md.filt_cur && !fused_gather) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the filter (sgpr_md_filter) runs in the gather form of the fused last kernel only");
+    if (m.run.adf.every && !fused_gather)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) read the step's list and its overflow word behind the gather form of the "
+                                        "fused last kernel only");
+    if (!b.on) return SGPR_OK;
+    if (!fused_gather)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only: the scatter form "
+                                        "and sharded frames take the host loop around calculate()");
+    const long long n = nx.md.t_index, want = b.merge ? m.run.meta_slot(n) / b.merge : 0;
+    const int N = h->N, nh = (int)m.run.meta_slot(n), own = n % b.pace == 0 ? nh : -1;   // (nh: the rows below this configuration; own: its own where it deposits)
+    if (const int rq = md_meta_ql_fits(h, " (the host loop around calculate() serves longer lists)")) return rq;   // (a qlvar reads this step's list, which may have grown)
+    MetaQl ql = b.ql;
+    ql.nn = h->d_nn.p; ql.nbr_j = h->d_nbr_j.p; ql.nbr_code = h->d_nbr_shift.p; ql.cell = cell_dev; ql.maxnn = h->maxnn;
+    // the merged form: the chunks that lie below this configuration and are not merged yet — at a crossing, or at the first configuration of a call that is behind
+    const MetaTab tb = m.meta_tab(want);
+    for (long long &j = b.enq; j < want; j++) {
+        hipLaunchKernelGGL(md_meta_merge_kernel, dim3(1), dim3(256), 0, st, b.par.D, b.merge, (int)j, (const double *)m.meta.centre.p,
+                           (const int *)m.meta.key.p, tb, (const int *)nx.md.halt, (int)step);
+        stamp(h, "md_meta_merge", st);
+    }
+    // md_meta.inc's four entry points take one argument list but for a qlvar's MetaQl (q) and the merged form's MetaTab (t)
+    auto with = [&](auto... q) {
+        return [&, q...](auto kernel, auto... t) {
+            hipLaunchKernelGGL(kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, b.par, q..., nx.md.x_cur, (const unsigned char *)m.meta.sel.p, m.meta.centre.p,
+                               m.meta.key.p, m.meta.rows.p, nh, own, h->d_F.p + 3 * (size_t)N, h->d_Epart.p, h->d_virpart.p, h->virpart_len, t...,
+                               (const int *)nx.md.halt, (int)step);
+        };
+    };
+    if (b.nql) b.merge ? with(ql)(md_meta_merged_ql_kernel, tb) : with(ql)(md_meta_ql_kernel);
+    else b.merge ? with()(md_meta_merged_kernel, tb) : with()(md_meta_kernel);
+    stamp(h, "md_meta", st);
+    return SGPR_OK;
+}
+
 // The close of a call: the scalar rows of the evaluations that stand to the caller — columns 14 and 15 are zeta and its time
 // integral under Nose-Hoover, a relaxation's own (keep_14_15), else spare: zeroed — and what the call reports.
 // The configuration is evaluated as far as the next call goes behind the covloss gate (1), convergence (3: a relaxation and a band
@@ -1067,12 +1153,7 @@ static int md_relax_run(sgpr_model *h, int nevals, double ediff, int final_eval,
     if (const int rp = md_prepare_call(h, nevals, st, true)) return rp;
     auto cell_of = [&](long long n) -> double * { return m.relax.cells.p + (size_t)RLX_CELL * (size_t)(n % RG); };
     m.run.relax.started = true; m.run.started = true;
-    if (!h->warm) {
-        const int sw = (int)(m.run.t % RG);
-        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * sw, cell_of(m.run.t), m.P.p + plen * sw, st);
-        if (rc_) return rc_;
-        h->warm = true;
-    }
+    if (const int rw = md_warm(h, m.X.p + (size_t)3 * N * (m.run.t % RG), cell_of(m.run.t), m.P.p + plen * (m.run.t % RG), st)) return rw;
     md_call_start(h, c);
     if (const int rl = md_reset_lists(h, st)) return rl;
     const unsigned step0 = c.step0; const double gate = c.gate;
@@ -1280,23 +1361,15 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     // where the capacities are not sized for this system, lists rebuilt by the first evaluation, bin populations cleared
     // (moving cell: the cell of configuration n is in the ring once the trajectory has started — md_npt_start, below, whose own
     // checked passes size the capacities of every handle; the cell of sgpr_md_begin until then)
-    if (cellrun) { m.run.npt.par.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.run.npt.par.rc_phys = h->rc; }   // (as sgpr_md_run sets them)
+    if (cellrun) md_npt_cutoffs(h);
     const bool start = cellrun && !m.run.npt.started;
     auto cell_of = [&](long long n) -> const double * { return (cellrun && m.run.npt.started) ? m.slot(n)->h : m.cell.p; };
-    if (!h->warm && !start) {
-        const int rc_ = run_checked(h, m.X.p + N3 * s0, cell_of(m.run.t), m.bcm.P.p + plen * K, st);
-        if (rc_) return rc_;
-        h->warm = true;
-    }
+    if (const int rw = start ? SGPR_OK : md_warm(h, m.X.p + N3 * s0, cell_of(m.run.t), m.bcm.P.p + plen * K, st)) return rw;
     for (int k = 0; k < K; k++) {
         sgpr_model *mk = m.run.bcm.members[k];
         if (!md_same_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1))
             if (const int rb = sgpr_bind_system(mk, N, m.run.numbers.data(), m.run.pbc, 0, 1)) return rb;
-        if (!mk->warm && !start) {
-            const int rc_ = run_checked(mk, m.bcm.x.p, cell_of(m.run.t), m.bcm.P.p + plen * k, st);
-            if (rc_) return rc_;
-            mk->warm = true;
-        }
+        if (const int rw = start ? SGPR_OK : md_warm(mk, m.bcm.x.p, cell_of(m.run.t), m.bcm.P.p + plen * k, st)) return rw;
     }
     if (start) {
         if (const int rs = md_npt_start(h, st, nevals)) return rs;
@@ -1311,7 +1384,7 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
     const unsigned step0 = c.step0; const double gate = c.gate;
     const bool pend0 = m.run.t > 0;   // (the closing half kick of the first configuration: due unless it is the start of the trajectory)
     const int rc_ = md_enqueue_ahead(h, nevals, st, &c.enq, [&](int j) -> int {
-        const int sl = (int)((m.run.t + j) % RG), sn = (sl + 1) % RG, sp = (sl + RG - 1) % RG;
+        const int sl = (int)((m.run.t + j) % RG);
         for (int k = 0; k < K; k++) {
             sgpr_model *mk = m.run.bcm.members[k];
             const int re = enqueue_step(mk, m.bcm.x.p, cell_of(m.run.t + j), m.bcm.P.p + plen * k, st, nullptr);
@@ -1329,22 +1402,12 @@ static int md_committee_run(sgpr_model *h, int nevals, const double *noise, doub
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         x.step = step;   // (the fused loop: enqueue_step sets it)
         const bool stay = final_eval && j == nevals - 1;
-        if (cellrun) {   // (the ring slots of this evaluation and the next, the scaled coordinates: as sgpr_md_run fills them)
-            x.npt_cur = m.slot(m.run.t + j); x.npt_next = m.slot(m.run.t + j + 1);
-            x.q_cur = m.npt.Q.p + N3 * sl; x.q_prev = m.npt.Q.p + N3 * sp; x.q_next = m.npt.Q.p + N3 * sn;
-        }
+        if (cellrun) md_fill_moving_cell(m, j, x);
         hipLaunchKernelGGL(cellrun ? md_bcm_move_kernel<true> : md_bcm_move_kernel<false>, dim3((N + 63) / 64), dim3(256), 0, st, N, K1, plen,
                            (const double *)m.bcm.P.p, (const double *)info, packed, m.bcm.x.p, (const int *)h->d_perm.p, x, stay ? 1 : 0);
         hipLaunchKernelGGL(md_bcm_ke_kernel, dim3(1), dim3(256), 0, st, N, (const double *)(m.KE.p + (size_t)2 * N * sl), (const int *)m.halt.p,
                            step, row);
-        if (cellrun)   // zeta, eta and the matrices of the next configuration, the cell after it, from the committee's virial in `packed`
-            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p,
-                               (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + N3 * sl), (const double *)m.mass.p,
-                               (const double *)packed, (const double *)h->d_cell0.p, (int)((m.run.t + j) & 0x3fffffff), (const int *)m.halt.p, step, row,
-                               m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j, (const double *)nullptr, (double *)nullptr, 0.0);
-        else if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy
-            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.run.t + j) & 0x3fffffff),
-                               m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, m.halt.p, step, row);
+        md_thermostat_launch(h, j, step, packed, st);   // (the barostat: from the committee's virial in `packed`; no filter: it and a committee refuse each other)
         return SGPR_OK;
     });
     for (int k = 0; k < K; k++) m.run.bcm.members[k]->lists_valid = false;
@@ -1462,10 +1525,8 @@ static int md_replica_run(sgpr_model *h, int nevals, const double *noise, double
     m.run.rep.info.clear();
     if (!h->warm) {   // the checked pass grows capacities: over every replica
         const size_t sw = (size_t)(m.run.t % RG);
-        for (int i = 0; i < R; i++) {
-            const int rc_ = run_checked(h, m.rep.X.p + RN3 * sw + N3 * i, m.cell.p, m.rep.P.p + plen * (R * sw + i), st);
-            if (rc_) return rc_;
-        }
+        for (int i = 0; i < R; i++)
+            if (const int rc_ = run_checked(h, m.rep.X.p + RN3 * sw + N3 * i, m.cell.p, m.rep.P.p + plen * (R * sw + i), st)) return rc_;
         h->warm = true;
     }
     md_call_start(h, c);
@@ -1765,13 +1826,11 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     const size_t plen = c.plen;
     if (m.run.meta.on) {
         // the bias rides in the single-rank gather form of the fused last kernel: what cannot take that form is refused here, before
-        // anything is enqueued (enqueue_step keeps its own check for what only a checked pass finds out: lists beyond the gather form)
-        if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
+        // anything is enqueued (md_before_last keeps the step's own check for what only a checked pass finds out: lists beyond the gather form)
+        if (!md_gather_form(h))
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias (sgpr_md_meta) runs in the gather form of the fused last kernel only (one rank, no graph "
                         "replay, no side-stream fork, a skin > 0): the host loop around calculate() serves this run");
-        if ((long long)m.run.meta.nql * h->maxnn > META_QL_MAXT)
-            return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bias has %d qlvar component(s) and the neighbour list holds up to %d entries per atom; together at "
-                        "most %d: the host loop around calculate() serves this run", m.run.meta.nql, h->maxnn, META_QL_MAXT);
+        if (const int rq = md_meta_ql_fits(h, ": the host loop around calculate() serves this run")) return rq;
         // the last configuration of the call that deposits a hill must find its row
         const long long nd = (m.run.t + nevals - 1) / m.run.meta.pace * m.run.meta.pace;
         if (nd >= m.run.t && m.run.meta_slot(nd) >= m.run.meta.cap)
@@ -1788,7 +1847,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     }
     if (m.run.adf.every) {
         // the bond angles read the list that the forward pass leaves behind the fused last kernel: the forms md_meta's qlvar takes
-        if (h->world != 1 || !h->gather_ok || h->use_graph || !h->fuse_next || !(h->skin > 0.0) || h->comm || (h->use_fork && h->side && !h->profile))
+        if (!md_gather_form(h))
             return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the bond angles (sgpr_md_adf) read the step's neighbour list behind the gather form of the fused last "
                         "kernel only (one rank, no graph replay, no side-stream fork, a skin > 0): the frame record and workloads.AdfCounts serve this run");
         size_t bytes = 0;
@@ -1800,18 +1859,13 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
     MdBinIdentity guard(h);
     if (const int rp = md_prepare_call(h, nevals, st, m.run.npt.on)) return rp;   // (the cell record: a moving cell only)
     if (const int ru = md_upload_noise(h, nevals, noise, st)) return ru;
-    // the first evaluation sizes the capacities for this configuration if nothing has yet (synchronised, results discarded)
     const int RG = m.run.ring, s0 = (int)(m.run.t % RG);
-    if (m.run.npt.on) { m.run.npt.par.rc_list = h->rc + (h->use_graph ? 0.0 : h->skin); m.run.npt.par.rc_phys = h->rc; }   // (the lists' cutoff as enqueue_step sets it)
+    if (m.run.npt.on) md_npt_cutoffs(h);
     if (m.run.npt.on && !m.run.npt.started)
         if (const int rs = md_npt_start(h, st)) return rs;
     // (moving cell: the cell of configuration n is in the ring)
     auto cell_of = [&](long long n) -> const double * { return m.run.npt.on ? m.slot(n)->h : m.cell.p; };
-    if (!h->warm) {
-        const int rc_ = run_checked(h, m.X.p + (size_t)3 * N * s0, cell_of(m.run.t), m.P.p + plen * s0, st);
-        if (rc_) return rc_;
-        h->warm = true;
-    }
+    if (const int rw = md_warm(h, m.X.p + (size_t)3 * N * s0, cell_of(m.run.t), m.P.p + plen * s0, st)) return rw;
     // the continuation of the last call (nothing else ran on the handle since, no re-binding, no option touched): its candidate
     // lists stand and its last kernel has binned this call's first configuration.  Otherwise: whatever ran in between — a model
     // update evaluates other frames — may have left other lists and bin populations (a run that halted: those of a step that
@@ -1835,8 +1889,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         FinNext &x = nx.md;
         md_fill_integrator(m, j, noise ? m.noise.p : nullptr, pend0, x);
         if (m.run.npt.on) {
-            x.npt_cur = m.slot(m.run.t + j); x.npt_next = m.slot(m.run.t + j + 1);
-            x.q_cur = m.npt.Q.p + (size_t)3 * N * sl; x.q_prev = m.npt.Q.p + (size_t)3 * N * sp; x.q_next = m.npt.Q.p + (size_t)3 * N * sn;
+            md_fill_moving_cell(m, j, x);
             nx.cell_next = x.npt_next->h;
             h->step_grid = &x.npt_cur->grid;
         }
@@ -1853,16 +1906,7 @@ extern "C" int sgpr_md_run(sgpr_model *h, int nevals, const double *noise, doubl
         h->lists_valid = true;  // (the first evaluation rebuilt the candidates; an overflow halts the run: FinNext)
         if (!h->pre_valid) return fail(SGPR_E_UNSUPPORTED, "sgpr_md_run: the fused last kernel is not available for this model / frame (sharded "
                                         "without the library's own exchange, graph capture or a zero skin)");
-        if (m.run.npt.on)  // zeta, eta and the matrices of the next configuration, the cell after it (md_npt.inc)
-            hipLaunchKernelGGL(md_npt_kernel, dim3(1), dim3(256), 0, st, N, m.run.npt.par, (NptSlot *)m.npt.ring.p, m.zeta.p,
-                               (const double *)(m.KE.p + (size_t)2 * N * sl), (const double *)(m.V.p + (size_t)3 * N * sl), (const double *)m.mass.p,
-                               (const double *)(m.P.p + plen * sl), (const double *)h->d_cell0.p, (int)((m.run.t + j) & 0x3fffffff), (const int *)m.halt.p,
-                               (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j, m.npt.cells_d.p + (size_t)SGPR_MD_CELL * j,
-                               m.run.filter.on ? (const double *)(m.filter.s.p + 6 * ((m.run.t + j) & 3)) : (const double *)nullptr,
-                               m.run.filter.on ? m.filter.s.p + 6 * ((m.run.t + j + 1) & 3) : (double *)nullptr, m.run.filter.shrink);
-        else if (m.run.nh.on)   // zeta of the next configuration from this one's kinetic energy (every integrating wave of the next launch needs it)
-            hipLaunchKernelGGL(md_nh_kernel, dim3(1), dim3(256), 0, st, N, m.KE.p + (size_t)2 * N * sl, m.zeta.p, (int)((m.run.t + j) & 0x3fffffff),
-                               m.run.dt, m.run.nh.c1, m.run.nh.c2, m.run.nh.K0, m.halt.p, (int)(step0 + j), m.scal_d.p + (size_t)SGPR_MD_SCAL * j);
+        md_thermostat_launch(h, j, (int)(step0 + j), m.P.p + plen * sl, st);
         // (the frame: the last kernel has written this evaluation's results and, Nose-Hoover, its centred velocity; the slots
         // read here are written again only when the rings come round)
         if (m.run.rec.every && (m.run.t + j) % m.run.rec.every == 0) md_record_frame(h, j, (int)(step0 + j), st);

@@ -326,6 +326,31 @@ def test_run_md_with_a_filter_equals_the_twin_around_calculate(tmp_path):
     assert [o[1] for o in po[j + 2:]] != [o[1] for o in do[j + 2:]]
 
 
+def test_the_scatter_form_refuses_the_filter_inside_the_step_and_the_handle_runs_on():
+    """The filter has no check in front of the run: with option reverse_scatter set, the step itself refuses it (behind its
+    reverse pass, before the last kernel).  Back in the gather form the same run, begun again, gives the rows of a handle that
+    never saw the option, bit for bit."""
+    from autoforce_amd import _lib
+    mdl, numbers, pos, cell, pbc, mass, vel, fx = _setup()
+    lib = _lib.load()
+    kw = dict(friction=FRICTION, seed=5, ml_filter=SHRINK)
+    _begin(mdl, numbers, pos, cell, pbc, mass, vel, **kw)
+    _lib.check(lib.sgpr_set_option(mdl.handle, b"reverse_scatter", 1))
+    with pytest.raises(_lib.SgprError) as e:
+        mdl.md_run(3)
+    assert e.value.code == _lib.E_UNSUPPORTED and "gather form of the fused last kernel only" in str(e.value), str(e.value)
+    _lib.check(lib.sgpr_set_option(mdl.handle, b"reverse_scatter", 0))
+    _begin(mdl, numbers, pos, cell, pbc, mass, vel, **kw)
+    sc, code = mdl.md_run(3)
+    assert code == 0 and len(sc) == 3
+    fresh = _setup()[0]
+    _begin(fresh, numbers, pos, cell, pbc, mass, vel, **kw)
+    ref, code = fresh.md_run(3)
+    assert code == 0 and len(ref) == 3 and np.array_equal(sc, ref)
+    fresh.close()
+    mdl.close()
+
+
 def test_error_cases_leave_the_handle_working():
     from autoforce_amd import _lib
     from autoforce_amd.workloads import FS
