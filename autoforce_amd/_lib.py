@@ -103,6 +103,8 @@ SIGNATURES = {
     "sgpr_md_vanhove_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sgpr_md_adf": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sgpr_md_adf_read": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "sgpr_md_sq": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),
+    "sgpr_md_sq_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "sgpr_md_committee": (C.c_int, [_vp, C.c_int, _vp]),
     "sgpr_md_committee_info": (C.c_int, [_vp, _vp, _vp]),
     "sgpr_md_filter": (C.c_int, [_vp, _dbl, _vp, _vp]),

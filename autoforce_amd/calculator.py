@@ -553,7 +553,7 @@ class ActiveCalculator(Calculator):
 
     def run_md(self, atoms, steps, temperature_K, dt_fs=1.0, friction=1e-3, rng=None, chunk=256, seed=1, sync_every=None,
                tdamp_fs=None, pfactor=None, externalstress=0.0, mask=None, iso=False, record=True, ml_filter=None, msd=None, rdf=None,
-               vacf=None, vanhove=None, adf=None):
+               vacf=None, vanhove=None, adf=None, sq=None):
         """`steps` steps of Langevin NVT (friction = 0: NVE) from atoms.positions / velocities, as cl/md.py:117-128 sets
         it up around this calculator — but the state stays in device memory between model updates: the integrator runs
         inside the step's last kernel (SGPRModel.md_run), the host reads 16 scalars per step and writes the same log
@@ -634,7 +634,14 @@ class ActiveCalculator(Calculator):
         coordination read it), by the same conventions: the device loop counts them itself from the step's neighbour list
         (SGPRModel.md_adf: two launches behind a sampled evaluation, the tables read once at the end; every cutoff at most the
         model's); with a committee or several ranks, and in the host loops, workloads.AdfCounts — the same integers — is fed the
-        positions of every step.  The cell is constant: with a barostat NotImplementedError."""
+        positions of every step.  The cell is constant: with a barostat NotImplementedError.
+        sq: a transport.Sq(every, hkl, lags, origin_every) holder — the partial structure factors and coherent intermediate
+        scattering functions of the run's configurations 0 ... steps at the wave vectors `hkl` of the cell's reciprocal lattice
+        (transport.q_vectors) are added to it at the end (transport.structure_factor, intermediate_scattering and
+        dynamic_structure_factor read it), by the same conventions: the device loop accumulates them itself (SGPRModel.md_sq:
+        three launches behind a sampled evaluation, the tables read once at the end); with a committee or several ranks, and in
+        the host loops, workloads.SqRing — the same definition, equal within md_sq.inc's bound — is fed the positions of every
+        step.  The cell is constant: with a barostat NotImplementedError."""
         from .ase_shim import kB
         from .workloads import FS, MASS, FilterState, langevin_nvt, nose_hoover_nvt, npt_moving_cell
         flt = ml_filter if (ml_filter is None or hasattr(ml_filter, "shrink")) else FilterState(float(ml_filter))
@@ -644,7 +651,7 @@ class ActiveCalculator(Calculator):
         if npt and not nh:
             raise ValueError("run_md: a barostat (pfactor) needs the Nose-Hoover thermostat (tdamp_fs)")
         # the holders given, by keyword, driven through the face they share (transport._InLoop)
-        holders = {k: a for k, a in dict(msd=msd, rdf=rdf, vacf=vacf, vanhove=vanhove, adf=adf).items() if a is not None}
+        holders = {k: a for k, a in dict(msd=msd, rdf=rdf, vacf=vacf, vanhove=vanhove, adf=adf, sq=sq).items() if a is not None}
         for k, a in holders.items():
             if npt and a.constant_cell:
                 raise NotImplementedError(f"run_md: {k}= with a barostat (pfactor): {a.constant_cell} at constant cell")

@@ -305,6 +305,10 @@ struct MdRun {
     // angle bins per (centre, end, end) of the S species of the model's table, nch chunks of centres of one species each; lds: the
     // form with LDS counters
     struct Adf { int every = 0, bins = 0, nch = 0, S = 0; bool lds = true; std::vector<int> nz; } adf;
+    // the structure factors and intermediate scattering functions (sgpr_md_sq, md_sq.inc): every `every`-th configuration is a
+    // sample, nq wave vectors of the reciprocal lattice, `lags` lags of one sample each, origins every `origin_every`-th sample;
+    // nch chunks of one species each — 64 atoms wide, 32 (narrow) where an index exceeds 16 —, S species of the model's table
+    struct Sq { int every = 0, nq = 0, lags = 0, origin_every = 1, nch = 0, S = 0; bool narrow = false; std::vector<int> nz; } sq;
     // the Bayesian committee (sgpr_md_committee, md_bcm.inc): the frozen members, BORROWED handles evaluated beside the live model
     // at every configuration (empty: the run is the one without a committee and launches what it launched before)
     struct Bcm {
@@ -412,6 +416,13 @@ struct MdState {
         DevBuf<int> tab;                            // [nch][3] the chunks | [S] a species' atoms
         bool held() const { return ctl.p != nullptr; }
     } adf;
+    struct SqBufs {
+        DevBuf<double> part, ring, mean, f;   // [nch][nq][2], [lags][nq][S][2], [nq][S][2], [lags][nq][S][S]
+        DevBuf<double> inv;                   // [3][3] the inverse of the run's cell: s_c = sum_k x_k inv[k][c]
+        DevBuf<long long> ctl;                // next_due | samples | count[lags]
+        DevBuf<int> tab;                      // [nch][2] the chunks | [S + 1] a species' chunks | [nq][3] the wave vectors
+        bool held() const { return ctl.p != nullptr; }
+    } sq;
     struct {
         DevBuf<double> P;          // [K + 1][4N + 11] packed results of one evaluation's plain steps, the live model last
         DevBuf<double> x;          // [N][3] the current positions in caller atom order: what the members bin
@@ -1340,6 +1351,7 @@ __global__ __launch_bounds__(256) void md_nh_kernel(int N, const double *ke, dou
 #include "md_vacf.inc"
 #include "md_vanhove.inc"
 #include "md_adf.inc"
+#include "md_sq.inc"
 #include "md_meta.inc"
 
 // The same gather, and with it the first kernel of the NEXT step (FinNext): a 16-lane row takes an atom to its next

@@ -1,11 +1,11 @@
 // md_host.inc — the host side of the device-resident loops (sgpr_md_*), included by api.hip behind the step's entry points.
 // One run at a time per handle (MdRun, api.hip), begun by sgpr_md_begin and shaped by the attach functions, one per mode:
 // sgpr_md_thermostat (Nose-Hoover), _barostat (the moving cell), _relax (FIRE on atoms and cell; _relax_lbfgs: L-BFGS in its place), _fix (held components),
-// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _vanhove (displacement and pair histograms per lag), _adf (bond angles and coordination), _committee (the Bayesian committee), _neb
+// _filter (model-update jumps), _meta and _meta_merge (metadynamics), _record (frames), _msd (displacements), _rdf (pair distances), _vacf (velocity correlations), _vanhove (displacement and pair histograms per lag), _adf (bond angles and coordination), _sq (structure factors and F(q, t)), _committee (the Bayesian committee), _neb
 // (the nudged elastic band), _pimd (the ring polymer).  sgpr_md_run drives dynamics itself and hands a relaxation and a committee
 // to md_relax_run and md_committee_run, a band and a polymer — R replicas evaluated by the one handle — to md_replica_run with
 // the mode's three launches (md_neb_run, md_pimd_run); the four share the look-ahead driver and the frame of a call (MdCall).
-// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_vanhove.inc, md_adf.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
+// The kernels are in api.hip, md_npt.inc, md_relax.inc, md_record.inc, md_msd.inc, md_rdf.inc, md_vacf.inc, md_vanhove.inc, md_adf.inc, md_sq.inc, md_bcm.inc, md_neb.inc, md_pimd.inc and md_meta.inc (the
 // one small kernel of sgpr_md_filter_push stands beside it, further down).
 //
 // The reference integrates in ASE (cl/md.py:117-128: ase.md.langevin.Langevin around ActiveCalculator; velocities
@@ -52,6 +52,7 @@ static int md_rdf_sample(sgpr_model *h, int j, int step, hipStream_t st);
 static int md_vacf_sample(sgpr_model *h, int j, int step, hipStream_t st);
 static int md_vh_sample(sgpr_model *h, int j, int step, hipStream_t st);
 static int md_adf_sample(sgpr_model *h, int j, int step, hipStream_t st);
+static int md_sq_sample(sgpr_model *h, int j, int step, hipStream_t st);
 struct MdAcc {
     const char *fn, *noun;      // the attach function; what it accumulates, as the messages name it
     const char *moving_cell;    // why a barostat and the accumulator exclude each other
@@ -70,8 +71,10 @@ static const MdAcc MD_ACC[] = {
      [](const MdRun &r) { return r.vh.every; }, md_vh_sample},
     {"sgpr_md_adf", "bond angles", "the neighbours are read from the list of a constant cell", "beads are",
      [](const MdRun &r) { return r.adf.every; }, md_adf_sample},
+    {"sgpr_md_sq", "structure factors", "the wave vectors are the reciprocal lattice of a constant cell", "beads are",
+     [](const MdRun &r) { return r.sq.every; }, md_sq_sample},
 };
-enum { MD_MSD, MD_RDF, MD_VACF, MD_VH, MD_ADF };
+enum { MD_MSD, MD_RDF, MD_VACF, MD_VH, MD_ADF, MD_SQ };
 
 // The first accumulator attached to the run (NULL: none): what a mode that excludes them refuses with.
 static const MdAcc *md_acc_attached(const MdRun &r)
@@ -1068,8 +1071,31 @@ static int md_adf_sample(sgpr_model *h, int j, int step, hipStream_t st)
     return SGPR_OK;
 }
 
+// The same for the structure factors (md_sq.inc): the phase sums of the X slot of configuration n per chunk and wave vector, the
+// fold into the ring, the mean and the due lags of f, and the launch that counts the sample.  Which lags are due follows from s
+// and origin_every alone; whether n is the awaited sample is the device's decision.
+static int md_sq_sample(sgpr_model *h, int j, int step, hipStream_t st)
+{
+    MdState &m = h->md;
+    const MdRun::Sq &a = m.run.sq;
+    const long long n = m.run.t + j, s = n / a.every;
+    const double *x = m.X.p + (size_t)3 * m.run.N * (size_t)(n % m.run.ring);
+    const int *chunk = m.sq.tab.p, *coff = chunk + 2 * a.nch, *hkl = coff + a.S + 1, *halt = m.halt.p;
+    const long long *ctl = m.sq.ctl.p;
+    const int tiles = (a.nq + SQ_TILE - 1) / SQ_TILE;
+    const auto wide = md_sq_part_kernel<64, SQ_WIDE_H + 1>, narrow = md_sq_part_kernel<32, SQ_MAXH + 1>;
+    if (a.nch)
+        hipLaunchKernelGGL(a.narrow ? narrow : wide, dim3(a.nch, tiles), dim3(256), 0, st, chunk, x, (const double *)m.sq.inv.p, hkl, a.nq,
+                           m.sq.part.p, ctl, n, halt, step);
+    static_assert(sizeof(double) * 2 * SGPR_MAX_S * SQ_TILE <= 65536, "the fold's densities [S][2][SQ_TILE] fit the LDS of a workgroup at every S (64 KiB at SGPR_MAX_S: one workgroup per CU there)");
+    hipLaunchKernelGGL(md_sq_fold_kernel, dim3(tiles, (a.lags + SQ_FOLD - 1) / SQ_FOLD), dim3(256), sizeof(double) * 2 * a.S * SQ_TILE, st, coff, a.S,
+                       a.nq, a.lags, a.origin_every, s, (const double *)m.sq.part.p, m.sq.ring.p, m.sq.mean.p, m.sq.f.p, ctl, n, halt, step);
+    hipLaunchKernelGGL(md_sq_done_kernel, dim3(1), dim3(256), 0, st, m.sq.ctl.p, n, a.every, a.lags, a.origin_every, s, halt, step);
+    return SGPR_OK;
+}
+
 // Behind evaluation j of a call (and its frame): the samples of the accumulators whose interval divides the configuration's
-// index, in the table's order.  A run without accumulators tests five integers and launches nothing.
+// index, in the table's order.  A run without accumulators tests six integers and launches nothing.
 static int md_sample_due(sgpr_model *h, int j, int step, hipStream_t st)
 {
     const MdRun &r = h->md.run;
@@ -2384,6 +2410,7 @@ extern "C" int sgpr_md_vanhove(sgpr_model *h, int every, int levels, double rmax
         m.vh.over.alloc((size_t)levels * S) || m.vh.hd.alloc((size_t)levels * S * S * dbins) || m.vh.ctl.alloc((size_t)VH_CTL + levels) ||
         m.vh.tab.alloc(tab.size(), false)) {
         m.vh = MdState::VanHoveBufs();
+        m.run.vh = MdRun::VanHove();   // (an earlier attach's settings go with its buffers: the run launches nothing on them)
         return fail(SGPR_E_NODEVICE, "sgpr_md_vanhove: device allocation failed");
     }
     HIPCHK(hipMemcpy(m.vh.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
@@ -2488,6 +2515,7 @@ extern "C" int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut
     if (m.adf.angles.alloc((size_t)S * S * S * bins) || m.adf.coord.alloc((size_t)S * S * ADF_MAXCOORD) || m.adf.par.alloc(par.size(), false) ||
         m.adf.ctl.alloc(2) || m.adf.tab.alloc(tab.size(), false)) {
         m.adf = MdState::AdfBufs();
+        m.run.adf = MdRun::Adf();   // (an earlier attach's settings go with its buffers: the run launches nothing on them)
         return fail(SGPR_E_NODEVICE, "sgpr_md_adf: device allocation failed");
     }
     HIPCHK(hipMemcpy(m.adf.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
@@ -2525,6 +2553,97 @@ extern "C" int sgpr_md_adf_read(sgpr_model *h, uint64_t *angles, uint64_t *coord
         HIPCHK(hipMemcpy(ctl, m.adf.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
         info[0] = ctl[1]; info[1] = ctl[0]; info[2] = bins; info[3] = S;
         for (int z = 0; z < S; z++) info[4 + z] = a.nz[z];
+    }
+    return SGPR_OK;
+}
+
+// Partial structure factors and coherent intermediate scattering functions of the run (md_sq.inc has the definition and the
+// accuracy bound the device is held to; workloads.SqRing is the host twin): every >= 1 — configuration n with n % every == 0 is
+// sample n / every; behind its evaluation three launches form, per species of the model's table and wave vector q_j = 2 pi hkl_j
+// inv(cell)^T (hkl [nq][3], one of each +- pair), the density rho_z(q_j), keep it in a ring of `lags` slots, and add
+// Re(rho_a(s) conj rho_b(o)) to f [lags][nq][S][S] for every lag k < lags whose origin o = s - k >= 0 has o % origin_every == 0,
+// rho to mean [nq][S] and 1 to count [k] and to samples.  After sgpr_md_begin (and _fix, _thermostat, _filter, _meta, _record
+// and the other accumulators), before the first sgpr_md_run; every = 0 detaches and frees.  The attach zeroes the tables.
+// Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, beside a mask, the filter, a bias, the frame record
+// and the other accumulators (each keeps its own next_due); a barostat, a committee, a relaxation, a band, a polymer and several
+// ranks: SGPR_E_UNSUPPORTED, from here and from their attach functions.  Limits: nq <= SQ_MAXQ, |index| <= SQ_MAXH, lags <=
+// SQ_MAXLAGS, f and the ring together lags nq S (8 S + 16) bytes <= SQ_MAXBYTES.
+extern "C" int sgpr_md_sq(sgpr_model *h, int every, int nq, const int32_t *hkl, int lags, int origin_every)
+{
+    const MdAcc &acc = MD_ACC[MD_SQ];
+    if (const int rr = md_acc_run(h, acc)) return rr;
+    MdState &m = h->md;
+    if (every == 0) { m.run.sq = MdRun::Sq(); return md_release(h, m.sq); }
+    if (every < 0 || nq < 1 || nq > SQ_MAXQ || !hkl || lags < 1 || lags > SQ_MAXLAGS || origin_every < 1)
+        return fail(SGPR_E_INVALID, "sgpr_md_sq: every >= 0, 1 <= nq <= %d wave vectors hkl[nq][3], 1 <= lags <= %d, origin_every >= 1", SQ_MAXQ, SQ_MAXLAGS);
+    int hmax = 0;
+    for (int j = 0; j < nq; j++) {
+        const int32_t *v = hkl + 3 * (size_t)j;
+        if (!v[0] && !v[1] && !v[2]) return fail(SGPR_E_INVALID, "sgpr_md_sq: wave vector %d is (0, 0, 0): rho(0) is the number of atoms", j);
+        for (int k = 0; k < 3; k++) {
+            if (v[k] > SQ_MAXH || v[k] < -SQ_MAXH)
+                return fail(SGPR_E_INVALID, "sgpr_md_sq: wave vector %d has the index %d along direction %d; at most %d either way", j, (int)v[k], k, SQ_MAXH);
+            if (v[k] && !m.run.pbc[k])
+                return fail(SGPR_E_INVALID, "sgpr_md_sq: wave vector %d has the index %d along direction %d, which is not periodic: no reciprocal lattice there",
+                            j, (int)v[k], k);
+            hmax = std::max(hmax, std::abs((int)v[k]));
+        }
+    }
+    if (const int ru = md_acc_unstarted(h, acc)) return ru;
+    if (const int rm = md_acc_modes(h, acc)) return rm;
+    const int S = h->S;
+    const unsigned long long bytes = (unsigned long long)lags * (unsigned long long)nq * (unsigned long long)S * (8ull * S + 16ull);
+    if (bytes > SQ_MAXBYTES)
+        return fail(SGPR_E_UNSUPPORTED, "sgpr_md_sq: %d lags of %d wave vectors and %d species: f and the ring take %llu bytes; at most %llu "
+                    "(fewer lags, a larger `every`, or fewer wave vectors)", lags, nq, S, bytes, (unsigned long long)SQ_MAXBYTES);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    double cell[9], height[3], volume = 0.0;
+    HIPCHK(hipMemcpy(cell, m.cell.p, sizeof(double) * 9, hipMemcpyDeviceToHost));
+    RdfGeom g = {};   // (the inverse of the pair sweeps: one formula for every accumulator that scales coordinates)
+    if (!md_rdf_geometry(cell, m.run.pbc, 1.0, g, volume, height)) return fail(SGPR_E_INVALID, "sgpr_md_sq: the cell has no volume; a reciprocal lattice needs one");
+    const bool narrow = hmax > SQ_WIDE_H;
+    MdSpecies sp;   // the chunks | a species' chunks | the wave vectors
+    if (const int rs = md_species_chunks(h, acc.fn, narrow ? 32 : 64, false, sp)) return rs;
+    std::vector<int> &tab = sp.tab;
+    const int nch = sp.nch;
+    tab.insert(tab.end(), sp.coff.begin(), sp.coff.end());
+    tab.insert(tab.end(), hkl, hkl + 3 * (size_t)nq);
+    const size_t LQ = (size_t)lags * nq;
+    // (part and ring slots are written before they are read: only the tables and the control words start from zero)
+    if (m.sq.part.alloc((size_t)std::max(nch, 1) * nq * 2, false) || m.sq.ring.alloc(LQ * S * 2, false) || m.sq.mean.alloc((size_t)nq * S * 2) ||
+        m.sq.f.alloc(LQ * S * S) || m.sq.inv.alloc(9, false) || m.sq.ctl.alloc((size_t)2 + lags) || m.sq.tab.alloc(tab.size(), false)) {
+        m.sq = MdState::SqBufs();
+        m.run.sq = MdRun::Sq();   // (an earlier attach's settings go with its buffers: the run launches nothing on them)
+        return fail(SGPR_E_NODEVICE, "sgpr_md_sq: device allocation failed");
+    }
+    HIPCHK(hipMemcpy(m.sq.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.sq.inv.p, g.inv, sizeof(double) * 9, hipMemcpyHostToDevice));
+    MdRun::Sq &a = m.run.sq;
+    a = MdRun::Sq();
+    a.every = every; a.nq = nq; a.lags = lags; a.origin_every = origin_every; a.nch = nch; a.S = S; a.narrow = narrow; a.nz = sp.nz;
+    return SGPR_OK;
+}
+
+// The tables as they stand (between two calls of a run; the stream is synchronised): f [lags][nq][S][S], mean [nq][S][2] (real,
+// imaginary), count [lags], info [2 + S] = samples taken, next_due (the configuration the tables wait for), and the atoms of
+// every species in the frame.  Any pointer may be NULL.
+extern "C" int sgpr_md_sq_read(sgpr_model *h, double *f, double *mean, int64_t *count, int64_t *info)
+{
+    if (!h) return fail(SGPR_E_INVALID, "sgpr_md_sq_read: bad arguments");
+    MdState &m = h->md;
+    if (!m.active || !m.run.sq.every) return fail(SGPR_E_INVALID, "sgpr_md_sq_read: call sgpr_md_begin and sgpr_md_sq first");
+    const MdRun::Sq &a = m.run.sq;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<long long> ctl((size_t)2 + a.lags);
+    HIPCHK(hipMemcpy(ctl.data(), m.sq.ctl.p, sizeof(long long) * ctl.size(), hipMemcpyDeviceToHost));
+    if (f) HIPCHK(hipMemcpy(f, m.sq.f.p, sizeof(double) * (size_t)a.lags * a.nq * a.S * a.S, hipMemcpyDeviceToHost));
+    if (mean) HIPCHK(hipMemcpy(mean, m.sq.mean.p, sizeof(double) * (size_t)a.nq * a.S * 2, hipMemcpyDeviceToHost));
+    if (count) for (int k = 0; k < a.lags; k++) count[k] = ctl[2 + k];
+    if (info) {
+        info[0] = ctl[1]; info[1] = ctl[0];
+        for (int z = 0; z < a.S; z++) info[2 + z] = a.nz[z];
     }
     return SGPR_OK;
 }
@@ -2918,6 +3037,7 @@ extern "C" int sgpr_md_end(sgpr_model *h)
     (void)md_release(h, m.vacf);
     (void)md_release(h, m.vh);
     (void)md_release(h, m.adf);
+    (void)md_release(h, m.sq);
     m.run = MdRun();   // (the borrowed members are let go with everything else the run was)
     return SGPR_OK;
 }

@@ -1298,6 +1298,47 @@ class SGPRModel:
         return dict(angles=angles, coord=coord, samples=int(info[0]), next_due=int(info[1]), every=every, bins=int(info[2]), cut=cut.copy(),
                     **self._md_species(info[4:]))
 
+    def md_sq(self, every, hkl=None, lags=1, origin_every=1):
+        """Accumulate partial structure factors and coherent intermediate scattering functions inside the loop (sgpr_md_sq;
+        md_sq.inc has the scheme and the accuracy bound, workloads.SqRing is the host twin and the definition).  `hkl`: int
+        [nq, 3] vectors of the reciprocal lattice of the run's cell, q_j = 2 pi hkl_j inv(cell)^T (transport.q_vectors lists a
+        half-sphere of them), one of each +- pair, every |index| <= 32.  Configuration n with n % every == 0 is sample n / every:
+        per species of the model's table the density rho_z(q_j) = sum_z exp(i q_j . r_i) is formed, added to `mean`, kept in a
+        ring of `lags` samples, and for every lag k < lags whose origin o = s - k has o % origin_every == 0 the S x S block
+        Re(rho_a(s) conj rho_b(o)) is added to f[k, j].  After md_begin, before the first md_run; every = 0 detaches and frees.
+        md_sq_table() reads the tables; transport.structure_factor, intermediate_scattering and dynamic_structure_factor read
+        those.  Langevin, velocity Verlet and Nose-Hoover at constant cell on one rank, with or without fixed=, ml_filter=,
+        md_meta, md_record and the other accumulators; a barostat, a committee, a relaxation, a band, a polymer, several ranks
+        and tables over 1 GiB: NotImplementedError."""
+        lib = _lib.load()
+        if not every:
+            check(lib.sgpr_md_sq(self._h, 0, 0, None, 0, 0))
+            self._md["sq"] = None
+            return
+        if hkl is None:
+            raise ValueError("md_sq: hkl= (int [nq, 3]; transport.q_vectors) names the wave vectors")
+        given = np.asarray(hkl)
+        if given.ndim != 2 or given.shape[1] != 3 or not np.array_equal(given, np.rint(given)):
+            raise ValueError("md_sq: hkl is an integer array [nq, 3]")
+        hkl = np.ascontiguousarray(given, dtype=np.int32)
+        _attach(lib.sgpr_md_sq(self._h, int(every), len(hkl), ptr(hkl), int(lags), int(origin_every)))
+        self._md["sq"] = (int(every), hkl.astype(np.int64), int(lags), int(origin_every))
+
+    def md_sq_table(self):
+        """The tables of md_sq as they stand (sgpr_md_sq_read; between two md_run calls): dict(f [lags, nq, S, S] the sums of
+        Re(rho_a(s) conj rho_b(s - k)) over the pairs of a lag, mean [nq, S] complex the sum of rho over the samples, count
+        [lags] the pairs, lags [lags] in configurations, hkl [nq, 3], q [nq, 3] = 2 pi hkl inv(cell)^T, species [S] the model's
+        table, n [S] its atoms in the frame, origin_every, samples, next_due)."""
+        if not self._md.get("sq"):
+            raise RuntimeError("md_sq_table: no accumulator on this run (md_sq)")
+        from .workloads import sq_vectors
+        every, hkl, L, origin_every = self._md["sq"]
+        S, nq = len(self.species), len(hkl)
+        f, mean, cnt, info = np.zeros((L, nq, S, S)), np.zeros((nq, S, 2)), np.zeros(L, dtype=np.int64), np.zeros(2 + S, dtype=np.int64)
+        check(_lib.load().sgpr_md_sq_read(self._h, ptr(f), ptr(mean), ptr(cnt), ptr(info)))
+        return dict(f=f, mean=mean[:, :, 0] + 1j * mean[:, :, 1], count=cnt, lags=every * np.arange(L, dtype=np.int64), hkl=hkl.copy(),
+                    q=sq_vectors(hkl, self._md["cell"]), origin_every=origin_every, samples=int(info[0]), next_due=int(info[1]), **self._md_species(info[2:]))
+
     def md_committee(self, members, moving_cell=None):
         """The Bayesian committee of the run just begun (sgpr_md_committee; calculator_bcm.py has the rule): `members`, frozen
         SGPRModels with weights and choli on this model's device, are evaluated beside this (live) model at every

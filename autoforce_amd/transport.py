@@ -11,7 +11,10 @@ level's windows, and of their squares; the windows of a level do not overlap, so
 workloads.VanHoveCounts; `displacement_histogram` is the return of analysis.py:178-210 (`hist_rtp_displacements`), `self_van_hove`,
 `distinct_van_hove` and `non_gaussian` form G_s(r, t), G_d(r, t) and alpha_2(t).
   And the three-body structure: `Adf` holds the bond-angle and coordination counts of SGPRModel.md_adf / workloads.AdfCounts (the
-reference has no angular analysis); `angle_distribution` and `coordination` form P(theta) and P(n) per species."""
+reference has no angular analysis); `angle_distribution` and `coordination` form P(theta) and P(n) per species.
+  And reciprocal space: `Sq` holds the density correlations of SGPRModel.md_sq / workloads.SqRing at the wave vectors `q_vectors`
+lists (the reference has none); `structure_factor`, `intermediate_scattering` and `dynamic_structure_factor` form S_ab(q),
+F_ab(q, t) and S_ab(q, omega)."""
 import numpy as np
 
 KEYS = ("msd", "msd_sq", "smd", "smd_sq")
@@ -503,3 +506,161 @@ def non_gaussian(vh):
             m2, m4 = (P * r ** 2).sum(axis=1) / tot, (P * r ** 4).sum(axis=1) / tot
             out[int(Z)] = 3.0 * m4 / (5.0 * m2 * m2) - 1.0
     return out
+
+
+def q_vectors(cell, qmax, limit=8192):
+    """hkl int [nq, 3]: every integer triple whose vector of the reciprocal lattice q = 2 pi hkl inv(cell)^T has 0 < |q| <= qmax,
+    one of each +- pair — the one whose first non-zero index is positive —, ordered by |q|, then by the triple: what
+    SGPRModel.md_sq, workloads.SqRing and Sq take.  More than `limit` (the accumulator's 8192): ValueError."""
+    h = np.asarray(cell, float).reshape(3, 3)
+    rec = 2.0 * np.pi * np.linalg.inv(h).T     # (rows: the reciprocal vectors b_a; q = hkl @ rec)
+    # h_a = q . a_a / 2 pi: |h_a| <= qmax |a_a| / 2 pi
+    top = [int(np.floor(float(qmax) * np.linalg.norm(h[a]) / (2.0 * np.pi) + 1e-9)) for a in range(3)]
+    grid = np.stack(np.meshgrid(*[np.arange(-t, t + 1) for t in top], indexing="ij"), axis=-1).reshape(-1, 3)
+    first = np.where(grid[:, 0] != 0, grid[:, 0], np.where(grid[:, 1] != 0, grid[:, 1], grid[:, 2]))
+    grid = grid[first > 0]
+    q = np.linalg.norm(grid @ rec, axis=1)
+    keep = q <= float(qmax)
+    grid, q = grid[keep], q[keep]
+    if len(grid) > int(limit):
+        raise ValueError(f"q_vectors: {len(grid)} wave vectors within qmax = {qmax:g}; at most {int(limit)}")
+    order = np.lexsort((grid[:, 2], grid[:, 1], grid[:, 0], q))
+    return grid[order].astype(np.int64)
+
+
+class Sq(_InLoop):
+    """Holder of structure-factor tables: ActiveCalculator.run_md(sq=Sq(every, hkl, lags, origin_every)) fills it, as msd= fills
+    an Msd; `hkl` int [nq, 3] names the wave vectors (q_vectors).  add(table) adds the tables of a run (SGPRModel.md_sq_table(),
+    SqRing.table()) — those of several runs of one frame with equal settings add up.  structure_factor, intermediate_scattering
+    and dynamic_structure_factor read it."""
+    md, twin_of, constant_cell = "md_sq", "SqRing", "the wave vectors are the reciprocal lattice"
+
+    def __init__(self, every, hkl, lags=1, origin_every=1):
+        self.every, self.nlags, self.origin_every = int(every), int(lags), int(origin_every)
+        self.hkl = np.asarray(hkl, dtype=np.int64).reshape(-1, 3).copy()
+        self.lags = self.every * np.arange(self.nlags, dtype=np.int64)   # in configurations
+        self.count = np.zeros(self.nlags, dtype=np.int64)
+        self.samples = 0
+        self.f = self.mean = self.q = self.species = self.n = None
+
+    def settings(self):
+        return (self.every, self.hkl, self.nlags, self.origin_every)
+
+    def add(self, table):
+        if not (np.array_equal(np.asarray(table["lags"]), self.lags) and np.array_equal(np.asarray(table["hkl"]), self.hkl)
+                and int(table["origin_every"]) == self.origin_every):
+            raise ValueError("Sq.add: the table was taken with other settings (every, lags, origin_every, hkl)")
+        species, n, q = np.asarray(table["species"]), np.asarray(table["n"]), np.asarray(table["q"], float)
+        if self.species is None:
+            self.species, self.n, self.q = species.copy(), n.copy(), q.copy()
+            self.f = np.zeros((self.nlags, len(self.hkl), len(species), len(species)))
+            self.mean = np.zeros((len(self.hkl), len(species)), dtype=complex)
+        elif not (np.array_equal(species, self.species) and np.array_equal(n, self.n) and np.array_equal(q, self.q)):
+            raise ValueError("Sq.add: the table is of another frame (species, atoms per species, cell)")
+        self.count = self.count + np.asarray(table["count"], dtype=np.int64)
+        self.f = self.f + np.asarray(table["f"], float)
+        self.mean = self.mean + np.asarray(table["mean"], complex)
+        self.samples += int(table["samples"])
+        return self
+
+    def table(self):
+        if self.f is None:
+            raise ValueError("Sq.table: the holder has no table")
+        return dict(f=self.f.copy(), mean=self.mean.copy(), count=self.count.copy(), lags=self.lags.copy(), hkl=self.hkl.copy(), q=self.q,
+                    species=self.species, n=self.n, origin_every=self.origin_every, samples=self.samples, next_due=self.samples * self.every)
+
+
+def _sq_table(sq, who):
+    t = sq.table() if hasattr(sq, "table") else sq
+    if t.get("f") is None or int(t["count"][0]) == 0:
+        raise ValueError(f"{who}: the table has no samples")
+    return t
+
+
+def _q_shells(q, dq):
+    """(|q| per shell [nsh], the shell of every wave vector [nq]): dq None — the exact shells, vectors of one length (to nine
+    digits); else bins [k dq, (k + 1) dq), the empty ones dropped, each at the mean length of its vectors."""
+    qn = np.linalg.norm(np.asarray(q, float), axis=1)
+    key = np.round(qn / qn.max(), 9) if dq is None else np.floor(qn / float(dq)).astype(np.int64)
+    _, shell = np.unique(key, return_inverse=True)
+    shell = shell.reshape(-1)
+    return np.bincount(shell, weights=qn) / np.bincount(shell), shell
+
+
+def _shell_mean(x, shell, axis):
+    """The mean of x over the wave vectors of every shell, along `axis`."""
+    x = np.moveaxis(np.asarray(x, float), axis, 0)
+    out = np.zeros((int(shell.max()) + 1,) + x.shape[1:])
+    np.add.at(out, shell, x)
+    cnt = np.bincount(shell).astype(float).reshape((-1,) + (1,) * (x.ndim - 1))
+    return np.moveaxis(out / cnt, 0, axis)
+
+
+def _al_norm(n):
+    """sqrt(n_a n_b) [S, S] of the Ashcroft-Langreth partials; nan where a species has no atom in the frame."""
+    n = np.asarray(n, float)
+    r = np.sqrt(n[:, None] * n[None, :])
+    return np.where(r > 0.0, r, np.nan)
+
+
+def structure_factor(sq, weights=None, dq=None, diffuse=False):
+    """(q [nsh], S) from an Sq holder or a table (md_sq_table(), SqRing.table()): the Ashcroft-Langreth partials
+        S_ab(|q|) = f[0][j][a][b] / (count[0] sqrt(n_a n_b))
+    averaged over the wave vectors of a shell — dq None: exact shells, vectors of equal length; else shells of width dq — as
+    S [nsh, S, S] (nan for a species without atoms).  diffuse=True takes the Bragg part Re(<rho_a> conj <rho_b>) / sqrt(n_a n_b),
+    <rho> = mean / samples, off every vector before the average: what is left is the diffuse scattering.  weights ({Z: w} or
+    [S], scattering lengths or form factors at q = 0): the weighted total [nsh]
+        S(q) = sum_ab w_a w_b sqrt(c_a c_b) S_ab(q) / sum_a c_a w_a^2,   c_a = n_a / N,
+    which tends to 1 at large q."""
+    t = _sq_table(sq, "structure_factor")
+    n = np.asarray(t["n"], float)
+    part = np.asarray(t["f"], float)[0] / float(t["count"][0])
+    if diffuse:
+        m = np.asarray(t["mean"], complex) / float(t["samples"])
+        part = part - (m[:, :, None] * np.conj(m)[:, None, :]).real
+    qs, shell = _q_shells(t["q"], dq)
+    S = _shell_mean(part, shell, 0) / _al_norm(n)[None]
+    if weights is None:
+        return qs, S
+    w = np.array([float(weights.get(int(z), 0.0)) for z in t["species"]]) if hasattr(weights, "get") else np.asarray(weights, float)
+    c = n / n.sum()
+    ww = (w[:, None] * w[None, :]) * np.sqrt(c[:, None] * c[None, :])
+    return qs, np.nansum(np.where(ww[None] != 0.0, ww[None] * S, 0.0), axis=(1, 2)) / float(np.sum(c * w * w))
+
+
+def intermediate_scattering(sq, dq=None):
+    """(q [nsh], t [lags] in configurations, F [lags, nsh, S, S], Fn [lags, nsh, S, S]): the coherent intermediate scattering
+    functions F_ab(|q|, t_k) = f[k][j][a][b] / (count[k] sqrt(n_a n_b)) averaged over the shells of structure_factor (a at time
+    t, b at the origin: not symmetric in a, b at t > 0), and Fn = F / F(t = 0), the normalised decay.  nan where a lag has no
+    pair of samples."""
+    t = _sq_table(sq, "intermediate_scattering")
+    cnt = np.asarray(t["count"])
+    c = np.where(cnt > 0, cnt, 1).astype(float)[:, None, None, None]
+    qs, shell = _q_shells(t["q"], dq)
+    F = _shell_mean(np.asarray(t["f"], float) / c, shell, 1) / _al_norm(t["n"])[None, None]
+    F = np.where((cnt > 0)[:, None, None, None], F, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Fn = F / F[0][None]
+    return qs, np.asarray(t["lags"]).copy(), F, Fn
+
+
+def dynamic_structure_factor(sq, dt_fs, window="hann"):
+    """(f [L] THz, q [nsh], S [L, nsh, S, S]): the cosine transform over the lags that have samples of the intermediate scattering
+    functions on exact shells, windowed as vibrational_dos:
+        S_ab(q, f_j) = 2 step sum_k a_k w_k F_ab(q, t_k) cos(2 pi f_j t_k),   f_j = j / (2 L step),  a_0 = 1/2, else 1,
+    step = every dt_fs, w the falling half of a Hann window (window="hann") or 1 (None); in fs."""
+    if window not in ("hann", None):
+        raise ValueError("dynamic_structure_factor: window = 'hann' or None")
+    qs, lags, F, _ = intermediate_scattering(sq, None)
+    t = _sq_table(sq, "dynamic_structure_factor")
+    cnt = np.asarray(t["count"])
+    L = int(np.argmin(cnt > 0)) if not np.all(cnt > 0) else len(cnt)
+    if L < 2:
+        raise ValueError("dynamic_structure_factor: fewer than two lags with samples")
+    k = np.arange(L)
+    w = 0.5 * (1.0 + np.cos(np.pi * k / L)) if window == "hann" else np.ones(L)
+    w[0] *= 0.5
+    step_fs = float(lags[1] - lags[0]) * float(dt_fs)
+    f = k / (2.0 * L * step_fs) * 1e3   # 1 / fs = 1000 THz
+    kern = np.cos(np.pi * np.outer(k, k) / L)   # [j, k]: 2 pi f_j t_k
+    return f, qs, 2.0 * step_fs * np.einsum("jk,k,kqab->jqab", kern, w, F[:L])

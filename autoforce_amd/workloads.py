@@ -1954,6 +1954,125 @@ class VacfRing:
                     samples=self.samples, pending=1 if due > 0 else 0, next_due=due * self.every)
 
 
+SQ_MAXQ, SQ_MAXLAGS, SQ_MAXH = 8192, 8192, 32   # wave vectors, lags and |index| of a table (md_sq.inc)
+
+
+def sq_vectors(hkl, cell):
+    """q [nq, 3] = 2 pi hkl inv(cell)^T: the vectors of the reciprocal lattice that the integer triples name (q . r = 2 pi
+    hkl . s for r = s cell)."""
+    return 2.0 * np.pi * np.asarray(hkl, float).reshape(-1, 3) @ np.linalg.inv(np.asarray(cell, float).reshape(3, 3)).T
+
+
+def sq_bounds(hmax, smax, nz, count):
+    """The a-priori bounds the device accumulator (md_sq.inc) and SqRing are held to against each other and against any other
+    evaluation in double precision: B [S] with |d rho_z(q)| <= B_z = 128 hmax (1 + smax) n_z 2^-52 (hmax: the largest |index|,
+    smax: the largest |scaled coordinate| fed; a phase error of 2 pi (|h| + |k| + |l|) roundings of a three-term scaled
+    coordinate, a few roundings per power, that much on both sides) and F [lags, S, S] with
+    |d f[k, j, a, b]| <= count[k] (n_a B_b + n_b B_a + count[k] n_a n_b 2^-52)."""
+    n = np.asarray(nz, float)
+    c = np.asarray(count, float)[:, None, None]
+    B = 128.0 * float(hmax) * (1.0 + float(smax)) * n * 2.0 ** -52
+    return B, c * (n[:, None] * B[None, :] + n[None, :] * B[:, None] + c * n[:, None] * n[None, :] * 2.0 ** -52)
+
+
+class SqRing:
+    """Partial structure factors and coherent intermediate scattering functions over a ring of stored densities — the host twin of
+    the accumulator inside the device loop (SGPRModel.md_sq, md_sq.inc) and its definition.  The reference has nothing in
+    reciprocal space; the definition is ours.
+      hkl: int [nq, 3], vectors of the reciprocal lattice of `cell`: q_j = 2 pi hkl_j inv(cell)^T, so q_j . r = 2 pi hkl_j . s
+    with s = r inv(cell) — wrapped and unwrapped positions give the same phases.  One vector of each +- pair (the real part is the
+    average over the pair); duplicates are not checked for.
+      add(x) is fed the configurations 0, 1, 2, ... of a run ([N, 3], caller atom order, wrapped or not).  Configuration n with
+    n % every == 0 is sample s = n / every.  Per atom f = s - rint(s) and e_a = exp(2 pi i f_a) per axis, the powers 0 ... hmax
+    of e_a by repeated multiplication (a negative index: the conjugate), and per species z of `species` (the model's table; one
+    absent from the frame keeps zeros)
+        rho_z(q_j; s) = sum_{i in z} e_0^h e_1^k e_2^l
+    For every lag k < lags and origin o = s - k with o >= 0 and o % origin_every == 0
+        f[k, j, a, b] += Re(rho_a(q_j; s) conj rho_b(q_j; o)),  count[k] += 1      (the full block: a != b is not symmetric at k > 0)
+    and per sample mean[j, a] += rho_a(q_j; s), samples += 1.  rho(s) is kept in slot s % lags of a ring.  Lag 0 is the static S_ab.
+      The device's sincospi is not numpy's sin and cos: the two tables agree within sq_bounds, not bit for bit; count, samples and
+    next_due are equal."""
+
+    def __init__(self, every, hkl, lags, origin_every, numbers, species, cell, pbc):
+        if every < 1 or lags < 1 or origin_every < 1:
+            raise ValueError("SqRing: every >= 1, lags >= 1, origin_every >= 1")
+        self.every, self.lags, self.origin_every = int(every), int(lags), int(origin_every)
+        given = np.asarray(hkl)
+        if given.ndim != 2 or given.shape[1] != 3 or not np.array_equal(given, np.rint(given)):
+            raise ValueError("SqRing: hkl is an integer array [nq, 3]")
+        self.hkl = given.astype(np.int64)
+        pbc = np.broadcast_to(np.asarray(pbc, bool), (3,))
+        if not 1 <= len(self.hkl) <= SQ_MAXQ or self.lags > SQ_MAXLAGS:
+            raise ValueError(f"SqRing: 1 <= nq <= {SQ_MAXQ}, lags <= {SQ_MAXLAGS}")
+        if np.any(np.all(self.hkl == 0, axis=1)) or np.abs(self.hkl).max() > SQ_MAXH or np.any(self.hkl[:, ~pbc] != 0):
+            raise ValueError(f"SqRing: no zero row, every |index| <= {SQ_MAXH}, 0 along a direction that is not periodic")
+        self.cell = np.asarray(cell, float).reshape(3, 3).copy()
+        self.inv = rdf_geometry(self.cell, pbc, 1.0)[0]   # (sgpr_md_sq's inverse: frac_c = sum_k x_k inv[k, c])
+        self.hmax = int(np.abs(self.hkl).max())
+        numbers = np.asarray(numbers)
+        self.species = [int(z) for z in species]
+        self.idx = [np.flatnonzero(numbers == z) for z in self.species]
+        self.nz = np.array([len(i) for i in self.idx])
+        S, nq = len(self.species), len(self.hkl)
+        self.ring = np.zeros((self.lags, nq, S), dtype=complex)
+        self.f = np.zeros((self.lags, nq, S, S))
+        self.mean = np.zeros((nq, S), dtype=complex)
+        self.count = np.zeros(self.lags, dtype=np.int64)
+        self.samples = 0
+        self.n = 0         # configurations seen
+        self.smax = 0.0    # the largest |scaled coordinate| fed: what the bound takes
+
+    def density(self, positions):
+        """rho [nq, S] of one configuration."""
+        x = np.asarray(positions, float).reshape(-1, 3)
+        inv = self.inv
+        s = np.stack([(x[:, 0] * inv[0, c] + x[:, 1] * inv[1, c]) + x[:, 2] * inv[2, c] for c in range(3)], axis=1)
+        if len(s):
+            self.smax = max(self.smax, float(np.abs(s).max()))
+        f = s - np.rint(s)
+        e = np.cos(2.0 * np.pi * f) + 1j * np.sin(2.0 * np.pi * f)
+        pw = np.ones((self.hmax + 1,) + e.shape, dtype=complex)   # [power, atom, axis]
+        for p in range(1, self.hmax + 1):
+            pw[p] = pw[p - 1] * e
+        rho = np.zeros((len(self.hkl), len(self.species)), dtype=complex)
+        fac = []
+        for ax in range(3):
+            t = pw[np.abs(self.hkl[:, ax]), :, ax]   # [nq, atom]
+            fac.append(np.where((self.hkl[:, ax] < 0)[:, None], np.conj(t), t))
+        prod = (fac[0] * fac[1]) * fac[2]
+        for z, i in enumerate(self.idx):
+            if len(i):
+                rho[:, z] = prod[:, i].sum(axis=1)
+        return rho
+
+    def add(self, positions):
+        """The next configuration of the run."""
+        n = self.n
+        self.n += 1
+        if n % self.every:
+            return
+        s = n // self.every
+        rho = self.density(positions)
+        self.ring[s % self.lags] = rho
+        self.mean += rho
+        for k in range(self.lags):
+            o = s - k
+            if o < 0:
+                break
+            if o % self.origin_every:
+                continue
+            org = self.ring[o % self.lags]
+            self.f[k] += (rho[:, :, None] * np.conj(org)[:, None, :]).real
+            self.count[k] += 1
+        self.samples += 1
+
+    def table(self):
+        """What SGPRModel.md_sq_table returns."""
+        return dict(f=self.f.copy(), mean=self.mean.copy(), count=self.count.copy(), lags=self.every * np.arange(self.lags, dtype=np.int64),
+                    hkl=self.hkl.copy(), q=sq_vectors(self.hkl, self.cell), species=np.array(self.species), n=self.nz.copy(),
+                    origin_every=self.origin_every, samples=self.samples, next_due=-(-self.n // self.every) * self.every)
+
+
 RDF_MAXR = 2      # images |s_k| <= 2 around a pair's nearest one: at most 125 shifts (md_rdf.inc)
 RDF_MAXBINS = 2048
 

@@ -710,6 +710,39 @@ int sgpr_md_vanhove_read(sgpr_model *h, uint64_t *self_hist, uint64_t *over, uin
  * The handle stays usable after every error above. */
 int sgpr_md_adf(sgpr_model *h, int every, int bins, const double *cut, const double *ct);
 int sgpr_md_adf_read(sgpr_model *h, uint64_t *angles, uint64_t *coord, int64_t *info);
+/* Partial static structure factors S_ab(q) and coherent intermediate scattering functions F_ab(q, t) accumulated inside the loop:
+ * the run in reciprocal space — what diffraction measures, Bragg and diffuse scattering, collective density fluctuations in time.
+ * The reference has nothing of the kind; workloads.SqRing is the definition and the host twin.  Wave vectors are vectors of the
+ * reciprocal lattice of the run's constant cell, q_j = 2 pi hkl_j inv(cell)^T, so that q_j . r = 2 pi hkl_j . s with s = r inv(cell):
+ * wrapped and unwrapped positions give the same phases.  Sample s is configuration n = s every.  Per atom f = s - rint(s) per axis,
+ * e_a = exp(2 pi i f_a), and per species z of the model's table
+ *     rho_z(q_j; s) = sum over the atoms of z of e_0^h e_1^k e_2^l          (a negative index: the conjugate of the positive power)
+ * For every lag k < lags and origin o = s - k >= 0 with o mod origin_every == 0
+ *     f[k][j][a][b] += Re(rho_a(q_j; s) conj rho_b(q_j; o)),  count[k] += 1  (not symmetric in a, b at k > 0: the full block is kept)
+ * and per sample mean[j][a] += rho_a(q_j; s) (complex: |<rho>|^2 is the Bragg part), samples += 1.  Lag 0 is the static S_ab.  The
+ * caller passes one vector of each +- pair (the real part is the average over the pair); duplicates are not checked for.
+ * Fixed summation order, no float atomics: two runs give the same bits, however they are cut.  Against the twin the device is held
+ * to a bound, not bit for bit (its sincospi is not numpy's): |d rho_z| <= B_z = 128 hmax (1 + smax) n_z 2^-52 with hmax the largest
+ * |index| and smax the largest |scaled coordinate|, |d f[k][j][a][b]| <= count[k] (n_a B_b + n_b B_a + count[k] n_a n_b 2^-52);
+ * count, samples and next_due are equal.  The positions of a configuration do not depend on the model: a configuration evaluated
+ * twice (the repeat behind a covloss halt or an overflow) counts once, at its first evaluation; the speculative evaluation behind a
+ * halt not at all.  Nothing is left pending.
+ *
+ * sgpr_md_sq       every >= 1, 1 <= nq <= 8192, hkl[nq][3] with no zero row, every |index| <= 32 and 0 along a direction that is
+ *                  not periodic, 1 <= lags <= 8192, origin_every >= 1: after sgpr_md_begin (and sgpr_md_fix, _thermostat, _filter,
+ *                  _meta, _record and the other accumulators, if used), before the first sgpr_md_run; zeroes the tables.  every = 0
+ *                  detaches and frees them: the run launches what it launched before.  Three launches behind a sampled evaluation:
+ *                  N nq complex phase products per sample from three sincos per atom; lags nq S^2 doubles of f are updated per
+ *                  sample (origin_every thins them).  SGPR_E_INVALID: no run begun, a run that has started, values out of range
+ *                  (these come first), a cell without volume, atoms not sorted by the model's species.  SGPR_E_UNSUPPORTED: f and
+ *                  the ring, lags nq S (8 S + 16) bytes, over 1 GiB; several ranks, a barostat, a committee, a relaxation, a band,
+ *                  a polymer — and from sgpr_md_barostat, _committee, _relax, _neb and _pimd on a run that has the accumulator.
+ * sgpr_md_sq_read  between two calls of the run (synchronises the stream): f[lags][nq][S][S], mean[nq][S][2] (real, imaginary),
+ *                  count[lags], info[2 + S] = samples taken, the configuration the tables wait for next, the atoms of every species
+ *                  in the frame.  Any pointer may be NULL.
+ * The handle stays usable after every error above. */
+int sgpr_md_sq(sgpr_model *h, int every, int nq, const int32_t *hkl, int lags, int origin_every);
+int sgpr_md_sq_read(sgpr_model *h, double *f, double *mean, int64_t *count, int64_t *info);
 /* The Bayesian committee inside the device MD loop: the reference combines frozen sub-models and the live one per step on the
  * host (theforce/calculator/active_bcm.py:589-633, get_covloss_total :885-894); here every evaluation of sgpr_md_run evaluates
  * the K members and the live handle h at the same positions and combines them on the device, members k = 0 ... K - 1 in the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall time per step of the Langevin device loop with and without one of its accumulators — `--which` msd (sgpr_md_msd), rdf
-(sgpr_md_rdf), vacf (sgpr_md_vacf), vanhove (sgpr_md_vanhove) or adf (sgpr_md_adf) — on the headline frame of bench.py (LiPS 4096
+(sgpr_md_rdf), vacf (sgpr_md_vacf), vanhove (sgpr_md_vanhove), adf (sgpr_md_adf) or sq (sgpr_md_sq) — on the headline frame of bench.py (LiPS 4096
 atoms, 512 inducing, fp64, deviates drawn on the device; --dims 32 32 16: 16384 atoms), taken in ONE process.  Path (a) is the plain
 loop in calls of `--call` evaluations; the further paths of an accumulator are in its row of ROWS below: the device loop with the
 accumulator in the settings worth comparing, and what a user had before it — md_record, the frames of every call fetched behind it
@@ -8,7 +8,7 @@ and fed to the accumulator's host twin in workloads.  Where the host pass takes 
 `--host-steps` steps (0 leaves it out: larger frames).  Every device path is warmed up first; then the paths alternate in `--rounds`
 rounds of `--steps` steps, every window starting from the same frame.  The tables are read once at the end of a window, inside the
 timing.  Prints one JSON line: microseconds per step of each path per round, medians, the differences to (a) per round, and whether
-the device's tables equal the host twin's over the same steps.
+the device's tables equal the host twin's over the same steps (sq: agree within md_sq.inc's bound; its integers equal).
 
     python tools/accumulator_step_time.py --which rdf [--rounds 2] [--steps 2048] [--call 256] [--dims 16 | --dims 32 32 16 --host-steps 0]"""
 import argparse
@@ -26,7 +26,7 @@ from autoforce_amd.ase_shim import kB
 from autoforce_amd.workloads import FS, MASS, fit_to_teacher, lips
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--which", required=True, choices=("msd", "rdf", "vacf", "vanhove", "adf"))
+ap.add_argument("--which", required=True, choices=("msd", "rdf", "vacf", "vanhove", "adf", "sq"))
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--steps", type=int, default=2048)
 ap.add_argument("--call", type=int, default=256)
@@ -34,7 +34,7 @@ ap.add_argument("--warmup", type=int, default=256)
 ap.add_argument("--dims", type=int, nargs="+", default=[16])
 # (the accumulators' own settings: the defaults are in the rows)
 for name, kind in (("host-steps", int), ("levels", int), ("rmax", float), ("bins", int), ("rmax-images", float), ("lags", int), ("rbins", int),
-                   ("tbins", int), ("pbins", int), ("dmax", float), ("dbins", int)):
+                   ("tbins", int), ("pbins", int), ("dmax", float), ("dbins", int), ("nq", int)):
     ap.add_argument("--" + name, type=kind, default=None)
 args = ap.parse_args()
 
@@ -48,6 +48,24 @@ vel = np.random.default_rng(1).normal(size=(N, 3)) * np.sqrt(kB * T / mass[:, No
 BONDS = {(15, 16): 2.6, (3, 16): 3.0}   # (adf: P-S, Li-S; the other pairs never bond)
 RC = float(mdl.cutoff)
 frame = (numbers, mdl.species, cell, pbc)
+
+
+def half_sphere(nq):
+    """The nq shortest wave vectors of the cell's half-sphere (sq)."""
+    from autoforce_amd.transport import q_vectors
+    qmax = 1.0
+    while True:
+        hkl = q_vectors(cell, qmax, limit=1 << 30)
+        if len(hkl) >= nq:
+            return hkl[:nq]
+        qmax *= 1.2
+
+
+def sq_within(dev, host):
+    """The device's tables within md_sq.inc's bound of the twin's, the integers equal."""
+    B, F = wl.sq_bounds(np.abs(host["hkl"]).max(), host["smax"], host["n"], host["count"])
+    return bool(np.array_equal(dev["count"], host["count"]) and dev["samples"] == host["samples"] and dev["next_due"] == host["next_due"]
+                and np.all(np.abs(dev["f"] - host["f"]).max(axis=1) <= F) and np.all(np.abs(dev["mean"] - host["mean"]).max(axis=0) <= host["samples"] * B))
 
 
 def vh(a, distinct):
@@ -113,6 +131,15 @@ ROWS = dict(
         after=lambda a: [dict(every=1, steps=a.host_steps, key="device")], equal=(("device", "host"),), keys=("angles", "coord", "samples"),
         minus=dict(adf_bonds_every_step_minus_loop_us="b_adf_bonds_every_step", adf_rc_every_step_minus_loop_us="c_adf_rc_every_step",
                    adf_bonds_every_tenth_minus_loop_us="d_adf_bonds_every_tenth")),
+    sq=dict(
+        defaults=dict(host_steps=8, nq=2000, lags=64), head=lambda a: dict(nq=a.nq, lags=a.lags, host_steps=a.host_steps),
+        attach=lambda every, lags=1: mdl.md_sq(every, half_sphere(args.nq), lags), twin=lambda lags=1: wl.SqRing(1, half_sphere(args.nq), lags, 1, *frame),
+        paths=lambda a: dict(b_sq_every_step_one_lag=dict(every=1), c_sq_every_step_lags=dict(every=1, lags=a.lags), d_sq_every_tenth_one_lag=dict(every=10),
+                             e_sq_every_tenth_lags=dict(every=10, lags=a.lags),
+                             f_record_and_host_pass_every_step=dict(every=1, lags=a.lags, host=True, steps=a.host_steps, key="host")),
+        after=lambda a: [dict(every=1, lags=a.lags, steps=a.host_steps, key="device")], equal=(("device", "host"),), compare=sq_within,
+        minus=dict(sq_every_step_one_lag_minus_loop_us="b_sq_every_step_one_lag", sq_every_step_lags_minus_loop_us="c_sq_every_step_lags",
+                   sq_every_tenth_one_lag_minus_loop_us="d_sq_every_tenth_one_lag", sq_every_tenth_lags_minus_loop_us="e_sq_every_tenth_lags")),
 )
 row = ROWS[args.which]
 for k, v in row["defaults"].items():
@@ -147,6 +174,8 @@ def loop(steps, every=0, host=False, key=None, skip=0, **variant):
                     twin.add(x)
     if key:
         tables[key] = twin.table() if host else getattr(mdl, f"md_{args.which}_table")()
+        if host and hasattr(twin, "smax"):   # (sq: what its bound takes)
+            tables[key]["smax"] = twin.smax
     return (time.perf_counter() - t0) / (done - timed_from)
 
 
@@ -169,7 +198,10 @@ same = None
 if all(h in tables for _, h in row["equal"]):
     for p in row.get("after", lambda a: [])(args):
         loop(p.pop("steps"), **p)
-    same = bool(all(np.array_equal(tables[d][k], tables[h][k]) for d, h in row["equal"] for k in row["keys"]))
+    if "compare" in row:
+        same = bool(all(row["compare"](tables[d], tables[h]) for d, h in row["equal"]))
+    else:
+        same = bool(all(np.array_equal(tables[d][k], tables[h][k]) for d, h in row["equal"] for k in row["keys"]))
 med = {k: float(np.median(v)) for k, v in times.items()}
 minus = {j: [round(b - a, 2) for a, b in zip(times["a_loop"], times[k])] for j, k in row.get("minus", {}).items()}
 if "minus_nested" in row:
