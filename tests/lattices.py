@@ -282,6 +282,21 @@ def walk_frames():
     return (numbers, pos, cell, pbc), frames
 
 
+# ---------------------------------------------------------------------------- a cell thinner than the cut-off
+THIN = dict(cell=(2.9, 12.0, 13.0, 75.0, 80.0, 70.0), natoms=20, seed=9)
+
+
+def thin_frame():
+    """Twenty atoms of two species, at least 1.4 A apart, in a sheared cell whose first vector is 2.9 A long: the height along it
+    lies between 0.8 RC and RC (test_accumulator_geometry_cpu.py), so every atom's own images at +- that vector stand in its
+    list at RC."""
+    cell = cell_from(*THIN["cell"])
+    rng = np.random.default_rng(THIN["seed"])
+    n = THIN["natoms"]
+    numbers = np.array(SPECIES * (n // 2), np.int32)
+    return push_apart((numbers, rng.random((n, 3)) @ cell, cell, (True, True, True)), PHYS["dmin"])
+
+
 # ---------------------------------------------------------------------------- constructed edges
 # Each returns dict(frame=, rc=, marked=[((i, j, o0, o1, o2), listed)], ...): `marked` are the pairs the frame was built
 # for, with whether the list must hold them.

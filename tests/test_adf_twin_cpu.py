@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import pytest
 
+import accumulator_refs
 from autoforce_amd.transport import Adf, angle_distribution, coordination
 from autoforce_amd.workloads import ADF_MAXCOORD, AdfCounts, adf_cutoffs, adf_edges
 
@@ -119,57 +120,19 @@ def _random_frame():
     return numbers, [15, 16], cell, x, cut
 
 
-@functools.lru_cache(maxsize=None)
-def _brute_neighbours():
-    """Independent of the twin: the atoms wrapped into the cell, every image in a fixed block, a plain norm.  Per centre the list of
-    (d, r, slot); and the smallest gap between a distance and its cutoff."""
-    numbers, species, cell, x, cut = _random_frame()
-    slot = np.array([species.index(int(z)) for z in numbers])
-    ctab = adf_cutoffs(cut, species)
-    fr = x @ np.linalg.inv(cell)
-    xw = (fr - np.floor(fr)) @ cell
-    shifts = [s0 * cell[0] + s1 * cell[1] + s2 * cell[2] for s0 in range(-2, 3) for s1 in range(-2, 3) for s2 in range(-2, 3)]
-    out, gap_r = [], np.inf
-    for i in range(len(x)):
-        nb = []
-        for j in range(len(x)):
-            for sh in shifts:
-                if j == i and not sh.any():
-                    continue
-                d = xw[j] + sh - xw[i]
-                r = np.linalg.norm(d)
-                gap_r = min(gap_r, abs(r - ctab[slot[i], slot[j]]))
-                if r < ctab[slot[i], slot[j]]:
-                    nb.append((d, r, slot[j]))
-        out.append(nb)
-    return slot, out, gap_r
-
-
 def _brute(bins):
-    """arccos and floor on the brute-force neighbours: (H, C, the smallest gap between an angle and an edge in rad, the gap of the
-    distances, sum over centres of n_b (n_b - 1) / 2 or n_b n_c)."""
-    slot, nbs, gap_r = _brute_neighbours()
-    S = 2
-    H, C = np.zeros((S, S, S, bins), dtype=np.int64), np.zeros((S, S, ADF_MAXCOORD), dtype=np.int64)
-    gap_angle, nsum = np.inf, np.zeros((S, S, S), dtype=np.int64)
-    for i, nb in enumerate(nbs):
-        a = slot[i]
-        cnt = np.bincount([b for _, _, b in nb], minlength=S)
+    """Independent of the twin (accumulator_refs.adf: every image from the oracle's all-pairs list, a plain norm, arccos and
+    floor): (H, C, the smallest gap between an angle and an edge in rad, the gap of the distances to their cutoffs, sum over
+    centres of n_b (n_b - 1) / 2 or n_b n_c)."""
+    numbers, species, cell, x, cut = _random_frame()
+    t = accumulator_refs.adf((numbers, x, cell, (True, True, True)), species, adf_cutoffs(cut, species), bins)
+    S = len(species)
+    nsum = np.zeros((S, S, S), dtype=np.int64)
+    for a, cnt in zip(accumulator_refs._slots(numbers, species), t["per_centre"]):
         for b in range(S):
-            C[a, b, min(cnt[b], ADF_MAXCOORD - 1)] += 1
             for c in range(S):
                 nsum[a, b, c] += cnt[b] * (cnt[b] - 1) // 2 if b == c else cnt[b] * cnt[c]
-        for u in range(len(nb)):
-            for v in range(u + 1, len(nb)):
-                th = np.arccos(np.clip(np.dot(nb[u][0], nb[v][0]) / (nb[u][1] * nb[v][1]), -1.0, 1.0))
-                f = th / (np.pi / bins)
-                gap_angle = min(gap_angle, abs(f - np.rint(f)) * (np.pi / bins))
-                k = min(int(np.floor(f)), bins - 1)
-                b, c = sorted((nb[u][2], nb[v][2]))
-                H[a, b, c, k] += 1
-                if b != c:
-                    H[a, c, b, k] += 1
-    return H, C, gap_angle, gap_r, nsum
+    return t["angles"], t["coord"], t["gap_angle"], t["gap_r"], nsum
 
 
 @functools.lru_cache(maxsize=None)

@@ -8,6 +8,7 @@ And transport.q_vectors against a brute-force enumeration, and the readers on sy
 import numpy as np
 import pytest
 
+import accumulator_refs
 from autoforce_amd import transport
 from autoforce_amd.workloads import SqRing, sq_bounds, sq_vectors
 
@@ -49,26 +50,9 @@ def _hkl(seed=2, nq=41, hmax=16):
 
 
 def _direct(frames, hkl, every, lags, origin_every, numbers=NUMBERS, species=SPECIES, cell=CELL):
-    """The definition with nothing shared with the twin: exp(1j x . q) per atom, summed per species, every density of the run
-    kept, the correlations by plain loops over (sample, lag)."""
-    q = 2.0 * np.pi * np.asarray(hkl, float) @ np.linalg.inv(cell).T
-    rho = []
-    for n, x in enumerate(frames):
-        if n % every == 0:
-            ph = np.exp(1j * x @ q.T)   # [atom, nq]
-            rho.append(np.stack([ph[numbers == z].sum(axis=0) for z in species], axis=1))
-    S, nq = len(species), len(hkl)
-    f, mean, count = np.zeros((lags, nq, S, S)), np.zeros((nq, S), dtype=complex), np.zeros(lags, dtype=np.int64)
-    for s in range(len(rho)):
-        mean += rho[s]
-        for k in range(lags):
-            o = s - k
-            if o >= 0 and o % origin_every == 0:
-                count[k] += 1
-                for a in range(S):
-                    for b in range(S):
-                        f[k, :, a, b] += (rho[s][:, a] * np.conj(rho[o][:, b])).real
-    return dict(f=f, mean=mean, count=count, samples=len(rho), rho=rho)
+    """The definition with nothing shared with the twin (accumulator_refs.sq: exp(1j x . q) per atom, summed per species in
+    extended precision, every density of the run kept, the correlations by plain loops over (sample, lag))."""
+    return accumulator_refs.sq(frames, hkl, every, lags, origin_every, numbers, species, cell)
 
 
 def _twin(frames, hkl, every=1, lags=1, origin_every=1, numbers=NUMBERS, species=SPECIES, cell=CELL):
