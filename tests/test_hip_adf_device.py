@@ -7,16 +7,12 @@ that centres have no or one neighbour, all cutoffs at the model's rc (every list
 of its wave; and on a compressed frame more than 64 neighbours per centre: several passes of the gather),
 an exact cubic lattice whose right angles sit ON an edge, both counter forms, a covloss halt in the middle, a run that is not disturbed, the other accumulators beside it, what a later run
 and the handle's memory owe to it, every refusal in both directions, and ActiveCalculator.run_md(adf=) on the device against the
-host loop.  Frame and model are those of test_hip_rdf_device.py (LiPS, side 8: 192 / 64 / 256 atoms, cubic 21.76 A, m = 48,
-rc = 6)."""
-import ctypes as C
-import os
-import time
-
+host loop.  Frame, model, run loop and the bodies the six accumulators share: accumulator_device.py (cubic 21.76 A, rc = 6)."""
 import numpy as np
 import pytest
 
-from test_hip_rdf_device import _begin, _frame as _rdf_frame, _model, _noise, _shared
+import accumulator_device as A
+from accumulator_device import _begin, _shared
 
 pytestmark = pytest.mark.gpu
 
@@ -27,54 +23,20 @@ ADF = (1, 36, CUT)           # every, bins, cutoffs
 
 
 def _frame(kind=None):
-    """test_hip_rdf_device's frames (None, "sub200", "chunks", "thin"), and "dense": the module's frame compressed to 0.85 of its
+    """accumulator_device's frames (None, "sub200", "chunks", "thin"), and "dense": the module's frame compressed to 0.85 of its
     size, 73 neighbours within rc on average — no helper frame reaches 64 (the module's has 45)."""
     if kind != "dense":
-        return _rdf_frame(kind)
-    numbers, pos, cell, pbc, mass, vel = _rdf_frame(None)
+        return A._frame(kind)
+    numbers, pos, cell, pbc, mass, vel = A._frame(None)
     return numbers, 0.85 * pos, 0.85 * np.asarray(cell), pbc, mass, vel
 
 
-def _run(fr, adf, cuts=(24,), nh=False, record=True, seed=None, msd=None, rdf=None, vanhove=None, **kw):
-    """A run of sum(cuts) evaluations on the module's model with the accumulator `adf` = (every, bins, cutoffs) or None (and the
-    other accumulators beside it).  Returns (table or None, recorded positions or None, scalar rows, final state, dict of the
-    others' tables)."""
-    mdl = _shared()[0]
-    _begin(mdl, fr, nh=nh, **({} if seed is None else dict(seed=seed)), **kw)
-    if record:
-        mdl.md_record(1, velocities=False, results=False)
-    if msd is not None:
-        mdl.md_msd(*msd)
-    if rdf is not None:
-        mdl.md_rdf(*rdf)
-    if vanhove is not None:
-        mdl.md_vanhove(*vanhove)
-    if adf is not None:
-        mdl.md_adf(*adf)
-    noise = None if (nh or seed is not None) else _noise(fr, sum(cuts))
-    rows, xs, t = [], [], 0
-    for n in cuts:
-        done = 0
-        for _ in range(4):   # (halt code 2: a capacity was outgrown at evaluation `done`; the rows before it stand, the call is repeated)
-            t_call = time.perf_counter()
-            sc, code = mdl.md_run(n - done, None if noise is None else noise[t + done:t + n])
-            print(f"md_run({n - done}) on {len(fr[0])} atoms, accumulator {adf and adf[:2]}: code {code}, "
-                  f"{1e6 * (time.perf_counter() - t_call) / max(len(sc), 1):.1f} us per evaluation")
-            assert code in (0, 2) and (code == 2 or len(sc) == n - done), (code, len(sc), n, done)
-            rows.extend(sc)
-            if record and len(sc):
-                f = mdl.md_frames()
-                assert list(f["index"]) == list(range(t + done, t + done + len(sc)))
-                xs.append(f["positions"].copy())
-            done += len(sc)
-            if code == 0:
-                break
-        assert done == n, (done, n)
-        t += n
-    tab = None if adf is None else mdl.md_adf_table()
-    others = dict(msd=None if msd is None else mdl.md_msd_table(), rdf=None if rdf is None else mdl.md_rdf_table(),
-                  vanhove=None if vanhove is None else mdl.md_vanhove_table())
-    return tab, (np.concatenate(xs) if record else None), np.array(rows), mdl.md_state(), others
+def _run(fr, adf, cuts=(24,), **kw):
+    """accumulator_device.run with the accumulator `adf` = (every, bins, cutoffs) or None; a capacity the model outgrows halts a
+    call with the loop's overflow code, and the call is repeated.  Returns (table or None, recorded positions or None, scalar
+    rows, final state)."""
+    tabs, xs, rows, state = A.run(fr, *A.attached(adf=adf), cuts=cuts, overflow=True, label=f"accumulator {adf and adf[:2]}", **kw)
+    return tabs.get("adf"), xs, rows, state
 
 
 def _twin(fr, adf, xs):
@@ -99,9 +61,45 @@ def _same(tab, want, what=""):
         assert tab[k] == want[k], (what, k, tab[k], want[k])
 
 
+def _cut0():
+    from autoforce_amd.workloads import adf_cutoffs
+    return adf_cutoffs(CUT, _shared()[0].species)
+
+
+def _raw(h, every=1, bins=36, cut=None, ct=None):
+    from autoforce_amd._lib import ptr
+    from autoforce_amd.workloads import adf_edges
+    cut = np.ascontiguousarray(_cut0() if cut is None else cut, dtype=np.float64)
+    ct = np.ascontiguousarray(adf_edges(max(bins, 1)) if ct is None else ct, dtype=np.float64)
+    return A.lib().sgpr_md_adf(h, every, bins, ptr(cut), ptr(ct))
+
+
+def _invalid():
+    from autoforce_amd.workloads import adf_edges
+    asym, neg = _cut0(), _cut0()
+    asym[0, 2] += 0.1
+    neg[0, 1] = neg[1, 0] = -1.0
+    return [dict(every=-1), dict(bins=0), dict(bins=1025), dict(cut=asym), dict(cut=neg), dict(cut=np.zeros((3, 3))), dict(ct=adf_edges(36)[::-1])]
+
+
+def _limits(c):
+    assert c.raw(cut=np.full((3, 3), RC)) == 0 and c.raw(cut=np.full((3, 3), RC + 0.5)) == c.UNS
+    c.words(b"lies beyond the model's cutoff 6")
+    with pytest.raises(NotImplementedError, match="beyond the model's cutoff"):
+        c.mdl.md_adf(1, 36, {(15, 16): 6.5})
+    with pytest.raises(ValueError):
+        c.mdl.md_adf(1, 36)
+
+
+ACC = A.Acc(name="adf", noun=b"bond angles", moving_cell=b"the neighbours are read from the list of a constant cell", polymer=b"beads are",
+            raw=_raw, detach=lambda h: _raw(h, every=0), read=lambda h: A.lib().sgpr_md_adf_read(h, None, None, None),
+            py=lambda mdl: mdl.md_adf(1, 36, CUT), invalid=_invalid, limits=_limits,
+            port=29960, ports=30, run=_run, twin=lambda fr, adf, xs: _twin(fr, adf, xs).table(), same=_same)
+
+
 def test_one_call_and_a_cut_run_equal_the_twin():
     fr = _frame()
-    tab, xs, rows, _, _ = _run(fr, ADF)
+    tab, xs, rows, _ = _run(fr, ADF)
     want = _twin(fr, ADF, xs).table()
     assert want["samples"] == 24 and want["cut"][1, 1] == 0.0 and len(set(want["cut"][np.triu_indices(3)])) == 6
     S = 3
@@ -112,7 +110,7 @@ def test_one_call_and_a_cut_run_equal_the_twin():
     assert want["coord"][1, 1, 0] == 24 * want["n"][1]
     _same(tab, want, "one call")
     assert np.array_equal(tab["angles"], tab["angles"].transpose(0, 2, 1, 3))
-    tab2, xs2, rows2, _, _ = _run(fr, ADF, cuts=(7, 1, 12, 4))
+    tab2, xs2, rows2, _ = _run(fr, ADF, cuts=(7, 1, 12, 4))
     assert np.array_equal(xs2, xs) and np.array_equal(rows2, rows)
     _same(tab2, want, "cut 7 + 1 + 12 + 4")
 
@@ -123,7 +121,7 @@ def test_variants_equal_the_twin(variant):
     fr = _frame()
     adf = (3, 36, CUT) if variant == "every3" else ADF
     kw = dict(fixed=mask(len(fr[0]))) if variant == "held" else {}
-    tab, xs, _, _, _ = _run(fr, adf, cuts=(20,), nh=(variant == "nose-hoover"), **kw)
+    tab, xs, _, _ = _run(fr, adf, cuts=(20,), nh=(variant == "nose-hoover"), **kw)
     want = _twin(fr, adf, xs).table()
     if variant == "every3":
         assert want["samples"] == 7 and want["next_due"] == 21
@@ -137,7 +135,7 @@ def test_the_thin_cell_atoms_under_several_images():
     and -z), both in the list and both neighbours."""
     fr = _frame("thin")
     adf = (1, 36, 5.9)
-    tab, xs, _, _, _ = _run(fr, adf, cuts=(2, 2))
+    tab, xs, _, _ = _run(fr, adf, cuts=(2, 2))
     tw = _twin(fr, adf, xs)
     assert list(tw.R) == [0, 0, 1] and len(fr[0]) == 256
     twice = 0
@@ -160,7 +158,7 @@ def test_segments_off_a_chunk_over_many_chunks_and_lonely_centres(kind, cut):
     else:
         assert n.max() > 256 and np.any(n % 16 != 0)
     adf = (1, 36, cut)
-    tab, xs, _, _, _ = _run(fr, adf, cuts=(2, 3))
+    tab, xs, _, _ = _run(fr, adf, cuts=(2, 3))
     want = _twin(fr, adf, xs).table()
     assert np.array_equal(want["n"], n)
     if cut == 2.5:
@@ -180,7 +178,7 @@ def test_all_cutoffs_at_the_models_cutoff(kind):
     overflow code and the call is repeated (_run) — the configuration evaluated again counts once."""
     fr = _frame(kind)
     adf = (1, 30, RC)
-    tab, xs, _, _, _ = _run(fr, adf, cuts=(1, 2))
+    tab, xs, _, _ = _run(fr, adf, cuts=(1, 2))
     want = _twin(fr, adf, xs).table()
     total = want["coord"].sum(axis=(0, 1))   # (per-species counts; the neighbours of a centre are their sum over the species)
     print(f"frame {kind}: per-species coordination up to {int(np.flatnonzero(total).max())}, clamped {int(want['coord'][:, :, 63].sum())}")
@@ -237,60 +235,34 @@ def test_both_counter_forms(bins):
     global atomics.  The same frame and run, each equal to the twin."""
     fr = _frame()
     adf = (1, bins, CUT)
-    tab, xs, _, _, _ = _run(fr, adf, cuts=(3,))
+    tab, xs, _, _ = _run(fr, adf, cuts=(3,))
     _same(tab, _twin(fr, adf, xs).table(), f"{bins} bins")
 
 
 def test_a_covloss_halt_counts_every_configuration_once():
-    """The gate fires at evaluation k inside a call: k has been sampled (its halt is known one evaluation late), the speculative
-    evaluation k + 1 behind it must stay out, and the repeat of k — the model unchanged, resumed as device_loop.batches resumes:
-    one ungated evaluation, then on — must not count again."""
-    fr, evals = _frame(), 24
-    want, xs, rows, state, _ = _run(fr, ADF, cuts=(evals,), seed=77)
-    b = rows[:, 11]
-    ks = [k for k in range(2, evals - 2) if b[k] > b[:k].max()]
-    assert ks, "the covloss never exceeds its earlier values on this walk"
-    k = ks[0]
-    ediff = 0.5 * (b[:k].max() + b[k])
-    print(f"halt at evaluation {k} of {evals}: covloss {b[k]:.6e} over {b[:k].max():.6e}")
-    mdl = _shared()[0]
-    _begin(mdl, fr, seed=77)
-    mdl.md_adf(*ADF)
-    sc, code = mdl.md_run(evals, None, ediff=ediff)
-    assert code == 1 and len(sc) == k + 1, (code, len(sc), k)
-    mid = mdl.md_adf_table()
-    assert mid["next_due"] == k + 1 and mid["samples"] == k + 1
-    _same(mid, _twin(fr, ADF, xs[:k + 1]).table(), f"behind the halt at {k}")
-    sc1, code = mdl.md_run(1, None, ediff=0.0)
-    assert code == 0 and len(sc1) == 1 and mdl.md_adf_table()["next_due"] == k + 1
-    sc2, code = mdl.md_run(evals - k - 1, None, ediff=0.0)
-    assert code == 0 and np.array_equal(np.concatenate([sc[:k], sc1, sc2]), rows)
-    _same(mdl.md_adf_table(), want, f"halt at {k}")
-    _same(want, _twin(fr, ADF, xs).table(), "the run that never halted")
+    def halted(mid, k, xs):
+        assert mid["samples"] == k + 1
+        _same(mid, _twin(_frame(), ADF, xs[:k + 1]).table(), f"behind the halt at {k}")
+    A.halt_counts_once(ACC, ADF, halted)
 
 
 @pytest.mark.parametrize("nh", [False, True])
 def test_the_accumulator_moves_nothing(nh):
-    fr = _frame()
-    _, xs0, rows0, st0, _ = _run(fr, None, cuts=(9, 11), nh=nh)
-    tab, xs1, rows1, st1, _ = _run(fr, (2, 36, CUT), cuts=(9, 11), nh=nh)
-    print(f"nh {nh}: samples {tab['samples']}, E of the last row without / with {rows0[-1, 0]!r} / {rows1[-1, 0]!r}")
-    assert tab["samples"] == 10 and np.array_equal(rows0, rows1) and np.array_equal(xs0, xs1)
-    for key in ("positions", "velocities_pre"):
-        assert np.array_equal(st0[key], st1[key]), key
+    A.moves_nothing(ACC, nh, (2, 36, CUT), lambda tab: tab["samples"] == 10, record=True)
 
 
 def test_beside_the_other_accumulators_each_table_equals_the_one_taken_alone():
-    from test_hip_msd_device import KEYS
     fr = _frame()
-    adf, msd, rdf, vh = (3, 36, CUT), (2, 3, True), (4, 6.0, 60, 0.0), (2, 3, 3.0, 30, 2, 2, 6.0, 20)
-    both, _, rows, _, o = _run(fr, adf, cuts=(9, 11), msd=msd, rdf=rdf, vanhove=vh, record=False, seed=5)
-    alone, _, rows_a, _, _ = _run(fr, adf, cuts=(9, 11), record=False, seed=5)
-    _, _, rows_o, _, oa = _run(fr, None, cuts=(9, 11), msd=msd, rdf=rdf, vanhove=vh, record=False, seed=5)
+    adf, others = (3, 36, CUT), dict(msd=(2, 3, True), rdf=(4, 6.0, 60, 0.0), vanhove=(2, 3, 3.0, 30, 2, 2, 6.0, 20))
+    kw = dict(cuts=(9, 11), record=False, seed=5, overflow=True)
+    o, _, rows, _ = A.run(fr, *A.attached(**others, adf=adf), **kw)
+    alone, _, rows_a, _ = _run(fr, adf, cuts=(9, 11), record=False, seed=5)
+    oa, _, rows_o, _ = A.run(fr, *A.attached(**others), **kw)
+    both = o["adf"]
     assert np.array_equal(rows, rows_a) and np.array_equal(rows, rows_o)
     assert both["samples"] == 7 and both["next_due"] == 21 and o["msd"]["next_due"] == 20 and o["rdf"]["next_due"] == 20 and o["rdf"]["samples"] == 5
     _same(both, alone, "beside md_msd, md_rdf and md_vanhove")
-    for k in KEYS:
+    for k in ("count", "msd", "msd_sq", "smd", "smd_sq"):
         assert np.array_equal(o["msd"][k], oa["msd"][k]), k
     assert np.array_equal(o["rdf"]["hist"], oa["rdf"]["hist"])
     for k in ("self", "over", "distinct", "count"):
@@ -299,230 +271,52 @@ def test_beside_the_other_accumulators_each_table_equals_the_one_taken_alone():
 
 
 def test_a_later_run_starts_from_zeros_and_the_memory_owes_it_nothing():
-    """A second attach on the same handle zeroes the tables; a run begun behind an accumulator run is the run on a fresh handle;
-    md_adf_table refuses the plain run; a detach gives the tables back at once, md_end and close() every byte."""
-    from autoforce_amd import _lib
+    """accumulator_device.later_run_and_memory; a second attach on the same handle zeroes the tables; md_adf_table refuses the
+    plain run; a detach gives the tables back at once, md_end and close() every byte."""
     from test_hip_teardown import _live
-    fr = _frame()                     # (the module's own model is alive before the first reading)
-    before = _live()
-    mdl, _ = _model()
 
-    def R():
-        _begin(mdl, fr, seed=7)
-        out = [mdl.md_run(n, None, final=f) for n, f in ((2, False), (4, True))]
-        assert all(code == 0 for _, code in out)
-        return np.concatenate([sc for sc, _ in out]), mdl.md_state(results=True)
+    def accumulate(mdl, fr):
+        def attach_and_run():
+            _begin(mdl, fr, seed=7)
+            mdl.md_adf(*ADF)
+            t0 = mdl.md_adf_table()
+            assert not t0["angles"].any() and not t0["coord"].any() and t0["samples"] == 0
+            sc, code = mdl.md_run(6, None)
+            assert code == 0
+            return mdl.md_adf_table()
+        t1 = attach_and_run()
+        t2 = attach_and_run()
+        assert t1["samples"] == 6 and t1["angles"].sum() > 0
+        _same(t2, t1, "the second attach")
 
-    def A():
+    def detach(mdl, fr, first):
+        mdl.md_end()                      # (the tables go with the run)
         _begin(mdl, fr, seed=7)
+        held = _live()
+        mdl.md_adf(*ADF)                  # 192 / 64 / 256 atoms: 12 + 4 + 16 chunks of 16 centres
+        assert np.array_equal(_live() - held, [8 * 27 * 36 + 8 * 9 * 64 + 8 * (9 + 36) + 8 * 2 + 4 * (32 * 3 + 3), 5])
+        mdl.md_adf(0)                     # (a detach frees them)
+        assert np.array_equal(_live() - held, [0, 0])
+        with pytest.raises(RuntimeError, match="no accumulator"):
+            mdl.md_adf_table()
         mdl.md_adf(*ADF)
-        t0 = mdl.md_adf_table()
-        assert not t0["angles"].any() and not t0["coord"].any() and t0["samples"] == 0
-        sc, code = mdl.md_run(6, None)
-        assert code == 0
-        return mdl.md_adf_table()
-    first = R()
-    t1 = A()
-    t2 = A()
-    assert t1["samples"] == 6 and t1["angles"].sum() > 0
-    _same(t2, t1, "the second attach")
-    again = R()
-    assert np.array_equal(first[0], again[0])
-    for key in ("positions", "velocities_pre", "velocities", "forces", "beta", "energy", "stress"):
-        assert np.array_equal(np.asarray(first[1][key]), np.asarray(again[1][key])), key
-    assert _lib.load().sgpr_md_adf_read(mdl.handle, None, None, None) == _lib.E_INVALID
-    assert b"call sgpr_md_begin and sgpr_md_adf first" in _lib.load().sgpr_last_error()
-    mdl.md_end()                      # (the tables go with the run)
-    _begin(mdl, fr, seed=7)
-    held = _live()
-    mdl.md_adf(*ADF)                  # 192 / 64 / 256 atoms: 12 + 4 + 16 chunks of 16 centres
-    assert np.array_equal(_live() - held, [8 * 27 * 36 + 8 * 9 * 64 + 8 * (9 + 36) + 8 * 2 + 4 * (32 * 3 + 3), 5])
-    mdl.md_adf(0)                     # (a detach frees them)
-    assert np.array_equal(_live() - held, [0, 0])
-    with pytest.raises(RuntimeError, match="no accumulator"):
-        mdl.md_adf_table()
-    mdl.md_adf(*ADF)
-    mdl.md_end()                      # (and so does the end of the run)
-    mdl.close()
-    assert np.array_equal(_live() - before, [0, 0])
+    A.later_run_and_memory(ACC, accumulate, detach)
 
 
 def test_refusals_in_both_directions_leave_the_handle_working():
-    from autoforce_amd import _lib
-    from autoforce_amd.ase_shim import kB
-    from autoforce_amd.npt import GPA
-    from autoforce_amd.workloads import FS, adf_cutoffs, adf_edges
-    from test_hip_msd_device import T
-    from test_hip_neb_device import _band
-    from test_hip_pimd_device import _begin as _begin_pimd, _polymer
-    mdl, lib = _shared()[0], _lib.load()
-    fr = _frame()
-    numbers, pos, cell, pbc, mass, vel = fr
-    h, N = mdl.handle, len(numbers)
-    e0 = float(mdl.predict(numbers, pos, cell, pbc)["energy"])
-    _, _, rows, _, _ = _run(fr, None, cuts=(4,), record=False, seed=77)
-    UNS, INV = _lib.E_UNSUPPORTED, _lib.E_INVALID
-    cut0 = adf_cutoffs(CUT, mdl.species)
-
-    def adf(every=1, bins=36, cut=cut0, ct=None):
-        cut = np.ascontiguousarray(cut, dtype=np.float64)
-        ct = np.ascontiguousarray(adf_edges(max(bins, 1)) if ct is None else ct, dtype=np.float64)
-        return lib.sgpr_md_adf(h, every, bins, _lib.ptr(cut), _lib.ptr(ct))
-
-    def words(w):
-        assert w in lib.sgpr_last_error(), lib.sgpr_last_error()
-    mdl.md_end()
-    assert adf() == INV and lib.sgpr_md_adf_read(h, None, None, None) == INV            # no run
-    _begin(mdl, fr, seed=77)
-    asym, neg = cut0.copy(), cut0.copy()
-    asym[0, 2] += 0.1
-    neg[0, 1] = neg[1, 0] = -1.0
-    for args in (dict(every=-1), dict(bins=0), dict(bins=1025), dict(cut=asym), dict(cut=neg), dict(cut=np.zeros((3, 3))),
-                 dict(ct=adf_edges(36)[::-1])):
-        assert adf(**args) == INV, args
-    assert lib.sgpr_md_adf_read(h, None, None, None) == INV                             # a run without the accumulator
-    assert adf(cut=np.full((3, 3), RC)) == 0 and adf(cut=np.full((3, 3), RC + 0.5)) == UNS
-    words(b"lies beyond the model's cutoff 6")
-    with pytest.raises(NotImplementedError, match="beyond the model's cutoff"):
-        mdl.md_adf(1, 36, {(15, 16): 6.5})
-    with pytest.raises(ValueError):
-        mdl.md_adf(1, 36)
-    # a barostat
-    ext = np.array([-GPA] * 3 + [0.0] * 3)
-    baro = lambda: lib.sgpr_md_barostat(h, (100.0 * FS) ** 2 * 30.0 * GPA, _lib.ptr(ext), None, 1.0)
-    _begin(mdl, fr, nh=True)
-    assert adf() == 0 and baro() == UNS
-    words(b"sgpr_md_barostat: the run accumulates bond angles")
-    _begin(mdl, fr, nh=True)
-    assert baro() == 0 and adf() == UNS
-    words(b"sgpr_md_adf: the run has a barostat")
-    # a relaxation
-    _begin(mdl, fr)
-    assert adf() == 0 and lib.sgpr_md_relax(h, 0.05, None, 0, None) == UNS
-    words(b"sgpr_md_relax: the run accumulates bond angles")
-    _begin(mdl, fr)
-    assert lib.sgpr_md_relax(h, 0.05, None, 0, None) == 0 and adf() == UNS
-    words(b"sgpr_md_adf: the run is a relaxation")
-    # a band
-    band = np.ascontiguousarray(_band(pos, 1))
-    _begin(mdl, fr)
-    assert adf() == 0 and lib.sgpr_md_neb(h, 1, _lib.ptr(band[1:2]), 0.05, 0.1, 0, None) == UNS
-    words(b"sgpr_md_neb: the run accumulates bond angles")
-    mdl.neb_begin(numbers, band, cell, pbc, 0.05)
-    assert adf() == UNS
-    words(b"sgpr_md_adf: the run is a nudged elastic band")
-    # a polymer
-    _, beads, bvel, _ = _polymer(numbers, pos, 2)
-    _begin(mdl, fr)
-    assert adf() == 0 and lib.sgpr_md_pimd(h, 2, _lib.ptr(np.ascontiguousarray(beads)), _lib.ptr(np.ascontiguousarray(bvel)), kB * T, 0.001, 1.0) == UNS
-    words(b"sgpr_md_pimd: the run accumulates bond angles")
-    _begin_pimd(mdl, numbers, beads, bvel, mass, cell, pbc, seed=7)
-    assert adf() == UNS
-    words(b"sgpr_md_adf: the run is a ring polymer")
-    # a committee
-    member, _ = _model(seed=2)
-    arr = (C.c_void_p * 1)(member.handle.value)
-    _begin(mdl, fr)
-    assert adf() == 0 and lib.sgpr_md_committee(h, 1, arr) == UNS
-    words(b"sgpr_md_committee: the run accumulates bond angles")
-    _begin(mdl, fr)
-    assert lib.sgpr_md_committee(h, 1, arr) == 0 and adf() == UNS
-    words(b"sgpr_md_adf: the run has a committee")
-    with pytest.raises(NotImplementedError, match="committee"):
-        mdl.md_adf(1, 36, CUT)
-    mdl.md_end()
-    member.close()
-    # a run that has started; a detach is always taken
-    _begin(mdl, fr, seed=77)
-    sc, code = mdl.md_run(2, None)
-    assert code == 0 and adf() == INV
-    words(b"sgpr_md_adf: the run has started")
-    assert adf(every=0) == 0
-    # the handle works: the energy it predicted, the plain run it ran
-    assert float(mdl.predict(numbers, pos, cell, pbc)["energy"]) == e0
-    _, _, again, _, _ = _run(fr, None, cuts=(4,), record=False, seed=77)
-    assert np.array_equal(again, rows)
-
-
-def _two_rank_worker(rank, world, port, q):
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [root, os.path.join(root, "tests")]
-    import torch.distributed as dist
-    from autoforce_amd import _lib
-    from autoforce_amd.watchdog import Watchdog
-    from autoforce_amd.workloads import adf_edges
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["SGPR_PEER_TIMEOUT_MS"] = "20000"   # (the processes share the one GPU of the test box)
-    with Watchdog(f"bond angles on two ranks, rank {rank} of {world}", seconds=240, rank=rank):
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        mdl, (numbers, pos, cell, pbc) = _model()
-        N = len(numbers)
-        blobs = [None] * world
-        dist.all_gather_object(blobs, mdl.peer_export(rank, world, 7 * N + 11))
-        mdl.peer_attach(blobs)
-        dist.barrier()
-        e0 = float(mdl.predict(numbers, pos, cell, pbc, rank=rank, world=world)["energy"])
-        mdl.md_begin(numbers, pos, cell, pbc, np.ones(N), None, dt=1.0, friction=0.0, kT=0.0)
-        cut, ct = np.full((3, 3), 3.0), np.ascontiguousarray(adf_edges(36))
-        code = _lib.load().sgpr_md_adf(mdl.handle, 1, 36, _lib.ptr(cut), _lib.ptr(ct))
-        e1 = float(mdl.predict(numbers, pos, cell, pbc, rank=rank, world=world)["energy"])
-        q.put((rank, code, e0, e1))
-        dist.barrier()
-        mdl.peer_destroy()
-        dist.destroy_process_group()
+    A.refusals(ACC)
 
 
 def test_a_run_begun_on_two_ranks_refuses_the_accumulator_and_goes_on_working():
-    """Bond angles are accumulated on one rank (test_hip_rdf_device.py's two-rank refusal, for sgpr_md_adf)."""
-    import torch.multiprocessing as mp
-    from autoforce_amd import _lib
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29960 + (os.getpid() % 30)
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = sorted(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, code, e0, e1 in got:
-        assert code == _lib.E_UNSUPPORTED and e0 == e1
-    assert got[0][2] == got[1][2]
+    A.two_rank_refusal(ACC, cut=np.full((3, 3), 3.0))
 
 
 def test_run_md_fills_equal_tables_on_the_device_and_through_the_host_loop(tmp_path):
-    """ActiveCalculator.run_md(adf=holder) with a teacher — the gate fires, calculate() updates the model, the run goes on — on
-    the device (the accumulator inside the loop) and through the host loop (AdfCounts fed every step's positions): the same
-    trajectory (rng= given), so the same integers."""
-    import active_common as ac
-    from autoforce_amd import SGPRModel
-    from autoforce_amd.ase_shim import Atoms
-    from autoforce_amd.calculator import ActiveCalculator
+    """accumulator_device.run_md_host_and_device with run_md(adf=holder), the host loop's AdfCounts fed every step's positions:
+    the same integers."""
     from autoforce_amd.transport import Adf, angle_distribution, coordination
-    from helpers import PairTeacher
-    steps, tabs, upd = 40, [], []
-    for mode in ("host", "device"):
-        np.random.seed(1234)
-        rng0, numbers, pos, cell = ac.start(0)
-        d = tmp_path / mode
-        d.mkdir()
-        calc = ActiveCalculator(engine=SGPRModel(3, 3, 4, 4.5, species=ac.SPECIES), calculator=PairTeacher(rc=4.0),
-                                logfile=str(d / "active.log"), pckl=None, tape=None, **ac.KW)
-        if mode == "host":
-            calc.md_on_device_ok = lambda: False
-        at = Atoms(numbers, pos, cell, True, velocities=0.02 * np.random.default_rng(3).normal(size=pos.shape))
-        holder = Adf(2, 45, 3.6)
-        out = list(calc.run_md(at, steps, 300.0, dt_fs=1.0, friction=0.02, rng=np.random.default_rng(9), chunk=16, adf=holder))
-        assert len(out) == steps + 1
-        upd.append([o[0] for o in out if o[3]])
-        tabs.append(holder.table())
-        calc.engine.close()
-    print(f"updates at steps {upd}, samples {tabs[0]['samples']}, angles host {int(tabs[0]['angles'].sum())} device {int(tabs[1]['angles'].sum())}")
-    assert upd[0] == upd[1] and len(upd[0]) >= 1, upd        # (the device loop halted and went on)
+    tabs, holder, numbers = A.run_md_host_and_device(tmp_path, "adf", lambda cell: Adf(2, 45, 3.6))
+    print(f"samples {tabs[0]['samples']}, angles host {int(tabs[0]['angles'].sum())} device {int(tabs[1]['angles'].sum())}")
     assert tabs[0]["samples"] == 21 and tabs[0]["angles"].sum() > 0
     _same(tabs[1], tabs[0], "run_md")
     a, b, c = np.unravel_index(np.argmax(holder.angles.sum(axis=3)), holder.angles.shape[:3])

@@ -6,17 +6,13 @@ The device's sincospi is not numpy's sin and cos, so the two are held to the a-p
 of the SAME run's frame record at every = 1.  One call and a cut run, other settings and sets of wave vectors, held atoms,
 Nose-Hoover, device deviates, frames whose species segments end off a chunk and off a wave, a covloss halt in the middle with and
 without a model update, runs beside the record, the filter, a bias and the other five accumulators, every refusal in both
-directions, and ActiveCalculator.run_md(sq=) on the device against the host loop.  Frame and model are those of
-test_hip_msd_device.py (LiPS, side 8: 192 / 64 / 256 atoms)."""
-import ctypes as C
-import os
-import time
-
+directions, and ActiveCalculator.run_md(sq=) on the device against the host loop.  Frame, model, run loop and the bodies the six
+accumulators share: accumulator_device.py."""
 import numpy as np
 import pytest
 
-from test_hip_msd_device import EVALS, T, _begin, _frame, _noise, _shared
-from test_hip_npt_device import _model
+import accumulator_device as A
+from accumulator_device import EVALS, T, _begin, _frame, _shared
 
 pytestmark = pytest.mark.gpu
 
@@ -43,33 +39,22 @@ def _hkl(kind="mixed", cell=None):
     return np.concatenate([q_vectors(cell, 1.2), np.array(own)])
 
 
-def _run(fr, sq, cuts=(EVALS,), nh=False, record=True, seed=None, beside=None, **kw):
-    """A run of sum(cuts) evaluations on the module's model with the accumulator `sq` = (every, hkl, lags, origin_every) or None;
-    beside(mdl) attaches what runs beside it and returns a reader of its tables.  Returns (table or None, recorded positions or
-    None, scalar rows, final state, what the reader read)."""
-    mdl = _shared()[0]
-    _begin(mdl, fr, nh=nh, **({} if seed is None else dict(seed=seed)), **kw)
-    if record:
-        mdl.md_record(1, velocities=False, results=False)
-    reader = beside(mdl) if beside is not None else None
-    if sq is not None:
-        mdl.md_sq(*sq)
-    noise = None if (nh or seed is not None) else _noise(fr, sum(cuts))
-    rows, xs, t = [], [], 0
-    for n in cuts:
-        t_call = time.perf_counter()
-        sc, code = mdl.md_run(n, None if noise is None else noise[t:t + n])
-        print(f"md_run({n}) on {len(fr[0])} atoms, sq {None if sq is None else (sq[0], len(sq[1])) + tuple(sq[2:])}: "
-              f"{1e6 * (time.perf_counter() - t_call) / n:.1f} us per evaluation")
-        assert code == 0 and len(sc) == n, (code, len(sc), n)
-        rows.extend(sc)
-        if record:
-            f = mdl.md_frames()
-            assert list(f["index"]) == list(range(t, t + n))
-            xs.append(f["positions"].copy())
-        t += n
-    tab = None if sq is None else mdl.md_sq_table()
-    return tab, (np.concatenate(xs) if record else None), np.array(rows), mdl.md_state(), (reader() if reader else None)
+def _run(fr, sq, beside=None, **kw):
+    """accumulator_device.run with the accumulator `sq` = (every, hkl, lags, origin_every) or None; beside(mdl) attaches what runs
+    beside it, ahead of it, and returns a reader of its tables.  Returns (table or None, recorded positions or None, scalar rows,
+    final state, what the reader read)."""
+    reader = []
+
+    def attach(mdl):
+        if beside is not None:
+            reader.append(beside(mdl))
+        if sq is not None:
+            mdl.md_sq(*sq)
+
+    def read(mdl):
+        return (None if sq is None else mdl.md_sq_table()), (reader[0]() if reader else None)
+    (tab, other), xs, rows, state = A.run(fr, attach, read, label=f"sq {None if sq is None else (sq[0], len(sq[1])) + tuple(sq[2:])}", **kw)
+    return tab, xs, rows, state, other
 
 
 def _twin(fr, sq, xs):
@@ -155,7 +140,7 @@ def test_variants_lie_within_the_bound_of_the_twin(variant):
 
 
 def _off_grid(kind):
-    """test_hip_msd_device's "sub200" and "chunks", and "absent": sub200 without the atoms of its smallest species."""
+    """accumulator_device's "sub200" and "chunks", and "absent": sub200 without the atoms of its smallest species."""
     if kind != "absent":
         return _frame(kind)
     numbers, pos, cell, pbc, mass, vel = _frame("sub200")
@@ -193,12 +178,7 @@ def test_a_covloss_halt_counts_the_configuration_once():
     fr, evals = _frame(), 24
     sq = (1, _hkl(), 6, 1)
     want, xs, rows, _, _ = _run(fr, sq, cuts=(evals,), seed=77)
-    b = rows[:, 11]
-    ks = [k for k in range(2, evals - 2) if b[k] > b[:k].max()]
-    assert ks, "the covloss never exceeds its earlier values on this walk"
-    k = ks[0]
-    ediff = 0.5 * (b[:k].max() + b[k])
-    print(f"halt at evaluation {k} of {evals}: covloss {b[k]:.6e} over {b[:k].max():.6e}")
+    k, ediff = A.first_halt(rows, evals)
     mdl = _shared()[0]
     mu0, vs0 = np.array(mdl.mu, float), dict(mdl._vscale)   # (the update changes the weights alone and puts them back)
     for update in (False, True):
@@ -318,197 +298,61 @@ def test_a_detach_frees_and_a_fresh_attach_starts_from_zeros():
     mdl.md_end()
 
 
-def test_refusals_in_both_directions_leave_the_handle_working():
-    from autoforce_amd import _lib
-    from autoforce_amd.ase_shim import kB
-    from autoforce_amd.npt import GPA
-    from autoforce_amd.workloads import FS
-    from test_hip_neb_device import _band
-    from test_hip_pimd_device import _begin as _begin_pimd, _polymer
-    mdl, lib = _shared()[0], _lib.load()
-    fr = _frame()
-    numbers, pos, cell, pbc, mass, vel = fr
-    h = mdl.handle
-    e0 = float(mdl.predict(numbers, pos, cell, pbc)["energy"])
-    _, _, rows, _, _ = _run(fr, None, cuts=(4,), record=False, seed=77)
-    UNS, INV = _lib.E_UNSUPPORTED, _lib.E_INVALID
-    good = np.ascontiguousarray([[1, 0, 0], [0, -2, 3]], dtype=np.int32)
+GOOD = np.ascontiguousarray([[1, 0, 0], [0, -2, 3]], dtype=np.int32)
 
-    def sq(every=1, hkl=good, lags=4, origin_every=1, nq=None):
-        return lib.sgpr_md_sq(h, every, len(hkl) if nq is None else nq, None if hkl is None else _lib.ptr(np.ascontiguousarray(hkl, dtype=np.int32)),
+
+def _raw(h, every=1, hkl=GOOD, lags=4, origin_every=1, nq=None):
+    from autoforce_amd._lib import ptr
+    return A.lib().sgpr_md_sq(h, every, len(hkl) if nq is None else nq, None if hkl is None else ptr(np.ascontiguousarray(hkl, dtype=np.int32)),
                               lags, origin_every)
 
-    def words(w):
-        assert w in lib.sgpr_last_error(), lib.sgpr_last_error()
-    mdl.md_end()
-    assert sq() == INV and lib.sgpr_md_sq_read(h, None, None, None, None) == INV           # no run
-    _begin(mdl, fr, seed=77)
-    assert lib.sgpr_md_sq_read(h, None, None, None, None) == INV                            # a run without the accumulator
-    words(b"call sgpr_md_begin and sgpr_md_sq first")
-    # each bad argument — SGPR_E_INVALID, ahead of the mode refusals (a relaxation stands on the handle for the second pass)
-    big = np.ones((8193, 3), dtype=np.int32)
-    bad = [dict(every=-1), dict(nq=0), dict(hkl=big), dict(hkl=None, nq=2), dict(hkl=[[1, 0, 0], [0, 0, 0]]), dict(hkl=[[33, 0, 0]]),
-           dict(hkl=[[0, -33, 1]]), dict(lags=0), dict(lags=8193), dict(origin_every=0)]
-    for relax in (False, True):
-        _begin(mdl, fr, seed=77)
-        if relax:
-            assert lib.sgpr_md_relax(h, 0.05, None, 0, None) == 0
-        for kw in bad:
-            assert sq(**kw) == INV, kw
-        assert sq() == (UNS if relax else 0)
-    words(b"sgpr_md_sq: the run is a relaxation")
-    mdl.md_begin(numbers, pos, cell, (True, True, False), mass, vel, dt=1.0 * FS, kT=kB * T, friction=0.05)
-    assert sq(hkl=[[1, 0, 1]]) == INV
-    words(b"not periodic")
-    assert sq(hkl=[[1, -1, 0]]) == 0
-    # a table over the byte limit
-    _begin(mdl, fr, seed=77)
-    assert sq(hkl=np.ones((8192, 3), dtype=np.int32), lags=8192) == UNS
-    words(b"at most 1073741824")
-    # a barostat
-    ext = np.array([-GPA] * 3 + [0.0] * 3)
-    baro = lambda: lib.sgpr_md_barostat(h, (100.0 * FS) ** 2 * 30.0 * GPA, _lib.ptr(ext), None, 1.0)
-    _begin(mdl, fr, nh=True)
-    assert sq() == 0 and baro() == UNS
-    words(b"sgpr_md_barostat: the run accumulates structure factors")
-    _begin(mdl, fr, nh=True)
-    assert baro() == 0 and sq() == UNS
-    words(b"sgpr_md_sq: the run has a barostat; the wave vectors are the reciprocal lattice of a constant cell")
-    # a relaxation
-    _begin(mdl, fr)
-    assert sq() == 0 and lib.sgpr_md_relax(h, 0.05, None, 0, None) == UNS
-    words(b"sgpr_md_relax: the run accumulates structure factors")
-    # a band
-    band = np.ascontiguousarray(_band(pos, 1))
-    _begin(mdl, fr)
-    assert sq() == 0 and lib.sgpr_md_neb(h, 1, _lib.ptr(band[1:2]), 0.05, 0.1, 0, None) == UNS
-    words(b"sgpr_md_neb: the run accumulates structure factors")
-    mdl.neb_begin(numbers, band, cell, pbc, 0.05)
-    assert sq() == UNS
-    words(b"sgpr_md_sq: the run is a nudged elastic band")
-    # a polymer
-    _, beads, bvel, _ = _polymer(numbers, pos, 2)
-    _begin(mdl, fr)
-    assert sq() == 0 and lib.sgpr_md_pimd(h, 2, _lib.ptr(np.ascontiguousarray(beads)), _lib.ptr(np.ascontiguousarray(bvel)), kB * T, 0.001, 1.0) == UNS
-    words(b"sgpr_md_pimd: the run accumulates structure factors")
-    _begin_pimd(mdl, numbers, beads, bvel, mass, cell, pbc, seed=7)
-    assert sq() == UNS
-    words(b"sgpr_md_sq: the run is a ring polymer (sgpr_md_pimd); its beads are not sampled")
-    # a committee
-    member, _ = _model(seed=2)
-    arr = (C.c_void_p * 1)(member.handle.value)
-    _begin(mdl, fr)
-    assert sq() == 0 and lib.sgpr_md_committee(h, 1, arr) == UNS
-    words(b"sgpr_md_committee: the run accumulates structure factors")
-    _begin(mdl, fr)
-    assert lib.sgpr_md_committee(h, 1, arr) == 0 and sq() == UNS
-    words(b"sgpr_md_sq: the run has a committee")
-    with pytest.raises(NotImplementedError, match="committee"):
-        mdl.md_sq(1, good)
-    mdl.md_end()
-    member.close()
-    # a run that has started; a detach is always taken, frees, and leaves the handle working
-    _begin(mdl, fr, seed=77)
-    assert sq() == 0
-    sc, code = mdl.md_run(2, None)
-    assert code == 0 and sq() == INV
-    words(b"sgpr_md_sq: the run has started")
-    assert lib.sgpr_md_sq(h, 0, 0, None, 0, 0) == 0 and lib.sgpr_md_sq_read(h, None, None, None, None) == INV
-    sc, code = mdl.md_run(2, None)
-    assert code == 0
-    assert float(mdl.predict(numbers, pos, cell, pbc)["energy"]) == e0
-    _, _, again, _, _ = _run(fr, None, cuts=(4,), record=False, seed=77)
-    assert np.array_equal(again, rows)
+
+def _limits(c):
+    """A wave vector with a component along a direction that is not periodic; a table over the byte limit."""
+    from autoforce_amd.ase_shim import kB
+    from autoforce_amd.workloads import FS
+    numbers, pos, cell, pbc, mass, vel = c.fr
+    c.mdl.md_begin(numbers, pos, cell, (True, True, False), mass, vel, dt=1.0 * FS, kT=kB * T, friction=0.05)
+    assert c.raw(hkl=[[1, 0, 1]]) == c.INV
+    c.words(b"not periodic")
+    assert c.raw(hkl=[[1, -1, 0]]) == 0
+    _begin(c.mdl, c.fr, seed=77)
+    assert c.raw(hkl=np.ones((8192, 3), dtype=np.int32), lags=8192) == c.UNS
+    c.words(b"at most 1073741824")
 
 
-def _two_rank_worker(rank, world, port, q):
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [root, os.path.join(root, "tests")]
-    import torch.distributed as dist
-    from autoforce_amd import _lib
-    from autoforce_amd.watchdog import Watchdog
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["SGPR_PEER_TIMEOUT_MS"] = "20000"   # (the processes share the one GPU of the test box)
-    with Watchdog(f"structure factors on two ranks, rank {rank} of {world}", seconds=240, rank=rank):
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        mdl, (numbers, pos, cell, pbc) = _model()
-        N = len(numbers)
-        blobs = [None] * world
-        dist.all_gather_object(blobs, mdl.peer_export(rank, world, 7 * N + 11))
-        mdl.peer_attach(blobs)
-        dist.barrier()
-        e0 = float(mdl.predict(numbers, pos, cell, pbc, rank=rank, world=world)["energy"])
-        mdl.md_begin(numbers, pos, cell, pbc, np.ones(N), None, dt=1.0, friction=0.0, kT=0.0)
-        hkl = np.ascontiguousarray([[1, 0, 0]], dtype=np.int32)
-        code = _lib.load().sgpr_md_sq(mdl.handle, 1, 1, _lib.ptr(hkl), 2, 1)
-        e1 = float(mdl.predict(numbers, pos, cell, pbc, rank=rank, world=world)["energy"])
-        q.put((rank, code, e0, e1))
-        dist.barrier()
-        mdl.peer_destroy()
-        dist.destroy_process_group()
+ACC = A.Acc(name="sq", noun=b"structure factors", moving_cell=b"the wave vectors are the reciprocal lattice of a constant cell", polymer=b"beads are",
+            raw=_raw, detach=lambda h: A.lib().sgpr_md_sq(h, 0, 0, None, 0, 0), read=lambda h: A.lib().sgpr_md_sq_read(h, None, None, None, None),
+            py=lambda mdl: mdl.md_sq(1, GOOD), limits=_limits,
+            invalid=[dict(every=-1), dict(nq=0), dict(hkl=np.ones((8193, 3), dtype=np.int32)), dict(hkl=None, nq=2), dict(hkl=[[1, 0, 0], [0, 0, 0]]),
+                     dict(hkl=[[33, 0, 0]]), dict(hkl=[[0, -33, 1]]), dict(lags=0), dict(lags=8193), dict(origin_every=0)],
+            port=29920)
+
+
+def test_refusals_in_both_directions_leave_the_handle_working():
+    A.refusals(ACC)
 
 
 def test_a_run_begun_on_two_ranks_refuses_the_accumulator_and_goes_on_working():
-    """Structure factors are accumulated on one rank (test_hip_msd_device.py's two-rank refusal, for sgpr_md_sq)."""
     import torch
-    import torch.multiprocessing as mp
-    from autoforce_amd import _lib
     if torch.cuda.device_count() < 2:
         pytest.skip("two ranks need two devices")
-    world = 2
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = 29920 + (os.getpid() % 40)
-    procs = [ctx.Process(target=_two_rank_worker, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = sorted(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, code, e0, e1 in got:
-        assert code == _lib.E_UNSUPPORTED and e0 == e1
-    assert got[0][2] == got[1][2]
+    A.two_rank_refusal(ACC)
 
 
 def test_run_md_fills_tables_on_the_device_and_through_the_host_loop_that_agree_within_the_bound(tmp_path):
-    """ActiveCalculator.run_md(sq=holder) with a teacher — the gate fires, calculate() updates the model, the run goes on — on
-    the device (the accumulator inside the loop) and through the host loop (SqRing fed every step's positions): the same
-    trajectory (rng= given), so the same integers and tables within the bound."""
-    import active_common as ac
-    from autoforce_amd import SGPRModel
-    from autoforce_amd.ase_shim import Atoms
-    from autoforce_amd.calculator import ActiveCalculator
+    """accumulator_device.run_md_host_and_device with run_md(sq=holder), the host loop's SqRing fed every step's positions: the
+    same integers and tables within the bound."""
     from autoforce_amd.transport import Sq, intermediate_scattering, q_vectors, structure_factor
-    from helpers import PairTeacher
-    steps, tabs, upd, smax = 40, [], [], 0.0
-    for mode in ("host", "device"):
-        np.random.seed(1234)
-        rng0, numbers, pos, cell = ac.start(0)
-        d = tmp_path / mode
-        d.mkdir()
-        calc = ActiveCalculator(engine=SGPRModel(3, 3, 4, 4.5, species=ac.SPECIES), calculator=PairTeacher(rc=4.0),
-                                logfile=str(d / "active.log"), pckl=None, tape=None, **ac.KW)
-        if mode == "host":
-            calc.md_on_device_ok = lambda: False
-        at = Atoms(numbers, pos, cell, True, velocities=0.02 * np.random.default_rng(3).normal(size=pos.shape))
-        hkl = q_vectors(cell, 2.0)
-        holder = Sq(2, hkl, lags=5, origin_every=2)
-        out = []
-        for o in calc.run_md(at, steps, 300.0, dt_fs=1.0, friction=0.02, rng=np.random.default_rng(9), chunk=16, sq=holder):
-            out.append(o)
-            if mode == "host" and o[0] % holder.every == 0:   # (the host loop sets atoms.positions before every yield: the sample the twin was fed)
-                smax = max(smax, float(np.abs(np.asarray(at.positions) @ np.linalg.inv(np.asarray(cell, float).reshape(3, 3))).max()))
-        assert len(out) == steps + 1
-        upd.append([o[0] for o in out if o[3]])
-        tabs.append(holder.table())
-        calc.engine.close()
-    print(f"updates at steps {upd}, counts {list(tabs[0]['count'])}, nq {len(hkl)}")
-    assert upd[0] == upd[1] and len(upd[0]) >= 1, upd        # (the device loop halted and went on)
+    smax = [0.0]
+
+    def seen(mode, o, at, cell, holder):
+        if mode == "host" and o[0] % holder.every == 0:   # (the host loop sets atoms.positions before every yield: the sample the twin was fed)
+            smax[0] = max(smax[0], float(np.abs(np.asarray(at.positions) @ np.linalg.inv(np.asarray(cell, float).reshape(3, 3))).max()))
+    tabs, holder, numbers = A.run_md_host_and_device(tmp_path, "sq", lambda cell: Sq(2, q_vectors(cell, 2.0), lags=5, origin_every=2), seen)
+    print(f"counts {list(tabs[0]['count'])}, nq {len(tabs[0]['hkl'])}")
     assert list(tabs[0]["count"]) == [11, 10, 10, 9, 9] and tabs[0]["samples"] == 21
-    _within(tabs[1], tabs[0], smax, "run_md on the device against the host loop")
+    _within(tabs[1], tabs[0], smax[0], "run_md on the device against the host loop")
     q, S = structure_factor(holder)
     present = np.flatnonzero(np.asarray(holder.n) > 0)
     assert np.all(np.isfinite(S[:, present][:, :, present])) and np.all(S[:, present, present] > 0.0)
